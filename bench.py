@@ -20,6 +20,13 @@ The fp32 3x3 layers run as Winograd F(2x2,3x3) (16 multiplies per 2x2 tile and c
 operand split exactly into three bf16 pieces (six bf16 MFMA products per fp32 product, fp32 accumulate): `frac` is against
 the bf16 MFMA peak that pipe has; the algorithmic (direct-convolution) rate and the fp32-equivalent rate are reported next
 to it and never as `frac`.  `gat` is the graph kernel's record (HBM bound), at the headline batch and at 64 graphs.
+
+`--dump-outputs DIR` writes what the LAST of the K timed steps returned (rank 0) as DIR/<name>.npy, float32 (float64 where the
+step returns float64): infer mode the forward's logits, skips_<i>, decoder_feats_<i> and node_embeddings; train mode the loss
+and the flat parameter and gradient buffers after that step.  An array of more than DUMP_FULL_MAX elements is written as
+DUMP_SAMPLE elements at fixed positions (seeded by the array's name; flat index order of the array as the caller sees it), so
+that the files stay under DUMP_MAX_BYTES in all.  The inputs and weights depend only on the arguments: two builds run with the
+same arguments can be compared file for file.
 """
 import argparse
 import ctypes as C
@@ -28,6 +35,7 @@ import os
 import statistics
 import sys
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 for _p in (os.path.join(ROOT, "mingraph-unet_amd"), os.path.join(ROOT, "oracle")):
@@ -41,6 +49,36 @@ PEAK_BF16_MFMA_TFLOPS = 2500.0  # same guide: bf16 MFMA dense (never the 2:1-spa
 PEAK_HBM_TBS = 8.0              # same guide: HBM3E spec peak (6.3 TB/s achievable by a streaming copy)
 ARITH_3PIECE = "3xbf16 split (fp32 operands split exactly into 3 bf16 pieces, 6 bf16 MFMA products per fp32 product), fp32 accumulate"
 PIPE = {0: ("fp32 MFMA (v_mfma_f32_32x32x2_f32)", PEAK_F32_MFMA_TFLOPS), 1: ("bf16 MFMA (v_mfma_f32_32x32x16_bf16)", PEAK_BF16_MFMA_TFLOPS)}
+DUMP_MAX_BYTES = 64 << 20    # --dump-outputs: all files together
+DUMP_FULL_MAX = 4 << 20      # arrays up to this many elements are written whole ...
+DUMP_SAMPLE = 1 << 20        # ... larger ones as this many elements at seeded positions
+
+
+def dump_arrays(named):
+    """Host copies of the step's outputs for --dump-outputs: [(name, tensor or number)] -> {name: float32/float64 ndarray}.
+    Arrays above DUMP_FULL_MAX elements are sampled at DUMP_SAMPLE sorted positions drawn without replacement from a generator
+    seeded by the name (the same positions for the same name and shape on every run and build)."""
+    import numpy as np
+    out = {}
+    for name, t in named:
+        t = torch.as_tensor(t).detach()
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        if t.numel() > DUMP_FULL_MAX:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(t.numel(), DUMP_SAMPLE, replace=False))
+            pos = tuple(torch.from_numpy(np.ascontiguousarray(c)).to(t.device) for c in np.unravel_index(idx, tuple(t.shape)))
+            t = t[pos]          # advanced indexing of the caller's (possibly strided) view: no full copy
+        out[name] = t.to(dt).cpu().numpy()
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes exceed {DUMP_MAX_BYTES}"
+    return out
+
+
+def write_dump(d, arrays):
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    print(f"bench.py: wrote {len(arrays)} arrays ({sum(a.nbytes for a in arrays.values()) / 2**20:.1f} MiB) to {d}", file=sys.stderr)
 
 
 def host_cores():
@@ -332,6 +370,8 @@ def bench_train(a, world, rank, local_rank, dev, dist):
         loss = tr.train_step(x, y)
     barrier()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:   # before the profile pass below steps the parameters further
+        write_dump(a.dump_outputs, dump_arrays([("loss", loss), ("parameters", tr.flat), ("gradient", tr.grad)]))
     assert bool(torch.isfinite(loss).all())
     tr.check()
     dt = max_over_ranks(dt, dist, dev)
@@ -417,7 +457,12 @@ def main():
     ap.add_argument("--sustained-seconds", type=float, default=2.0,
                     help="length of the one long window reported as `sustained` (0 = off); `value` stays the K timed steps")
     ap.add_argument("--spread-windows", type=int, default=4, help="extra timed windows of --steps steps for the min/median/max record")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32/float64, large arrays sampled at "
+                         "seeded positions, at most 64 MiB in all)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -504,6 +549,10 @@ def main():
         ev1.record()
         barrier()
         dt = time.perf_counter() - t0
+        if a.dump_outputs and rank == 0:   # the last timed step's outputs, before the windows below recompute them
+            lg, sk, ft, emb = out
+            write_dump(a.dump_outputs, dump_arrays([("logits", lg)] + [(f"skips_{i}", t) for i, t in enumerate(sk)] +
+                                                   [(f"decoder_feats_{i}", t) for i, t in enumerate(ft)] + [("node_embeddings", emb)]))
         # spread: further windows of the same K steps (local clock; the headline `value` stays the first, barrier-bracketed window)
         windows = [dt / a.steps * 1e3]
         for _ in range(max(0, a.spread_windows)):

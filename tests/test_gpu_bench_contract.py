@@ -41,6 +41,26 @@ def test_train_line(cuda):
     assert 0.0 < j["final_loss"] < 10.0
 
 
+def test_dump_outputs_of_the_last_timed_step(cuda, tmp_path):
+    """--dump-outputs: the forward's outputs as float32 .npy files under 64 MiB in all, and the same bytes from a run of one timed
+    step and from the last of three (the inputs depend only on the workload arguments; the forward is deterministic)."""
+    import numpy as np
+    quiet = ("--gpus", "1", "--no-cpu-baseline", "--no-profile-pass", "--sustained-seconds", "0", "--spread-windows", "0")
+    j1 = run_bench(*quiet, "--steps", "1", "--warmup", "0", "--dump-outputs", str(tmp_path / "a"))
+    j3 = run_bench(*quiet, "--steps", "3", "--warmup", "2", "--dump-outputs", str(tmp_path / "b"))
+    assert j1["steps"] == 1 and j3["steps"] == 3
+    names = {"logits", "node_embeddings"} | {f"{k}_{i}" for k in ("skips", "decoder_feats") for i in range(4)}
+    files = {p.stem for p in (tmp_path / "a").iterdir()}
+    assert files == names == {p.stem for p in (tmp_path / "b").iterdir()}
+    a = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    b = {n: np.load(tmp_path / "b" / (n + ".npy")) for n in names}
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["logits"].shape == (8, 2, 512, 512) and a["node_embeddings"].shape == (8 * 1024, 64)
+    for n in names:
+        assert a[n].dtype == np.float32 and np.isfinite(a[n]).all(), n
+        assert np.array_equal(a[n], b[n]), n
+
+
 def test_plain_run_carries_cpu_baseline_and_other_configs(cuda):
     """What the driver runs at round end (no extra flags): the headline line plus the CPU baseline and the bf16 / train-step side measurements."""
     j = run_bench("--steps", "3", "--warmup", "1", "--sustained-seconds", "0")
