@@ -380,6 +380,28 @@ int mgu_elliptical_shape_loss_masks(mgu_ctx* ctx, const uint8_t* masks_dev, int 
 int mgu_elliptical_shape_loss_probs(mgu_ctx* ctx, const void* probs_dev, int B, int num_classes, int H, int W, int64_t ps_n, int64_t ps_c,
                                     int64_t ps_p, float epsilon, float* loss_dev, void* hip_stream);
 
+/* ---- segmentation evaluation: replaces the scoring loop of experiments/segmentation_performance.py:125-151 (forward -> argmax ->
+ *      .view(-1).cpu() of predictions and masks -> experiments/metrics.py:6-69 segmentation_metrics, whose sklearn confusion matrix
+ *      is the only data it needs) and the validation loss scripts/train_segmentation.py:145-151 leaves commented out ---------------
+ * ONE read of logits (B,H,W,C) NHWC fp32 -- what mgu_unet_forward writes -- and int64 labels (B, HW): per pixel the first maximal
+ * class (bit-identical to mgu_argmax_classes; = torch.argmax, :141, on finite input, ties included) and confusion_dev[y][pred] += 1
+ * when 0 <= y < C -- sklearn's confusion_matrix(labels=range(C)) (metrics.py:21), which drops any other label.  confusion_dev: int64
+ * (C, C), ACCUMULATED with integer atomics (exact, order-free: a whole test set adds up without a host synchronisation).
+ * pred_dev: int64 (B, HW) predictions, NULL = not written.  loss_kind 0: counts only (no exp / log); 1: nn.CrossEntropyLoss()
+ * (mean, ignore_index -100; an out-of-range label as mgu_cross_entropy: NaN loss + the ctx's data-error word); 2: that + dice_loss
+ * (train_segmentation.py:29-40, smoothing dice_smooth; any label outside [0, C) flagged as mgu_dice_loss does; num_classes <= 8).
+ * With a loss, loss_acc_dev (double[2]) is ACCUMULATED: [0] += (double)batch_loss (fp32 CE [+ fp32 dice], summed in fp32: :130),
+ * [1] += 1 -- the reference's val_loss += loss.item() and its batch count; the partials are added in a fixed order (bitwise
+ * reproducible).  mgu_loss_sync_check reports a flagged label.  loss_acc_dev must be NULL iff loss_kind == 0. */
+int mgu_segmentation_eval(mgu_ctx* ctx, const void* logits_dev, const int64_t* labels_dev, int B, int64_t HW, int num_classes,
+                          int64_t* confusion_dev, int64_t* pred_dev, int loss_kind, float dice_smooth, double* loss_acc_dev,
+                          void* hip_stream);
+/* Confusion counts of given predictions (segmentation_metrics takes two label tensors, metrics.py:6): confusion_dev[t][p] += 1 for
+ * every i with t = true_dev[i], p = pred_dev[i] both in [0, num_classes); other pairs are dropped, as sklearn drops them.  int64
+ * (num_classes, num_classes), accumulated. */
+int mgu_confusion_matrix(mgu_ctx* ctx, const int64_t* true_dev, const int64_t* pred_dev, int64_t n, int num_classes,
+                         int64_t* confusion_dev, void* hip_stream);
+
 /* ---- resize / gather building blocks of FeatureFusion (model/fusion_detection/feature_fusion.py:43-162) ----------------------------
  * F.interpolate(mode='bilinear', align_corners=False) (:69-76, :140-144) of an NHWC fp32 map (B,Hi,Wi,C) with pixel pitch ld_in into
  * channels [c_off, c_off + C) of a (B,Ho,Wo,ld_out) buffer -- i.e. straight into its slice of the fused tensor. */
