@@ -423,6 +423,26 @@ int mgu_preprocess_image_u8(mgu_ctx* ctx, const uint8_t* img_dev, int Hs, int Ws
 /* preprocess_mask (:87-126): cv2.resize(INTER_NEAREST) (source index floor(dst * src/dst), clamped), np.clip to [0, num_classes-1], int64. */
 int mgu_preprocess_mask_u8(mgu_ctx* ctx, const uint8_t* mask_dev, int Hs, int Ws, int H, int W, int num_classes, int64_t* out_dev,
                            void* hip_stream);
+/* ---- training augmentation (image_preprocess.py:34-51): RandomHorizontalFlip then RandomRotation of the resized PIL image ------------
+ * The flip and the rotation (PIL's img.rotate(angle, NEAREST, expand=False, fillcolor=0) through its 16.16 fixed-point affine path) of
+ * one image are described by the flag `flip` and six int32 coefficients fix = {a0..a5} (mgunet.preprocess.pil_rotation_fixed): output
+ * pixel (x, y) reads source pixel (xin, yin) = ((a2 + y a1 + x a0) >> 16, (a5 + y a4 + x a3) >> 16) -- column W-1-xin under flip -- when it
+ * lies inside the image, else the fill.  H, W <= 8192 (above that PIL uses a float64 path that is not reproduced: MGU_ERR_INVALID).
+ * Batch form: images (B, C, H, W) fp32, element (b, c, y, x) at [b*s[0] + c*s[1] + y*s[2] + x*s[3]] for in_strides / out_strides (HOST
+ * arrays of 4; NCHW, channels-last or a slot of a bigger batch), out of place; fill_c: HOST array of C <= 16 floats (the fill per
+ * channel, e.g. (0 - mean) / std); masks: optional int64 (B, H, W) contiguous (both null or both set), fill mask_fill; params_dev:
+ * DEVICE int32 (B, 7) rows {flip, a0, a1, a2, a3, a4, a5}.  One launch for images and masks. */
+int mgu_augment_flip_rotate(mgu_ctx* ctx, const float* img_in, float* img_out, int B, int C, int H, int W, const int64_t* in_strides,
+                            const int64_t* out_strides, const float* fill_c, const int64_t* mask_in, int64_t* mask_out, int64_t mask_fill,
+                            const int32_t* params_dev, void* hip_stream);
+/* mgu_preprocess_image_u8 with the flip / rotation applied to the resized image (fix6: HOST array of 6); out-of-image pixels are the
+ * normalised black (0/255 - mean) / std.  Same launches as mgu_preprocess_image_u8. */
+int mgu_preprocess_image_u8_aug(mgu_ctx* ctx, const uint8_t* img_dev, int Hs, int Ws, int channels, int bgr, int H, int W, const float* mean3,
+                                const float* std3, void* out_dev, int64_t os_c, int64_t os_h, int64_t os_w, int flip, const int32_t* fix6,
+                                void* hip_stream);
+/* mgu_preprocess_mask_u8 followed by the flip / rotation of the (H, W) label map; out-of-image pixels get mask_fill (not clipped). */
+int mgu_preprocess_mask_u8_aug(mgu_ctx* ctx, const uint8_t* mask_dev, int Hs, int Ws, int H, int W, int num_classes, int flip, const int32_t* fix6,
+                               int64_t mask_fill, int64_t* out_dev, void* hip_stream);
 /* EdgeDetector.sobel_edges (preprocessing/graph_feature_processing/edge_detection.py:14-44), kernel size 3: RGB -> grey (14-bit fixed
  * point), Sobel x / y with reflect-101 borders, magnitude / max * 255 in double, truncated to uint8.  rgb (H,W,3) -> out (H,W). */
 int mgu_sobel_edges_u8(mgu_ctx* ctx, const uint8_t* rgb_dev, int H, int W, uint8_t* out_dev, void* hip_stream);

@@ -305,13 +305,13 @@ int mgu_resize_bilinear_nhwc(mgu_ctx* c, const void* in_dev, int ld_in, int B, i
   return MGU_OK;
 }
 
-int mgu_preprocess_image_u8(mgu_ctx* c, const uint8_t* img_dev, int Hs, int Ws, int channels, int bgr, int H, int W, const float* mean3,
-                            const float* std3, void* out_dev, int64_t os_c, int64_t os_h, int64_t os_w, void* hip_stream) {
-  if (!c) return MGU_ERR_INVALID;
-  if (!img_dev || !out_dev || !mean3 || !std3 || Hs < 1 || Ws < 1 || H < 1 || W < 1 || (channels != 1 && channels != 3))
-    return fail(c, MGU_ERR_INVALID, "bad preprocess_image args (1 or 3 channels)");
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = (hipStream_t)hip_stream;
+}  // extern "C"
+
+namespace mgu {
+// The resize half of mgu_preprocess_image_u8 (also used by mgu_preprocess_image_u8_aug, augment.hip): PIL's BILINEAR resample of the
+// (Hs, Ws, channels) uint8 image to (H, W) on stream s; *out is the (H, W, channels) uint8 result -- the context's image workspace, or
+// img_dev itself when no resize is needed.
+int preprocess_resize_u8(mgu_ctx* c, const uint8_t* img_dev, int Hs, int Ws, int channels, int H, int W, hipStream_t s, const uint8_t** out) {
   const bool need_h = W != Ws, need_v = H != Hs;
   const ResampleTable th = need_h ? pil_bilinear_coeffs(Ws, W) : ResampleTable(), tv = need_v ? pil_bilinear_coeffs(Hs, H) : ResampleTable();
   // scratch: [tables (int)] [horizontal result Hs x W x C] [final H x W x C]
@@ -346,6 +346,23 @@ int mgu_preprocess_image_u8(mgu_ctx* c, const uint8_t* img_dev, int Hs, int Ws, 
                        (int64_t)curW * channels, (int64_t)channels, (int64_t)curW * channels, (int64_t)channels, tb, tb + tv.bounds.size(), tv.ksize);
     cur = fin;
   }
+  *out = cur;
+  return MGU_OK;
+}
+}  // namespace mgu
+
+extern "C" {
+
+int mgu_preprocess_image_u8(mgu_ctx* c, const uint8_t* img_dev, int Hs, int Ws, int channels, int bgr, int H, int W, const float* mean3,
+                            const float* std3, void* out_dev, int64_t os_c, int64_t os_h, int64_t os_w, void* hip_stream) {
+  if (!c) return MGU_ERR_INVALID;
+  if (!img_dev || !out_dev || !mean3 || !std3 || Hs < 1 || Ws < 1 || H < 1 || W < 1 || (channels != 1 && channels != 3))
+    return fail(c, MGU_ERR_INVALID, "bad preprocess_image args (1 or 3 channels)");
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)hip_stream;
+  const uint8_t* cur = nullptr;
+  int rc = preprocess_resize_u8(c, img_dev, Hs, Ws, channels, H, W, s, &cur);
+  if (rc) return rc;
   hipLaunchKernelGGL(to_tensor_normalize_kernel, dim3(nb((int64_t)H * W * 3)), dim3(256), 0, s, cur, H, W, channels, bgr, mean3[0], mean3[1],
                      mean3[2], std3[0], std3[1], std3[2], (float*)out_dev, os_c, os_h, os_w);
   HIPCHK(c, hipGetLastError());

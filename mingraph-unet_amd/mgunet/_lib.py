@@ -155,6 +155,14 @@ _PROTOS = {
     "mgu_preprocess_image_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float),
                                           C.POINTER(C.c_float), C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
     "mgu_preprocess_mask_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "mgu_augment_flip_rotate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64),
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                          C.c_void_p]),
+    "mgu_preprocess_image_u8_aug": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                              C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int,
+                                              C.POINTER(C.c_int32), C.c_void_p]),
+    "mgu_preprocess_mask_u8_aug": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.POINTER(C.c_int32), C.c_int64, C.c_void_p, C.c_void_p]),
     "mgu_sobel_edges_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "mgu_equalize_hist_rgb_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "mgu_patch_mean_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

@@ -9,11 +9,16 @@
 Same class names, constructor arguments and method names.  The reference works on host numpy arrays with cv2 / PIL; here the
 pixels go to the device once (uint8) and every step is a HIP kernel that reproduces the library's integer arithmetic exactly.
 Methods accept a numpy array (returned type: what the reference returns) or a uint8 CUDA tensor (returned: CUDA tensors, no host
-round trip).  File paths are decoded with PIL (RGB order): cv2 is not a dependency of this package.  The random augmentations of
-ImagePreprocessor (flip / rotation through torchvision's RNG) are not reproduced: apply_augmentation=True raises."""
+round trip).  File paths are decoded with PIL (RGB order): cv2 is not a dependency of this package.
+
+ImagePreprocessor(apply_augmentation=True) reproduces the reference's RandomHorizontalFlip(0.5) -> RandomRotation(15) bit for bit: the
+host makes torchvision's two draws from torch's generator (draw_flip_rotate) and the device applies PIL's fixed-point NEAREST rotation
+(pil_rotation_fixed) inside the ToTensor + Normalize pass.  preprocess_pair applies one draw to an image AND its mask (the reference
+augments only the image), and RandomFlipRotate augments a whole device batch in one launch."""
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -43,38 +48,111 @@ def _to_dev_u8(a):
     raise TypeError("Input must be an image path (str) or a NumPy array.")
 
 
+_MAX_SIDE = 8192   # PIL rotates larger images through a float64 path that is not reproduced
+
+
+def pil_rotation_fixed(angle: float, w: int, h: int) -> tuple:
+    """The int32 coefficients (a0..a5) PIL's NEAREST affine path (affine_fixed in libImaging/Geometry.c) uses for
+    Image.rotate(angle, expand=False, center=None) of a w x h image: output pixel (x, y) reads source pixel
+    ((a2 + y a1 + x a0) >> 16, (a5 + y a4 + x a3) >> 16), or the fill colour when that lies outside the image.  The matrix is built as
+    Image.rotate builds it (angle % 360, -radians, cos / sin rounded to 15 digits, centre (w/2, h/2)), then FIX(v) = floor(v 65536 + 0.5)
+    with the half-pixel centre folded into a2 / a5.  Sides above 8192 raise: PIL would switch to its float64 path."""
+    w, h = int(w), int(h)
+    if not (1 <= w <= _MAX_SIDE and 1 <= h <= _MAX_SIDE):
+        raise ValueError(f"rotation of a {w} x {h} image: sides must be in [1, {_MAX_SIDE}] (PIL's fixed-point path)")
+    cx, cy = w / 2.0, h / 2.0
+    r = -math.radians(float(angle) % 360.0)
+    m0, m1, m3, m4 = round(math.cos(r), 15), round(math.sin(r), 15), round(-math.sin(r), 15), round(math.cos(r), 15)
+    m2 = m0 * -cx + m1 * -cy + 0.0 + cx
+    m5 = m3 * -cx + m4 * -cy + 0.0 + cy
+
+    def fix(v):
+        return int(math.floor(v * 65536.0 + 0.5))
+
+    return fix(m0), fix(m1), fix(m2 + m0 * 0.5 + m1 * 0.5), fix(m3), fix(m4), fix(m5 + m3 * 0.5 + m4 * 0.5)
+
+
+def draw_flip_rotate(p: float = 0.5, degrees: float = 15, generator: torch.Generator = None) -> tuple:
+    """One image's draws of RandomHorizontalFlip(p) -> RandomRotation(degrees), in torchvision's order and with its calls:
+    flip = torch.rand(1) < p (RandomHorizontalFlip.forward), then angle = float(torch.empty(1).uniform_(-degrees, degrees).item())
+    (RandomRotation.get_params); both are drawn for every image.  generator=None draws from torch's global CPU generator, as the
+    reference does, and leaves it where those two calls leave it.  -> (bool, float).
+    The order and the calls follow torchvision's transforms.py as documented for 0.8 and later (RandomRotation's fill=0 default
+    since 0.12 does not change the draws); it has not yet been run side by side with an installed torchvision."""
+    d = float(degrees)
+    if d < 0:
+        raise ValueError("If degrees is a single number, it must be positive.")   # torchvision's _setup_angle
+    flip = bool(torch.rand(1, generator=generator) < p)
+    angle = float(torch.empty(1).uniform_(-d, d, generator=generator).item())
+    return flip, angle
+
+
+def _load_image(image_path_or_array):
+    """-> (device uint8 (H, W, 1 | 3), bgr flag)"""
+    bgr = 1                                   # arrays are BGR, as cv2.imread delivers them (:76-78)
+    if isinstance(image_path_or_array, str):
+        from PIL import Image
+        try:
+            image = np.asarray(Image.open(image_path_or_array).convert("RGB"))
+        except FileNotFoundError:
+            raise FileNotFoundError(f"Image not found at {image_path_or_array}")
+        bgr = 0
+    else:
+        image = image_path_or_array
+    img, _ = _to_dev_u8(image)
+    if img.dim() == 2:
+        img = img.unsqueeze(-1)               # grey -> three equal channels (:79-80)
+    if img.dim() != 3 or img.shape[2] not in (1, 3):
+        raise ValueError("expected an (H, W, 3) or (H, W) uint8 image")
+    return img, bgr
+
+
+def _load_mask(mask_path_or_array):
+    if isinstance(mask_path_or_array, str):
+        from PIL import Image
+        try:
+            mask = np.asarray(Image.open(mask_path_or_array).convert("L"))
+        except FileNotFoundError:
+            raise FileNotFoundError(f"Mask not found at {mask_path_or_array}")
+    else:
+        mask = mask_path_or_array
+        if isinstance(mask, np.ndarray) and mask.ndim == 3:
+            mask = mask.squeeze(2) if mask.shape[2] == 1 else np.argmax(mask, axis=2).astype(np.uint8)   # :108-114
+    m, _ = _to_dev_u8(mask)
+    if m.dim() != 2:
+        raise ValueError("expected an (H, W) mask")
+    return m
+
+
 class ImagePreprocessor:
     def __init__(self, resize_dim=(128, 128), mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), apply_augmentation=False):
         self.resize_dim = resize_dim  # H, W
         self.mean, self.std = mean, std
         self.apply_augmentation = apply_augmentation
-        if apply_augmentation:
-            raise NotImplementedError("the random flip / rotation of image_preprocess.py:34-51 draws from torchvision's RNG and is not "
-                                      "reproduced; augment on the host or pass apply_augmentation=False")
+        # image_preprocess.py:44-51: RandomHorizontalFlip(p=0.5) -> RandomRotation(degrees=15) between Resize and ToTensor
+        self.flip_p, self.degrees = 0.5, 15
 
-    def preprocess(self, image_path_or_array, out: torch.Tensor = None):
-        """-> (3, H, W) float32 CUDA tensor (or fills `out`, any (3, H, W) view -- e.g. one image of an NHWC batch)."""
-        bgr = 1                                   # arrays are BGR, as cv2.imread delivers them (:76-78)
-        if isinstance(image_path_or_array, str):
-            from PIL import Image
-            try:
-                image = np.asarray(Image.open(image_path_or_array).convert("RGB"))
-            except FileNotFoundError:
-                raise FileNotFoundError(f"Image not found at {image_path_or_array}")
-            bgr = 0
-        else:
-            image = image_path_or_array
-        img, _ = _to_dev_u8(image)
-        if img.dim() == 2:
-            img = img.unsqueeze(-1)               # grey -> three equal channels (:79-80)
-        if img.dim() != 3 or img.shape[2] not in (1, 3):
-            raise ValueError("expected an (H, W, 3) or (H, W) uint8 image")
+    def _draw(self, augment, generator=None):
+        if augment is not None:
+            return bool(augment[0]), float(augment[1])
+        return draw_flip_rotate(self.flip_p, self.degrees, generator)
+
+    def preprocess(self, image_path_or_array, out: torch.Tensor = None, augment=None):
+        """-> (3, H, W) float32 CUDA tensor (or fills `out`, any (3, H, W) view -- e.g. one image of an NHWC batch).
+        With apply_augmentation the flip / rotation draws come from torch's global generator exactly as the reference's transforms
+        make them; augment=(flip, angle) gives them explicitly instead."""
+        if augment is not None and not self.apply_augmentation:
+            raise ValueError("augment=(flip, angle) needs apply_augmentation=True")
+        img, bgr = _load_image(image_path_or_array)
         Hs, Ws, ch = img.shape
         H, W = int(self.resize_dim[0]), int(self.resize_dim[1])
         if out is None:
             out = torch.empty((3, H, W), device=img.device, dtype=torch.float32)
         elif tuple(out.shape) != (3, H, W) or out.dtype != torch.float32 or out.device != img.device:
             raise ValueError("`out` must be a float32 (3, H, W) view on the image's device")
+        if self.apply_augmentation:
+            flip, angle = self._draw(augment)
+            return self._image_aug(img, bgr, out, flip, angle)
         mean, std = (C.c_float * 3)(*self.mean), (C.c_float * 3)(*self.std)
         ctx = _context(img.device)
         with torch.cuda.device(img.device):
@@ -83,20 +161,21 @@ class ImagePreprocessor:
         _lib.check(rc, ctx.handle)
         return out
 
+    def _image_aug(self, img, bgr, out, flip, angle):
+        Hs, Ws, ch = img.shape
+        H, W = int(self.resize_dim[0]), int(self.resize_dim[1])
+        fix = (C.c_int32 * 6)(*pil_rotation_fixed(angle, W, H))
+        mean, std = (C.c_float * 3)(*self.mean), (C.c_float * 3)(*self.std)
+        ctx = _context(img.device)
+        with torch.cuda.device(img.device):
+            rc = _lib.lib().mgu_preprocess_image_u8_aug(ctx.handle, img.data_ptr(), Hs, Ws, ch, bgr, H, W, mean, std, out.data_ptr(),
+                                                        out.stride(0), out.stride(1), out.stride(2), int(flip), fix,
+                                                        _lib.current_stream_ptr(img.device))
+        _lib.check(rc, ctx.handle)
+        return out
+
     def preprocess_mask(self, mask_path_or_array, num_classes):
-        if isinstance(mask_path_or_array, str):
-            from PIL import Image
-            try:
-                mask = np.asarray(Image.open(mask_path_or_array).convert("L"))
-            except FileNotFoundError:
-                raise FileNotFoundError(f"Mask not found at {mask_path_or_array}")
-        else:
-            mask = mask_path_or_array
-            if isinstance(mask, np.ndarray) and mask.ndim == 3:
-                mask = mask.squeeze(2) if mask.shape[2] == 1 else np.argmax(mask, axis=2).astype(np.uint8)   # :108-114
-        m, _ = _to_dev_u8(mask)
-        if m.dim() != 2:
-            raise ValueError("expected an (H, W) mask")
+        m = _load_mask(mask_path_or_array)
         H, W = int(self.resize_dim[0]), int(self.resize_dim[1])
         out = torch.empty((H, W), device=m.device, dtype=torch.int64)
         ctx = _context(m.device)
@@ -105,6 +184,87 @@ class ImagePreprocessor:
                                                    _lib.current_stream_ptr(m.device))
         _lib.check(rc, ctx.handle)
         return out
+
+    def preprocess_pair(self, image, mask, num_classes, mask_fill=0, generator=None, out: torch.Tensor = None, augment=None):
+        """preprocess(image) and preprocess_mask(mask, num_classes) under ONE flip / rotation draw -> ((3, H, W) float32, (H, W) int64).
+        The reference's MangoDataset.__getitem__ (utils/mango_dataset.py:58-62) augments the image through `preprocess` but calls
+        `preprocess_mask` unaugmented, so with apply_augmentation=True its images and masks no longer line up; here both get the same
+        flip and rotation.  Rotated-in mask pixels get mask_fill (-100: ignored by the Trainer's cross entropy).  Draws come from
+        `generator` (None: torch's global generator), or augment=(flip, angle); without apply_augmentation neither is transformed."""
+        if not self.apply_augmentation:
+            if augment is not None:
+                raise ValueError("augment=(flip, angle) needs apply_augmentation=True")
+            return self.preprocess(image, out=out), self.preprocess_mask(mask, num_classes)
+        flip, angle = self._draw(augment, generator)
+        img, bgr = _load_image(image)
+        m = _load_mask(mask)
+        H, W = int(self.resize_dim[0]), int(self.resize_dim[1])
+        if out is None:
+            out = torch.empty((3, H, W), device=img.device, dtype=torch.float32)
+        elif tuple(out.shape) != (3, H, W) or out.dtype != torch.float32 or out.device != img.device:
+            raise ValueError("`out` must be a float32 (3, H, W) view on the image's device")
+        self._image_aug(img, bgr, out, flip, angle)
+        mout = torch.empty((H, W), device=m.device, dtype=torch.int64)
+        fix = (C.c_int32 * 6)(*pil_rotation_fixed(angle, W, H))
+        ctx = _context(m.device)
+        with torch.cuda.device(m.device):
+            rc = _lib.lib().mgu_preprocess_mask_u8_aug(ctx.handle, m.data_ptr(), m.shape[0], m.shape[1], H, W, int(num_classes), int(flip), fix,
+                                                       int(mask_fill), mout.data_ptr(), _lib.current_stream_ptr(m.device))
+        _lib.check(rc, ctx.handle)
+        return out, mout
+
+
+class RandomFlipRotate:
+    """RandomHorizontalFlip(p) -> RandomRotation(degrees) (NEAREST, fill black) of a normalised fp32 batch on the device, one launch for
+    the images and their masks.  Per image the draws are those of draw_flip_rotate, in batch order, so images[i] comes out bitwise as
+    ImagePreprocessor(apply_augmentation=True).preprocess_pair would have made it from the same draws.  Rotated-in pixels get
+    `fill` (default: the normalised black (0 - mean) / std in float32) and mask_fill (-100: ignored by the Trainer's cross entropy)."""
+
+    def __init__(self, p=0.5, degrees=15, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), mask_fill=0, fill=None):
+        if float(degrees) < 0:
+            raise ValueError("If degrees is a single number, it must be positive.")
+        self.p, self.degrees, self.mask_fill = p, degrees, int(mask_fill)
+        if fill is None:
+            fill = (np.float32(0) / np.float32(255) - np.asarray(mean, np.float32)) / np.asarray(std, np.float32)
+        self.fill = tuple(float(v) for v in np.asarray(fill, np.float32).reshape(-1))
+
+    def draw(self, B: int, W: int, H: int, generator=None) -> torch.Tensor:
+        """-> (B, 7) int32 host table of {flip, a0..a5}, two draws per image in batch order."""
+        rows = []
+        for _ in range(B):
+            flip, angle = draw_flip_rotate(self.p, self.degrees, generator)
+            rows.append((int(flip),) + pil_rotation_fixed(angle, W, H))
+        return torch.tensor(rows, dtype=torch.int32).reshape(B, 7)
+
+    def __call__(self, images: torch.Tensor, masks: torch.Tensor = None, generator=None, out: torch.Tensor = None):
+        """images: (B, C, H, W) float32 on the device, any strides; masks: optional (B, H, W) int64.  -> augmented images (a new tensor
+        with the layout of `images`, or `out`) and, with masks, (images, masks)."""
+        if not images.is_cuda or images.dtype != torch.float32 or images.dim() != 4:
+            raise TypeError("images must be a (B, C, H, W) float32 tensor on the HIP device")
+        B, Cc, H, W = images.shape
+        if Cc != len(self.fill):
+            raise ValueError(f"{Cc} channels but {len(self.fill)} fill values (mean / std)")
+        dev = images.device
+        if masks is not None:
+            if masks.dtype != torch.int64 or masks.device != dev or tuple(masks.shape) != (B, H, W):
+                raise ValueError("masks must be a (B, H, W) int64 tensor on the images' device")
+            masks = masks.contiguous()
+        if out is None:
+            out = torch.empty_like(images)
+        elif tuple(out.shape) != (B, Cc, H, W) or out.dtype != torch.float32 or out.device != dev:
+            raise ValueError("`out` must be a float32 (B, C, H, W) tensor on the images' device")
+        params = self.draw(B, W, H, generator).to(dev)
+        mout = torch.empty((B, H, W), device=dev, dtype=torch.int64) if masks is not None else None
+        si, so = (C.c_int64 * 4)(*images.stride()), (C.c_int64 * 4)(*out.stride())
+        fill = (C.c_float * Cc)(*self.fill)
+        ctx = _context(dev)
+        with torch.cuda.device(dev):
+            rc = _lib.lib().mgu_augment_flip_rotate(ctx.handle, images.data_ptr(), out.data_ptr(), B, Cc, H, W, si, so, fill,
+                                                    masks.data_ptr() if masks is not None else None,
+                                                    mout.data_ptr() if mout is not None else None, self.mask_fill, params.data_ptr(),
+                                                    _lib.current_stream_ptr(dev))
+        _lib.check(rc, ctx.handle)
+        return (out, mout) if masks is not None else out
 
 
 def _rgb_op(fn_name, image_array_rgb, out_channels):
