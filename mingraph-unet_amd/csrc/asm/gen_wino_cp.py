@@ -19,23 +19,7 @@ W % 32 == 0, N % 64 == 0, Cp % 32 == 0, channel pitches and offsets % 4 == 0, sc
 
 Usage: gen_wino_cp.py OUT.s
 """
-import os
 import sys
-
-DEBUG = os.environ.get("GEN_WINO_DEBUG", "")
-# Options of the kernel being emitted (main() emits the shipping kernel and, with GEN_WINO_VARIANTS=1, timing-only variants):
-#   no_epilogue   timing only: no inverse transform / stores (accumulators cleared)
-#   no_valu       timing only: no input transform / split in the chunk loop (operand pieces stay constant)
-#   no_mfma       timing only: no MFMAs in the chunk loop
-#   no_barrier    timing only: no s_barrier in the chunk loop
-#   b1_step       step in front of which barrier B1 sits (2 or 3)
-#   valu_from     first MFMA gap of a step that carries transform work
-OPT = {}
-def opt(k, d=None): return OPT.get(k, d)
-def TT(i):
-    """cold-code temporary i (0 / 1): raw half 1's last registers; in the ping-pong experiment (whole raw set in flight across chunk tops)
-    the unused second operand-piece slot"""
-    return (198 + i) if OPT.get("pingpong") else (230 + i)
 
 # ---------------------------------------------------------------------------------------------------------------------
 # register map
@@ -58,7 +42,7 @@ VHST = [246, 247, 248]
 VHOFF = [249, 250, 251]
 VLANE16 = 252
 VTID = 253
-VT0, VT1 = 230, 231   # temporaries of the cold code (halo-offset setup, epilogue addressing, debug stores): the last two registers of raw half 1,
+VT0, VT1 = 230, 231   # temporaries of the cold code (halo-offset setup, epilogue addressing): the last two registers of raw half 1,
                       # free at every point those run (narrow kernels: see emit_epilogue_n, which keeps its own temporaries clear of them)
 def VMASK(): return 254 if CFG["ntb"] == 2 else 172   # 0xffff0000 in a VGPR and the wave's transform sign (+-1.0) in a VGPR: with all-VGPR VOP2
 def VSGN(): return 255 if CFG["ntb"] == 2 else 173    # forms (v_fmac / v_add / v_sub / v_and) two waves of a SIMD issue the transform + split at
@@ -172,33 +156,33 @@ def setup_load():
     L(lvalu)
     for i in range(3):
         d = VHOFF[i]
-        E(f"v_lshrrev_b32_e32 v{TT(0)}, 2, v{VTID}")
+        E(f"v_lshrrev_b32_e32 v{VT0}, 2, v{VTID}")
         if i:
-            E(f"v_add_u32_e32 v{TT(0)}, {128 * i}, v{TT(0)}")                    # hp
-        E(f"v_mul_u32_u24_e32 v{TT(1)}, 0x788, v{TT(0)}")
-        E(f"v_lshrrev_b32_e32 v{TT(1)}, 16, v{TT(1)}")                            # r = hp / 34
-        E(f"v_mul_u32_u24_e32 v{d}, 34, v{TT(1)}")
-        E(f"v_sub_u32_e32 v{d}, v{TT(0)}, v{d}")                                # cc
-        E(f"v_cmp_gt_u32_e32 vcc, 0x154, v{TT(0)}")                             # hp < 340
-        E(f"v_add_u32_e32 v{TT(1)}, s{S_T[6]}, v{TT(1)}")                         # y
+            E(f"v_add_u32_e32 v{VT0}, {128 * i}, v{VT0}")                    # hp
+        E(f"v_mul_u32_u24_e32 v{VT1}, 0x788, v{VT0}")
+        E(f"v_lshrrev_b32_e32 v{VT1}, 16, v{VT1}")                            # r = hp / 34
+        E(f"v_mul_u32_u24_e32 v{d}, 34, v{VT1}")
+        E(f"v_sub_u32_e32 v{d}, v{VT0}, v{d}")                                # cc
+        E(f"v_cmp_gt_u32_e32 vcc, 0x154, v{VT0}")                             # hp < 340
+        E(f"v_add_u32_e32 v{VT1}, s{S_T[6]}, v{VT1}")                         # y
         E(f"v_add_u32_e32 v{d}, s{S_T[7]}, v{d}")                             # x
-        E(f"v_cmp_gt_u32_e64 s[{S_M}:{S_M + 1}], s{S_H}, v{TT(1)}")
+        E(f"v_cmp_gt_u32_e64 s[{S_M}:{S_M + 1}], s{S_H}, v{VT1}")
         E(f"s_and_b64 vcc, vcc, s[{S_M}:{S_M + 1}]")
         E(f"v_cmp_gt_u32_e64 s[{S_M}:{S_M + 1}], s{S_W}, v{d}")
         E(f"s_and_b64 vcc, vcc, s[{S_M}:{S_M + 1}]")
-        E(f"v_mad_u32_u24 v{TT(1)}, v{TT(1)}, s{S_W}, v{d}")                      # y * W + x
-        E(f"v_mul_lo_u32 v{TT(1)}, v{TT(1)}, s{S_LDIN}")
-        E(f"v_and_b32_e32 v{TT(0)}, 3, v{VTID}")                                # kq
-        E(f"v_lshl_add_u32 v{TT(1)}, v{TT(0)}, 2, v{TT(1)}")
-        E(f"v_lshlrev_b32_e32 v{TT(1)}, 2, v{TT(1)}")                             # bytes
+        E(f"v_mad_u32_u24 v{VT1}, v{VT1}, s{S_W}, v{d}")                      # y * W + x
+        E(f"v_mul_lo_u32 v{VT1}, v{VT1}, s{S_LDIN}")
+        E(f"v_and_b32_e32 v{VT0}, 3, v{VTID}")                                # kq
+        E(f"v_lshl_add_u32 v{VT1}, v{VT0}, 2, v{VT1}")
+        E(f"v_lshlrev_b32_e32 v{VT1}, 2, v{VT1}")                             # bytes
         E(f"v_mov_b32_e32 v{d}, s{S_OOB}")
         E("s_nop 1")
-        E(f"v_cndmask_b32_e32 v{d}, v{d}, v{TT(1)}, vcc")
+        E(f"v_cndmask_b32_e32 v{d}, v{d}, v{VT1}, vcc")
     L(ldone)
 
 
-def halo_loads(issue=True, setn=0):
-    for i in range(3 if issue else 0):
+def halo_loads(setn=0):
+    for i in range(3):
         E(f"buffer_load_dwordx4 {vr(HSET(setn, i), 4)}, v{VHOFF[i]}, s[{S_INR}:{S_INR + 3}], s{S_LC64} offen")
     # lc = lc + 1 == nC ? 0 : lc + 1;  lp += lc == 0
     E(f"s_add_u32 s{S_LC}, s{S_LC}, 1")
@@ -233,27 +217,20 @@ def form_valu(jp, jj, slot, hf):
     w = "-1.0" if not (jj == 1 and jp == 0) else "1.0"
     a, b, c, d = RAW(hf, 0), RAW(hf, 1), RAW(hf, 2), RAW(hf, 3)
     r = []
-    if opt("slow_valu"):                  # the first version's forms (VOP3 / SGPR operands), kept for the A/B
-        for e in range(4):
-            r.append(f"v_fma_f32 v{a + e}, s{S_SGN}, v{b + e}, v{a + e}")       # qx = sgn * rb_x + ra_x
-        for e in range(4):
-            r.append(f"v_fma_f32 v{c + e}, s{S_SGN}, v{d + e}, v{c + e}")       # qy
-        for e in range(4):
-            r.append(f"v_fma_f32 v{a + e}, {w}, v{c + e}, v{a + e}")            # v = w * qy + qx
-    else:                                 # the same values bit for bit: fma(sgn, b, a) as v_fmac; fma(+-1, qy, qx) = qx +- qy rounded once
-        for e in range(4):
-            r.append(f"v_fmac_f32_e32 v{a + e}, v{VSGN()}, v{b + e}")
-        for e in range(4):
-            r.append(f"v_fmac_f32_e32 v{c + e}, v{VSGN()}, v{d + e}")
-        for e in range(4):
-            r.append(f"v_{'add' if w == '1.0' else 'sub'}_f32_e32 v{a + e}, v{a + e}, v{c + e}")
+    # v = fma(w, fma(sgn, rb_y, ra_y), fma(sgn, rb_x, ra_x)) bit for bit: fma(sgn, b, a) as v_fmac; fma(+-1, qy, qx) = qx +- qy rounded once
+    for e in range(4):
+        r.append(f"v_fmac_f32_e32 v{a + e}, v{VSGN()}, v{b + e}")
+    for e in range(4):
+        r.append(f"v_fmac_f32_e32 v{c + e}, v{VSGN()}, v{d + e}")
+    for e in range(4):
+        r.append(f"v_{'add' if w == '1.0' else 'sub'}_f32_e32 v{a + e}, v{a + e}, v{c + e}")
     # pairs (0,1) -> piece dword hf*2, (2,3) -> hf*2+1;  temporaries: the b registers
     for piece in range(3):
         for p in range(2):
             r.append(f"v_perm_b32 v{PC(slot, piece) + hf * 2 + p}, v{a + 2 * p + 1}, v{a + 2 * p}, s{S_PERM}")
         if piece < 2:
             for e in range(4):
-                r.append(f"v_and_b32_e32 v{b + e}, {'s' + str(S_MASK) if opt('slow_valu') else 'v' + str(VMASK())}, v{a + e}")
+                r.append(f"v_and_b32_e32 v{b + e}, v{VMASK()}, v{a + e}")
             for e in range(4):
                 r.append(f"v_sub_f32_e32 v{a + e}, v{a + e}, v{b + e}")
     assert len(r) == 34
@@ -267,7 +244,7 @@ def mfmas(jj, mi, slot):
     for nt in range(2):
         acc = vr(ACC(jj, nt, mi), 16)
         for k, (pa, pb) in enumerate(((2, 0), (0, 2), (1, 1), (1, 0), (0, 1), (0, 0))):
-            src = "0" if (FIRST_CHUNK[0] and k == 0 and not opt("zero_acc")) else acc
+            src = "0" if (FIRST_CHUNK[0] and k == 0) else acc
             r.append(f"v_mfma_f32_32x32x16_bf16 {acc}, {vr(PC(slot, pa), 4)}, {vr(BX(jj, nt, pb), 4)}, {src}")
     return r
 
@@ -276,15 +253,7 @@ def weight_load(jj, nt, p):
     return f"buffer_load_dwordx4 {vr(BX(jj, nt, p), 4)}, v{VLANE16}, s[{S_UR}:{S_UR + 3}], s{S_WO[jj][nt]} offen offset:{p * 1024}"
 
 
-STAMP_PAIRS = [60, 62, 64, 66, 70, 72, 74, 76]
-def stamp(i):
-    """timing-only (steptimes): s_memtime into pair i; placed only where no LDS read is in flight (lgkmcnt returns out of order with SMEM)"""
-    if opt("steptimes"):
-        E(f"s_memtime s[{STAMP_PAIRS[i]}:{STAMP_PAIRS[i] + 1}]")
-        E("s_waitcnt lgkmcnt(0)")
-
-
-def emit_step_spread(jp, s):
+def emit_step(jp, s):
     """Step s with the raw-operand reads spread over the MFMA gaps (at most two ds_read_b128 per gap, none waited for in the
     step it was issued in): the raw registers are two halves of four 16-byte registers (input channels 0-3 / 4-7 of the lane's
     eight); half 0 of step s + 2 is requested in gaps 7-8 of step s (its registers are free once the first half of step s + 1's
@@ -292,17 +261,14 @@ def emit_step_spread(jp, s):
     of step 2 and the read bases flip to the other buffer inside it."""
     jj, mi, slot = s >> 1, s & 1, s & 1
     n1, n2 = (s + 1) & 3, (s + 2) & 3
-    stamp((2, 3, 4, 6)[s])                # starts of steps 0, 1; arrival at B1; start of step 3
     if s == 2:
         E("s_waitcnt lgkmcnt(0)")
-        if not opt("no_barrier"):
-            E("s_barrier")                # B1: chunk c + 1 is complete in the other buffer
-        stamp(5)
+        E("s_barrier")                    # B1: chunk c + 1 is complete in the other buffer
     if s == 0:
         # this component's weight pieces (requested in step 1 of the previous chunk).  VMEM operations retire in order: younger than
-        # them are the other component's six pieces (step 3) and, when the staging stood in front of this step, this chunk's three
-        # halo loads; with the staging inside the step they are issued BEHIND this wait.  The halo registers (older) are covered.
-        E(f"s_waitcnt vmcnt({6 if opt('stage_in_step0', 1) else 9})")
+        # them are the other component's six pieces (step 3); this chunk's staging is issued BEHIND this wait.  The halo registers
+        # (older) are covered.
+        E("s_waitcnt vmcnt(6)")
     if s == 2:
         E("s_waitcnt vmcnt(9)")           # pieces requested in step 3 of the previous chunk; younger: 3 halo loads + 6 pieces of step 1
     # two wait states between the v_perm that wrote the last dword of this step's low-order operand piece (tail of the previous
@@ -311,43 +277,34 @@ def emit_step_spread(jp, s):
     mf = mfmas(jj, mi, slot)
     v0 = form_valu(jp, n1 >> 1, slot ^ 1, 0)
     v1 = form_valu(jp, n1 >> 1, slot ^ 1, 1)
-    if opt("no_valu"):
-        v0, v1 = [], []
     r1 = raw_reads(jp, n1 >> 1, n1 & 1)[4:8]        # half 1 of the next step
     r2 = raw_reads(jp, n2 >> 1, n2 & 1)[0:4]        # half 0 of the step after it
-    if opt("no_ldsread"):
-        r1, r2 = [], []
     wl = {}
-    if mi == 1 and not opt("no_wload"):
+    if mi == 1:
         wl = {1: [weight_load(jj, 0, 2)], 4: [weight_load(jj, 0, 1)], 5: [weight_load(jj, 0, 0)],
               7: [weight_load(jj, 1, 2)], 10: [weight_load(jj, 1, 1)], 11: [weight_load(jj, 1, 0)]}
     def take(lst, n):
         for _ in range(min(n, len(lst))):
             E(lst.pop(0))
     extra = {}
-    if s == 0 and opt("stage_in_step0", 1):
+    if s == 0:
         # Parking chunk c + 1 (halo registers -> the idle buffer) and requesting chunk c + 2 ride in the gaps of step 0 instead of
-        # standing in front of it: the matrix pipe starts right behind B0.  vmcnt(9) above covers the halo registers (they are
+        # standing in front of it: the matrix pipe starts right behind B0.  vmcnt(6) above covers the halo registers (they are
         # older than the weight pieces it waits for).
-        if not opt("no_halo"):
-            for i in range(3):
-                extra.setdefault(i, []).append(f"ds_write_b128 v{VHST[i]}, {vr(HREG(i), 4)}")
-            for i in range(3):
-                extra.setdefault(3 + i, []).append(f"buffer_load_dwordx4 {vr(HREG(i), 4)}, v{VHOFF[i]}, s[{S_INR}:{S_INR + 3}], s{S_LC64} offen")
+        for i in range(3):
+            extra.setdefault(i, []).append(f"ds_write_b128 v{VHST[i]}, {vr(HREG(i), 4)}")
+        for i in range(3):
+            extra.setdefault(3 + i, []).append(f"buffer_load_dwordx4 {vr(HREG(i), 4)}, v{VHOFF[i]}, s[{S_INR}:{S_INR + 3}], s{S_LC64} offen")
         extra.setdefault(6, []).extend([
             f"s_add_u32 s{S_LC}, s{S_LC}, 1", f"s_cmp_eq_u32 s{S_LC}, s{S_NC}", f"s_cselect_b32 s{S_LC}, 0, s{S_LC}",
             f"s_cmp_eq_u32 s{S_LC}, 0", f"s_addc_u32 s{S_LP}, s{S_LP}, 0", f"s_lshl_b32 s{S_LC64}, s{S_LC}, 6"])
         extra.setdefault(3, []).extend([f"v_xor_b32_e32 v{VHST[i]}, 0x{BUFX:x}, v{VHST[i]}" for i in range(3)])
-    a0, a1 = opt("sp_v0", (2, 6)), opt("sp_v1", (7, 10))      # gap ranges of the two transform halves
+    a0, a1 = (2, 6), (7, 10)              # gap ranges of the two transform halves
     per0 = -(-34 // (a0[1] - a0[0] + 1))
     per1 = -(-34 // (a1[1] - a1[0] + 1))
-    pr = opt("prio")                      # timing experiments: s_setprio per (jp, step)
-    if pr and pr[jp][s] != pr[jp][(s + 3) & 3]:
-        E(f"s_setprio {pr[jp][s]}")
     nlds = 0                              # LDS operations issued in this step so far (all younger than half 0's reads)
     for k in range(12):
-        if not opt("no_mfma"):
-            E(mf[k])
+        E(mf[k])
         for x in wl.get(k, []):
             E(x)
         for x in extra.get(k, []):
@@ -374,145 +331,6 @@ def emit_step_spread(jp, s):
     assert not v1 and not r1 and not r2
 
 
-def emit_step_pp(jp, s):
-    """Ping-pong schedule (option pingpong; an experiment of record -- measured 1.8 % slower than the spread schedule, see
-    profiles/r05_asm_experiments.txt -- and not maintained against later changes of the register map: the cold-code temporaries of
-    setup_load / the epilogue would have to move out of the raw set, which it keeps in flight across chunk tops): a wave alternates a PURE matrix phase (the step's twelve MFMAs back to back) with a
-    transform phase (wait for the raw operands requested before the burst, 68 VALU into the single operand-piece slot), and the two
-    waves of a SIMD run the phases in opposite order -- waves 0-3 (jp 0): M(s) then V(s + 1); waves 4-7 (jp 1): V(s) then M(s) -- so
-    one wave's transform always lies beside its partner's burst (tools/ubench: a burst of 8 MFMAs followed by 48 VALU, two waves per
-    SIMD: both finish together at 100 % of the matrix pipe; the same work interleaved per gap: 75-93 %).  One operand-piece slot and
-    one raw set per wave; the raw reads of the next transform are issued right in front of the burst."""
-    jj, mi = s >> 1, s & 1
-    X = jp == 0
-    ns = (s + 1) & 3
-    stamp(2 + s if s < 3 else 5)          # starts of steps 0..2; arrival at B1
-    if s == 3:
-        E("s_waitcnt lgkmcnt(0)")
-        if not opt("no_barrier"):
-            E("s_barrier")                # B1: the next chunk is complete in the other buffer (first read of it: this step)
-        stamp(6)
-    def reads(step):
-        if not opt("no_ldsread"):
-            for r in raw_reads(jp, step >> 1, step & 1):
-                E(r)
-    def flip():
-        E(f"v_xor_b32_e32 v{VA}, 0x{BUFX:x}, v{VA}")
-        E(f"v_xor_b32_e32 v{VB}, 0x{BUFX:x}, v{VB}")
-    def staging():
-        if opt("no_halo"):
-            return
-        for i in range(3):
-            E(f"ds_write_b128 v{VHST[i]}, {vr(HREG(i), 4)}")
-        for i in range(3):
-            E(f"v_xor_b32_e32 v{VHST[i]}, 0x{BUFX:x}, v{VHST[i]}")
-        halo_loads(True)
-    def V(step):                          # transform + split of `step`'s operands into slot 0
-        E("s_waitcnt lgkmcnt(0)")
-        if not opt("no_valu"):
-            for hf in range(2):
-                for x in form_valu(jp, step >> 1, 0, hf):
-                    E(x)
-    def M():
-        mf = mfmas(jj, mi, 0)
-        wl = {}
-        if mi == 1 and not opt("no_wload"):
-            wl = {1: [weight_load(jj, 0, 2)], 4: [weight_load(jj, 0, 1)], 5: [weight_load(jj, 0, 0)],
-                  7: [weight_load(jj, 1, 2)], 10: [weight_load(jj, 1, 1)], 11: [weight_load(jj, 1, 0)]}
-        if opt("pp_prio"):
-            E("s_setprio 1")
-        for k in range(12):
-            if not opt("no_mfma"):
-                E(mf[k])
-            for x in wl.get(k, []):
-                E(x)
-        if opt("pp_prio"):
-            E("s_setprio 0")
-    if X:
-        if s == 3:
-            flip()
-        reads(ns)                         # operands of the NEXT step: requested in front of the burst, transformed behind it
-        if s == 0:
-            E("s_waitcnt vmcnt(6)")       # weight pieces of component 0 (step 1 of the previous chunk); younger: the six of step 3
-        if s == 2:
-            E("s_waitcnt vmcnt(9)")       # pieces of step 3 of the previous chunk; younger: 3 halo loads + 6 pieces of step 1
-        M()
-        V(ns)
-        if s == 0:
-            staging()                     # halo registers are older than the pieces waited for above
-    else:
-        if s == 0:
-            E("s_waitcnt vmcnt(12)")      # the halo registers (both sets of weight pieces are younger)
-        V(s)
-        if s == 0:
-            staging()
-        if s == 3:
-            flip()
-        reads(ns)
-        E("s_nop 1")
-        if s in (0, 2):
-            E("s_waitcnt vmcnt(9)")       # this component's pieces; younger: the other six + three halo loads (step 0: just issued)
-        M()
-
-
-def emit_step(jp, s):
-    if opt("pingpong"):
-        return emit_step_pp(jp, s)
-    if opt("spread", 1):
-        return emit_step_spread(jp, s)
-    jj, mi, slot = s >> 1, s & 1, s & 1
-    ns = (s + 1) & 3
-    njj, nmi = ns >> 1, ns & 1
-    if s == 2:
-        pass
-    stamp(2 + s if s < 3 else 5)         # 2, 3, 4: starts of steps 0..2; 5: arrival at B1
-    if s == opt("b1_step", 3):
-        # B1: chunk c + 1 is complete in the other buffer (step 3's reads are the next chunk's step 0)
-        E("s_waitcnt lgkmcnt(0)")
-        if not opt("no_barrier"):
-            E("s_barrier")
-        stamp(6)
-    if s == 3:
-        E(f"v_xor_b32_e32 v{VA}, 0x{BUFX:x}, v{VA}")
-        E(f"v_xor_b32_e32 v{VB}, 0x{BUFX:x}, v{VB}")
-    if not opt("no_ldsread"):
-        for r in raw_reads(jp, njj, nmi):
-            E(r)
-    if s in (0, 2):
-        E("s_waitcnt vmcnt(9)")          # this component's weight pieces (requested a chunk ago)
-    mf = mfmas(jj, mi, slot)
-    v0 = form_valu(jp, njj, slot ^ 1, 0)
-    v1 = form_valu(jp, njj, slot ^ 1, 1)
-    wl = {}
-    if mi == 1 and not opt("no_wload"):   # pieces of the next chunk into the registers this step has finished with
-        wl = {1: [weight_load(jj, 0, 2)], 4: [weight_load(jj, 0, 1)], 5: [weight_load(jj, 0, 0)],
-              7: [weight_load(jj, 1, 2)], 10: [weight_load(jj, 1, 1)], 11: [weight_load(jj, 1, 0)]}
-    def take(lst, n):
-        for _ in range(min(n, len(lst))):
-            E(lst.pop(0))
-    if opt("no_valu"):
-        v0, v1 = [], []
-    f0 = opt("valu_from", 2)                     # first gap with transform work
-    n0 = 5 if f0 >= 2 else 6 - f0                # gaps of the first half
-    per0 = -(-34 // n0)
-    per1 = -(-34 // (10 - (f0 + n0 - 1)))
-    for k in range(12):
-        if not opt("no_mfma"):
-            E(mf[k])
-        for x in wl.get(k, []):
-            E(x)
-        if k == f0:
-            E("s_waitcnt lgkmcnt(4)")
-        if f0 <= k < f0 + n0:
-            take(v0, per0)
-        if k == f0 + n0 - 1:
-            assert not v0
-            E("s_waitcnt lgkmcnt(0)")
-        if f0 + n0 <= k <= 10:
-            take(v1, per1)
-    assert not v1
-
-
 def emit_chunk(jp):
     """one 16-channel chunk: B0, park chunk c + 1, request chunk c + 2, four steps"""
     lskip = newlabel("nosetup")
@@ -523,18 +341,7 @@ def emit_chunk(jp):
     setup_load()
     L(lskip)
     E("s_waitcnt lgkmcnt(0)")
-    stamp(0)                              # arrival at B0
-    if not opt("no_barrier"):
-        E("s_barrier")                    # B0
-    stamp(1)
-    inl = (opt("spread", 1) and opt("stage_in_step0", 1)) or opt("pingpong")
-    if not inl:
-        E("s_waitcnt vmcnt(12)")          # the halo registers (two sets of weight pieces are younger)
-        if not opt("no_halo"):
-            halo_stores()
-        halo_loads(not opt("no_halo"))
-        for i in range(3):
-            E(f"v_xor_b32_e32 v{VHST[i]}, 0x{BUFX:x}, v{VHST[i]}")
+    E("s_barrier")                        # B0 (parking chunk c + 1 and requesting chunk c + 2 ride in step 0: emit_step)
     # weight soffsets of chunk cn = c + 1 == nC ? 0 : c + 1
     E(f"s_add_u32 s{S_T[0]}, s{S_C}, 1")
     E(f"s_cmp_eq_u32 s{S_T[0]}, s{S_NC}")
@@ -545,37 +352,6 @@ def emit_chunk(jp):
     E(f"s_add_u32 s{S_WO[1][1]}, s{S_WO[0][1]}, 0xc00")
     for s in range(4):
         emit_step(jp, s)
-    if opt("steptimes"):                  # stamp 7: end of the chunk; chunk 8's stamps -> out[(wg * 8 + wave) * 8 ..]
-        E("s_waitcnt lgkmcnt(0)")
-        E("s_memtime s[92:93]")
-        E("s_waitcnt lgkmcnt(0)")
-        lno = newlabel("nostore")
-        E(f"s_cmp_lg_u32 s{S_C}, 8")
-        E(f"s_cbranch_scc1 {lno}")
-        E(f"s_mov_b32 s{S_OUTR}, s{S_OUT}")
-        E(f"s_and_b32 s{S_OUTR + 1}, s{S_OUT + 1}, 0xffff")
-        E(f"s_mov_b32 s{S_OUTR + 2}, 0x7ffffff0")
-        E(f"s_mov_b32 s{S_OUTR + 3}, 0x00020000")
-        E("s_lshl_b32 s94, s2, 3")
-        E(f"s_lshl_b32 s95, s{S_JP}, 2")
-        E(f"s_add_u32 s95, s95, s{S_WI}")
-        E("s_add_u32 s94, s94, s95")
-        E("s_lshl_b32 s94, s94, 5")
-        E("s_mov_b64 s[96:97], exec")
-        E(f"v_and_b32_e32 v{TT(0)}, 63, v{VTID}")
-        E(f"v_cmp_eq_u32_e32 vcc, 0, v{TT(0)}")
-        E("s_and_b64 exec, exec, vcc")
-        for k in range(4):
-            a, b = STAMP_PAIRS[2 * k], (STAMP_PAIRS[2 * k + 1] if k < 3 else 92)
-            if k == 3:
-                a = STAMP_PAIRS[6]
-            E(f"v_mov_b32_e32 v{TT(0)}, s{a}")
-            E(f"v_mov_b32_e32 v{TT(1)}, s{b}")
-            E(f"v_mov_b32_e32 v{VHOFF[0]}, 0")
-            E(f"buffer_store_dwordx2 v[{TT(0)}:{TT(1)}], v{VHOFF[0]}, s[{S_OUTR}:{S_OUTR + 3}], s94 offen offset:{8 * k}")
-            E("s_waitcnt vmcnt(0)")
-        E("s_mov_b64 exec, s[96:97]")
-        L(lno)
 
 
 def pk2(op, d, a, b, neg_a=False, neg_b=False):
@@ -625,7 +401,6 @@ def emit_epilogue(jp):
     # the finishing pass); e0..e3 are dead once the addresses are formed
     SC4 = [E0 + 4, 226]
     SH4 = [e0, 220]
-    assert not opt("pingpong")
     E("s_nop 7")
     E("s_nop 7")
     E("s_nop 7")
@@ -729,7 +504,6 @@ def emit_epilogue(jp):
                     E("s_nop 0")
                     for k in range(4):
                         off = (32 * mi + 2 * (r0 + k)) * 128 + (ZBIAS if q else 0)
-                        assert "noaddtid" not in DEBUG
                         E(f"ds_write_addtid_b32 v{src[k]} offset:{off}")
         E("s_waitcnt lgkmcnt(0)")
         E("s_barrier")
@@ -773,12 +547,7 @@ def emit_epilogue(jp):
         E(f"buffer_store_dwordx4 {vr(pm, 4)}, v{VPOOL}, s[{S_POOLR}:{S_POOLR + 3}], 0 offen offset:{nt * 128}")
         L(lnp)
         # (the accumulators -- registers of the finishing pass -- are NOT cleared: the first chunk of a patch is a peeled copy of the
-        # chunk loop whose accumulator chains start from the constant 0; option zero_acc restores the clearing for the A/B)
-        if opt("zero_acc"):
-            E("s_nop 1")
-            for b in sorted(zb):
-                for r in range(16):
-                    E(f"v_mov_b32_e32 v{b + r}, 0")
+        # chunk loop whose accumulator chains start from the constant 0)
         E("s_waitcnt lgkmcnt(0)")
         E("s_barrier")                   # the regions are rewritten by the next pass / receive the next raw chunk
 
@@ -1023,46 +792,19 @@ def emit_patch_loop(jp):
     lp, lc = newlabel("patch"), newlabel("chunk")
     L(lp)
     E(f"s_mov_b32 s{S_C}, 0")
-    if not opt("zero_acc"):              # chunk 0, peeled (a layer has at least two chunks: Cp % 32 == 0)
-        FIRST_CHUNK[0] = True
-        emit_chunk(jp)
-        FIRST_CHUNK[0] = False
-        E(f"s_mov_b32 s{S_C}, 1")
+    FIRST_CHUNK[0] = True                # chunk 0, peeled (a layer has at least two chunks: Cp % 32 == 0)
+    emit_chunk(jp)
+    FIRST_CHUNK[0] = False
+    E(f"s_mov_b32 s{S_C}, 1")
     L(lc)
     emit_chunk(jp)
     E(f"s_add_u32 s{S_C}, s{S_C}, 1")
     E(f"s_cmp_lt_u32 s{S_C}, s{S_NC}")
     E(f"s_cbranch_scc1 {lc}")
-    if opt("no_epilogue"):
-        E("s_nop 7")
-        E("s_nop 7")
-        for r in range(128):
-            E(f"v_mov_b32_e32 v{r}, 0")
-    else:
-        emit_epilogue(jp)
+    emit_epilogue(jp)
     E(f"s_add_u32 s{S_PI}, s{S_PI}, 1")
     E(f"s_cmp_lt_u32 s{S_PI}, s{S_NPATCH}")
     E(f"s_cbranch_scc1 {lp}")
-    if opt("stamp"):                 # (cycles, 100 MHz ticks) of the workgroup's life -> out[2 * wg .. 2 * wg + 1] (wave 0 writes)
-        E("s_waitcnt vmcnt(0) lgkmcnt(0)")
-        E("s_memtime s[60:61]")
-        E("s_memrealtime s[62:63]")
-        E("s_waitcnt lgkmcnt(0)")
-        E(f"s_sub_u32 s60, s60, s{S_PAD}")
-        E(f"s_sub_u32 s62, s62, s{S_W1}")
-        E("v_mov_b32_e32 v0, s60")
-        E("v_mov_b32_e32 v1, s62")
-        E(f"s_mov_b32 s{S_OUTR}, s{S_OUT}")
-        E(f"s_and_b32 s{S_OUTR + 1}, s{S_OUT + 1}, 0xffff")
-        E(f"s_mov_b32 s{S_OUTR + 2}, 0x7ffffff0")
-        E(f"s_mov_b32 s{S_OUTR + 3}, 0x00020000")
-        E("s_lshl_b32 s61, s2, 3")
-        E(f"v_cmp_eq_u32_e32 vcc, 0, v{VTID}")
-        E("s_and_saveexec_b64 s[64:65], vcc")
-        E("v_mov_b32_e32 v2, 0")
-        E(f"buffer_store_dwordx2 v[0:1], v2, s[{S_OUTR}:{S_OUTR + 3}], s61 offen")
-        E("s_waitcnt vmcnt(0)")
-        E("s_mov_b64 exec, s[64:65]")
     E(f"s_branch {END_LABEL}")
 
 
@@ -1073,12 +815,6 @@ def emit_prologue():
     E("s_load_dwordx2 s[32:33], s[0:1], 0x70")
     E(f"v_mov_b32_e32 v{VTID}, v0")
     E("s_waitcnt lgkmcnt(0)")
-    if opt("stamp"):                 # timing-only: shader clock and 100 MHz real-time counter at the start of the workgroup
-        E("s_memtime s[60:61]")
-        E("s_memrealtime s[62:63]")
-        E("s_waitcnt lgkmcnt(0)")
-        E(f"s_mov_b32 s{S_PAD}, s60")
-        E(f"s_mov_b32 s{S_W1}, s62")
     # item = (wg & 7) * per_xcd + (wg >> 3)
     t = S_T
     E(f"s_and_b32 s{t[0]}, s2, 7")
@@ -1193,7 +929,7 @@ def emit_prologue():
                 for pp in range(3):
                     E(f"buffer_load_dwordx4 {vr(WN(c, jj, pp), 4)}, v{VLANE16}, s[{S_UR}:{S_UR + 3}], s{S_WO[0][0]} offen offset:{pp * 1024}")
         setup_load()
-        halo_loads(True, 0)
+        halo_loads(0)
         for i in range(3):
             E(f"v_xor_b32_e32 v{VHST[i]}, 0x{BUFX:x}, v{VHST[i]}")
         E("s_waitcnt vmcnt(0)")
@@ -1208,7 +944,7 @@ def emit_prologue():
             E(f"s_cbranch_scc1 {lsk}")
             setup_load()
             L(lsk)
-            halo_loads(True, setn)
+            halo_loads(setn)
         E("s_waitcnt lgkmcnt(0)")
         E("s_barrier")
         return
@@ -1237,44 +973,20 @@ def emit_prologue():
         for nt in range(2):
             for p in range(3):
                 E(weight_load(jj, nt, p))
-    if opt("zero_acc") or opt("no_epilogue"):
-        for r in range(128):
-            E(f"v_mov_b32_e32 v{r}, 0")
     E("s_waitcnt lgkmcnt(0)")
     E("s_barrier")
 
 
-def emit_dump(first_reg):
-    """debug: thread tid stores 32 consecutive registers at out + tid * 128 bytes and the program ends"""
-    E("s_waitcnt vmcnt(0) lgkmcnt(0)")
-    E("s_nop 7")
-    E("s_nop 7")
-    E(f"s_mov_b32 s{S_OUTR}, s{S_OUT}")
-    E(f"s_and_b32 s{S_OUTR + 1}, s{S_OUT + 1}, 0xffff")
-    E(f"s_mov_b32 s{S_OUTR + 2}, 0x7ffffff0")
-    E(f"s_mov_b32 s{S_OUTR + 3}, 0x00020000")
-    E(f"v_lshlrev_b32_e32 v{TT(0)}, 7, v{VTID}")
-    for k in range(8):
-        E(f"buffer_store_dwordx4 {vr(first_reg + 4 * k, 4)}, v{TT(0)}, s[{S_OUTR}:{S_OUTR + 3}], 0 offen offset:{16 * k}")
-    E("s_waitcnt vmcnt(0)")
-    E("s_endpgm")
-
-
 def emit_first_form(jp):
     """step 0 of the first chunk (no MFMAs to hide behind)"""
-    if opt("pingpong") and jp == 1:       # waves 4-7 transform inside the loop: only the request
-        for r in raw_reads(jp, 0, 0):
-            E(r)
-        return
     for r in raw_reads(jp, 0, 0):
         E(r)
     E("s_waitcnt lgkmcnt(0)")
     for hf in range(2):
         for x in form_valu(jp, 0, 0, hf):
             E(x)
-    if opt("spread", 1) and not opt("pingpong"):
-        for r in raw_reads(jp, 0, 1)[0:4]:
-            E(r)
+    for r in raw_reads(jp, 0, 1)[0:4]:
+        E(r)
 
 
 def emit_kernel(name):
@@ -1292,21 +1004,11 @@ def emit_kernel(name):
     global END_LABEL
     END_LABEL = end
     emit_prologue()
-    if DEBUG.startswith("dump_pro:"):      # registers after the lead-in (raw reads of step 0 are issued but not transformed)
-        for r in raw_reads(0, 0, 0):
-            E(r)
-        for i, sr in enumerate((S_SGN, S_WI, S_JP, 60, 61, 62, 63, S_NBLOCK, S_PBEGIN, S_NPATCH, S_LC, S_LP, S_NC, S_UR, S_UR + 1, S_UR + 2)):
-            E(f"v_mov_b32_e32 v{224 + i}, s{sr}")
-        emit_dump(int(DEBUG.split(":")[1]))
     E(f"s_cmp_lg_u32 s{S_JP}, 0")
     E(f"s_cbranch_scc1 {jp1}")
-    if opt("prio_jp0"):
-        E(f"s_setprio {opt('prio_jp0')}")
     emit_first_form(0)
     (emit_patch_loop if NTB() == 2 else emit_patch_loop_n)(0)
     L(jp1)
-    if opt("prio_jp1"):      # static priority for the second-dispatched half (the SIMD partners of waves 0-3)
-        E(f"s_setprio {opt('prio_jp1')}")
     emit_first_form(1)
     (emit_patch_loop if NTB() == 2 else emit_patch_loop_n)(1)
     L(end)
@@ -1372,45 +1074,14 @@ def emit_kernel(name):
 
 META = []
 END_LABEL = ".Lend"
-VARIANTS = [   # (kernel-name suffix, options); suffix "" = the shipping kernel
-    ("", {}),
-]
-if os.environ.get("GEN_WINO_VARIANTS"):
-    VARIANTS += [
-        ("_v1", {"no_epilogue": 1}),
-        ("_v2", {"no_epilogue": 1, "no_valu": 1}),
-        ("_v3", {"no_epilogue": 1, "no_mfma": 1}),
-        ("_v4", {"no_epilogue": 1, "no_barrier": 1}),
-        ("_v5", {"slow_valu": 1}),
-        ("_v6", {"sp_v0": (1, 5), "sp_v1": (6, 10)}),
-        ("_v7", {"prio": ((0, 0, 1, 1), (1, 1, 0, 0))}),
-        ("_v8", {"no_epilogue": 1, "stamp": 1}),
-        ("_v9", {"no_epilogue": 1, "no_valu": 1, "stamp": 1}),
-        ("_v10", {"no_epilogue": 1, "no_mfma": 1, "stamp": 1}),
-        ("_v11", {"no_epilogue": 1, "no_wload": 1, "stamp": 1}),
-        ("_v12", {"no_epilogue": 1, "no_halo": 1, "stamp": 1}),
-        ("_v13", {"no_epilogue": 1, "no_ldsread": 1, "stamp": 1}),
-        ("_v15", {"no_epilogue": 1, "steptimes": 1}),
-        ("_v16", {"no_epilogue": 1, "steptimes": 1, "slow_valu": 1}),
-        ("_v17", {"prio": ((0, 0, 0, 0), (0, 1, 0, 1))}),
-        ("_v18", {"sp_v0": (0, 5), "sp_v1": (6, 11)}),
-        ("_v19", {"sp_v0": (0, 5), "sp_v1": (6, 11), "prio": ((0, 0, 0, 0), (1, 0, 1, 0))}),
-        ("_v20", {"no_epilogue": 1, "steptimes": 1, "sp_v0": (0, 5), "sp_v1": (6, 11)}),
-        ("_v21", {"zero_acc": 1}),
-        ("_v14", {"no_epilogue": 1, "no_wload": 1, "no_halo": 1, "no_ldsread": 1, "no_valu": 1, "no_barrier": 1, "stamp": 1}),
-    ]
 
 
 def main():
     path = sys.argv[1]
     out.append('\t.amdgcn_target "amdgcn-amd-amdhsa--gfx950"')
-    for suffix, o in VARIANTS:
-        OPT.clear()
-        OPT.update(o)
-        CFG.update(ntb=2, nc=None)
-        emit_kernel("mgu_wino_cp2_gfx950" + suffix)
+    CFG.update(ntb=2, nc=None)
+    emit_kernel("mgu_wino_cp2_gfx950")
     for nc in (2, 4):            # the narrow kernels: 32 output channels, the layer's 2 / 4 chunks of weight pieces resident
-        OPT.clear()
         CFG.update(ntb=1, nc=nc)
         emit_kernel(f"mgu_wino_cp1r{nc}_gfx950")
     out.append("\t.amdgpu_metadata\n---\namdhsa.kernels:")

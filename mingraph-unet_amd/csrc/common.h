@@ -19,20 +19,12 @@ namespace mgu {
 // the launch descriptors, so two contexts of a process never see each other's settings.
 struct Tuning {
   bool first_mfma = true;   // MGU_NO_FIRST_MFMA=1: the first convolution on the VALU kernel (conv3x3_first_kernel) instead of the matrix cores (A/B)
-  bool use_halo = true;     // MGU_NO_HALO=1: generic gather kernel instead of the LDS-halo conv kernel (A/B)
-  bool halo_tps3 = true;    // MGU_HALO_TPS1=1: one tap per barrier on the N <= 32 halo tile too (A/B)
-  int halo_max_ppb = 16;    // MGU_HALO_PPB=n: patches a halo workgroup walks (1 = no persistence)
   bool use_wino = true;     // MGU_NO_WINOGRAD=1: direct kernels for the fp32 3x3 layers
-  int wino_mode = -1;       // MGU_WINO_MODE=1: force the 32-channel work split on every layer (A/B)
   int wino_prec = 1;        // MGU_WINO_PREC: 1 = three exact bf16 pieces per fp32 operand on the bf16 MFMA (default),
                             //                0 = fp32 MFMA operands
-  bool wino_cp_narrow = true;   // MGU_WINO_CP_NARROW=0: N <= 32 layers stay on wino3x3_f32_kernel<1,1> (A/B)
-  bool wino_yfast = false;  // MGU_WINO_YFAST=1: Winograd / halo workgroups walk their patches y fastest inside an image (A/B)
   bool convt_frag = true;   // MGU_NO_CONVT_FRAG=1: ConvTranspose on the generic tile kernel instead of convt_x3.hip's kernels (A/B)
-  bool wino_deep = true;    // MGU_NO_WINO_DEEP=1: one chunk of load lead on the narrow Winograd layers too (A/B)
   bool wino_cp = true;      // MGU_NO_WINO_CP=1: the four-components-per-wave kernel instead of the component-pair split (A/B)
-  int wino_rounds = 1;      // MGU_WINO_ROUNDS / MGU_WINO_PPB_CAP: persistence of the Winograd workgroups
-  int wino_ppb_cap = 32;
+  int wino_ppb_cap = 32;    // MGU_WINO_PPB_CAP: patches a Winograd workgroup walks at most
   bool wgrad_halo = true;   // MGU_NO_WGRAD_HALO=1
   bool wino_wgrad = true;   // MGU_NO_WINO_WGRAD=1
   bool convt_dgrad_x3 = true;   // MGU_NO_CONVT_DGRAD_X3=1: ConvTranspose data gradient on the generic fp32 tile kernel
@@ -40,11 +32,8 @@ struct Tuning {
   bool wgrad_thin = true;   // MGU_NO_THIN_WGRAD=1
   bool wino_dgrad = true;   // MGU_NO_WINO_DGRAD=1
   bool gat_fused = true;    // MGU_NO_GAT_FUSED=1
-  bool wino_ures = true;    // MGU_NO_WINO_URES=1: the 32-input-channel narrow layers reload their weight pieces every chunk (A/B)
-  bool wino_prio = false;   // MGU_WINO_PRIO=1: s_setprio 1 for waves 4-7 of the component-pair Winograd kernels (A/B)
-  bool wino_asm_narrow = true;   // MGU_WINO_ASM_NARROW=0: the assembly form only for the wide layers (A/B)
-  int wino_asm = 1;         // MGU_WINO_ASM=0: the C++ component-pair kernels instead of their hand-scheduled assembly forms (wino_asm.hip; bitwise
-                            // equal results, A/B and fallback); n > 1: timing-only variant n - 1 of a GEN_WINO_VARIANTS=1 build (never shipped)
+  bool wino_asm = true;     // MGU_WINO_ASM=0: the C++ component-pair kernels instead of their hand-scheduled assembly forms (wino_asm.hip; bitwise
+                            // equal results)
 };
 const Tuning& default_tuning();
 // The >64 KB dynamic-LDS opt-in is a per-DEVICE function attribute: set it once per (kernel, device).
@@ -86,7 +75,14 @@ struct IgemmDesc {
 
 inline const Tuning& tun(const IgemmDesc& d) { return d.tn ? *d.tn : default_tuning(); }
 hipError_t launch_igemm_f32(const IgemmDesc& d, hipStream_t s);
-int wino_grid_blocks(const IgemmDesc& d);   // wino_f32.hip: workgroups of the Winograd launch for d (= accumulator rows of its statistics)
+// wino_f32.hip: work split of the Winograd kernels.  8 x 32 pixel patches; a workgroup covers 64 output channels of a wide layer
+// (N > 32), 32 of a narrow one, and walks ppb patches; item (n block, patch group) of XCD x is x * per_xcd + (workgroup / 8)
+inline bool wino_wide(const IgemmDesc& d) { return d.N > 32; }
+struct WinoPlan {
+  int tiles_x, tiles_y, total, nblk, ppb, ngroups, per_xcd;
+};
+WinoPlan wino_plan(const IgemmDesc& d);
+int wino_grid_blocks(const IgemmDesc& d);   // workgroups of the Winograd launch for d (= accumulator rows of its statistics)
 bool halo_pool_fusable(const IgemmDesc& d, int dtype);   // the halo conv kernel will run: MaxPool2d(2) can ride in its epilogue
 hipError_t launch_igemm_bf16(const IgemmDesc& d, hipStream_t s);
 const char* igemm_kernel_name(const IgemmDesc& d, int dtype);

@@ -288,27 +288,6 @@ hipError_t launch_gat_prep(const float* W, const float* a, float* wa, unsigned* 
 // measurement; the cause of the round-4 failure at the ISA level remains unidentified (recorded as such in NOTES.md).
 __device__ __forceinline__ void lds_barrier() { __syncthreads(); }
 
-#if defined(MGU_DIAG) && (MGU_DIAG == 40 || MGU_DIAG == 41)
-// diagnostic builds (never shipped): phase stamps of one workgroup of gat_fused2_kernel, mgu_diag_gat[wave][tile][slot].
-//   40: every stamp drains the wave's memory operations first, so the intervals are the LATENCIES of the phases (and of the stamp's
-//       own store: ~1000-2000 cycles of floor per interval);
-//   41: no drain -- the stamps go to LDS and are copied out when the workgroup is done: the pipelined cost of the phases.
-__device__ unsigned long long mgu_diag_gat[4][8][16];
-#if MGU_DIAG == 40
-#define GAT_T(slot)                                                                                                    \
-  do {                                                                                                                 \
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                                         \
-    if (blockIdx.x == 100 && lane == 0 && dti < 8) mgu_diag_gat[wave][dti][slot] = __builtin_readcyclecounter();       \
-  } while (0)
-#else
-#define GAT_T(slot)                                                                                \
-  do {                                                                                             \
-    if (lane == 0 && dti >= 0 && dti < 8) diag_ts[wave][dti][slot] = __builtin_readcyclecounter(); \
-  } while (0)
-#endif
-#else
-#define GAT_T(slot) do {} while (0)
-#endif
 template <int FIN, int NT, int H>
 __global__ __launch_bounds__(256, FIN == 32 ? 3 : 2) void gat_fused2_kernel(const float* __restrict__ x, const float* __restrict__ st,
                                                          const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
@@ -459,14 +438,8 @@ __global__ __launch_bounds__(256, FIN == 32 ? 3 : 2) void gat_fused2_kernel(cons
     meta_cols(m_nxt);
   }
   m_nn = m_nxt;
-  [[maybe_unused]] int dti = -1;
-#if defined(MGU_DIAG) && MGU_DIAG == 41
-  __shared__ unsigned long long diag_ts[4][8][16];
-#endif
   for (int ti = ti0; ti < t_count; ti += wgx) {
     const int n0 = tile_n0(ti);
-    ++dti;
-    GAT_T(0);
     // rows of the tile after next: requested FIRST, a whole tile before their first use (the source ids read through them behind
     // this tile's GEMM): hipcc hoists the dependent address arithmetic as far up as it can, and with the request just in front of
     // barrier A the second MFMA of the GEMM waited for it -- and, vmcnt retiring in order, for the row prefetch in front of it
@@ -489,7 +462,6 @@ __global__ __launch_bounds__(256, FIN == 32 ? 3 : 2) void gat_fused2_kernel(cons
       const int rs = m_cur.rs[p], deg = m_cur.deg[p];
       const fH tj = m_cur.tj[p];
       fH gm = gm_cached;
-      GAT_T(1);   // (gmax)
       if (!one_graph) {   // a tile that straddles graphs (rare on image grids; the rule for tiny graphs): per-lane entries
         const int g = gf_graph_of(gp, G, min(n0 + nl, N - 1));
 #pragma unroll
@@ -514,7 +486,6 @@ __global__ __launch_bounds__(256, FIN == 32 ? 3 : 2) void gat_fused2_kernel(cons
           const int c_own = e0 == 0 ? m_cur.c0[p] : col[own ? rs + e0 + q : 0];
           fetch_rows(nl, c_own, xj, sj);
         }
-        GAT_T(3);   // source rows
         fH w = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int h = 0; h < H; ++h) {
@@ -565,9 +536,7 @@ __global__ __launch_bounds__(256, FIN == 32 ? 3 : 2) void gat_fused2_kernel(cons
 #pragma unroll
     for (int p = 0; p < PASSES; ++p) m_nxt.rs[p] = m_nn.rs[p], m_nxt.deg[p] = m_nn.deg[p];
     meta_t(tile_n0(ti + 2 * wgx), m_nxt);   // (its t one tile ahead)
-    GAT_T(4);   // weights, aggregate written
     lds_barrier();   // (A) the aggregate tile is complete; every wave has left the previous tile's exchange reads
-    GAT_T(5);
     // ---- (32 nodes x FIN) . W_h^T (FIN x 32) per (head, n tile) item on the bf16 matrix cores, exact three-way splits --------
     f32x16 c[HPW];
 #pragma unroll
@@ -597,7 +566,6 @@ __global__ __launch_bounds__(256, FIN == 32 ? 3 : 2) void gat_fused2_kernel(cons
     __builtin_amdgcn_sched_barrier(0);
     meta_cols(m_nxt);
     asm volatile("" ::"v"(c[0][0]));
-    GAT_T(6);   // GEMM
     auto elu = [](const float v) { return v > 0.f ? v : (__expf(v) - 1.f); };   // (:118)
     // (inside a wave that holds a head, every one of its HPW slots holds one: H is a multiple of NG or smaller than it -- so the
     // epilogue below has no per-register conditions: with a test per value hipcc emitted a branch per value, and the 32 exp chains of
@@ -661,22 +629,8 @@ __global__ __launch_bounds__(256, FIN == 32 ? 3 : 2) void gat_fused2_kernel(cons
           *reinterpret_cast<f32x4*>(out + (size_t)(n0 + row) * FO + nt * 32 + 4 * qd) = sum * invH;
       }
     }
-    GAT_T(7);   // ELU, head mean, stores
   }
-#if defined(MGU_DIAG) && MGU_DIAG == 41
-  if (blockIdx.x == 100 && lane == 0)
-    for (int t = 0; t <= min(dti, 7); ++t)
-      for (int k = 0; k < 16; ++k) mgu_diag_gat[wave][t][k] = diag_ts[wave][t][k];
-#endif
 }
-#if defined(MGU_DIAG) && (MGU_DIAG == 40 || MGU_DIAG == 41)
-}  // namespace mgu
-extern "C" int mgu_diag_gat_read(unsigned long long* out, int n) {
-  if (n > 4 * 8 * 16) n = 4 * 8 * 16;
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(mgu::mgu_diag_gat), (size_t)n * sizeof(unsigned long long));
-}
-namespace mgu {
-#endif
 
 bool gat_fused_applicable(int Fin, int heads, int Fh, int64_t E) {
   return (Fin == 32 || Fin == 64) && (Fh == 32 || Fh == 64) && (heads == 1 || heads == 2 || heads == 4) && Fin <= Fh && E > 0;

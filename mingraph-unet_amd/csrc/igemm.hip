@@ -293,24 +293,6 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmDesc d) {
 // double-buffered LDS panel, so there is a single s_barrier per tap.  The halo of the next chunk is
 // prefetched into registers while the current chunk computes.
 // =================================================================================================
-#if defined(MGU_DIAG) && MGU_DIAG == 23   // diagnostic build: step timeline of one workgroup of the selected layer (tools/diag_timeline.py --halo)
-#ifndef MGU_DIAG_H
-#define MGU_DIAG_H 128
-#endif
-#ifndef MGU_DIAG_CP
-#define MGU_DIAG_CP 128
-#endif
-#ifndef MGU_DIAG_N
-#define MGU_DIAG_N 128
-#endif
-__device__ unsigned long long mgu_halo_ts[4][256][4];
-#define HALO_T(slot)                                                                                                   \
-  do {                                                                                                                 \
-    if (diag_on && (threadIdx.x & 63) == 0 && st < 256) mgu_halo_ts[threadIdx.x >> 6][st][slot] = __builtin_readcyclecounter(); \
-  } while (0)
-#else
-#define HALO_T(slot) do {} while (0)
-#endif
 // max(lo, x) as ONE v_max_f32 (fmaxf() is two: the backend first quiets a possible signalling NaN).  A NaN operand yields the OTHER
 // operand (IEEE mode), a NaN only if both are: callers that must pass x through untouched hand in lo = quiet NaN.
 __device__ __forceinline__ float max_1op(const float lo, const float x) {
@@ -325,13 +307,9 @@ __device__ __forceinline__ void wait_vmcnt() {
   __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | 0x70 | 0xF00);
 }
 
-#if defined(MGU_DIAG) && MGU_DIAG == 50
-__device__ unsigned mgu_diag_glds_bad;
-__device__ unsigned long long mgu_diag_glds_n;
-#endif
 template <typename T, int NP, int TH, int WAVES_M, int WAVES_N, int WMT, int WNT, int TPS>
 __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(const IgemmDesc d, const int tiles_x, const int tiles_y,
-                                                           const int total_patches, const int patches_per_block, const int yfast) {
+                                                           const int total_patches, const int patches_per_block) {
   constexpr int VEC = Elem<T>::VEC;      // elements per 16-byte chunk
   constexpr int CK = NP * VEC;           // channels per chunk (NP 16-byte pieces per pixel)
   constexpr int LDS_LD = CK + VEC;       // LDS row pitch in elements
@@ -356,11 +334,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(const IgemmDesc d,
   // (global_load_lds_dwordx4: no registers, no ds_write pass, no wait in front of a hand-off).  An instruction writes 1 KB = eight
   // 128-byte rows in lane order, so the rows cannot be padded: 16-byte piece q of row r sits at position q ^ ((r >> 1) & 7) (the
   // SOURCE address is per lane, the image is linear) and the fragment reads of 16 consecutive rows fall on 16 distinct bank groups.
-#if defined(MGU_HALO_NO_GLDS)   // (A/B build: weight tiles through registers, as the 32-channel-chunk tiles do)
-  constexpr bool GLDS = false;
-#else
   constexpr bool GLDS = NP == 8 && BN % 32 == 0;
-#endif
   constexpr int BROW = GLDS ? CK : LDS_LD;   // weight-row pitch in LDS (elements)
   // GLDS: three weight buffers (the tile of step s + 2 requested at the top of step s) where two workgroups of the CU still fit
   constexpr int NBUF = (GLDS && (HP * LDS_LD + 3 * TPS * BN * CK) * (int)sizeof(T) <= 80 * 1024) ? 3 : 2;
@@ -386,11 +360,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(const IgemmDesc d,
   int hoff[HR];
   auto in_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(in_t), 0, 0x7ffffff0, 0x00020000);
   const unsigned img_bytes = (unsigned)((size_t)d.H * d.W * d.ldin * sizeof(T));
-  // x fastest by default; y fastest (MGU_WINO_YFAST=1, as in wino3x3_cp_kernel) measured neutral (+-0.5 %) in the bf16 mode
+  // x fastest (y fastest, as tried in wino3x3_cp_kernel, measured neutral (+-0.5 %) in the bf16 mode)
   struct PatchPos { int img, y0, x0; };
   auto setup_patch = [&](int p) {   // (by value: out-parameters through the nested closures of the item loop ended up in scratch)
-    const int ty = yfast ? p % tiles_y : (p / tiles_x) % tiles_y;
-    const int tx = yfast ? (p / tiles_y) % tiles_x : p % tiles_x;
+    const int ty = (p / tiles_x) % tiles_y;
+    const int tx = p % tiles_x;
     return PatchPos{p / (tiles_x * tiles_y), ty * TH, tx * TW};
   };
   auto setup_load = [&](int p) {
@@ -540,10 +514,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(const IgemmDesc d,
   if constexpr (DEEPH) load_next_halo(Set1{});   // item 1 -> set 1
   int c = 0, pi = 0;         // chunk / patch of the item being computed
   int par = 0;               // weight buffer of the step being computed
-  [[maybe_unused]] int st = 0;
-#if defined(MGU_DIAG) && MGU_DIAG == 23
-  const bool diag_on = blockIdx.x == 40 && blockIdx.y == 0 && d.H == MGU_DIAG_H && d.Cp == MGU_DIAG_CP && d.N == MGU_DIAG_N && sizeof(T) == 2;
-#endif
   // The SPI steps of an item are unrolled (the tap is a compile-time constant) and EVERY step issues the same loads whatever the
   // position in the walk (past the end: clamped re-reads that nobody uses): with a runtime tap and conditional loads hipcc merged the
   // pending-load states of the paths into `s_waitcnt vmcnt(0)` at every step, and -- vmcnt retiring in order -- each weight tile's wait
@@ -557,7 +527,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(const IgemmDesc d,
     const int cnext = c + 1 == nchunks ? 0 : c + 1;   // chunk of the next item
     x3_static_for<0, SPI>([&](auto tap_c) {
       constexpr int tap = decltype(tap_c)::value;
-      HALO_T(0);
       if constexpr (GLDS) {
         // this step's weight tile has landed: everything of this wave older than the operations issued BEHIND its DMA is complete.
         // NBUF == 2: the DMA was issued at the top of the previous step; behind it: the halo loads of step 0 (tap 1), the previous
@@ -577,26 +546,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(const IgemmDesc d,
         }
       }
       wg_barrier();  // Bs[par] (and a fresh halo when tap == 0) visible; the buffer of the previous step no longer read
-      HALO_T(1);
-#if defined(MGU_DIAG) && MGU_DIAG == 50
-      // one-shot checking build (never shipped): the weight tile of THIS step, as it stands in LDS behind the hand-counted wait and
-      // the barrier, against its global source; a mismatch sets bit 0 of mgu_diag_glds_bad, every compared 16-byte piece counts in
-      // mgu_diag_glds_n (tests read both through mgu_diag_glds_read)
-      if constexpr (GLDS) {
-#pragma unroll
-        for (int tt = 0; tt < TPS; ++tt) {
-          const int k0 = (tap * TPS + tt) * d.Cp + c * CK;
-          for (int e = tid; e < BN * 8; e += 256) {
-            const int row = e >> 3, piece = e & 7;
-            const int pos = piece ^ ((row >> 1) & 7);      // LDS position of logical piece `piece` of the row
-            const u32x4 got = *reinterpret_cast<const u32x4*>(Bs + ((size_t)(par * TPS + tt) * BN + row) * BROW + pos * VEC);
-            const u32x4 ref = *reinterpret_cast<const u32x4*>(w_t + (size_t)(bn0 + row) * d.Kp + k0 + piece * VEC);
-            if (got[0] != ref[0] || got[1] != ref[1] || got[2] != ref[2] || got[3] != ref[3]) atomicOr(&mgu_diag_glds_bad, 1u);
-          }
-          if (tid == 0) atomicAdd(&mgu_diag_glds_n, (unsigned long long)(BN * 8));
-        }
-      }
-#endif
       if constexpr (GLDS) {   // the tile of step s + NBUF - 1 into the buffer the previous step read
         constexpr int ahead = NBUF - 1;
         const int tgt = NBUF == 2 ? (par ^ 1) : (par == 0 ? 2 : par - 1);
@@ -641,7 +590,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(const IgemmDesc d,
           for (int ni = 0; ni < WNT; ++ni) acc[mi][ni] = mma_chunk<T>(a[gidx % DEPTH][mi], b[gidx % DEPTH][ni], acc[mi][ni]);
       }
     }
-      HALO_T(2);   // MFMAs of the step issued
       if constexpr (!GLDS) {
         store_b(par ^ 1);                         // the next step's weight tile (its buffer is free since the barrier above)
         if constexpr (tap + 2 < SPI) load_b(c, tap + 2);   // the tile of the step after it: (chunk, step) two steps ahead
@@ -650,8 +598,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(const IgemmDesc d,
       }
       if constexpr (NBUF == 2) par ^= 1;
       else par = par == 2 ? 0 : par + 1;
-      HALO_T(3);
-      ++st;
     });
     {
       const bool patch_done = (c + 1 == nchunks);
@@ -731,22 +677,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(const IgemmDesc d,
             }
           }
         };
-#if defined(MGU_DIAG) && MGU_DIAG == 7   // diagnostic build: no output stores (accumulators kept live)
-        {
-          float sacc = 0.f;
-#pragma unroll
-          for (int mi = 0; mi < WMT; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < WNT; ++ni)
-#pragma unroll
-              for (int rr = 0; rr < 16; ++rr) sacc += acc[mi][ni][rr], acc[mi][ni][rr] = 0.f;
-          if (sacc == 123.456f) img_out[tid] = (T)sacc;
-        }
-#else
         if (interior) store_patch(std::false_type{});
         else store_patch(std::true_type{});
         w0 = interior ? 1 : 0;
-#endif
       }
       // (plain arithmetic: `if (done) { c = 0; ++pi; } else ++c;` became an increment through a selected ADDRESS, with c and pi in scratch)
       pi += patch_done ? 1 : 0;
@@ -769,23 +702,16 @@ static hipError_t launch_halo(const IgemmDesc& d, hipStream_t s) {
   const int B = d.M / (d.H * d.W);
   const int total = tiles_x * tiles_y * B, ntn = (d.N + BN - 1) / BN;
   // patches per workgroup: keep >= ~4 workgroups per CU in the grid (2 are resident), at most 16 patches each
-  int ppb = (int)(((long)total * ntn) / (256 * 4));
-  if (ppb < 1) ppb = 1;
-  if (ppb > tun(d).halo_max_ppb) ppb = std::max(1, tun(d).halo_max_ppb);
+  const int ppb = std::min(std::max((int)(((long)total * ntn) / (256 * 4)), 1), 16);
   dim3 grid((total + ppb - 1) / ppb, ntn);
   size_t lds = (size_t)(HP + 2 * TPS * BN) * (NP * 16 + 16);
-#if !defined(MGU_HALO_NO_GLDS)
   if (NP == 8 && BN % 32 == 0 && (size_t)HP * (NP * 16 + 16) + (size_t)3 * TPS * BN * NP * 16 <= 80 * 1024)
     lds = (size_t)HP * (NP * 16 + 16) + (size_t)3 * TPS * BN * NP * 16;   // three unpadded weight buffers (the kernel's NBUF)
-#endif
-#if defined(MGU_DIAG) && MGU_DIAG == 23
-  if (getenv("MGU_DIAG_OCC1")) lds = std::max<size_t>(lds, 100 * 1024);   // timing experiment: one workgroup per CU
-#endif
   static bool attr_done[64] = {};
   hipError_t ae = ensure_dyn_lds(reinterpret_cast<const void*>(&conv3x3_halo_kernel<T, NP, TH, WAVES_M, WAVES_N, WMT, WNT, TPS>), lds, attr_done);
   if (ae != hipSuccess) return ae;
   hipLaunchKernelGGL((conv3x3_halo_kernel<T, NP, TH, WAVES_M, WAVES_N, WMT, WNT, TPS>), grid, dim3(256), lds, s, d, tiles_x,
-                     tiles_y, total, ppb, tun(d).wino_yfast ? 1 : 0);
+                     tiles_y, total, ppb);
   return hipGetLastError();
 }
 
@@ -795,7 +721,7 @@ static int halo_np(const IgemmDesc& d) {   // 16-byte pieces per pixel chunk the
   // one image in BYTES below the buffer descriptors' reach: the input offsets must stay under the out-of-image marker (0x7fff0000), the
   // interior stores under the output descriptor's num_records (0x7ffffff0) -- a store past it would be dropped silently
   if (!(d.KS == 3 && d.out_mode == 0 && d.K == 9 * d.Cp && d.ldin == d.Cp && (long)d.H * d.W * d.ldin * (long)sizeof(T) < 0x7fff0000l &&
-        (long)d.H * d.W * d.ldout * (long)sizeof(T) < 0x7ffffff0l && tun(d).use_halo))
+        (long)d.H * d.W * d.ldout * (long)sizeof(T) < 0x7ffffff0l))
     return 0;
   if (d.Cp % (8 * VEC) == 0) return 8;
   if (sizeof(T) == 2 && d.Cp % (4 * VEC) == 0) return 4;   // bf16 layers with 32 input channels
@@ -823,8 +749,7 @@ template <typename T, int NP>
 static hipError_t launch_halo_tiles(const IgemmDesc& d, hipStream_t s) {
   if (d.N > 64) return launch_halo<T, NP, 8, 2, 2, 2, 2, 1>(d, s);     // 8x16 px  x 128 ch, wave 64x64
   if (d.N > 32) return launch_halo<T, NP, 16, 4, 1, 2, 2, 1>(d, s);    // 16x16 px x 64 ch,  wave 64x64
-  if (tun(d).halo_tps3) return launch_halo<T, NP, 16, 4, 1, 2, 1, 3>(d, s);  // 16x16 px x 32 ch, wave 64x32, 3 taps per barrier
-  return launch_halo<T, NP, 16, 4, 1, 2, 1, 1>(d, s);
+  return launch_halo<T, NP, 16, 4, 1, 2, 1, 3>(d, s);                  // 16x16 px x 32 ch, wave 64x32, 3 taps per barrier
 }
 
 // does a descriptor run on the halo kernel (whose epilogue can also write the 2x2 max-pooled tensor, IgemmDesc::pool)?
@@ -840,8 +765,8 @@ const char* igemm_kernel_name(const IgemmDesc& d, int dtype) {
   }
   if (d.out_mode == 1) return convt_x3_applicable(d) ? "convt2x2_x3_kernel" : "igemm_kernel<f32> (ConvTranspose)";
   if (wino_applicable(d)) {
-    const bool wide = d.N > 32 && tun(d).wino_mode != 1;
-    if (tun(d).wino_prec && tun(d).wino_cp && (wide || tun(d).wino_cp_narrow) && (long)d.H * d.W * d.ldin * 4 < (1l << 31))
+    const bool wide = wino_wide(d);
+    if (tun(d).wino_prec && tun(d).wino_cp && (long)d.H * d.W * d.ldin * 4 < (1l << 31))
       return wide ? (wino_asm_applicable(d) ? "mgu_wino_cp2_gfx950 (asm form of wino3x3_cp_kernel<2>)" : "wino3x3_cp_kernel<2>")
                   : (wino_asm_applicable(d) ? "mgu_wino_cp1r_gfx950 (asm form of wino3x3_cp_kernel<1>)" : "wino3x3_cp_kernel<1>");
     if (tun(d).wino_prec) return wide ? "wino3x3_f32_kernel<0,1>" : "wino3x3_f32_kernel<1,1>";
@@ -888,23 +813,3 @@ hipError_t launch_igemm_bf16(const IgemmDesc& d, hipStream_t s) {
 }
 
 }  // namespace mgu
-
-#if defined(MGU_DIAG) && MGU_DIAG == 23
-extern "C" int mgu_diag_read(unsigned long long* out, int n) {
-  if (n > 4 * 256 * 4) n = 4 * 256 * 4;
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(mgu::mgu_halo_ts), (size_t)n * sizeof(unsigned long long));
-}
-#endif
-
-#if defined(MGU_DIAG) && MGU_DIAG == 50
-// checking build: (mismatch flag, 16-byte pieces compared) of the LDS-DMA weight tiles since the last call; clears both
-extern "C" int mgu_diag_glds_read(unsigned* bad, unsigned long long* n) {
-  unsigned z = 0;
-  unsigned long long zn = 0;
-  if (hipMemcpyFromSymbol(bad, HIP_SYMBOL(mgu::mgu_diag_glds_bad), sizeof(unsigned)) != hipSuccess) return -1;
-  if (hipMemcpyFromSymbol(n, HIP_SYMBOL(mgu::mgu_diag_glds_n), sizeof(unsigned long long)) != hipSuccess) return -1;
-  if (hipMemcpyToSymbol(HIP_SYMBOL(mgu::mgu_diag_glds_bad), &z, sizeof z) != hipSuccess) return -1;
-  if (hipMemcpyToSymbol(HIP_SYMBOL(mgu::mgu_diag_glds_n), &zn, sizeof zn) != hipSuccess) return -1;
-  return 0;
-}
-#endif

@@ -66,18 +66,10 @@ int mgu_create(int device_id, mgu_ctx** out) {
   auto num = [](const char* name, int dflt) { const char* v = getenv(name); return v && v[0] ? atoi(v) : dflt; };
   Tuning& t = c->tn;
   t.first_mfma = !flag("MGU_NO_FIRST_MFMA");
-  t.use_halo = !flag("MGU_NO_HALO");
-  t.halo_tps3 = !flag("MGU_HALO_TPS1");
-  t.halo_max_ppb = std::max(1, num("MGU_HALO_PPB", t.halo_max_ppb));
   t.use_wino = !flag("MGU_NO_WINOGRAD");
-  t.wino_mode = num("MGU_WINO_MODE", -1);
   t.wino_prec = num("MGU_WINO_PREC", t.wino_prec) ? 1 : 0;
   t.wino_cp = !flag("MGU_NO_WINO_CP");
-  t.wino_deep = !flag("MGU_NO_WINO_DEEP");
   t.convt_frag = !flag("MGU_NO_CONVT_FRAG");
-  t.wino_yfast = flag("MGU_WINO_YFAST");
-  t.wino_cp_narrow = num("MGU_WINO_CP_NARROW", 1) != 0;
-  t.wino_rounds = std::max(1, num("MGU_WINO_ROUNDS", 1));
   t.wino_ppb_cap = std::max(1, num("MGU_WINO_PPB_CAP", 32));
   t.wgrad_halo = !flag("MGU_NO_WGRAD_HALO");
   t.wino_wgrad = !flag("MGU_NO_WINO_WGRAD");
@@ -86,10 +78,7 @@ int mgu_create(int device_id, mgu_ctx** out) {
   t.wgrad_thin = !flag("MGU_NO_THIN_WGRAD");
   t.wino_dgrad = !flag("MGU_NO_WINO_DGRAD");
   t.gat_fused = !flag("MGU_NO_GAT_FUSED");
-  t.wino_ures = !flag("MGU_NO_WINO_URES");
-  t.wino_prio = flag("MGU_WINO_PRIO");
-  t.wino_asm = std::max(0, num("MGU_WINO_ASM", t.wino_asm));
-  t.wino_asm_narrow = num("MGU_WINO_ASM_NARROW", 1) != 0;
+  t.wino_asm = num("MGU_WINO_ASM", 1) > 0;
   *out = c;
   return MGU_OK;
 }

@@ -6,8 +6,6 @@
 // (tests/test_gpu_wino_asm.py).  The code object is loaded once per device through the module API; everything the assembly
 // does not cover (ragged sizes, statistics epilogue, odd chunk counts, missing scale / shift) stays on the C++ kernel.
 #include "common.h"
-#include <algorithm>
-#include <cstdio>
 #include <mutex>
 
 extern "C" const unsigned char mgu_wino_cp2_hsaco[];
@@ -34,46 +32,26 @@ static_assert(sizeof(WinoAsmArgs) == 120, "kernarg layout of mgu_wino_cp2_gfx950
 
 unsigned magic(unsigned d) { return d <= 1 ? 0xffffffffu : (unsigned)((1ull << 32) / d); }
 
-struct Plan {
-  int tiles_x, tiles_y, total, nblk, ppb, ngroups, per_xcd;
-};
-bool is_wide(const IgemmDesc& d) { return d.N > 32 && tun(d).wino_mode != 1; }
-Plan plan_of(const IgemmDesc& d) {
-  Plan p;
-  p.tiles_x = (d.W + 31) / 32, p.tiles_y = (d.H + 7) / 8;
-  const int B = d.M / (d.H * d.W);
-  const int nc = is_wide(d) ? 64 : 32;   // output channels of a workgroup
-  p.total = p.tiles_x * p.tiles_y * B, p.nblk = (d.N + nc - 1) / nc;
-  const int rounds = std::max(1, tun(d).wino_rounds), cap = std::max(1, tun(d).wino_ppb_cap);
-  int ppb = (int)(((long)p.total * p.nblk) / (256 * rounds));   // the C++ launcher's walk (launch_wino_cp)
-  if (ppb < 1) ppb = 1;
-  if (ppb > cap) ppb = cap;
-  p.ppb = ppb;
-  p.ngroups = (p.total + ppb - 1) / ppb;
-  p.per_xcd = (p.ngroups * p.nblk + 7) / 8;
-  return p;
-}
-
-constexpr int MAX_VARIANTS = 32;   // wino_asm = 1: the shipping kernel; n > 1: timing-only variant _v(n-1) of a GEN_WINO_VARIANTS=1 build
+// the code object's kernels: the wide one and the narrow ones of 2 and 4 chunks (32 / 64 input channels)
+const char* const kNames[3] = {"mgu_wino_cp2_gfx950", "mgu_wino_cp1r2_gfx950", "mgu_wino_cp1r4_gfx950"};
 std::mutex g_mu;
 hipModule_t g_mod[64] = {};
-hipFunction_t g_fn[64][MAX_VARIANTS + 2] = {};   // loaded functions per device (the last two: the narrow kernels), written once under
-                                                 // g_mu, immutable afterwards
+hipFunction_t g_fn[64][3] = {};   // loaded functions per device (kNames order), written once under g_mu, immutable afterwards
 }  // namespace
 
 bool wino_asm_applicable(const IgemmDesc& d) {
-  if (!tun(d).wino_asm || !tun(d).wino_prec || !tun(d).wino_cp || tun(d).wino_yfast || tun(d).wino_prio) return false;
+  if (!tun(d).wino_asm || !tun(d).wino_prec || !tun(d).wino_cp) return false;
   if (d.stat_slots) return false;   // (a missing scale / shift array is 1 / 0 in the kernels, as in the C++ epilogue)
-  if (is_wide(d)) {
+  if (wino_wide(d)) {
     if (d.N & 63) return false;
   } else {   // narrow kernels: exactly one 32-channel tile, 2 or 4 chunks (their weight pieces stay in registers), the C++ kernel's
              // two-chunk load lead and reader-side scale / shift (what launch_wino_f32 picks for these layers)
-    if (!tun(d).wino_asm_narrow || d.N != 32 || !(d.Cp == 32 || d.Cp == 64) || !tun(d).wino_cp_narrow || !tun(d).wino_deep || tun(d).wino_asm > 1) return false;
+    if (d.N != 32 || !(d.Cp == 32 || d.Cp == 64)) return false;
   }
   if ((d.H & 7) || (d.W & 31) || (d.Cp & 31) || (d.ldin & 3) || (d.ldout & 3) || (d.coff & 3)) return false;
   if (d.pool && ((d.ldpool & 3) || (d.H & 1) || (d.W & 1))) return false;
   if ((long)d.H * d.W * d.ldin * 4 >= 0x7fff0000l || (long)d.H * d.W * d.ldout * 4 >= 0x7fff0000l) return false;
-  const Plan p = plan_of(d);
+  const WinoPlan p = wino_plan(d);
   if ((long)p.total * p.tiles_x * p.tiles_y >= (1l << 32) || (long)p.ngroups * p.nblk * p.ngroups >= (1l << 32)) return false;
   return true;
 }
@@ -84,25 +62,20 @@ hipError_t launch_wino_cp_asm(const IgemmDesc& d, hipStream_t s) {
   if (e != hipSuccess) return e;
   if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
   hipFunction_t fn;
-  const bool wide = is_wide(d);
-  const int var = wide ? std::min(std::max(tun(d).wino_asm, 1), MAX_VARIANTS) - 1 : MAX_VARIANTS + (d.Cp == 64);
+  const int k = wino_wide(d) ? 0 : d.Cp == 32 ? 1 : 2;
   {
     std::lock_guard<std::mutex> lk(g_mu);
     if (!g_mod[dev]) {
       e = hipModuleLoadData(&g_mod[dev], mgu_wino_cp2_hsaco);
       if (e != hipSuccess) return e;
     }
-    if (!g_fn[dev][var]) {
-      char name[64];
-      if (!wide) snprintf(name, sizeof name, "mgu_wino_cp1r%d_gfx950", d.Cp >> 4);
-      else if (var) snprintf(name, sizeof name, "mgu_wino_cp2_gfx950_v%d", var);
-      else snprintf(name, sizeof name, "mgu_wino_cp2_gfx950");
-      e = hipModuleGetFunction(&g_fn[dev][var], g_mod[dev], name);
+    if (!g_fn[dev][k]) {
+      e = hipModuleGetFunction(&g_fn[dev][k], g_mod[dev], kNames[k]);
       if (e != hipSuccess) return e;
     }
-    fn = g_fn[dev][var];
+    fn = g_fn[dev][k];
   }
-  const Plan p = plan_of(d);
+  const WinoPlan p = wino_plan(d);
   WinoAsmArgs a;
   a.in = d.in, a.wu = d.wu, a.out = d.out + d.coff, a.scale = d.scale, a.shift = d.shift, a.pool = d.pool;
   a.H = d.H, a.W = d.W, a.ldin = d.ldin, a.ldout = d.ldout;

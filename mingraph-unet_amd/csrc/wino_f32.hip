@@ -799,36 +799,11 @@ constexpr int WINO_CP_RAWF = 8192;
 // URES (DEEP with exactly two chunks, i.e. 32 input channels): the two register sets of weight pieces hold the layer's WHOLE
 // transformed filter slice of this wave, so they are loaded once per workgroup and never again -- no weight-piece load sits in
 // the in-order memory pipe behind the halo loads and the epilogue's stores.
-#if defined(MGU_DIAG) && MGU_DIAG == 20
-// diagnostic build: phase timeline of ONE workgroup of the selected layer (-DMGU_DIAG_H=.. -DMGU_DIAG_CP=.. -DMGU_DIAG_N=..), every wave's
-// lane 0 stamping s_memtime at the phase boundaries of every patch: mgu_diag_ts[wave][patch][slot]; tools/diag_timeline.py reads it
-#ifndef MGU_DIAG_H
-#define MGU_DIAG_H 512
-#endif
-#ifndef MGU_DIAG_CP
-#define MGU_DIAG_CP 32
-#endif
-#ifndef MGU_DIAG_N
-#define MGU_DIAG_N 32
-#endif
-__device__ unsigned long long mgu_diag_ts[8][64][32];
-#define DIAG_T(slot)                                                                                                       \
-  do {                                                                                                                     \
-    if (diag_on && (threadIdx.x & 63) == 0 && pi < 64) mgu_diag_ts[threadIdx.x >> 6][pi][slot] = __builtin_readcyclecounter(); \
-  } while (0)
-#else
-#define DIAG_T(slot) do {} while (0)
-#endif
 template <int NTB, bool STATS, bool DEEP, bool URES = false>
 __global__ __launch_bounds__(512) void wino3x3_cp_kernel(const IgemmDesc d, const int tiles_x, const int tiles_y, const int total_patches,
-                        const int patches_per_block, const int ngroups, const int nitems, const int per_xcd, const int flags) {
+                        const int patches_per_block, const int ngroups, const int nitems, const int per_xcd) {
   constexpr int NWAVES = 8;
   constexpr int MT = 2;                          // both m tiles of the 8 x 32 pixel patch
-  const int yfast = flags & 1;
-  // flags & 2 (MGU_WINO_PRIO=1, A/B): static priority for the second-dispatched half of the workgroup (waves 4-7 = the jp = 1
-  // waves, each the SIMD partner of wave - 4): the younger wave loses every VALU arbitration against its partner otherwise
-  // (MI355X_MICROARCH.md, "Two waves per SIMD", item 4)
-  if ((flags & 2) && (threadIdx.x >> 8)) __builtin_amdgcn_s_setprio(1);
   constexpr int NC = 32 * NTB;                   // output channels per workgroup
   constexpr int ZP = 32;                         // exchange-buffer pitch of a tile (floats): one n tile per pass, no padding
                                                  // (32 lanes write 32 consecutive floats; the finishing 16-byte reads of
@@ -890,12 +865,12 @@ __global__ __launch_bounds__(512) void wino3x3_cp_kernel(const IgemmDesc d, cons
   unsigned hmask = 0u, hmask_next = 0u;
   auto in_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(d.in), 0, 0x7ffffff0, 0x00020000);
   const int img_bytes = d.H * d.W * d.ldin * (int)sizeof(float);   // the launcher guarantees H*W*ldin < 2^31 elements ... and bytes fit below
-  // Patch order inside an image: x fastest by default.  y fastest (MGU_WINO_YFAST=1) lets vertically adjacent patches, which
-  // share two of their ten halo rows, follow each other while those rows are still in the XCD's L2 -- measured with alternating
-  // runs on one box: 1 % SLOWER on the headline step (the HBM read volume is not what bounds these kernels).
+  // Patch order inside an image: x fastest.  (y fastest, so that vertically adjacent patches, which share two of their ten halo
+  // rows, follow each other while those rows are still in the XCD's L2, measured 1 % SLOWER on the headline step: the HBM read
+  // volume is not what bounds these kernels.)
   auto setup_patch = [&](int p, int& img, int& y0, int& x0) {
-    const int py = yfast ? p % tiles_y : (p / tiles_x) % tiles_y;
-    const int px = yfast ? (p / tiles_y) % tiles_x : p % tiles_x;
+    const int py = (p / tiles_x) % tiles_y;
+    const int px = p % tiles_x;
     img = p / (tiles_x * tiles_y);
     y0 = py * 8;
     x0 = px * 32;
@@ -930,16 +905,7 @@ __global__ __launch_bounds__(512) void wino3x3_cp_kernel(const IgemmDesc d, cons
     hmask_set[set] = hmask_next;
 #pragma unroll
     for (int i = 0; i < HR; ++i)
-#if defined(MGU_DIAG) && MGU_DIAG == 3   // diagnostic build: no halo loads
-      hreg[set][i] = f32x4{1.f, 1.f, 1.f, 1.f};
-#else
-#if defined(MGU_DIAG) && MGU_DIAG == 30   // diagnostic build (timing only): every chunk loads the channels of chunk c & 1 -- after the first
-      // pair of a pixel every halo load hits in L2: what the kernel would take if no chunk waited for an HBM miss
-      hreg[set][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, hoff[i], (c & 1) * 64, 0));
-#else
       hreg[set][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, hoff[i], c * 64, 0));
-#endif
-#endif
   };
   auto store_halo = [&](float* Hs, auto set_c) {
     constexpr int set = decltype(set_c)::value;
@@ -1057,11 +1023,7 @@ __global__ __launch_bounds__(512) void wino3x3_cp_kernel(const IgemmDesc d, cons
 #pragma unroll
   for (int nt = 0; nt < NTB; ++nt) st1[nt] = f32x4{0.f, 0.f, 0.f, 0.f}, st2[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
   int buf = 0;
-#if defined(MGU_DIAG) && MGU_DIAG == 20
-  const bool diag_on = blockIdx.x == 100 && blockIdx.y == 0 && d.H == MGU_DIAG_H && d.Cp == MGU_DIAG_CP && d.N == MGU_DIAG_N;
-#endif
   for (int pi = 0; pi < npatch; ++pi) {
-    DIAG_T(0);
     auto chunk_body = [&](const int c, auto par_c) {
       constexpr int P = decltype(par_c)::value;                  // DEEP: parity of the chunk = its register set
       using SetNext = std::integral_constant<int, DEEP ? (P ^ 1) : 0>;   // set holding chunk c + 1 (stored now, then refilled)
@@ -1075,7 +1037,6 @@ __global__ __launch_bounds__(512) void wino3x3_cp_kernel(const IgemmDesc d, cons
       //   B1 (after step 1): chunk c + 1 is complete in LDS.
       prep_next();
       lds_barrier();                                     // B0
-      if (c < 4) DIAG_T(1 + 3 * c);
       const float* Hs = smem + (buf ^ 1) * BUFSTEP;      // chunk c
       const float* Hn = smem + buf * BUFSTEP;            // chunk c + 1 (or the next patch's first)
       store_halo(smem + buf * BUFSTEP, SetNext{});
@@ -1084,18 +1045,7 @@ __global__ __launch_bounds__(512) void wino3x3_cp_kernel(const IgemmDesc d, cons
       static_for<0, 4>([&](auto st_c) {
         constexpr int st = decltype(st_c)::value;
         constexpr int jj = st >> 1, mi = st & 1, slot = st & 1;
-        if constexpr (st == 2) {
-          if (c < 4) DIAG_T(2 + 3 * c);                  // arrival at B1
-          lds_barrier();                                 // B1
-          if (c < 4) DIAG_T(3 + 3 * c);
-        }
-#if defined(MGU_DIAG) && MGU_DIAG == 11   // diagnostic build: no MFMAs in the chunk loop (operands folded into one register each)
-#pragma unroll
-        for (int nt = 0; nt < NTB; ++nt)
-#pragma unroll
-          for (int q3 = 0; q3 < 3; ++q3)
-            acc[jj][nt][mi][q3] += __uint_as_float(pc[slot][q3][0] ^ pc[slot][q3][1] ^ pc[slot][q3][2] ^ pc[slot][q3][3] ^ bx[SetCur::value][jj][nt][q3][0]);
-#else
+        if constexpr (st == 2) lds_barrier();            // B1
 #pragma unroll
         for (int nt = 0; nt < NTB; ++nt) {
           f32x16 t = acc[jj][nt][mi];
@@ -1107,22 +1057,15 @@ __global__ __launch_bounds__(512) void wino3x3_cp_kernel(const IgemmDesc d, cons
           t = mfma_bf16(pc[slot][0], bx[SetCur::value][jj][nt][0], t);
           acc[jj][nt][mi] = t;
         }
-#endif
-#if defined(MGU_DIAG) && MGU_DIAG == 10   // diagnostic build: no input transform / split in the chunk loop (pieces stay constant)
-        if constexpr (false) {
-#else
         if constexpr (RPF) {
-#endif
           // transform the raw operands of step st + 1 (read one step ago), request those of step st + 2 (the next chunk's after
           // B1: steps 2 and 3 read chunk c + 1)
           form_from(((st + 1) >> 1) & 1, (st + 1) & 1, slot ^ 1);
           if constexpr (st < 2) fetch_raw(Hs, (st + 2) >> 1, (st + 2) & 1, st & 1);
           else fetch_raw(Hn, (st - 2) >> 1, (st - 2) & 1, st & 1);
         } else {
-#if !(defined(MGU_DIAG) && MGU_DIAG == 10)
           if constexpr (st < 3) form(Hs, (st + 1) >> 1, (st + 1) & 1, slot ^ 1);
           else form(Hn, 0, 0, slot ^ 1);
-#endif
         }
         if constexpr (mi == 1 && !URES) load_bx(jj, cn, SetCur{});   // this component's pieces of the next chunk using this set
         constexpr int NM = 6 * NTB;                               // MFMAs of the step
@@ -1200,9 +1143,7 @@ __global__ __launch_bounds__(512) void wino3x3_cp_kernel(const IgemmDesc d, cons
         }
       }
     }
-    DIAG_T(13);      // main loop done (arrival at the epilogue's first barrier)
     lds_barrier();   // every wave has finished reading the consumed raw buffer, which is exchange region 0 from here on
-    DIAG_T(14);
     // Exchange regions Z[q][jp] ([4 rows i][64 tiles][32 channels] each): the column part of Z[i][q] = sum_j M[i][j] A[j][q]
     // (A^T = [1 1 1 0; 0 1 -1 -1]) is split over the two component-pair waves of a row,
     //   jp = 0 (M0, M1): q = 0: M0 + M1, q = 1: M1;      jp = 1 (M2, M3): q = 0: M2, q = 1: -M2 - M3,
@@ -1220,20 +1161,6 @@ __global__ __launch_bounds__(512) void wino3x3_cp_kernel(const IgemmDesc d, cons
     const bool top0 = jp == 0 && buf != 0;   // this wave's q = 0 share goes to the top slot (odd chunk counts only): ordinary stores
     const unsigned mz0 = lds0 + (unsigned)((jp == 0 ? buf * BUFSTEP : RAWF) + wi * 64 * ZP) * 4u;
     const unsigned mz1 = lds0 + (unsigned)((2 + jp) * RAWF + wi * 64 * ZP) * 4u - (unsigned)ZBIAS;
-#if defined(MGU_DIAG) && MGU_DIAG == 2   // diagnostic build: no inverse transform / epilogue at all
-    {
-      float sacc = 0.f;
-#pragma unroll
-      for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-        for (int nt = 0; nt < NTB; ++nt)
-#pragma unroll
-          for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sacc += acc[jj][nt][mi][r];
-      if (sacc == 123.456f) img_out[et] = sacc;
-    }
-#else
 #pragma unroll
     for (int nt = 0; nt < NTB; ++nt) {
       const int n0 = nblock * NC + nt * 32 + cq * 4;
@@ -1267,13 +1194,7 @@ __global__ __launch_bounds__(512) void wino3x3_cp_kernel(const IgemmDesc d, cons
         if (jp == 0) write_shares(std::true_type{});
         else write_shares(std::false_type{});
       }
-      if (nt == 0) DIAG_T(15);   // shares written (arrival)
       lds_barrier();
-      if (nt == 0) DIAG_T(16);
-#if defined(MGU_DIAG) && MGU_DIAG == 5   // diagnostic build: exchange writes and barriers only
-      lds_barrier();
-      continue;
-#endif
       // row part + epilogue of unit (T, cq): y(2tr, .) = Z0 + Z1 + Z2, y(2tr+1, .) = Z1 - Z2 - Z3, both output columns q
       f32x4 ya[2], yb[2];
       // all sixteen share reads of the unit in flight before the first add (the epilogue has the registers; two waves per SIMD do not
@@ -1311,11 +1232,7 @@ __global__ __launch_bounds__(512) void wino3x3_cp_kernel(const IgemmDesc d, cons
         }
       }
       const unsigned idx = (unsigned)((oy * d.W + ox) * d.ldout + n0);
-#if defined(MGU_DIAG) && MGU_DIAG == 1   // diagnostic build: the output stores only if a value is a magic number
-      if (ya[0][0] == 123.456f) {
-#else
       if (interior) {
-#endif
         // write-once data that the next layer reads after this kernel has finished: non-temporal (streaming) stores, measured
         // 1.2 % of the headline step against ordinary stores
         __builtin_nontemporal_store(ya[0], reinterpret_cast<f32x4*>(img_out + idx));
@@ -1351,11 +1268,8 @@ __global__ __launch_bounds__(512) void wino3x3_cp_kernel(const IgemmDesc d, cons
           }
         }
       }
-      if (nt == 0) DIAG_T(17);   // finishing pass issued (arrival)
       lds_barrier();   // the regions are rewritten by the next pass / region 0 receives the next raw chunk
-      if (nt == NTB - 1) DIAG_T(18);
     }
-#endif
 #pragma unroll
     for (int jj = 0; jj < 2; ++jj)
 #pragma unroll
@@ -1386,45 +1300,42 @@ __global__ __launch_bounds__(512) void wino3x3_cp_kernel(const IgemmDesc d, cons
   }
 }
 
+// One round of workgroups (one per CU is resident: 8 waves x ~200-256 registers), each walking up to wino_ppb_cap patches
+// (measured against 2-4 rounds of shorter walks: fewer pipeline prologues and no second-round tail, 0.7 % of the headline step).
+WinoPlan wino_plan(const IgemmDesc& d) {
+  WinoPlan p;
+  p.tiles_x = (d.W + 31) / 32, p.tiles_y = (d.H + 7) / 8;
+  const int B = d.M / (d.H * d.W);
+  const int nc = wino_wide(d) ? 64 : 32;   // output channels of a workgroup
+  p.total = p.tiles_x * p.tiles_y * B, p.nblk = (d.N + nc - 1) / nc;
+  p.ppb = std::min(std::max((int)(((long)p.total * p.nblk) / 256), 1), tun(d).wino_ppb_cap);
+  p.ngroups = (p.total + p.ppb - 1) / p.ppb;
+  p.per_xcd = (p.ngroups * p.nblk + 7) / 8;
+  return p;
+}
+
+int wino_grid_blocks(const IgemmDesc& d) { return 8 * wino_plan(d).per_xcd; }
+
 template <int NTB, bool STATS, bool DEEP = false, bool URES = false>
 static hipError_t launch_wino_cp(const IgemmDesc& d, hipStream_t s) {
   constexpr int NWAVES = 8;
-  const int tiles_x = (d.W + 31) / 32, tiles_y = (d.H + 7) / 8;
-  const int B = d.M / (d.H * d.W);
-  const int total = tiles_x * tiles_y * B, nblk = (d.N + 32 * NTB - 1) / (32 * NTB);
-  // one workgroup per CU is resident (registers: 8 waves x ~200-256): ONE round of 256, each walking its share of the patches
-  const int rounds = std::max(1, tun(d).wino_rounds), cap = std::max(1, tun(d).wino_ppb_cap);
-  int ppb = (int)(((long)total * nblk) / (256 * rounds));
-  if (ppb < 1) ppb = 1;
-  if (ppb > cap) ppb = cap;
-  const int ngroups = (total + ppb - 1) / ppb;
-  const int per_xcd = (ngroups * nblk + 7) / 8;
-  dim3 grid(8 * per_xcd, 1);
+  const WinoPlan p = wino_plan(d);
+  dim3 grid(8 * p.per_xcd, 1);
   if (d.stat_slots && grid.x > (unsigned)STAT_ROWS) return hipErrorInvalidValue;   // one accumulator row per workgroup (common.h)
   const size_t lds = (size_t)(5 * WINO_CP_RAWF) * sizeof(float);   // two raw buffers + three exchange regions = the CU's 160 KB
   static bool attr_done[64] = {};
   hipError_t ae = ensure_dyn_lds(reinterpret_cast<const void*>(&wino3x3_cp_kernel<NTB, STATS, DEEP, URES>), lds, attr_done);
   if (ae != hipSuccess) return ae;
-  hipLaunchKernelGGL((wino3x3_cp_kernel<NTB, STATS, DEEP, URES>), grid, dim3(64 * NWAVES), lds, s, d, tiles_x, tiles_y, total, ppb, ngroups, ngroups * nblk,
-                     per_xcd, (tun(d).wino_yfast ? 1 : 0) | (tun(d).wino_prio ? 2 : 0));
+  hipLaunchKernelGGL((wino3x3_cp_kernel<NTB, STATS, DEEP, URES>), grid, dim3(64 * NWAVES), lds, s, d, p.tiles_x, p.tiles_y, p.total,
+                     p.ppb, p.ngroups, p.ngroups * p.nblk, p.per_xcd);
   return hipGetLastError();
 }
 
 template <int MODE, int PREC>
 static hipError_t launch_wino_mode(const IgemmDesc& d, hipStream_t s) {
   constexpr int NTB = MODE == 0 ? 2 : 1, NWAVES = 8;
-  const int tiles_x = (d.W + 31) / 32, tiles_y = (d.H + 7) / 8;
-  const int B = d.M / (d.H * d.W);
-  const int total = tiles_x * tiles_y * B, nblk = (d.N + 32 * NTB - 1) / (32 * NTB);
-  // one workgroup per CU is resident: ONE round of them, each walking up to 32 patches (measured against 2-4 rounds of
-  // shorter walks: fewer pipeline prologues and no second-round tail, 0.7 % of the headline step)
-  const int rounds = std::max(1, tun(d).wino_rounds), cap = std::max(1, tun(d).wino_ppb_cap);
-  int ppb = (int)(((long)total * nblk) / (256 * rounds));
-  if (ppb < 1) ppb = 1;
-  if (ppb > cap) ppb = cap;
-  const int ngroups = (total + ppb - 1) / ppb;
-  const int per_xcd = (ngroups * nblk + 7) / 8;
-  dim3 grid(8 * per_xcd, 1);
+  const WinoPlan p = wino_plan(d);
+  dim3 grid(8 * p.per_xcd, 1);
   if (d.stat_slots && grid.x > (unsigned)STAT_ROWS) return hipErrorInvalidValue;   // one accumulator row per workgroup (common.h)
   constexpr int HSTRIDE = NWAVES * 16, HR = (340 + HSTRIDE - 1) / HSTRIDE;
   constexpr int RAWF = HR * HSTRIDE / 34 * 34 * 20 + 34 * 20;   // must match the kernel
@@ -1432,24 +1343,9 @@ static hipError_t launch_wino_mode(const IgemmDesc& d, hipStream_t s) {
   static bool attr_done[64] = {};
   hipError_t ae = ensure_dyn_lds(reinterpret_cast<const void*>(&wino3x3_f32_kernel<MODE, PREC>), lds, attr_done);
   if (ae != hipSuccess) return ae;
-  hipLaunchKernelGGL((wino3x3_f32_kernel<MODE, PREC>), grid, dim3(64 * NWAVES), lds, s, d, tiles_x, tiles_y, total, ppb, ngroups,
-                     ngroups * nblk, per_xcd);
+  hipLaunchKernelGGL((wino3x3_f32_kernel<MODE, PREC>), grid, dim3(64 * NWAVES), lds, s, d, p.tiles_x, p.tiles_y, p.total, p.ppb,
+                     p.ngroups, p.ngroups * p.nblk, p.per_xcd);
   return hipGetLastError();
-}
-
-// workgroups launch_wino_f32 starts for d (every work split uses the same formula): the rows its statistics epilogue adds into
-int wino_grid_blocks(const IgemmDesc& d) {
-  const bool wide = d.N > 32 && tun(d).wino_mode != 1;
-  const int ntb = wide ? 2 : 1;
-  const int tiles_x = (d.W + 31) / 32, tiles_y = (d.H + 7) / 8;
-  const int B = d.M / (d.H * d.W);
-  const int total = tiles_x * tiles_y * B, nblk = (d.N + 32 * ntb - 1) / (32 * ntb);
-  const int rounds = std::max(1, tun(d).wino_rounds), cap = std::max(1, tun(d).wino_ppb_cap);
-  int ppb = (int)(((long)total * nblk) / (256 * rounds));
-  if (ppb < 1) ppb = 1;
-  if (ppb > cap) ppb = cap;
-  const int ngroups = (total + ppb - 1) / ppb;
-  return 8 * ((ngroups * nblk + 7) / 8);
 }
 
 bool wino_applicable(const IgemmDesc& d) {
@@ -1458,27 +1354,21 @@ bool wino_applicable(const IgemmDesc& d) {
 }
 
 hipError_t launch_wino_f32(const IgemmDesc& d, hipStream_t s) {
-  const bool wide = d.N > 32 && tun(d).wino_mode != 1;
-  if (tun(d).wino_prec && tun(d).wino_cp && (wide || tun(d).wino_cp_narrow) &&
+  const bool wide = wino_wide(d);
+  if (tun(d).wino_prec && tun(d).wino_cp &&
       (long)d.H * d.W * d.ldin * 4 < 0x7fff0000l) {   // image bytes below the out-of-image marker offset of the buffer descriptor
-    // narrow layers: raw-operand prefetch always (RPF in the kernel) + the two-chunk load lead (DEEP) for an even chunk count; the
-    // training forward (fused statistics) keeps the one-chunk lead (DEEP + RPF + statistics spills 4 registers)
-    const bool deep = !wide && ((d.Cp >> 4) & 1) == 0 && tun(d).wino_deep && !d.stat_slots;
-    const bool ures = deep && (d.Cp >> 4) == 2 && tun(d).wino_ures;
-    if (d.stat_slots) return wide ? launch_wino_cp<2, true>(d, s) : deep ? launch_wino_cp<1, true, true>(d, s) : launch_wino_cp<1, true>(d, s);
+    // training forward (fused statistics): the one-chunk load lead (DEEP + RPF + statistics spills 4 registers)
+    if (d.stat_slots) return wide ? launch_wino_cp<2, true>(d, s) : launch_wino_cp<1, true>(d, s);
     if (wino_asm_applicable(d)) return launch_wino_cp_asm(d, s);   // wide layers and the two- / four-chunk narrow layers (wino_asm.hip)
-    if (deep && ures) return launch_wino_cp<1, false, true, true>(d, s);
-    return wide ? launch_wino_cp<2, false>(d, s) : deep ? launch_wino_cp<1, false, true>(d, s) : launch_wino_cp<1, false>(d, s);
+    if (wide) return launch_wino_cp<2, false>(d, s);
+    // narrow layers: raw-operand prefetch always (RPF in the kernel) + the two-chunk load lead (DEEP) for an even chunk count, with
+    // the weight pieces held in registers (URES) when there are exactly two chunks
+    const int nC = d.Cp >> 4;
+    if (nC & 1) return launch_wino_cp<1, false>(d, s);
+    return nC == 2 ? launch_wino_cp<1, false, true, true>(d, s) : launch_wino_cp<1, false, true>(d, s);
   }
   if (tun(d).wino_prec) return wide ? launch_wino_mode<0, 1>(d, s) : launch_wino_mode<1, 1>(d, s);
   return wide ? launch_wino_mode<0, 0>(d, s) : launch_wino_mode<1, 0>(d, s);
 }
 
 }  // namespace mgu
-
-#if defined(MGU_DIAG) && MGU_DIAG == 20
-extern "C" int mgu_diag_read(unsigned long long* out, int n) {
-  if (n > 8 * 64 * 32) n = 8 * 64 * 32;
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(mgu::mgu_diag_ts), (size_t)n * sizeof(unsigned long long));
-}
-#endif

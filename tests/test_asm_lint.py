@@ -1,7 +1,7 @@
 """The hand-scheduled Winograd assembly (csrc/asm/gen_wino_cp.py) carries no compiler-inserted waits: every s_waitcnt count and
 every wait state is the generator's.  csrc/asm/lint_wino_asm.py replays the generated stream with the machine's in-order counters;
-this test (CPU only: it needs neither a GPU nor the assembler) runs it on what the generator emits now, on the timing-only variants,
-and on deliberately broken streams -- the lint must pass the first two and catch the seeded faults."""
+this test (CPU only: it needs neither a GPU nor the assembler) runs it on what the generator emits now and on deliberately broken
+streams -- the lint must pass the first and catch the seeded faults."""
 import importlib.util
 import os
 import re
@@ -19,15 +19,9 @@ def _load(name):
     return m
 
 
-def _generate(tmp_path, variants=False):
-    out = tmp_path / ("v.s" if variants else "k.s")
-    env = dict(os.environ)
-    env.pop("GEN_WINO_DEBUG", None)
-    if variants:
-        env["GEN_WINO_VARIANTS"] = "1"
-    else:
-        env.pop("GEN_WINO_VARIANTS", None)
-    subprocess.run([sys.executable, os.path.join(ASM, "gen_wino_cp.py"), str(out)], check=True, env=env)
+def _generate(tmp_path):
+    out = tmp_path / "k.s"
+    subprocess.run([sys.executable, os.path.join(ASM, "gen_wino_cp.py"), str(out)], check=True)
     return out.read_text()
 
 
@@ -40,20 +34,6 @@ def test_generated_streams_pass_the_lint(tmp_path):
     assert len(re.findall(r"v_mfma_f32_32x32x16_bf16", text)) == 2 * (2 * 48 + 24 * 2 + 24 * 4)
     # every accumulator chain of a patch starts from the constant 0 (no clearing pass): 8 tuples in the wide kernel, 4 in a narrow one
     assert len(re.findall(r"v_mfma_f32_32x32x16_bf16 v\[\d+:\d+\], v\[\d+:\d+\], v\[\d+:\d+\], 0\n", text)) == 2 * (8 + 4 + 4)
-
-
-def test_shipping_kernels_of_a_variants_build_pass_the_lint(tmp_path):
-    lint = _load("lint_wino_asm")
-    text = _generate(tmp_path, variants=True)
-    ks = lint.kernels(text)
-    ship = {k: v for k, v in ks.items() if not re.search(r"_v\d+$", k)}
-    assert len(ship) == 3 and len(ks) > 10
-    errs = []
-    for name, lines in ship.items():
-        lint.replay(lines, errs, name)
-        for lab, body in lint.loop_bodies(lines):
-            lint.replay(body * 3, errs, f"{name} {lab}")
-    assert not errs, errs[:5]
 
 
 def test_lint_catches_seeded_faults(tmp_path):

@@ -2,7 +2,7 @@
 context is created, i.e. per mgunet.UNet): prints ms per step for every setting and round, and whether the outputs are bitwise equal
 to the first setting's.
   python tools/ab_env_step.py ROUNDS NAME=VALUE[,NAME=VALUE...] [NAME=VALUE...] ...     ("-" = no override)
-  e.g.  python tools/ab_env_step.py 3 - MGU_WINO_ASM_NARROW=0 MGU_WINO_ASM=0
+  e.g.  python tools/ab_env_step.py 3 - MGU_WINO_ASM=0
 """
 import json
 import os
