@@ -7,7 +7,10 @@ C++ kernel -- with the register map and the instruction order of the chunk loop 
 
   * 256 VGPRs per wave, no scratch: 128 accumulators | 48 weight pieces | 2 x 12 operand pieces | 32 raw operands |
     12 halo registers | 9 lane constants | 3 temporaries;
-  * a step issues the eight LDS reads of the NEXT step's raw operands first, then its twelve MFMAs with the transform and the
+  * the steps of a chunk run in the order (jj, mi) = (0,0), (1,0), (0,1), (1,1): the two components of a pair share one tile
+    column, and the jj = 1 step takes that column's inner sum from the raw registers of the jj = 0 step before it (raw_reads,
+    form_valu) -- four LDS reads and four VALU per half fewer;
+  * a step issues the LDS reads of the NEXT step's raw operands first, then its twelve MFMAs with the transform and the
     three-way split of those operands spread between them (nothing waits for a read it has just issued); the weight pieces of
     the next chunk are requested right behind the last MFMA that uses the register they land in;
   * every s_waitcnt is counted (vmcnt: halo loads, weight pieces and stores retire in order; lgkmcnt: LDS only, no scalar
@@ -198,32 +201,49 @@ def halo_stores(setn=0):
         E(f"ds_write_b128 v{VHST[i]}, {vr(HSET(setn, i), 4)}")
 
 
-def raw_reads(jp, jj, mi):
-    """the eight ds_read_b128 of step (jj, mi): returns instruction strings"""
-    cx = (S2F if jp else 0) if jj == 0 else S1F
-    cy = (S1F if jp else S2F) if jj == 0 else (S3F if jp else S2F)
-    r = []
-    for hf in range(2):
-        base = mi * 10880 + hf * 16
-        r.append(f"ds_read_b128 {vr(RAW(hf, 0), 4)}, v{VA} offset:{base + cx * 4}")
-        r.append(f"ds_read_b128 {vr(RAW(hf, 1), 4)}, v{VB} offset:{base + cx * 4}")
-        r.append(f"ds_read_b128 {vr(RAW(hf, 2), 4)}, v{VA} offset:{base + cy * 4}")
-        r.append(f"ds_read_b128 {vr(RAW(hf, 3), 4)}, v{VB} offset:{base + cy * 4}")
-    return r
+def step_jm(s):
+    """(jj, mi) of step s of a chunk: the two steps of one mi are adjacent, jj = 0 first"""
+    return s & 1, s >> 1
+
+
+def raw_reads(jp, jj, mi, hf):
+    """the ds_read_b128 of half hf of step (jj, mi): returns instruction strings.
+    The two components of a pair share one tile column (jp 0: cy = S2F for both; jp 1: cy = S1F of jj = 0 is cx of jj = 1), and
+    the jj = 0 forming leaves that column's inner sum in the c quad (form_valu).  A jj = 1 step reads only its other column, into
+    the a / b quads: two reads instead of four; the jj = 0 step of the same mi must be formed right before it."""
+    base = mi * 10880 + hf * 16
+    if jj == 1:
+        cu = S3F if jp else S1F
+        return [f"ds_read_b128 {vr(RAW(hf, 0), 4)}, v{VA} offset:{base + cu * 4}",
+                f"ds_read_b128 {vr(RAW(hf, 1), 4)}, v{VB} offset:{base + cu * 4}"]
+    cx = S2F if jp else 0
+    cy = S1F if jp else S2F
+    return [f"ds_read_b128 {vr(RAW(hf, 0), 4)}, v{VA} offset:{base + cx * 4}",
+            f"ds_read_b128 {vr(RAW(hf, 1), 4)}, v{VB} offset:{base + cx * 4}",
+            f"ds_read_b128 {vr(RAW(hf, 2), 4)}, v{VA} offset:{base + cy * 4}",
+            f"ds_read_b128 {vr(RAW(hf, 3), 4)}, v{VB} offset:{base + cy * 4}"]
 
 
 def form_valu(jp, jj, slot, hf):
-    """transform + three-way split of half hf of step (jj, .) into pc[slot]: 34 VALU, chains interleaved"""
+    """transform + three-way split of half hf of step (jj, .) into pc[slot]: 34 VALU (jj = 0) / 30 VALU (jj = 1), chains interleaved"""
     w = "-1.0" if not (jj == 1 and jp == 0) else "1.0"
     a, b, c, d = RAW(hf, 0), RAW(hf, 1), RAW(hf, 2), RAW(hf, 3)
     r = []
     # v = fma(w, fma(sgn, rb_y, ra_y), fma(sgn, rb_x, ra_x)) bit for bit: fma(sgn, b, a) as v_fmac; fma(+-1, qy, qx) = qx +- qy rounded once
     for e in range(4):
         r.append(f"v_fmac_f32_e32 v{a + e}, v{VSGN()}, v{b + e}")
-    for e in range(4):
-        r.append(f"v_fmac_f32_e32 v{c + e}, v{VSGN()}, v{d + e}")
-    for e in range(4):
-        r.append(f"v_{'add' if w == '1.0' else 'sub'}_f32_e32 v{a + e}, v{a + e}, v{c + e}")
+    if jj == 0:
+        # the c quad keeps qy: the shared column's inner sum, which the jj = 1 step of the same mi reuses
+        for e in range(4):
+            r.append(f"v_fmac_f32_e32 v{c + e}, v{VSGN()}, v{d + e}")
+        for e in range(4):
+            r.append(f"v_{'add' if w == '1.0' else 'sub'}_f32_e32 v{a + e}, v{a + e}, v{c + e}")
+    elif jp == 0:
+        for e in range(4):                # a = qx (column S1F), c = qy (S2F, shared): qx + qy
+            r.append(f"v_add_f32_e32 v{a + e}, v{a + e}, v{c + e}")
+    else:
+        for e in range(4):                # c = qx (S1F, shared), a = qy (column S3F): qx - qy, the operands in the same order
+            r.append(f"v_sub_f32_e32 v{a + e}, v{c + e}, v{a + e}")
     # pairs (0,1) -> piece dword hf*2, (2,3) -> hf*2+1;  temporaries: the b registers
     for piece in range(3):
         for p in range(2):
@@ -233,7 +253,7 @@ def form_valu(jp, jj, slot, hf):
                 r.append(f"v_and_b32_e32 v{b + e}, v{VMASK()}, v{a + e}")
             for e in range(4):
                 r.append(f"v_sub_f32_e32 v{a + e}, v{a + e}, v{b + e}")
-    assert len(r) == 34
+    assert len(r) == (34 if jj == 0 else 30)
     return r
 
 
@@ -257,30 +277,32 @@ def emit_step(jp, s):
     """Step s with the raw-operand reads spread over the MFMA gaps (at most two ds_read_b128 per gap, none waited for in the
     step it was issued in): the raw registers are two halves of four 16-byte registers (input channels 0-3 / 4-7 of the lane's
     eight); half 0 of step s + 2 is requested in gaps 7-8 of step s (its registers are free once the first half of step s + 1's
-    transform has run), half 1 of step s + 1 in gaps 0-1.  Reads of the next chunk begin in gap 7 of step 2: B1 sits in front
-    of step 2 and the read bases flip to the other buffer inside it."""
-    jj, mi, slot = s >> 1, s & 1, s & 1
+    transform has run), half 1 of step s + 1 in gaps 0-1 -- four reads per half for a jj = 0 step, two for a jj = 1 step (the
+    shared column's inner sum stays in the c quad from the jj = 0 forming, one step earlier).  Reads of the next chunk begin in
+    gap 7 of step 2: B1 sits in front of step 2 and the read bases flip to the other buffer inside it."""
+    jj, mi = step_jm(s)
+    slot = s & 1
     n1, n2 = (s + 1) & 3, (s + 2) & 3
     if s == 2:
         E("s_waitcnt lgkmcnt(0)")
         E("s_barrier")                    # B1: chunk c + 1 is complete in the other buffer
     if s == 0:
-        # this component's weight pieces (requested in step 1 of the previous chunk).  VMEM operations retire in order: younger than
+        # this component's weight pieces (requested in step 2 of the previous chunk).  VMEM operations retire in order: younger than
         # them are the other component's six pieces (step 3); this chunk's staging is issued BEHIND this wait.  The halo registers
         # (older) are covered.
         E("s_waitcnt vmcnt(6)")
-    if s == 2:
-        E("s_waitcnt vmcnt(9)")           # pieces requested in step 3 of the previous chunk; younger: 3 halo loads + 6 pieces of step 1
+    if s == 1:
+        E("s_waitcnt vmcnt(3)")           # pieces requested in step 3 of the previous chunk; younger: the 3 halo loads of step 0
     # two wait states between the v_perm that wrote the last dword of this step's low-order operand piece (tail of the previous
     # step: only its final MFMA lies between) and the first MFMA, which reads that piece
     E("s_nop 1")
     mf = mfmas(jj, mi, slot)
-    v0 = form_valu(jp, n1 >> 1, slot ^ 1, 0)
-    v1 = form_valu(jp, n1 >> 1, slot ^ 1, 1)
-    r1 = raw_reads(jp, n1 >> 1, n1 & 1)[4:8]        # half 1 of the next step
-    r2 = raw_reads(jp, n2 >> 1, n2 & 1)[0:4]        # half 0 of the step after it
+    v0 = form_valu(jp, step_jm(n1)[0], slot ^ 1, 0)
+    v1 = form_valu(jp, step_jm(n1)[0], slot ^ 1, 1)
+    r1 = raw_reads(jp, *step_jm(n1), 1)            # half 1 of the next step
+    r2 = raw_reads(jp, *step_jm(n2), 0)            # half 0 of the step after it
     wl = {}
-    if mi == 1:
+    if mi == 1:                           # steps 2 (jj = 0) and 3 (jj = 1): the last reads of this component's pieces in the chunk
         wl = {1: [weight_load(jj, 0, 2)], 4: [weight_load(jj, 0, 1)], 5: [weight_load(jj, 0, 0)],
               7: [weight_load(jj, 1, 2)], 10: [weight_load(jj, 1, 1)], 11: [weight_load(jj, 1, 0)]}
     def take(lst, n):
@@ -300,8 +322,8 @@ def emit_step(jp, s):
             f"s_cmp_eq_u32 s{S_LC}, 0", f"s_addc_u32 s{S_LP}, s{S_LP}, 0", f"s_lshl_b32 s{S_LC64}, s{S_LC}, 6"])
         extra.setdefault(3, []).extend([f"v_xor_b32_e32 v{VHST[i]}, 0x{BUFX:x}, v{VHST[i]}" for i in range(3)])
     a0, a1 = (2, 6), (7, 10)              # gap ranges of the two transform halves
-    per0 = -(-34 // (a0[1] - a0[0] + 1))
-    per1 = -(-34 // (a1[1] - a1[0] + 1))
+    per0 = -(-len(v0) // (a0[1] - a0[0] + 1))
+    per1 = -(-len(v1) // (a1[1] - a1[0] + 1))
     nlds = 0                              # LDS operations issued in this step so far (all younger than half 0's reads)
     for k in range(12):
         E(mf[k])
@@ -389,17 +411,18 @@ def emit_finish_math(Z, q, SCq, SHq):
 
 
 def emit_epilogue(jp):
-    # free registers: the second operand slot (v188..v199) and raw half 1 (v216..v231); raw half 0 holds the next patch's
-    # first reads (spread schedule) and stays untouched
+    # free registers: the second operand slot (v188..v199), the d quads of both raw halves (v212..v215, v228..v231) and the a / b
+    # quads of raw half 1 (v216..v223).  The a / b quads of raw half 0 receive the next patch's first reads (spread schedule) and the
+    # c quads hold the inner sums of its step 0 that its step 1 reuses (raw_reads): they stay untouched
     E0 = 188
-    CQ, VT = 224, 225
+    CQ, VT = 212, 213
     VZ0, VZ1, VOUT, VPOOL = E0 + 0, E0 + 1, E0 + 2, E0 + 3
     e0, e1, e2, e3 = E0 + 8, E0 + 9, E0 + 10, E0 + 11
     TMP = [216 + i for i in range(4)] * 2
     # per-channel scale / shift of the FINISHING unit's channel quad, both n tiles (reader side: two of the four shares are then plain
     # copies of the accumulators and the other two one add / subtract -- 32 instead of 96 VALU per n tile in the write phase, 16 fma in
     # the finishing pass); e0..e3 are dead once the addresses are formed
-    SC4 = [E0 + 4, 226]
+    SC4 = [E0 + 4, 228]
     SH4 = [e0, 220]
     E("s_nop 7")
     E("s_nop 7")
@@ -567,7 +590,8 @@ def mfmas_n(jj, mi, slot, c):
 
 
 def emit_step_n(jp, s, c):
-    jj, mi, slot = s >> 1, s & 1, s & 1
+    jj, mi = step_jm(s)
+    slot = s & 1
     n1, n2 = (s + 1) & 3, (s + 2) & 3
     if s == 2:
         E("s_waitcnt lgkmcnt(0)")
@@ -575,10 +599,11 @@ def emit_step_n(jp, s, c):
     E("s_nop 1")                          # the previous step ends with the v_perm that writes this step's low-order operand piece, and the
     #                                       first MFMA reads that piece: two wait states between a VALU write and an MFMA read of it
     mf = mfmas_n(jj, mi, slot, c)
-    v0 = form_valu(jp, n1 >> 1, slot ^ 1, 0)
-    v1 = form_valu(jp, n1 >> 1, slot ^ 1, 1)
-    r1 = raw_reads(jp, n1 >> 1, n1 & 1)[4:8]
-    r2 = raw_reads(jp, n2 >> 1, n2 & 1)[0:4]
+    v0 = form_valu(jp, step_jm(n1)[0], slot ^ 1, 0)
+    v1 = form_valu(jp, step_jm(n1)[0], slot ^ 1, 1)
+    r1 = raw_reads(jp, *step_jm(n1), 1)
+    r2 = raw_reads(jp, *step_jm(n2), 0)
+    per0, per1 = -(-len(v0) // 2), -(-len(v1) // 3)
     extra = {}
     if s == 0:
         hs = (c + 1) & 1                  # the set holding chunk c + 1; it is refilled with chunk c + 3
@@ -601,12 +626,12 @@ def emit_step_n(jp, s, c):
             E(x)
             nlds += x.startswith("ds_")
         if k in (0, 1):
+            nlds += min(2, len(r1))
             take(r1, 2)
-            nlds += 2
         if k == 1:
             E(f"s_waitcnt lgkmcnt({nlds})")   # half 0 (requested in the previous step); everything issued in this step may be in flight
         if k in (1, 2):
-            take(v0, 17)
+            take(v0, per0)
         if k == 3:
             E("s_waitcnt lgkmcnt(0)")
             if s == 2:
@@ -615,7 +640,7 @@ def emit_step_n(jp, s, c):
         if k in (3, 4):
             take(r2, 2)
         if k >= 3:
-            take(v1, 12)
+            take(v1, per1)
     assert not v0 and not v1 and not r1 and not r2
 
 
@@ -634,11 +659,13 @@ def emit_chunk_n(jp, c):
 
 
 def emit_epilogue_n(jp):
+    # free registers as in emit_epilogue: the c quads of the raw halves (v208..v211, v224..v227) carry the next patch's step 0 inner
+    # sums into its step 1
     CQ, VT = 228, 229
     VZ0, VZ1, VOUT, VPOOL = 188, 189, 190, 191
     e0, e1, e2, e3 = 192, 193, 194, 195
-    SC4, SH4 = 196, 216
-    TMP = [220 + i for i in range(8)]
+    SC4, SH4 = 196, 212
+    TMP = [216 + i for i in range(8)]
     E("s_nop 7")
     E("s_nop 7")
     E("s_nop 7")
@@ -979,13 +1006,13 @@ def emit_prologue():
 
 def emit_first_form(jp):
     """step 0 of the first chunk (no MFMAs to hide behind)"""
-    for r in raw_reads(jp, 0, 0):
+    for r in raw_reads(jp, 0, 0, 0) + raw_reads(jp, 0, 0, 1):
         E(r)
     E("s_waitcnt lgkmcnt(0)")
     for hf in range(2):
         for x in form_valu(jp, 0, 0, hf):
             E(x)
-    for r in raw_reads(jp, 0, 1)[0:4]:
+    for r in raw_reads(jp, *step_jm(1), 0):
         E(r)
 
 

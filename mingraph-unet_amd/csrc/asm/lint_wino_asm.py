@@ -10,7 +10,11 @@ in-order counters and fails on:
   * an MFMA that reads a VGPR written by a VALU instruction fewer than 2 wait states earlier;
   * a non-MFMA read of an MFMA result fewer than 18 wait states after the MFMA that wrote it;
   * a VALU write of the data registers of a 16-byte LDS / buffer store in the very next instruction;
-  * an LDS add-TID store directly behind the s_mov that wrote M0; v_readfirstlane directly behind the VALU write of its source.
+  * an LDS add-TID store directly behind the s_mov that wrote M0; v_readfirstlane directly behind the VALU write of its source;
+  * a transform's outer sum (v_add_f32 / v_sub_f32 of an inner sum) whose other operand is no longer an inner sum, or is the inner
+    sum of an older read base: the jj = 1 forming takes the shared tile column's inner sum from the registers the jj = 0 forming
+    left it in, and nothing may overwrite them in between (the model tracks what each register holds: an LDS read, an inner sum
+    v_fmac_f32 of two of them, or anything else).
 Used by tests/test_asm_lint.py (CPU) and runnable by hand:  lint_wino_asm.py FILE.s
 """
 import re
@@ -110,6 +114,8 @@ def replay(stream, errors, where, prime=()):
     mfma_age = {}                   # reg -> wait states since an MFMA wrote it
     prev = None
     m0_fresh = False
+    held = {}                       # reg -> ("lds", version of the address register) / ("sum", version) / ("other", writer text)
+    writes = {}                     # reg -> number of writes so far (the version of a read base)
 
     def age(n):
         for d in (valu_age, mfma_age):
@@ -173,6 +179,14 @@ def replay(stream, errors, where, prime=()):
             errors.append(f"{where}: `{text}` directly behind the write of M0")
         if kind == "readlane" and any(valu_age.get(r, 99) < 1 for r in src):
             errors.append(f"{where}: `{text}` directly behind the VALU write of its source")
+        if op in ("v_add_f32_e32", "v_sub_f32_e32"):
+            hs = [held.get(r) for a in args[1:3] for r in sorted(regs(a))]
+            if len(hs) == 2 and any(h and h[0] == "sum" for h in hs):
+                if hs[0] and hs[1] and hs[0] != hs[1]:
+                    o = hs[1] if hs[0][0] == "sum" else hs[0]
+                    why = f"holds what `{o[1]}` wrote" if o[0] == "other" else \
+                          "holds an LDS read, not an inner sum" if o[0] == "lds" else "holds an inner sum of another read base"
+                    errors.append(f"{where}: `{text}` combines an inner sum with a register that {why}")
         age(1)
         if kind == "valu":
             for r in dst:
@@ -182,6 +196,19 @@ def replay(stream, errors, where, prime=()):
             for r in dst:
                 mfma_age[r] = 0
                 valu_age.pop(r, None)
+        if kind == "lds_load":
+            ver = min(writes.get(r, 0) for r in src) if src else 0
+            for r in dst:
+                held[r] = ("lds", ver)
+        elif op == "v_fmac_f32_e32":
+            for r in dst:                # the inner sum of a transform: the LDS read in the accumulator register +- its partner
+                h = held.get(r, ("",))
+                held[r] = ("sum", h[1] if h[0] == "lds" else None)
+        else:
+            for r in dst:
+                held[r] = ("other", text)
+        for r in dst:
+            writes[r] = writes.get(r, 0) + 1
         if kind == "vm_load":
             vm.append((dst, text))
         elif kind == "vm_store":

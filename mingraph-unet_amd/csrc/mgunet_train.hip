@@ -186,8 +186,9 @@ int conv_dgrad(Bwd& w, const Layer& L, const float* dz, float* out, int ldout) {
     // record under the name of the kernel family the dispatcher will pick (the same one as a forward conv of this shape)
     const std::string fam = std::string(igemm_kernel_name(d, 0));
     const char* label = "igemm/halo (dgrad)";
-    if (fam == "wino3x3_cp_kernel<2>") label = "wino3x3_cp_kernel<2> (dgrad)";
-    else if (fam == "wino3x3_cp_kernel<1>") label = "wino3x3_cp_kernel<1> (dgrad)";
+    // (the assembly forms, mgu_wino_cp2_gfx950 and mgu_wino_cp1r2/4_gfx950, count with the C++ kernel they replace)
+    if (fam == "wino3x3_cp_kernel<2>" || fam.rfind("mgu_wino_cp2_", 0) == 0) label = "wino3x3_cp_kernel<2> (dgrad)";
+    else if (fam == "wino3x3_cp_kernel<1>" || fam.rfind("mgu_wino_cp1r", 0) == 0) label = "wino3x3_cp_kernel<1> (dgrad)";
     else if (wn) label = c->tn.wino_prec ? "wino3x3_f32_kernel<*,1> (dgrad)" : "wino3x3_f32_kernel<*,0> (dgrad)";
     ProfScope ps(c, w.s, label, alg, mfma, wn && c->tn.wino_prec ? 1 : 0);
     HIPCHK(c, launch_igemm_f32(d, w.s));
