@@ -3,8 +3,8 @@
 // caller-provided tensors.  They exist so that every backward kernel can be checked in isolation against a float64
 // reference on fixed (x, dz) -- where nothing is ill-conditioned -- instead of only through a whole train step whose
 // BatchNorm + ReLU + MaxPool chain amplifies rounding (tests/test_gpu_backward_kernels.py).
-// Kernel selection follows the context's switches (MGU_NO_WINO_WGRAD, MGU_NO_WGRAD_HALO, MGU_NO_THIN_WGRAD,
-// MGU_NO_WINO_DGRAD, MGU_NO_WINOGRAD read at mgu_create), so a test reaches every variant.
+// Kernel selection is the launchers' own (pick_conv, pick_wgrad), on the context's switches (MGU_NO_WINO_WGRAD, MGU_NO_WGRAD_HALO,
+// MGU_NO_THIN_WGRAD, MGU_NO_WINO_DGRAD, MGU_NO_WINOGRAD, ... read at mgu_create), so a test reaches every variant.
 #include <algorithm>
 
 #include "ctx.h"
@@ -98,7 +98,7 @@ int mgu_conv2d_dgrad_nhwc(mgu_ctx* c, const void* dz_dev, const void* w_oihw_dev
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)hip_stream;
   const int Cop = rup(Cout, 4), Kd = ksize * ksize * Cop, Kpd = rup(Kd, 32);
-  const bool wino = c->tn.wino_dgrad && c->tn.use_wino && ksize == 3 && Cop % 16 == 0;
+  const bool wino = wino_dgrad_layer(c->tn, ksize, Cop);
   Scratch sc;
   int rc = get_scratch(c, 0, (size_t)rup(Cin, 128) * Kpd, wino ? wino_u_floats(Cin, Cop) : 0, 64, &sc);
   if (rc) return rc;
@@ -110,13 +110,14 @@ int mgu_conv2d_dgrad_nhwc(mgu_ctx* c, const void* dz_dev, const void* w_oihw_dev
   d.Cp = Cop, d.ldin = Cop, d.KS = ksize, d.K = Kd, d.Kp = Kpd;
   d.N = Cin, d.ldout = ld_out;
   if (wino) d.wu = sc.wug;
-  if (wino_applicable(d)) {
+  const ConvKernel k = pick_conv(d, 0);
+  if (conv_is_wino(k)) {
     HIPCHK(c, launch_pack_wino_w((const float*)w_oihw_dev, sc.wug, Cin, Cout, Cop, 1, c->tn.wino_prec, s));
   } else {
     HIPCHK(c, hipMemsetAsync(sc.dgp, 0, (size_t)rup(Cin, 128) * Kpd * sizeof(float), s));   // panel rows are padded to 128
     HIPCHK(c, launch_pack_dgrad_w((const float*)w_oihw_dev, sc.dgp, Cout, Cin, Cop, ksize, Kpd, s));
   }
-  HIPCHK(c, launch_igemm_f32(d, s));
+  HIPCHK(c, launch_conv(d, k, 0, s));
   return MGU_OK;
 }
 
@@ -168,14 +169,14 @@ int mgu_conv_transpose2x2_dgrad_nhwc(mgu_ctx* c, const void* dout_dev, int ld_d,
   q.ldin = ld_d;
   q.KS = 2, q.K = Kt, q.Kp = Kpt, q.N = Cin, q.ldout = Cin, q.Hout = 2 * H, q.Wout = 2 * W;
   q.wu = sc.dgp;
-  if (c->tn.convt_dgrad_x3 && convt_x3_dgrad_applicable(q)) {   // the forward layer's three-piece kernel in its gather mode
+  const ConvKernel k = pick_conv(q, 0);
+  if (k == ConvKernel::ConvtX3Dgrad) {   // the forward layer's three-piece kernel in its gather mode
     HIPCHK(c, launch_pack_convt_x3_dgrad((const float*)w_iohw_dev, sc.dgp, Cin, Cout, s));
   } else {
-    q.wu = nullptr;
     HIPCHK(c, hipMemsetAsync(sc.dgp, 0, (size_t)rup(Cin, 128) * Kpt * sizeof(float), s));
     HIPCHK(c, launch_pack_convt_dgrad_w((const float*)w_iohw_dev, sc.dgp, Cin, Cout, Kpt, s));
   }
-  HIPCHK(c, launch_igemm_f32(q, s));
+  HIPCHK(c, launch_conv(q, k, 0, s));
   return MGU_OK;
 }
 

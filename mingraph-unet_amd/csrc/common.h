@@ -16,7 +16,8 @@ namespace mgu {
 //             -> out[((img*Hout + 2y+dy)*Wout + 2x+dx)*ldout + coff + co]
 // ---------------------------------------------------------------------------------------------
 // Kernel-selection switches of ONE context (mgu_ctx::tn, filled from the MGU_* environment in mgu_create).  They ride in
-// the launch descriptors, so two contexts of a process never see each other's settings.
+// the launch descriptors, so two contexts of a process never see each other's settings.  The convolution switches are read
+// only by the picks (pick_conv, pick_wgrad) and by the layer-level predicates next to pick_conv that size weight forms.
 struct Tuning {
   bool first_mfma = true;   // MGU_NO_FIRST_MFMA=1: the first convolution on the VALU kernel (conv3x3_first_kernel) instead of the matrix cores (A/B)
   bool use_wino = true;     // MGU_NO_WINOGRAD=1: direct kernels for the fp32 3x3 layers
@@ -74,7 +75,45 @@ struct IgemmDesc {
 };
 
 inline const Tuning& tun(const IgemmDesc& d) { return d.tn ? *d.tn : default_tuning(); }
-hipError_t launch_igemm_f32(const IgemmDesc& d, hipStream_t s);
+// The kernel a convolution descriptor runs on.  pick_conv makes the choice once (it alone reads the conv switches of Tuning, through
+// the descriptor-level *_applicable tests in igemm.hip); the launch, the profiling label and cost, the fused epilogues and the weight
+// form a caller packs all follow from the returned value.
+enum class ConvKernel {
+  None,                                       // no kernel takes the descriptor: the launch returns hipErrorInvalidValue
+  WinoAsmWide, WinoAsmCp1r2, WinoAsmCp1r4,    // mgu_wino_cp2 / cp1r2 / cp1r4_gfx950 (wino_asm.hip)
+  WinoCp2, WinoCp1, WinoCp2Stats, WinoCp1Stats,   // wino3x3_cp_kernel<2|1, STATS> (wino_f32.hip)
+  WinoF32Wide, WinoF32Narrow,                 // wino3x3_f32_kernel<0|1, 0>: fp32 MFMA operands (MGU_WINO_PREC=0)
+  WinoX3Wide, WinoX3Narrow,                   // wino3x3_f32_kernel<0|1, 1>: three-piece bf16 operands
+  HaloF32, HaloBf16Np8, HaloBf16Np4,          // conv3x3_halo_kernel
+  TilesF32, TilesBf16,                        // igemm_kernel (KS, out_mode from the descriptor)
+  ConvtX3, ConvtBf16f, ConvtX3Dgrad,          // convt2x2_x3_kernel, convt2x2_bf16_kernel, convt2x2_x3_kernel in its gather mode
+};
+ConvKernel pick_conv(const IgemmDesc& d, int dtype);   // dtype: 0 = fp32, 1 = bf16 storage (in / w / out point to bf16, sizes in elements)
+hipError_t launch_conv(const IgemmDesc& d, ConvKernel k, int dtype, hipStream_t s);   // k = pick_conv(d, dtype)
+inline hipError_t launch_igemm_f32(const IgemmDesc& d, hipStream_t s) { return launch_conv(d, pick_conv(d, 0), 0, s); }
+inline hipError_t launch_igemm_bf16(const IgemmDesc& d, hipStream_t s) { return launch_conv(d, pick_conv(d, 1), 1, s); }
+const char* conv_kernel_name(ConvKernel k, const IgemmDesc& d);   // profiling label of a forward launch
+const char* conv_dgrad_name(ConvKernel k, const IgemmDesc& d);    // ... of a data-gradient launch
+struct ConvCost {
+  double mfma;   // FLOPs issued on the matrix pipe
+  int pipe;      // 0 = fp32 MFMA, 1 = bf16 MFMA
+};
+ConvCost conv_cost(ConvKernel k, const IgemmDesc& d);
+inline bool conv_is_wino(ConvKernel k) { return k >= ConvKernel::WinoAsmWide && k <= ConvKernel::WinoX3Narrow; }
+inline bool conv_fuses_pool(ConvKernel k) {   // the epilogue can also write the 2x2 max-pooled tensor (IgemmDesc::pool)
+  return conv_is_wino(k) || (k >= ConvKernel::HaloF32 && k <= ConvKernel::HaloBf16Np4);
+}
+inline bool conv_reads_panel(ConvKernel k) {   // the kernel reads the direct panel d.w (the others read d.wu)
+  return !conv_is_wino(k) && k != ConvKernel::ConvtX3 && k != ConvKernel::ConvtBf16f && k != ConvKernel::ConvtX3Dgrad;
+}
+// Layer-level forms of the same choice, for the places that size or pack a weight form before a descriptor exists: the layer's
+// shape and switches admit the kernel (the descriptor-level test in pick_conv checks the rest; a caller that holds no such form
+// leaves d.wu null)
+bool wino_layer(const Tuning& t, int KS, int Cp);             // fp32 3x3 conv on the Winograd kernels (U: launch_pack_wino_w)
+bool wino_dgrad_layer(const Tuning& t, int KS, int Cop);      // its data gradient too (Cop = Cout rounded up to 4)
+bool convt_x3_layer(const Tuning& t, int Cin, int Cout);      // fp32 ConvTranspose on convt2x2_x3_kernel (launch_pack_convt_x3)
+bool convt_x3_dgrad_layer(const Tuning& t, int Cin, int Cout);   // its data gradient too (launch_pack_convt_x3_dgrad)
+bool convt_bf16f_layer(const Tuning& t, int Cin, int Cout);   // bf16-storage ConvTranspose on convt2x2_bf16_kernel
 // wino_f32.hip: work split of the Winograd kernels.  8 x 32 pixel patches; a workgroup covers 64 output channels of a wide layer
 // (N > 32), 32 of a narrow one, and walks ppb patches; item (n block, patch group) of XCD x is x * per_xcd + (workgroup / 8)
 inline bool wino_wide(const IgemmDesc& d) { return d.N > 32; }
@@ -83,26 +122,19 @@ struct WinoPlan {
 };
 WinoPlan wino_plan(const IgemmDesc& d);
 int wino_grid_blocks(const IgemmDesc& d);   // workgroups of the Winograd launch for d (= accumulator rows of its statistics)
-bool halo_pool_fusable(const IgemmDesc& d, int dtype);   // the halo conv kernel will run: MaxPool2d(2) can ride in its epilogue
-hipError_t launch_igemm_bf16(const IgemmDesc& d, hipStream_t s);
-const char* igemm_kernel_name(const IgemmDesc& d, int dtype);
 // convt_x3.hip: fp32 ConvTranspose2d(k2,s2) on the bf16 matrix cores with exact three-way operand splits (IgemmDesc::wu =
 // fragment-ordered weight pieces)
 size_t convt_x3_floats(int Cin, int Cout);
 hipError_t launch_pack_convt_x3(const float* w, float* Wx, int Cin, int Cout, hipStream_t s);
-bool convt_x3_applicable(const IgemmDesc& d);
 hipError_t launch_convt_x3(const IgemmDesc& d, hipStream_t s);
 // convt_bf16.hip: the bf16-storage ConvTranspose2d(k2,s2) on fragment-ordered bf16 weights (IgemmDesc::wu), 16-byte transposed stores
 size_t convt_bf16f_floats(int Cin, int Cout);
 hipError_t launch_pack_convt_bf16f(const float* w, float* Wf, int Cin, int Cout, hipStream_t s);
-bool convt_bf16f_applicable(const IgemmDesc& d);
 hipError_t launch_convt_bf16f(const IgemmDesc& d, hipStream_t s);
 // the same kernel as the layer's data gradient (KS = 2 gather descriptors whose d.wu holds launch_pack_convt_x3_dgrad's panel)
 size_t convt_x3_dgrad_floats(int Cin, int Cout);
 hipError_t launch_pack_convt_x3_dgrad(const float* w, float* Wx, int Cin, int Cout, hipStream_t s);
-bool convt_x3_dgrad_applicable(const IgemmDesc& d);
 hipError_t launch_convt_x3_dgrad(const IgemmDesc& d, hipStream_t s);
-  // the kernel family launch_igemm_* will pick (profiling records)  // in / w / out point to bf16, sizes in elements
 // elementwise.hip: first convolution (<= 4 input channels on the packed NHWC4 input), VALU + scalar-cache weights
 hipError_t launch_pack_first_w(const float* w, float* wf, int Cout, int Cin, hipStream_t s);
 // first_mfma.hip: the same layer on the bf16 matrix cores (Cin <= 3, Cout == 32)
@@ -142,11 +174,9 @@ struct WinoPackBatch {
 };
 bool wino_pack_batch_prepare(WinoPackBatch& b);   // fills Np / blk0 / total_blocks; false if an item cannot be packed
 hipError_t launch_pack_wino_w_multi(const WinoPackBatch* batch_dev, unsigned total_blocks, hipStream_t s);
-bool wino_applicable(const IgemmDesc& d);
-hipError_t launch_wino_f32(const IgemmDesc& d, hipStream_t s);
-// wino_asm.hip: the assembly form of wino3x3_cp_kernel<2> (bitwise equal results)
-bool wino_asm_applicable(const IgemmDesc& d);
-hipError_t launch_wino_cp_asm(const IgemmDesc& d, hipStream_t s);
+hipError_t launch_wino_f32(const IgemmDesc& d, ConvKernel k, hipStream_t s);   // k: one of the C++ Winograd kernels
+// wino_asm.hip: the assembly forms of wino3x3_cp_kernel<2> and <1> (bitwise equal results; k: one of the WinoAsm* kernels)
+hipError_t launch_wino_cp_asm(const IgemmDesc& d, ConvKernel k, hipStream_t s);
 
 // wgrad_f32.hip:  Dw[n][k] += sum_m Z[m][n] * A(m,k)   (A = the forward kernels' im2col gather)
 struct WgradDesc {
@@ -166,12 +196,26 @@ struct WgradDesc {
   int rows_per_split;  // set by the launcher
 };
 inline const Tuning& tun(const WgradDesc& d) { return d.tn ? *d.tn : default_tuning(); }
+// The weight-gradient kernel of a descriptor, picked once (it alone reads the weight-gradient switches of Tuning): the launch and
+// the profiling label and cost follow from it
+enum class WgradKernel {
+  Thin,     // wgrad_thin.hip: the first 3x3 conv (Cin 3) and the 1x1 head
+  WinoX3,   // wino_wgrad_f32_kernel<.., X3 = true>: three-piece bf16 products
+  Wino,     // wino_wgrad_f32_kernel<.., X3 = false>: fp32 MFMA
+  Halo,     // wgrad3x3_halo_f32_kernel
+  Tiles,    // the generic tile kernels
+};
+WgradKernel pick_wgrad(const WgradDesc& d);
+const char* wgrad_kernel_name(WgradKernel k);
+struct WgradCost {
+  double mfma;   // FLOPs issued on the matrix pipe for `alg` algorithmic FLOPs
+  int pipe;      // 0 = fp32 MFMA, 1 = bf16 MFMA, -1 = none
+};
+WgradCost wgrad_cost(WgradKernel k, double alg);
 hipError_t launch_wgrad_f32(WgradDesc& d, hipStream_t s);
-// wino_wgrad_f32.hip: Winograd F(3x3,2x2) weight gradient (Cp % 64 == 0, N % 64 == 0); same partial-panel output as the halo kernel
-bool wino_wgrad_applicable(const WgradDesc& d);
-hipError_t launch_wino_wgrad_f32(WgradDesc& d, hipStream_t s);
+// wino_wgrad_f32.hip: Winograd F(3x3,2x2) weight gradient (Cp % 32 == 0, N % 32 == 0); same partial-panel output as the halo kernel
+hipError_t launch_wino_wgrad_f32(WgradDesc& d, bool x3, hipStream_t s);
 // wgrad_thin.hip: the first 3x3 conv (Cin 3) and the 1x1 head: HBM-bound streaming kernels, same partial-panel output
-bool wgrad_thin_applicable(const WgradDesc& d);
 hipError_t launch_wgrad_thin(WgradDesc& d, hipStream_t s);
 
 // train_kernels.hip

@@ -185,12 +185,6 @@ hipError_t launch_pack_convt_bf16f(const float* w, float* Wf, int Cin, int Cout,
 }
 
 // d: the ConvTranspose descriptor of the bf16 mode (in / out point to bf16; d.wu = launch_pack_convt_bf16f's fragments)
-bool convt_bf16f_applicable(const IgemmDesc& d) {
-  return d.out_mode == 1 && d.wu && d.KS == 1 && d.K == d.Cp && (d.Cp & 63) == 0 && (d.ct_cout & 31) == 0 && d.N == 4 * d.ct_cout &&
-         (d.ldin & 7) == 0 && (d.ldout & 7) == 0 && (d.coff & 7) == 0 && !d.scale && !d.relu && !d.split_n && tun(d).convt_frag &&
-         (9l * 128 + 8l * d.Wout) * d.ldout < (1l << 31);   // the output pixels of a tile's 128 rows span < 2^31 elements
-}
-
 hipError_t launch_convt_bf16f(const IgemmDesc& d, hipStream_t s) {
   const int mtiles = (d.M + 127) / 128, ntn = d.N / 128;
   const int nb = mtiles * ntn;

@@ -291,12 +291,6 @@ hipError_t launch_pack_convt_x3_dgrad(const float* w, float* Wx, int Cin, int Co
 
 // d: the KS = 2 gather descriptor of the generic path (in = dout + c_off with pitch ldin, Cp = the layer's Cout, N = the layer's Cin,
 // H x W the input grid, Hout x Wout the grid of dout), d.wu = launch_pack_convt_x3_dgrad's panel
-bool convt_x3_dgrad_applicable(const IgemmDesc& d) {
-  return d.KS == 2 && d.wu && d.out_mode == 0 && (d.Cp & 31) == 0 && d.K == 4 * d.Cp && (d.N & 63) == 0 && (d.ldin & 3) == 0 && !d.scale &&
-         !d.shift && !d.relu && !d.split_n && !d.pool && tun(d).wino_prec != 0 && (long)d.M * d.ldout < (1l << 31) &&
-         (long)d.Hout * d.Wout * d.ldin < (1l << 31);
-}
-
 hipError_t launch_convt_x3_dgrad(const IgemmDesc& d, hipStream_t s) {
   const bool wide = (d.N & 127) == 0;
   const int mtiles = (d.M + 127) / 128, ntn = d.N / (wide ? 128 : 64);
@@ -316,12 +310,6 @@ hipError_t launch_pack_convt_x3(const float* w, float* Wx, int Cin, int Cout, hi
   hipLaunchKernelGGL(pack_convt_x3_kernel, dim3((unsigned)std::min<int64_t>(4096, ((int64_t)Cin * Cout * 4 + 255) / 256)), dim3(256), 0, s, w, reinterpret_cast<uint16_t*>(Wx), Cin,
                      Cout);
   return hipGetLastError();
-}
-
-bool convt_x3_applicable(const IgemmDesc& d) {
-  return d.out_mode == 1 && d.wu && d.KS == 1 && d.K == d.Cp && (d.Cp & 31) == 0 && (d.ct_cout & 31) == 0 && d.N == 4 * d.ct_cout &&
-         (d.ldin & 3) == 0 && !d.scale && !d.relu && !d.split_n && tun(d).wino_prec != 0 &&
-         (9l * 128 + 8l * d.Wout) * d.ldout < (1l << 31);   // the output pixels of a tile's 128 rows span < 2^31 elements
 }
 
 hipError_t launch_convt_x3(const IgemmDesc& d, hipStream_t s) {

@@ -752,65 +752,158 @@ static hipError_t launch_halo_tiles(const IgemmDesc& d, hipStream_t s) {
   return launch_halo<T, NP, 16, 4, 1, 2, 1, 3>(d, s);                  // 16x16 px x 32 ch, wave 64x32, 3 taps per barrier
 }
 
-// does a descriptor run on the halo kernel (whose epilogue can also write the 2x2 max-pooled tensor, IgemmDesc::pool)?
-bool halo_pool_fusable(const IgemmDesc& d, int dtype) {
-  if (d.out_mode != 0 || d.split_n) return false;
-  return dtype == 0 ? (!wino_applicable(d) && halo_np<float>(d) == 8) : halo_np<__bf16>(d) != 0;
+// ---- kernel choice -----------------------------------------------------------------------------------------------------------
+bool wino_layer(const Tuning& t, int KS, int Cp) { return t.use_wino && KS == 3 && Cp % 16 == 0; }
+bool wino_dgrad_layer(const Tuning& t, int KS, int Cop) { return t.wino_dgrad && wino_layer(t, KS, Cop); }
+bool convt_x3_layer(const Tuning& t, int Cin, int Cout) { return t.wino_prec != 0 && t.convt_frag && Cin % 32 == 0 && Cout % 32 == 0; }
+bool convt_x3_dgrad_layer(const Tuning& t, int Cin, int Cout) {
+  return t.wino_prec != 0 && t.convt_dgrad_x3 && Cin % 64 == 0 && Cout % 32 == 0;
+}
+bool convt_bf16f_layer(const Tuning& t, int Cin, int Cout) { return t.convt_frag && Cin % 64 == 0 && Cout % 32 == 0; }
+
+static bool wino_applicable(const IgemmDesc& d) {
+  return wino_layer(tun(d), d.KS, d.Cp) && d.wu && d.out_mode == 0 && d.split_n == 0 && d.K == 9 * d.Cp && (d.ldin & 3) == 0 &&
+         (long)d.H * d.W * d.ldin < (1l << 31) && (long)d.H * d.W * d.ldout < (1l << 31);
 }
 
-const char* igemm_kernel_name(const IgemmDesc& d, int dtype) {
+// the assembly forms of wino3x3_cp_kernel (wino_asm.hip)
+static bool wino_asm_applicable(const IgemmDesc& d) {
+  if (!tun(d).wino_asm) return false;
+  if (d.stat_slots) return false;   // (a missing scale / shift array is 1 / 0 in the kernels, as in the C++ epilogue)
+  if (wino_wide(d)) {
+    if (d.N & 63) return false;
+  } else {   // narrow kernels: exactly one 32-channel tile, 2 or 4 chunks (their weight pieces stay in registers), the C++ kernel's
+             // two-chunk load lead and reader-side scale / shift (what launch_wino_f32 runs for these layers)
+    if (d.N != 32 || !(d.Cp == 32 || d.Cp == 64)) return false;
+  }
+  if ((d.H & 7) || (d.W & 31) || (d.Cp & 31) || (d.ldin & 3) || (d.ldout & 3) || (d.coff & 3)) return false;
+  if (d.pool && ((d.ldpool & 3) || (d.H & 1) || (d.W & 1))) return false;
+  if ((long)d.H * d.W * d.ldin * 4 >= 0x7fff0000l || (long)d.H * d.W * d.ldout * 4 >= 0x7fff0000l) return false;
+  const WinoPlan p = wino_plan(d);
+  if ((long)p.total * p.tiles_x * p.tiles_y >= (1l << 32) || (long)p.ngroups * p.nblk * p.ngroups >= (1l << 32)) return false;
+  return true;
+}
+
+static bool convt_x3_applicable(const IgemmDesc& d) {
+  return convt_x3_layer(tun(d), d.Cp, d.ct_cout) && d.wu && d.KS == 1 && d.K == d.Cp && d.N == 4 * d.ct_cout && (d.ldin & 3) == 0 &&
+         !d.scale && !d.relu && !d.split_n && (9l * 128 + 8l * d.Wout) * d.ldout < (1l << 31);   // a tile's 128 rows span < 2^31 elements
+}
+
+static bool convt_bf16f_applicable(const IgemmDesc& d) {
+  return convt_bf16f_layer(tun(d), d.Cp, d.ct_cout) && d.wu && d.KS == 1 && d.K == d.Cp && d.N == 4 * d.ct_cout && (d.ldin & 7) == 0 &&
+         (d.ldout & 7) == 0 && (d.coff & 7) == 0 && !d.scale && !d.relu && !d.split_n &&
+         (9l * 128 + 8l * d.Wout) * d.ldout < (1l << 31);   // the output pixels of a tile's 128 rows span < 2^31 elements
+}
+
+static bool convt_x3_dgrad_applicable(const IgemmDesc& d) {   // (N = the forward layer's Cin, Cp = its Cout)
+  return convt_x3_dgrad_layer(tun(d), d.N, d.Cp) && d.KS == 2 && d.wu && d.K == 4 * d.Cp && (d.ldin & 3) == 0 && !d.scale && !d.shift &&
+         !d.relu && !d.split_n && !d.pool && (long)d.M * d.ldout < (1l << 31) && (long)d.Hout * d.Wout * d.ldin < (1l << 31);
+}
+
+ConvKernel pick_conv(const IgemmDesc& d, int dtype) {
+  using K = ConvKernel;
+  if (d.M <= 0 || d.N <= 0) return K::None;   // (nothing to launch)
   if (dtype == 1) {
-    if (d.out_mode == 1) return convt_bf16f_applicable(d) ? "convt2x2_bf16_kernel" : "igemm_kernel<bf16> (ConvTranspose)";
-    return halo_np<__bf16>(d) ? "conv3x3_halo_kernel<bf16>" : "igemm_kernel<bf16>";
+    if (d.out_mode == 1) return d.KS != 1 ? K::None : convt_bf16f_applicable(d) ? K::ConvtBf16f : K::TilesBf16;
+    const int np = halo_np<__bf16>(d);
+    if (np) return np == 8 ? K::HaloBf16Np8 : K::HaloBf16Np4;
+    return d.KS == 3 || d.KS == 1 ? K::TilesBf16 : K::None;
   }
-  if (d.out_mode == 1) return convt_x3_applicable(d) ? "convt2x2_x3_kernel" : "igemm_kernel<f32> (ConvTranspose)";
+  if (d.out_mode == 1) return d.KS != 1 ? K::None : convt_x3_applicable(d) ? K::ConvtX3 : K::TilesF32;
+  if (convt_x3_dgrad_applicable(d)) return K::ConvtX3Dgrad;
   if (wino_applicable(d)) {
+    const Tuning& t = tun(d);
     const bool wide = wino_wide(d);
-    if (tun(d).wino_prec && tun(d).wino_cp && (long)d.H * d.W * d.ldin * 4 < (1l << 31))
-      return wide ? (wino_asm_applicable(d) ? "mgu_wino_cp2_gfx950 (asm form of wino3x3_cp_kernel<2>)" : "wino3x3_cp_kernel<2>")
-                  : (wino_asm_applicable(d) ? (d.Cp == 32 ? "mgu_wino_cp1r2_gfx950 (asm form of wino3x3_cp_kernel<1>)"
-                                                             : "mgu_wino_cp1r4_gfx950 (asm form of wino3x3_cp_kernel<1>)")
-                                            : "wino3x3_cp_kernel<1>");
-    if (tun(d).wino_prec) return wide ? "wino3x3_f32_kernel<0,1>" : "wino3x3_f32_kernel<1,1>";
-    return wide ? "wino3x3_f32_kernel<0,0>" : "wino3x3_f32_kernel<1,0>";
+    if (!t.wino_prec) return wide ? K::WinoF32Wide : K::WinoF32Narrow;
+    // the component-pair kernels address the image through buffer descriptors: its bytes must stay below the out-of-image marker
+    if (!t.wino_cp || (long)d.H * d.W * d.ldin * 4 >= 0x7fff0000l) return wide ? K::WinoX3Wide : K::WinoX3Narrow;
+    if (d.stat_slots) return wide ? K::WinoCp2Stats : K::WinoCp1Stats;   // training forward: statistics in the epilogue
+    if (wino_asm_applicable(d)) return wide ? K::WinoAsmWide : d.Cp == 32 ? K::WinoAsmCp1r2 : K::WinoAsmCp1r4;
+    return wide ? K::WinoCp2 : K::WinoCp1;
   }
-  if (halo_np<float>(d) == 8) return "conv3x3_halo_kernel<f32>";
-  if (d.KS == 2) return convt_x3_dgrad_applicable(d) ? "convt2x2_x3_kernel<dgrad>" : "igemm_kernel<f32> (ConvTranspose dgrad)";
-  return "igemm_kernel<f32>";
+  if (halo_np<float>(d) == 8) return K::HaloF32;
+  return d.KS >= 1 && d.KS <= 3 ? K::TilesF32 : K::None;
 }
 
-hipError_t launch_igemm_f32(const IgemmDesc& d, hipStream_t s) {
-  if (d.M <= 0 || d.N <= 0) return hipSuccess;
-  if ((d.Cp & 3) || (d.ldin & 3) || (d.Kp % 32) || d.K > d.Kp) return hipErrorInvalidValue;
-  if (d.out_mode == 1) {
-    if (d.KS != 1) return hipErrorInvalidValue;
-    if (convt_x3_applicable(d)) return launch_convt_x3(d, s);
-    return launch_tiles<float, 1, 1>(d, s);
+const char* conv_kernel_name(ConvKernel k, const IgemmDesc& d) {
+  switch (k) {
+    case ConvKernel::WinoAsmWide: return "mgu_wino_cp2_gfx950 (asm form of wino3x3_cp_kernel<2>)";
+    case ConvKernel::WinoAsmCp1r2: return "mgu_wino_cp1r2_gfx950 (asm form of wino3x3_cp_kernel<1>)";
+    case ConvKernel::WinoAsmCp1r4: return "mgu_wino_cp1r4_gfx950 (asm form of wino3x3_cp_kernel<1>)";
+    case ConvKernel::WinoCp2: case ConvKernel::WinoCp2Stats: return "wino3x3_cp_kernel<2>";
+    case ConvKernel::WinoCp1: case ConvKernel::WinoCp1Stats: return "wino3x3_cp_kernel<1>";
+    case ConvKernel::WinoF32Wide: return "wino3x3_f32_kernel<0,0>";
+    case ConvKernel::WinoF32Narrow: return "wino3x3_f32_kernel<1,0>";
+    case ConvKernel::WinoX3Wide: return "wino3x3_f32_kernel<0,1>";
+    case ConvKernel::WinoX3Narrow: return "wino3x3_f32_kernel<1,1>";
+    case ConvKernel::HaloF32: return "conv3x3_halo_kernel<f32>";
+    case ConvKernel::HaloBf16Np8: case ConvKernel::HaloBf16Np4: return "conv3x3_halo_kernel<bf16>";
+    case ConvKernel::TilesBf16: return d.out_mode == 1 ? "igemm_kernel<bf16> (ConvTranspose)" : "igemm_kernel<bf16>";
+    case ConvKernel::ConvtX3: return "convt2x2_x3_kernel";
+    case ConvKernel::ConvtBf16f: return "convt2x2_bf16_kernel";
+    case ConvKernel::ConvtX3Dgrad: return "convt2x2_x3_kernel<dgrad>";
+    case ConvKernel::TilesF32: case ConvKernel::None: break;
   }
-  if (d.KS == 2 && convt_x3_dgrad_applicable(d)) return launch_convt_x3_dgrad(d, s);
-  if (wino_applicable(d)) return launch_wino_f32(d, s);
-  if (halo_np<float>(d) == 8) return launch_halo_tiles<float, 8>(d, s);
-  if (d.KS == 3) return launch_tiles<float, 3, 0>(d, s);
-  if (d.KS == 1) return launch_tiles<float, 1, 0>(d, s);
-  if (d.KS == 2) return launch_tiles<float, 2, 0>(d, s);
-  return hipErrorInvalidValue;
+  return d.out_mode == 1 ? "igemm_kernel<f32> (ConvTranspose)" : d.KS == 2 ? "igemm_kernel<f32> (ConvTranspose dgrad)" : "igemm_kernel<f32>";
 }
 
-// bf16 storage, fp32 accumulate (inference): `in`, `w`, `out` of the descriptor point to bf16 data, ld/Cp/K/Kp are in
-// elements (Cp % 8 == 0, Kp % 64 == 0); scale/shift stay fp32.
-hipError_t launch_igemm_bf16(const IgemmDesc& d, hipStream_t s) {
-  if (d.M <= 0 || d.N <= 0) return hipSuccess;
-  if ((d.Cp & 7) || (d.ldin & 7) || (d.Kp % 64) || d.K > d.Kp || d.split_n) return hipErrorInvalidValue;
-  if (d.out_mode == 1) {
-    if (d.KS != 1) return hipErrorInvalidValue;
-    if (convt_bf16f_applicable(d)) return launch_convt_bf16f(d, s);
-    return launch_tiles<__bf16, 1, 1>(d, s);
+// (the assembly forms count with the C++ kernel they replace)
+const char* conv_dgrad_name(ConvKernel k, const IgemmDesc& d) {
+  switch (k) {
+    case ConvKernel::WinoAsmWide: case ConvKernel::WinoCp2: case ConvKernel::WinoCp2Stats: return "wino3x3_cp_kernel<2> (dgrad)";
+    case ConvKernel::WinoAsmCp1r2: case ConvKernel::WinoAsmCp1r4: case ConvKernel::WinoCp1: case ConvKernel::WinoCp1Stats:
+      return "wino3x3_cp_kernel<1> (dgrad)";
+    case ConvKernel::WinoX3Wide: case ConvKernel::WinoX3Narrow: return "wino3x3_f32_kernel<*,1> (dgrad)";
+    case ConvKernel::WinoF32Wide: case ConvKernel::WinoF32Narrow: return "wino3x3_f32_kernel<*,0> (dgrad)";
+    case ConvKernel::ConvtX3Dgrad: return "convt2x2_x3_kernel (dgrad)";
+    default: return d.KS == 2 ? "igemm_kernel<f32> (ConvTranspose dgrad)" : "igemm/halo (dgrad)";
   }
-  const int np = halo_np<__bf16>(d);
-  if (np == 8) return launch_halo_tiles<__bf16, 8>(d, s);
-  if (np == 4) return launch_halo_tiles<__bf16, 4>(d, s);
-  if (d.KS == 3) return launch_tiles<__bf16, 3, 0>(d, s);
-  if (d.KS == 1) return launch_tiles<__bf16, 1, 0>(d, s);
+}
+
+// what the matrix pipe issues: 2 * M * K * N for the direct kernels; Winograd F(2x2,3x3) 16 products per 2x2 tile and channel pair;
+// the three-piece operand split six bf16 products per fp32 product
+ConvCost conv_cost(ConvKernel k, const IgemmDesc& d) {
+  const double direct = 2.0 * d.M * (double)d.K * d.N;
+  switch (k) {
+    case ConvKernel::WinoF32Wide: case ConvKernel::WinoF32Narrow:
+      return {2.0 * (d.M / (d.H * d.W)) * ((d.H + 1) / 2) * ((d.W + 1) / 2) * 16.0 * d.Cp * d.N, 0};
+    case ConvKernel::ConvtX3: case ConvKernel::ConvtX3Dgrad: return {6.0 * direct, 1};
+    case ConvKernel::HaloBf16Np8: case ConvKernel::HaloBf16Np4: case ConvKernel::TilesBf16: case ConvKernel::ConvtBf16f: return {direct, 1};
+    case ConvKernel::HaloF32: case ConvKernel::TilesF32: case ConvKernel::None: return {direct, 0};
+    default:   // the three-piece Winograd kernels
+      return {2.0 * (d.M / (d.H * d.W)) * ((d.H + 1) / 2) * ((d.W + 1) / 2) * 16.0 * d.Cp * d.N * 6.0, 1};
+  }
+}
+
+hipError_t launch_conv(const IgemmDesc& d, ConvKernel k, int dtype, hipStream_t s) {
+  if (d.M <= 0 || d.N <= 0) return hipSuccess;
+  if (dtype == 1) {   // bf16 storage, fp32 accumulate (inference): Cp % 8 == 0, Kp % 64 == 0; scale/shift stay fp32
+    if ((d.Cp & 7) || (d.ldin & 7) || (d.Kp % 64) || d.K > d.Kp || d.split_n) return hipErrorInvalidValue;
+  } else {
+    if ((d.Cp & 3) || (d.ldin & 3) || (d.Kp % 32) || d.K > d.Kp) return hipErrorInvalidValue;
+  }
+  switch (k) {
+    case ConvKernel::WinoAsmWide: case ConvKernel::WinoAsmCp1r2: case ConvKernel::WinoAsmCp1r4: return launch_wino_cp_asm(d, k, s);
+    case ConvKernel::WinoCp2: case ConvKernel::WinoCp1: case ConvKernel::WinoCp2Stats: case ConvKernel::WinoCp1Stats:
+    case ConvKernel::WinoF32Wide: case ConvKernel::WinoF32Narrow: case ConvKernel::WinoX3Wide: case ConvKernel::WinoX3Narrow:
+      return launch_wino_f32(d, k, s);
+    case ConvKernel::HaloF32: return launch_halo_tiles<float, 8>(d, s);
+    case ConvKernel::HaloBf16Np8: return launch_halo_tiles<__bf16, 8>(d, s);
+    case ConvKernel::HaloBf16Np4: return launch_halo_tiles<__bf16, 4>(d, s);
+    case ConvKernel::TilesF32:
+      if (d.out_mode == 1) return launch_tiles<float, 1, 1>(d, s);
+      if (d.KS == 3) return launch_tiles<float, 3, 0>(d, s);
+      if (d.KS == 1) return launch_tiles<float, 1, 0>(d, s);
+      return launch_tiles<float, 2, 0>(d, s);
+    case ConvKernel::TilesBf16:
+      if (d.out_mode == 1) return launch_tiles<__bf16, 1, 1>(d, s);
+      if (d.KS == 3) return launch_tiles<__bf16, 3, 0>(d, s);
+      return launch_tiles<__bf16, 1, 0>(d, s);
+    case ConvKernel::ConvtX3: return launch_convt_x3(d, s);
+    case ConvKernel::ConvtBf16f: return launch_convt_bf16f(d, s);
+    case ConvKernel::ConvtX3Dgrad: return launch_convt_x3_dgrad(d, s);
+    case ConvKernel::None: break;
+  }
   return hipErrorInvalidValue;
 }
 

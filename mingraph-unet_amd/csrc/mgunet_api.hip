@@ -171,16 +171,16 @@ int mgu_unet_configure(mgu_ctx* c, int in_ch, int ncls, int feat, int depth, int
     L.N = L.convt ? 4 * L.Cout : L.Cout;
     L.Np = rup(L.N, 128);
     total += (size_t)L.Np * L.Kp + 2 * (size_t)L.Np + (L.bn.empty() ? 0 : 4 * (size_t)L.Np);
-    L.wino = dtype == MGU_DTYPE_F32 && !L.convt && L.KS == 3 && L.Cp % 16 == 0;   // Winograd F(2x2,3x3) layers (wino_f32.hip)
+    L.wino = dtype == MGU_DTYPE_F32 && !L.convt && wino_layer(c->tn, L.KS, L.Cp);   // Winograd F(2x2,3x3) layers (wino_f32.hip)
     if (L.wino) total += wino_u_floats(L.Cout, L.Cp);
     if (L.wino && rup(L.Cout, 4) % 16 == 0) total += wino_u_floats(L.Cin, rup(L.Cout, 4));   // data-gradient conv: roles swapped
     // fp32 ConvTranspose on fragment-ordered three-piece weights (convt_x3.hip).  (A bf16-storage sibling of that kernel -- one
     // fragment per operand straight from global memory -- was measured SLOWER than the LDS-tiled generic kernel, 0.178 vs 0.163 ms per
     // step: 32-byte row segments per K slice; not kept.)
-    L.ctx3 = dtype == MGU_DTYPE_F32 && L.convt && L.Cin % 32 == 0 && L.Cout % 32 == 0 && c->tn.wino_prec != 0 && c->tn.convt_frag;
+    L.ctx3 = dtype == MGU_DTYPE_F32 && L.convt && convt_x3_layer(c->tn, L.Cin, L.Cout);
     if (L.ctx3) total += convt_x3_floats(L.Cin, L.Cout) + convt_x3_dgrad_floats(L.Cin, L.Cout);
     // bf16 storage: the layer's weights as bf16 MFMA fragments for convt2x2_bf16_kernel (whole-row LDS staging, transposed 16-byte stores)
-    L.ctb = dtype == MGU_DTYPE_BF16 && L.convt && L.Cin % 64 == 0 && L.Cout % 32 == 0 && c->tn.convt_frag;
+    L.ctb = dtype == MGU_DTYPE_BF16 && L.convt && convt_bf16f_layer(c->tn, L.Cin, L.Cout);
     if (L.ctb) total += convt_bf16f_floats(L.Cin, L.Cout);
     if (dtype == MGU_DTYPE_F32 && !L.convt && L.bn.empty()) total += (size_t)rup(L.Cin, 128) * rup(L.KS * L.KS * rup(L.Cout, 4), 32);   // final conv: data-gradient panel
     L.first = !L.convt && L.KS == 3 && first_conv_applicable(dtype, L.Cin, L.Cp, L.Cout, 8, 0);
@@ -360,7 +360,7 @@ int mgud::repack_weights(mgu_ctx* c, hipStream_t s) {
       if (L.ctb) HIPCHK(c, launch_pack_convt_bf16f(w, L.wu, L.Cin, L.Cout, s));
       if (L.ctx3) items.push_back(WinoPackItem{w, L.wu, L.Cout, L.Cin, 0, 0, 0, 0, PACK_CONVT_X3});
       items.push_back(WinoPackItem{b, L.shift, L.Cout, 4, 0, 0, 0, 0, PACK_BIAS_TILE});   // scale unused (nullptr at launch)
-      if (L.wxg && c->want_train && c->tn.convt_dgrad_x3 && (L.Cin & 63) == 0 && (L.Cout & 31) == 0) {
+      if (L.wxg && c->want_train && convt_x3_dgrad_layer(c->tn, L.Cin, L.Cout)) {
         items.push_back(WinoPackItem{w, L.wxg, L.Cout, L.Cin, 0, 0, 1, 0, PACK_CONVT_X3});
         L.wxg_valid = true;
       }
@@ -370,7 +370,7 @@ int mgud::repack_weights(mgu_ctx* c, hipStream_t s) {
       L.wp_dirty = true;
       if (L.wu) items.push_back(WinoPackItem{w, L.wu, L.Cout, L.Cin, L.Cp, 0, 0, 0, PACK_WINO});
       L.wug_valid = false;
-      if (L.wug && c->want_train && c->tn.wino_dgrad && c->tn.use_wino) {
+      if (L.wug && c->want_train && wino_dgrad_layer(c->tn, L.KS, rup(L.Cout, 4))) {
         items.push_back(WinoPackItem{w, L.wug, L.Cin, L.Cout, rup(L.Cout, 4), 0, 1, 0, PACK_WINO});
         L.wug_valid = true;
       }
@@ -460,40 +460,30 @@ int mgud::run_layer(mgu_ctx* c, const Layer& L, const void* in_v, int ldin, int 
     HIPCHK(c, launch_first_conv(c->dtype, in_v, L.wf, scale, shift, out_v, B, H, W, L.Cin, L.Cout, ldout, coff, relu, s));
     return MGU_OK;
   }
+  ConvKernel k = pick_conv(d, c->dtype);
   // the Winograd epilogue also accumulates sum z, sum z^2: one accumulator row per workgroup, so only while the launch's grid fits
   // the table (>= 19 images of 512^2 or 5 of 1024^2 per GPU on the full-resolution 32-channel layer, or a small MGU_WINO_PPB_CAP, do
   // not: the caller then takes the separate statistics pass, launch_bn_stats)
-  if (stat_slots && c->dtype == MGU_DTYPE_F32 && wino_applicable(d) && wino_grid_blocks(d) <= STAT_ROWS) {
+  if (stat_slots && conv_is_wino(k) && wino_grid_blocks(d) <= STAT_ROWS) {
     d.stat_slots = stat_slots;
     c->last_stat_rows = wino_grid_blocks(d);
     if (stat_fused) *stat_fused = true;
   }
-  if (pool && ((c->dtype == MGU_DTYPE_F32 && wino_applicable(d)) || halo_pool_fusable(d, c->dtype))) {
-    // the Winograd / halo epilogue also writes the 2x2 max-pooled tensor
+  if (pool && conv_fuses_pool(k)) {   // the Winograd / halo epilogue also writes the 2x2 max-pooled tensor
     d.pool = (float*)pool, d.ldpool = ldpool;
     if (pool_fused) *pool_fused = true;
   }
-  if (L.wp_dirty) {   // falling back to the direct kernel: build its panel now
-    const bool direct = L.convt ? !(c->dtype == MGU_DTYPE_F32 && convt_x3_applicable(d)) : !(c->dtype == MGU_DTYPE_F32 && wino_applicable(d));
-    if (direct) {
-      if (L.convt) HIPCHK(c, launch_pack_convt_w(L.w_src, L.wp, c->dtype, L.Cin, L.Cout, L.Kp, s));
-      else HIPCHK(c, launch_pack_conv_w(L.w_src, L.wp, c->dtype, L.Cout, L.Cin, L.Cp, L.KS, L.Kp, s));
-      L.wp_dirty = false;
-    }
+  if (d.stat_slots || d.pool) k = pick_conv(d, c->dtype);   // the fused epilogue narrows the choice (not every kernel form has it)
+  if (L.wp_dirty && conv_reads_panel(k)) {   // falling back to the direct kernel: build its panel now
+    if (L.convt) HIPCHK(c, launch_pack_convt_w(L.w_src, L.wp, c->dtype, L.Cin, L.Cout, L.Kp, s));
+    else HIPCHK(c, launch_pack_conv_w(L.w_src, L.wp, c->dtype, L.Cout, L.Cin, L.Cp, L.KS, L.Kp, s));
+    L.wp_dirty = false;
   }
-  // profiling record: algorithmic 2*MAC of the operator and what the matrix pipe really issues (Winograd F(2x2,3x3): 16 products
-  // per 2x2 tile and channel pair; the three-piece operand split issues six bf16 products per fp32 product)
+  // profiling record: algorithmic 2*MAC of the operator and what the matrix pipe really issues
   const double alg = L.convt ? 2.0 * d.M * (double)L.Cin * L.Cout * 4.0 : 2.0 * d.M * (double)L.KS * L.KS * L.Cin * L.Cout;
-  double mfma = L.convt ? alg : 2.0 * d.M * (double)L.K * L.Cout;
-  int pipe = c->dtype == MGU_DTYPE_BF16 ? 1 : 0;
-  if (c->dtype == MGU_DTYPE_F32 && convt_x3_applicable(d)) mfma = 6.0 * alg, pipe = 1;
-  if (c->dtype == MGU_DTYPE_F32 && wino_applicable(d)) {
-    mfma = 2.0 * B * ((H + 1) / 2) * ((W + 1) / 2) * 16.0 * L.Cp * L.Cout * (c->tn.wino_prec ? 6.0 : 1.0);
-    pipe = c->tn.wino_prec ? 1 : 0;
-  }
-  ProfScope ps(c, s, igemm_kernel_name(d, c->dtype), alg, mfma, pipe);
-  if (c->dtype == MGU_DTYPE_BF16) HIPCHK(c, launch_igemm_bf16(d, s));
-  else HIPCHK(c, launch_igemm_f32(d, s));
+  const ConvCost cost = conv_cost(k, d);
+  ProfScope ps(c, s, conv_kernel_name(k, d), alg, cost.mfma, cost.pipe);
+  HIPCHK(c, launch_conv(d, k, c->dtype, s));
   return MGU_OK;
 }
 
@@ -670,7 +660,7 @@ int mgu_conv2d_prepare(mgu_ctx* c, const void* w_dev, int Cout, int Cin, int ksi
   mgu_conv_weights* p = new mgu_conv_weights();
   p->Cout = Cout, p->Cin = Cin, p->ksize = ksize;
   p->K = ksize * ksize * Cin, p->Kp = rup(p->K, 32), p->Np = rup(Cout, 128);
-  const bool wino = ksize == 3 && Cin % 16 == 0 && c->tn.use_wino;
+  const bool wino = wino_layer(c->tn, ksize, Cin);
   const size_t panel = (size_t)p->Np * p->Kp, total = panel + p->Np + (wino ? wino_u_floats(Cout, Cin) : 0);
   hipError_t e = hipMalloc((void**)&p->wp, total * sizeof(float));
   if (e != hipSuccess) {
@@ -748,7 +738,7 @@ int mgu_conv2d_nhwc(mgu_ctx* c, const void* in_dev, int B, int H, int W, int Cin
   int rc = block_scratch(c, L.Np, L.Kp, &L.wp, &sc, &sh, s);
   if (rc) return rc;
   HIPCHK(c, launch_pack_conv_w((const float*)w_dev, L.wp, 0, Cout, Cin, Cin, ksize, L.Kp, s));
-  if (ksize == 3 && Cin % 16 == 0 && c->tn.use_wino) {   // same routing as the model's layers: Winograd F(2x2,3x3)
+  if (wino_layer(c->tn, ksize, Cin)) {   // same routing as the model's layers: Winograd F(2x2,3x3)
     if ((rc = ensure(c, &c->wuws, &c->wuws_bytes, wino_u_floats(Cout, Cin) * sizeof(float)))) return rc;
     L.wu = (float*)c->wuws;
     HIPCHK(c, launch_pack_wino_w((const float*)w_dev, L.wu, Cout, Cin, Cin, 0, c->tn.wino_prec, s));
@@ -784,9 +774,9 @@ int mgu_conv_transpose2x2_nhwc(mgu_ctx* c, const void* in_dev, int B, int H, int
   float *wp, *sc, *sh;
   // Two packed forms, each in a region of its own: the direct [4 Cout][Cin] panel the tile kernel reads (always built), and -- when
   // the layer shape is eligible and the context's switches allow it (MGU_NO_CONVT_FRAG, MGU_WINO_PREC) -- the fragment-order
-  // three-piece weights of convt2x2_x3_kernel.  Which kernel runs is decided by the dispatcher (convt_x3_applicable) on the
-  // COMPLETE descriptor; a launch it rejects falls back to the tile kernel, which then finds a real panel in d.w.
-  const bool x3_shape = Cin % 32 == 0 && Cout % 32 == 0 && c->tn.wino_prec != 0 && c->tn.convt_frag;
+  // three-piece weights of convt2x2_x3_kernel.  Which kernel runs is decided by pick_conv on the COMPLETE descriptor; a launch it
+  // sends to the tile kernel finds a real panel in d.w.
+  const bool x3_shape = convt_x3_layer(c->tn, Cin, Cout);
   const size_t panel = (size_t)Np * Kp + 2 * (size_t)Np;
   int rc = ensure(c, &c->gws, &c->gws_bytes, (panel + (x3_shape ? convt_x3_floats(Cin, Cout) : 0)) * sizeof(float));
   if (rc) return rc;
@@ -804,14 +794,12 @@ int mgu_conv_transpose2x2_nhwc(mgu_ctx* c, const void* in_dev, int B, int H, int
     HIPCHK(c, launch_bias_tile((const float*)bias_dev, sh, Cout, 4, s));
     d.shift = sh;
   }
-  if (x3_shape) {
-    float* wx = wp + panel;
-    d.wu = wx;
-    if (convt_x3_applicable(d)) HIPCHK(c, launch_pack_convt_x3((const float*)w_dev, wx, Cin, Cout, s));
-    else d.wu = nullptr;
-  }
+  float* wx = x3_shape ? wp + panel : nullptr;
+  d.wu = wx;
+  const ConvKernel k = pick_conv(d, 0);
+  if (k == ConvKernel::ConvtX3) HIPCHK(c, launch_pack_convt_x3((const float*)w_dev, wx, Cin, Cout, s));
   ProfScope ps(c, s);
-  HIPCHK(c, launch_igemm_f32(d, s));
+  HIPCHK(c, launch_conv(d, k, 0, s));
   return MGU_OK;
 }
 
@@ -875,7 +863,7 @@ double mgu_unet_mfma_flops(mgu_ctx* c, int B, int H, int W) {
   std::vector<int> hs, wsz;
   level_dims(H, W, c->depth, hs, wsz);
   auto conv = [&](const Layer& L, int h, int w) {
-    if (L.wino && L.wu && c->tn.use_wino) return 2.0 * ((h + 1) / 2) * ((w + 1) / 2) * 16.0 * L.Cp * L.Cout;   // per 2x2 tile: 16 products
+    if (L.wino) return 2.0 * ((h + 1) / 2) * ((w + 1) / 2) * 16.0 * L.Cp * L.Cout;   // per 2x2 tile: 16 products
     return 2.0 * h * w * 9.0 * L.Cin * L.Cout;
   };
   double fl = 0;

@@ -139,11 +139,9 @@ int conv_wgrad(Bwd& w, const Layer& L, const float* dz) {
   d.dw_capacity = w.dwp_floats;
   {
     const double alg = 2.0 * d.M * (double)L.KS * L.KS * L.Cin * L.Cout;
-    const bool ww = wino_wgrad_applicable(d) && !wgrad_thin_applicable(d);
-    const bool x3 = ww && c->tn.wgrad_x3;   // three-piece mode: six bf16 MFMA products per Winograd multiply, on the bf16 pipe
-    ProfScope ps(c, w.s,
-                 wgrad_thin_applicable(d) ? "wgrad_thin kernels" : x3 ? "wino_wgrad_f32_kernel<X3>" : ww ? "wino_wgrad_f32_kernel" : "wgrad (direct) kernels",
-                 alg, ww ? alg * 16.0 / 36.0 * (x3 ? 6.0 : 1.0) : alg, wgrad_thin_applicable(d) ? -1 : x3 ? 1 : 0);
+    const WgradKernel k = pick_wgrad(d);
+    const WgradCost cost = wgrad_cost(k, alg);
+    ProfScope ps(c, w.s, wgrad_kernel_name(k), alg, cost.mfma, cost.pipe);
     HIPCHK(c, launch_wgrad_f32(d, w.s));
   }
   // ... and, in the same launch, the fold of the bias gradient's column sums that bn_relu_bwd left in the reduction slots
@@ -165,12 +163,11 @@ int conv_dgrad(Bwd& w, const Layer& L, const float* dz, float* out, int ldout) {
   d.M = L.t_B * L.t_H * L.t_W, d.H = L.t_H, d.W = L.t_W;
   d.Cp = Cop, d.ldin = L.Cout == Cop ? L.Cout : Cop, d.KS = L.KS, d.K = Kd, d.Kp = Kpd;
   d.N = L.Cin, d.ldout = ldout;
-  if (c->tn.wino_dgrad && L.wino && L.KS == 3 && Cop % 16 == 0 && c->tn.use_wino) {   // same Winograd kernel, weights flipped + transposed
-    d.wu = L.wug ? L.wug : w.wug;
-  }
+  if (L.wino && wino_dgrad_layer(c->tn, L.KS, Cop)) d.wu = L.wug ? L.wug : w.wug;   // same Winograd kernel, weights flipped + transposed
   // only the weight form the chosen kernel reads is built: Winograd U (normally already packed with all the others by the last
   // weight refresh, repack_weights) or the direct flipped/transposed panel
-  if (wino_applicable(d)) {
+  const ConvKernel k = pick_conv(d, 0);
+  if (conv_is_wino(k)) {
     if (!(L.wug && L.wug_valid)) {
       HIPCHK(c, launch_pack_wino_w(L.w_src, const_cast<float*>(d.wu), L.Cin, L.Cout, Cop, 1, c->tn.wino_prec, w.s));
       if (L.wug) L.wug_valid = true;
@@ -180,18 +177,9 @@ int conv_dgrad(Bwd& w, const Layer& L, const float* dz, float* out, int ldout) {
   }
   {
     const double alg = 2.0 * d.M * (double)L.KS * L.KS * L.Cin * L.Cout;
-    const bool wn = wino_applicable(d);
-    double mfma = 2.0 * d.M * (double)d.K * d.N;
-    if (wn) mfma = 2.0 * L.t_B * ((L.t_H + 1) / 2) * ((L.t_W + 1) / 2) * 16.0 * d.Cp * d.N * (c->tn.wino_prec ? 6.0 : 1.0);
-    // record under the name of the kernel family the dispatcher will pick (the same one as a forward conv of this shape)
-    const std::string fam = std::string(igemm_kernel_name(d, 0));
-    const char* label = "igemm/halo (dgrad)";
-    // (the assembly forms, mgu_wino_cp2_gfx950 and mgu_wino_cp1r2/4_gfx950, count with the C++ kernel they replace)
-    if (fam == "wino3x3_cp_kernel<2>" || fam.rfind("mgu_wino_cp2_", 0) == 0) label = "wino3x3_cp_kernel<2> (dgrad)";
-    else if (fam == "wino3x3_cp_kernel<1>" || fam.rfind("mgu_wino_cp1r", 0) == 0) label = "wino3x3_cp_kernel<1> (dgrad)";
-    else if (wn) label = c->tn.wino_prec ? "wino3x3_f32_kernel<*,1> (dgrad)" : "wino3x3_f32_kernel<*,0> (dgrad)";
-    ProfScope ps(c, w.s, label, alg, mfma, wn && c->tn.wino_prec ? 1 : 0);
-    HIPCHK(c, launch_igemm_f32(d, w.s));
+    const ConvCost cost = conv_cost(k, d);
+    ProfScope ps(c, w.s, conv_dgrad_name(k, d), alg, cost.mfma, cost.pipe);
+    HIPCHK(c, launch_conv(d, k, 0, w.s));
   }
   return MGU_OK;
 }
@@ -439,17 +427,15 @@ static int backward_body(mgu_ctx* c, const void* dlogits_dev, void* flat_grad_de
     q.in = dcat + C, q.w = w.dgp, q.out = tc, q.M = U.t_B * U.t_H * U.t_W, q.H = U.t_H, q.W = U.t_W, q.Cp = C, q.ldin = 2 * C;
     q.KS = 2, q.K = Kt, q.Kp = Kpt, q.N = U.Cin, q.ldout = U.Cin, q.Hout = hs[i], q.Wout = ws[i];
     // three-piece kernel of the forward layer in its gather mode (convt_x3.hip) where the shapes allow, else the generic tile kernel
-    q.wu = U.wxg_valid ? U.wxg : w.dgp;
-    if (c->tn.convt_dgrad_x3 && convt_x3_dgrad_applicable(q) && (U.wxg_valid || convt_x3_dgrad_floats(U.Cin, C) <= w.dgp_floats)) {
-      if (!U.wxg_valid) HIPCHK(c, launch_pack_convt_x3_dgrad(U.w_src, w.dgp, U.Cin, C, s));   // else: packed by the last weight refresh
-    } else {
-      q.wu = nullptr;
-      HIPCHK(c, launch_pack_convt_dgrad_w(U.w_src, w.dgp, U.Cin, C, Kpt, s));
-    }
+    if (U.wxg_valid || convt_x3_dgrad_floats(U.Cin, C) <= w.dgp_floats) q.wu = U.wxg_valid ? U.wxg : w.dgp;
+    const ConvKernel k = pick_conv(q, 0);
+    if (k != ConvKernel::ConvtX3Dgrad) HIPCHK(c, launch_pack_convt_dgrad_w(U.w_src, w.dgp, U.Cin, C, Kpt, s));
+    else if (!U.wxg_valid) HIPCHK(c, launch_pack_convt_x3_dgrad(U.w_src, w.dgp, U.Cin, C, s));   // else: packed by the last weight refresh
     {
       const double alg = 2.0 * q.M * (double)Kt * U.Cin;
-      ProfScope ps(c, s, q.wu ? "convt2x2_x3_kernel (dgrad)" : "igemm_kernel<f32> (ConvTranspose dgrad)", alg, q.wu ? 6.0 * alg : alg, q.wu ? 1 : 0);
-      HIPCHK(c, launch_igemm_f32(q, s));
+      const ConvCost cost = conv_cost(k, q);
+      ProfScope ps(c, s, conv_dgrad_name(k, q), alg, cost.mfma, cost.pipe);
+      HIPCHK(c, launch_conv(q, k, 0, s));
     }
     dy = tc, lddy = U.Cin;
     if ((rc = block_done(U.off_w, false))) return rc;

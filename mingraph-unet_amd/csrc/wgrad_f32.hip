@@ -354,18 +354,61 @@ static hipError_t launch_wg_halo(WgradDesc& d, hipStream_t s) {
 }
 
 
+// the streaming kernels of the first 3x3 conv (Cin 3) and the 1x1 head (wgrad_thin.hip)
+static bool wgrad_thin_applicable(const WgradDesc& d) {
+  if (!tun(d).wgrad_thin || d.M < 4096 || (d.ldz & 3) || (d.zoff & 3) || (d.ldin & 3) || (d.inoff & 3)) return false;
+  if (d.KS == 1 && d.N == 4 && (d.Cp == 32 || d.Cp == 64) && d.K == d.Cp) return true;
+  if (d.KS == 3 && d.N == 32 && d.Cp == 4 && d.K == 36 && d.M == (d.M / (d.H * d.W)) * d.H * d.W) return true;
+  return false;
+}
+
+// Winograd F(3x3,2x2) (wino_wgrad_f32.hip)
+static bool wino_wgrad_applicable(const WgradDesc& d) {
+  return tun(d).wino_wgrad && d.KS == 3 && d.Cp % 32 == 0 && d.N % 32 == 0 && d.K == 9 * d.Cp && (d.ldin & 3) == 0 && (d.ldz & 3) == 0 &&
+         (d.inoff & 3) == 0 && (d.zoff & 3) == 0 && (long)d.H * d.W * d.ldin < (1l << 31) && (long)d.H * d.W * d.ldz < (1l << 31) &&
+         d.dw_capacity >= (size_t)d.N * d.Kp;
+}
+
+WgradKernel pick_wgrad(const WgradDesc& d) {
+  const Tuning& t = tun(d);
+  if (wgrad_thin_applicable(d)) return WgradKernel::Thin;
+  if (wino_wgrad_applicable(d)) return t.wgrad_x3 ? WgradKernel::WinoX3 : WgradKernel::Wino;   // F(3x3,2x2): 2.25x fewer multiplies
+  if (t.wgrad_halo && d.KS == 3 && d.Cp % 32 == 0 && d.N % 32 == 0 && d.K == 9 * d.Cp && (long)d.H * d.W * d.ldin < (1l << 31) &&
+      (long)d.H * d.W * d.ldz < (1l << 31) && d.dw_capacity >= (size_t)d.N * d.Kp)
+    return WgradKernel::Halo;
+  return WgradKernel::Tiles;
+}
+
+const char* wgrad_kernel_name(WgradKernel k) {
+  switch (k) {
+    case WgradKernel::Thin: return "wgrad_thin kernels";
+    case WgradKernel::WinoX3: return "wino_wgrad_f32_kernel<X3>";
+    case WgradKernel::Wino: return "wino_wgrad_f32_kernel";
+    default: return "wgrad (direct) kernels";
+  }
+}
+
+// Winograd: 16 multiplies per 2x2 output tile where the direct form takes 36; three-piece mode six bf16 MFMA products per multiply
+WgradCost wgrad_cost(WgradKernel k, double alg) {
+  switch (k) {
+    case WgradKernel::Thin: return {alg, -1};
+    case WgradKernel::WinoX3: return {alg * 16.0 / 36.0 * 6.0, 1};
+    case WgradKernel::Wino: return {alg * 16.0 / 36.0 * 1.0, 0};
+    default: return {alg, 0};
+  }
+}
+
 hipError_t launch_wgrad_f32(WgradDesc& d, hipStream_t s) {
   d.groups = 1;   // every path sets the number of partial panels it wrote (the caller sums them: unpack_conv*_grad_kernel)
   if (d.M <= 0 || d.N <= 0 || d.K <= 0) return hipSuccess;
   if ((d.N & 3) || (d.ldz & 3) || (d.zoff & 3) || (d.Cp & 3) || (d.ldin & 3) || (d.inoff & 3) || d.K > d.Kp)
     return hipErrorInvalidValue;
-  if (wgrad_thin_applicable(d)) return launch_wgrad_thin(d, s);       // first conv / 1x1 head: streaming kernels (wgrad_thin.hip)
-  if (wino_wgrad_applicable(d)) return launch_wino_wgrad_f32(d, s);   // F(3x3,2x2): 2.25x fewer multiplies (wino_wgrad_f32.hip)
-  if (tun(d).wgrad_halo && d.KS == 3 && d.Cp % 32 == 0 && d.N % 32 == 0 && d.K == 9 * d.Cp &&
-      (long)d.H * d.W * d.ldin < (1l << 31) && (long)d.H * d.W * d.ldz < (1l << 31) &&
-      d.dw_capacity >= (size_t)d.N * d.Kp) {
-    if (d.N % 64 == 0) return launch_wg_halo<2>(d, s);
-    return launch_wg_halo<1>(d, s);
+  switch (pick_wgrad(d)) {
+    case WgradKernel::Thin: return launch_wgrad_thin(d, s);
+    case WgradKernel::WinoX3: return launch_wino_wgrad_f32(d, true, s);
+    case WgradKernel::Wino: return launch_wino_wgrad_f32(d, false, s);
+    case WgradKernel::Halo: return d.N % 64 == 0 ? launch_wg_halo<2>(d, s) : launch_wg_halo<1>(d, s);
+    case WgradKernel::Tiles: break;
   }
   if (d.dw_capacity < (size_t)d.N * d.Kp) return hipErrorInvalidValue;
   if (d.KS == 3) return launch_wg_tiles<3>(d, s);

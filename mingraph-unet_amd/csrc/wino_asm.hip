@@ -4,7 +4,7 @@
 // Same operator, same layouts and the same arithmetic order as wino3x3_cp_kernel<2, false, false, false> (wino_f32.hip; the
 // 3x3 convolutions of ConvBlock, model/unet/unet_encoder.py:15-25): outputs are bitwise equal to the C++ kernel's
 // (tests/test_gpu_wino_asm.py).  The code object is loaded once per device through the module API; everything the assembly
-// does not cover (ragged sizes, statistics epilogue, odd chunk counts, missing scale / shift) stays on the C++ kernel.
+// does not cover (ragged sizes, statistics epilogue, odd chunk counts) stays on the C++ kernel (pick_conv, igemm.hip).
 #include "common.h"
 #include <mutex>
 
@@ -39,30 +39,13 @@ hipModule_t g_mod[64] = {};
 hipFunction_t g_fn[64][3] = {};   // loaded functions per device (kNames order), written once under g_mu, immutable afterwards
 }  // namespace
 
-bool wino_asm_applicable(const IgemmDesc& d) {
-  if (!tun(d).wino_asm || !tun(d).wino_prec || !tun(d).wino_cp) return false;
-  if (d.stat_slots) return false;   // (a missing scale / shift array is 1 / 0 in the kernels, as in the C++ epilogue)
-  if (wino_wide(d)) {
-    if (d.N & 63) return false;
-  } else {   // narrow kernels: exactly one 32-channel tile, 2 or 4 chunks (their weight pieces stay in registers), the C++ kernel's
-             // two-chunk load lead and reader-side scale / shift (what launch_wino_f32 picks for these layers)
-    if (d.N != 32 || !(d.Cp == 32 || d.Cp == 64)) return false;
-  }
-  if ((d.H & 7) || (d.W & 31) || (d.Cp & 31) || (d.ldin & 3) || (d.ldout & 3) || (d.coff & 3)) return false;
-  if (d.pool && ((d.ldpool & 3) || (d.H & 1) || (d.W & 1))) return false;
-  if ((long)d.H * d.W * d.ldin * 4 >= 0x7fff0000l || (long)d.H * d.W * d.ldout * 4 >= 0x7fff0000l) return false;
-  const WinoPlan p = wino_plan(d);
-  if ((long)p.total * p.tiles_x * p.tiles_y >= (1l << 32) || (long)p.ngroups * p.nblk * p.ngroups >= (1l << 32)) return false;
-  return true;
-}
-
-hipError_t launch_wino_cp_asm(const IgemmDesc& d, hipStream_t s) {
+hipError_t launch_wino_cp_asm(const IgemmDesc& d, ConvKernel kind, hipStream_t s) {
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return e;
   if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
   hipFunction_t fn;
-  const int k = wino_wide(d) ? 0 : d.Cp == 32 ? 1 : 2;
+  const int k = kind == ConvKernel::WinoAsmWide ? 0 : kind == ConvKernel::WinoAsmCp1r2 ? 1 : 2;
   {
     std::lock_guard<std::mutex> lk(g_mu);
     if (!g_mod[dev]) {

@@ -1348,27 +1348,25 @@ static hipError_t launch_wino_mode(const IgemmDesc& d, hipStream_t s) {
   return hipGetLastError();
 }
 
-bool wino_applicable(const IgemmDesc& d) {
-  return tun(d).use_wino && d.wu && d.KS == 3 && d.out_mode == 0 && d.split_n == 0 && (d.Cp % 16) == 0 && d.K == 9 * d.Cp &&
-         (d.ldin & 3) == 0 && (long)d.H * d.W * d.ldin < (1l << 31) && (long)d.H * d.W * d.ldout < (1l << 31);
-}
-
-hipError_t launch_wino_f32(const IgemmDesc& d, hipStream_t s) {
-  const bool wide = wino_wide(d);
-  if (tun(d).wino_prec && tun(d).wino_cp &&
-      (long)d.H * d.W * d.ldin * 4 < 0x7fff0000l) {   // image bytes below the out-of-image marker offset of the buffer descriptor
+hipError_t launch_wino_f32(const IgemmDesc& d, ConvKernel k, hipStream_t s) {
+  switch (k) {
     // training forward (fused statistics): the one-chunk load lead (DEEP + RPF + statistics spills 4 registers)
-    if (d.stat_slots) return wide ? launch_wino_cp<2, true>(d, s) : launch_wino_cp<1, true>(d, s);
-    if (wino_asm_applicable(d)) return launch_wino_cp_asm(d, s);   // wide layers and the two- / four-chunk narrow layers (wino_asm.hip)
-    if (wide) return launch_wino_cp<2, false>(d, s);
-    // narrow layers: raw-operand prefetch always (RPF in the kernel) + the two-chunk load lead (DEEP) for an even chunk count, with
-    // the weight pieces held in registers (URES) when there are exactly two chunks
-    const int nC = d.Cp >> 4;
-    if (nC & 1) return launch_wino_cp<1, false>(d, s);
-    return nC == 2 ? launch_wino_cp<1, false, true, true>(d, s) : launch_wino_cp<1, false, true>(d, s);
+    case ConvKernel::WinoCp2Stats: return launch_wino_cp<2, true>(d, s);
+    case ConvKernel::WinoCp1Stats: return launch_wino_cp<1, true>(d, s);
+    case ConvKernel::WinoCp2: return launch_wino_cp<2, false>(d, s);
+    case ConvKernel::WinoCp1: {
+      // narrow layers: raw-operand prefetch always (RPF in the kernel) + the two-chunk load lead (DEEP) for an even chunk count, with
+      // the weight pieces held in registers (URES) when there are exactly two chunks
+      const int nC = d.Cp >> 4;
+      if (nC & 1) return launch_wino_cp<1, false>(d, s);
+      return nC == 2 ? launch_wino_cp<1, false, true, true>(d, s) : launch_wino_cp<1, false, true>(d, s);
+    }
+    case ConvKernel::WinoX3Wide: return launch_wino_mode<0, 1>(d, s);
+    case ConvKernel::WinoX3Narrow: return launch_wino_mode<1, 1>(d, s);
+    case ConvKernel::WinoF32Wide: return launch_wino_mode<0, 0>(d, s);
+    case ConvKernel::WinoF32Narrow: return launch_wino_mode<1, 0>(d, s);
+    default: return hipErrorInvalidValue;
   }
-  if (tun(d).wino_prec) return wide ? launch_wino_mode<0, 1>(d, s) : launch_wino_mode<1, 1>(d, s);
-  return wide ? launch_wino_mode<0, 0>(d, s) : launch_wino_mode<1, 0>(d, s);
 }
 
 }  // namespace mgu

@@ -299,12 +299,6 @@ __global__ __launch_bounds__(256 * CI_T, (X3 && CI_T == 1 && CO_T == 2) ? 2 : 1)
   ww_epilogue<CO_T, CI_T>(d, smem, acc, wi, wg, lane, lr, lh, cob, cib);
 }
 
-bool wino_wgrad_applicable(const WgradDesc& d) {
-  return tun(d).wino_wgrad && d.KS == 3 && d.Cp % 32 == 0 && d.N % 32 == 0 && d.K == 9 * d.Cp && (d.ldin & 3) == 0 && (d.ldz & 3) == 0 &&
-         (d.inoff & 3) == 0 && (d.zoff & 3) == 0 && (long)d.H * d.W * d.ldin < (1l << 31) && (long)d.H * d.W * d.ldz < (1l << 31) &&
-         d.dw_capacity >= (size_t)d.N * d.Kp;
-}
-
 template <int CO_T, int CI_T, bool X3>
 static hipError_t launch_ww_x(WgradDesc& d, hipStream_t s) {
   const int tiles_x = (d.W + 15) / 16, tiles_y = (d.H + 7) / 8;
@@ -330,22 +324,22 @@ static hipError_t launch_ww_x(WgradDesc& d, hipStream_t s) {
 }
 
 template <int CO_T, int CI_T>
-static hipError_t launch_ww(WgradDesc& d, hipStream_t s) {
+static hipError_t launch_ww(WgradDesc& d, bool x3, hipStream_t s) {
   if constexpr (CO_T == 2 && CI_T == 2) return launch_ww_x<2, 2, false>(d, s);   // three-piece mode never takes this tile (see below)
-  else return tun(d).wgrad_x3 ? launch_ww_x<CO_T, CI_T, true>(d, s) : launch_ww_x<CO_T, CI_T, false>(d, s);
+  else return x3 ? launch_ww_x<CO_T, CI_T, true>(d, s) : launch_ww_x<CO_T, CI_T, false>(d, s);
 }
 
-hipError_t launch_wino_wgrad_f32(WgradDesc& d, hipStream_t s) {
+hipError_t launch_wino_wgrad_f32(WgradDesc& d, bool x3, hipStream_t s) {
   const bool co2 = d.N % 64 == 0, ci2 = d.Cp % 64 == 0;
   // three-piece mode: the 64 x 64 tile needs 256 registers + spills (measured 28 % slower than its fp32-MFMA form), the 64 x 32
   // tile without register prefetch does not (254, two workgroups per CU cover each other's load phase).  A 64 x 64 tile with LDS-DMA
   // staging into a second LDS buffer (global_load_lds_dwordx4, XOR-swizzled dense images, counted vmcnt) was built and measured EQUAL
   // to it on every layer shape (88-92 us per 8.6 issued GFLOP either way): staging is not what bounds this kernel, VALU issue is
-  if (tun(d).wgrad_x3 && co2) return launch_ww_x<2, 1, true>(d, s);
-  if (co2 && ci2) return launch_ww<2, 2>(d, s);
-  if (co2) return launch_ww<2, 1>(d, s);
-  if (ci2) return launch_ww<1, 2>(d, s);
-  return launch_ww<1, 1>(d, s);
+  if (x3 && co2) return launch_ww_x<2, 1, true>(d, s);
+  if (co2 && ci2) return launch_ww<2, 2>(d, x3, s);
+  if (co2) return launch_ww<2, 1>(d, x3, s);
+  if (ci2) return launch_ww<1, 2>(d, x3, s);
+  return launch_ww<1, 1>(d, x3, s);
 }
 
 }  // namespace mgu

@@ -70,3 +70,155 @@ def test_plain_run_carries_cpu_baseline_and_other_configs(cuda):
     o = j["other_configs"]
     assert not any(k.endswith("_error") for k in o), o
     assert len(o) == 2 and all(v["ms_per_step"] > 0 and v["mpix_per_s"] > 0 for v in o.values())
+
+
+# Kernel-family labels of the profiling records (mgu_profile_read_kernels), which bench.py's kernel tables, dominant kernel and
+# traffic lookup key on.  One small U-Net (1 x 64 x 256, depth 4: Winograd assembly kernels on the upper levels, the C++ kernels on
+# the 4 x 16 bottleneck, the halo kernels under MGU_NO_WINOGRAD and in bf16) under each kernel-selection switch: forward, then one
+# train step (fp32 only), as (label, launches, pipe) in the order of first launch.
+FAMILY_CASES = {
+    "default": ({}, "f32", {
+        "forward": [
+            ["conv3x3_first_mfma_kernel", 1, 1],
+            ["mgu_wino_cp1r2_gfx950 (asm form of wino3x3_cp_kernel<1>)", 2, 1],
+            ["mgu_wino_cp2_gfx950 (asm form of wino3x3_cp_kernel<2>)", 12, 1],
+            ["wino3x3_cp_kernel<2>", 2, 1],
+            ["convt2x2_x3_kernel", 4, 1],
+            ["mgu_wino_cp1r4_gfx950 (asm form of wino3x3_cp_kernel<1>)", 1, 1],
+            ["conv1x1_head_kernel", 1, -1]],
+        "train": [
+            ["conv3x3_first_mfma_kernel", 1, 1],
+            ["wino3x3_cp_kernel<1>", 3, 1],
+            ["wino3x3_cp_kernel<2>", 14, 1],
+            ["convt2x2_x3_kernel", 4, 1],
+            ["wino_wgrad_f32_kernel<X3>", 17, 1],
+            ["wino3x3_cp_kernel<1> (dgrad)", 3, 1],
+            ["wino3x3_cp_kernel<2> (dgrad)", 14, 1],
+            ["convt2x2_x3_kernel (dgrad)", 4, 1],
+            ["wgrad_thin kernels", 1, -1]],
+    }),
+    "wino_asm_0": ({"MGU_WINO_ASM": "0"}, "f32", {
+        "forward": [
+            ["conv3x3_first_mfma_kernel", 1, 1],
+            ["wino3x3_cp_kernel<1>", 3, 1],
+            ["wino3x3_cp_kernel<2>", 14, 1],
+            ["convt2x2_x3_kernel", 4, 1],
+            ["conv1x1_head_kernel", 1, -1]],
+        "train": [
+            ["conv3x3_first_mfma_kernel", 1, 1],
+            ["wino3x3_cp_kernel<1>", 3, 1],
+            ["wino3x3_cp_kernel<2>", 14, 1],
+            ["convt2x2_x3_kernel", 4, 1],
+            ["wino_wgrad_f32_kernel<X3>", 17, 1],
+            ["wino3x3_cp_kernel<1> (dgrad)", 3, 1],
+            ["wino3x3_cp_kernel<2> (dgrad)", 14, 1],
+            ["convt2x2_x3_kernel (dgrad)", 4, 1],
+            ["wgrad_thin kernels", 1, -1]],
+    }),
+    "wino_prec_0": ({"MGU_WINO_PREC": "0"}, "f32", {
+        "forward": [
+            ["conv3x3_first_mfma_kernel", 1, 1],
+            ["wino3x3_f32_kernel<1,0>", 3, 0],
+            ["wino3x3_f32_kernel<0,0>", 14, 0],
+            ["igemm_kernel<f32> (ConvTranspose)", 4, 0],
+            ["conv1x1_head_kernel", 1, -1]],
+        "train": [
+            ["conv3x3_first_mfma_kernel", 1, 1],
+            ["wino3x3_f32_kernel<1,0>", 3, 0],
+            ["wino3x3_f32_kernel<0,0>", 14, 0],
+            ["igemm_kernel<f32> (ConvTranspose)", 4, 0],
+            ["wino_wgrad_f32_kernel<X3>", 17, 1],
+            ["wino3x3_f32_kernel<*,0> (dgrad)", 17, 0],
+            ["igemm_kernel<f32> (ConvTranspose dgrad)", 4, 0],
+            ["wgrad_thin kernels", 1, -1]],
+    }),
+    "no_winograd": ({"MGU_NO_WINOGRAD": "1"}, "f32", {
+        "forward": [
+            ["conv3x3_first_mfma_kernel", 1, 1],
+            ["conv3x3_halo_kernel<f32>", 17, 0],
+            ["convt2x2_x3_kernel", 4, 1],
+            ["conv1x1_head_kernel", 1, -1]],
+        "train": [
+            ["conv3x3_first_mfma_kernel", 1, 1],
+            ["conv3x3_halo_kernel<f32>", 17, 0],
+            ["convt2x2_x3_kernel", 4, 1],
+            ["wino_wgrad_f32_kernel<X3>", 17, 1],
+            ["igemm/halo (dgrad)", 17, 0],
+            ["convt2x2_x3_kernel (dgrad)", 4, 1],
+            ["wgrad_thin kernels", 1, -1]],
+    }),
+    "no_wino_dgrad": ({"MGU_NO_WINO_DGRAD": "1"}, "f32", {
+        "forward": [
+            ["conv3x3_first_mfma_kernel", 1, 1],
+            ["mgu_wino_cp1r2_gfx950 (asm form of wino3x3_cp_kernel<1>)", 2, 1],
+            ["mgu_wino_cp2_gfx950 (asm form of wino3x3_cp_kernel<2>)", 12, 1],
+            ["wino3x3_cp_kernel<2>", 2, 1],
+            ["convt2x2_x3_kernel", 4, 1],
+            ["mgu_wino_cp1r4_gfx950 (asm form of wino3x3_cp_kernel<1>)", 1, 1],
+            ["conv1x1_head_kernel", 1, -1]],
+        "train": [
+            ["conv3x3_first_mfma_kernel", 1, 1],
+            ["wino3x3_cp_kernel<1>", 3, 1],
+            ["wino3x3_cp_kernel<2>", 14, 1],
+            ["convt2x2_x3_kernel", 4, 1],
+            ["wino_wgrad_f32_kernel<X3>", 17, 1],
+            ["igemm/halo (dgrad)", 17, 0],
+            ["convt2x2_x3_kernel (dgrad)", 4, 1],
+            ["wgrad_thin kernels", 1, -1]],
+    }),
+    "bf16": ({}, "bf16", {
+        "forward": [
+            ["conv3x3_first_mfma_kernel", 1, 1],
+            ["conv3x3_halo_kernel<bf16>", 17, 1],
+            ["convt2x2_bf16_kernel", 4, 1],
+            ["conv1x1_head_kernel", 1, -1]],
+    }),
+    "bf16_no_convt_frag": ({"MGU_NO_CONVT_FRAG": "1"}, "bf16", {
+        "forward": [
+            ["conv3x3_first_mfma_kernel", 1, 1],
+            ["conv3x3_halo_kernel<bf16>", 17, 1],
+            ["igemm_kernel<bf16> (ConvTranspose)", 4, 1],
+            ["conv1x1_head_kernel", 1, -1]],
+    }),
+}
+
+
+def profiled_families(dev, dtype, train):
+    import torch
+    import mgunet
+    import mgunet_oracle as O
+    from mgunet import _lib
+    g = torch.Generator().manual_seed(7)
+    x = torch.randn(1, 3, 64, 256, generator=g).to(dev)
+    m = mgunet.UNet(3, 2, 32, 4, compute_dtype=torch.bfloat16 if dtype == "bf16" else torch.float32)
+    m.load_state_dict(O.make_unet_params(3, 2, 32, 4, seed=3))
+    m = m.to(dev).eval()
+    ctx, L = m._context(dev), _lib.lib()
+
+    def record(run):
+        run()
+        torch.cuda.synchronize(dev)
+        L.mgu_profile_enable(ctx.handle, 1)
+        run()
+        torch.cuda.synchronize(dev)
+        ks = _lib.read_kernel_stats(ctx)
+        L.mgu_profile_enable(ctx.handle, 0)
+        return [[k["name"], k["launches"], k["pipe"]] for k in ks]
+
+    with torch.no_grad():
+        out = {"forward": record(lambda: m(x))}
+    if train:
+        y = torch.randint(0, 2, (1, 64, 256), generator=g).to(dev)
+        tr = mgunet.Trainer(m.train())
+        out["train"] = record(lambda: tr.train_step(x, y))
+    return out
+
+
+@pytest.mark.parametrize("case", list(FAMILY_CASES))
+def test_profiled_kernel_families(cuda, monkeypatch, case):
+    env, dtype, want = FAMILY_CASES[case]
+    for k in ("MGU_WINO_ASM", "MGU_WINO_PREC", "MGU_NO_WINOGRAD", "MGU_NO_WINO_DGRAD", "MGU_NO_CONVT_FRAG"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)   # read when the model's context is created
+    assert profiled_families(cuda, dtype, dtype == "f32") == want
