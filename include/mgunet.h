@@ -402,6 +402,35 @@ int mgu_segmentation_eval(mgu_ctx* ctx, const void* logits_dev, const int64_t* l
 int mgu_confusion_matrix(mgu_ctx* ctx, const int64_t* true_dev, const int64_t* pred_dev, int64_t n, int num_classes,
                          int64_t* confusion_dev, void* hip_stream);
 
+/* ---- object counting: the instance step model/unet/shape_loss.py:43-91 leaves commented out (skimage.measure.label(mask,
+ *      connectivity=2, background=0)) and the object matching of experiments/metrics.py:160-253 yield_estimation_metrics -------------
+ * Connected components of B images of H x W.  src_kind 0: int64 class map (B, H*W); 1: NHWC fp32 logits (B,H,W,C) -- what
+ * mgu_unet_forward writes -- whose per-pixel class is the first maximal one (bit-identical to mgu_argmax_classes), computed in the
+ * first pass (no class map is written).  Two pixels join when they are neighbours (connectivity 1: 4-neighbours, 2: 8-neighbours),
+ * hold the same value and that value is foreground: != background and, when num_classes > 0, inside [0, num_classes) (so -100
+ * ignore labels are background).  Images never join.  labels_dev: int32 (B,H,W), 0 = background, objects 1..n_b per image in raster
+ * order of their first pixel (skimage.measure.label / scipy.ndimage.label numbering); deterministic.  Objects of fewer than
+ * min_area pixels become background and the rest are renumbered 1..n'.  counts_dev: int64 (B) objects per image; offsets_dev:
+ * int64 (B+1) exclusive prefix of counts (object k of image b has the batch-wide index offsets[b] + k - 1).  B*H*W < 2^31. */
+int mgu_connected_components(mgu_ctx* ctx, const void* src_dev, int src_kind, int B, int H, int W, int C, int connectivity, int64_t background,
+                             int64_t num_classes, int min_area, int32_t* labels_dev, int64_t* counts_dev, int64_t* offsets_dev,
+                             void* hip_stream);
+/* Per-object statistics of mgu_connected_components' labels (same src, src_kind, B, H, W, C; its offsets_dev), at batch-wide object
+ * index i < capacity (objects past capacity are skipped): class_dev int64 (the pixels' value / argmax class), area_dev int64,
+ * bbox_dev int32 (4): [xmin, ymin, xmax, ymax] with EXCLUSIVE max edges (w*h is the box area), sums_dev int64 (2): [sum x, sum y]
+ * (centroid = sums / area).  Integer atomics: exact and order-free.  area_dev and sums_dev may be NULL. */
+int mgu_object_stats(mgu_ctx* ctx, const int32_t* labels_dev, const void* src_dev, int src_kind, int B, int H, int W, int C,
+                     const int64_t* offsets_dev, int64_t capacity, int64_t* class_dev, int64_t* area_dev, int32_t* bbox_dev, int64_t* sums_dev,
+                     void* hip_stream);
+/* The greedy matching of metrics.py:215-240, one workgroup per image: predictions in object order (every confidence 1.0), each
+ * matched to the unused GT object of its class with the first strictly largest IoU (fp64 inter / (a1 + a2 - inter), 0.0 when they do
+ * not overlap) if that IoU is > 0 and >= iou_thresh.  Objects as mgu_object_stats writes them (offsets, class, bbox; capacity = the
+ * arrays' length; an image whose objects pass the capacity is skipped).  totals_dev int64 (3) ACCUMULATED: [GT objects, predicted
+ * objects, matched GT objects]. */
+int mgu_match_objects(mgu_ctx* ctx, int B, const int64_t* gt_offsets_dev, const int64_t* gt_class_dev, const int32_t* gt_bbox_dev,
+                      int64_t gt_capacity, const int64_t* pred_offsets_dev, const int64_t* pred_class_dev, const int32_t* pred_bbox_dev,
+                      int64_t pred_capacity, double iou_thresh, int64_t* totals_dev, void* hip_stream);
+
 /* ---- resize / gather building blocks of FeatureFusion (model/fusion_detection/feature_fusion.py:43-162) ----------------------------
  * F.interpolate(mode='bilinear', align_corners=False) (:69-76, :140-144) of an NHWC fp32 map (B,Hi,Wi,C) with pixel pitch ld_in into
  * channels [c_off, c_off + C) of a (B,Ho,Wo,ld_out) buffer -- i.e. straight into its slice of the fused tensor. */

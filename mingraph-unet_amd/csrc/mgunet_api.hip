@@ -98,6 +98,7 @@ void mgu_destroy(mgu_ctx* c) {
   if (c->redws) (void)hipFree(c->redws);
   if (c->wuws) (void)hipFree(c->wuws);
   if (c->ncws) (void)hipFree(c->ncws);
+  if (c->objws) (void)hipFree(c->objws);
   if (c->lossws) (void)hipFree(c->lossws);
   if (c->imgws) (void)hipFree(c->imgws);
   gat_destroy(c);

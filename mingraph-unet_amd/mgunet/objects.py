@@ -1,0 +1,270 @@
+"""Object counting and yield estimation: the instance step model/unet/shape_loss.py:43-91 leaves commented out
+(skimage.measure.label) and experiments/metrics.py:160-253 (yield_estimation_metrics).
+
+Connected components, per-object statistics and the reference's greedy box matching all run on the device (csrc/objects.hip);
+YieldEvaluator accumulates per-image counts and matching totals across batches without a host synchronisation, and the host only
+turns them into the reference's dictionary with the reference's own arithmetic (bitwise equal results).  There is no scipy or
+skimage dependency."""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _lib
+from .gat import _context
+
+
+@dataclass
+class ObjectTable:
+    """Objects of a batch, all on the device.  labels: int32 (B, H, W), 0 = background, objects 1..n_b per image in raster order of
+    their first pixel.  counts: int64 (B).  offsets: int64 (B + 1), object k of image b is row offsets[b] + k - 1 of the per-object
+    arrays: class_id int64 (N), area int64 (N), bbox int32 (N, 4) [xmin, ymin, xmax, ymax] with exclusive max edges, sums int64
+    (N, 2) [sum x, sum y] (centroid = sums / area)."""
+    labels: torch.Tensor
+    counts: torch.Tensor
+    offsets: torch.Tensor
+    class_id: torch.Tensor
+    area: torch.Tensor
+    bbox: torch.Tensor
+    sums: torch.Tensor
+
+    def to_dicts(self) -> list:
+        """The reference's per-image object lists: [[{'bbox': [xmin, ymin, xmax, ymax], 'class_id': int}, ...], ...]."""
+        off = self.offsets.cpu().tolist()
+        bbox, cls = self.bbox.cpu().tolist(), self.class_id.cpu().tolist()
+        return [[{"bbox": bbox[i], "class_id": cls[i]} for i in range(off[b], off[b + 1])] for b in range(len(off) - 1)]
+
+    def masks(self) -> list:
+        """object_masks_list of EllipticalShapeLoss: per image, one bool (H, W) device mask per object, in label order."""
+        counts = self.counts.cpu().tolist()
+        return [[self.labels[b] == k for k in range(1, n + 1)] for b, n in enumerate(counts)]
+
+
+def _stream(dev):
+    return _lib.current_stream_ptr(dev)
+
+
+def _source(x: torch.Tensor):
+    """(src tensor, kind, B, H, W, C): an int64 class map (kind 0) or the NHWC storage of (B, C, H, W) fp32 logits (kind 1)."""
+    if not x.is_cuda:
+        raise RuntimeError("connected components run only on a HIP device (no CPU fallback)")
+    if x.is_floating_point():
+        if x.dim() != 4 or x.dtype != torch.float32:
+            raise TypeError("logits must be (B, C, H, W) float32")
+        B, C, H, W = x.shape
+        nhwc = x.permute(0, 2, 3, 1)
+        if not nhwc.is_contiguous():
+            nhwc = nhwc.contiguous()
+        return nhwc, 1, B, H, W, C
+    if x.dtype == torch.bool or x.dim() not in (2, 3):
+        raise TypeError("a class map must be an integer (H, W) or (B, H, W) tensor")
+    m = x.reshape((1,) + tuple(x.shape)) if x.dim() == 2 else x
+    B, H, W = m.shape
+    return m.to(torch.int64).contiguous(), 0, B, H, W, 0
+
+
+def _label(src, kind, B, H, W, C, connectivity, background, num_classes, min_area, labels, counts, offsets):
+    ctx = _context(src.device)
+    with torch.cuda.device(src.device):
+        _lib.check(_lib.lib().mgu_connected_components(ctx.handle, src.data_ptr(), kind, B, H, W, C, int(connectivity), int(background),
+                                                       int(num_classes), int(min_area), labels.data_ptr(), counts.data_ptr(),
+                                                       offsets.data_ptr(), _stream(src.device)), ctx.handle)
+
+
+def _stats(labels, src, kind, B, H, W, C, offsets, capacity, cls, bbox, area=None, sums=None):
+    ctx = _context(src.device)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    with torch.cuda.device(src.device):
+        _lib.check(_lib.lib().mgu_object_stats(ctx.handle, labels.data_ptr(), src.data_ptr(), kind, B, H, W, C, offsets.data_ptr(),
+                                               int(capacity), cls.data_ptr(), ptr(area), bbox.data_ptr(), ptr(sums), _stream(src.device)),
+                   ctx.handle)
+
+
+def _check_args(connectivity, min_area):
+    if connectivity not in (1, 2):
+        raise ValueError(f"connectivity must be 1 (4-neighbours) or 2 (8-neighbours), got {connectivity}")
+    if min_area < 0:
+        raise ValueError("min_area must be >= 0")
+
+
+def connected_components(x: torch.Tensor, connectivity: int = 2, background: int = 0, min_area: int = 0) -> ObjectTable:
+    """skimage.measure.label(x, connectivity, background) per image, plus per-object statistics, on the device.
+
+    x: an integer class map (H, W) or (B, H, W) -- every value other than `background` is foreground, and pixels join when they are
+    neighbours holding the same value -- or (B, C, H, W) float32 logits (the NCHW view UNet.forward returns, its NHWC storage read in
+    place), whose per-pixel class is the first maximal one (= torch.argmax(x, 1)).  Objects smaller than min_area pixels become
+    background.  An (H, W) map is labelled as a batch of one.  Synchronises once, to size the per-object arrays."""
+    _check_args(connectivity, min_area)
+    src, kind, B, H, W, C = _source(x)
+    dev = src.device
+    labels = torch.empty((B, H, W), device=dev, dtype=torch.int32)
+    counts = torch.empty(B, device=dev, dtype=torch.int64)
+    offsets = torch.empty(B + 1, device=dev, dtype=torch.int64)
+    _label(src, kind, B, H, W, C, connectivity, background, 0, min_area, labels, counts, offsets)
+    N = int(offsets[B].item())
+    cls = torch.empty(N, device=dev, dtype=torch.int64)
+    area = torch.empty(N, device=dev, dtype=torch.int64)
+    bbox = torch.empty((N, 4), device=dev, dtype=torch.int32)
+    sums = torch.empty((N, 2), device=dev, dtype=torch.int64)
+    if N:
+        _stats(labels, src, kind, B, H, W, C, offsets, N, cls, bbox, area, sums)
+    return ObjectTable(labels, counts, offsets, cls, area, bbox, sums)
+
+
+def _iou(b1, b2) -> float:
+    """IoU of two [xmin, ymin, xmax, ymax] boxes, with the operation order of metrics.py:142-157."""
+    iw = max(0, min(b1[2], b2[2]) - max(b1[0], b2[0]))
+    ih = max(0, min(b1[3], b2[3]) - max(b1[1], b2[1]))
+    inter = iw * ih
+    if inter == 0:
+        return 0.0
+    a1 = (b1[2] - b1[0]) * (b1[3] - b1[1])
+    a2 = (b2[2] - b2[0]) * (b2[3] - b2[1])
+    return inter / (a1 + a2 - inter)
+
+
+def _match_host(gt_objects_list, pred_objects_list, thresh):
+    """The greedy loop of metrics.py:215-240: (total GT, matched GT, occluded GT, matched occluded GT)."""
+    n_gt = n_match = n_occ = n_occ_match = 0
+    for gts, preds in zip(gt_objects_list, pred_objects_list):
+        used = [False] * len(gts)
+        n_gt += len(gts)
+        n_occ += sum(1 for o in gts if o.get("occluded", False))
+        for p in sorted(preds, key=lambda o: o.get("confidence", 1.0), reverse=True):
+            best, best_j = 0, -1
+            for j, g in enumerate(gts):
+                if not used[j] and g["class_id"] == p["class_id"]:
+                    iou = _iou(p["bbox"], g["bbox"])
+                    if iou > best:
+                        best, best_j = iou, j
+            if best >= thresh and best_j != -1:
+                used[best_j] = True
+                n_match += 1
+                if gts[best_j].get("occluded", False):
+                    n_occ_match += 1
+    return n_gt, n_match, n_occ, n_occ_match
+
+
+def _yield_dict(gt_counts, pred_counts, match, smooth) -> dict:
+    """The arithmetic of metrics.py:178-253 given the matching totals (None: no object lists)."""
+    gt_counts = np.array(gt_counts)
+    pred_counts = np.array(pred_counts)
+    count_accuracy = (1.0 - np.abs(np.sum(pred_counts) - np.sum(gt_counts)) / (np.sum(gt_counts) + smooth)) * 100
+    valid = gt_counts > 0
+    if np.any(valid):
+        yield_error = np.mean(np.abs((gt_counts[valid] - pred_counts[valid]) / gt_counts[valid])) * 100
+    else:
+        yield_error = 0 if np.sum(np.abs(gt_counts - pred_counts)) == 0 else float("inf")
+    matching_rate, occlusion = -1.0, -1.0
+    if match is not None:
+        n_gt, n_match, n_occ, n_occ_match = match
+        matching_rate = (n_match / (n_gt + smooth)) * 100
+        occlusion = (n_occ_match / (n_occ + smooth)) * 100 if n_occ > 0 else -1.0
+    return {"count_accuracy_perc": count_accuracy, "yield_estimation_error_perc": yield_error,
+            "object_matching_rate_perc": matching_rate, "occlusion_robustness_perc": occlusion,
+            "total_gt_count_sum": np.sum(gt_counts), "total_pred_count_sum": np.sum(pred_counts)}
+
+
+def yield_estimation_metrics(gt_counts, pred_counts, gt_objects_list=None, pred_objects_list=None, matching_iou_thresh=0.5,
+                             smooth=1e-6) -> dict:
+    """experiments/metrics.py:160-253 yield_estimation_metrics: same arguments, same dictionary, same arithmetic (host numpy).
+    The reference reads an undefined `smooth` (NameError); here it is a keyword with segmentation_metrics' default 1e-6.  Boxes are
+    [xmin, ymin, xmax, ymax]; occlusion_robustness_perc stays -1.0 unless a GT object carries 'occluded': True."""
+    match = None
+    if gt_objects_list and pred_objects_list:
+        match = _match_host(gt_objects_list, pred_objects_list, matching_iou_thresh)
+    return _yield_dict(gt_counts, pred_counts, match, smooth)
+
+
+class YieldEvaluator:
+    """Device-side yield estimation over a test set.  update(logits, masks) labels the predicted objects (argmax fused into the
+    labelling) and the GT objects (mask values in [1, num_classes); 0, -100 and anything out of range are background), appends the
+    per-image counts to device buffers and accumulates the matching totals; it never blocks the host.  min_area applies to the
+    predicted objects.  compute() synchronises once and returns yield_estimation_metrics' dictionary -- equal to calling it on the
+    per-image counts and to_dicts() of the same batches."""
+
+    def __init__(self, num_classes: int, device, connectivity: int = 2, min_area: int = 0, iou_thresh: float = 0.5, smooth: float = 1e-6):
+        _check_args(connectivity, min_area)
+        self.num_classes, self.device = int(num_classes), torch.device(device)
+        if self.num_classes < 1:
+            raise ValueError("num_classes must be >= 1")
+        if self.device.type != "cuda":
+            raise RuntimeError("YieldEvaluator runs only on a HIP device (no CPU fallback)")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.connectivity, self.min_area = connectivity, int(min_area)
+        self.iou_thresh, self.smooth = float(iou_thresh), smooth
+        self._bufs, self._cap = None, -1
+        self.reset()
+
+    def reset(self) -> None:
+        self.totals = torch.zeros(3, device=self.device, dtype=torch.int64)   # GT objects, predicted objects, matched GT objects
+        self.gt_counts, self.pred_counts = [], []
+
+    def _buffers(self, B, H, W):
+        n = B * H * W
+        if n > self._cap:   # per-object arrays sized for the worst case (every pixel its own object): no host synchronisation
+            mk = lambda shape, dt: torch.empty(shape, device=self.device, dtype=dt)  # noqa: E731
+            self._bufs = {s: (mk(n, torch.int32), mk(n, torch.int64), mk((n, 4), torch.int32)) for s in ("gt", "pred")}
+            self._cap = n
+        return self._bufs
+
+    def update(self, logits_nchw: torch.Tensor, masks: torch.Tensor) -> None:
+        """Add one batch: logits (B, C, H, W) float32 -- the view UNet.forward returns -- and integer masks (B, H, W)."""
+        if not logits_nchw.is_cuda or logits_nchw.device != self.device:
+            raise RuntimeError(f"logits must live on {self.device}")
+        src, kind, B, H, W, C = _source(logits_nchw)
+        if kind != 1:
+            raise TypeError("expected (B, C, H, W) float32 logits")
+        if C != self.num_classes:
+            raise ValueError(f"logits have {C} classes, the evaluator {self.num_classes}")
+        if tuple(masks.shape) != (B, H, W):
+            raise ValueError(f"masks shape {tuple(masks.shape)} does not match logits {(B, H, W)}")
+        masks = masks.to(self.device, torch.int64).contiguous()
+        bufs = self._buffers(B, H, W)
+        counts, offsets = {}, {}
+        for side, s, k, cc, ncls, amin in (("gt", masks, 0, 0, self.num_classes, 0), ("pred", src, 1, C, 0, self.min_area)):
+            lab, cls, bbox = bufs[side]
+            lab = lab[:B * H * W].view(B, H, W)
+            counts[side] = torch.empty(B, device=self.device, dtype=torch.int64)
+            offsets[side] = torch.empty(B + 1, device=self.device, dtype=torch.int64)
+            _label(s, k, B, H, W, cc, self.connectivity, 0, ncls, amin, lab, counts[side], offsets[side])
+            _stats(lab, s, k, B, H, W, cc, offsets[side], self._cap, cls, bbox)
+        ctx = _context(self.device)
+        (gl, gc, gb), (pl, pc, pb) = bufs["gt"], bufs["pred"]
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().mgu_match_objects(ctx.handle, B, offsets["gt"].data_ptr(), gc.data_ptr(), gb.data_ptr(), self._cap,
+                                                    offsets["pred"].data_ptr(), pc.data_ptr(), pb.data_ptr(), self._cap, self.iou_thresh,
+                                                    self.totals.data_ptr(), _stream(self.device)), ctx.handle)
+        self.gt_counts.append(counts["gt"])
+        self.pred_counts.append(counts["pred"])
+
+    def compute(self) -> dict:
+        """Synchronise once and return yield_estimation_metrics' dictionary over every batch since the last reset()."""
+        if not self.gt_counts:
+            return yield_estimation_metrics([], [], smooth=self.smooth)
+        gt = torch.cat(self.gt_counts).cpu().tolist()
+        pred = torch.cat(self.pred_counts).cpu().tolist()
+        n_gt, _, n_match = self.totals.cpu().tolist()
+        return _yield_dict(gt, pred, (n_gt, n_match, 0, 0), self.smooth)
+
+
+def evaluate_yield(model, loader, num_classes=None, connectivity=2, min_area=0, iou_thresh=0.5, smooth=1e-6) -> dict:
+    """Yield estimation over `loader`'s (images, masks) batches: logits = model(images) under torch.no_grad() in eval mode, objects
+    labelled and matched on the device.  Returns yield_estimation_metrics' dictionary; the model's training flag is restored."""
+    dev = next(model.parameters()).device
+    C = int(num_classes if num_classes is not None else model.num_classes)
+    ev = YieldEvaluator(C, dev, connectivity=connectivity, min_area=min_area, iou_thresh=iou_thresh, smooth=smooth)
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            for images, masks in loader:
+                out = model(images.to(dev))
+                logits = out[0] if isinstance(out, (tuple, list)) else out
+                ev.update(logits, masks.to(dev))
+        return ev.compute()
+    finally:
+        model.train(was_training)
