@@ -430,6 +430,30 @@ int mgu_object_stats(mgu_ctx* ctx, const int32_t* labels_dev, const void* src_de
 int mgu_match_objects(mgu_ctx* ctx, int B, const int64_t* gt_offsets_dev, const int64_t* gt_class_dev, const int32_t* gt_bbox_dev,
                       int64_t gt_capacity, const int64_t* pred_offsets_dev, const int64_t* pred_class_dev, const int32_t* pred_bbox_dev,
                       int64_t pred_capacity, double iou_thresh, int64_t* totals_dev, void* hip_stream);
+/* Per-object confidence: scores_dev[i] (fp32) = the mean over object i's pixels of probs[pixel][class_dev[i]], for the objects of
+ * mgu_connected_components' labels_dev / offsets_dev and mgu_object_stats' class_dev / area_dev at batch-wide index i < capacity.
+ * probs_dev: NHWC fp32 (B,H,W,C), values clamped to [0, 1]; an object whose class lies outside [0, C) scores 0.  Each pixel adds
+ * round_half_even(p * 2^32) to a uint64 sum with integer atomics (exact and order-free: deterministic); the score is
+ * (sum * 2^-32) / area in fp64, rounded to fp32.  B*H*W < 2^31. */
+int mgu_object_scores(mgu_ctx* ctx, const int32_t* labels_dev, const float* probs_dev, int B, int H, int W, int C, const int64_t* offsets_dev,
+                      int64_t capacity, const int64_t* class_dev, const int64_t* area_dev, float* scores_dev, void* hip_stream);
+
+/* ---- test-time augmentation: flipped / rotated views of a batch and the mean of their softmaxes ----------------------------------
+ * A view is the image flipped (flip bit 0: along W, torch.flip(x, (3,)); bit 1: along H, torch.flip(x, (2,))) and then turned r
+ * quarter turns (torch.rot90(x, r, (2, 3))); r odd swaps H and W.  mgunet.tta.view_table lists the views of each transform set.
+ * Views: writes G views of the (B,C,H,W) fp32 batch img_dev (element (b,c,y,x) at [b*s[0] + c*s[1] + y*s[2] + x*s[3]], in_strides a
+ * HOST array of 4) as one contiguous NCHW batch (G*B, C, Hv, Wv), view-major (view k of the call, then image b).  views: HOST int32
+ * (G, 2) rows {flip, r}; all G views must have the same shape (r of one parity unless H == W).  G <= 8, G*B <= 65535. */
+int mgu_tta_views(mgu_ctx* ctx, const float* img_dev, int B, int C, int H, int W, const int64_t* in_strides, int G, const int32_t* views,
+                  float* out_dev, void* hip_stream);
+/* Merge: for every output pixel (b, y, x) and view k (in order), the softmax (fp32, maximum subtracted, expf) of the C logits of the
+ * view pixel that the view's transform moved (y, x) to, summed in fp32 and multiplied by 1/K.  The logits are the NHWC output of the
+ * forward of each shape group: group 0 = the views with r even (every view when H == W), (G0*B, H, W, C); group 1 = the views with r
+ * odd when H != W, (G1*B, W, H, C) (logits1_dev may be NULL when no view is in it).  views: HOST int32 (K, 4) rows {group, slot, flip,
+ * r}: view k is image slot*B + b of its group.  K in {1, 2, 4, 8}, C <= 16.  Writes probs_dev NHWC fp32 (B,H,W,C), labels_dev
+ * int64 (B,H,W) = the first maximal class, conf_dev fp32 (B,H,W) = its probability. */
+int mgu_tta_merge(mgu_ctx* ctx, const float* logits0_dev, const float* logits1_dev, int B, int C, int H, int W, int K, const int32_t* views,
+                  float* probs_dev, int64_t* labels_dev, float* conf_dev, void* hip_stream);
 
 /* ---- resize / gather building blocks of FeatureFusion (model/fusion_detection/feature_fusion.py:43-162) ----------------------------
  * F.interpolate(mode='bilinear', align_corners=False) (:69-76, :140-144) of an NHWC fp32 map (B,Hi,Wi,C) with pixel pitch ld_in into

@@ -4,6 +4,7 @@
 //                             objects 1..n_b per image in raster order of their first pixel; counts (B) and offsets (B + 1)
 //   mgu_object_stats          per object: class, area, bbox [xmin, ymin, xmax, ymax) and the coordinate sums, all integer
 //   mgu_match_objects         the reference's greedy IoU matching, one workgroup per image; int64 totals accumulated
+//   mgu_object_scores         per object: the mean probability of its class over its pixels (fixed-point integer sums, fp32 result)
 // Labelling is block union-find: (1) a 32 x 32 tile joins its pixels in LDS, (2) tile borders are joined in global memory,
 // (3) every pixel points straight at its root, (4) roots are numbered by a per-image scan of root flags in raster order.  Every
 // union hooks the larger root under the smaller one with atomicMin, so each root ends as its component's smallest linear index:
@@ -346,6 +347,56 @@ __global__ __launch_bounds__(OB_THREADS) void stats_kernel(const int* __restrict
   }
 }
 
+// ---- per-object confidence: mean probability of the object's class over its pixels ----------------------------------------------
+__global__ __launch_bounds__(OB_THREADS) void scores_init_kernel(const long long* __restrict__ offsets, int B, int64_t cap,
+                                                                 unsigned long long* __restrict__ acc) {
+  const int64_t n = offsets[B] < cap ? offsets[B] : cap;
+  for (int64_t i = (int64_t)blockIdx.x * OB_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * OB_THREADS) acc[i] = 0;
+}
+
+// one thread per pixel: the probability of its object's class, clamped to [0, 1], as the fixed-point integer round_half_even(p * 2^32)
+// (exact in fp64); summed inside the wave per object as stats_kernel does, then one integer atomic per object and wave
+__global__ __launch_bounds__(OB_THREADS) void scores_kernel(const int* __restrict__ labels, const float* __restrict__ probs, int C, int64_t HW,
+                                                            int64_t n, const long long* __restrict__ offsets, int64_t cap,
+                                                            const long long* __restrict__ cls, unsigned long long* __restrict__ acc) {
+  const int64_t g = (int64_t)blockIdx.x * OB_THREADS + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  long long obj = -1;
+  unsigned long long q = 0;
+  if (g < n) {
+    const int lab = labels[g];
+    const int64_t b = g / HW;
+    if (lab > 0) obj = offsets[b] + lab - 1;
+    if (obj >= cap) obj = -1;
+    if (obj >= 0) {
+      const long long k = cls[obj];
+      const float p = (k >= 0 && k < C) ? fminf(fmaxf(probs[g * C + k], 0.f), 1.f) : 0.f;
+      q = __double2ull_rn((double)p * 4294967296.0);
+    }
+  }
+  bool pending = obj >= 0;
+  for (int it = 0; it < LEADER_ROUNDS; ++it) {
+    const unsigned long long act = __ballot(pending);
+    if (!act) break;
+    const int leader = __ffsll((long long)act) - 1;
+    const long long lo = __shfl(obj, leader);
+    const bool mine = pending && obj == lo;
+    const unsigned long long s = wave_sum<unsigned long long>(mine ? q : 0ull);
+    if (lane == leader) atomicAdd(&acc[lo], s);
+    if (mine) pending = false;
+  }
+  if (pending) atomicAdd(&acc[obj], q);
+}
+
+// score = (acc * 2^-32) / area in fp64, rounded to fp32
+__global__ __launch_bounds__(OB_THREADS) void scores_finish_kernel(const long long* __restrict__ offsets, int B, int64_t cap,
+                                                                   const unsigned long long* __restrict__ acc, const long long* __restrict__ area,
+                                                                   float* __restrict__ scores) {
+  const int64_t n = offsets[B] < cap ? offsets[B] : cap;
+  for (int64_t i = (int64_t)blockIdx.x * OB_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * OB_THREADS)
+    scores[i] = area[i] > 0 ? (float)(((double)acc[i] * 0x1p-32) / (double)area[i]) : 0.f;
+}
+
 // ---- greedy matching (metrics.py:215-240), one wave per image ---------------------------------------------------------------------
 // Predictions in object order (every confidence 1.0: the stable sort keeps list order); for each, the unused GT objects of its class
 // are scored by IoU (fp64, inter / (a1 + a2 - inter), = Python's correctly rounded int / int); the first strictly larger IoU wins
@@ -484,6 +535,33 @@ int mgu_object_stats(mgu_ctx* c, const int32_t* labels_dev, const void* src_dev,
   else
     hipLaunchKernelGGL(stats_kernel<1>, dim3(pixblocks), dim3(OB_THREADS), 0, s, labels_dev, src_dev, C, W, HW, n, off, capacity,
                        (long long*)class_dev, ar, bbox_dev, su);
+  HIPCHK(c, hipGetLastError());
+  return MGU_OK;
+}
+
+int mgu_object_scores(mgu_ctx* c, const int32_t* labels_dev, const float* probs_dev, int B, int H, int W, int C, const int64_t* offsets_dev,
+                      int64_t capacity, const int64_t* class_dev, const int64_t* area_dev, float* scores_dev, void* hip_stream) {
+  if (!c) return MGU_ERR_INVALID;
+  if (!labels_dev || !probs_dev || !offsets_dev || !class_dev || !area_dev || !scores_dev || B < 0 || H < 0 || W < 0 || C < 1 || capacity < 0)
+    return fail(c, MGU_ERR_INVALID, "bad object_scores args (null pointer, negative size or C < 1)");
+  if ((double)B * H * W >= (double)INT_MAX) return fail(c, MGU_ERR_INVALID, "object_scores: B*H*W must stay below 2^31");
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)hip_stream;
+  const int64_t HW = (int64_t)H * W, n = (int64_t)B * HW;
+  if (capacity == 0) return MGU_OK;
+  int rc = ensure(c, &c->objws, &c->objws_bytes, (size_t)capacity * 8);
+  if (rc) return rc;
+  unsigned long long* acc = (unsigned long long*)c->objws;
+  const long long* off = (const long long*)offsets_dev;
+  const unsigned objblocks = (unsigned)std::min<int64_t>(1024, (capacity + OB_THREADS - 1) / OB_THREADS);
+  hipLaunchKernelGGL(scores_init_kernel, dim3(objblocks), dim3(OB_THREADS), 0, s, off, B, capacity, acc);
+  if (n > 0) {
+    const unsigned pixblocks = (unsigned)((n + OB_THREADS - 1) / OB_THREADS);
+    hipLaunchKernelGGL(scores_kernel, dim3(pixblocks), dim3(OB_THREADS), 0, s, labels_dev, probs_dev, C, HW, n, off, capacity,
+                       (const long long*)class_dev, acc);
+  }
+  hipLaunchKernelGGL(scores_finish_kernel, dim3(objblocks), dim3(OB_THREADS), 0, s, off, B, capacity, acc, (const long long*)area_dev,
+                     scores_dev);
   HIPCHK(c, hipGetLastError());
   return MGU_OK;
 }

@@ -30,11 +30,19 @@ class ObjectTable:
     bbox: torch.Tensor
     sums: torch.Tensor
 
-    def to_dicts(self) -> list:
-        """The reference's per-image object lists: [[{'bbox': [xmin, ymin, xmax, ymax], 'class_id': int}, ...], ...]."""
+    def to_dicts(self, scores=None) -> list:
+        """The reference's per-image object lists: [[{'bbox': [xmin, ymin, xmax, ymax], 'class_id': int}, ...], ...].  With scores
+        (one float per object in row order, e.g. mgunet.object_scores), every dict also carries 'confidence': float, the key
+        yield_estimation_metrics sorts predictions by."""
         off = self.offsets.cpu().tolist()
         bbox, cls = self.bbox.cpu().tolist(), self.class_id.cpu().tolist()
-        return [[{"bbox": bbox[i], "class_id": cls[i]} for i in range(off[b], off[b + 1])] for b in range(len(off) - 1)]
+        if scores is None:
+            return [[{"bbox": bbox[i], "class_id": cls[i]} for i in range(off[b], off[b + 1])] for b in range(len(off) - 1)]
+        conf = scores.cpu().tolist() if isinstance(scores, torch.Tensor) else [float(v) for v in scores]
+        if len(conf) != len(cls):
+            raise ValueError(f"{len(conf)} scores for {len(cls)} objects")
+        return [[{"bbox": bbox[i], "class_id": cls[i], "confidence": conf[i]} for i in range(off[b], off[b + 1])]
+                for b in range(len(off) - 1)]
 
     def masks(self) -> list:
         """object_masks_list of EllipticalShapeLoss: per image, one bool (H, W) device mask per object, in label order."""
