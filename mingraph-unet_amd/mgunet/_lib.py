@@ -1,12 +1,15 @@
-"""ctypes binding of libmgunet.so (include/mgunet.h).  No torch types cross this boundary: only
-device pointers (tensor.data_ptr()), sizes and the HIP stream handle.  There is no CPU fallback:
-if the shared library is missing or no HIP device exists, every call raises."""
+"""ctypes binding of libmgunet.so.  The prototypes are read from include/mgunet.h itself; `call` is the one path from the modules
+to an entry point: no torch types cross the boundary, only device pointers (tensor.data_ptr()), sizes and the HIP stream handle.
+There is no CPU fallback: if the shared library is missing or no HIP device exists, every call raises."""
 from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import subprocess
 import threading
+
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 PKG_ROOT = os.path.dirname(_HERE)                      # .../mingraph-unet_amd
@@ -38,158 +41,37 @@ def read_kernel_stats(ctx) -> list:
 _lib = None
 _lock = threading.Lock()
 
-# name -> (restype, argtypes); must list every symbol include/mgunet.h declares (tests check this)
-_PROTOS = {
-    "mgu_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
-    "mgu_destroy": (None, [C.c_void_p]),
-    "mgu_last_error": (C.c_char_p, [C.c_void_p]),
-    "mgu_version": (C.c_char_p, []),
-    "mgu_unet_configure": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
-    "mgu_unet_param_count": (C.c_int64, [C.c_void_p]),
-    "mgu_unet_load_weights": (C.c_int, [C.c_void_p, C.POINTER(TensorDesc), C.c_int, C.c_void_p]),
-    "mgu_unet_refresh_weights": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "mgu_unet_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
-    "mgu_unet_reserve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
-    "mgu_unet_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64,
-                                   C.c_int64, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int,
-                                   C.c_void_p]),
-    "mgu_unet_param_offset": (C.c_int64, [C.c_void_p, C.c_char_p]),
-    "mgu_cross_entropy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_void_p,
-                                    C.c_void_p, C.c_void_p]),
-    "mgu_sync_check": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "mgu_unet_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mgu_comm_get_unique_id": (C.c_int, [C.c_void_p]),
-    "mgu_comm_init_rank": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
-    "mgu_comm_destroy": (C.c_int, [C.c_void_p]),
-    "mgu_comm_handle": (C.c_void_p, [C.c_void_p]),
-    "mgu_comm_world_size": (C.c_int, [C.c_void_p]),
-    "mgu_allreduce_grads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "mgu_unet_backward_allreduce": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mgu_conv2d_wgrad_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                        C.c_void_p, C.c_void_p]),
-    "mgu_conv2d_dgrad_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                        C.c_void_p, C.c_int, C.c_void_p]),
-    "mgu_conv_transpose2x2_wgrad_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                   C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mgu_conv_transpose2x2_dgrad_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                                   C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "mgu_bn_relu_train_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mgu_bn_relu_backward_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mgu_maxpool2x2_backward_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                               C.c_int, C.c_int, C.c_void_p]),
-    "mgu_sgd_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int,
-                               C.c_float, C.c_void_p]),
-    "mgu_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float,
-                                C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_void_p]),
-    "mgu_conv2d_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                  C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                  C.c_void_p]),
-    "mgu_conv2d_prepare": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
-    "mgu_conv2d_release": (None, [C.c_void_p, C.c_void_p]),
-    "mgu_conv2d_prepared_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
-    "mgu_conv_transpose2x2_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                             C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
-    "mgu_maxpool2x2_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                      C.c_void_p]),
-    "mgu_argmax_classes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
-    "mgu_patch_graph_build": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "mgu_coo_to_csr": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
-    "mgu_coo_to_csr_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mgu_csr_transpose_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mgu_gat_layer_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mgu_gat_layer_backward_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mgu_gat_layer_forward_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
-                                              C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
-                                              C.c_void_p]),
-    "mgu_dropout_mask": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
-    "mgu_patch_mean": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                 C.c_void_p]),
-    "mgu_gat_layer_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
-                                        C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                        C.c_float, C.c_void_p, C.c_void_p]),
-    "mgu_gat_prepare": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
-    "mgu_gat_release": (None, [C.c_void_p, C.c_void_p]),
-    "mgu_gat_layer_forward_prepared": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                                 C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
-    "mgu_ncut_edge_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "mgu_ncut_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                   C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mgu_ncut_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                    C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mgu_relu_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "mgu_region_mean_pool": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "mgu_region_fuse_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                       C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "mgu_tv_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
-                              C.c_float, C.c_void_p, C.c_void_p]),
-    "mgu_dice_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int64,
-                                C.c_float, C.c_void_p, C.c_void_p]),
-    "mgu_feature_consistency_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
-                                               C.c_void_p, C.c_void_p]),
-    "mgu_tv_loss_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
-                                       C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
-    "mgu_dice_loss_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int64,
-                                         C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p,
-                                         C.c_void_p]),
-    "mgu_feature_consistency_loss_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
-                                                        C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mgu_loss_sync_check": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "mgu_elliptical_shape_loss_masks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
-    "mgu_elliptical_shape_loss_probs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
-                                                  C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
-    "mgu_segmentation_eval": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                        C.c_float, C.c_void_p, C.c_void_p]),
-    "mgu_confusion_matrix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
-    "mgu_connected_components": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64,
-                                           C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mgu_object_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64,
-                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mgu_match_objects": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_int64, C.c_double, C.c_void_p, C.c_void_p]),
-    "mgu_object_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64,
-                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mgu_tta_views": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int,
-                                C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
-    "mgu_tta_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32),
-                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mgu_resize_bilinear_nhwc":(C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                           C.c_int, C.c_int, C.c_void_p]),
-    "mgu_region_map_gather_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int,
-                                             C.c_void_p]),
-    "mgu_preprocess_image_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float),
-                                          C.POINTER(C.c_float), C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
-    "mgu_preprocess_mask_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "mgu_augment_flip_rotate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64),
-                                          C.POINTER(C.c_int64), C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                          C.c_void_p]),
-    "mgu_preprocess_image_u8_aug": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                              C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int,
-                                              C.POINTER(C.c_int32), C.c_void_p]),
-    "mgu_preprocess_mask_u8_aug": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                             C.POINTER(C.c_int32), C.c_int64, C.c_void_p, C.c_void_p]),
-    "mgu_sobel_edges_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "mgu_equalize_hist_rgb_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "mgu_patch_mean_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "mgu_colorize_labels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mgu_channel_affine_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                          C.c_void_p, C.c_int, C.c_void_p]),
-    "mgu_channel_sum_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
-    "mgu_channel_sum_images_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
-    "mgu_unet_request_patch_mean": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
-    "mgu_unet_flops": (C.c_double, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
-    "mgu_unet_mfma_flops": (C.c_double, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
-    "mgu_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
-    "mgu_profile_read_kernels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
-    "mgu_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double)]),
-}
+HEADER = os.path.join(os.path.dirname(PKG_ROOT), "include", "mgunet.h")
+_CTYPES = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "unsigned long long": C.c_uint64, "float": C.c_float,
+           "double": C.c_double, "size_t": C.c_size_t, "void": None, "char*": C.c_char_p, "mgu_tensor_desc*": C.POINTER(TensorDesc)}
+
+
+def _ctype(t: str, decl: str):
+    t = re.sub(r"\s*\*", "*", " ".join(re.sub(r"\bconst\b", "", t).split()))   # "void* const*" -> "void**"
+    if t in _CTYPES:
+        return _CTYPES[t]
+    if t.endswith("*"):                                                   # every other pointer, host or device
+        return C.c_void_p
+    raise TypeError(f"mgunet.h: no ctypes type for '{t}' in `{decl}`")
+
+
+def parse_header(path: str = HEADER) -> dict:
+    """name -> (restype, argtypes, takes_stream) of every `ret mgu_name(params);` the header declares; takes_stream: the last
+    parameter is `hip_stream`."""
+    txt = re.sub(r"/\*.*?\*/|//[^\n]*|^\s*#[^\n]*", "", open(path).read(), flags=re.S | re.M)
+    protos = {}
+    for m in re.finditer(r"([\w\s*]+?)\b(mgu_\w+)\s*\(([^)]*)\)\s*;", txt):
+        ret, name, params = m.groups()
+        decl = " ".join(m.group(0).split())
+        ps = [re.fullmatch(r"(.+?)\s*\b(\w+)", p.strip()) for p in params.split(",")] if params.strip() not in ("", "void") else []
+        if not all(ps):
+            raise TypeError(f"mgunet.h: unnamed parameter in `{decl}`")
+        protos[name] = (_ctype(ret, decl), [_ctype(p[1], decl) for p in ps], bool(ps) and ps[-1][2] == "hip_stream")
+    return protos
+
+
+_PROTOS = {}   # parse_header(), installed by lib()
+_CALLS = {}    # name -> (function, takes_stream)
 
 
 def build(verbose: bool = False) -> str:
@@ -212,9 +94,11 @@ def lib() -> C.CDLL:
                 raise RuntimeError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                                    "(or `make -C mingraph-unet_amd/csrc`).  There is no CPU fallback.")
             L = C.CDLL(LIB_PATH)
-            for name, (res, args) in _PROTOS.items():
+            _PROTOS.update(parse_header())
+            for name, (res, args, takes_stream) in _PROTOS.items():
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = res, args
+                _CALLS[name] = (fn, takes_stream)
             _lib = L
     return _lib
 
@@ -249,6 +133,61 @@ class Context:
             pass
 
 
+_CTX = {}
+
+
+def context(device: torch.device) -> Context:
+    """The Context shared by everything on `device` that does not configure one of its own (the UNet does)."""
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    ctx = _CTX.get(idx)
+    if ctx is None:
+        ctx = _CTX[idx] = Context(idx)
+    return ctx
+
+
 def current_stream_ptr(device) -> int:
-    import torch
     return int(torch.cuda.current_stream(device).cuda_stream)
+
+
+def call(name: str, device, *args, ctx: Context = None) -> None:
+    """Run the status-returning entry point `name` on `device` (the device of `ctx` when one is given) and raise on failure.  The
+    context (the shared one unless `ctx` is given) goes first, a tensor argument as its data_ptr(), the device's current stream
+    last where the prototype ends in `hip_stream`.  device=None: a host routine, which takes neither a context nor a stream."""
+    if _lib is None:
+        lib()
+    fn, takes_stream = _CALLS[name]
+    if device is None:
+        check(fn(*args))
+        return
+    if ctx is None:
+        ctx = context(device)
+    idx = ctx.device_index
+    args = [a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args]
+    with torch.cuda.device(idx):
+        if takes_stream:
+            args.append(torch.cuda.current_stream(idx).cuda_stream)
+        check(fn(ctx.handle, *args), ctx.handle)
+
+
+def require_hip(t, what: str) -> None:
+    """Raise unless the tensor (or torch.device) `t` is on a HIP device."""
+    if (t if isinstance(t, torch.device) else t.device).type != "cuda":
+        raise RuntimeError(f"{what} runs only on a HIP device (MI355X); there is deliberately no CPU fallback")
+
+
+class Prepared:
+    """A prepared-weights handle (mgu_gat_prepare / mgu_conv2d_prepare: `prepare(..., &out, hip_stream)`), released with the object.
+    `key` records what it was prepared from."""
+
+    def __init__(self, prepare: str, device, *args, ctx: Context = None, key=None):
+        self.ctx = ctx if ctx is not None else context(device)
+        self.release, self.key, self.handle = prepare.replace("_prepare", "_release"), key, C.c_void_p()
+        call(prepare, device, *args, C.byref(self.handle), ctx=self.ctx)
+
+    def __del__(self):
+        try:
+            if self.handle:
+                getattr(lib(), self.release)(self.ctx.handle, self.handle)
+                self.handle = C.c_void_p()
+        except Exception:
+            pass

@@ -9,7 +9,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .gat import GATNetwork, _context, _csr_cache, prepared_head_weights, stacked_head_weights
+from .gat import GATNetwork, _csr_cache, prepared_head_weights, stacked_head_weights
 from .patch_graph import PatchGraphConstructor
 from .unet import UNet
 
@@ -35,12 +35,12 @@ class MinGraphUNet(nn.Module):
             X = torch.empty((B * ((H + p - 1) // p) * ((W + p - 1) // p), self.unet.init_features), device=x.device,
                             dtype=torch.float32)
             ctx = self.unet._context(x.device)
-            _lib.check(_lib.lib().mgu_unet_request_patch_mean(ctx.handle, p, X.data_ptr()), ctx.handle)
+            _lib.call("mgu_unet_request_patch_mean", x.device, p, X, ctx=ctx)
         try:
             logits, skips, feats = self.unet(x)
         except Exception:
             if X is not None:   # the forward was rejected before it could serve the request: cancel it
-                _lib.lib().mgu_unet_request_patch_mean(ctx.handle, 0, None)
+                _lib.call("mgu_unet_request_patch_mean", x.device, 0, None, ctx=ctx)
             raise
         if X is None:
             X = self.graph.patch_mean_features(feats[0])
@@ -93,7 +93,6 @@ def gat_forward_csr(gat: GATNetwork, X, rowptr, col, graph_ptr):
     """GATNetwork.forward on a prebuilt device CSR (skips the COO->CSR conversion of the COO API)."""
     h = X
     dev = X.device
-    ctx = _context(dev)
     G = graph_ptr.numel() - 1 if graph_ptr is not None else 1
     for layer in gat.gat_layers:
         if layer.training and layer.dropout_rate > 0:
@@ -106,30 +105,20 @@ def gat_forward_csr(gat: GATNetwork, X, rowptr, col, graph_ptr):
             raise ValueError("node feature width must be a multiple of 4 and match W")
         h = h.contiguous()
         out = torch.empty((h.shape[0], H * Fh if layer.concat else Fh), device=dev, dtype=torch.float32)
-        handle = prepared_head_weights(heads, _csr_cache(layer), ctx, dev, col.numel() > 0)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().mgu_gat_layer_forward_prepared(ctx.handle, handle, h.data_ptr(), h.shape[0], rowptr.data_ptr(),
-                                                           col.data_ptr() if col.numel() else None, col.numel(),
-                                                           graph_ptr.data_ptr() if graph_ptr is not None else None, G,
-                                                           1 if layer.concat else 0, float(layer.alpha), out.data_ptr(),
-                                                           _lib.current_stream_ptr(dev))
-        _lib.check(rc, ctx.handle)
+        handle = prepared_head_weights(heads, _csr_cache(layer), dev, col.numel() > 0)
+        _lib.call("mgu_gat_layer_forward_prepared", dev, handle, h, h.shape[0], rowptr, col if col.numel() else None, col.numel(),
+                  graph_ptr, G, 1 if layer.concat else 0, float(layer.alpha), out)
         h = out
     return h
 
 
 def argmax_classes(logits_nchw: torch.Tensor) -> torch.Tensor:
     """torch.argmax(seg_logits, dim=1) of segmentation_performance.py:141 on the GPU (NHWC logits)."""
-    if not logits_nchw.is_cuda:
-        raise RuntimeError("argmax_classes runs only on a HIP device")
+    _lib.require_hip(logits_nchw, "argmax_classes")
     B, Cc, H, W = logits_nchw.shape
     nhwc = logits_nchw.permute(0, 2, 3, 1).contiguous()
     pred = torch.empty((B, H, W), device=logits_nchw.device, dtype=torch.int64)
-    ctx = _context(logits_nchw.device)
-    with torch.cuda.device(logits_nchw.device):
-        rc = _lib.lib().mgu_argmax_classes(ctx.handle, nhwc.data_ptr(), B * H * W, Cc, pred.data_ptr(),
-                                           _lib.current_stream_ptr(logits_nchw.device))
-    _lib.check(rc, ctx.handle)
+    _lib.call("mgu_argmax_classes", logits_nchw.device, nhwc, B * H * W, Cc, pred)
     return pred
 
 
@@ -229,8 +218,7 @@ class Trainer:
             raise ValueError(f"unknown optimizer {optimizer!r}: 'adam' or 'sgd'")
         self.optimizer, self.momentum = optimizer, float(momentum)
         params = list(model.named_parameters())
-        if not params or not params[0][1].is_cuda:
-            raise RuntimeError("move the model to a HIP device before building a Trainer (no CPU fallback)")
+        _lib.require_hip(params[0][1], "Trainer")
         self.model, self.group = model, process_group
         self.lr, self.wd, self.betas, self.eps = lr, weight_decay, betas, eps
         dev = params[0][1].device
@@ -280,18 +268,17 @@ class Trainer:
         """ncclCommInitRank inside libmgunet for this rank's context.  Rank 0 draws the ncclUniqueId; the launcher's process
         group is used ONLY to hand its 128 bytes to the other ranks."""
         import torch.distributed as dist
-        L, ctx = _lib.lib(), self.model._context(self.device)
+        ctx = self.model._context(self.device)
         world, rank = self._dist_world(), (dist.get_rank(self.group) if self._dist_world() > 1 else 0)
         buf = C.create_string_buffer(128)
         if rank == 0:
-            _lib.check(L.mgu_comm_get_unique_id(buf), None)
+            _lib.call("mgu_comm_get_unique_id", None, buf)
         if world > 1:
             box = [bytes(buf.raw)]
             with torch.cuda.device(self.device):   # an NCCL group moves the pickled object through the CURRENT device
                 dist.broadcast_object_list(box, src=dist.get_global_rank(self.group, 0) if self.group is not None else 0, group=self.group)
             buf = C.create_string_buffer(box[0], 128)
-        with torch.cuda.device(self.device):
-            _lib.check(L.mgu_comm_init_rank(ctx.handle, buf, rank, world), ctx.handle)
+        _lib.call("mgu_comm_init_rank", self.device, buf, rank, world, ctx=ctx)
         self._rccl = True
 
     def set_lr(self, lr: float) -> None:  # schedulers live on the host (train_segmentation.py:105,143): see StepLR below
@@ -386,48 +373,36 @@ class Trainer:
         if tuple(masks.shape) != (B, H, W):
             raise ValueError(f"masks shape {tuple(masks.shape)} does not match logits {(B, H, W)}")
         ctx = model._context(dev)
-        L = _lib.lib()
         nhwc = logits.permute(0, 2, 3, 1)
         assert nhwc.is_contiguous()
         masks = masks.contiguous()
         npix = B * H * W
         ldd = (Cc + 3) // 4 * 4
         dlogits = torch.empty((npix, ldd), device=dev, dtype=torch.float32)
-        stream = _lib.current_stream_ptr(dev)
         loss = self._loss
-        with torch.cuda.device(dev):
-            _lib.check(L.mgu_cross_entropy(ctx.handle, nhwc.data_ptr(), masks.data_ptr(), npix, Cc, 1.0 / npix,
-                                           dlogits.data_ptr(), self._loss.data_ptr(), stream), ctx.handle)
-            if self.loss_kind == "ce+dice":   # loss = loss_ce + loss_dice (:130): d(dice)/d(logits) is ADDED to the CE gradient
-                _lib.check(L.mgu_dice_loss_backward(ctx.handle, nhwc.data_ptr(), masks.data_ptr(), B, H * W, Cc, H * W * Cc, 1, Cc,
-                                                    self.dice_smooth, 1.0, None, dlogits.data_ptr(), H * W * ldd, 1, ldd, 1,
-                                                    self._dice.data_ptr(), stream), ctx.handle)
-                loss = self._loss + self._dice
-            bwd = L.mgu_unet_backward_allreduce if exchange else L.mgu_unet_backward
-            _lib.check(bwd(ctx.handle, dlogits.data_ptr(), self.grad.data_ptr(), stream), ctx.handle)
+        _lib.call("mgu_cross_entropy", dev, nhwc, masks, npix, Cc, 1.0 / npix, dlogits, self._loss, ctx=ctx)
+        if self.loss_kind == "ce+dice":   # loss = loss_ce + loss_dice (:130): d(dice)/d(logits) is ADDED to the CE gradient
+            _lib.call("mgu_dice_loss_backward", dev, nhwc, masks, B, H * W, Cc, H * W * Cc, 1, Cc, self.dice_smooth, 1.0, None, dlogits,
+                      H * W * ldd, 1, ldd, 1, self._dice, ctx=ctx)
+            loss = self._loss + self._dice
+        _lib.call("mgu_unet_backward_allreduce" if exchange else "mgu_unet_backward", dev, dlogits, self.grad, ctx=ctx)
         return loss
 
     def check(self) -> None:
         """Synchronise and raise ValueError if a kernel of this trainer met invalid data (a label outside [0, C) other than
         the ignore_index -100) -- the place torch would have raised; train_step itself never blocks the host."""
-        ctx = self.model._context(self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().mgu_sync_check(ctx.handle, _lib.current_stream_ptr(self.device)), ctx.handle)
+        _lib.call("mgu_sync_check", self.device, ctx=self.model._context(self.device))
 
     def optimizer_step(self, grad_scale: float = 1.0) -> None:
         model, dev = self.model, self.device
         ctx = model._context(dev)
         self.step_count += 1
-        with torch.cuda.device(dev):
-            if self.optimizer == "sgd":   # the momentum buffer lives in exp_avg (exp_avg_sq is unused by this branch)
-                _lib.check(_lib.lib().mgu_sgd_step(ctx.handle, self.flat.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(),
-                                                   self.flat.numel(), self.lr, self.momentum, self.wd, self.step_count, grad_scale,
-                                                   _lib.current_stream_ptr(dev)), ctx.handle)
-            else:
-                _lib.check(_lib.lib().mgu_adam_step(ctx.handle, self.flat.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(),
-                                                    self.exp_avg_sq.data_ptr(), self.flat.numel(), self.lr, self.betas[0],
-                                                    self.betas[1], self.eps, self.wd, self.step_count, grad_scale,
-                                                    _lib.current_stream_ptr(dev)), ctx.handle)
+        if self.optimizer == "sgd":   # the momentum buffer lives in exp_avg (exp_avg_sq is unused by this branch)
+            _lib.call("mgu_sgd_step", dev, self.flat, self.grad, self.exp_avg, self.flat.numel(), self.lr, self.momentum, self.wd,
+                      self.step_count, grad_scale, ctx=ctx)
+        else:
+            _lib.call("mgu_adam_step", dev, self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.flat.numel(), self.lr, self.betas[0],
+                      self.betas[1], self.eps, self.wd, self.step_count, grad_scale, ctx=ctx)
         model.refresh_packed_weights(dev)   # same tensors, new contents: repack in place (no state_dict round trip per step)
 
     def train_step(self, images: torch.Tensor, masks: torch.Tensor) -> torch.Tensor:
@@ -456,8 +431,9 @@ class FlatAdam:
                 if id(q) not in seen and q.requires_grad and not any(x in name for x in exclude):
                     seen.add(id(q))
                     params.append(q)
-        if not params or not params[0].is_cuda:
-            raise RuntimeError("move the modules to a HIP device before building the optimizer (no CPU fallback)")
+        if not params:
+            raise RuntimeError("FlatAdam: no parameters to optimize")
+        _lib.require_hip(params[0], "FlatAdam")
         self.params, self.device = params, params[0].device
         self.lr, self.wd, self.betas, self.eps = lr, weight_decay, betas, eps
         n = sum(q.numel() for q in params)
@@ -478,14 +454,9 @@ class FlatAdam:
         self.grad.zero_()          # the .grad views stay in place (set_to_none would detach them from the flat buffer)
 
     def step(self, grad_scale: float = 1.0) -> None:
-        from .gat import _context
-        ctx = _context(self.device)
         self.step_count += 1
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().mgu_adam_step(ctx.handle, self.flat.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(),
-                                                self.exp_avg_sq.data_ptr(), self.flat.numel(), self.lr, self.betas[0], self.betas[1],
-                                                self.eps, self.wd, self.step_count, grad_scale, _lib.current_stream_ptr(self.device)),
-                       ctx.handle)
+        _lib.call("mgu_adam_step", self.device, self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.flat.numel(), self.lr,
+                  self.betas[0], self.betas[1], self.eps, self.wd, self.step_count, grad_scale)
         for q in self.params:      # the kernel wrote the parameters behind torch's back: the packed-weight caches key on _version
             torch.autograd.graph.increment_version(q)
 

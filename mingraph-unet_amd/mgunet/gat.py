@@ -30,19 +30,14 @@ def coo_to_csr_device(edge_index: torch.Tensor, num_nodes: int):
         raise ValueError("edge_index must have shape (2, E)")
     if edge_index.dtype != torch.int64:
         raise TypeError("edge_index must be int64 (torch.long) like the reference's")
-    if not edge_index.is_cuda:
-        raise RuntimeError("mgunet GAT runs only on a HIP device (MI355X); there is deliberately no CPU fallback")
+    _lib.require_hip(edge_index, "mgunet GAT")
     dev = edge_index.device
     ei = edge_index.contiguous()
     E = ei.shape[1]
     rowptr = torch.empty(num_nodes + 1, dtype=torch.int32, device=dev)
     col = torch.empty(E, dtype=torch.int32, device=dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)
-    ctx = _context(dev)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().mgu_coo_to_csr_device(ctx.handle, ei.data_ptr() if E else None, E, num_nodes, rowptr.data_ptr(),
-                                              col.data_ptr() if E else None, status.data_ptr(), _lib.current_stream_ptr(dev))
-    _lib.check(rc, ctx.handle)
+    _lib.call("mgu_coo_to_csr_device", dev, ei if E else None, E, num_nodes, rowptr, col if E else None, status)
     if int(status.item()):
         raise IndexError(f"edge_index values must be in [0, {num_nodes})")
     return rowptr, col
@@ -75,15 +70,7 @@ def _csr_cache(mod):
     return c
 
 
-_CTX = {}
-
-
-def _context(device: torch.device):
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    ctx = _CTX.get(idx)
-    if ctx is None:
-        ctx = _CTX[idx] = _lib.Context(idx)
-    return ctx
+_context, _CTX = _lib.context, _lib._CTX   # the shared per-device contexts, under the names bench.py, tools/ and tests use
 
 
 def stacked_head_weights(heads, cache):
@@ -105,34 +92,14 @@ def stacked_head_weights(heads, cache):
     return ent[1], ent[2]
 
 
-class _Prepared:
-    """A mgu_gat_weights handle (the layer's weight-only preparation) tied to the weight versions it was built from."""
-
-    def __init__(self, ctx, handle, sig):
-        self.ctx, self.handle, self.sig = ctx, handle, sig
-
-    def __del__(self):
-        try:
-            if self.handle:
-                _lib.lib().mgu_gat_release(self.ctx.handle, self.handle)
-                self.handle = None
-        except Exception:
-            pass
-
-
-def prepared_head_weights(heads, cache, ctx, dev, has_edges: bool):
+def prepared_head_weights(heads, cache, dev, has_edges: bool):
     """mgu_gat_prepare once per (weight versions, device, has_edges): W^T a rows + fragment-order W^T (or the GEMM panel)."""
-    import ctypes as C
     W, a = stacked_head_weights(heads, cache)
     sig = (cache["weights"][0], str(dev), bool(has_edges))
     ent = cache.get("prepared")
-    if ent is None or ent.sig != sig:
+    if ent is None or ent.key != sig:
         Fh = (heads[0].out_features + 3) // 4 * 4
-        h = C.c_void_p()
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().mgu_gat_prepare(ctx.handle, W.data_ptr(), a.data_ptr(), len(heads), Fh, W.shape[1], 1 if has_edges else 0,
-                                                  C.byref(h), _lib.current_stream_ptr(dev)), ctx.handle)
-        ent = cache["prepared"] = _Prepared(ctx, h, sig)
+        ent = cache["prepared"] = _lib.Prepared("mgu_gat_prepare", dev, W, a, len(heads), Fh, W.shape[1], 1 if has_edges else 0, key=sig)
     return ent.handle
 
 
@@ -154,21 +121,18 @@ def _rank_key() -> int:
         return 0
 
 
-def _draw_mask(ctx, dev, shape, p: float) -> torch.Tensor:
+def _draw_mask(dev, shape, p: float) -> torch.Tensor:
     """nn.Dropout's mask (0 or 1 / (1 - p)) from Philox-4x32-10 on the device: element i of stream s under the key
     seed + 0x9E3779B97F4A7C15 * (rank, device index): ranks and devices of one process group never share a mask sequence."""
     m = torch.empty(shape, device=dev, dtype=torch.float32)
     _DROPOUT["stream"] += 1
     key = (_DROPOUT["seed"] + 0x9E3779B97F4A7C15 * (_rank_key() * 64 + (dev.index or 0))) & (2 ** 64 - 1)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().mgu_dropout_mask(ctx.handle, key, _DROPOUT["stream"], m.numel(), float(p), m.data_ptr(),
-                                               _lib.current_stream_ptr(dev)), ctx.handle)
+    _lib.call("mgu_dropout_mask", dev, key, _DROPOUT["stream"], m.numel(), float(p), m)
     return m
 
 
 def _gat_layer_forward(heads, X, edge_index, concat, alpha, training, dropout_rate, graph_ptr, cache, owner=None, out_dropout=True):
-    if not X.is_cuda:
-        raise RuntimeError("mgunet GAT runs only on a HIP device (MI355X); there is deliberately no CPU fallback")
+    _lib.require_hip(X, "mgunet GAT")
     if X.dtype != torch.float32:
         raise TypeError(f"expected float32 node features, got {X.dtype}")
     if X.dim() != 2:
@@ -223,23 +187,18 @@ def _gat_layer_run(X, m):
         gp = m.graph_ptr.to(device=dev, dtype=torch.int32).contiguous()
         G = gp.numel() - 1
     out = torch.empty((N, H * Fh if m.concat else Fh), device=dev, dtype=torch.float32)
-    ctx = _context(dev)
     if W.device != dev:
         raise RuntimeError(f"GAT parameters are on {W.device}, node features on {dev}")
-    handle = prepared_head_weights(heads, cache, ctx, dev, col.numel() > 0)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().mgu_gat_layer_forward_prepared(ctx.handle, handle, Xc.data_ptr(), N, rowptr.data_ptr(),
-                                                       col.data_ptr() if col.numel() else None, col.numel(), gp.data_ptr() if gp is not None else None,
-                                                       G, 1 if m.concat else 0, float(m.alpha), out.data_ptr(),
-                                                       _lib.current_stream_ptr(dev))
-    _lib.check(rc, ctx.handle)
+    handle = prepared_head_weights(heads, cache, dev, col.numel() > 0)
+    _lib.call("mgu_gat_layer_forward_prepared", dev, handle, Xc, N, rowptr, col if col.numel() else None, col.numel(), gp, G,
+              1 if m.concat else 0, float(m.alpha), out)
     saved = (Xc, W, a, rowptr, col, gp, G, Fh, Fh_true, Fin)
     if Fh != Fh_true:
         out = out.view(N, -1, Fh)[:, :, :Fh_true].reshape(N, -1).contiguous()
     return out, saved
 
 
-def _transposed_csr(cache, rowptr, col, N, dev, ctx):
+def _transposed_csr(cache, rowptr, col, N, dev):
     """CSR by source of the cached CSR by target (mgu_csr_transpose_device), built once per graph."""
     ent = cache.get("csr_t")
     if ent is None or ent[0] is not rowptr:
@@ -247,9 +206,7 @@ def _transposed_csr(cache, rowptr, col, N, dev, ctx):
         rp = torch.empty(N + 1, dtype=torch.int32, device=dev)
         eid = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
         tgt = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().mgu_csr_transpose_device(ctx.handle, rowptr.data_ptr(), col.data_ptr() if E else None, E, N, rp.data_ptr(),
-                                                           eid.data_ptr(), tgt.data_ptr(), _lib.current_stream_ptr(dev)), ctx.handle)
+        _lib.call("mgu_csr_transpose_device", dev, rowptr, col if E else None, E, N, rp, eid, tgt)
         ent = cache["csr_t"] = (rowptr, rp, eid, tgt)
     return ent[1], ent[2], ent[3]
 
@@ -271,19 +228,13 @@ class _GatLayerFn(torch.autograd.Function):
         if Fh != Fh_true:   # the padded output features never reach the caller: their gradient is 0
             g = F.pad(g.view(N, -1, Fh_true), (0, Fh - Fh_true)).reshape(N, -1)
         g = g.contiguous()
-        ctx = _context(dev)
-        rps, eid, tgt = _transposed_csr(m.cache, rowptr, col, N, dev, ctx)
+        rps, eid, tgt = _transposed_csr(m.cache, rowptr, col, N, dev)
         need_x = ctx_.needs_input_grad[0]
         dX = torch.empty_like(Xc) if need_x else None
         dW, da = torch.empty_like(W), torch.empty_like(a)
         E = col.numel()
-        with torch.cuda.device(dev):
-            rc = _lib.lib().mgu_gat_layer_backward(ctx.handle, Xc.data_ptr(), N, Xc.shape[1], rowptr.data_ptr(), col.data_ptr() if E else None, E,
-                                                   rps.data_ptr(), eid.data_ptr(), tgt.data_ptr(), gp.data_ptr() if gp is not None else None, G,
-                                                   W.data_ptr(), a.data_ptr(), H, Fh, 1 if m.concat else 0, float(m.alpha), g.data_ptr(),
-                                                   dX.data_ptr() if need_x else None, dW.data_ptr(), da.data_ptr(),
-                                                   _lib.current_stream_ptr(dev))
-        _lib.check(rc, ctx.handle)
+        _lib.call("mgu_gat_layer_backward", dev, Xc, N, Xc.shape[1], rowptr, col if E else None, E, rps, eid, tgt, gp, G, W, a, H, Fh,
+                  1 if m.concat else 0, float(m.alpha), g, dX, dW, da)
         grads = []
         for h in range(H):
             grads.append(dW[h * Fh:h * Fh + Fh_true, :Fin].contiguous())
@@ -332,7 +283,6 @@ class _GatLayerTrainFn(torch.autograd.Function):
         if m.graph_ptr is not None:
             gp = m.graph_ptr.to(device=dev, dtype=torch.int32).contiguous()
             G = gp.numel() - 1
-        c = _context(dev)
         Fo_true = H * Fh_true if m.concat else Fh_true
         if m.injected is not None:   # (H, E) in COO order, (N, F_out) or None: the hook a test feeds the reference's draw through
             em_coo, om_true = m.injected
@@ -341,8 +291,8 @@ class _GatLayerTrainFn(torch.autograd.Function):
             edge_mask = em_coo.to(device=dev, dtype=torch.float32)[:, perm].t().contiguous()
             om_true = om_true.to(device=dev, dtype=torch.float32) if om_true is not None else None
         else:
-            edge_mask = _draw_mask(c, dev, (max(E, 1), H), m.dropout_rate)
-            om_true = _draw_mask(c, dev, (N, Fo_true), m.dropout_rate) if m.out_dropout else None
+            edge_mask = _draw_mask(dev, (max(E, 1), H), m.dropout_rate)
+            om_true = _draw_mask(dev, (N, Fo_true), m.dropout_rate) if m.out_dropout else None
         if om_true is None:
             out_mask = None
         elif Fh != Fh_true:   # heads run zero-padded to 16-byte lanes: the pad features are ELU(0) = 0 whatever their mask
@@ -350,13 +300,8 @@ class _GatLayerTrainFn(torch.autograd.Function):
         else:
             out_mask = om_true.contiguous()
         out = torch.empty((N, H * Fh if m.concat else Fh), device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().mgu_gat_layer_forward_train(c.handle, Xc.data_ptr(), N, Xc.shape[1], rowptr.data_ptr(), col.data_ptr() if E else None, E,
-                                                        gp.data_ptr() if gp is not None else None, G, W.data_ptr(), a.data_ptr(), H, Fh,
-                                                        1 if m.concat else 0, float(m.alpha), edge_mask.data_ptr(),
-                                                        out_mask.data_ptr() if out_mask is not None else None, out.data_ptr(),
-                                                        _lib.current_stream_ptr(dev))
-        _lib.check(rc, c.handle)
+        _lib.call("mgu_gat_layer_forward_train", dev, Xc, N, Xc.shape[1], rowptr, col if E else None, E, gp, G, W, a, H, Fh,
+                  1 if m.concat else 0, float(m.alpha), edge_mask, out_mask, out)
         ctx_.meta = m
         ctx_.saved = (Xc, W, a, rowptr, col, gp, G, Fh, Fh_true, Fin, edge_mask, out_mask)
         if Fh != Fh_true:
@@ -373,19 +318,13 @@ class _GatLayerTrainFn(torch.autograd.Function):
         if Fh != Fh_true:
             g = F.pad(g.view(N, -1, Fh_true), (0, Fh - Fh_true)).reshape(N, -1)
         g = g.contiguous()
-        c = _context(dev)
-        rps, eid, tgt = _transposed_csr(m.cache, rowptr, col, N, dev, c)
+        rps, eid, tgt = _transposed_csr(m.cache, rowptr, col, N, dev)
         need_x = ctx_.needs_input_grad[0]
         dX = torch.empty_like(Xc) if need_x else None
         dW, da = torch.empty_like(W), torch.empty_like(a)
         E = col.numel()
-        with torch.cuda.device(dev):
-            rc = _lib.lib().mgu_gat_layer_backward_train(c.handle, Xc.data_ptr(), N, Xc.shape[1], rowptr.data_ptr(), col.data_ptr() if E else None, E,
-                                                         rps.data_ptr(), eid.data_ptr(), tgt.data_ptr(), gp.data_ptr() if gp is not None else None, G,
-                                                         W.data_ptr(), a.data_ptr(), H, Fh, 1 if m.concat else 0, float(m.alpha),
-                                                         edge_mask.data_ptr(), out_mask.data_ptr() if out_mask is not None else None, g.data_ptr(),
-                                                         dX.data_ptr() if need_x else None, dW.data_ptr(), da.data_ptr(), _lib.current_stream_ptr(dev))
-        _lib.check(rc, c.handle)
+        _lib.call("mgu_gat_layer_backward_train", dev, Xc, N, Xc.shape[1], rowptr, col if E else None, E, rps, eid, tgt, gp, G, W, a, H, Fh,
+                  1 if m.concat else 0, float(m.alpha), edge_mask, out_mask, g, dX, dW, da)
         grads = []
         for h in range(H):
             grads.append(dW[h * Fh:h * Fh + Fh_true, :Fin].contiguous())

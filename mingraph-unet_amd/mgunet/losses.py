@@ -16,12 +16,6 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .gat import _context
-
-
-def _need_cuda(t: torch.Tensor, what: str):
-    if not t.is_cuda:
-        raise RuntimeError(f"mgunet {what} runs only on a HIP device (MI355X); there is deliberately no CPU fallback")
 
 
 def _f32(t: torch.Tensor) -> torch.Tensor:
@@ -31,9 +25,7 @@ def _f32(t: torch.Tensor) -> torch.Tensor:
 def check_labels(device) -> None:
     """Synchronise and raise ValueError if a loss kernel on `device` met a label outside [0, C) since the last check (the place
     F.one_hot raises in the reference, scripts/train_segmentation.py:34); the loss calls themselves never block the host."""
-    ctx = _context(torch.device(device))
-    with torch.cuda.device(device):
-        _lib.check(_lib.lib().mgu_loss_sync_check(ctx.handle, _lib.current_stream_ptr(torch.device(device))), ctx.handle)
+    _lib.call("mgu_loss_sync_check", torch.device(device))
 
 
 class _TVFn(torch.autograd.Function):
@@ -42,10 +34,7 @@ class _TVFn(torch.autograd.Function):
         xd = _f32(x)
         B, C_, H, W = xd.shape
         out = torch.empty((), device=xd.device, dtype=torch.float32)
-        ctx = _context(xd.device)
-        with torch.cuda.device(xd.device):
-            _lib.check(_lib.lib().mgu_tv_loss(ctx.handle, xd.data_ptr(), B, C_, H, W, *xd.stride(), float(weight), out.data_ptr(),
-                                              _lib.current_stream_ptr(xd.device)), ctx.handle)
+        _lib.call("mgu_tv_loss", xd.device, xd, B, C_, H, W, *xd.stride(), float(weight), out)
         ctx_.save_for_backward(xd)
         ctx_.weight, ctx_.in_dtype = float(weight), x.dtype
         return out
@@ -56,10 +45,7 @@ class _TVFn(torch.autograd.Function):
         B, C_, H, W = xd.shape
         dx = torch.empty_like(xd)
         g = g.detach().float().contiguous()
-        ctx = _context(xd.device)
-        with torch.cuda.device(xd.device):
-            _lib.check(_lib.lib().mgu_tv_loss_backward(ctx.handle, xd.data_ptr(), B, C_, H, W, *xd.stride(), ctx_.weight, 1.0, g.data_ptr(),
-                                                       dx.data_ptr(), *dx.stride(), _lib.current_stream_ptr(xd.device)), ctx.handle)
+        _lib.call("mgu_tv_loss_backward", xd.device, xd, B, C_, H, W, *xd.stride(), ctx_.weight, 1.0, g, dx, *dx.stride())
         return dx.to(ctx_.in_dtype), None
 
 
@@ -69,7 +55,7 @@ class TVLoss(nn.Module):
         self.weight = weight
 
     def forward(self, x):
-        _need_cuda(x, "TVLoss")
+        _lib.require_hip(x, "mgunet TVLoss")
         if x.dim() != 4:
             raise ValueError("expected (B, C, H, W)")
         return _TVFn.apply(x, self.weight)
@@ -84,10 +70,7 @@ class _DiceFn(torch.autograd.Function):
             pd = pd.contiguous()
         target = target.contiguous()
         out = torch.empty((), device=pd.device, dtype=torch.float32)
-        ctx = _context(pd.device)
-        with torch.cuda.device(pd.device):
-            _lib.check(_lib.lib().mgu_dice_loss(ctx.handle, pd.data_ptr(), target.data_ptr(), B, H * W, C_, pd.stride(0), pd.stride(1),
-                                                pd.stride(3), float(smooth), out.data_ptr(), _lib.current_stream_ptr(pd.device)), ctx.handle)
+        _lib.call("mgu_dice_loss", pd.device, pd, target, B, H * W, C_, pd.stride(0), pd.stride(1), pd.stride(3), float(smooth), out)
         ctx_.save_for_backward(pd, target)
         ctx_.smooth, ctx_.in_dtype = float(smooth), pred.dtype
         return out
@@ -100,18 +83,15 @@ class _DiceFn(torch.autograd.Function):
         if d.stride() != pd.stride():
             d = torch.empty_strided(pd.shape, pd.stride(), device=pd.device, dtype=torch.float32)
         g = g.detach().float().contiguous()
-        ctx = _context(pd.device)
-        with torch.cuda.device(pd.device):
-            _lib.check(_lib.lib().mgu_dice_loss_backward(ctx.handle, pd.data_ptr(), target.data_ptr(), B, H * W, C_, pd.stride(0), pd.stride(1),
-                                                         pd.stride(3), ctx_.smooth, 1.0, g.data_ptr(), d.data_ptr(), d.stride(0), d.stride(1),
-                                                         d.stride(3), 0, None, _lib.current_stream_ptr(pd.device)), ctx.handle)
+        _lib.call("mgu_dice_loss_backward", pd.device, pd, target, B, H * W, C_, pd.stride(0), pd.stride(1), pd.stride(3), ctx_.smooth, 1.0,
+                  g, d, d.stride(0), d.stride(1), d.stride(3), 0, None)
         return d.to(ctx_.in_dtype), None, None
 
 
 def dice_loss(pred, target, smooth=1.):
     """pred (B, C, H, W) logits (any strides: NHWC storage is read in place), target (B, H, W) int64.  Differentiable w.r.t. pred.
     A label outside [0, C) -- F.one_hot raises on it -- is reported by check_labels(pred.device) (no host sync inside the call)."""
-    _need_cuda(pred, "dice_loss")
+    _lib.require_hip(pred, "mgunet dice_loss")
     if pred.dim() != 4 or target.dim() != 3 or target.dtype != torch.int64:
         raise ValueError("expected logits (B, C, H, W) and an int64 target (B, H, W)")
     return _DiceFn.apply(pred, target, smooth)
@@ -123,10 +103,7 @@ class _FeatConsFn(torch.autograd.Function):
         fu, fg = _f32(f_unet).contiguous(), _f32(f_graph).contiguous()
         B, N, D = fu.shape
         out = torch.empty((), device=fu.device, dtype=torch.float32)
-        ctx = _context(fu.device)
-        with torch.cuda.device(fu.device):
-            _lib.check(_lib.lib().mgu_feature_consistency_loss(ctx.handle, fu.data_ptr(), fg.data_ptr(), y.data_ptr(), B, N, D,
-                                                               float(margin), out.data_ptr(), _lib.current_stream_ptr(fu.device)), ctx.handle)
+        _lib.call("mgu_feature_consistency_loss", fu.device, fu, fg, y, B, N, D, float(margin), out)
         ctx_.save_for_backward(fu, fg, y)
         ctx_.margin = float(margin)
         return out
@@ -139,11 +116,7 @@ class _FeatConsFn(torch.autograd.Function):
         du = torch.empty_like(fu) if need_u else None
         dg = torch.empty_like(fg) if need_g else None
         g = g.detach().float().contiguous()
-        ctx = _context(fu.device)
-        with torch.cuda.device(fu.device):
-            _lib.check(_lib.lib().mgu_feature_consistency_loss_backward(
-                ctx.handle, fu.data_ptr(), fg.data_ptr(), y.data_ptr(), B, N, D, ctx_.margin, 1.0, g.data_ptr(),
-                du.data_ptr() if need_u else None, dg.data_ptr() if need_g else None, _lib.current_stream_ptr(fu.device)), ctx.handle)
+        _lib.call("mgu_feature_consistency_loss_backward", fu.device, fu, fg, y, B, N, D, ctx_.margin, 1.0, g, du, dg)
         return du, dg, None, None
 
 
@@ -153,7 +126,7 @@ class FeatureConsistencyLoss(nn.Module):
         self.margin = margin
 
     def forward(self, f_unet, f_graph, correspondence_map_y, regions_unet=None, regions_graph=None):
-        _need_cuda(f_unet, "FeatureConsistencyLoss")
+        _lib.require_hip(f_unet, "mgunet FeatureConsistencyLoss")
         B, N, D = f_unet.shape                                                  # (N, D) inputs raise here, as in the reference (:88)
         if f_unet.shape != f_graph.shape:
             raise ValueError(f"f_unet ({f_unet.shape}) and f_graph ({f_graph.shape}) must have same dimensions for this loss version.")
@@ -171,29 +144,23 @@ class EllipticalShapeLoss(nn.Module):
         self.epsilon = epsilon
 
     def forward(self, segmentation_probs, object_masks_list=None):
-        L = _lib.lib()
         if object_masks_list is None:
-            _need_cuda(segmentation_probs, "EllipticalShapeLoss")
+            _lib.require_hip(segmentation_probs, "mgunet EllipticalShapeLoss")
             p = _f32(segmentation_probs)
             B, C_, H, W = p.shape
             if p.stride(2) != W * p.stride(3):
                 p = p.contiguous()
             out = torch.empty((), device=p.device, dtype=torch.float32)
-            ctx = _context(p.device)
-            with torch.cuda.device(p.device):
-                _lib.check(L.mgu_elliptical_shape_loss_probs(ctx.handle, p.data_ptr(), B, C_, H, W, p.stride(0), p.stride(1), p.stride(3),
-                                                             float(self.epsilon), out.data_ptr(), _lib.current_stream_ptr(p.device)), ctx.handle)
+            _lib.call("mgu_elliptical_shape_loss_probs", p.device, p, B, C_, H, W, p.stride(0), p.stride(1), p.stride(3), float(self.epsilon),
+                      out)
             return out
         masks = [m for img in object_masks_list for m in img]
         if not masks:
             dev = segmentation_probs.device if segmentation_probs is not None else torch.device("cuda")
             return torch.tensor(0.0, device=dev)
-        _need_cuda(masks[0], "EllipticalShapeLoss")
+        _lib.require_hip(masks[0], "mgunet EllipticalShapeLoss")
         stack = torch.stack([(m != 0) for m in masks]).to(torch.uint8).contiguous()   # (M, H, W): one pass over all objects
         M, H, W = stack.shape
         out = torch.empty((), device=stack.device, dtype=torch.float32)
-        ctx = _context(stack.device)
-        with torch.cuda.device(stack.device):
-            _lib.check(L.mgu_elliptical_shape_loss_masks(ctx.handle, stack.data_ptr(), M, H, W, float(self.epsilon), out.data_ptr(),
-                                                         _lib.current_stream_ptr(stack.device)), ctx.handle)
+        _lib.call("mgu_elliptical_shape_loss_masks", stack.device, stack, M, H, W, float(self.epsilon), out)
         return out

@@ -12,7 +12,6 @@ import numpy as np
 import torch
 
 from . import _lib
-from .gat import _context
 
 _LOSS_KINDS = {None: 0, "ce": 1, "ce+dice": 2}
 
@@ -66,10 +65,7 @@ def confusion_matrix_device(true_flat: torch.Tensor, pred_flat: torch.Tensor, nu
     C = int(num_classes)
     if out is None:
         out = torch.zeros((C, C), device=dev, dtype=torch.int64)
-    ctx = _context(dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().mgu_confusion_matrix(ctx.handle, t.data_ptr(), p.data_ptr(), t.numel(), C, out.data_ptr(),
-                                                   _lib.current_stream_ptr(dev)), ctx.handle)
+    _lib.call("mgu_confusion_matrix", dev, t, p, t.numel(), C, out)
     return out
 
 
@@ -134,8 +130,7 @@ class SegmentationEvaluator:
         self.num_classes, self.device = int(num_classes), torch.device(device)
         if self.num_classes < 1:
             raise ValueError("num_classes must be >= 1")
-        if self.device.type != "cuda":
-            raise RuntimeError("SegmentationEvaluator runs only on a HIP device (no CPU fallback)")
+        _lib.require_hip(self.device, "SegmentationEvaluator")
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.loss, self.loss_kind = loss, _LOSS_KINDS[loss]
@@ -165,21 +160,14 @@ class SegmentationEvaluator:
         if not nhwc.is_contiguous():
             nhwc = nhwc.contiguous()
         pred = torch.empty((B, H, W), device=self.device, dtype=torch.int64) if return_pred else None
-        ctx = _context(self.device)
-        with torch.cuda.device(self.device):
-            rc = _lib.lib().mgu_segmentation_eval(ctx.handle, nhwc.data_ptr(), masks.data_ptr(), B, H * W, Cc, self.confusion.data_ptr(),
-                                                  pred.data_ptr() if pred is not None else None, self.loss_kind, self.dice_smooth,
-                                                  self.loss_acc.data_ptr() if self.loss_acc is not None else None,
-                                                  _lib.current_stream_ptr(self.device))
-        _lib.check(rc, ctx.handle)
+        _lib.call("mgu_segmentation_eval", self.device, nhwc, masks, B, H * W, Cc, self.confusion, pred, self.loss_kind, self.dice_smooth,
+                  self.loss_acc)
         return pred
 
     def compute(self, group=None) -> dict:
         """Synchronise, raise ValueError if a loss kernel met an invalid label (as losses.check_labels), SUM the counts and loss
         accumulators over the ranks of `group` when torch.distributed runs more than one, and return the reference's dictionary."""
-        ctx = _context(self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().mgu_loss_sync_check(ctx.handle, _lib.current_stream_ptr(self.device)), ctx.handle)
+        _lib.call("mgu_loss_sync_check", self.device)
         cm, acc = allreduce_eval_state(self.confusion, self.loss_acc, group)
         res = metrics_from_confusion(cm.cpu().numpy(), self.smooth)
         if acc is not None:

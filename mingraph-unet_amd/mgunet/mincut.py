@@ -14,20 +14,17 @@ source; it is derived once per edge_index tensor and cached, like the GAT's CSR 
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 import torch.nn as nn
 
 from . import _lib
-from .gat import GATNetwork, _context, coo_to_csr_device
+from .gat import GATNetwork, coo_to_csr_device
 
 
 def _check_features(x: torch.Tensor, what: str) -> None:
     if not isinstance(x, torch.Tensor) or x.dim() != 2:
         raise ValueError(f"{what} must be a (N, D) tensor")
-    if not x.is_cuda:
-        raise RuntimeError("mgunet MinCut runs only on a HIP device (MI355X); there is deliberately no CPU fallback")
+    _lib.require_hip(x, "mgunet MinCut")
     if x.dtype != torch.float32:
         raise TypeError(f"expected float32 {what}, got {x.dtype}")
 
@@ -41,11 +38,7 @@ def _linear_run(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, relu: bool) -
         raise ValueError("MLP predictor widths must be multiples of 4 (16-byte NHWC pixels)")
     ld = (Cout + 3) // 4 * 4
     out = torch.empty((N, ld), device=x.device, dtype=torch.float32)
-    ctx = _context(x.device)
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().mgu_conv2d_nhwc(ctx.handle, x.data_ptr(), 1, N, 1, Cin, w.data_ptr(), b.data_ptr(), None, None, Cout, 1,
-                                        1 if relu else 0, out.data_ptr(), ld, 0, _lib.current_stream_ptr(x.device))
-    _lib.check(rc, ctx.handle)
+    _lib.call("mgu_conv2d_nhwc", x.device, x, 1, N, 1, Cin, w, b, None, None, Cout, 1, 1 if relu else 0, out, ld, 0)
     return out
 
 
@@ -69,23 +62,19 @@ class _LinearFn(torch.autograd.Function):
         Cout, ld = ctx.cout, y.shape[1]
         dz = torch.zeros((N, ld), device=dev, dtype=torch.float32)
         dz[:, :Cout] = gy
-        c = _context(dev)
-        L = _lib.lib()
-        st = _lib.current_stream_ptr(dev)
         dx = torch.empty((N, Cin), device=dev, dtype=torch.float32) if ctx.needs_input_grad[0] else None
         dw = torch.empty_like(w) if ctx.needs_input_grad[1] else None
         db = None
-        with torch.cuda.device(dev):
-            if ctx.relu:
-                _lib.check(L.mgu_relu_backward(c.handle, dz.data_ptr(), y.data_ptr(), dz.numel(), dz.data_ptr(), st), c.handle)
-            if dx is not None:
-                _lib.check(L.mgu_conv2d_dgrad_nhwc(c.handle, dz.data_ptr(), w.data_ptr(), 1, N, 1, Cin, Cout, 1, dx.data_ptr(), Cin, st), c.handle)
-            if dw is not None:
-                _lib.check(L.mgu_conv2d_wgrad_nhwc(c.handle, x.data_ptr(), Cin, dz.data_ptr(), 1, N, 1, Cin, Cout, 1, dw.data_ptr(), st), c.handle)
-            if ctx.needs_input_grad[2]:
-                dbp = torch.empty(ld, device=dev, dtype=torch.float32)
-                _lib.check(L.mgu_channel_sum_nhwc(c.handle, dz.data_ptr(), ld, N, ld, dbp.data_ptr(), st), c.handle)
-                db = dbp[:Cout]
+        if ctx.relu:
+            _lib.call("mgu_relu_backward", dev, dz, y, dz.numel(), dz)
+        if dx is not None:
+            _lib.call("mgu_conv2d_dgrad_nhwc", dev, dz, w, 1, N, 1, Cin, Cout, 1, dx, Cin)
+        if dw is not None:
+            _lib.call("mgu_conv2d_wgrad_nhwc", dev, x, Cin, dz, 1, N, 1, Cin, Cout, 1, dw)
+        if ctx.needs_input_grad[2]:
+            dbp = torch.empty(ld, device=dev, dtype=torch.float32)
+            _lib.call("mgu_channel_sum_nhwc", dev, dz, ld, N, ld, dbp)
+            db = dbp[:Cout]
         return dx, dw, db, None
 
 
@@ -116,13 +105,8 @@ class _NcutFn(torch.autograd.Function):
         gs = gsoft.detach().to(torch.float32).contiguous() if (ctx.is_logits and gsoft is not None) else None
         dA = torch.empty((N, K), device=dev, dtype=torch.float32)
         dF = torch.empty((N, D), device=dev, dtype=torch.float32) if ctx.needs_input_grad[0] else None
-        c = _context(dev)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().mgu_ncut_backward(c.handle, f.data_ptr(), N, D, rp_s.data_ptr(), col_t.data_ptr() if E else None,
-                                              rp_t.data_ptr(), col_s.data_ptr() if E else None, E, P.data_ptr(), K,
-                                              1 if ctx.is_logits else 0, gl.data_ptr(), gs.data_ptr() if gs is not None else None,
-                                              dA.data_ptr(), dF.data_ptr() if dF is not None else None, _lib.current_stream_ptr(dev))
-        _lib.check(rc, c.handle)
+        _lib.call("mgu_ncut_backward", dev, f, N, D, rp_s, col_t if E else None, rp_t, col_s if E else None, E, P, K, 1 if ctx.is_logits else 0,
+                  gl, gs, dA, dF)
         return dF, (dA if ctx.needs_input_grad[1] else None), None, None, None, None
 
 
@@ -200,11 +184,7 @@ class MinCutRefinement(nn.Module):
             if lo < 0 or hi >= N:
                 raise IndexError(f"edge_index values must be in [0, {N}); got [{lo}, {hi}]")
         w = torch.empty(E, device=dev, dtype=torch.float32)
-        ctx = _context(dev)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().mgu_ncut_edge_weights(ctx.handle, f.data_ptr(), N, D, ei.data_ptr() if E else None, E,
-                                                  w.data_ptr() if E else None, _lib.current_stream_ptr(dev))
-        _lib.check(rc, ctx.handle)
+        _lib.call("mgu_ncut_edge_weights", dev, f, N, D, ei if E else None, E, w if E else None)
         return w
 
     def _ncut(self, node_features, edge_index, assign, K, is_logits):
@@ -225,13 +205,8 @@ class MinCutRefinement(nn.Module):
         loss = torch.empty(1, device=dev, dtype=torch.float32)
         soft = torch.empty((N, K), device=dev, dtype=torch.float32) if is_logits else None
         hard = torch.empty(N, device=dev, dtype=torch.int32) if is_logits else None
-        ctx = _context(dev)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().mgu_ncut_forward(ctx.handle, f.data_ptr(), N, D, rowptr.data_ptr(), col.data_ptr() if col.numel() else None,
-                                             col.numel(), a.data_ptr(), K, 1 if is_logits else 0,
-                                             soft.data_ptr() if is_logits else None, hard.data_ptr() if is_logits else None,
-                                             loss.data_ptr(), _lib.current_stream_ptr(dev))
-        _lib.check(rc, ctx.handle)
+        _lib.call("mgu_ncut_forward", dev, f, N, D, rowptr, col if col.numel() else None, col.numel(), a, K, 1 if is_logits else 0, soft, hard,
+                  loss)
         return loss[0], soft, hard
 
     def forward_batched(self, patch_features, edge_index_single, B, num_expected_segments, segment_logits):

@@ -13,7 +13,6 @@ import numpy as np
 import torch
 
 from . import _lib
-from .gat import _context
 
 
 @dataclass
@@ -50,14 +49,9 @@ class ObjectTable:
         return [[self.labels[b] == k for k in range(1, n + 1)] for b, n in enumerate(counts)]
 
 
-def _stream(dev):
-    return _lib.current_stream_ptr(dev)
-
-
 def _source(x: torch.Tensor):
     """(src tensor, kind, B, H, W, C): an int64 class map (kind 0) or the NHWC storage of (B, C, H, W) fp32 logits (kind 1)."""
-    if not x.is_cuda:
-        raise RuntimeError("connected components run only on a HIP device (no CPU fallback)")
+    _lib.require_hip(x, "connected components")
     if x.is_floating_point():
         if x.dim() != 4 or x.dtype != torch.float32:
             raise TypeError("logits must be (B, C, H, W) float32")
@@ -74,20 +68,12 @@ def _source(x: torch.Tensor):
 
 
 def _label(src, kind, B, H, W, C, connectivity, background, num_classes, min_area, labels, counts, offsets):
-    ctx = _context(src.device)
-    with torch.cuda.device(src.device):
-        _lib.check(_lib.lib().mgu_connected_components(ctx.handle, src.data_ptr(), kind, B, H, W, C, int(connectivity), int(background),
-                                                       int(num_classes), int(min_area), labels.data_ptr(), counts.data_ptr(),
-                                                       offsets.data_ptr(), _stream(src.device)), ctx.handle)
+    _lib.call("mgu_connected_components", src.device, src, kind, B, H, W, C, int(connectivity), int(background), int(num_classes),
+              int(min_area), labels, counts, offsets)
 
 
 def _stats(labels, src, kind, B, H, W, C, offsets, capacity, cls, bbox, area=None, sums=None):
-    ctx = _context(src.device)
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    with torch.cuda.device(src.device):
-        _lib.check(_lib.lib().mgu_object_stats(ctx.handle, labels.data_ptr(), src.data_ptr(), kind, B, H, W, C, offsets.data_ptr(),
-                                               int(capacity), cls.data_ptr(), ptr(area), bbox.data_ptr(), ptr(sums), _stream(src.device)),
-                   ctx.handle)
+    _lib.call("mgu_object_stats", src.device, labels, src, kind, B, H, W, C, offsets, int(capacity), cls, area, bbox, sums)
 
 
 def _check_args(connectivity, min_area):
@@ -198,8 +184,7 @@ class YieldEvaluator:
         self.num_classes, self.device = int(num_classes), torch.device(device)
         if self.num_classes < 1:
             raise ValueError("num_classes must be >= 1")
-        if self.device.type != "cuda":
-            raise RuntimeError("YieldEvaluator runs only on a HIP device (no CPU fallback)")
+        _lib.require_hip(self.device, "YieldEvaluator")
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.connectivity, self.min_area = connectivity, int(min_area)
@@ -240,12 +225,9 @@ class YieldEvaluator:
             offsets[side] = torch.empty(B + 1, device=self.device, dtype=torch.int64)
             _label(s, k, B, H, W, cc, self.connectivity, 0, ncls, amin, lab, counts[side], offsets[side])
             _stats(lab, s, k, B, H, W, cc, offsets[side], self._cap, cls, bbox)
-        ctx = _context(self.device)
         (gl, gc, gb), (pl, pc, pb) = bufs["gt"], bufs["pred"]
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().mgu_match_objects(ctx.handle, B, offsets["gt"].data_ptr(), gc.data_ptr(), gb.data_ptr(), self._cap,
-                                                    offsets["pred"].data_ptr(), pc.data_ptr(), pb.data_ptr(), self._cap, self.iou_thresh,
-                                                    self.totals.data_ptr(), _stream(self.device)), ctx.handle)
+        _lib.call("mgu_match_objects", self.device, B, offsets["gt"], gc, gb, self._cap, offsets["pred"], pc, pb, self._cap, self.iou_thresh,
+                  self.totals)
         self.gt_counts.append(counts["gt"])
         self.pred_counts.append(counts["pred"])
 

@@ -16,15 +16,13 @@ from . import _lib
 
 
 def _build(H: int, W: int, patch: int):
-    L = _lib.lib()
     E, nph, npw = C.c_int64(), C.c_int(), C.c_int()
-    _lib.check(L.mgu_patch_graph_build(H, W, patch, None, None, None, C.byref(E), C.byref(nph), C.byref(npw)))
+    _lib.call("mgu_patch_graph_build", None, H, W, patch, None, None, None, C.byref(E), C.byref(nph), C.byref(npw))
     n = nph.value * npw.value
     coo = np.empty((2, E.value), dtype=np.int64)
     rowptr = np.empty(n + 1, dtype=np.int32)
     col = np.empty(E.value, dtype=np.int32)
-    _lib.check(L.mgu_patch_graph_build(H, W, patch, coo.ctypes.data_as(C.c_void_p), rowptr.ctypes.data_as(C.c_void_p),
-                                       col.ctypes.data_as(C.c_void_p), None, None, None))
+    _lib.call("mgu_patch_graph_build", None, H, W, patch, coo.ctypes.data, rowptr.ctypes.data, col.ctypes.data, None, None, None)
     return coo, rowptr, col, nph.value, npw.value
 
 
@@ -94,8 +92,7 @@ class PatchGraphConstructor:
 
     def patch_mean_features(self, feat_nchw: torch.Tensor) -> torch.Tensor:
         """(B,C,H,W) feature map (NHWC storage preferred) -> (B*nph*npw, C) patch means on the GPU."""
-        if not feat_nchw.is_cuda:
-            raise RuntimeError("patch_mean_features runs only on a HIP device")
+        _lib.require_hip(feat_nchw, "patch_mean_features")
         B, Cc, H, W = feat_nchw.shape
         if feat_nchw.dtype not in (torch.float32, torch.bfloat16):
             raise TypeError(f"expected float32 or bfloat16 features, got {feat_nchw.dtype}")
@@ -103,12 +100,7 @@ class PatchGraphConstructor:
         nhwc = feat_nchw.permute(0, 2, 3, 1).contiguous()  # no copy when storage is already NHWC
         nph, npw = (H + self.patch_size - 1) // self.patch_size, (W + self.patch_size - 1) // self.patch_size
         out = torch.empty((B * nph * npw, Cc), device=feat_nchw.device, dtype=torch.float32)
-        from .gat import _context
-        ctx = _context(feat_nchw.device)
-        with torch.cuda.device(feat_nchw.device):
-            rc = _lib.lib().mgu_patch_mean(ctx.handle, nhwc.data_ptr(), code, B, H, W, Cc, self.patch_size, out.data_ptr(),
-                                           _lib.current_stream_ptr(feat_nchw.device))
-        _lib.check(rc, ctx.handle)
+        _lib.call("mgu_patch_mean", feat_nchw.device, nhwc, code, B, H, W, Cc, self.patch_size, out)
         return out
 
     def get_patch_features_from_unet_encoder(self, unet_encoder_features, patches_coords_info=None):

@@ -24,14 +24,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .gat import _context
-
-_DEV = None
-
 
 def _device():
-    if not torch.cuda.is_available():
-        raise RuntimeError("mgunet.preprocess runs only on a HIP device (MI355X); there is deliberately no CPU fallback")
+    """The current HIP device, where host images are moved."""
+    _lib.require_hip(torch.device("cuda" if torch.cuda.is_available() else "cpu"), "mgunet.preprocess")
     return torch.device("cuda", torch.cuda.current_device())
 
 
@@ -154,11 +150,7 @@ class ImagePreprocessor:
             flip, angle = self._draw(augment)
             return self._image_aug(img, bgr, out, flip, angle)
         mean, std = (C.c_float * 3)(*self.mean), (C.c_float * 3)(*self.std)
-        ctx = _context(img.device)
-        with torch.cuda.device(img.device):
-            rc = _lib.lib().mgu_preprocess_image_u8(ctx.handle, img.data_ptr(), Hs, Ws, ch, bgr, H, W, mean, std, out.data_ptr(), out.stride(0),
-                                                    out.stride(1), out.stride(2), _lib.current_stream_ptr(img.device))
-        _lib.check(rc, ctx.handle)
+        _lib.call("mgu_preprocess_image_u8", img.device, img, Hs, Ws, ch, bgr, H, W, mean, std, out, *out.stride())
         return out
 
     def _image_aug(self, img, bgr, out, flip, angle):
@@ -166,23 +158,14 @@ class ImagePreprocessor:
         H, W = int(self.resize_dim[0]), int(self.resize_dim[1])
         fix = (C.c_int32 * 6)(*pil_rotation_fixed(angle, W, H))
         mean, std = (C.c_float * 3)(*self.mean), (C.c_float * 3)(*self.std)
-        ctx = _context(img.device)
-        with torch.cuda.device(img.device):
-            rc = _lib.lib().mgu_preprocess_image_u8_aug(ctx.handle, img.data_ptr(), Hs, Ws, ch, bgr, H, W, mean, std, out.data_ptr(),
-                                                        out.stride(0), out.stride(1), out.stride(2), int(flip), fix,
-                                                        _lib.current_stream_ptr(img.device))
-        _lib.check(rc, ctx.handle)
+        _lib.call("mgu_preprocess_image_u8_aug", img.device, img, Hs, Ws, ch, bgr, H, W, mean, std, out, *out.stride(), int(flip), fix)
         return out
 
     def preprocess_mask(self, mask_path_or_array, num_classes):
         m = _load_mask(mask_path_or_array)
         H, W = int(self.resize_dim[0]), int(self.resize_dim[1])
         out = torch.empty((H, W), device=m.device, dtype=torch.int64)
-        ctx = _context(m.device)
-        with torch.cuda.device(m.device):
-            rc = _lib.lib().mgu_preprocess_mask_u8(ctx.handle, m.data_ptr(), m.shape[0], m.shape[1], H, W, int(num_classes), out.data_ptr(),
-                                                   _lib.current_stream_ptr(m.device))
-        _lib.check(rc, ctx.handle)
+        _lib.call("mgu_preprocess_mask_u8", m.device, m, m.shape[0], m.shape[1], H, W, int(num_classes), out)
         return out
 
     def preprocess_pair(self, image, mask, num_classes, mask_fill=0, generator=None, out: torch.Tensor = None, augment=None):
@@ -206,11 +189,7 @@ class ImagePreprocessor:
         self._image_aug(img, bgr, out, flip, angle)
         mout = torch.empty((H, W), device=m.device, dtype=torch.int64)
         fix = (C.c_int32 * 6)(*pil_rotation_fixed(angle, W, H))
-        ctx = _context(m.device)
-        with torch.cuda.device(m.device):
-            rc = _lib.lib().mgu_preprocess_mask_u8_aug(ctx.handle, m.data_ptr(), m.shape[0], m.shape[1], H, W, int(num_classes), int(flip), fix,
-                                                       int(mask_fill), mout.data_ptr(), _lib.current_stream_ptr(m.device))
-        _lib.check(rc, ctx.handle)
+        _lib.call("mgu_preprocess_mask_u8_aug", m.device, m, m.shape[0], m.shape[1], H, W, int(num_classes), int(flip), fix, int(mask_fill), mout)
         return out, mout
 
 
@@ -257,13 +236,7 @@ class RandomFlipRotate:
         mout = torch.empty((B, H, W), device=dev, dtype=torch.int64) if masks is not None else None
         si, so = (C.c_int64 * 4)(*images.stride()), (C.c_int64 * 4)(*out.stride())
         fill = (C.c_float * Cc)(*self.fill)
-        ctx = _context(dev)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().mgu_augment_flip_rotate(ctx.handle, images.data_ptr(), out.data_ptr(), B, Cc, H, W, si, so, fill,
-                                                    masks.data_ptr() if masks is not None else None,
-                                                    mout.data_ptr() if mout is not None else None, self.mask_fill, params.data_ptr(),
-                                                    _lib.current_stream_ptr(dev))
-        _lib.check(rc, ctx.handle)
+        _lib.call("mgu_augment_flip_rotate", dev, images, out, B, Cc, H, W, si, so, fill, masks, mout, self.mask_fill, params)
         return (out, mout) if masks is not None else out
 
 
@@ -273,10 +246,7 @@ def _rgb_op(fn_name, image_array_rgb, out_channels):
     img, was_np = _to_dev_u8(image_array_rgb)
     H, W, _ = img.shape
     out = torch.empty((H, W, 3) if out_channels == 3 else (H, W), device=img.device, dtype=torch.uint8)
-    ctx = _context(img.device)
-    with torch.cuda.device(img.device):
-        rc = getattr(_lib.lib(), fn_name)(ctx.handle, img.data_ptr(), H, W, out.data_ptr(), _lib.current_stream_ptr(img.device))
-    _lib.check(rc, ctx.handle)
+    _lib.call(fn_name, img.device, img, H, W, out)
     return out.cpu().numpy() if was_np else out
 
 
@@ -306,11 +276,7 @@ def patch_features_u8(image, patch_size: int, per_channel: bool = False) -> torc
     H, W, ch = img.shape
     nph, npw = (H + patch_size - 1) // patch_size, (W + patch_size - 1) // patch_size
     out = torch.empty((nph * npw, ch if per_channel else 1), device=img.device, dtype=torch.float32)
-    ctx = _context(img.device)
-    with torch.cuda.device(img.device):
-        rc = _lib.lib().mgu_patch_mean_u8(ctx.handle, img.data_ptr(), H, W, ch, patch_size, 1 if per_channel else 0, out.data_ptr(),
-                                          _lib.current_stream_ptr(img.device))
-    _lib.check(rc, ctx.handle)
+    _lib.call("mgu_patch_mean_u8", img.device, img, H, W, ch, patch_size, 1 if per_channel else 0, out)
     return out
 
 
@@ -321,8 +287,7 @@ def postprocess_segmentation(seg_logits_or_probs, num_classes, colors=None):
     """infer_segmentation.py:20-51: (C, H, W) / (1, C, H, W) scores or (H, W) labels -> (labels (H, W) numpy, colour map (H, W, 3) uint8
     numpy).  Classes beyond the four fixed colours get random colours in the reference (np.random): pass `colors` to fix them."""
     t = seg_logits_or_probs
-    if not t.is_cuda:
-        raise RuntimeError("mgunet.postprocess_segmentation runs only on a HIP device")
+    _lib.require_hip(t, "mgunet.postprocess_segmentation")
     if t.ndim == 4:
         t = t.squeeze(0)
     if t.shape[0] == num_classes and t.ndim == 3:
@@ -337,9 +302,5 @@ def postprocess_segmentation(seg_logits_or_probs, num_classes, colors=None):
     palette = torch.tensor(pal[:num_classes], dtype=torch.uint8, device=t.device).contiguous()
     H, W = labels.shape
     vis = torch.empty((H, W, 3), device=t.device, dtype=torch.uint8)
-    ctx = _context(t.device)
-    with torch.cuda.device(t.device):
-        rc = _lib.lib().mgu_colorize_labels(ctx.handle, labels.data_ptr(), H * W, palette.data_ptr(), int(num_classes), vis.data_ptr(), None,
-                                            _lib.current_stream_ptr(t.device))
-    _lib.check(rc, ctx.handle)
+    _lib.call("mgu_colorize_labels", t.device, labels, H * W, palette, int(num_classes), vis, None)
     return labels.cpu().numpy(), vis.cpu().numpy()

@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .gat import GATNetwork, _context
+from .gat import GATNetwork
 
 
 _REGION_GRAPHS = {}
@@ -29,8 +29,7 @@ def region_edge_index(K: int, device=None) -> torch.Tensor:
 
 
 def _f32_cuda(x, what):
-    if not x.is_cuda:
-        raise RuntimeError(f"{what}: the region stage runs only on a HIP device (MI355X); there is deliberately no CPU fallback")
+    _lib.require_hip(x, f"{what}: the region stage")
     if x.dtype != torch.float32:
         raise TypeError(f"{what} must be float32, got {x.dtype}")
 
@@ -46,11 +45,7 @@ def region_mean_pool(patch_feats: torch.Tensor, hard_labels: torch.Tensor, B: in
     f = patch_feats.detach().contiguous()
     h = hard_labels.to(device=dev, dtype=torch.int32).contiguous()
     out = torch.empty((B * K, D), device=dev, dtype=torch.float32)
-    ctx = _context(dev)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().mgu_region_mean_pool(ctx.handle, f.data_ptr(), h.data_ptr(), B, N // B, D, K, out.data_ptr(),
-                                             _lib.current_stream_ptr(dev))
-    _lib.check(rc, ctx.handle)
+    _lib.call("mgu_region_mean_pool", dev, f, h, B, N // B, D, K, out)
     return out
 
 
@@ -60,22 +55,17 @@ def region_fuse(f_u, region_emb: torch.Tensor, hard_labels: torch.Tensor, B: int
     _f32_cuda(region_emb, "region_emb")
     dev = region_emb.device
     D = region_emb.shape[1]
-    Cu, fu_ptr = 0, None
+    Cu, fu_nhwc = 0, None
     if f_u is not None:
         _f32_cuda(f_u, "f_u")
         if tuple(f_u.shape[0:1] + f_u.shape[2:]) != (B, H, W):
             raise ValueError(f"f_u must be (B, C, {H}, {W})")
         Cu = f_u.shape[1]
         fu_nhwc = f_u.detach().permute(0, 2, 3, 1).contiguous()   # a no-op for mgunet's NHWC-stored feature maps
-        fu_ptr = fu_nhwc.data_ptr()
     h = hard_labels.to(device=dev, dtype=torch.int32).contiguous()
     emb = region_emb.detach().contiguous()
     out = torch.empty((B, H, W, Cu + D), device=dev, dtype=torch.float32)
-    ctx = _context(dev)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().mgu_region_fuse_nhwc(ctx.handle, fu_ptr, Cu, emb.data_ptr(), h.data_ptr(), B, H, W, nph, npw, K, D,
-                                             out.data_ptr(), _lib.current_stream_ptr(dev))
-    _lib.check(rc, ctx.handle)
+    _lib.call("mgu_region_fuse_nhwc", dev, fu_nhwc, Cu, emb, h, B, H, W, nph, npw, K, D, out)
     return out.permute(0, 3, 1, 2)
 
 
@@ -111,7 +101,7 @@ class FeatureFusion(nn.Module):
         self.fusion_method = fusion_method.lower()
 
     @staticmethod
-    def _place(ctx, src_nchw, out_nhwc, c_off, H, W):
+    def _place(src_nchw, out_nhwc, c_off, H, W):
         """src (B, C, h, w) -> channels [c_off, c_off + C) of out (B, H, W, ld)."""
         B, Cs, h, w = src_nchw.shape
         if Cs % 4:
@@ -120,11 +110,7 @@ class FeatureFusion(nn.Module):
             out_nhwc[..., c_off:c_off + Cs] = src_nchw.permute(0, 2, 3, 1)      # same size: a strided copy, no arithmetic
             return
         src = src_nchw.detach().float().permute(0, 2, 3, 1).contiguous()        # a no-op for mgunet's NHWC-stored feature maps
-        dev = src.device
-        with torch.cuda.device(dev):
-            rc = _lib.lib().mgu_resize_bilinear_nhwc(ctx.handle, src.data_ptr(), Cs, B, h, w, Cs, out_nhwc.data_ptr(), out_nhwc.shape[3],
-                                                     c_off, H, W, _lib.current_stream_ptr(dev))
-        _lib.check(rc, ctx.handle)
+        _lib.call("mgu_resize_bilinear_nhwc", src.device, src, Cs, B, h, w, Cs, out_nhwc, out_nhwc.shape[3], c_off, H, W)
 
     def forward(self, f_u_list, f_g, target_spatial_size=None, region_to_pixel_map=None):
         B = f_u_list[0].size(0)
@@ -134,8 +120,7 @@ class FeatureFusion(nn.Module):
         if self.fusion_method not in ("concat", "add"):
             raise NotImplementedError(f"Fusion method '{self.fusion_method}' not implemented.")  # :157
         dev = f_u_list[0].device
-        if not f_u_list[0].is_cuda:
-            raise RuntimeError("mgunet.FeatureFusion runs only on a HIP device (MI355X); there is deliberately no CPU fallback")
+        _lib.require_hip(f_u_list[0], "mgunet.FeatureFusion")
         per_region = f_g.ndim == 2 and region_to_pixel_map is not None
         if not per_region and f_g.ndim != 4:
             raise ValueError(f"f_g has unsupported shape {f_g.shape}. "
@@ -145,13 +130,12 @@ class FeatureFusion(nn.Module):
         add = self.fusion_method == "add"
         if add and Cu != Dg:
             raise ValueError("Channel dimensions must match for 'add' fusion or implement adaptation.")  # :153-154
-        ctx = _context(dev)
         fused = torch.empty((B, H, W, Cu if add else Cu + Dg), device=dev, dtype=torch.float32)
         gbuf = torch.empty((B, H, W, Dg), device=dev, dtype=torch.float32) if add else fused
         g_off = 0 if add else Cu
         off = 0
         for t in f_u_list:                                                      # :67-78
-            self._place(ctx, t, fused, off, H, W)
+            self._place(t, fused, off, H, W)
             off += int(t.size(1))
         if per_region:                                                          # :84-138
             if Dg % 4 or f_g.shape[1] != Dg:
@@ -160,12 +144,9 @@ class FeatureFusion(nn.Module):
             if tuple(ids.shape) != (B, H, W):
                 raise ValueError(f"region_to_pixel_map must be (B, H, W) = ({B}, {H}, {W})")
             table = f_g.detach().float().contiguous()
-            with torch.cuda.device(dev):
-                rc = _lib.lib().mgu_region_map_gather_nhwc(ctx.handle, table.data_ptr(), table.shape[0], Dg, ids.data_ptr(), B * H * W,
-                                                           gbuf.data_ptr(), gbuf.shape[3], g_off, _lib.current_stream_ptr(dev))
-            _lib.check(rc, ctx.handle)
+            _lib.call("mgu_region_map_gather_nhwc", dev, table, table.shape[0], Dg, ids, B * H * W, gbuf, gbuf.shape[3], g_off)
         else:                                                                   # :140-144
-            self._place(ctx, f_g, gbuf, g_off, H, W)
+            self._place(f_g, gbuf, g_off, H, W)
         if add:
             fused += gbuf
         return fused.permute(0, 3, 1, 2)

@@ -13,7 +13,6 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .gat import _context
 from .objects import ObjectTable
 from .unet import UNet
 
@@ -81,9 +80,7 @@ def predict_tta(model: UNet, images: torch.Tensor, transforms: str = "d4"):
     _check_model(model)
     if not isinstance(images, torch.Tensor) or images.dim() != 4:
         raise ValueError("expected a (B,C,H,W) tensor")
-    if not images.is_cuda:
-        raise RuntimeError("predict_tta runs only on a HIP device (MI355X); move the model and input to 'cuda' -- there is "
-                           "deliberately no CPU fallback")
+    _lib.require_hip(images, "predict_tta")
     if images.dtype != torch.float32:
         raise TypeError(f"expected float32 input, got {images.dtype}")
     B, Cin, H, W = images.shape
@@ -96,28 +93,24 @@ def predict_tta(model: UNet, images: torch.Tensor, transforms: str = "d4"):
     if B == 0 or H == 0 or W == 0:
         raise ValueError("predict_tta needs a non-empty batch")
     dev = images.device
-    ctx = _context(dev)
-    stream = _lib.current_stream_ptr(dev)
     strides = (C.c_int64 * 4)(*images.stride())
     logits = []
-    with torch.no_grad(), torch.cuda.device(dev):
+    with torch.no_grad():
         for Hv, Wv, gv in groups:
             if gv == [(0, 0)]:   # the identity alone: the forward reads the caller's image through its strides
                 lg = model(images)[0]
             else:
                 buf = torch.empty((len(gv) * B, Cin, Hv, Wv), device=dev, dtype=torch.float32)
                 codes = (C.c_int32 * (2 * len(gv)))(*[v for fr in gv for v in fr])
-                _lib.check(_lib.lib().mgu_tta_views(ctx.handle, images.data_ptr(), B, Cin, H, W, strides, len(gv), codes,
-                                                    buf.data_ptr(), stream), ctx.handle)
+                _lib.call("mgu_tta_views", dev, images, B, Cin, H, W, strides, len(gv), codes, buf)
                 lg = model(buf)[0]
             logits.append(lg.permute(0, 2, 3, 1))   # the NHWC storage the forward wrote (contiguous)
         probs = torch.empty((B, H, W, Cls), device=dev, dtype=torch.float32)
         labels = torch.empty((B, H, W), device=dev, dtype=torch.int64)
         conf = torch.empty((B, H, W), device=dev, dtype=torch.float32)
         table = (C.c_int32 * (4 * len(views)))(*[v for row in views for v in row])
-        _lib.check(_lib.lib().mgu_tta_merge(ctx.handle, logits[0].data_ptr(), logits[1].data_ptr() if len(logits) > 1 else None, B, Cls,
-                                            H, W, len(views), table, probs.data_ptr(), labels.data_ptr(), conf.data_ptr(), stream),
-                   ctx.handle)
+        _lib.call("mgu_tta_merge", dev, logits[0], logits[1] if len(logits) > 1 else None, B, Cls, H, W, len(views), table, probs, labels,
+                  conf)
     return probs.permute(0, 3, 1, 2), labels, conf
 
 
@@ -140,9 +133,5 @@ def object_scores(table: ObjectTable, probs: torch.Tensor) -> torch.Tensor:
     nhwc = probs.permute(0, 2, 3, 1)
     if not nhwc.is_contiguous():
         nhwc = nhwc.contiguous()
-    ctx = _context(dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().mgu_object_scores(ctx.handle, table.labels.data_ptr(), nhwc.data_ptr(), B, H, W, Cls, table.offsets.data_ptr(),
-                                                N, table.class_id.data_ptr(), table.area.data_ptr(), scores.data_ptr(),
-                                                _lib.current_stream_ptr(dev)), ctx.handle)
+    _lib.call("mgu_object_scores", dev, table.labels, nhwc, B, H, W, Cls, table.offsets, N, table.class_id, table.area, scores)
     return scores

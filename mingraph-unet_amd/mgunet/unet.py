@@ -117,8 +117,7 @@ class UNet(nn.Module):
         if ctx is None:
             ctx = _lib.Context(idx)
             ctx.key = key
-            _lib.check(_lib.lib().mgu_unet_configure(ctx.handle, self.in_channels, self.num_classes,
-                                                     self.init_features, self.depth, code), ctx.handle)
+            _lib.call("mgu_unet_configure", device, self.in_channels, self.num_classes, self.init_features, self.depth, code, ctx=ctx)
             self._ctx[key] = ctx
         return ctx
 
@@ -151,8 +150,7 @@ class UNet(nn.Module):
             keep.append(v)
             descs.append(_lib.TensorDesc(k.encode(), v.data_ptr(), v.numel()))
         arr = (_lib.TensorDesc * len(descs))(*descs)
-        _lib.check(_lib.lib().mgu_unet_load_weights(ctx.handle, arr, len(descs), _lib.current_stream_ptr(device)),
-                   ctx.handle)
+        _lib.call("mgu_unet_load_weights", device, arr, len(descs), ctx=ctx)
         self._loaded_sig[ctx.key] = sig
 
     def mark_parameters_changed(self) -> None:
@@ -174,8 +172,7 @@ class UNet(nn.Module):
                 del self._loaded_sig[key]
         if self._loaded_sig.get(ctx.key) is None:
             return
-        with torch.cuda.device(device):
-            _lib.check(_lib.lib().mgu_unet_refresh_weights(ctx.handle, _lib.current_stream_ptr(device)), ctx.handle)
+        _lib.call("mgu_unet_refresh_weights", device, ctx=ctx)
 
     def _bn_counters(self):
         return [m.num_batches_tracked for m in self.modules() if isinstance(m, nn.BatchNorm2d)]
@@ -191,9 +188,7 @@ class UNet(nn.Module):
     def forward(self, x):
         if not isinstance(x, torch.Tensor) or x.dim() != 4:
             raise ValueError("expected a (B,C,H,W) tensor")
-        if not x.is_cuda:
-            raise RuntimeError("mgunet.UNet runs only on a HIP device (MI355X); move the model and input to "
-                               "'cuda' -- there is deliberately no CPU fallback")
+        _lib.require_hip(x, "mgunet.UNet")
         if x.dtype != torch.float32:
             raise TypeError(f"expected float32 input, got {x.dtype}")
         if self.training and self.compute_dtype != torch.float32:
@@ -209,19 +204,14 @@ class UNet(nn.Module):
         for _ in range(d):
             hs.append(hs[-1] // 2)
             ws.append(ws[-1] // 2)
-        with torch.cuda.device(dev):
-            # NHWC storage, NCHW logical view (channels_last semantics without its size-1 ambiguities)
-            adt = self.compute_dtype  # activations the forward stores; logits are always fp32
-            logits = torch.empty((B, H, W, self.num_classes), device=dev, dtype=torch.float32)
-            cats = [torch.empty((B, hs[i], ws[i], 2 * (f << i)), device=dev, dtype=adt) for i in range(d)]
-            feats = [torch.empty((B, hs[i], ws[i], f << i), device=dev, dtype=adt) for i in range(d)]
-            cat_ptrs = (C.c_void_p * d)(*[t.data_ptr() for t in cats])
-            feat_ptrs = (C.c_void_p * d)(*[t.data_ptr() for t in feats])
-            sn, sc, sh, sw = x.stride()
-            rc = _lib.lib().mgu_unet_forward(ctx.handle, x.data_ptr(), B, H, W, sn, sc, sh, sw, logits.data_ptr(),
-                                            cat_ptrs, feat_ptrs, 1 if self.training else 0,
-                                            _lib.current_stream_ptr(dev))
-        _lib.check(rc, ctx.handle)
+        # NHWC storage, NCHW logical view (channels_last semantics without its size-1 ambiguities)
+        adt = self.compute_dtype  # activations the forward stores; logits are always fp32
+        logits = torch.empty((B, H, W, self.num_classes), device=dev, dtype=torch.float32)
+        cats = [torch.empty((B, hs[i], ws[i], 2 * (f << i)), device=dev, dtype=adt) for i in range(d)]
+        feats = [torch.empty((B, hs[i], ws[i], f << i), device=dev, dtype=adt) for i in range(d)]
+        cat_ptrs = (C.c_void_p * d)(*[t.data_ptr() for t in cats])
+        feat_ptrs = (C.c_void_p * d)(*[t.data_ptr() for t in feats])
+        _lib.call("mgu_unet_forward", dev, x, B, H, W, *x.stride(), logits, cat_ptrs, feat_ptrs, 1 if self.training else 0, ctx=ctx)
         if self.training:
             # the library updated running_mean/var in place through raw pointers: bump the counters the
             # reference's BatchNorm bumps (num_batches_tracked) and drop the folded eval scale/shift

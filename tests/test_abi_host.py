@@ -32,6 +32,26 @@ def test_library_exports_every_declared_symbol():
     assert sorted(_lib._PROTOS) == syms
 
 
+def test_prototypes_are_read_from_the_header(tmp_path):
+    _lib.lib()
+    protos = _lib._PROTOS
+    assert sorted(protos) == header_symbols()
+    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mgunet.h")).read(), flags=re.S)
+    streamed = {s for s in header_symbols() if re.search(rf"\b{s}\s*\([^)]*\bhip_stream\s*\)", txt)}
+    assert streamed and {name for name, (_, _, takes_stream) in protos.items() if takes_stream} == streamed
+    assert protos["mgu_dropout_mask"][1][1:4] == [C.c_uint64, C.c_uint64, C.c_int64]
+    assert protos["mgu_match_objects"][1][9:11] == [C.c_int64, C.c_double]
+    assert protos["mgu_unet_param_count"][0] is C.c_int64
+    assert protos["mgu_unet_flops"][0] is C.c_double
+    assert protos["mgu_version"][:2] == (C.c_char_p, [])
+    assert protos["mgu_unet_load_weights"][1] == [C.c_void_p, C.POINTER(_lib.TensorDesc), C.c_int, C.c_void_p]
+    assert protos["mgu_tv_loss"][1][6:11] == [C.c_int64] * 4 + [C.c_float]
+    bad = tmp_path / "bad.h"
+    bad.write_text("int mgu_fine(mgu_ctx* ctx, void* hip_stream);\nint mgu_bad(mgu_ctx* ctx, long n);\n")
+    with pytest.raises(TypeError, match="mgu_bad"):
+        _lib.parse_header(str(bad))
+
+
 def test_create_fails_loudly_without_gpu():
     if torch.cuda.is_available():
         pytest.skip("GPU present")
