@@ -1,6 +1,6 @@
 // Backward building blocks behind the C-ABI: each entry point runs ONE stage of loss.backward()
-// (scripts/train_segmentation.py:133) through exactly the launchers mgu_unet_backward uses (mgunet_train.hip), on
-// caller-provided tensors.  They exist so that every backward kernel can be checked in isolation against a float64
+// (scripts/train_segmentation.py:133) on caller-provided tensors.  The convolution stages call the very functions mgu_unet_backward
+// runs (conv_wgrad, conv_dgrad, convt_wgrad, convt_dgrad in mgunet_train.hip) on a Layer that describes the caller's tensors.  They exist so that every backward kernel can be checked in isolation against a float64
 // reference on fixed (x, dz) -- where nothing is ill-conditioned -- instead of only through a whole train step whose
 // BatchNorm + ReLU + MaxPool chain amplifies rounding (tests/test_gpu_backward_kernels.py).
 // Kernel selection is the launchers' own (pick_conv, pick_wgrad), on the context's switches (MGU_NO_WINO_WGRAD, MGU_NO_WGRAD_HALO,
@@ -25,23 +25,16 @@ __global__ void fold_batch_stats_kernel(const float* gamma, const float* beta, c
   }
 }
 
-struct Scratch {
-  float *dwp, *dgp, *wug;
-  size_t dwp_floats;
-  double *red, *sums;
+struct Scratch : BwdScratch {
+  float* wug;   // a Winograd data-gradient set
 };
 
 int get_scratch(mgu_ctx* c, size_t panel_floats, size_t dgp_floats, size_t wug_floats, int Cmax, Scratch* out) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off += (bytes + 255) / 256 * 256;
-    return o;
-  };
+  Carve k;
   const size_t dwp_floats = std::max(panel_floats, (size_t)12 << 20);   // room for the atomics-free kernels' partial panels
-  const size_t o_dwp = take(dwp_floats * 4), o_dgp = take(std::max<size_t>(dgp_floats, 64) * 4), o_wug = take((wug_floats + 64) * 4);
-  const size_t o_sums = take(sizeof(double) * 2 * (size_t)std::max(Cmax, 64) + 64);
-  int rc = ensure(c, &c->gws, &c->gws_bytes, off);
+  const size_t o_dwp = k.take(dwp_floats * 4), o_dgp = k.take(std::max<size_t>(dgp_floats, 64) * 4), o_wug = k.take((wug_floats + 64) * 4);
+  const size_t o_sums = k.take(sizeof(double) * 2 * (size_t)std::max(Cmax, 64) + 64);
+  int rc = ensure(c, &c->gws, &c->gws_bytes, k.off);
   if (rc) return rc;
   const size_t need = chan_reduce_work_bytes(std::max(Cmax, 64));
   if (c->redws_bytes < need) {   // the slots must be zero between reductions: a fresh allocation is cleared once
@@ -50,10 +43,20 @@ int get_scratch(mgu_ctx* c, size_t panel_floats, size_t dgp_floats, size_t wug_f
   }
   char* g = (char*)c->gws;
   out->dwp = (float*)(g + o_dwp), out->dgp = (float*)(g + o_dgp), out->wug = (float*)(g + o_wug);
-  out->dwp_floats = dwp_floats;
+  out->dwp_floats = dwp_floats, out->dgp_floats = std::max<size_t>(dgp_floats, 64);
   out->sums = (double*)(g + o_sums);
   out->red = (double*)c->redws;
+  out->clear = true;   // the scratch is shared with every other building block: no panel row is known to be zero
   return MGU_OK;
+}
+
+// the caller's tensors as the layer whose backward runs: its shape and the grid its forward ran on (input grid of a ConvTranspose)
+Layer caller_layer(int Cin, int Cout, int KS, bool convt, int B, int H, int W) {
+  Layer L;
+  L.Cin = Cin, L.Cp = rup(Cin, 4), L.Cout = Cout, L.KS = KS, L.convt = convt;
+  L.K = KS * KS * L.Cp, L.Kp = rup(L.K, 32);
+  L.t_B = B, L.t_H = H, L.t_W = W;
+  return L;
 }
 
 }  // namespace
@@ -65,27 +68,15 @@ int mgu_conv2d_wgrad_nhwc(mgu_ctx* c, const void* in_dev, int ld_in, const void*
   if (!c) return MGU_ERR_INVALID;
   if (!in_dev || !dz_dev || !dw_oihw_dev || B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || (ksize != 1 && ksize != 3))
     return fail(c, MGU_ERR_INVALID, "bad conv2d_wgrad args (ksize must be 1 or 3)");
-  const int Cp = rup(Cin, 4), N = rup(Cout, 4);
-  if (ld_in < Cp || (ld_in & 3)) return fail(c, MGU_ERR_INVALID, "ld_in must be a multiple of 4 and >= Cin rounded up to 4");
+  if (ld_in < rup(Cin, 4) || (ld_in & 3)) return fail(c, MGU_ERR_INVALID, "ld_in must be a multiple of 4 and >= Cin rounded up to 4");
   if ((int64_t)B * H * W >= (1ll << 31)) return fail(c, MGU_ERR_INVALID, "B*H*W must be < 2^31");
   HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = (hipStream_t)hip_stream;
-  const int K = ksize * ksize * Cp, Kp = rup(K, 32);
+  Layer L = caller_layer(Cin, Cout, ksize, false, B, H, W);
+  L.t_in = (const float*)in_dev, L.t_ldin = ld_in;   // dz rows are padded to a multiple of 4 channels (zeros)
   Scratch sc;
-  int rc = get_scratch(c, (size_t)rup(N, 128) * Kp, 0, 0, 64, &sc);
+  int rc = get_scratch(c, (size_t)rup(rup(Cout, 4), 128) * L.Kp, 0, 0, 64, &sc);
   if (rc) return rc;
-  WgradDesc d;
-  memset(&d, 0, sizeof d);
-  d.tn = &c->tn;
-  d.z = (const float*)dz_dev, d.ldz = N, d.zoff = 0;   // dz rows are padded to a multiple of 4 channels (zeros)
-  d.in = (const float*)in_dev, d.ldin = ld_in, d.inoff = 0, d.Cp = Cp;
-  d.KS = ksize;
-  d.M = B * H * W, d.H = H, d.W = W;
-  d.N = N, d.K = K, d.Kp = Kp;
-  d.dw = sc.dwp, d.dw_capacity = sc.dwp_floats;
-  HIPCHK(c, launch_wgrad_f32(d, s));
-  HIPCHK(c, launch_unpack_conv_grad(sc.dwp, d.groups, (size_t)d.N * d.Kp, (float*)dw_oihw_dev, Cout, Cin, Cp, ksize, Kp, s));
-  return MGU_OK;
+  return conv_wgrad(c, L, (const float*)dz_dev, (float*)dw_oihw_dev, sc, false, (hipStream_t)hip_stream);
 }
 
 int mgu_conv2d_dgrad_nhwc(mgu_ctx* c, const void* dz_dev, const void* w_oihw_dev, int B, int H, int W, int Cin, int Cout, int ksize,
@@ -96,29 +87,15 @@ int mgu_conv2d_dgrad_nhwc(mgu_ctx* c, const void* dz_dev, const void* w_oihw_dev
   if (ld_out < Cin) return fail(c, MGU_ERR_INVALID, "ld_out %d < Cin %d", ld_out, Cin);
   if ((int64_t)B * H * W >= (1ll << 31)) return fail(c, MGU_ERR_INVALID, "B*H*W must be < 2^31");
   HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = (hipStream_t)hip_stream;
-  const int Cop = rup(Cout, 4), Kd = ksize * ksize * Cop, Kpd = rup(Kd, 32);
-  const bool wino = wino_dgrad_layer(c->tn, ksize, Cop);
+  const int Cop = rup(Cout, 4);
+  Layer L = caller_layer(Cin, Cout, ksize, false, B, H, W);
+  L.w_src = (const float*)w_oihw_dev;
   Scratch sc;
-  int rc = get_scratch(c, 0, (size_t)rup(Cin, 128) * Kpd, wino ? wino_u_floats(Cin, Cop) : 0, 64, &sc);
+  const bool wino = wino_dgrad_layer(c->tn, ksize, Cop);
+  int rc = get_scratch(c, 0, (size_t)rup(Cin, 128) * rup(ksize * ksize * Cop, 32), wino ? wino_u_floats(Cin, Cop) : 0, 64, &sc);
   if (rc) return rc;
-  IgemmDesc d;
-  memset(&d, 0, sizeof d);
-  d.tn = &c->tn;
-  d.in = (const float*)dz_dev, d.w = sc.dgp, d.out = (float*)din_dev;
-  d.M = B * H * W, d.H = H, d.W = W;
-  d.Cp = Cop, d.ldin = Cop, d.KS = ksize, d.K = Kd, d.Kp = Kpd;
-  d.N = Cin, d.ldout = ld_out;
-  if (wino) d.wu = sc.wug;
-  const ConvKernel k = pick_conv(d, 0);
-  if (conv_is_wino(k)) {
-    HIPCHK(c, launch_pack_wino_w((const float*)w_oihw_dev, sc.wug, Cin, Cout, Cop, 1, c->tn.wino_prec, s));
-  } else {
-    HIPCHK(c, hipMemsetAsync(sc.dgp, 0, (size_t)rup(Cin, 128) * Kpd * sizeof(float), s));   // panel rows are padded to 128
-    HIPCHK(c, launch_pack_dgrad_w((const float*)w_oihw_dev, sc.dgp, Cout, Cin, Cop, ksize, Kpd, s));
-  }
-  HIPCHK(c, launch_conv(d, k, 0, s));
-  return MGU_OK;
+  L.wug = sc.wug;   // the Winograd set, when the pick takes that kernel, is packed into the scratch
+  return conv_dgrad(c, L, (const float*)dz_dev, (float*)din_dev, ld_out, sc, false, (hipStream_t)hip_stream);
 }
 
 int mgu_conv_transpose2x2_wgrad_nhwc(mgu_ctx* c, const void* in_dev, const void* dout_dev, int ld_d, int c_off, int B, int H, int W,
@@ -130,19 +107,12 @@ int mgu_conv_transpose2x2_wgrad_nhwc(mgu_ctx* c, const void* in_dev, const void*
   if ((int64_t)B * H * W * 4 >= (1ll << 31)) return fail(c, MGU_ERR_INVALID, "4*B*H*W must be < 2^31");
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)hip_stream;
-  const int Kt = 4 * Cout, Kpt = rup(Kt, 32);
+  Layer U = caller_layer(Cin, Cout, 1, true, B, H, W);
+  U.t_in = (const float*)in_dev, U.t_ldin = Cin;
   Scratch sc;
-  int rc = get_scratch(c, (size_t)rup(Cin, 128) * Kpt, 0, 0, Cout, &sc);
+  int rc = get_scratch(c, (size_t)rup(Cin, 128) * rup(4 * Cout, 32), 0, 0, Cout, &sc);
   if (rc) return rc;
-  // the roles swap (mgu_unet_backward): Z = the layer's INPUT (M, Cin), A = 2x2 stride-2 gather of d(out)
-  WgradDesc g;
-  memset(&g, 0, sizeof g);
-  g.tn = &c->tn;
-  g.z = (const float*)in_dev, g.ldz = Cin, g.in = (const float*)dout_dev, g.ldin = ld_d, g.inoff = c_off, g.Cp = Cout, g.KS = 2;
-  g.M = B * H * W, g.H = H, g.W = W, g.Hs = 2 * H, g.Ws = 2 * W;
-  g.N = Cin, g.K = Kt, g.Kp = Kpt, g.dw = sc.dwp, g.dw_capacity = sc.dwp_floats;
-  HIPCHK(c, launch_wgrad_f32(g, s));
-  HIPCHK(c, launch_unpack_convt_grad(sc.dwp, g.groups, (size_t)g.N * g.Kp, (float*)dw_iohw_dev, Cin, Cout, Kpt, s));
+  if ((rc = convt_wgrad(c, U, (const float*)dout_dev, ld_d, c_off, 2 * H, 2 * W, (float*)dw_iohw_dev, sc, s))) return rc;
   if (dbias_dev)
     HIPCHK(c, launch_colsum((const float*)dout_dev + c_off, ld_d, (int64_t)B * H * W * 4, Cout, sc.red, (float*)dbias_dev, s));
   return MGU_OK;
@@ -156,28 +126,12 @@ int mgu_conv_transpose2x2_dgrad_nhwc(mgu_ctx* c, const void* dout_dev, int ld_d,
   if (ld_d < c_off + Cout || (ld_d & 3) || (c_off & 3)) return fail(c, MGU_ERR_INVALID, "ld_d / c_off must be multiples of 4, ld_d >= c_off + Cout");
   if ((int64_t)B * H * W * 4 >= (1ll << 31)) return fail(c, MGU_ERR_INVALID, "4*B*H*W must be < 2^31");
   HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = (hipStream_t)hip_stream;
-  const int Kt = 4 * Cout, Kpt = rup(Kt, 32);
+  Layer U = caller_layer(Cin, Cout, 1, true, B, H, W);
+  U.w_src = (const float*)w_iohw_dev;
   Scratch sc;
-  const size_t dgp_floats = std::max((size_t)rup(Cin, 128) * Kpt, convt_x3_dgrad_floats(Cin, Cout));
-  int rc = get_scratch(c, 0, dgp_floats, 0, 64, &sc);
+  int rc = get_scratch(c, 0, std::max((size_t)rup(Cin, 128) * rup(4 * Cout, 32), convt_x3_dgrad_floats(Cin, Cout)), 0, 64, &sc);
   if (rc) return rc;
-  IgemmDesc q;
-  memset(&q, 0, sizeof q);
-  q.tn = &c->tn;
-  q.in = (const float*)dout_dev + c_off, q.w = sc.dgp, q.out = (float*)din_dev, q.M = B * H * W, q.H = H, q.W = W, q.Cp = Cout,
-  q.ldin = ld_d;
-  q.KS = 2, q.K = Kt, q.Kp = Kpt, q.N = Cin, q.ldout = Cin, q.Hout = 2 * H, q.Wout = 2 * W;
-  q.wu = sc.dgp;
-  const ConvKernel k = pick_conv(q, 0);
-  if (k == ConvKernel::ConvtX3Dgrad) {   // the forward layer's three-piece kernel in its gather mode
-    HIPCHK(c, launch_pack_convt_x3_dgrad((const float*)w_iohw_dev, sc.dgp, Cin, Cout, s));
-  } else {
-    HIPCHK(c, hipMemsetAsync(sc.dgp, 0, (size_t)rup(Cin, 128) * Kpt * sizeof(float), s));
-    HIPCHK(c, launch_pack_convt_dgrad_w((const float*)w_iohw_dev, sc.dgp, Cin, Cout, Kpt, s));
-  }
-  HIPCHK(c, launch_conv(q, k, 0, s));
-  return MGU_OK;
+  return convt_dgrad(c, U, (const float*)dout_dev + c_off, ld_d, 2 * H, 2 * W, (float*)din_dev, sc, false, (hipStream_t)hip_stream);
 }
 
 int mgu_bn_relu_train_nhwc(mgu_ctx* c, const void* z_dev, const void* gamma_dev, const void* beta_dev, int64_t M, int C, void* y_dev,

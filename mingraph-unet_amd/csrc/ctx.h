@@ -47,6 +47,15 @@ struct Layer {
   float* t_y = nullptr;         // relu(bn(z)) with pitch t_ldy
   int t_ldy = 0;
   int t_B = 0, t_H = 0, t_W = 0;  // grid the conv ran on (input grid for convT)
+  int level = 0;                  // grid level the layer runs on (input grid for convT): H >> level after `level` MaxPool2d(2)
+};
+
+// One ConvBlock of the network (unet_encoder.py:4-25) and, in a decoder block, the ConvTranspose2d in front of it: indices into
+// mgu_ctx::layers.  Every walk over the network (parameter offsets, workspace plans, forwards, backward, FLOP counts) reads these.
+struct Block {
+  int up = -1;            // decoder: ConvTranspose2d (unet_decoder.py:36); -1 elsewhere
+  int conv1 = 0, conv2 = 0;
+  int level = 0;          // grid level of conv1 / conv2: also the skip connection's (cat_dev / feat_dev index)
 };
 
 struct mgu_ctx {
@@ -82,6 +91,9 @@ struct mgu_ctx {
   size_t objws_bytes = 0;
   int in_ch = 0, ncls = 0, feat = 0, depth = 0, dtype = 0, Cp0 = 0;
   std::vector<Layer> layers;  // enc[i].conv1, enc[i].conv2 ..., bott.conv1, bott.conv2, dec[b].up, dec[b].conv1, dec[b].conv2 ..., final
+  std::vector<Block> enc, dec;   // encoder blocks shallow -> deep (level i), decoder blocks deep -> shallow (level depth-1-b)
+  Block bott;                    // bottleneck (level depth)
+  int head = 0;                  // the final 1x1 conv
   int64_t nparams = 0;
   float* arena = nullptr;
   size_t arena_floats = 0;
@@ -100,12 +112,7 @@ struct mgu_ctx {
   int tB = 0, tH = 0, tW = 0;
   std::vector<float*> t_cat, t_feat, t_pooled;
   float* t_logits = nullptr;
-  void gat_destroy(mgu_ctx* c);   // gat_api.hip
-int gmax_buffer(mgu_ctx* c, int need, unsigned long long** buf, unsigned* gen);
-int gat_linear_st(mgu_ctx* c, const float* X, int N, int Fin, const float* W, const float* a, int heads, int Fh, float* wh, float* st,
-                  hipStream_t s);
-
-// gradient exchange (comm.hip): RCCL communicator owned by this context, its stream and a small pool of ordering events
+  // gradient exchange (comm.hip): RCCL communicator owned by this context, its stream and a small pool of ordering events
   void* comm = nullptr;     // ncclComm_t
   int comm_world = 1, comm_rank = 0;
   hipStream_t comm_stream = nullptr;
@@ -177,12 +184,22 @@ inline const char* err_word_message(int w) {
                    "mgu_dice_loss; F.one_hot / CrossEntropyLoss raise on it)";
 }
 
-struct ProfScope {  // records an event pair around one launch when profiling is on
+// 256-byte aligned regions of one scratch buffer: take(bytes) returns the next region's offset, off is the size so far
+struct Carve {
+  size_t off = 0;
+  size_t take(size_t bytes) {
+    const size_t o = off;
+    off += (bytes + 255) / 256 * 256;
+    return o;
+  }
+};
+
+struct ProfScope {  // records an event pair around one launch when profiling is on (c == nullptr: the caller records nothing)
   mgu_ctx* c;
   hipStream_t s;
   int idx = -1;
   ProfScope(mgu_ctx* c_, hipStream_t s_, const char* name = "conv/GEMM", double alg = 0, double mfma = 0, int pipe = -1) : c(c_), s(s_) {
-    if (!c->prof) return;
+    if (!c || !c->prof) return;
     if ((size_t)c->ev_used >= c->prec.size()) c->prec.resize(c->ev_used + 1);
     c->prec[c->ev_used] = {name, alg, mfma, pipe};
     if ((size_t)(2 * c->ev_used + 2) > c->ev.size()) {
@@ -210,6 +227,64 @@ inline void level_dims(int H, int W, int depth, std::vector<int>& hs, std::vecto
   }
 }
 
+// Descriptors of the three shapes the host code launches.  A forward Conv2d (KS 1 / 3) or ConvTranspose2d(2, 2) (out_mode 1) of
+// layer L on a B x H x W grid, reading L's packed weights; the caller adds relu / scale / shift / output grid / fused epilogues.
+inline mgu::IgemmDesc layer_desc(const mgu_ctx* c, const Layer& L, const void* in, int ldin, int B, int H, int W, void* out, int ldout, int coff) {
+  mgu::IgemmDesc d;
+  memset(&d, 0, sizeof d);
+  d.tn = &c->tn;
+  d.in = (const float*)in;   // element type follows c->dtype; the descriptor carries raw pointers
+  d.w = L.wp, d.wu = L.wu, d.out = (float*)out;
+  d.M = B * H * W, d.H = H, d.W = W;
+  d.Cp = L.Cp, d.ldin = ldin, d.KS = L.KS, d.K = L.K, d.Kp = L.Kp;
+  d.N = L.N, d.ldout = ldout, d.coff = coff;
+  d.out_mode = L.convt ? 1 : 0, d.ct_cout = L.Cout;
+  return d;
+}
+// The data gradient of layer L on the grid of its last forward (L.t_B, t_H, t_W) as a gather over dz (pitch lddz): KS 1 / 3 is the
+// conv with the flipped, transposed weights (Cout rounded up to 4 channels), a ConvTranspose the 2x2 stride-2 gather from its
+// Hout x Wout output.  `panel` is the direct-panel form; the caller offers the other forms in d.wu.
+inline mgu::IgemmDesc dgrad_desc(const mgu_ctx* c, const Layer& L, const float* dz, int lddz, const float* panel, float* out, int ldout,
+                            int Hout = 0, int Wout = 0) {
+  const int KS = L.convt ? 2 : L.KS, Cop = rup(L.Cout, 4);
+  mgu::IgemmDesc d;
+  memset(&d, 0, sizeof d);
+  d.tn = &c->tn;
+  d.in = dz, d.w = panel, d.out = out;
+  d.M = L.t_B * L.t_H * L.t_W, d.H = L.t_H, d.W = L.t_W;
+  d.Cp = Cop, d.ldin = lddz, d.KS = KS, d.K = KS * KS * Cop, d.Kp = rup(d.K, 32);
+  d.N = L.Cin, d.ldout = ldout, d.Hout = Hout, d.Wout = Wout;
+  return d;
+}
+// A plain GEMM out = in (M x K) * panel^T (N columns, row pitch Kp), columns >= split_n going to out2 (pitch ld2)
+inline mgu::IgemmDesc gemm_desc(const mgu_ctx* c, const float* in, int M, int K, const float* panel, int Kp, int N, float* out, int ldout,
+                           int split_n, float* out2, int ld2) {
+  mgu::IgemmDesc d;
+  memset(&d, 0, sizeof d);
+  d.tn = &c->tn;
+  d.in = in, d.w = panel, d.out = out;
+  d.M = M, d.H = 1, d.W = M;
+  d.Cp = K, d.ldin = K, d.KS = 1, d.K = K, d.Kp = Kp;
+  d.N = N, d.ldout = ldout;
+  d.split_n = split_n, d.out2 = out2, d.ld2 = ld2;
+  return d;
+}
+// A weight gradient dW[n][k] = sum_m z[m][n] * gather(in)[m][k] over the B x H x W rows: KS 1 / 3 gathers a conv's input, KS 2 a
+// ConvTranspose's output (stride 2 from Hs x Ws); partial panels in dw (dw_capacity floats)
+inline mgu::WgradDesc wgrad_desc(const mgu_ctx* c, const float* z, int ldz, const float* in, int ldin, int inoff, int Cp, int KS, int B, int H,
+                            int W, int Hs, int Ws, int N, float* dw, size_t dw_capacity) {
+  mgu::WgradDesc d;
+  memset(&d, 0, sizeof d);
+  d.tn = &c->tn;
+  d.z = z, d.ldz = ldz;
+  d.in = in, d.ldin = ldin, d.inoff = inoff, d.Cp = Cp;
+  d.KS = KS;
+  d.M = B * H * W, d.H = H, d.W = W, d.Hs = Hs, d.Ws = Ws;
+  d.N = N, d.K = KS * KS * Cp, d.Kp = rup(d.K, 32);
+  d.dw = dw, d.dw_capacity = dw_capacity;
+  return d;
+}
+
 // one fused conv / convT / 1x1 launch described by a Layer (scale/shift chosen by the caller)
 int run_layer(mgu_ctx* c, const Layer& L, const void* in, int ldin, int B, int H, int W, void* out, int ldout, int coff,
               int relu, const float* scale, const float* shift, int Hout, int Wout, hipStream_t s,
@@ -227,6 +302,24 @@ int comm_join(mgu_ctx* c, hipStream_t s);
 
 int repack_weights(mgu_ctx* c, hipStream_t s);   // mgunet_api.hip: every packed weight form from the recorded parameter tensors
 // training path (mgunet_train.hip)
+// Scratch of the backward launches: partial weight-gradient panels, the data-gradient weight form, reduction slots
+struct BwdScratch {
+  float *dwp = nullptr, *dgp = nullptr;
+  size_t dwp_floats = 0, dgp_floats = 0;
+  double *red = nullptr, *sums = nullptr;
+  bool clear = false;   // zero a direct panel before packing it (the building blocks)
+};
+// The four backward operations of a layer whose last forward is recorded in L.t_* (mgu_unet_backward, and the building blocks of
+// bwd_blocks.hip on a Layer describing the caller's tensors).  Each picks its kernel once, packs the weight form that kernel reads
+// -- unless the layer keeps a current one (L.wug, L.wxg) -- and launches; `record` adds a profiling record.
+int conv_dgrad(mgu_ctx* c, const Layer& L, const float* dz, float* out, int ldout, const BwdScratch& w, bool record, hipStream_t s);
+int convt_dgrad(mgu_ctx* c, const Layer& U, const float* dout, int ld_d, int Hout, int Wout, float* out, const BwdScratch& w, bool record,
+                hipStream_t s);
+// dz dense with pitch rup(Cout, 4); fold_rows != nullptr: also folds the bias-gradient column sums pending in w.red (bn_relu_bwd)
+int conv_wgrad(mgu_ctx* c, const Layer& L, const float* dz, float* dw, const BwdScratch& w, bool record, hipStream_t s,
+               int* fold_rows = nullptr, float* dbias = nullptr);
+int convt_wgrad(mgu_ctx* c, const Layer& U, const float* dout, int ld_d, int c_off, int Hout, int Wout, float* dw, const BwdScratch& w,
+                hipStream_t s);
 size_t train_ws_bytes(const mgu_ctx* c, int B, int H, int W);
 int unet_forward_train(mgu_ctx* c, const float* x, int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w, int B, int H,
                        int W, float* logits, void* const* cat_dev, void* const* feat_dev, hipStream_t s);

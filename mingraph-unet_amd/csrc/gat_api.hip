@@ -93,15 +93,7 @@ int mgud::gat_linear_st(mgu_ctx* c, const float* X, int N, int Fin, const float*
   HIPCHK(c, hipMemsetAsync(panel, 0, (size_t)NPp * Kp * sizeof(float), s));
   HIPCHK(c, launch_pack_conv_w(W, panel, 0, HF, Fin, Fin, 1, Kp, s));
   HIPCHK(c, launch_gat_wa_rows(W, a, panel, HF, heads, Fh, Fin, Kp, s));
-  IgemmDesc d;
-  memset(&d, 0, sizeof d);
-  d.tn = &c->tn;
-  d.in = X, d.w = panel, d.out = wh;
-  d.M = N, d.H = 1, d.W = N;
-  d.Cp = Fin, d.ldin = Fin, d.KS = 1, d.K = Fin, d.Kp = Kp;
-  d.N = HF + 2 * heads, d.ldout = HF;
-  d.split_n = HF, d.out2 = st, d.ld2 = 2 * heads;
-  HIPCHK(c, launch_igemm_f32(d, s));
+  HIPCHK(c, launch_igemm_f32(gemm_desc(c, X, N, Fin, panel, Kp, HF + 2 * heads, wh, HF, HF, st, 2 * heads), s));
   return MGU_OK;
 }
 
@@ -147,19 +139,9 @@ int forward_prepared(mgu_ctx* c, const mgu_gat_weights* p, const float* X, int N
   float* st = (float*)(g + o_st);
   const mgu_gat_weights* pw = p;
   if (p->fused) return fail(c, MGU_ERR_STATE, "internal: aggregate-first weights on the gather path");
-  IgemmDesc d;
-  memset(&d, 0, sizeof d);
-  d.tn = &c->tn;
-  d.in = X;
-  d.w = pw->buf;
-  d.out = Whp;
-  d.M = N, d.H = 1, d.W = N;
-  d.Cp = Fin, d.ldin = Fin, d.KS = 1, d.K = Fin, d.Kp = pw->Kp;
-  d.N = NP, d.ldout = HF;
-  d.split_n = HF, d.out2 = st, d.ld2 = 2 * heads;
   {
     ProfScope ps(c, s, "igemm_kernel (GAT linear)");
-    HIPCHK(c, launch_igemm_f32(d, s));
+    HIPCHK(c, launch_igemm_f32(gemm_desc(c, X, N, Fin, pw->buf, pw->Kp, NP, Whp, HF, HF, st, 2 * heads), s));
   }
   int32_t* node_graph = nullptr;  // node -> graph id (NULL: a single graph)
   if (num_graphs > 1) {

@@ -22,25 +22,52 @@ struct WsPlan {
 WsPlan plan_ws(const mgu_ctx* c, int B, int H, int W) {
   std::vector<int> hs, wsz;
   level_dims(H, W, c->depth, hs, wsz);
+  // elements of a block's output (Cout channels) on level l
+  auto out = [&](const Block& b, int l) { return (size_t)B * hs[l] * wsz[l] * c->layers[b.conv2].Cout; };
   WsPlan p;
-  size_t off = 0;
+  Carve k;
   const size_t es = c->dtype == MGU_DTYPE_BF16 ? 2 : 4;
-  auto take = [&](size_t elems) {
-    size_t o = off;
-    off += (elems * es + 255) / 256 * 256;
-    return o;
-  };
-  p.xin = take((size_t)B * H * W * c->Cp0);
-  size_t tmax = 0;
-  for (int i = 0; i <= c->depth; ++i) {
-    size_t f = (size_t)B * hs[i] * wsz[i] * ((size_t)c->feat << i);
-    if (f > tmax) tmax = f;
-  }
-  p.tmp = take(tmax);
-  for (int i = 0; i < c->depth; ++i) p.pooled.push_back(take((size_t)B * hs[i + 1] * wsz[i + 1] * ((size_t)c->feat << i)));
-  p.bott = take((size_t)B * hs[c->depth] * wsz[c->depth] * ((size_t)c->feat << c->depth));
-  p.total = off;
+  p.xin = k.take((size_t)B * H * W * c->Cp0 * es);
+  size_t tmax = out(c->bott, c->bott.level);
+  for (const Block& b : c->enc) tmax = std::max(tmax, out(b, b.level));
+  p.tmp = k.take(tmax * es);
+  for (const Block& b : c->enc) p.pooled.push_back(k.take(out(b, b.level + 1) * es));
+  p.bott = k.take(out(c->bott, c->bott.level) * es);
+  p.total = k.off;
   return p;
+}
+
+// Every weight form layer L keeps in the arena, in arena order: form(pointer, floats) once per form the layer holds.  It also makes
+// the layer's kernel-form decisions (wino, ctx3, ctb, first).  The one list sizes the arena and hands out its pointers.
+template <class F>
+void weight_forms(const mgu_ctx* c, Layer& L, F form) {
+  const int dtype = c->dtype;
+  L.wino = dtype == MGU_DTYPE_F32 && !L.convt && wino_layer(c->tn, L.KS, L.Cp);   // Winograd F(2x2,3x3) layers (wino_f32.hip)
+  // fp32 ConvTranspose on fragment-ordered three-piece weights (convt_x3.hip).  (A bf16-storage sibling of that kernel -- one
+  // fragment per operand straight from global memory -- was measured SLOWER than the LDS-tiled generic kernel, 0.178 vs 0.163 ms per
+  // step: 32-byte row segments per K slice; not kept.)
+  L.ctx3 = dtype == MGU_DTYPE_F32 && L.convt && convt_x3_layer(c->tn, L.Cin, L.Cout);
+  // bf16 storage: the layer's weights as bf16 MFMA fragments for convt2x2_bf16_kernel (whole-row LDS staging, transposed 16-byte stores)
+  L.ctb = dtype == MGU_DTYPE_BF16 && L.convt && convt_bf16f_layer(c->tn, L.Cin, L.Cout);
+  L.first = !L.convt && L.KS == 3 && first_conv_applicable(dtype, L.Cin, L.Cp, L.Cout, 8, 0);
+  form(L.wp, (size_t)L.Np * L.Kp);
+  form(L.scale, (size_t)L.Np);
+  form(L.shift, (size_t)L.Np);
+  if (L.wino) form(L.wu, wino_u_floats(L.Cout, L.Cp));
+  if (L.wino && rup(L.Cout, 4) % 16 == 0) form(L.wug, wino_u_floats(L.Cin, rup(L.Cout, 4)));   // data-gradient conv: roles swapped
+  if (L.ctx3) form(L.wu, convt_x3_floats(L.Cin, L.Cout));
+  if (L.ctb) form(L.wu, convt_bf16f_floats(L.Cin, L.Cout));
+  if (L.ctx3) form(L.wxg, convt_x3_dgrad_floats(L.Cin, L.Cout));
+  if (dtype == MGU_DTYPE_F32 && !L.convt && L.bn.empty())   // final conv: data-gradient panel
+    form(L.wxg, (size_t)rup(L.Cin, 128) * rup(L.KS * L.KS * rup(L.Cout, 4), 32));
+  if (L.first) form(L.wf, 9 * 4 * (size_t)L.Cout);
+  if (L.first) form(L.wfm, first_mfma_floats());
+  if (!L.bn.empty()) {   // batch statistics of the training forward
+    form(L.mean, (size_t)L.Np);
+    form(L.invstd, (size_t)L.Np);
+    form(L.tscale, (size_t)L.Np);
+    form(L.tshift, (size_t)L.Np);
+  }
 }
 
 }  // namespace
@@ -123,130 +150,77 @@ int mgu_unet_configure(mgu_ctx* c, int in_ch, int ncls, int feat, int depth, int
   c->in_ch = in_ch, c->ncls = ncls, c->feat = feat, c->depth = depth, c->dtype = dtype;
   c->Cp0 = rup(in_ch, dtype == MGU_DTYPE_BF16 ? 8 : 4);
   c->layers.clear();
-  auto add_block = [&](const std::string& prefix, int cin, int cp, int cout) {  // ConvBlock, unet_encoder.py:4-25
-    for (int j = 0; j < 2; ++j) {
-      Layer L;
-      L.prefix = prefix;
-      L.conv = j == 0 ? "conv1" : "conv2";
-      L.bn = j == 0 ? "bn1" : "bn2";
-      L.Cin = j == 0 ? cin : cout;
-      L.Cp = j == 0 ? cp : cout;
-      L.Cout = cout;
-      L.KS = 3;
-      c->layers.push_back(L);
-    }
+  c->enc.clear();
+  c->dec.clear();
+  auto add = [&](const std::string& prefix, const char* conv, const char* bn, int cin, int cp, int cout, int KS, bool convt, int level) {
+    Layer L;
+    L.prefix = prefix, L.conv = conv, L.bn = bn;
+    L.Cin = cin, L.Cp = cp, L.Cout = cout, L.KS = KS, L.convt = convt, L.level = level;
+    c->layers.push_back(L);
+    return (int)c->layers.size() - 1;
+  };
+  auto add_block = [&](const std::string& prefix, int cin, int cp, int cout, int level, int up) {  // ConvBlock, unet_encoder.py:4-25
+    Block b;
+    b.up = up, b.level = level;
+    b.conv1 = add(prefix, "conv1", "bn1", cin, cp, cout, 3, false, level);
+    b.conv2 = add(prefix, "conv2", "bn2", cout, cout, cout, 3, false, level);
+    return b;
   };
   int cin = in_ch, cp = c->Cp0, f = feat;
   for (int i = 0; i < depth; ++i) {  // unet_encoder.py:46-50
-    add_block("encoder.encoder_blocks." + std::to_string(i) + ".", cin, cp, f);
+    c->enc.push_back(add_block("encoder.encoder_blocks." + std::to_string(i) + ".", cin, cp, f, i, -1));
     cin = cp = f;
     f *= 2;
   }
-  add_block("encoder.bottleneck.", cin, cp, f);  // :53
+  c->bott = add_block("encoder.bottleneck.", cin, cp, f, depth, -1);  // :53
   int prev = f;
   for (int b = 0; b < depth; ++b) {  // unet_decoder.py:103-114
-    const int ci = feat << (depth - 1 - b);
-    Layer U;
-    U.prefix = "decoder.decoder_blocks." + std::to_string(b) + ".";
-    U.conv = "upsample";
-    U.Cin = U.Cp = prev;
-    U.Cout = prev / 2;
-    U.KS = 1;
-    U.convt = true;
-    c->layers.push_back(U);
-    add_block(U.prefix + "conv_block.", ci + prev / 2, ci + prev / 2, ci);
+    const int i = depth - 1 - b, ci = feat << i;
+    const std::string prefix = "decoder.decoder_blocks." + std::to_string(b) + ".";
+    const int up = add(prefix, "upsample", "", prev, prev, prev / 2, 1, true, i + 1);
+    c->dec.push_back(add_block(prefix + "conv_block.", ci + prev / 2, ci + prev / 2, ci, i, up));
     prev = ci;
   }
-  Layer Fc;  // unet_decoder.py:117
-  Fc.prefix = "decoder.";
-  Fc.conv = "final_conv";
-  Fc.Cin = Fc.Cp = prev;
-  Fc.Cout = ncls;
-  Fc.KS = 1;
-  c->layers.push_back(Fc);
-
-  size_t total = 0;
+  c->head = add("decoder.", "final_conv", "", prev, prev, ncls, 1, false, 0);  // unet_decoder.py:117
   for (auto& L : c->layers) {
     L.K = L.KS * L.KS * L.Cp;
     L.Kp = rup(L.K, dtype == MGU_DTYPE_BF16 ? 64 : 32);   // one 128-byte LDS row of k per pipeline step
     L.N = L.convt ? 4 * L.Cout : L.Cout;
     L.Np = rup(L.N, 128);
-    total += (size_t)L.Np * L.Kp + 2 * (size_t)L.Np + (L.bn.empty() ? 0 : 4 * (size_t)L.Np);
-    L.wino = dtype == MGU_DTYPE_F32 && !L.convt && wino_layer(c->tn, L.KS, L.Cp);   // Winograd F(2x2,3x3) layers (wino_f32.hip)
-    if (L.wino) total += wino_u_floats(L.Cout, L.Cp);
-    if (L.wino && rup(L.Cout, 4) % 16 == 0) total += wino_u_floats(L.Cin, rup(L.Cout, 4));   // data-gradient conv: roles swapped
-    // fp32 ConvTranspose on fragment-ordered three-piece weights (convt_x3.hip).  (A bf16-storage sibling of that kernel -- one
-    // fragment per operand straight from global memory -- was measured SLOWER than the LDS-tiled generic kernel, 0.178 vs 0.163 ms per
-    // step: 32-byte row segments per K slice; not kept.)
-    L.ctx3 = dtype == MGU_DTYPE_F32 && L.convt && convt_x3_layer(c->tn, L.Cin, L.Cout);
-    if (L.ctx3) total += convt_x3_floats(L.Cin, L.Cout) + convt_x3_dgrad_floats(L.Cin, L.Cout);
-    // bf16 storage: the layer's weights as bf16 MFMA fragments for convt2x2_bf16_kernel (whole-row LDS staging, transposed 16-byte stores)
-    L.ctb = dtype == MGU_DTYPE_BF16 && L.convt && convt_bf16f_layer(c->tn, L.Cin, L.Cout);
-    if (L.ctb) total += convt_bf16f_floats(L.Cin, L.Cout);
-    if (dtype == MGU_DTYPE_F32 && !L.convt && L.bn.empty()) total += (size_t)rup(L.Cin, 128) * rup(L.KS * L.KS * rup(L.Cout, 4), 32);   // final conv: data-gradient panel
-    L.first = !L.convt && L.KS == 3 && first_conv_applicable(dtype, L.Cin, L.Cp, L.Cout, 8, 0);
-    if (L.first) total += 9 * 4 * (size_t)L.Cout + first_mfma_floats();
   }
   // flat parameter order = the reference's named_parameters(): per ConvBlock conv1.{w,b}, conv2.{w,b},
   // bn1.{w,b}, bn2.{w,b} (unet_encoder.py:7-13); decoder block: upsample.{w,b} then its conv_block; final.
   {
     int64_t off = 0;
-    size_t i = 0;
-    auto wsize = [](const Layer& L) { return (int64_t)L.Cout * L.Cin * L.KS * L.KS * (L.convt ? 4 : 1); };
-    while (i < c->layers.size()) {
-      Layer& A = c->layers[i];
-      if (!A.bn.empty()) {  // ConvBlock = two consecutive layers
-        Layer& B2 = c->layers[i + 1];
-        A.off_w = off, off += wsize(A);
-        A.off_b = off, off += A.Cout;
-        B2.off_w = off, off += wsize(B2);
-        B2.off_b = off, off += B2.Cout;
-        A.off_gamma = off, off += A.Cout;
-        A.off_beta = off, off += A.Cout;
-        B2.off_gamma = off, off += B2.Cout;
-        B2.off_beta = off, off += B2.Cout;
-        i += 2;
-      } else {
-        A.off_w = off, off += wsize(A);
-        A.off_b = off, off += A.Cout;
-        i += 1;
-      }
-    }
+    auto conv = [&](Layer& L) {
+      L.off_w = off, off += (int64_t)L.Cout * L.Cin * L.KS * L.KS * (L.convt ? 4 : 1);
+      L.off_b = off, off += L.Cout;
+    };
+    auto bn = [&](Layer& L) {
+      L.off_gamma = off, off += L.Cout;
+      L.off_beta = off, off += L.Cout;
+    };
+    auto block = [&](const Block& b) {
+      if (b.up >= 0) conv(c->layers[b.up]);
+      conv(c->layers[b.conv1]), conv(c->layers[b.conv2]);
+      bn(c->layers[b.conv1]), bn(c->layers[b.conv2]);
+    };
+    for (const Block& b : c->enc) block(b);
+    block(c->bott);
+    for (const Block& b : c->dec) block(b);
+    conv(c->layers[c->head]);
     c->nparams = off;
   }
+  // one walk over every layer's weight forms sizes the arena, a second hands out its pointers
+  size_t total = 0;
+  for (auto& L : c->layers) weight_forms(c, L, [&](float*&, size_t n) { total += n; });
   if (c->arena) HIPCHK(c, hipFree(c->arena));
   c->arena = nullptr;
   HIPCHK(c, hipMalloc((void**)&c->arena, total * sizeof(float)));
   HIPCHK(c, hipMemset(c->arena, 0, total * sizeof(float)));
   c->arena_floats = total;
   float* p = c->arena;
-  for (auto& L : c->layers) {
-    L.wp = p;
-    p += (size_t)L.Np * L.Kp;
-    L.scale = p;
-    p += L.Np;
-    L.shift = p;
-    p += L.Np;
-    L.wu = nullptr;
-    if (L.wino) L.wu = p, p += wino_u_floats(L.Cout, L.Cp);
-    L.wug = nullptr, L.wug_valid = false;
-    if (L.wino && rup(L.Cout, 4) % 16 == 0) L.wug = p, p += wino_u_floats(L.Cin, rup(L.Cout, 4));
-    if (L.ctx3) L.wu = p, p += convt_x3_floats(L.Cin, L.Cout);
-    if (L.ctb) L.wu = p, p += convt_bf16f_floats(L.Cin, L.Cout);
-    L.wxg = nullptr, L.wxg_valid = false;
-    if (L.ctx3) L.wxg = p, p += convt_x3_dgrad_floats(L.Cin, L.Cout);
-    if (c->dtype == MGU_DTYPE_F32 && !L.convt && L.bn.empty()) L.wxg = p, p += (size_t)rup(L.Cin, 128) * rup(L.KS * L.KS * rup(L.Cout, 4), 32);
-    L.wf = nullptr;
-    if (L.first) L.wf = p, p += 9 * 4 * (size_t)L.Cout;
-    L.wfm = nullptr;
-    if (L.first) L.wfm = p, p += first_mfma_floats();
-    if (!L.bn.empty()) {
-      L.mean = p, p += L.Np;
-      L.invstd = p, p += L.Np;
-      L.tscale = p, p += L.Np;
-      L.tshift = p, p += L.Np;
-    }
-  }
+  for (auto& L : c->layers) weight_forms(c, L, [&](float*& form, size_t n) { form = p, p += n; });
   c->configured = true;
   c->have_train_fwd = false;
   c->loaded = false;
@@ -422,31 +396,8 @@ int mgud::repack_weights(mgu_ctx* c, hipStream_t s) {
 int mgud::run_layer(mgu_ctx* c, const Layer& L, const void* in_v, int ldin, int B, int H, int W, void* out_v, int ldout,
                     int coff, int relu, const float* scale, const float* shift, int Hout, int Wout, hipStream_t s,
                     void* pool, int ldpool, bool* pool_fused, double* stat_slots, bool* stat_fused) {
-  IgemmDesc d;
-  memset(&d, 0, sizeof d);
-  d.tn = &c->tn;
-  d.in = (const float*)in_v;   // element type follows c->dtype; the descriptor carries raw pointers
-  d.w = L.wp;
-  d.wu = L.wu;
-  d.scale = scale;
-  d.shift = shift;
-  d.out = (float*)out_v;
-  d.M = B * H * W;
-  d.H = H;
-  d.W = W;
-  d.Cp = L.Cp;
-  d.ldin = ldin;
-  d.KS = L.KS;
-  d.K = L.K;
-  d.Kp = L.Kp;
-  d.N = L.N;
-  d.ldout = ldout;
-  d.coff = coff;
-  d.relu = relu;
-  d.out_mode = L.convt ? 1 : 0;
-  d.ct_cout = L.Cout;
-  d.Hout = Hout;
-  d.Wout = Wout;
+  IgemmDesc d = layer_desc(c, L, in_v, ldin, B, H, W, out_v, ldout, coff);
+  d.scale = scale, d.shift = shift, d.relu = relu, d.Hout = Hout, d.Wout = Wout;
   if (pool_fused) *pool_fused = false;
   if (stat_fused) *stat_fused = false;
   if (L.wfm && c->tn.first_mfma && ldin == L.Cp && first_mfma_applicable(c->dtype, L.Cin, L.Cp, L.Cout, ldout, coff, H, W)) {
@@ -544,57 +495,57 @@ int mgu_unet_forward(mgu_ctx* c, const void* x_dev, int B, int H, int W, int64_t
   }
 
   // odd sizes: F.pad (unet_decoder.py:46-47) leaves a zero row/column in the up-sampled half
-  for (int i = 0; i < depth; ++i)
+  for (const Block& b : c->enc) {
+    const int i = b.level;
     if (2 * hs[i + 1] != hs[i] || 2 * wsz[i + 1] != wsz[i])
-      HIPCHK(c, hipMemsetAsync(cat_dev[i], 0, (size_t)B * hs[i] * wsz[i] * 2 * ((size_t)c->feat << i) * es, s));
+      HIPCHK(c, hipMemsetAsync(cat_dev[i], 0, (size_t)B * hs[i] * wsz[i] * 2 * c->layers[b.conv2].Cout * es, s));
+  }
 
   // the first convolution on the matrix cores reads the caller's image itself (first_mfma.hip): no packed copy of the input
-  const Layer& L0 = c->layers[0];
+  const Layer& L0 = c->layers[c->enc[0].conv1];
   const bool first_direct = L0.wfm && c->tn.first_mfma && first_mfma_applicable(c->dtype, L0.Cin, L0.Cp, L0.Cout, c->feat, 0, H, W) &&
                             (int64_t)B * H * W < (1ll << 31);
   if (!first_direct) HIPCHK(c, launch_pack_input((const float*)x_dev, xin, c->dtype, B, c->in_ch, c->Cp0, H, W, xs_n, xs_c, xs_h, xs_w, s));
 
-  int li = 0;
   const void* cur = xin;
   int cur_ld = c->Cp0;
-  for (int i = 0; i < depth; ++i) {  // encoder, unet_encoder.py:67-70
-    const int C = c->feat << i;
-    if (i == 0 && first_direct) {
+  for (const Block& b : c->enc) {  // encoder, unet_encoder.py:67-70
+    const int i = b.level, C = c->layers[b.conv1].Cout;
+    if (&b == &c->enc.front() && first_direct) {
       if (c->fold_dirty) return fail(c, MGU_ERR_STATE, "internal: eval scale/shift not folded");
       const double alg = 2.0 * B * H * W * 9.0 * L0.Cin * L0.Cout;
       ProfScope ps(c, s, "conv3x3_first_mfma_kernel", alg, 2.0 * B * H * W * 32.0 * 32.0 * (c->dtype == MGU_DTYPE_F32 ? 6.0 : 3.0), 1);
       HIPCHK(c, launch_first_mfma_direct(c->dtype, (const float*)x_dev, xs_n, xs_c, xs_h, xs_w, c->in_ch, L0.wfm, L0.bn.empty() ? nullptr : L0.scale,
                                          L0.shift, tmp, B, H, W, C, 0, 1, s));
-      ++li;
-    } else if ((rc = run_conv(c, c->layers[li++], cur, cur_ld, B, hs[i], wsz[i], tmp, C, 0, 1, 0, 0, s))) return rc;
+    } else if ((rc = run_conv(c, c->layers[b.conv1], cur, cur_ld, B, hs[i], wsz[i], tmp, C, 0, 1, 0, 0, s))) return rc;
     void* pooled = ws + plan.pooled[i];
     bool fused = false;   // MaxPool2d(2) (unet_encoder.py:48) rides in the conv2 epilogue on the Winograd path
-    if ((rc = run_conv(c, c->layers[li++], tmp, C, B, hs[i], wsz[i], cat_dev[i], 2 * C, 0, 1, 0, 0, s, pooled, C, &fused))) return rc;
+    if ((rc = run_conv(c, c->layers[b.conv2], tmp, C, B, hs[i], wsz[i], cat_dev[i], 2 * C, 0, 1, 0, 0, s, pooled, C, &fused))) return rc;
     if (!fused) HIPCHK(c, launch_maxpool2(cat_dev[i], 2 * C, pooled, c->dtype, B, hs[i], wsz[i], C, s));
     cur = pooled;
     cur_ld = C;
   }
   {  // bottleneck, :72
-    const int C = c->feat << depth;
-    if ((rc = run_conv(c, c->layers[li++], cur, cur_ld, B, hs[depth], wsz[depth], tmp, C, 0, 1, 0, 0, s))) return rc;
-    if ((rc = run_conv(c, c->layers[li++], tmp, C, B, hs[depth], wsz[depth], bott, C, 0, 1, 0, 0, s))) return rc;
+    const Block& b = c->bott;
+    const int i = b.level, C = c->layers[b.conv1].Cout;
+    if ((rc = run_conv(c, c->layers[b.conv1], cur, cur_ld, B, hs[i], wsz[i], tmp, C, 0, 1, 0, 0, s))) return rc;
+    if ((rc = run_conv(c, c->layers[b.conv2], tmp, C, B, hs[i], wsz[i], bott, C, 0, 1, 0, 0, s))) return rc;
     cur = bott;
     cur_ld = C;
   }
-  for (int b = 0; b < depth; ++b) {  // decoder, unet_decoder.py:139-141
-    const int i = depth - 1 - b;
-    const int C = c->feat << i;
+  for (const Block& b : c->dec) {  // decoder, unet_decoder.py:139-141
+    const int i = b.level, C = c->layers[b.conv1].Cout;
     // ConvTranspose2d(k2,s2) -> pixel-shuffle store into channels [C, 2C) of the concat buffer (:36,:53)
-    if ((rc = run_conv(c, c->layers[li++], cur, cur_ld, B, hs[i + 1], wsz[i + 1], cat_dev[i], 2 * C, C, 0, hs[i], wsz[i], s)))
+    if ((rc = run_conv(c, c->layers[b.up], cur, cur_ld, B, hs[i + 1], wsz[i + 1], cat_dev[i], 2 * C, C, 0, hs[i], wsz[i], s)))
       return rc;
-    if ((rc = run_conv(c, c->layers[li++], cat_dev[i], 2 * C, B, hs[i], wsz[i], tmp, C, 0, 1, 0, 0, s))) return rc;
-    if ((rc = run_conv(c, c->layers[li++], tmp, C, B, hs[i], wsz[i], feat_dev[i], C, 0, 1, 0, 0, s))) return rc;
+    if ((rc = run_conv(c, c->layers[b.conv1], cat_dev[i], 2 * C, B, hs[i], wsz[i], tmp, C, 0, 1, 0, 0, s))) return rc;
+    if ((rc = run_conv(c, c->layers[b.conv2], tmp, C, B, hs[i], wsz[i], feat_dev[i], C, 0, 1, 0, 0, s))) return rc;
     cur = feat_dev[i];
     cur_ld = C;
   }
   // final 1x1 conv (:143): a few output channels -> HBM-bound head kernel reading the reference's (ncls, C) weight
+  const Layer& F = c->layers[c->head];
   {
-    const Layer& F = c->layers[li++];
     const int pm_dtype = c->dtype;   // decoder features are stored in the compute dtype
     if (c->pm_out && F.w_src && F.b_src && patch_mean_head_fusable(pm_dtype, F.Cin, c->ncls) && F.Cin <= 256) {
       // requested patch means + the 1x1 head in ONE pass over the decoder feature (both are pure bandwidth)
@@ -611,7 +562,7 @@ int mgu_unet_forward(mgu_ctx* c, const void* x_dev, int B, int H, int W, int64_t
     }
   }
   if (c->pm_out) {   // request not served by the fused pass (head shape): separate kernel, same result
-    HIPCHK(c, launch_patch_mean(cur, c->dtype, (float*)c->pm_out, B, H, W, c->layers.back().Cin, c->pm_patch, s));
+    HIPCHK(c, launch_patch_mean(cur, c->dtype, (float*)c->pm_out, B, H, W, F.Cin, c->pm_patch, s));
     c->pm_out = nullptr;
   }
   if (c->prof) HIPCHK(c, hipEventRecord(c->ev_total[1], s));
@@ -626,31 +577,43 @@ int mgu_unet_request_patch_mean(mgu_ctx* c, int patch, void* out_dev) {
     return MGU_OK;
   }
   if (patch < 1) return fail(c, MGU_ERR_INVALID, "bad patch_mean request");
-  const int C = c->layers.back().Cin, vec = c->dtype == MGU_DTYPE_BF16 ? 8 : 4;
+  const int C = c->layers[c->head].Cin, vec = c->dtype == MGU_DTYPE_BF16 ? 8 : 4;
   if ((C % vec) || C > 256) return fail(c, MGU_ERR_INVALID, "patch means need init_features %% %d == 0 and <= 256 (got %d)", vec, C);
   c->pm_patch = patch;
   c->pm_out = out_dev;
   return MGU_OK;
 }
 
-// scratch for the building-block entry points: packed panel + scale/shift, grown on demand
-static int block_scratch(mgu_ctx* c, int Np, int Kp, float** wp, float** scale, float** shift, hipStream_t s) {
-  const size_t need = ((size_t)Np * Kp + 2 * (size_t)Np) * sizeof(float);
-  int rc = ensure(c, &c->gws, &c->gws_bytes, need);
-  if (rc) return rc;
-  *wp = (float*)c->gws;
-  *scale = *wp + (size_t)Np * Kp;
-  *shift = *scale + Np;
-  HIPCHK(c, hipMemsetAsync(c->gws, 0, need, s));
-  return MGU_OK;
-}
-
 // Packed forms of one Conv2d weight (direct panel and, for fp32 3x3 layers with Cin % 16 == 0, the Winograd U), owned by the
 // library: built once by mgu_conv2d_prepare and reused by every mgu_conv2d_prepared_nhwc call until the weight changes.
 struct mgu_conv_weights {
-  int Cout = 0, Cin = 0, ksize = 0, K = 0, Kp = 0, Np = 0;
-  float *wp = nullptr, *wu = nullptr, *shift = nullptr;   // one allocation: [panel | bias-as-shift | U]
+  Layer L;   // shape; L.wp, L.shift, L.wu in one allocation: [panel | bias-as-shift | U]
 };
+
+// the building blocks' layers: an fp32 Conv2d / ConvTranspose2d(2, 2) on Cin % 4 == 0 channels
+static Layer block_layer(int Cin, int Cout, int ksize, bool convt) {
+  Layer L;
+  L.Cin = L.Cp = Cin, L.Cout = Cout, L.KS = ksize, L.convt = convt;
+  L.K = ksize * ksize * Cin, L.Kp = rup(L.K, 32), L.N = convt ? 4 * Cout : Cout, L.Np = rup(L.N, 128);
+  return L;
+}
+
+// the Conv2d launch of both building blocks on the packed forms of L (L.shift: room for the bias)
+static int conv2d_launch(mgu_ctx* c, const Layer& L, const void* in_dev, int B, int H, int W, const void* bias_dev, const void* scale_dev,
+                         const void* shift_dev, int relu, void* out_dev, int ld_out, int c_off, hipStream_t s) {
+  IgemmDesc d = layer_desc(c, L, in_dev, L.Cin, B, H, W, out_dev, ld_out, c_off);
+  d.relu = relu;
+  if (scale_dev && shift_dev) {  // y = scale*(conv) + shift, bias folded by the caller into shift
+    d.scale = (const float*)scale_dev;
+    d.shift = (const float*)shift_dev;
+  } else if (bias_dev) {
+    HIPCHK(c, launch_bias_tile((const float*)bias_dev, L.shift, L.Cout, 1, s));
+    d.shift = L.shift;
+  }
+  ProfScope ps(c, s);
+  HIPCHK(c, launch_igemm_f32(d, s));
+  return MGU_OK;
+}
 
 int mgu_conv2d_prepare(mgu_ctx* c, const void* w_dev, int Cout, int Cin, int ksize, mgu_conv_weights** out, void* hip_stream) {
   if (!c) return MGU_ERR_INVALID;
@@ -659,24 +622,24 @@ int mgu_conv2d_prepare(mgu_ctx* c, const void* w_dev, int Cout, int Cin, int ksi
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)hip_stream;
   mgu_conv_weights* p = new mgu_conv_weights();
-  p->Cout = Cout, p->Cin = Cin, p->ksize = ksize;
-  p->K = ksize * ksize * Cin, p->Kp = rup(p->K, 32), p->Np = rup(Cout, 128);
+  Layer& L = p->L;
+  L = block_layer(Cin, Cout, ksize, false);
   const bool wino = wino_layer(c->tn, ksize, Cin);
-  const size_t panel = (size_t)p->Np * p->Kp, total = panel + p->Np + (wino ? wino_u_floats(Cout, Cin) : 0);
-  hipError_t e = hipMalloc((void**)&p->wp, total * sizeof(float));
+  const size_t panel = (size_t)L.Np * L.Kp, total = panel + L.Np + (wino ? wino_u_floats(Cout, Cin) : 0);
+  hipError_t e = hipMalloc((void**)&L.wp, total * sizeof(float));
   if (e != hipSuccess) {
     delete p;
     return fail(c, MGU_ERR_NOMEM, "hipMalloc(%zu) failed: %s", total * sizeof(float), hipGetErrorString(e));
   }
-  p->shift = p->wp + panel;
-  e = hipMemsetAsync(p->wp, 0, (panel + p->Np) * sizeof(float), s);
-  if (e == hipSuccess) e = launch_pack_conv_w((const float*)w_dev, p->wp, 0, Cout, Cin, Cin, ksize, p->Kp, s);
+  L.shift = L.wp + panel;
+  e = hipMemsetAsync(L.wp, 0, (panel + L.Np) * sizeof(float), s);
+  if (e == hipSuccess) e = launch_pack_conv_w((const float*)w_dev, L.wp, 0, Cout, Cin, Cin, ksize, L.Kp, s);
   if (e == hipSuccess && wino) {
-    p->wu = p->shift + p->Np;
-    e = launch_pack_wino_w((const float*)w_dev, p->wu, Cout, Cin, Cin, 0, c->tn.wino_prec, s);
+    L.wu = L.shift + L.Np;
+    e = launch_pack_wino_w((const float*)w_dev, L.wu, Cout, Cin, Cin, 0, c->tn.wino_prec, s);
   }
   if (e != hipSuccess) {
-    (void)hipFree(p->wp);
+    (void)hipFree(L.wp);
     delete p;
     return fail(c, MGU_ERR_HIP, "conv2d_prepare: %s", hipGetErrorString(e));
   }
@@ -688,7 +651,7 @@ void mgu_conv2d_release(mgu_ctx* c, mgu_conv_weights* p) {
   if (!p) return;
   if (c) (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();   // launches that read the panels may still be in flight
-  if (p->wp) (void)hipFree(p->wp);
+  if (p->L.wp) (void)hipFree(p->L.wp);
   delete p;
 }
 
@@ -697,30 +660,14 @@ int mgu_conv2d_prepared_nhwc(mgu_ctx* c, const mgu_conv_weights* p, const void* 
                              void* hip_stream) {
   if (!c) return MGU_ERR_INVALID;
   if (!p || !in_dev || !out_dev || B < 1 || H < 1 || W < 1) return fail(c, MGU_ERR_INVALID, "bad conv2d args");
-  if (ld_out < c_off + p->Cout) return fail(c, MGU_ERR_INVALID, "ld_out %d < c_off %d + Cout %d", ld_out, c_off, p->Cout);
+  if (ld_out < c_off + p->L.Cout) return fail(c, MGU_ERR_INVALID, "ld_out %d < c_off %d + Cout %d", ld_out, c_off, p->L.Cout);
   if ((int64_t)B * H * W >= (1ll << 31)) return fail(c, MGU_ERR_INVALID, "B*H*W must be < 2^31");
   HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = (hipStream_t)hip_stream;
-  IgemmDesc d;
-  memset(&d, 0, sizeof d);
-  d.tn = &c->tn;
-  d.in = (const float*)in_dev, d.w = p->wp, d.wu = p->wu, d.out = (float*)out_dev;
-  d.M = B * H * W, d.H = H, d.W = W, d.Cp = p->Cin, d.ldin = p->Cin, d.KS = p->ksize, d.K = p->K, d.Kp = p->Kp;
-  d.N = p->Cout, d.ldout = ld_out, d.coff = c_off, d.relu = relu;
-  if (scale_dev && shift_dev) {  // y = scale*(conv) + shift, bias folded by the caller into shift
-    d.scale = (const float*)scale_dev;
-    d.shift = (const float*)shift_dev;
-  } else if (bias_dev) {
-    HIPCHK(c, launch_bias_tile((const float*)bias_dev, p->shift, p->Cout, 1, s));
-    d.shift = p->shift;
-  }
-  ProfScope ps(c, s);
-  HIPCHK(c, launch_igemm_f32(d, s));
-  return MGU_OK;
+  return conv2d_launch(c, p->L, in_dev, B, H, W, bias_dev, scale_dev, shift_dev, relu, out_dev, ld_out, c_off, (hipStream_t)hip_stream);
 }
 
-// One-shot form: packs the weight on EVERY call (parity tests, weights that change between calls); steady-state callers
-// use mgu_conv2d_prepare + mgu_conv2d_prepared_nhwc.
+// One-shot form: packs the weight on EVERY call (parity tests, weights that change between calls) into the context's scratch, then
+// the mgu_conv2d_prepared_nhwc launch; steady-state callers use mgu_conv2d_prepare + mgu_conv2d_prepared_nhwc.
 int mgu_conv2d_nhwc(mgu_ctx* c, const void* in_dev, int B, int H, int W, int Cin, const void* w_dev, const void* bias_dev,
                     const void* scale_dev, const void* shift_dev, int Cout, int ksize, int relu, void* out_dev,
                     int ld_out, int c_off, void* hip_stream) {
@@ -732,34 +679,20 @@ int mgu_conv2d_nhwc(mgu_ctx* c, const void* in_dev, int B, int H, int W, int Cin
   if ((int64_t)B * H * W >= (1ll << 31)) return fail(c, MGU_ERR_INVALID, "B*H*W must be < 2^31");
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)hip_stream;
-  Layer L;
-  L.Cin = L.Cp = Cin, L.Cout = Cout, L.KS = ksize;
-  L.K = ksize * ksize * Cin, L.Kp = rup(L.K, 32), L.N = Cout, L.Np = rup(Cout, 128);
-  float *sc, *sh;
-  int rc = block_scratch(c, L.Np, L.Kp, &L.wp, &sc, &sh, s);
+  Layer L = block_layer(Cin, Cout, ksize, false);
+  const size_t need = ((size_t)L.Np * L.Kp + 2 * (size_t)L.Np) * sizeof(float);   // panel + scale/shift
+  int rc = ensure(c, &c->gws, &c->gws_bytes, need);
   if (rc) return rc;
+  L.wp = (float*)c->gws;
+  L.shift = L.wp + (size_t)L.Np * L.Kp + L.Np;
+  HIPCHK(c, hipMemsetAsync(c->gws, 0, need, s));
   HIPCHK(c, launch_pack_conv_w((const float*)w_dev, L.wp, 0, Cout, Cin, Cin, ksize, L.Kp, s));
   if (wino_layer(c->tn, ksize, Cin)) {   // same routing as the model's layers: Winograd F(2x2,3x3)
     if ((rc = ensure(c, &c->wuws, &c->wuws_bytes, wino_u_floats(Cout, Cin) * sizeof(float)))) return rc;
     L.wu = (float*)c->wuws;
     HIPCHK(c, launch_pack_wino_w((const float*)w_dev, L.wu, Cout, Cin, Cin, 0, c->tn.wino_prec, s));
   }
-  IgemmDesc d;
-  memset(&d, 0, sizeof d);
-  d.tn = &c->tn;
-  d.in = (const float*)in_dev, d.w = L.wp, d.wu = L.wu, d.out = (float*)out_dev;
-  d.M = B * H * W, d.H = H, d.W = W, d.Cp = Cin, d.ldin = Cin, d.KS = ksize, d.K = L.K, d.Kp = L.Kp;
-  d.N = Cout, d.ldout = ld_out, d.coff = c_off, d.relu = relu;
-  if (scale_dev && shift_dev) {  // y = scale*(conv) + shift, bias folded by the caller into shift
-    d.scale = (const float*)scale_dev;
-    d.shift = (const float*)shift_dev;
-  } else if (bias_dev) {
-    HIPCHK(c, launch_bias_tile((const float*)bias_dev, sh, Cout, 1, s));
-    d.shift = sh;
-  }
-  ProfScope ps(c, s);
-  HIPCHK(c, launch_igemm_f32(d, s));
-  return MGU_OK;
+  return conv2d_launch(c, L, in_dev, B, H, W, bias_dev, scale_dev, shift_dev, relu, out_dev, ld_out, c_off, s);
 }
 
 int mgu_conv_transpose2x2_nhwc(mgu_ctx* c, const void* in_dev, int B, int H, int W, int Cin, const void* w_dev,
@@ -771,34 +704,28 @@ int mgu_conv_transpose2x2_nhwc(mgu_ctx* c, const void* in_dev, int B, int H, int
   if ((int64_t)B * H * W * 4 >= (1ll << 31)) return fail(c, MGU_ERR_INVALID, "4*B*H*W must be < 2^31");
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)hip_stream;
-  const int Kp = rup(Cin, 32), N = 4 * Cout, Np = rup(N, 128);
-  float *wp, *sc, *sh;
+  Layer U = block_layer(Cin, Cout, 1, true);
   // Two packed forms, each in a region of its own: the direct [4 Cout][Cin] panel the tile kernel reads (always built), and -- when
   // the layer shape is eligible and the context's switches allow it (MGU_NO_CONVT_FRAG, MGU_WINO_PREC) -- the fragment-order
   // three-piece weights of convt2x2_x3_kernel.  Which kernel runs is decided by pick_conv on the COMPLETE descriptor; a launch it
   // sends to the tile kernel finds a real panel in d.w.
   const bool x3_shape = convt_x3_layer(c->tn, Cin, Cout);
-  const size_t panel = (size_t)Np * Kp + 2 * (size_t)Np;
+  const size_t panel = (size_t)U.Np * U.Kp + 2 * (size_t)U.Np;   // panel + scale/shift
   int rc = ensure(c, &c->gws, &c->gws_bytes, (panel + (x3_shape ? convt_x3_floats(Cin, Cout) : 0)) * sizeof(float));
   if (rc) return rc;
-  wp = (float*)c->gws, sc = wp + (size_t)Np * Kp, sh = sc + Np;
-  (void)sc;
+  U.wp = (float*)c->gws;
+  U.shift = U.wp + (size_t)U.Np * U.Kp + U.Np;
+  U.wu = x3_shape ? U.wp + panel : nullptr;
   HIPCHK(c, hipMemsetAsync(c->gws, 0, panel * sizeof(float), s));
-  HIPCHK(c, launch_pack_convt_w((const float*)w_dev, wp, 0, Cin, Cout, Kp, s));
-  IgemmDesc d;
-  memset(&d, 0, sizeof d);
-  d.tn = &c->tn;
-  d.in = (const float*)in_dev, d.w = wp, d.out = (float*)out_dev;
-  d.M = B * H * W, d.H = H, d.W = W, d.Cp = Cin, d.ldin = Cin, d.KS = 1, d.K = Cin, d.Kp = Kp;
-  d.N = N, d.ldout = ld_out, d.coff = c_off, d.out_mode = 1, d.ct_cout = Cout, d.Hout = 2 * H, d.Wout = 2 * W;
+  HIPCHK(c, launch_pack_convt_w((const float*)w_dev, U.wp, 0, Cin, Cout, U.Kp, s));
+  IgemmDesc d = layer_desc(c, U, in_dev, Cin, B, H, W, out_dev, ld_out, c_off);
+  d.Hout = 2 * H, d.Wout = 2 * W;
   if (bias_dev) {
-    HIPCHK(c, launch_bias_tile((const float*)bias_dev, sh, Cout, 4, s));
-    d.shift = sh;
+    HIPCHK(c, launch_bias_tile((const float*)bias_dev, U.shift, Cout, 4, s));
+    d.shift = U.shift;
   }
-  float* wx = x3_shape ? wp + panel : nullptr;
-  d.wu = wx;
   const ConvKernel k = pick_conv(d, 0);
-  if (k == ConvKernel::ConvtX3) HIPCHK(c, launch_pack_convt_x3((const float*)w_dev, wx, Cin, Cout, s));
+  if (k == ConvKernel::ConvtX3) HIPCHK(c, launch_pack_convt_x3((const float*)w_dev, U.wu, Cin, Cout, s));
   ProfScope ps(c, s);
   HIPCHK(c, launch_conv(d, k, 0, s));
   return MGU_OK;
@@ -835,51 +762,23 @@ int mgu_patch_mean(mgu_ctx* c, const void* feat_dev, int feat_dtype, int B, int 
   return MGU_OK;
 }
 
-double mgu_unet_flops(mgu_ctx* c, int B, int H, int W) {
-  if (!c || !c->configured) return -1.0;
+// FLOPs of the network on a B x H x W input: every layer at its level.  mfma: what the matrix pipe issues, the Winograd layers'
+// 16 products per 2x2 tile instead of 36.  Every term is an integer far below 2^53: the sums are exact.
+static double net_flops(const mgu_ctx* c, int B, int H, int W, bool mfma) {
   std::vector<int> hs, wsz;
   level_dims(H, W, c->depth, hs, wsz);
   double fl = 0;
-  int li = 0;
-  for (int i = 0; i <= c->depth; ++i)
-    for (int j = 0; j < 2; ++j, ++li) {
-      const Layer& L = c->layers[li];
-      fl += 2.0 * hs[i] * wsz[i] * 9.0 * L.Cin * L.Cout;
-    }
-  for (int b = 0; b < c->depth; ++b) {
-    const int i = c->depth - 1 - b;
-    const Layer& U = c->layers[li++];
-    fl += 2.0 * hs[i + 1] * wsz[i + 1] * (double)U.Cin * U.Cout * 4.0;
-    for (int j = 0; j < 2; ++j, ++li) {
-      const Layer& L = c->layers[li];
-      fl += 2.0 * hs[i] * wsz[i] * 9.0 * L.Cin * L.Cout;
-    }
+  for (const Layer& L : c->layers) {
+    const int h = hs[L.level], w = wsz[L.level];
+    if (mfma && L.wino) fl += 2.0 * ((h + 1) / 2) * ((w + 1) / 2) * 16.0 * L.Cp * L.Cout;   // per 2x2 tile: 16 products
+    else fl += 2.0 * h * w * L.KS * L.KS * L.Cin * L.Cout * (L.convt ? 4.0 : 1.0);
   }
-  fl += 2.0 * H * W * (double)c->layers[li].Cin * c->ncls;
   return fl * B;
 }
 
-double mgu_unet_mfma_flops(mgu_ctx* c, int B, int H, int W) {
-  if (!c || !c->configured) return -1.0;
-  std::vector<int> hs, wsz;
-  level_dims(H, W, c->depth, hs, wsz);
-  auto conv = [&](const Layer& L, int h, int w) {
-    if (L.wino) return 2.0 * ((h + 1) / 2) * ((w + 1) / 2) * 16.0 * L.Cp * L.Cout;   // per 2x2 tile: 16 products
-    return 2.0 * h * w * 9.0 * L.Cin * L.Cout;
-  };
-  double fl = 0;
-  int li = 0;
-  for (int i = 0; i <= c->depth; ++i)
-    for (int j = 0; j < 2; ++j, ++li) fl += conv(c->layers[li], hs[i], wsz[i]);
-  for (int b = 0; b < c->depth; ++b) {
-    const int i = c->depth - 1 - b;
-    const Layer& U = c->layers[li++];
-    fl += 2.0 * hs[i + 1] * wsz[i + 1] * (double)U.Cin * U.Cout * 4.0;
-    for (int j = 0; j < 2; ++j, ++li) fl += conv(c->layers[li], hs[i], wsz[i]);
-  }
-  fl += 2.0 * H * W * (double)c->layers[li].Cin * c->ncls;
-  return fl * B;
-}
+double mgu_unet_flops(mgu_ctx* c, int B, int H, int W) { return c && c->configured ? net_flops(c, B, H, W, false) : -1.0; }
+
+double mgu_unet_mfma_flops(mgu_ctx* c, int B, int H, int W) { return c && c->configured ? net_flops(c, B, H, W, true) : -1.0; }
 
 int mgu_profile_enable(mgu_ctx* c, int on) {
   if (!c) return MGU_ERR_INVALID;

@@ -16,43 +16,37 @@ using namespace mgud;
 namespace {
 
 struct TPlan {
-  size_t xin = 0, bott = 0, ta = 0, tb = 0, tc = 0, dwp = 0, dwp_floats = 0, dgp = 0, dgp_floats = 0, wug = 0, sums = 0, total = 0;
+  size_t xin = 0, bott = 0, ta = 0, tb = 0, tc = 0, dwp = 0, dwp_floats = 0, dgp = 0, dgp_floats = 0, sums = 0, total = 0;
   std::vector<size_t> z, y1, pooled, dcat;
 };
 
 TPlan plan_train(const mgu_ctx* c, int B, int H, int W) {
-  const int d = c->depth;
   std::vector<int> hs, ws;
-  level_dims(H, W, d, hs, ws);
+  level_dims(H, W, c->depth, hs, ws);
+  // floats of a block's output (Cout channels) on level l
+  auto out = [&](const Block& b, int l) { return (size_t)B * hs[l] * ws[l] * c->layers[b.conv2].Cout; };
   TPlan p;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off += (bytes + 255) / 256 * 256;
-    return o;
-  };
-  auto fl = [&](size_t n) { return take(n * sizeof(float)); };
+  Carve k;
+  auto fl = [&](size_t n) { return k.take(n * sizeof(float)); };
   p.xin = fl((size_t)B * H * W * c->Cp0);
   p.z.assign(c->layers.size(), 0);
   p.y1.assign(c->layers.size(), 0);
-  auto blk = [&](int li, int lvl) {
-    const size_t M = (size_t)B * hs[lvl] * ws[lvl];
-    const size_t C = c->layers[li].Cout;
-    p.z[li] = fl(M * C);
-    p.y1[li] = fl(M * C);
-    p.z[li + 1] = fl(M * C);
+  auto blk = [&](const Block& b) {
+    p.z[b.conv1] = fl(out(b, b.level));
+    p.y1[b.conv1] = fl(out(b, b.level));
+    p.z[b.conv2] = fl(out(b, b.level));
   };
-  for (int i = 0; i < d; ++i) blk(2 * i, i);
-  blk(2 * d, d);
-  for (int b = 0; b < d; ++b) blk(2 * d + 2 + 3 * b + 1, d - 1 - b);
-  for (int i = 0; i < d; ++i) p.pooled.push_back(fl((size_t)B * hs[i + 1] * ws[i + 1] * ((size_t)c->feat << i)));
-  p.bott = fl((size_t)B * hs[d] * ws[d] * ((size_t)c->feat << d));
-  size_t tmax = 0;
-  for (int i = 0; i <= d; ++i) tmax = std::max(tmax, (size_t)B * hs[i] * ws[i] * ((size_t)c->feat << i));
+  for (const Block& b : c->enc) blk(b);
+  blk(c->bott);
+  for (const Block& b : c->dec) blk(b);
+  for (const Block& b : c->enc) p.pooled.push_back(fl(out(b, b.level + 1)));
+  p.bott = fl(out(c->bott, c->bott.level));
+  size_t tmax = out(c->bott, c->bott.level);
+  for (const Block& b : c->enc) tmax = std::max(tmax, out(b, b.level));
   p.ta = fl(tmax);
   p.tb = fl(tmax);
   p.tc = fl(tmax);
-  for (int i = 0; i < d; ++i) p.dcat.push_back(fl((size_t)B * hs[i] * ws[i] * 2 * ((size_t)c->feat << i)));
+  for (const Block& b : c->enc) p.dcat.push_back(fl(2 * out(b, b.level)));
   size_t pmax = (size_t)128 * 32;
   for (auto& L : c->layers) {
     pmax = std::max(pmax, (size_t)L.Np * L.Kp);                                              // wgrad panel (conv / convT)
@@ -64,12 +58,14 @@ TPlan plan_train(const mgu_ctx* c, int B, int H, int W) {
   p.dwp = fl(p.dwp_floats);
   p.dgp = fl(pmax);
   p.dgp_floats = pmax;
-  size_t umax = 0;   // Winograd-transformed dgrad weights (conv_dgrad)
+  // a Winograd data-gradient set the size of the largest L.wug: unused since every layer that takes that kernel keeps its own (the
+  // region stays so that the published workspace size does not change)
+  size_t umax = 0;
   for (const auto& L : c->layers)
-    if (L.wino && rup(L.Cout, 4) % 16 == 0) umax = std::max(umax, wino_u_floats(L.Cin, rup(L.Cout, 4)));
-  p.wug = fl(umax + 64);
-  p.sums = take(sizeof(double) * 2 * ((size_t)c->feat << d) + 64);
-  p.total = off;
+    if (L.wug) umax = std::max(umax, wino_u_floats(L.Cin, rup(L.Cout, 4)));
+  fl(umax + 64);
+  p.sums = k.take(sizeof(double) * 2 * (size_t)c->layers[c->bott.conv2].Cout + 64);
+  p.total = k.off;
   return p;
 }
 
@@ -113,76 +109,13 @@ int conv_bn_relu_train(mgu_ctx* c, Layer& L, const float* in, int ldin, int B, i
   return MGU_OK;
 }
 
-struct Bwd {
+struct Bwd : BwdScratch {
   mgu_ctx* c;
   hipStream_t s;
-  float *ta, *tb, *dwp, *dgp, *wug, *flat;
-  size_t dgp_floats = 0;
-  size_t dwp_floats;
-  double *sums, *red;
+  float *ta, *tb, *flat;
   int pend_rows = 0;   // rows of `red` holding the column sums of the last bn_relu_bwd (= the conv bias gradient), folded by the layer's
                        // gradient unpack launch (conv_wgrad)
 };
-
-// weight gradient of a conv layer into flat[off_w]: Z = dz (dense, pitch Cout), A = gather of the layer's input
-int conv_wgrad(Bwd& w, const Layer& L, const float* dz) {
-  mgu_ctx* c = w.c;
-  WgradDesc d;
-  memset(&d, 0, sizeof d);
-  d.tn = &c->tn;
-  d.z = dz, d.ldz = L.Cout, d.zoff = 0;
-  d.in = L.t_in, d.ldin = L.t_ldin, d.inoff = 0, d.Cp = L.Cp;
-  d.KS = L.KS;
-  d.M = L.t_B * L.t_H * L.t_W, d.H = L.t_H, d.W = L.t_W;
-  d.N = L.Cout, d.K = L.K, d.Kp = L.Kp;
-  d.dw = w.dwp;
-  d.dw_capacity = w.dwp_floats;
-  {
-    const double alg = 2.0 * d.M * (double)L.KS * L.KS * L.Cin * L.Cout;
-    const WgradKernel k = pick_wgrad(d);
-    const WgradCost cost = wgrad_cost(k, alg);
-    ProfScope ps(c, w.s, wgrad_kernel_name(k), alg, cost.mfma, cost.pipe);
-    HIPCHK(c, launch_wgrad_f32(d, w.s));
-  }
-  // ... and, in the same launch, the fold of the bias gradient's column sums that bn_relu_bwd left in the reduction slots
-  HIPCHK(c, launch_unpack_conv_grad(w.dwp, d.groups, (size_t)d.N * d.Kp, w.flat + L.off_w, L.Cout, L.Cin, L.Cp, L.KS, L.Kp, w.s, w.red,
-                                    w.pend_rows, L.Cout, w.flat + L.off_b));
-  w.pend_rows = 0;
-  return MGU_OK;
-}
-
-// data gradient of a conv layer: din = conv(dz, flipped/transposed W) -> out (pitch ldout)
-int conv_dgrad(Bwd& w, const Layer& L, const float* dz, float* out, int ldout) {
-  mgu_ctx* c = w.c;
-  const int Cop = rup(L.Cout, 4);
-  const int Kd = L.KS * L.KS * Cop, Kpd = rup(Kd, 32);
-  IgemmDesc d;
-  memset(&d, 0, sizeof d);
-  d.tn = &c->tn;
-  d.in = dz, d.w = w.dgp, d.out = out;
-  d.M = L.t_B * L.t_H * L.t_W, d.H = L.t_H, d.W = L.t_W;
-  d.Cp = Cop, d.ldin = L.Cout == Cop ? L.Cout : Cop, d.KS = L.KS, d.K = Kd, d.Kp = Kpd;
-  d.N = L.Cin, d.ldout = ldout;
-  if (L.wino && wino_dgrad_layer(c->tn, L.KS, Cop)) d.wu = L.wug ? L.wug : w.wug;   // same Winograd kernel, weights flipped + transposed
-  // only the weight form the chosen kernel reads is built: Winograd U (normally already packed with all the others by the last
-  // weight refresh, repack_weights) or the direct flipped/transposed panel
-  const ConvKernel k = pick_conv(d, 0);
-  if (conv_is_wino(k)) {
-    if (!(L.wug && L.wug_valid)) {
-      HIPCHK(c, launch_pack_wino_w(L.w_src, const_cast<float*>(d.wu), L.Cin, L.Cout, Cop, 1, c->tn.wino_prec, w.s));
-      if (L.wug) L.wug_valid = true;
-    }
-  } else {
-    HIPCHK(c, launch_pack_dgrad_w(L.w_src, w.dgp, L.Cout, L.Cin, Cop, L.KS, Kpd, w.s));
-  }
-  {
-    const double alg = 2.0 * d.M * (double)L.KS * L.KS * L.Cin * L.Cout;
-    const ConvCost cost = conv_cost(k, d);
-    ProfScope ps(c, w.s, conv_dgrad_name(k, d), alg, cost.mfma, cost.pipe);
-    HIPCHK(c, launch_conv(d, k, 0, w.s));
-  }
-  return MGU_OK;
-}
 
 // BN(train) + ReLU backward: dy (pitch lddy) -> dz (dense) ; fills dgamma, dbeta, conv bias grad
 int bn_relu_bwd(Bwd& w, const Layer& L, const float* dy, int lddy, float* dz) {
@@ -199,24 +132,103 @@ int bn_relu_bwd(Bwd& w, const Layer& L, const float* dy, int lddy, float* dz) {
 }
 
 // ConvBlock backward (unet_encoder.py:15-25 reversed).  dy has pitch lddy; dinput may be null.
-int block_backward(Bwd& w, const Layer& L1, const Layer& L2, const float* dy, int lddy, float* dinput, int ld_dinput) {
+int block_backward(Bwd& w, const Block& b, const float* dy, int lddy, float* dinput, int ld_dinput) {
+  mgu_ctx* c = w.c;
+  const Layer &L1 = c->layers[b.conv1], &L2 = c->layers[b.conv2];
   int rc;
   if ((rc = bn_relu_bwd(w, L2, dy, lddy, w.ta))) return rc;
-  if ((rc = conv_wgrad(w, L2, w.ta))) return rc;
-  if ((rc = conv_dgrad(w, L2, w.ta, w.tb, L2.Cin))) return rc;   // d(y1), dense pitch C
+  if ((rc = conv_wgrad(c, L2, w.ta, w.flat + L2.off_w, w, true, w.s, &w.pend_rows, w.flat + L2.off_b))) return rc;
+  if ((rc = conv_dgrad(c, L2, w.ta, w.tb, L2.Cin, w, true, w.s))) return rc;   // d(y1), dense pitch C
   if ((rc = bn_relu_bwd(w, L1, w.tb, L2.Cin, w.ta))) return rc;
-  if ((rc = conv_wgrad(w, L1, w.ta))) return rc;
-  if (dinput && (rc = conv_dgrad(w, L1, w.ta, dinput, ld_dinput))) return rc;
+  if ((rc = conv_wgrad(c, L1, w.ta, w.flat + L1.off_w, w, true, w.s, &w.pend_rows, w.flat + L1.off_b))) return rc;
+  if (dinput && (rc = conv_dgrad(c, L1, w.ta, dinput, ld_dinput, w, true, w.s))) return rc;
   return MGU_OK;
 }
 
 }  // namespace
 
+// weight gradient of a conv layer: Z = dz (dense, pitch rup(Cout, 4)), A = gather of the layer's input
+int mgud::conv_wgrad(mgu_ctx* c, const Layer& L, const float* dz, float* dw, const BwdScratch& w, bool record, hipStream_t s,
+                     int* fold_rows, float* dbias) {
+  const int N = rup(L.Cout, 4);
+  WgradDesc d = wgrad_desc(c, dz, N, L.t_in, L.t_ldin, 0, L.Cp, L.KS, L.t_B, L.t_H, L.t_W, 0, 0, N, w.dwp, w.dwp_floats);
+  {
+    const double alg = 2.0 * d.M * (double)L.KS * L.KS * L.Cin * L.Cout;
+    const WgradKernel k = pick_wgrad(d);
+    const WgradCost cost = wgrad_cost(k, alg);
+    ProfScope ps(record ? c : nullptr, s, wgrad_kernel_name(k), alg, cost.mfma, cost.pipe);
+    HIPCHK(c, launch_wgrad_f32(d, s));
+  }
+  if (!fold_rows) {
+    HIPCHK(c, launch_unpack_conv_grad(w.dwp, d.groups, (size_t)d.N * d.Kp, dw, L.Cout, L.Cin, L.Cp, L.KS, L.Kp, s));
+    return MGU_OK;
+  }
+  // ... and, in the same launch, the fold of the bias gradient's column sums that bn_relu_bwd left in the reduction slots
+  HIPCHK(c, launch_unpack_conv_grad(w.dwp, d.groups, (size_t)d.N * d.Kp, dw, L.Cout, L.Cin, L.Cp, L.KS, L.Kp, s, w.red, *fold_rows,
+                                    L.Cout, dbias));
+  *fold_rows = 0;
+  return MGU_OK;
+}
+
+// data gradient of a conv layer: din = conv(dz, flipped/transposed W) -> out (pitch ldout)
+int mgud::conv_dgrad(mgu_ctx* c, const Layer& L, const float* dz, float* out, int ldout, const BwdScratch& w, bool record, hipStream_t s) {
+  const int Cop = rup(L.Cout, 4);
+  IgemmDesc d = dgrad_desc(c, L, dz, Cop, L.wxg_valid ? L.wxg : w.dgp, out, ldout);
+  if (L.wug && wino_dgrad_layer(c->tn, L.KS, Cop)) d.wu = L.wug;   // same Winograd kernel, weights flipped + transposed
+  // only the weight form the chosen kernel reads is built -- Winograd U or the direct flipped/transposed panel -- unless the layer
+  // keeps a current one (normally packed with all the others by the last weight refresh, repack_weights)
+  const ConvKernel k = pick_conv(d, 0);
+  if (conv_is_wino(k)) {
+    if (!L.wug_valid) {
+      HIPCHK(c, launch_pack_wino_w(L.w_src, L.wug, L.Cin, L.Cout, Cop, 1, c->tn.wino_prec, s));
+      L.wug_valid = true;
+    }
+  } else if (!L.wxg_valid) {
+    if (w.clear) HIPCHK(c, hipMemsetAsync(w.dgp, 0, (size_t)rup(L.Cin, 128) * d.Kp * sizeof(float), s));   // panel rows are padded to 128
+    HIPCHK(c, launch_pack_dgrad_w(L.w_src, w.dgp, L.Cout, L.Cin, Cop, L.KS, d.Kp, s));
+  }
+  const double alg = 2.0 * d.M * (double)L.KS * L.KS * L.Cin * L.Cout;
+  const ConvCost cost = conv_cost(k, d);
+  ProfScope ps(record ? c : nullptr, s, conv_dgrad_name(k, d), alg, cost.mfma, cost.pipe);
+  HIPCHK(c, launch_conv(d, k, 0, s));
+  return MGU_OK;
+}
+
+// ConvTranspose2d(2, 2) data gradient: the 2x2 stride-2 gather of d(out) (channels at dout, pitch ld_d, on its Hout x Wout grid) -> out
+// (dense, pitch Cin).  The forward layer's three-piece kernel in its gather mode (convt_x3.hip) where the shapes allow, else the
+// generic tile kernel.
+int mgud::convt_dgrad(mgu_ctx* c, const Layer& U, const float* dout, int ld_d, int Hout, int Wout, float* out, const BwdScratch& w,
+                      bool record, hipStream_t s) {
+  IgemmDesc q = dgrad_desc(c, U, dout, ld_d, w.dgp, out, U.Cin, Hout, Wout);
+  if (U.wxg_valid || convt_x3_dgrad_floats(U.Cin, U.Cout) <= w.dgp_floats) q.wu = U.wxg_valid ? U.wxg : w.dgp;
+  const ConvKernel k = pick_conv(q, 0);
+  if (k != ConvKernel::ConvtX3Dgrad) {
+    if (w.clear) HIPCHK(c, hipMemsetAsync(w.dgp, 0, (size_t)rup(U.Cin, 128) * q.Kp * sizeof(float), s));
+    HIPCHK(c, launch_pack_convt_dgrad_w(U.w_src, w.dgp, U.Cin, U.Cout, q.Kp, s));
+  } else if (!U.wxg_valid) {
+    HIPCHK(c, launch_pack_convt_x3_dgrad(U.w_src, w.dgp, U.Cin, U.Cout, s));   // else: packed by the last weight refresh
+  }
+  const double alg = 2.0 * q.M * (double)q.K * U.Cin;
+  const ConvCost cost = conv_cost(k, q);
+  ProfScope ps(record ? c : nullptr, s, conv_dgrad_name(k, q), alg, cost.mfma, cost.pipe);
+  HIPCHK(c, launch_conv(q, k, 0, s));
+  return MGU_OK;
+}
+
+// ConvTranspose2d(2, 2) weight gradient: the roles swap -- Z = the layer's INPUT (M, Cin), A = the 2x2 stride-2 gather of d(out)
+// (channels [c_off, c_off + Cout) of a pixel with pitch ld_d, on its Hout x Wout grid)
+int mgud::convt_wgrad(mgu_ctx* c, const Layer& U, const float* dout, int ld_d, int c_off, int Hout, int Wout, float* dw,
+                      const BwdScratch& w, hipStream_t s) {
+  WgradDesc g = wgrad_desc(c, U.t_in, U.t_ldin, dout, ld_d, c_off, U.Cout, 2, U.t_B, U.t_H, U.t_W, Hout, Wout, U.Cin, w.dwp, w.dwp_floats);
+  HIPCHK(c, launch_wgrad_f32(g, s));
+  HIPCHK(c, launch_unpack_convt_grad(w.dwp, g.groups, (size_t)g.N * g.Kp, dw, U.Cin, U.Cout, g.Kp, s));
+  return MGU_OK;
+}
+
 size_t mgud::train_ws_bytes(const mgu_ctx* c, int B, int H, int W) { return plan_train(c, B, H, W).total; }
 
 int mgud::unet_forward_train(mgu_ctx* c, const float* x, int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w, int B,
                              int H, int W, float* logits, void* const* cat_dev, void* const* feat_dev, hipStream_t s) {
-  const int d = c->depth;
   for (auto& L : c->layers)
     if (!L.w_src || !L.b_src || (!L.bn.empty() && (!L.gamma || !L.run_mean)))
       return fail(c, MGU_ERR_STATE, "training needs the parameter tensors recorded by mgu_unet_load_weights");
@@ -227,55 +239,60 @@ int mgud::unet_forward_train(mgu_ctx* c, const float* x, int64_t xs_n, int64_t x
   int rc = ensure(c, &c->tws, &c->tws_bytes, p.total);
   if (rc) return rc;
   if ((rc = ensure_red(c))) return rc;
-  c->fold_dirty = true;   // this forward rewrites running_mean/var in place
   std::vector<int> hs, ws;
-  level_dims(H, W, d, hs, ws);
+  level_dims(H, W, c->depth, hs, ws);
   double* sums = (double*)((char*)c->tws + p.sums);
   double* red = (double*)c->redws;
-  for (int i = 0; i < d; ++i)
+  for (const Block& b : c->enc) {
+    const int i = b.level;
     if (2 * hs[i + 1] != hs[i] || 2 * ws[i + 1] != ws[i])
-      HIPCHK(c, hipMemsetAsync(cat_dev[i], 0, (size_t)B * hs[i] * ws[i] * 2 * ((size_t)c->feat << i) * sizeof(float), s));
+      HIPCHK(c, hipMemsetAsync(cat_dev[i], 0, (size_t)B * hs[i] * ws[i] * 2 * c->layers[b.conv2].Cout * sizeof(float), s));
+  }
   float* xin = at(c, p.xin);
   HIPCHK(c, launch_pack_input(x, xin, 0, B, c->in_ch, c->Cp0, H, W, xs_n, xs_c, xs_h, xs_w, s));
 
-  c->t_cat.assign(d, nullptr);
-  c->t_feat.assign(d, nullptr);
-  c->t_pooled.assign(d, nullptr);
+  // conv1 -> BN -> ReLU -> conv2 -> BN -> ReLU of block b on its level, output y with pitch ldy (and, fused where it can be, pooled)
+  auto block = [&](const Block& b, const float* in, int ldin, float* y, int ldy, float* pooled, bool* pooled_done) {
+    Layer &L1 = c->layers[b.conv1], &L2 = c->layers[b.conv2];
+    const int i = b.level, C = L1.Cout;
+    int r = conv_bn_relu_train(c, L1, in, ldin, B, hs[i], ws[i], at(c, p.z[b.conv1]), at(c, p.y1[b.conv1]), C, sums, red, s);
+    if (r) return r;
+    return conv_bn_relu_train(c, L2, at(c, p.y1[b.conv1]), C, B, hs[i], ws[i], at(c, p.z[b.conv2]), y, ldy, sums, red, s, pooled,
+                              pooled_done);
+  };
+  c->t_cat.assign(c->depth, nullptr);
+  c->t_feat.assign(c->depth, nullptr);
+  c->t_pooled.assign(c->depth, nullptr);
   const float* cur = xin;
   int ld = c->Cp0;
-  for (int i = 0; i < d; ++i) {  // encoder
-    const int C = c->feat << i, li = 2 * i;
+  for (const Block& b : c->enc) {  // encoder
+    const int i = b.level, C = c->layers[b.conv1].Cout;
     float* cat = (float*)cat_dev[i];
-    if ((rc = conv_bn_relu_train(c, c->layers[li], cur, ld, B, hs[i], ws[i], at(c, p.z[li]), at(c, p.y1[li]), C, sums, red, s))) return rc;
     float* pooled = at(c, p.pooled[i]);
     bool pooled_done = false;
-    if ((rc = conv_bn_relu_train(c, c->layers[li + 1], at(c, p.y1[li]), C, B, hs[i], ws[i], at(c, p.z[li + 1]), cat, 2 * C, sums, red, s, pooled,
-                                 &pooled_done)))
-      return rc;
+    if ((rc = block(b, cur, ld, cat, 2 * C, pooled, &pooled_done))) return rc;
     if (!pooled_done) HIPCHK(c, launch_maxpool2(cat, 2 * C, pooled, 0, B, hs[i], ws[i], C, s));
     c->t_cat[i] = cat, c->t_pooled[i] = pooled;
     cur = pooled, ld = C;
   }
   {  // bottleneck
-    const int C = c->feat << d, li = 2 * d;
     float* bott = at(c, p.bott);
-    if ((rc = conv_bn_relu_train(c, c->layers[li], cur, ld, B, hs[d], ws[d], at(c, p.z[li]), at(c, p.y1[li]), C, sums, red, s))) return rc;
-    if ((rc = conv_bn_relu_train(c, c->layers[li + 1], at(c, p.y1[li]), C, B, hs[d], ws[d], at(c, p.z[li + 1]), bott, C, sums, red, s))) return rc;
+    const int C = c->layers[c->bott.conv1].Cout;
+    if ((rc = block(c->bott, cur, ld, bott, C, nullptr, nullptr))) return rc;
     cur = bott, ld = C;
   }
-  for (int b = 0; b < d; ++b) {  // decoder
-    const int i = d - 1 - b, C = c->feat << i, lu = 2 * d + 2 + 3 * b;
+  for (const Block& b : c->dec) {  // decoder
+    const int i = b.level, C = c->layers[b.conv1].Cout;
     float* cat = (float*)cat_dev[i];
     float* feat = (float*)feat_dev[i];
-    Layer& U = c->layers[lu];
+    Layer& U = c->layers[b.up];
     if ((rc = run_layer(c, U, cur, ld, B, hs[i + 1], ws[i + 1], cat, 2 * C, C, 0, nullptr, U.shift, hs[i], ws[i], s))) return rc;
     U.t_in = cur, U.t_ldin = ld, U.t_B = B, U.t_H = hs[i + 1], U.t_W = ws[i + 1];
-    if ((rc = conv_bn_relu_train(c, c->layers[lu + 1], cat, 2 * C, B, hs[i], ws[i], at(c, p.z[lu + 1]), at(c, p.y1[lu + 1]), C, sums, red, s))) return rc;
-    if ((rc = conv_bn_relu_train(c, c->layers[lu + 2], at(c, p.y1[lu + 1]), C, B, hs[i], ws[i], at(c, p.z[lu + 2]), feat, C, sums, red, s))) return rc;
+    if ((rc = block(b, cat, 2 * C, feat, C, nullptr, nullptr))) return rc;
     c->t_feat[i] = feat;
     cur = feat, ld = C;
   }
-  Layer& F = c->layers.back();
+  Layer& F = c->layers[c->head];
   if (c->ncls <= 4) {
     HIPCHK(c, launch_conv1x1_head(cur, 0, ld, F.Cin, F.w_src, F.b_src, logits, c->ncls, c->ncls, (int64_t)B * H * W, s));
   } else if ((rc = run_layer(c, F, cur, ld, B, H, W, logits, c->ncls, 0, 0, nullptr, F.shift, 0, 0, s))) {
@@ -310,12 +327,8 @@ int mgu_cross_entropy(mgu_ctx* c, const void* logits_dev, const int64_t* labels_
   if (rc) return rc;
   hipStream_t s = (hipStream_t)hip_stream;
   if ((rc = ensure(c, &c->gws, &c->gws_bytes, 256))) return rc;
-  if (!c->err_word) {
-    HIPCHK(c, hipHostMalloc((void**)&c->err_word, sizeof(int), hipHostMallocMapped));
-    *c->err_word = 0;
-  }
   int* err_dev = nullptr;
-  HIPCHK(c, hipHostGetDevicePointer((void**)&err_dev, c->err_word, 0));
+  if ((rc = err_word_dev(c, &err_dev))) return rc;
   HIPCHK(c, launch_ce((const float*)logits_dev, labels_dev, npix, num_classes, -100 /* nn.CrossEntropyLoss default */, grad_scale,
                       (float*)dlogits_dev, rup(num_classes, 4), (double*)c->gws, err_dev, loss_dev, s));
   return MGU_OK;
@@ -344,17 +357,16 @@ static int backward_body(mgu_ctx* c, const void* dlogits_dev, void* flat_grad_de
     if (prc) return prc;
   }
   hipStream_t s = (hipStream_t)hip_stream;
-  const int d = c->depth, B = c->tB, H = c->tH, W = c->tW;
+  const int B = c->tB, H = c->tH, W = c->tW;
   const TPlan p = plan_train(c, B, H, W);
   if (p.total > c->tws_bytes) return fail(c, MGU_ERR_STATE, "training workspace changed since the forward");
   std::vector<int> hs, ws;
-  level_dims(H, W, d, hs, ws);
+  level_dims(H, W, c->depth, hs, ws);
   Bwd w;
   w.c = c, w.s = s;
   w.ta = at(c, p.ta), w.tb = at(c, p.tb), w.dwp = at(c, p.dwp), w.dgp = at(c, p.dgp);
   w.dgp_floats = p.dgp_floats;
   w.dwp_floats = p.dwp_floats;
-  w.wug = at(c, p.wug);
   w.flat = (float*)flat_grad_dev;
   w.sums = (double*)((char*)c->tws + p.sums);
   w.red = (double*)c->redws;
@@ -370,91 +382,50 @@ static int backward_body(mgu_ctx* c, const void* dlogits_dev, void* flat_grad_de
   };
 
   // ---- final 1x1 conv (unet_decoder.py:143) ------------------------------------------------------
-  const Layer& F = c->layers.back();
-  const int64_t M0 = (int64_t)B * H * W;
-  const int ldd = rup(c->ncls, 4), C0 = F.Cin;
+  const Layer& F = c->layers[c->head];
+  const int ldd = rup(c->ncls, 4);
   const float* dlog = (const float*)dlogits_dev;
-  HIPCHK(c, launch_colsum(dlog, ldd, M0, ldd, w.red, (float*)w.sums, s));   // padded to ldd columns, then trimmed
+  HIPCHK(c, launch_colsum(dlog, ldd, (int64_t)B * H * W, ldd, w.red, (float*)w.sums, s));   // padded to ldd columns, then trimmed
   HIPCHK(c, hipMemcpyAsync(w.flat + F.off_b, w.sums, sizeof(float) * c->ncls, hipMemcpyDeviceToDevice, s));
-  {
-    WgradDesc g;
-    memset(&g, 0, sizeof g);
-    g.tn = &c->tn;
-    g.z = dlog, g.ldz = ldd, g.in = F.t_in, g.ldin = F.t_ldin, g.Cp = C0, g.KS = 1;
-    g.M = (int)M0, g.H = H, g.W = W, g.N = ldd, g.K = C0, g.Kp = F.Kp, g.dw = w.dwp, g.dw_capacity = w.dwp_floats;
-    HIPCHK(c, launch_wgrad_f32(g, s));
-    HIPCHK(c, launch_unpack_conv_grad(w.dwp, g.groups, (size_t)g.N * g.Kp, w.flat + F.off_w, c->ncls, C0, C0, 1, F.Kp, s));
-    const int Kpd = rup(ldd, 32);
-    // the panel of the data gradient: normally already packed with every other weight form by the last refresh (repack_weights)
-    const float* dpanel = F.wxg_valid ? F.wxg : w.dgp;
-    if (!F.wxg_valid) HIPCHK(c, launch_pack_dgrad_w(F.w_src, w.dgp, c->ncls, C0, ldd, 1, Kpd, s));
-    IgemmDesc q;
-    memset(&q, 0, sizeof q);
-    q.tn = &c->tn;
-    q.in = dlog, q.w = dpanel, q.out = tc, q.M = (int)M0, q.H = H, q.W = W, q.Cp = ldd, q.ldin = ldd, q.KS = 1, q.K = ldd,
-    q.Kp = Kpd, q.N = C0, q.ldout = C0;
-    HIPCHK(c, launch_igemm_f32(q, s));
-  }
+  if ((rc = conv_wgrad(c, F, dlog, w.flat + F.off_w, w, false, s))) return rc;
+  // the panel of the data gradient: normally already packed with every other weight form by the last refresh (repack_weights)
+  if ((rc = conv_dgrad(c, F, dlog, tc, F.Cin, w, false, s))) return rc;
   const float* dy = tc;
-  int lddy = C0;
+  int lddy = F.Cin;
   if ((rc = block_done(F.off_w, false))) return rc;
 
   // ---- decoder blocks, shallow -> deep (reverse of unet_decoder.py:139-141) ------------------------
-  for (int b = d - 1; b >= 0; --b) {
-    const int i = d - 1 - b, C = c->feat << i, lu = 2 * d + 2 + 3 * b;
-    const Layer& U = c->layers[lu];
+  for (auto b = c->dec.rbegin(); b != c->dec.rend(); ++b) {
+    const int i = b->level, C = c->layers[b->conv1].Cout;
+    const Layer& U = c->layers[b->up];
     float* dcat = at(c, p.dcat[i]);
-    if ((rc = block_backward(w, c->layers[lu + 1], c->layers[lu + 2], dy, lddy, dcat, 2 * C))) return rc;
+    if ((rc = block_backward(w, *b, dy, lddy, dcat, 2 * C))) return rc;
     // ConvTranspose2d backward (unet_decoder.py:36): d(up) = channels [C, 2C) of d(cat)
     const int64_t Mi = (int64_t)B * hs[i] * ws[i];
     if (2 * hs[i + 1] != hs[i] || 2 * ws[i + 1] != ws[i])  // F.pad backward (unet_decoder.py:46-47) drops the pad row/col
       HIPCHK(c, launch_zero_pad_region(dcat, 2 * C, C, C, B, hs[i], ws[i], 2 * hs[i + 1], 2 * ws[i + 1], s));
     HIPCHK(c, launch_colsum(dcat + C, 2 * C, Mi, C, w.red, w.flat + U.off_b, s));
-    const int Kt = 4 * C, Kpt = rup(Kt, 32);
-    {
-      WgradDesc g;
-      memset(&g, 0, sizeof g);
-    g.tn = &c->tn;
-      g.z = U.t_in, g.ldz = U.t_ldin, g.in = dcat, g.ldin = 2 * C, g.inoff = C, g.Cp = C, g.KS = 2;
-      g.M = U.t_B * U.t_H * U.t_W, g.H = U.t_H, g.W = U.t_W, g.Hs = hs[i], g.Ws = ws[i];
-      g.N = U.Cin, g.K = Kt, g.Kp = Kpt, g.dw = w.dwp, g.dw_capacity = w.dwp_floats;
-      HIPCHK(c, launch_wgrad_f32(g, s));
-      HIPCHK(c, launch_unpack_convt_grad(w.dwp, g.groups, (size_t)g.N * g.Kp, w.flat + U.off_w, U.Cin, C, Kpt, s));
-    }
-    IgemmDesc q;
-    memset(&q, 0, sizeof q);
-    q.tn = &c->tn;
-    q.in = dcat + C, q.w = w.dgp, q.out = tc, q.M = U.t_B * U.t_H * U.t_W, q.H = U.t_H, q.W = U.t_W, q.Cp = C, q.ldin = 2 * C;
-    q.KS = 2, q.K = Kt, q.Kp = Kpt, q.N = U.Cin, q.ldout = U.Cin, q.Hout = hs[i], q.Wout = ws[i];
-    // three-piece kernel of the forward layer in its gather mode (convt_x3.hip) where the shapes allow, else the generic tile kernel
-    if (U.wxg_valid || convt_x3_dgrad_floats(U.Cin, C) <= w.dgp_floats) q.wu = U.wxg_valid ? U.wxg : w.dgp;
-    const ConvKernel k = pick_conv(q, 0);
-    if (k != ConvKernel::ConvtX3Dgrad) HIPCHK(c, launch_pack_convt_dgrad_w(U.w_src, w.dgp, U.Cin, C, Kpt, s));
-    else if (!U.wxg_valid) HIPCHK(c, launch_pack_convt_x3_dgrad(U.w_src, w.dgp, U.Cin, C, s));   // else: packed by the last weight refresh
-    {
-      const double alg = 2.0 * q.M * (double)Kt * U.Cin;
-      const ConvCost cost = conv_cost(k, q);
-      ProfScope ps(c, s, conv_dgrad_name(k, q), alg, cost.mfma, cost.pipe);
-      HIPCHK(c, launch_conv(q, k, 0, s));
-    }
+    if ((rc = convt_wgrad(c, U, dcat, 2 * C, C, hs[i], ws[i], w.flat + U.off_w, w, s))) return rc;
+    if ((rc = convt_dgrad(c, U, dcat + C, 2 * C, hs[i], ws[i], tc, w, true, s))) return rc;
     dy = tc, lddy = U.Cin;
     if ((rc = block_done(U.off_w, false))) return rc;
   }
   // ---- bottleneck -----------------------------------------------------------------------------------
   {
-    const Layer& L1 = c->layers[2 * d];
-    if ((rc = block_backward(w, L1, c->layers[2 * d + 1], dy, lddy, tc, L1.Cin))) return rc;
+    const Layer& L1 = c->layers[c->bott.conv1];
+    if ((rc = block_backward(w, c->bott, dy, lddy, tc, L1.Cin))) return rc;
     if ((rc = block_done(L1.off_w, false))) return rc;
   }
   // ---- encoder blocks, deep -> shallow -----------------------------------------------------------------
-  for (int i = d - 1; i >= 0; --i) {
-    const int C = c->feat << i;
+  for (auto b = c->enc.rbegin(); b != c->enc.rend(); ++b) {
+    const int i = b->level, C = c->layers[b->conv1].Cout;
+    const bool first = b + 1 == c->enc.rend();
     float* dcat = at(c, p.dcat[i]);
     // d(skip) = d(cat)[:, :C] (decoder path) + MaxPool backward of d(pooled)
     HIPCHK(c, launch_maxpool2_bwd_add(c->t_cat[i], 2 * C, tc, dcat, 2 * C, B, hs[i], ws[i], C, s));
-    const Layer& L1 = c->layers[2 * i];
-    if ((rc = block_backward(w, L1, c->layers[2 * i + 1], dcat, 2 * C, i > 0 ? tc : nullptr, L1.Cin))) return rc;
-    if ((rc = block_done(L1.off_w, i == 0))) return rc;
+    const Layer& L1 = c->layers[b->conv1];
+    if ((rc = block_backward(w, *b, dcat, 2 * C, first ? nullptr : tc, L1.Cin))) return rc;
+    if ((rc = block_done(L1.off_w, first))) return rc;
   }
   if (exchange && (rc = comm_join(c, s))) return rc;   // the caller's stream continues after the last bucket
   return MGU_OK;

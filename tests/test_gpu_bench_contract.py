@@ -222,3 +222,29 @@ def test_profiled_kernel_families(cuda, monkeypatch, case):
     for k, v in env.items():
         monkeypatch.setenv(k, v)   # read when the model's context is created
     assert profiled_families(cuda, dtype, dtype == "f32") == want
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_profiled_forward_flops_add_up_to_the_layer_walk(cuda, monkeypatch, dtype):
+    """The profile records of one eval forward add up to mgu_unet_flops exactly: the launches and the layer walk that counts them
+    cannot drift apart (every term is an integer far below 2^53, so the double sums are exact)."""
+    import torch
+    import mgunet
+    import mgunet_oracle as O
+    from mgunet import _lib
+    for k in ("MGU_WINO_ASM", "MGU_WINO_PREC", "MGU_NO_WINOGRAD", "MGU_NO_WINO_DGRAD", "MGU_NO_CONVT_FRAG"):
+        monkeypatch.delenv(k, raising=False)
+    x = torch.randn(1, 3, 64, 256, generator=torch.Generator().manual_seed(7)).to(cuda)
+    m = mgunet.UNet(3, 2, 32, 4, compute_dtype=torch.bfloat16 if dtype == "bf16" else torch.float32)
+    m.load_state_dict(O.make_unet_params(3, 2, 32, 4, seed=3))
+    m = m.to(cuda).eval()
+    ctx, L = m._context(cuda), _lib.lib()
+    with torch.no_grad():
+        m(x)
+        torch.cuda.synchronize(cuda)
+        L.mgu_profile_enable(ctx.handle, 1)
+        m(x)
+        torch.cuda.synchronize(cuda)
+    ks = _lib.read_kernel_stats(ctx)
+    L.mgu_profile_enable(ctx.handle, 0)
+    assert sum(k["flops_alg"] for k in ks) == L.mgu_unet_flops(ctx.handle, 1, 64, 256)
