@@ -99,10 +99,8 @@ struct mgu_ctx {
   size_t arena_floats = 0;
   void* ws = nullptr;   // eval scratch
   size_t ws_bytes = 0;
-  void* gbws = nullptr;     // GAT backward scratch (gat_bwd.hip)
+  void* gbws = nullptr;     // GAT train forward / backward scratch (gat_bwd.hip)
   size_t gbws_bytes = 0;
-  void* gbpanel = nullptr;  // GAT backward: the linear layer's packed panel
-  size_t gbpanel_bytes = 0;
   void* gws = nullptr;  // GAT / building-block scratch
   size_t gws_bytes = 0;
   void* tws = nullptr;  // training scratch (saved activations + backward temporaries)
@@ -291,10 +289,22 @@ int run_layer(mgu_ctx* c, const Layer& L, const void* in, int ldin, int B, int H
               void* pool = nullptr, int ldpool = 0, bool* pool_fused = nullptr,   // optional fused MaxPool2d(2) output
               double* stat_slots = nullptr, bool* stat_fused = nullptr);          // optional fused BatchNorm batch statistics
 
-void gat_destroy(mgu_ctx* c);   // gat_api.hip
-int gmax_buffer(mgu_ctx* c, int need, unsigned long long** buf, unsigned* gen);
-int gat_linear_st(mgu_ctx* c, const float* X, int N, int Fin, const float* W, const float* a, int heads, int Fh, float* wh, float* st,
-                  hipStream_t s);
+// GAT layer host code (gat_api.hip)
+void gat_destroy(mgu_ctx* c);
+// Fin, Fout_head (multiples of 4) and heads of a call to `fn`.  The eval schedules take 1..32 heads and heads * Fout_head <= 1024;
+// the train forward and the backward (train) any number of heads, heads * Fout_head <= 256 and N * heads * Fout_head < 2^31.
+int gat_check_layer(mgu_ctx* c, const char* fn, int Fin, int heads, int Fh, bool train = false, int N = 0);
+// the graphs of a layer call (no graph_ptr or num_graphs < 1: one graph, graph_ptr NULL) and their per-(graph, head) max accumulators
+int gmax_buffer(mgu_ctx* c, const int32_t** graph_ptr, int* num_graphs, int heads, unsigned long long** buf, unsigned* gen);
+// the gather schedule's GEMM panel [W | W^T a_src | W^T a_tgt] (rup(HF + 2H, 128) rows of rup(Fin, 32)); `clear` zeroes its padding
+size_t gat_panel_floats(int heads, int Fh, int Fin);
+int gat_pack_panel(mgu_ctx* c, const float* W, const float* a, float* panel, int heads, int Fh, int Fin, bool clear, hipStream_t s);
+// (gat_bwd.hip) The gather schedule's prologue: Wh (N, HF) and the attention scalars st (N, 2H) = [s | t] from ONE GEMM on `panel`,
+// the node -> graph table (G > 1), the per-graph max into the accumulators (gmax, gen) and, when gm != NULL, the max decoded into
+// a plain (G, H) float table.  `record` adds the eval forward's profiling records.
+int gat_prologue(mgu_ctx* c, const float* X, int N, int Fin, const float* panel, int heads, int Fh, const int32_t* rowptr, const int32_t* col,
+                 int64_t E, const int32_t* gp, int G, float alpha, unsigned long long* gmax, unsigned gen, float* wh, float* st,
+                 int32_t* node_graph, float* gm, bool record, hipStream_t s);
 
 // gradient exchange (comm.hip)
 int comm_bucket(mgu_ctx* c, float* flat, int64_t lo, int64_t hi, hipStream_t s);

@@ -340,12 +340,61 @@ __global__ __launch_bounds__(256) void gatb_da_final_kernel(const float* __restr
 using namespace mgu;
 using namespace mgud;
 
-extern "C" {
+// (ctx.h) here beside gatb_gmax_decode_kernel, the step the train forward and the backward add
+int mgud::gat_prologue(mgu_ctx* c, const float* X, int N, int Fin, const float* panel, int heads, int Fh, const int32_t* rowptr,
+                       const int32_t* col, int64_t E, const int32_t* gp, int G, float alpha, unsigned long long* gmax, unsigned gen, float* wh,
+                       float* st, int32_t* node_graph, float* gm, bool record, hipStream_t s) {
+  const int HF = heads * Fh;
+  {
+    ProfScope ps(record ? c : nullptr, s, "igemm_kernel (GAT linear)");
+    HIPCHK(c, launch_igemm_f32(gemm_desc(c, X, N, Fin, panel, rup(Fin, 32), HF + 2 * heads, wh, HF, HF, st, 2 * heads), s));
+  }
+  if (G > 1) HIPCHK(c, launch_gat_node_graph(gp, G, 0, N, node_graph, s));
+  if (E > 0 || !gm) {   // no edges, no scores: the decoded max needs no launch (the eval forward keeps its launch and record)
+    ProfScope ps(record ? c : nullptr, s, "gat_edge_max_kernel");
+    HIPCHK(c, launch_gat_edge_max(st, rowptr, col, node_graph, N, heads, alpha, gmax, c->gmax_cap, gen, s));
+  }
+  if (gm) hipLaunchKernelGGL(gatb_gmax_decode_kernel, dim3((G * heads + 63) / 64), dim3(64), 0, s, gmax, G * heads, gen, gm);
+  return MGU_OK;
+}
 
-int mgu_conv2d_dgrad_nhwc(mgu_ctx* c, const void* dz_dev, const void* w_oihw_dev, int B, int H, int W, int Cin, int Cout, int ksize,
-                          void* din_dev, int ld_out, void* hip_stream);
-int mgu_conv2d_wgrad_nhwc(mgu_ctx* c, const void* in_dev, int ld_in, const void* dz_dev, int B, int H, int W, int Cin, int Cout,
-                          int ksize, void* dw_oihw_dev, void* hip_stream);
+namespace {
+
+// Scratch of the train forward and the backward: one layout in c->gbws (not c->gws, which the backward's closing GEMMs carve).
+// The forward uses the regions up to gm.
+struct TrainWs {
+  float *panel, *wh, *st, *gm, *ghp, *al, *gz, *gt, *gs, *gmr, *gwh, *part;
+  int32_t* node_graph;   // node -> graph id (NULL: one graph)
+  int nb;                // row blocks of the da column reduction
+};
+
+// Carves c->gbws, packs the linear layer's panel and recomputes Wh, s, t and the per-graph max from the CURRENT weights, exactly as
+// the eval forward's gather schedule computes them (no profiling records).  *gp, *G come back normalised (gmax_buffer).
+int train_prologue(mgu_ctx* c, const float* X, int N, int Fin, const int32_t* rowptr, const int32_t* col, int64_t E, const int32_t** gp, int* G,
+                   const float* W, const float* a, int heads, int Fh, float alpha, TrainWs* w, hipStream_t s) {
+  unsigned long long* gmax;
+  unsigned gen;
+  int rc = gmax_buffer(c, gp, G, heads, &gmax, &gen);
+  if (rc) return rc;
+  const size_t NHF = (size_t)N * heads * Fh * 4, NH = (size_t)N * heads * 4, EH = (size_t)std::max<int64_t>(E, 1) * heads * 4;
+  w->nb = std::max(1, std::min(256, (N + 255) / 256));
+  Carve cv;
+  const size_t o_panel = cv.take(gat_panel_floats(heads, Fh, Fin) * 4), o_wh = cv.take(NHF), o_st = cv.take(2 * NH), o_ng = cv.take((size_t)N * 4),
+               o_gm = cv.take((size_t)*G * heads * 4), o_ghp = cv.take(NHF), o_al = cv.take(EH), o_gz = cv.take(EH), o_gt = cv.take(NH),
+               o_gs = cv.take(NH), o_gmr = cv.take(NH), o_gwh = cv.take(NHF), o_part = cv.take((size_t)w->nb * 2 * heads * Fh * 4);
+  if ((rc = ensure(c, &c->gbws, &c->gbws_bytes, cv.off))) return rc;
+  char* g = (char*)c->gbws;
+  auto at = [g](size_t o) { return (float*)(g + o); };
+  w->panel = at(o_panel), w->wh = at(o_wh), w->st = at(o_st), w->gm = at(o_gm), w->ghp = at(o_ghp), w->al = at(o_al), w->gz = at(o_gz);
+  w->gt = at(o_gt), w->gs = at(o_gs), w->gmr = at(o_gmr), w->gwh = at(o_gwh), w->part = at(o_part);
+  w->node_graph = *G > 1 ? (int32_t*)(g + o_ng) : nullptr;
+  if ((rc = gat_pack_panel(c, W, a, w->panel, heads, Fh, Fin, true, s))) return rc;
+  return gat_prologue(c, X, N, Fin, w->panel, heads, Fh, rowptr, col, E, *gp, *G, alpha, gmax, gen, w->wh, w->st, w->node_graph, w->gm, false, s);
+}
+
+}  // namespace
+
+extern "C" {
 
 int mgu_csr_transpose_device(mgu_ctx* c, const int32_t* rowptr_dev, const int32_t* col_dev, int64_t E, int num_nodes,
                              int32_t* rowptr_src_dev, int32_t* eid_src_dev, int32_t* tgt_of_edge_dev, void* hip_stream) {
@@ -383,64 +432,37 @@ static int gat_backward_impl(mgu_ctx* c, const void* X_dev, int N, int Fin, cons
                              void* dW_dev, void* da_dev, void* hip_stream) {
   if (!c) return MGU_ERR_INVALID;
   const int Fh = Fout_head, HF = heads * Fh;
-  if (!X_dev || !rowptr_dev || !W_dev || !a_dev || !dout_dev || !dW_dev || !da_dev || N < 1 || Fin < 4 || (Fin & 3) || heads < 1 || Fh < 4 ||
-      (Fh & 3) || E < 0 || (E > 0 && (!col_dev || !rowptr_src_dev || !eid_src_dev || !tgt_of_edge_dev)))
-    return fail(c, MGU_ERR_INVALID, "bad gat_layer_backward args (Fin, Fout_head multiples of 4)");
-  if (HF > 256) return fail(c, MGU_ERR_INVALID, "gat_layer_backward supports heads * Fout_head <= 256 (got %d x %d)", heads, Fh);
-  if ((int64_t)N * HF >= (1ll << 31)) return fail(c, MGU_ERR_INVALID, "N * heads * Fout_head must be < 2^31");
-  if (num_graphs < 1 || !graph_ptr_dev) num_graphs = 1, graph_ptr_dev = nullptr;
+  if (!X_dev || !rowptr_dev || !W_dev || !a_dev || !dout_dev || !dW_dev || !da_dev || N < 1 || E < 0 ||
+      (E > 0 && (!col_dev || !rowptr_src_dev || !eid_src_dev || !tgt_of_edge_dev)))
+    return fail(c, MGU_ERR_INVALID, "bad gat_layer_backward args");
+  int rc = gat_check_layer(c, "mgu_gat_layer_backward", Fin, heads, Fh, true, N);
+  if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)hip_stream;
-  // ---- scratch of its own (the GEMM launchers below use the shared building-block scratch) ----
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off += (bytes + 255) / 256 * 256;
-    return o;
-  };
-  const int nb = std::max(1, std::min(256, (N + 255) / 256));
-  const int rpb = (N + nb - 1) / nb;
-  const size_t o_wh = take((size_t)N * HF * 4), o_st = take((size_t)N * 2 * heads * 4), o_ng = take((size_t)N * 4),
-               o_gm = take((size_t)num_graphs * heads * 4), o_ghp = take((size_t)N * HF * 4), o_al = take((size_t)std::max<int64_t>(E, 1) * heads * 4),
-               o_gz = take((size_t)std::max<int64_t>(E, 1) * heads * 4), o_gt = take((size_t)N * heads * 4), o_gs = take((size_t)N * heads * 4),
-               o_gmr = take((size_t)N * heads * 4), o_gwh = take((size_t)N * HF * 4), o_part = take((size_t)nb * 2 * HF * 4);
-  int rc = ensure(c, &c->gbws, &c->gbws_bytes, off);
-  if (rc) return rc;
-  char* g = (char*)c->gbws;
-  float *wh = (float*)(g + o_wh), *st = (float*)(g + o_st), *gm_f = (float*)(g + o_gm), *ghp = (float*)(g + o_ghp), *al = (float*)(g + o_al),
-        *gz = (float*)(g + o_gz), *gt = (float*)(g + o_gt), *gs = (float*)(g + o_gs), *gmr = (float*)(g + o_gmr), *gwh = (float*)(g + o_gwh),
-        *part = (float*)(g + o_part);
-  int32_t* node_graph = num_graphs > 1 ? (int32_t*)(g + o_ng) : nullptr;
-  // ---- recompute Wh, s, t and the per-graph max exactly as the forward's gather schedule does ----
-  if ((rc = gat_linear_st(c, (const float*)X_dev, N, Fin, (const float*)W_dev, (const float*)a_dev, heads, Fh, wh, st, s))) return rc;
-  unsigned long long* gmax;
-  unsigned gen;
-  if ((rc = gmax_buffer(c, num_graphs * heads, &gmax, &gen))) return rc;
-  if (node_graph) HIPCHK(c, launch_gat_node_graph(graph_ptr_dev, num_graphs, 0, N, node_graph, s));
-  HIPCHK(c, launch_gat_edge_max(st, rowptr_dev, col_dev, node_graph, N, heads, alpha, gmax, c->gmax_cap, gen, s));
-  hipLaunchKernelGGL(gatb_gmax_decode_kernel, dim3((num_graphs * heads + 63) / 64), dim3(64), 0, s, gmax, num_graphs * heads, gen, gm_f);
+  TrainWs w;
+  if ((rc = train_prologue(c, (const float*)X_dev, N, Fin, rowptr_dev, col_dev, E, &graph_ptr_dev, &num_graphs, (const float*)W_dev,
+                           (const float*)a_dev, heads, Fh, alpha, &w, s)))
+    return rc;
   // ---- attention backward ----
-  hipLaunchKernelGGL(gatb_target_kernel, dim3((N + 3) / 4), dim3(256), 0, s, wh, st, rowptr_dev, col_dev, node_graph, gm_f,
-                     (const float*)dout_dev, N, heads, Fh, concat, alpha, ghp, al, gz, gt, gmr, edge_mask_dev, out_mask_dev);
+  hipLaunchKernelGGL(gatb_target_kernel, dim3((N + 3) / 4), dim3(256), 0, s, w.wh, w.st, rowptr_dev, col_dev, w.node_graph, w.gm,
+                     (const float*)dout_dev, N, heads, Fh, concat, alpha, w.ghp, w.al, w.gz, w.gt, w.gmr, edge_mask_dev, out_mask_dev);
   if (E > 0) {
     int* err_dev = nullptr;
     if ((rc = err_word_dev(c, &err_dev))) return rc;
-    hipLaunchKernelGGL(gatb_max_term_kernel, dim3(num_graphs * heads), dim3(256), 0, s, st, rowptr_dev, col_dev, tgt_of_edge_dev, graph_ptr_dev, N,
-                       heads, alpha, gm_f, gmr, gz, gt, err_dev);
-  }
-  if (E > 0) {
-    hipLaunchKernelGGL(gatb_source_kernel, dim3((N + 3) / 4), dim3(256), 0, s, ghp, al, gz, gt, rowptr_src_dev, eid_src_dev, tgt_of_edge_dev,
-                       (const float*)a_dev, N, heads, Fh, gwh, gs);
+    hipLaunchKernelGGL(gatb_max_term_kernel, dim3(num_graphs * heads), dim3(256), 0, s, w.st, rowptr_dev, col_dev, tgt_of_edge_dev, graph_ptr_dev,
+                       N, heads, alpha, w.gm, w.gmr, w.gz, w.gt, err_dev);
+    hipLaunchKernelGGL(gatb_source_kernel, dim3((N + 3) / 4), dim3(256), 0, s, w.ghp, w.al, w.gz, w.gt, rowptr_src_dev, eid_src_dev,
+                       tgt_of_edge_dev, (const float*)a_dev, N, heads, Fh, w.gwh, w.gs);
   } else {   // no edges: nothing reaches Wh (every output row is ELU(0) = 0)
-    HIPCHK(c, hipMemsetAsync(gwh, 0, (size_t)N * HF * 4, s));
-    HIPCHK(c, hipMemsetAsync(gs, 0, (size_t)N * heads * 4, s));
+    HIPCHK(c, hipMemsetAsync(w.gwh, 0, (size_t)N * HF * 4, s));
+    HIPCHK(c, hipMemsetAsync(w.gs, 0, (size_t)N * heads * 4, s));
   }
-  hipLaunchKernelGGL(gatb_da_partial_kernel, dim3(nb), dim3(256), 0, s, wh, gs, gt, N, heads, Fh, rpb, part);
-  hipLaunchKernelGGL(gatb_da_final_kernel, dim3(1), dim3(256), 0, s, part, nb, heads, Fh, (float*)da_dev);
+  hipLaunchKernelGGL(gatb_da_partial_kernel, dim3(w.nb), dim3(256), 0, s, w.wh, w.gs, w.gt, N, heads, Fh, (N + w.nb - 1) / w.nb, w.part);
+  hipLaunchKernelGGL(gatb_da_final_kernel, dim3(1), dim3(256), 0, s, w.part, w.nb, heads, Fh, (float*)da_dev);
   HIPCHK(c, hipGetLastError());
   // ---- the linear layer: gW = gWh^T X, gX = gWh W (a 1x1 convolution over an N x 1 image) ----
-  if ((rc = mgu_conv2d_wgrad_nhwc(c, X_dev, Fin, gwh, 1, 1, N, Fin, HF, 1, dW_dev, hip_stream))) return rc;
-  if (dX_dev && (rc = mgu_conv2d_dgrad_nhwc(c, gwh, W_dev, 1, 1, N, Fin, HF, 1, dX_dev, Fin, hip_stream))) return rc;
+  if ((rc = mgu_conv2d_wgrad_nhwc(c, X_dev, Fin, w.gwh, 1, 1, N, Fin, HF, 1, dW_dev, hip_stream))) return rc;
+  if (dX_dev && (rc = mgu_conv2d_dgrad_nhwc(c, w.gwh, W_dev, 1, 1, N, Fin, HF, 1, dX_dev, Fin, hip_stream))) return rc;
   return MGU_OK;
 }
 
@@ -466,38 +488,18 @@ int mgu_gat_layer_forward_train(mgu_ctx* c, const void* X_dev, int N, int Fin, c
                                 const int32_t* graph_ptr_dev, int num_graphs, const void* W_dev, const void* a_dev, int heads, int Fout_head,
                                 int concat, float alpha, const void* edge_mask_dev, const void* out_mask_dev, void* out_dev, void* hip_stream) {
   if (!c) return MGU_ERR_INVALID;
-  const int Fh = Fout_head, HF = heads * Fh;
-  if (!X_dev || !rowptr_dev || !W_dev || !a_dev || !out_dev || N < 1 || Fin < 4 || (Fin & 3) || heads < 1 || Fh < 4 || (Fh & 3) || E < 0 ||
-      (E > 0 && !col_dev))
-    return fail(c, MGU_ERR_INVALID, "bad gat_layer_forward_train args (Fin, Fout_head multiples of 4)");
-  if (HF > 256) return fail(c, MGU_ERR_INVALID, "gat_layer_forward_train supports heads * Fout_head <= 256 (got %d x %d)", heads, Fh);
-  if ((int64_t)N * HF >= (1ll << 31)) return fail(c, MGU_ERR_INVALID, "N * heads * Fout_head must be < 2^31");
-  if (num_graphs < 1 || !graph_ptr_dev) num_graphs = 1, graph_ptr_dev = nullptr;
+  if (!X_dev || !rowptr_dev || !W_dev || !a_dev || !out_dev || N < 1 || E < 0 || (E > 0 && !col_dev))
+    return fail(c, MGU_ERR_INVALID, "bad gat_layer_forward_train args");
+  int rc = gat_check_layer(c, "mgu_gat_layer_forward_train", Fin, heads, Fout_head, true, N);
+  if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)hip_stream;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off += (bytes + 255) / 256 * 256;
-    return o;
-  };
-  const size_t o_wh = take((size_t)N * HF * 4), o_st = take((size_t)N * 2 * heads * 4), o_ng = take((size_t)N * 4),
-               o_gm = take((size_t)num_graphs * heads * 4);
-  int rc = ensure(c, &c->gbws, &c->gbws_bytes, off);
-  if (rc) return rc;
-  char* g = (char*)c->gbws;
-  float *wh = (float*)(g + o_wh), *st = (float*)(g + o_st), *gm_f = (float*)(g + o_gm);
-  int32_t* node_graph = num_graphs > 1 ? (int32_t*)(g + o_ng) : nullptr;
-  // Wh, s, t from one GEMM and the per-graph max, exactly as mgu_gat_layer_backward recomputes them
-  if ((rc = gat_linear_st(c, (const float*)X_dev, N, Fin, (const float*)W_dev, (const float*)a_dev, heads, Fh, wh, st, s))) return rc;
-  unsigned long long* gmax;
-  unsigned gen;
-  if ((rc = gmax_buffer(c, num_graphs * heads, &gmax, &gen))) return rc;
-  if (node_graph) HIPCHK(c, launch_gat_node_graph(graph_ptr_dev, num_graphs, 0, N, node_graph, s));
-  if (E > 0) HIPCHK(c, launch_gat_edge_max(st, rowptr_dev, col_dev, node_graph, N, heads, alpha, gmax, c->gmax_cap, gen, s));
-  hipLaunchKernelGGL(gatb_gmax_decode_kernel, dim3((num_graphs * heads + 63) / 64), dim3(64), 0, s, gmax, num_graphs * heads, gen, gm_f);
-  hipLaunchKernelGGL(gatf_train_kernel, dim3((N + 3) / 4), dim3(256), 0, s, wh, st, rowptr_dev, col_dev, node_graph, gm_f, N, heads, Fh, concat,
-                     alpha, (const float*)edge_mask_dev, (const float*)out_mask_dev, (float*)out_dev);
+  TrainWs w;
+  if ((rc = train_prologue(c, (const float*)X_dev, N, Fin, rowptr_dev, col_dev, E, &graph_ptr_dev, &num_graphs, (const float*)W_dev,
+                           (const float*)a_dev, heads, Fout_head, alpha, &w, s)))
+    return rc;
+  hipLaunchKernelGGL(gatf_train_kernel, dim3((N + 3) / 4), dim3(256), 0, s, w.wh, w.st, rowptr_dev, col_dev, w.node_graph, w.gm, N, heads,
+                     Fout_head, concat, alpha, (const float*)edge_mask_dev, (const float*)out_mask_dev, (float*)out_dev);
   HIPCHK(c, hipGetLastError());
   return MGU_OK;
 }

@@ -120,7 +120,6 @@ void mgu_destroy(mgu_ctx* c) {
   if (c->gws) (void)hipFree(c->gws);
   if (c->gbws) (void)hipFree(c->gbws);
   if (c->pack_dev) (void)hipFree(c->pack_dev);
-  if (c->gbpanel) (void)hipFree(c->gbpanel);
   if (c->tws) (void)hipFree(c->tws);
   if (c->redws) (void)hipFree(c->redws);
   if (c->wuws) (void)hipFree(c->wuws);

@@ -9,7 +9,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .gat import GATNetwork, _csr_cache, prepared_head_weights, stacked_head_weights
+from .gat import GATNetwork, _csr_cache, _layer_forward, _LayerCall
 from .patch_graph import PatchGraphConstructor
 from .unet import UNet
 
@@ -90,25 +90,16 @@ class MinGraphUNetE2E(nn.Module):
 
 
 def gat_forward_csr(gat: GATNetwork, X, rowptr, col, graph_ptr):
-    """GATNetwork.forward on a prebuilt device CSR (skips the COO->CSR conversion of the COO API)."""
+    """GATNetwork.forward in eval mode on a prebuilt device CSR (skips the COO->CSR conversion of the COO API; no autograd node)."""
     h = X
-    dev = X.device
-    G = graph_ptr.numel() - 1 if graph_ptr is not None else 1
     for layer in gat.gat_layers:
         if layer.training and layer.dropout_rate > 0:
             raise RuntimeError("gat_forward_csr is the inference schedule on a prebuilt CSR: call .eval(), or run the layer through "
                                "GATNetwork.forward(X, edge_index) for train-mode dropout (see mgunet.gat)")
         heads = list(layer.heads)
-        Fh, H = heads[0].out_features, len(heads)
-        W, a = stacked_head_weights(heads, _csr_cache(layer))
-        if h.shape[1] % 4 or W.shape[1] != h.shape[1]:
-            raise ValueError("node feature width must be a multiple of 4 and match W")
-        h = h.contiguous()
-        out = torch.empty((h.shape[0], H * Fh if layer.concat else Fh), device=dev, dtype=torch.float32)
-        handle = prepared_head_weights(heads, _csr_cache(layer), dev, col.numel() > 0)
-        _lib.call("mgu_gat_layer_forward_prepared", dev, handle, h, h.shape[0], rowptr, col if col.numel() else None, col.numel(),
-                  graph_ptr, G, 1 if layer.concat else 0, float(layer.alpha), out)
-        h = out
+        if heads[0].W.weight.shape[1] != h.shape[1]:
+            raise ValueError("node feature width must match W")
+        h = _layer_forward(_LayerCall(heads, h, layer.concat, layer.alpha, _csr_cache(layer), graph_ptr, csr=(rowptr, col)), None)
     return h
 
 

@@ -140,62 +140,61 @@ def _gat_layer_forward(heads, X, edge_index, concat, alpha, training, dropout_ra
     if heads[0].W.weight.shape[1] != X.shape[1]:
         raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({X.shape[0]}x{X.shape[1]} and "
                            f"{heads[0].W.weight.shape[1]}x{heads[0].out_features})")
-    meta = _LayerCall(heads, edge_index, concat, alpha, graph_ptr, cache)
     params = [t for h in heads for t in (h.W.weight, h.a.weight)]
-    if training and dropout_rate > 0:
-        meta.dropout_rate = float(dropout_rate)
-        meta.injected = getattr(owner, "dropout_masks", None) if owner is not None else None
-        meta.out_dropout = out_dropout   # a lone GraphAttentionLayer drops coefficients only (:97); :160 belongs to the multi-head layer
-        return _GatLayerTrainFn.apply(X, meta, *params)
+    train = training and dropout_rate > 0
+    injected = getattr(owner, "dropout_masks", None) if train and owner is not None else None
+    m = _LayerCall(heads, X, concat, alpha, cache, graph_ptr, edge_index=edge_index, with_perm=injected is not None)
+    if train:   # a lone GraphAttentionLayer drops coefficients only (:97); :160 belongs to the multi-head layer
+        return _GatLayerFn.apply(X, m, _dropout_masks(m, float(dropout_rate), injected, out_dropout), *params)
     if torch.is_grad_enabled() and (X.requires_grad or any(t.requires_grad for t in params)):
         # a node of the autograd graph whose backward is mgu_gat_layer_backward (gat_bwd.hip): loss.backward() reaches the GAT
         # parameters as it does in the reference's loop (scripts/train_end_to_end.py:219-226, :478)
-        return _GatLayerFn.apply(X, meta, *params)
-    return _gat_layer_run(X, meta)[0]
+        return _GatLayerFn.apply(X, m, None, *params)
+    return _layer_forward(m, None)
 
 
 class _LayerCall:
-    """The non-tensor arguments of one layer call."""
+    """One layer call as the library takes it: the node features X (N, Fin) zero-padded to a multiple of 4 (exact: W is padded the
+    same way in stacked_head_weights), the CSR by target (the module's cache of edge_index, or the caller's `csr`), graph_ptr, and
+    the head width Fh padded to a multiple of 4 (narrow heads, e.g. the 2-segment predictor, run zero-padded and are sliced off)."""
 
-    def __init__(self, heads, edge_index, concat, alpha, graph_ptr, cache):
-        self.heads, self.edge_index, self.concat, self.alpha, self.graph_ptr, self.cache = heads, edge_index, concat, alpha, graph_ptr, cache
-        self.dropout_rate, self.injected, self.out_dropout = 0.0, None, True   # train mode (see _GatLayerTrainFn)
+    def __init__(self, heads, X, concat, alpha, cache, graph_ptr, edge_index=None, csr=None, with_perm=False):
+        self.heads, self.concat, self.alpha, self.cache, self.dev = heads, 1 if concat else 0, float(alpha), cache, X.device
+        self.N, self.Fin = X.shape
+        self.H, self.Fh_true = len(heads), heads[0].out_features
+        self.Fh = (self.Fh_true + 3) // 4 * 4
+        self.W, self.a = stacked_head_weights(heads, cache)
+        if self.W.device != self.dev:
+            raise RuntimeError(f"GAT parameters are on {self.W.device}, node features on {self.dev}")
+        Xc = X.detach().contiguous()
+        self.X = F.pad(Xc, (0, 4 - self.Fin % 4)) if self.Fin % 4 else Xc
+        if csr is None:
+            self.rowptr, self.col, self.perm = _cached_csr(cache, edge_index, self.N, self.dev, with_perm)
+        else:
+            (self.rowptr, self.col), self.perm = csr, None
+        self.E = self.col.numel()
+        self.gp, self.G = None, 1
+        if graph_ptr is not None:
+            self.gp = graph_ptr.to(device=self.dev, dtype=torch.int32).contiguous()
+            self.G = self.gp.numel() - 1
 
 
-def _gat_layer_run(X, m):
-    """The forward through libmgunet; returns (out, saved) with `saved` what a backward needs."""
-    heads, cache = m.heads, m.cache
-    dev = X.device
-    N, Fin = X.shape
-    H = len(heads)
-    Fh_true = heads[0].out_features
-    Fh = (Fh_true + 3) // 4 * 4   # narrow heads (e.g. the 2-segment predictor) run zero-padded, see stacked_head_weights
-    W, a = stacked_head_weights(heads, cache)
-    Xc = X.detach().contiguous()
-    if Fin % 4:  # zero-pad K to a multiple of 4: exact (W is padded the same way in stacked_head_weights)
-        Xc = F.pad(Xc, (0, 4 - Fin % 4))
-    edge_index = m.edge_index
+def _cached_csr(cache, edge_index, N, dev, with_perm):
+    """(rowptr, col, perm): the CSR by target of edge_index, built once per edge_index tensor, and with_perm: the stable COO -> CSR
+    edge permutation (the order mgu_coo_to_csr_device produces) that brings injected masks from COO order into CSR order."""
     key = (edge_index.data_ptr(), tuple(edge_index.shape), edge_index._version, N, str(edge_index.device))
     ent = cache.get("csr")
     if ent is None or ent[0] != key:
         rowptr, col = coo_to_csr_device(edge_index.to(dev), N)
         ent = cache["csr"] = (key, rowptr, col, edge_index)  # keep the key tensor alive so data_ptr stays unique
         cache.pop("csr_t", None)
-    rowptr, col = ent[1], ent[2]
-    G, gp = 1, None
-    if m.graph_ptr is not None:
-        gp = m.graph_ptr.to(device=dev, dtype=torch.int32).contiguous()
-        G = gp.numel() - 1
-    out = torch.empty((N, H * Fh if m.concat else Fh), device=dev, dtype=torch.float32)
-    if W.device != dev:
-        raise RuntimeError(f"GAT parameters are on {W.device}, node features on {dev}")
-    handle = prepared_head_weights(heads, cache, dev, col.numel() > 0)
-    _lib.call("mgu_gat_layer_forward_prepared", dev, handle, Xc, N, rowptr, col if col.numel() else None, col.numel(), gp, G,
-              1 if m.concat else 0, float(m.alpha), out)
-    saved = (Xc, W, a, rowptr, col, gp, G, Fh, Fh_true, Fin)
-    if Fh != Fh_true:
-        out = out.view(N, -1, Fh)[:, :, :Fh_true].reshape(N, -1).contiguous()
-    return out, saved
+        cache.pop("perm", None)
+    if not with_perm:
+        return ent[1], ent[2], None
+    pe = cache.get("perm")
+    if pe is None or pe[0] != key:
+        pe = cache["perm"] = (key, torch.sort(edge_index.to(dev)[1], stable=True).indices)
+    return ent[1], ent[2], pe[1]
 
 
 def _transposed_csr(cache, rowptr, col, N, dev):
@@ -211,125 +210,70 @@ def _transposed_csr(cache, rowptr, col, N, dev):
     return ent[1], ent[2], ent[3]
 
 
+def _dropout_masks(m, p, injected, out_dropout):
+    """(edge mask (E, H) in CSR order, output mask at the padded width or None) of a train-mode call: drawn by mgu_dropout_mask,
+    edge mask first, or injected as `layer.dropout_masks` = ((H, E) in COO order, (N, F_out) or None), the hook a test feeds the
+    reference's draw through."""
+    N, H, E = m.N, m.H, m.E
+    Fo_true = H * m.Fh_true if m.concat else m.Fh_true
+    if injected is not None:
+        em_coo, om = injected
+        if tuple(em_coo.shape) != (H, E) or (om is not None and tuple(om.shape) != (N, Fo_true)):
+            raise ValueError(f"dropout_masks must be ((heads, E) = {(H, E)}, (N, F_out) = {(N, Fo_true)} or None)")
+        edge_mask = em_coo.to(device=m.dev, dtype=torch.float32)[:, m.perm].t().contiguous()
+        om = om.to(device=m.dev, dtype=torch.float32) if om is not None else None
+    else:
+        edge_mask = _draw_mask(m.dev, (max(E, 1), H), p)
+        om = _draw_mask(m.dev, (N, Fo_true), p) if out_dropout else None
+    if om is not None and m.Fh != m.Fh_true:   # heads run zero-padded to 16-byte lanes: the pad features are ELU(0) = 0 whatever their mask
+        om = F.pad(om.view(N, -1, m.Fh_true), (0, m.Fh - m.Fh_true), value=1.0).reshape(N, -1)
+    return edge_mask, om.contiguous() if om is not None else None
+
+
+def _layer_forward(m, masks):
+    """The layer through libmgunet: eval (masks None) on the prepared weights, train mode with explicit dropout masks."""
+    out = torch.empty((m.N, m.H * m.Fh if m.concat else m.Fh), device=m.dev, dtype=torch.float32)
+    col = m.col if m.E else None
+    if masks is None:
+        handle = prepared_head_weights(m.heads, m.cache, m.dev, m.E > 0)
+        _lib.call("mgu_gat_layer_forward_prepared", m.dev, handle, m.X, m.N, m.rowptr, col, m.E, m.gp, m.G, m.concat, m.alpha, out)
+    else:
+        _lib.call("mgu_gat_layer_forward_train", m.dev, m.X, m.N, m.X.shape[1], m.rowptr, col, m.E, m.gp, m.G, m.W, m.a, m.H, m.Fh,
+                  m.concat, m.alpha, *masks, out)
+    if m.Fh != m.Fh_true:
+        out = out.view(m.N, -1, m.Fh)[:, :, :m.Fh_true].reshape(m.N, -1).contiguous()
+    return out
+
+
 class _GatLayerFn(torch.autograd.Function):
+    """One multi-head layer as a node of the autograd graph.  masks None: eval, backward mgu_gat_layer_backward; otherwise TRAIN mode
+    with dropout (graph_attention.py:97, :160): mgu_gat_layer_forward_train and mgu_gat_layer_backward_train with the same masks."""
+
     @staticmethod
-    def forward(ctx_, X, meta, *params):
-        out, saved = _gat_layer_run(X, meta)
-        ctx_.meta, ctx_.saved = meta, saved
-        return out
+    def forward(ctx_, X, m, masks, *params):
+        ctx_.m, ctx_.masks = m, masks
+        return _layer_forward(m, masks)
 
     @staticmethod
     def backward(ctx_, gout):
-        m = ctx_.meta
-        Xc, W, a, rowptr, col, gp, G, Fh, Fh_true, Fin = ctx_.saved
-        heads = m.heads
-        H, N, dev = len(heads), Xc.shape[0], Xc.device
+        m = ctx_.m
+        N, Fh, Fh_true = m.N, m.Fh, m.Fh_true
         g = gout.detach().float()
         if Fh != Fh_true:   # the padded output features never reach the caller: their gradient is 0
             g = F.pad(g.view(N, -1, Fh_true), (0, Fh - Fh_true)).reshape(N, -1)
-        g = g.contiguous()
-        rps, eid, tgt = _transposed_csr(m.cache, rowptr, col, N, dev)
-        need_x = ctx_.needs_input_grad[0]
-        dX = torch.empty_like(Xc) if need_x else None
-        dW, da = torch.empty_like(W), torch.empty_like(a)
-        E = col.numel()
-        _lib.call("mgu_gat_layer_backward", dev, Xc, N, Xc.shape[1], rowptr, col if E else None, E, rps, eid, tgt, gp, G, W, a, H, Fh,
-                  1 if m.concat else 0, float(m.alpha), g, dX, dW, da)
-        grads = []
-        for h in range(H):
-            grads.append(dW[h * Fh:h * Fh + Fh_true, :Fin].contiguous())
-            grads.append(torch.cat([da[h:h + 1, :Fh_true], da[h:h + 1, Fh:Fh + Fh_true]], 1).contiguous())
-        return (dX[:, :Fin].contiguous() if need_x else None, None, *grads)
-
-
-def _csr_with_perm(m, N, dev):
-    """(rowptr, col, perm): the cached CSR by target and, for injected masks, the stable COO -> CSR edge permutation."""
-    cache, edge_index = m.cache, m.edge_index
-    key = (edge_index.data_ptr(), tuple(edge_index.shape), edge_index._version, N, str(edge_index.device))
-    ent = cache.get("csr")
-    if ent is None or ent[0] != key:
-        rowptr, col = coo_to_csr_device(edge_index.to(dev), N)
-        ent = cache["csr"] = (key, rowptr, col, edge_index)
-        cache.pop("csr_t", None)
-        cache.pop("perm", None)
-    perm = None
-    if m.injected is not None:
-        pe = cache.get("perm")
-        if pe is None or pe[0] != key:
-            pe = cache["perm"] = (key, torch.sort(edge_index.to(dev)[1], stable=True).indices)   # the order mgu_coo_to_csr_device produces
-        perm = pe[1]
-    return ent[1], ent[2], perm
-
-
-class _GatLayerTrainFn(torch.autograd.Function):
-    """One multi-head layer in TRAIN mode with dropout (graph_attention.py:97, :160): mgu_gat_layer_forward_train with explicit masks
-    (drawn by mgu_dropout_mask, or injected through `layer.dropout_masks`), backward mgu_gat_layer_backward_train with the same masks."""
-
-    @staticmethod
-    def forward(ctx_, X, m, *params):
-        heads = m.heads
-        dev = X.device
-        N, Fin = X.shape
-        H = len(heads)
-        Fh_true = heads[0].out_features
-        Fh = (Fh_true + 3) // 4 * 4
-        W, a = stacked_head_weights(heads, m.cache)
-        Xc = X.detach().contiguous()
-        if Fin % 4:
-            Xc = F.pad(Xc, (0, 4 - Fin % 4))
-        rowptr, col, perm = _csr_with_perm(m, N, dev)
-        E = col.numel()
-        G, gp = 1, None
-        if m.graph_ptr is not None:
-            gp = m.graph_ptr.to(device=dev, dtype=torch.int32).contiguous()
-            G = gp.numel() - 1
-        Fo_true = H * Fh_true if m.concat else Fh_true
-        if m.injected is not None:   # (H, E) in COO order, (N, F_out) or None: the hook a test feeds the reference's draw through
-            em_coo, om_true = m.injected
-            if tuple(em_coo.shape) != (H, E) or (om_true is not None and tuple(om_true.shape) != (N, Fo_true)):
-                raise ValueError(f"dropout_masks must be ((heads, E) = {(H, E)}, (N, F_out) = {(N, Fo_true)} or None)")
-            edge_mask = em_coo.to(device=dev, dtype=torch.float32)[:, perm].t().contiguous()
-            om_true = om_true.to(device=dev, dtype=torch.float32) if om_true is not None else None
+        rps, eid, tgt = _transposed_csr(m.cache, m.rowptr, m.col, N, m.dev)
+        dX = torch.empty_like(m.X) if ctx_.needs_input_grad[0] else None
+        dW, da = torch.empty_like(m.W), torch.empty_like(m.a)
+        args = (m.X, N, m.X.shape[1], m.rowptr, m.col if m.E else None, m.E, rps, eid, tgt, m.gp, m.G, m.W, m.a, m.H, Fh, m.concat, m.alpha)
+        if ctx_.masks is None:
+            _lib.call("mgu_gat_layer_backward", m.dev, *args, g.contiguous(), dX, dW, da)
         else:
-            edge_mask = _draw_mask(dev, (max(E, 1), H), m.dropout_rate)
-            om_true = _draw_mask(dev, (N, Fo_true), m.dropout_rate) if m.out_dropout else None
-        if om_true is None:
-            out_mask = None
-        elif Fh != Fh_true:   # heads run zero-padded to 16-byte lanes: the pad features are ELU(0) = 0 whatever their mask
-            out_mask = F.pad(om_true.view(N, -1, Fh_true), (0, Fh - Fh_true), value=1.0).reshape(N, -1).contiguous()
-        else:
-            out_mask = om_true.contiguous()
-        out = torch.empty((N, H * Fh if m.concat else Fh), device=dev, dtype=torch.float32)
-        _lib.call("mgu_gat_layer_forward_train", dev, Xc, N, Xc.shape[1], rowptr, col if E else None, E, gp, G, W, a, H, Fh,
-                  1 if m.concat else 0, float(m.alpha), edge_mask, out_mask, out)
-        ctx_.meta = m
-        ctx_.saved = (Xc, W, a, rowptr, col, gp, G, Fh, Fh_true, Fin, edge_mask, out_mask)
-        if Fh != Fh_true:
-            out = out.view(N, -1, Fh)[:, :, :Fh_true].reshape(N, -1).contiguous()
-        return out
-
-    @staticmethod
-    def backward(ctx_, gout):
-        m = ctx_.meta
-        Xc, W, a, rowptr, col, gp, G, Fh, Fh_true, Fin, edge_mask, out_mask = ctx_.saved
-        heads = m.heads
-        H, N, dev = len(heads), Xc.shape[0], Xc.device
-        g = gout.detach().float()
-        if Fh != Fh_true:
-            g = F.pad(g.view(N, -1, Fh_true), (0, Fh - Fh_true)).reshape(N, -1)
-        g = g.contiguous()
-        rps, eid, tgt = _transposed_csr(m.cache, rowptr, col, N, dev)
-        need_x = ctx_.needs_input_grad[0]
-        dX = torch.empty_like(Xc) if need_x else None
-        dW, da = torch.empty_like(W), torch.empty_like(a)
-        E = col.numel()
-        _lib.call("mgu_gat_layer_backward_train", dev, Xc, N, Xc.shape[1], rowptr, col if E else None, E, rps, eid, tgt, gp, G, W, a, H, Fh,
-                  1 if m.concat else 0, float(m.alpha), edge_mask, out_mask, g, dX, dW, da)
+            _lib.call("mgu_gat_layer_backward_train", m.dev, *args, *ctx_.masks, g.contiguous(), dX, dW, da)
         grads = []
-        for h in range(H):
-            grads.append(dW[h * Fh:h * Fh + Fh_true, :Fin].contiguous())
+        for h in range(m.H):
+            grads.append(dW[h * Fh:h * Fh + Fh_true, :m.Fin].contiguous())
             grads.append(torch.cat([da[h:h + 1, :Fh_true], da[h:h + 1, Fh:Fh + Fh_true]], 1).contiguous())
-        return (dX[:, :Fin].contiguous() if need_x else None, None, *grads)
+        return (dX[:, :m.Fin].contiguous() if dX is not None else None, None, None, *grads)
 
 
 class MultiHeadGATLayer(nn.Module):

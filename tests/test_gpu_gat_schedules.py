@@ -52,9 +52,14 @@ def run(ctx, cuda, X, rowptr, col, gp, W, a, heads, Fh, concat):
                                                     gp.data_ptr() if gp is not None else None, gp.numel() - 1 if gp is not None else 1,
                                                     1 if concat else 0, 0.2, out.data_ptr(), s), ctx.handle)
         res.append(out.clone())
+    one = torch.full_like(out, float("nan"))       # the one-shot entry: prepares c->gat_tmp, then the same schedule
+    _lib.check(L.mgu_gat_layer_forward(ctx.handle, X.data_ptr(), N, Fin, rowptr.data_ptr(), col.data_ptr() if E else None, E,
+                                       gp.data_ptr() if gp is not None else None, gp.numel() - 1 if gp is not None else 1, Wd.data_ptr(),
+                                       ad.data_ptr(), heads, Fh, 1 if concat else 0, 0.2, one.data_ptr(), s), ctx.handle)
     torch.cuda.synchronize()
     L.mgu_gat_release(ctx.handle, h)
     assert torch.equal(res[0], res[1]) and torch.equal(res[1], res[2])
+    assert torch.equal(one, res[0])
     return res[0].cpu()
 
 
@@ -74,6 +79,50 @@ def test_batched_patch_graphs(cuda, sched, concat, Fin, heads, Fh):
     ref = oracle_layer(X, [(ei, g * N1, (g + 1) * N1) for g in range(G)], W, a, heads, Fh, concat)
     got = run(ctx, cuda, X.to(cuda), rowptr, col, gp, W, a, heads, Fh, concat)
     assert float((got - ref).abs().max()) <= 1e-4 * max(1.0, float(ref.abs().max()))
+
+
+@pytest.mark.parametrize("sched", ["aggregate_first", "wh_row_gather"])
+def test_one_shot_reuses_then_reshapes_its_weights(cuda, sched):
+    """mgu_gat_layer_forward keeps its weight buffer while the shape and schedule stay (the second call repacks it in place, keeping
+    the gather panel's zero padding) and reallocates on another shape (36 -> 2 x 32 takes the gather schedule, with K padding):
+    every call equals the prepared call bit for bit (run) and the oracle."""
+    ctx = make_ctx({"MGU_NO_GAT_FUSED": "1"} if sched == "wh_row_gather" else {})
+    G, H, Wd = 2, 80, 112
+    rowptr, col, gp, N1, E1 = mgunet.PatchGraphConstructor(16).batched_csr(H, Wd, G, cuda)
+    ei = torch.from_numpy(O.patch_graph_edges(H, Wd, 16))
+    N = N1 * G
+    for i, (Fin, heads, Fh) in enumerate([(32, 4, 64), (32, 4, 64), (36, 2, 32)]):
+        X = torch.from_numpy(O.formula_normal("gs/ox", (N, Fin), seed=20 + i))
+        W = torch.from_numpy(O.formula_uniform("gs/ow", (heads * Fh, Fin), -0.4, 0.4, seed=30 + i))
+        a = torch.from_numpy(O.formula_uniform("gs/oa", (heads, 2 * Fh), -0.4, 0.4, seed=40 + i))
+        ref = oracle_layer(X, [(ei, g * N1, (g + 1) * N1) for g in range(G)], W, a, heads, Fh, 1)
+        got = run(ctx, cuda, X.to(cuda), rowptr, col, gp, W, a, heads, Fh, 1)
+        assert float((got - ref).abs().max()) <= 1e-4 * max(1.0, float(ref.abs().max())), i
+
+
+@pytest.mark.parametrize("kind", ["mean", "concat", "two_layers"])
+@pytest.mark.parametrize("Fh", [8, 2, 6])
+@pytest.mark.parametrize("Fin", [16, 10])
+def test_gat_forward_csr_equals_network_forward(cuda, kind, Fh, Fin):
+    """mgunet.gat_forward_csr on the batched CSR gives GATNetwork.forward's bytes on the same graph, for head and node widths that
+    are not multiples of 4 too (run zero-padded and sliced, as the COO path runs them): one mean layer of 2 heads, one concat layer
+    of 2 heads, and the 2-layer 1-head network (concat, then mean: the second layer's input is Fh wide)."""
+    torch.manual_seed(Fh * 100 + Fin)
+    if kind == "two_layers":
+        net = mgunet.GATNetwork(Fin, Fh, 5, 1, num_gat_layers=2)
+    else:
+        net = mgunet.GATNetwork(Fin, 16, Fh, 2)
+        if kind == "concat":
+            net.gat_layers[0] = mgunet.MultiHeadGATLayer(Fin, 2 * Fh, 2, 0.1, 0.2, concat=True)
+    net = net.to(cuda).eval()
+    G, H, Wd = 2, 80, 112
+    pg = mgunet.PatchGraphConstructor(16)
+    rowptr, col, gp, N1, E1 = pg.batched_csr(H, Wd, G, cuda)
+    X = torch.from_numpy(O.formula_normal("gs/csr", (N1 * G, Fin), seed=Fin)).to(cuda)
+    with torch.no_grad():
+        ref = net(X, pg.edge_index(H, Wd, cuda, G), graph_ptr=gp)
+        got = mgunet.gat_forward_csr(net, X, rowptr, col, gp)
+    assert got.shape == ref.shape and torch.equal(got, ref)
 
 
 @pytest.mark.parametrize("sched", ["aggregate_first", "wh_row_gather"])
