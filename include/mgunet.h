@@ -438,6 +438,50 @@ int mgu_match_objects(mgu_ctx* ctx, int B, const int64_t* gt_offsets_dev, const 
 int mgu_object_scores(mgu_ctx* ctx, const int32_t* labels_dev, const float* probs_dev, int B, int H, int W, int C, const int64_t* offsets_dev,
                       int64_t capacity, const int64_t* class_dev, const int64_t* area_dev, float* scores_dev, void* hip_stream);
 
+/* ---- object shape: per-object moments, fitted ellipse and the per-instance form of EllipticalShapeLoss (model/unet/shape_loss.py
+ *      :155-180 over the instances :42-48 and :85-92 ask for) straight from the label map: no dense masks, no per-object launches,
+ *      no host synchronisation; the launch count does not depend on the number of objects ------------------------------------------
+ * Raw power sums of mgu_connected_components' labels_dev / offsets_dev at batch-wide object index i < capacity (objects past it
+ * are skipped).  moments_dev: uint64 (capacity, 12), row i = sum over the object's pixels of
+ *   [u^2, uv, v^2, u^3, u^2 v, u v^2, v^3, u^4, u^3 v, u^2 v^2, u v^3, v^4],  u = x - xmin, v = y - ymin in pixels,
+ * with (xmin, ymin) = bbox_dev[4i], bbox_dev[4i+1] as mgu_object_stats wrote them for the same labels (orders 0 and 1 are its
+ * area_dev and sums_dev).  The rows of the objects present are zeroed first.  Unsigned 64-bit integer atomics: exact and order-free,
+ * so bitwise repeatable.  A sum is exact while area * (max(w, h) - 1)^4 < 2^64 (w, h the box sides; a full-image object up to
+ * 1024 x 1024 qualifies); past that it wraps, and mgu_object_shapes marks the object status 2 instead of using it.  B*H*W < 2^31. */
+int mgu_object_moments(mgu_ctx* ctx, const int32_t* labels_dev, int B, int H, int W, const int64_t* offsets_dev, int64_t capacity,
+                       const int32_t* bbox_dev, uint64_t* moments_dev, void* hip_stream);
+/* Per-object shape from mgu_object_stats' area_dev / bbox_dev / sums_dev and mgu_object_moments' moments_dev (labels_dev, B, H, W as
+ * given to it), one thread per object, all arithmetic in fp64 from the exact integers, every output rounded to fp32 once.  Row
+ * i < min(offsets[B], capacity) of
+ *   centroid_dev (2)  [sum x / n, sum y / n] in image coordinates (pixels)
+ *   cov_dev (3)       [c_xx, c_xy, c_yy]: the sample covariance, divisor n - 1 (torch.cov), no epsilon (pixels^2)
+ *   axes_dev (2)      [a, b] = [2 sqrt(l1), 2 sqrt(l2)], l1 >= l2 the eigenvalues of cov, l2 = det(cov) / l1 clamped at 0: the
+ *                     semi-axes, in pixels, of the uniformly filled ellipse with that covariance
+ *   angle_dev         0.5 atan2(2 c_xy, c_xx - c_yy), radians, the major axis from +x towards +y; atan2(0, 0) = 0
+ *   fill_dev          n / (pi a b), 0 when b = 0: 1 for a filled ellipse, lower for a hollow or merged shape
+ *   term_dev          mean_j (d_j^T (cov + epsilon I)^-1 d_j - 1)^2 over the object's centred pixels d_j (shape_loss.py:161-176);
+ *                     ~7/3 for a filled ellipse, not 0
+ *   status_dev        uint8: 0 analysed; 1 fewer than max(min_pixels, 2) pixels (the reference skips under 10, :158); 2 too large
+ *                     for exact moments (the bound above).  With a status != 0 only the centroid is computed, the rest is 0.
+ * Conditioning.  While n * max(w, h) < 2^30 the second moments are taken as exact integers, so det(cov), and with it b and fill, is
+ * 0 exactly for collinear pixels (past that, fp64).  The term comes from the central moments of orders 2 and 4 (no second sweep)
+ * while (l1 + epsilon) <= 256 (l2 + epsilon): its fp64 error grows as the square of that ratio and stays below 1e-11 there.  A
+ * thinner object -- at the limit a one-pixel diagonal line, whose cov is singular and whose inverse has entries 1 / epsilon --
+ * takes a per-pixel pass over labels_dev instead: each pixel's Mahalanobis value from exact integers, (m - 1)^2 added in uint64
+ * fixed point (rounding below 2^-26 per pixel).  Both passes are always launched, whatever the objects.  A thin object
+ * with n * max(w, h) >= 2^30 keeps the closed form.  Deterministic: pure functions of exact integers and order-free integer sums.
+ * Uses the context's object scratch (8 bytes per capacity row).  B*H*W < 2^31. */
+int mgu_object_shapes(mgu_ctx* ctx, const int32_t* labels_dev, int B, int H, int W, const int64_t* offsets_dev, int64_t capacity,
+                      const int64_t* area_dev, const int32_t* bbox_dev, const int64_t* sums_dev, const uint64_t* moments_dev, float epsilon,
+                      int min_pixels, float* centroid_dev, float* cov_dev, float* axes_dev, float* angle_dev, float* fill_dev, float* term_dev,
+                      uint8_t* status_dev, void* hip_stream);
+/* EllipticalShapeLoss over instances: loss_dev (one fp32) = the mean of term_dev[i] over the objects i < min(offsets[B], capacity)
+ * with status_dev[i] == 0 and, when class_dev != NULL, class_dev[i] == keep_class; 0 when there are none (shape_loss.py:180).  One
+ * workgroup adds the terms in a fixed order in fp64: bitwise repeatable. */
+int mgu_elliptical_shape_loss_objects(mgu_ctx* ctx, int B, const int64_t* offsets_dev, int64_t capacity, const float* term_dev,
+                                      const uint8_t* status_dev, const int64_t* class_dev, int64_t keep_class, float* loss_dev,
+                                      void* hip_stream);
+
 /* ---- test-time augmentation: flipped / rotated views of a batch and the mean of their softmaxes ----------------------------------
  * A view is the image flipped (flip bit 0: along W, torch.flip(x, (3,)); bit 1: along H, torch.flip(x, (2,))) and then turned r
  * quarter turns (torch.rot90(x, r, (2, 3))); r odd swaps H and W.  mgunet.tta.view_table lists the views of each transform set.

@@ -143,7 +143,26 @@ class EllipticalShapeLoss(nn.Module):
         super().__init__()
         self.epsilon = epsilon
 
-    def forward(self, segmentation_probs, object_masks_list=None):
+    def forward(self, segmentation_probs, object_masks_list=None, objects=None):
+        """The reference's two forms (object_masks_list given, or the whole class-1 foreground of each image as ONE object), plus
+        the per-instance form the reference asks for (shape_loss.py:42-48, :85-92) through `objects`: an ObjectTable runs the loss
+        over that table's objects; True labels the arg-max map of segmentation_probs (B, C, H, W) float32 with 8-connectivity and
+        background 0 (:86-91), keeps the objects of class 1 (:68) and runs the loss per instance.  Both use
+        mgunet.object_shapes: one pass over the label map, no dense masks.  Note that the reference's term is about 7/3 for a
+        perfect ellipse, not 0: see ObjectShapes."""
+        if objects is not None and objects is not False:
+            if object_masks_list is not None:
+                raise ValueError("pass object_masks_list or objects, not both")
+            from .objects import connected_components, object_shapes
+            if objects is True:
+                _lib.require_hip(segmentation_probs, "mgunet EllipticalShapeLoss")
+                if segmentation_probs.dim() != 4:
+                    raise ValueError("expected probabilities (B, C, H, W)")
+                if segmentation_probs.shape[1] <= 1:       # no foreground class (:63-70)
+                    return torch.tensor(0.0, device=segmentation_probs.device)
+                table = connected_components(_f32(segmentation_probs), connectivity=2, background=0)
+                return object_shapes(table, epsilon=self.epsilon).loss(keep_class=1)
+            return object_shapes(objects, epsilon=self.epsilon).loss()
         if object_masks_list is None:
             _lib.require_hip(segmentation_probs, "mgunet EllipticalShapeLoss")
             p = _f32(segmentation_probs)

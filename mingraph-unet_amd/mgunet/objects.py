@@ -3,8 +3,9 @@
 
 Connected components, per-object statistics and the reference's greedy box matching all run on the device (csrc/objects.hip);
 YieldEvaluator accumulates per-image counts and matching totals across batches without a host synchronisation, and the host only
-turns them into the reference's dictionary with the reference's own arithmetic (bitwise equal results).  There is no scipy or
-skimage dependency."""
+turns them into the reference's dictionary with the reference's own arithmetic (bitwise equal results).  object_shapes adds the
+per-object shape (csrc/shapes.hip): exact integer moments of the label map, a fitted ellipse and the per-instance term of
+EllipticalShapeLoss (model/unet/shape_loss.py:155-180).  There is no scipy or skimage dependency."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -29,22 +30,36 @@ class ObjectTable:
     bbox: torch.Tensor
     sums: torch.Tensor
 
-    def to_dicts(self, scores=None) -> list:
+    def to_dicts(self, scores=None, shapes=None) -> list:
         """The reference's per-image object lists: [[{'bbox': [xmin, ymin, xmax, ymax], 'class_id': int}, ...], ...].  With scores
         (one float per object in row order, e.g. mgunet.object_scores), every dict also carries 'confidence': float, the key
-        yield_estimation_metrics sorts predictions by."""
+        yield_estimation_metrics sorts predictions by.  With shapes (mgunet.object_shapes of this table), every dict also carries
+        'ellipse': {'center': [x, y], 'axes': [a, b], 'angle': radians, 'fill': f} and 'shape_term': float; both are None for an
+        object that was not analysed (shapes.status != 0)."""
         off = self.offsets.cpu().tolist()
         bbox, cls = self.bbox.cpu().tolist(), self.class_id.cpu().tolist()
-        if scores is None:
-            return [[{"bbox": bbox[i], "class_id": cls[i]} for i in range(off[b], off[b + 1])] for b in range(len(off) - 1)]
-        conf = scores.cpu().tolist() if isinstance(scores, torch.Tensor) else [float(v) for v in scores]
-        if len(conf) != len(cls):
-            raise ValueError(f"{len(conf)} scores for {len(cls)} objects")
-        return [[{"bbox": bbox[i], "class_id": cls[i], "confidence": conf[i]} for i in range(off[b], off[b + 1])]
-                for b in range(len(off) - 1)]
+        rows = [{"bbox": bbox[i], "class_id": cls[i]} for i in range(len(cls))]
+        if scores is not None:
+            conf = scores.cpu().tolist() if isinstance(scores, torch.Tensor) else [float(v) for v in scores]
+            if len(conf) != len(cls):
+                raise ValueError(f"{len(conf)} scores for {len(cls)} objects")
+            for d, v in zip(rows, conf):
+                d["confidence"] = v
+        if shapes is not None:
+            if shapes.status.numel() != len(cls):
+                raise ValueError(f"shapes of {shapes.status.numel()} objects for {len(cls)} objects")
+            cen, axes, st = shapes.centroid.cpu().tolist(), shapes.axes.cpu().tolist(), shapes.status.cpu().tolist()
+            ang, fill, term = shapes.angle.cpu().tolist(), shapes.fill.cpu().tolist(), shapes.term.cpu().tolist()
+            for i, d in enumerate(rows):
+                ok = st[i] == 0
+                d["ellipse"] = {"center": cen[i], "axes": axes[i], "angle": ang[i], "fill": fill[i]} if ok else None
+                d["shape_term"] = term[i] if ok else None
+        return [rows[off[b]:off[b + 1]] for b in range(len(off) - 1)]
 
     def masks(self) -> list:
-        """object_masks_list of EllipticalShapeLoss: per image, one bool (H, W) device mask per object, in label order."""
+        """object_masks_list of EllipticalShapeLoss: per image, one bool (H, W) device mask per object, in label order.  Dense: M
+        full-image masks and a host synchronisation.  For the loss and the shape of every object use mgunet.object_shapes(table)
+        (or EllipticalShapeLoss()(None, objects=table)), which reads the label map once and builds no masks."""
         counts = self.counts.cpu().tolist()
         return [[self.labels[b] == k for k in range(1, n + 1)] for b, n in enumerate(counts)]
 
@@ -105,6 +120,73 @@ def connected_components(x: torch.Tensor, connectivity: int = 2, background: int
     if N:
         _stats(labels, src, kind, B, H, W, C, offsets, N, cls, bbox, area, sums)
     return ObjectTable(labels, counts, offsets, cls, area, bbox, sums)
+
+
+@dataclass
+class ObjectShapes:
+    """Per-object shape of an ObjectTable, all on the device, rows in the table's object order.  centroid (N, 2) [x, y] in image
+    coordinates; cov (N, 3) [c_xx, c_xy, c_yy], the sample covariance of the pixel coordinates (divisor n - 1); axes (N, 2) [a, b],
+    the semi-axes in pixels of the uniformly filled ellipse with that covariance (2 sqrt of its eigenvalues, a >= b); angle (N),
+    radians, the major axis from +x towards +y; fill (N) = area / (pi a b); term (N), the reference's per-object
+    EllipticalShapeLoss value; all float32.  status (N) uint8: 0 analysed, 1 fewer than min_pixels pixels (skipped, as the reference
+    skips them), 2 too large for exact moments (area * (max(w, h) - 1)^4 >= 2^64).  Rows with status != 0 hold the centroid and
+    zeros.
+
+    `term` is the reference's formula, and it does NOT vanish for an ellipse: a perfectly filled one scores about 7/3 (2.33 for a
+    rasterised ellipse, 2.60 for a square, 2.53 for two touching discs).  To tell a single fruit from a merged cluster or a
+    leaf-shaped false positive, read `fill` (1 for a filled ellipse, lower for hollow, merged or ragged shapes) and `axes`."""
+    centroid: torch.Tensor
+    cov: torch.Tensor
+    axes: torch.Tensor
+    angle: torch.Tensor
+    fill: torch.Tensor
+    term: torch.Tensor
+    status: torch.Tensor
+    offsets: torch.Tensor      # the table's offsets (B + 1) and class_id (N): what loss() needs of it
+    class_id: torch.Tensor
+
+    @property
+    def valid(self) -> torch.Tensor:
+        return self.status == 0
+
+    def loss(self, keep_class=None) -> torch.Tensor:
+        """EllipticalShapeLoss over the instances: the mean of `term` over the analysed objects (of class keep_class, when given), 0
+        when there are none -- a 0-d float32 device tensor, summed on the device in a fixed order (no host synchronisation)."""
+        out = torch.empty((), device=self.term.device, dtype=torch.float32)
+        _lib.call("mgu_elliptical_shape_loss_objects", out.device, self.offsets.numel() - 1, self.offsets, self.status.numel(), self.term,
+                  self.status, None if keep_class is None else self.class_id, 0 if keep_class is None else int(keep_class), out)
+        return out
+
+
+def _shapes(labels, B, H, W, offsets, capacity, area, bbox, sums, epsilon, min_pixels, out=None, moments=None):
+    """Moments and shape of the objects at rows < capacity of the per-object arrays (capacity may be a worst-case bound: rows past
+    offsets[B] are left alone).  out: (centroid, cov, axes, angle, fill, term, status) buffers and moments: the int64 (capacity, 12)
+    power-sum buffer (uint64 bit patterns), each of capacity rows; allocated when None -- a caller with worst-case buffers keeps
+    them across calls, as YieldEvaluator keeps its own."""
+    dev = labels.device
+    if out is None:
+        mk = lambda shape, dt=torch.float32: torch.empty(shape, device=dev, dtype=dt)  # noqa: E731
+        out = (mk((capacity, 2)), mk((capacity, 3)), mk((capacity, 2)), mk(capacity), mk(capacity), mk(capacity), mk(capacity, torch.uint8))
+    if moments is None:
+        moments = torch.empty((capacity, 12), device=dev, dtype=torch.int64)
+    _lib.call("mgu_object_moments", dev, labels, B, H, W, offsets, int(capacity), bbox, moments)
+    _lib.call("mgu_object_shapes", dev, labels, B, H, W, offsets, int(capacity), area, bbox, sums, moments, float(epsilon), int(min_pixels), *out)
+    return out
+
+
+def object_shapes(table: ObjectTable, epsilon: float = 1e-6, min_pixels: int = 10) -> ObjectShapes:
+    """Shape of every object of `table` (mgunet.connected_components) straight from its label map: one pass accumulates exact
+    integer moments per object, one thread per object turns them into centroid, covariance, fitted ellipse, fill ratio and the
+    reference's per-object EllipticalShapeLoss term (model/unet/shape_loss.py:161-176; epsilon and min_pixels as there); the term of
+    a thin object, whose covariance is too ill-conditioned for that closed form, comes from a per-pixel pass.  A fixed number of
+    launches whatever the objects, no dense masks, no host synchronisation; results are bitwise repeatable."""
+    _lib.require_hip(table.labels, "object_shapes")
+    if epsilon < 0 or min_pixels < 0:
+        raise ValueError("epsilon and min_pixels must be >= 0")
+    B, H, W = table.labels.shape
+    N = table.area.numel()
+    out = _shapes(table.labels, B, H, W, table.offsets, N, table.area, table.bbox, table.sums, epsilon, min_pixels)
+    return ObjectShapes(*out, table.offsets, table.class_id)
 
 
 def _iou(b1, b2) -> float:
