@@ -150,9 +150,7 @@ using namespace mgu;
 using namespace mgud;
 
 namespace {
-inline int nb(int64_t work) { return (int)std::max<int64_t>(1, std::min<int64_t>(256 * 8, (work + 255) / 256)); }
 inline AugRot make_rot(int flip, const int32_t* fix) { return AugRot{flip ? 1 : 0, fix[0], fix[1], fix[2], fix[3], fix[4], fix[5]}; }
-inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 }  // namespace
 
 extern "C" {
@@ -177,7 +175,7 @@ int mgu_augment_flip_rotate(mgu_ctx* c, const float* img_in, float* img_out, int
   const AugStrides so{out_strides[0], out_strides[1], out_strides[2], out_strides[3]};
   AugFill fill{};
   for (int i = 0; i < C; ++i) fill.v[i] = fill_c[i];
-  const bool vec = so.w == 1 && W % 4 == 0 && so.h % 4 == 0 && so.c % 4 == 0 && so.b % 4 == 0 && al16(img_out) && (!mask_out || al16(mask_out));
+  const bool vec = so.w == 1 && W % 4 == 0 && so.h % 4 == 0 && so.c % 4 == 0 && so.b % 4 == 0 && aligned16(img_out) && (!mask_out || aligned16(mask_out));
   hipStream_t s = (hipStream_t)hip_stream;
   if (vec)
     hipLaunchKernelGGL(flip_rotate_nearest_kernel<true>, dim3(grid), dim3(256), 0, s, img_in, img_out, B, C, H, W, si, so, fill, mask_in,
@@ -203,7 +201,7 @@ int mgu_preprocess_image_u8_aug(mgu_ctx* c, const uint8_t* img_dev, int Hs, int 
   const uint8_t* cur = nullptr;
   int rc = preprocess_resize_u8(c, img_dev, Hs, Ws, channels, H, W, s, &cur);
   if (rc) return rc;
-  hipLaunchKernelGGL(to_tensor_normalize_aug_kernel, dim3(nb((int64_t)H * W * 3)), dim3(256), 0, s, cur, H, W, channels, bgr, mean3[0], mean3[1],
+  hipLaunchKernelGGL(to_tensor_normalize_aug_kernel, dim3(grid_for((int64_t)H * W * 3, 256, 256 * 8)), dim3(256), 0, s, cur, H, W, channels, bgr, mean3[0], mean3[1],
                      mean3[2], std3[0], std3[1], std3[2], make_rot(flip, fix6), (float*)out_dev, os_c, os_h, os_w);
   HIPCHK(c, hipGetLastError());
   return MGU_OK;
@@ -218,7 +216,7 @@ int mgu_preprocess_mask_u8_aug(mgu_ctx* c, const uint8_t* mask_dev, int Hs, int 
     return fail(c, MGU_ERR_INVALID, "preprocess_mask_aug: %d x %d is above %d pixels a side (PIL's float64 path, not reproduced)", H, W,
                 AUG_MAX_SIDE);
   HIPCHK(c, hipSetDevice(c->device));
-  hipLaunchKernelGGL(mask_nearest_aug_kernel, dim3(nb((int64_t)H * W)), dim3(256), 0, (hipStream_t)hip_stream, mask_dev, Hs, Ws, out_dev, H, W,
+  hipLaunchKernelGGL(mask_nearest_aug_kernel, dim3(grid_for((int64_t)H * W, 256, 256 * 8)), dim3(256), 0, (hipStream_t)hip_stream, mask_dev, Hs, Ws, out_dev, H, W,
                      num_classes, make_rot(flip, fix6), mask_fill);
   HIPCHK(c, hipGetLastError());
   return MGU_OK;

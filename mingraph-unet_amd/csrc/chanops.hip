@@ -12,7 +12,6 @@
 
 namespace mgu {
 
-typedef float f32x4c __attribute__((ext_vector_type(4)));
 
 template <int ACT>
 __global__ __launch_bounds__(256) void channel_affine_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ scale,
@@ -23,15 +22,15 @@ __global__ __launch_bounds__(256) void channel_affine_kernel(const float* __rest
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int cq = (int)(i % Q);
     const int64_t m = i / Q;
-    f32x4c v = *reinterpret_cast<const f32x4c*>(x + m * ldx + cq * 4);
-    if (scale) v *= *reinterpret_cast<const f32x4c*>(scale + cq * 4);
-    if (shift) v += *reinterpret_cast<const f32x4c*>(shift + cq * 4);
+    f32x4 v = *reinterpret_cast<const f32x4*>(x + m * ldx + cq * 4);
+    if (scale) v *= *reinterpret_cast<const f32x4*>(scale + cq * 4);
+    if (shift) v += *reinterpret_cast<const f32x4*>(shift + cq * 4);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       if (ACT == 1) v[e] = fmaxf(v[e], 0.f);
       if (ACT == 2) v[e] = 1.f / (1.f + expf(-v[e]));
     }
-    *reinterpret_cast<f32x4c*>(y + m * ldy + cq * 4) = v;
+    *reinterpret_cast<f32x4*>(y + m * ldy + cq * 4) = v;
   }
 }
 

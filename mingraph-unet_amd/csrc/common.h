@@ -3,7 +3,19 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "device.h"
+
 namespace mgu {
+
+// ---- host launch helpers ----
+// workgroups of a grid-stride kernel: one per `threads` items of work, at least 1, at most `cap`
+inline int grid_for(int64_t work, int threads, int cap) {
+  int64_t b = (work + threads - 1) / threads;
+  if (b < 1) b = 1;
+  if (b > cap) b = cap;
+  return (int)b;
+}
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // ---------------------------------------------------------------------------------------------
 // Implicit-GEMM descriptor.  D[m][n] = act(scale[n] * sum_k A(m,k) * Wp[n][k] + shift[n])

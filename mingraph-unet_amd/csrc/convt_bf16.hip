@@ -24,21 +24,6 @@ namespace mgu {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ f32x16 mfma_bf16(const u32x4 a, const u32x4 b, const f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-// LDS hand-off barrier without the vmcnt(0) of __syncthreads()'s fence (the prefetched loads stay in flight); the empty asm statements
-// are compiler-only ordering points for the LDS accesses on both sides
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0)
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 // Wf[n / 128][k / 16][(n / 32) & 3][lane = 32 * ((k / 8) & 1) + (n & 31)][k & 7] = bf16(w[ci = k][co][dy][dx]),  n = (dy*2+dx)*Cout + co:
 // the B fragment of v_mfma_f32_32x32x16_bf16, one 16-byte lane load
@@ -118,7 +103,7 @@ __global__ __launch_bounds__(256, 2) void convt2x2_bf16_kernel(const __bf16* __r
   load_b(0, 0);
   store_a(0);
   if (nk > 1) load_a(1);
-  lds_barrier();
+  lds_barrier_builtin();
   for (int s = 0; s < nk; ++s) {
     const int buf = s & 1;
 #pragma unroll
@@ -137,7 +122,7 @@ __global__ __launch_bounds__(256, 2) void convt2x2_bf16_kernel(const __bf16* __r
       store_a(buf ^ 1);                               // step s + 1 (in registers since the previous step) -> the idle buffer
       if (s + 2 < nk) load_a(s + 2);
     }
-    lds_barrier();
+    lds_barrier_builtin();
   }
   // ---- epilogue: bias, bf16, wave-private transpose, 16-byte stores.  (The barrier above: every wave has left the A tiles.)
   __bf16* const tile_out = out + (size_t)pix0 * ldout + coff;

@@ -27,36 +27,13 @@
 
 namespace mgu {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
-
-// exact three-way split of two fp32 values into packed bf16 pieces (low half: a, high half: b)
-__device__ __forceinline__ void split3_pack(const float a, const float b, unsigned& p0, unsigned& p1, unsigned& p2) {
-  const unsigned ua = __float_as_uint(a), ub = __float_as_uint(b);
-  p0 = __builtin_amdgcn_perm(ub, ua, 0x07060302u);
-  const float ra = a - __uint_as_float(ua & 0xffff0000u), rb = b - __uint_as_float(ub & 0xffff0000u);
-  const unsigned va = __float_as_uint(ra), vb = __float_as_uint(rb);
-  p1 = __builtin_amdgcn_perm(vb, va, 0x07060302u);
-  const float sa = ra - __uint_as_float(va & 0xffff0000u), sb = rb - __uint_as_float(vb & 0xffff0000u);
-  p2 = __builtin_amdgcn_perm(__float_as_uint(sb), __float_as_uint(sa), 0x07060302u);
-}
-
-__device__ __forceinline__ f32x16 mfma_bf16(const u32x4 a, const u32x4 b, const f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 
 // weights in fragment order: pack_convt_x3_body (pack_small.h)
 __global__ void pack_convt_x3_kernel(const float* __restrict__ w, uint16_t* __restrict__ Wx, int Cin, int Cout) {
   pack_convt_x3_body(w, Wx, Cin, Cout, 0, blockIdx.x, gridDim.x);
 }
-
-// LDS hand-off barrier without the workgroup fence of __syncthreads(), which makes hipcc wait vmcnt(0): the prefetched loads of the next
-// steps would be drained at every step (wino_f32.hip: lds_barrier)
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // MODE 0: the forward layer.  Rows = input pixels (contiguous NHWC rows, K = Cin), columns n = (dy*2+dx)*Cout + co, pixel-shuffle store.
 // MODE 1: its data gradient (loss.backward() through unet_decoder.py:36): din[(y,x)][ci] = sum_{q,co} dout[(2y+qy, 2x+qx)][co] w[ci][co][q].

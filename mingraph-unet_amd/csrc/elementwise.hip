@@ -5,8 +5,6 @@
 
 namespace mgu {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // 16-byte chunk <-> fp32 lanes for the two storage types (fp32: 4 elements, bf16: 8 elements)
 template <typename T> struct Chunk;
@@ -35,13 +33,6 @@ template <> struct Chunk<__bf16> {
   }
 };
 
-static inline int nblocks(int64_t work, int threads, int cap = 256 * 16) {
-  int64_t b = (work + threads - 1) / threads;
-  if (b < 1) b = 1;
-  if (b > cap) b = cap;
-  return (int)b;
-}
-
 // ---- input: arbitrary-stride (n,c,y,x) fp32 -> NHWC with channels zero padded to Cp (Cp % 4 == 0) ----
 template <typename T>
 __global__ void pack_input_kernel(const float* __restrict__ x, T* __restrict__ out, int64_t npix_total, int C, int Cp, int H,
@@ -68,10 +59,10 @@ hipError_t launch_pack_input(const float* x, void* out, int dtype, int B, int C,
                              int64_t sh, int64_t sw, hipStream_t s) {
   const int64_t npix = (int64_t)B * H * W;
   if (dtype == 0)
-    hipLaunchKernelGGL(pack_input_kernel<float>, dim3(nblocks(npix * (Cp >> 2), 256)), dim3(256), 0, s, x, (float*)out, npix, C,
+    hipLaunchKernelGGL(pack_input_kernel<float>, dim3(grid_for(npix * (Cp >> 2), 256, 256 * 16)), dim3(256), 0, s, x, (float*)out, npix, C,
                        Cp, H, W, sn, sc, sh, sw);
   else
-    hipLaunchKernelGGL(pack_input_kernel<__bf16>, dim3(nblocks(npix * (Cp >> 3), 256)), dim3(256), 0, s, x, (__bf16*)out, npix,
+    hipLaunchKernelGGL(pack_input_kernel<__bf16>, dim3(grid_for(npix * (Cp >> 3), 256, 256 * 16)), dim3(256), 0, s, x, (__bf16*)out, npix,
                        C, Cp, H, W, sn, sc, sh, sw);
   return hipGetLastError();
 }
@@ -106,10 +97,10 @@ hipError_t launch_maxpool2(const void* in, int ldin, void* out, int dtype, int B
   const int64_t total = (int64_t)B * (H >> 1) * (W >> 1) * (C / vec);
   if (total == 0) return hipSuccess;
   if (dtype == 0)
-    hipLaunchKernelGGL(maxpool2_kernel<float>, dim3(nblocks(total, 256)), dim3(256), 0, s, (const float*)in, ldin, (float*)out, B,
+    hipLaunchKernelGGL(maxpool2_kernel<float>, dim3(grid_for(total, 256, 256 * 16)), dim3(256), 0, s, (const float*)in, ldin, (float*)out, B,
                        H, W, C);
   else
-    hipLaunchKernelGGL(maxpool2_kernel<__bf16>, dim3(nblocks(total, 256)), dim3(256), 0, s, (const __bf16*)in, ldin, (__bf16*)out,
+    hipLaunchKernelGGL(maxpool2_kernel<__bf16>, dim3(grid_for(total, 256, 256 * 16)), dim3(256), 0, s, (const __bf16*)in, ldin, (__bf16*)out,
                        B, H, W, C);
   return hipGetLastError();
 }
@@ -236,7 +227,7 @@ __global__ void pack_conv_w_kernel(const float* __restrict__ w, T* __restrict__ 
 }
 
 hipError_t launch_pack_conv_w(const float* w, void* wp, int dtype, int Cout, int Cin, int Cp, int KS, int Kp, hipStream_t s) {
-  dim3 g(nblocks((int64_t)Cout * Kp, 256)), b(256);
+  dim3 g(grid_for((int64_t)Cout * Kp, 256, 256 * 16)), b(256);
   if (dtype == 0) hipLaunchKernelGGL(pack_conv_w_kernel<float>, g, b, 0, s, w, (float*)wp, Cout, Cin, Cp, KS, Kp);
   else hipLaunchKernelGGL(pack_conv_w_kernel<__bf16>, g, b, 0, s, w, (__bf16*)wp, Cout, Cin, Cp, KS, Kp);
   return hipGetLastError();
@@ -254,7 +245,7 @@ __global__ void pack_convt_w_kernel(const float* __restrict__ w, T* __restrict__
 }
 
 hipError_t launch_pack_convt_w(const float* w, void* wp, int dtype, int Cin, int Cout, int Kp, hipStream_t s) {
-  dim3 g(nblocks((int64_t)4 * Cout * Kp, 256)), b(256);
+  dim3 g(grid_for((int64_t)4 * Cout * Kp, 256, 256 * 16)), b(256);
   if (dtype == 0) hipLaunchKernelGGL(pack_convt_w_kernel<float>, g, b, 0, s, w, (float*)wp, Cin, Cout, Kp);
   else hipLaunchKernelGGL(pack_convt_w_kernel<__bf16>, g, b, 0, s, w, (__bf16*)wp, Cin, Cout, Kp);
   return hipGetLastError();
@@ -326,7 +317,7 @@ hipError_t launch_conv1x1_head(const void* in, int dtype, int ldin, int C, const
                                int ldout, int ncls, int64_t npix, hipStream_t s) {
   const int vec = dtype == 0 ? 4 : 8;
   if ((C % vec) || (ldin % vec) || ncls < 1 || ncls > 4) return hipErrorInvalidValue;
-  const int blocks = nblocks(npix * 8, 256, 256 * 32);
+  const int blocks = grid_for(npix * 8, 256, 256 * 32);
 #define MGU_HEAD(NC)                                                                                                         \
   do {                                                                                                                       \
     if (dtype == 0)                                                                                                          \
@@ -490,7 +481,7 @@ __global__ void argmax_kernel(const float* __restrict__ logits, int64_t npix, in
 }
 
 hipError_t launch_argmax(const float* logits, int64_t npix, int C, int64_t* pred, hipStream_t s) {
-  hipLaunchKernelGGL(argmax_kernel, dim3(nblocks(npix, 256)), dim3(256), 0, s, logits, npix, C, pred);
+  hipLaunchKernelGGL(argmax_kernel, dim3(grid_for(npix, 256, 256 * 16)), dim3(256), 0, s, logits, npix, C, pred);
   return hipGetLastError();
 }
 

@@ -4,7 +4,7 @@
 // The VALU kernel it replaces on these shapes (conv3x3_first_kernel, elementwise.hip) spends 27 x 32 multiply-adds per pixel on the
 // vector unit: 46 us of pure issue at 8 x 512^2, for a layer whose 0.3 GB of traffic take ~50 us (fp32) / ~30 us (bf16 storage).
 // Here the layer is a GEMM with K = 27 padded to 32: M = pixels, N = 32 output channels, two k steps of v_mfma_f32_32x32x16_bf16.
-//   * fp32 storage: both operands split exactly into three bf16 pieces (x3.h), six piece products per k step -- an fp32 GEMM in
+//   * fp32 storage: both operands split exactly into three bf16 pieces (device.h), six piece products per k step -- an fp32 GEMM in
 //     accuracy, like the Winograd layers; bf16 storage: the activations ARE bf16 (one piece), the weights keep their three pieces
 //     (three products), as accurate as the fp32-weight VALU kernel it replaces.
 //   * a workgroup owns a 16 x 16 pixel patch: the 18 x 18 halo of packed pixels (one 16-byte load each: NHWC4 fp32 or NHWC8 bf16,
@@ -17,7 +17,6 @@
 
 #include "common.h"
 #include "pack_small.h"
-#include "x3.h"
 
 namespace mgu {
 
@@ -139,7 +138,7 @@ __global__ __launch_bounds__(256, 4) void conv3x3_first_mfma_kernel(const T* __r
           pa[0][e] = __builtin_amdgcn_perm(__float_as_uint(v[8 * s + 2 * e + 1]), __float_as_uint(v[8 * s + 2 * e]), 0x07060302u);
         }
       }
-      if constexpr (F32) {   // smallest products first (x3.h)
+      if constexpr (F32) {   // smallest products first (device.h)
         t16 = mfma_bf16(pa[2], bw[s][0], t16);
         t16 = mfma_bf16(pa[0], bw[s][2], t16);
         t16 = mfma_bf16(pa[1], bw[s][1], t16);

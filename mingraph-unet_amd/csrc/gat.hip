@@ -21,25 +21,6 @@
 
 namespace mgu {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned enc_ordered(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float dec_ordered(unsigned u) {
-  return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
-}
-
-__device__ __forceinline__ int graph_of(const int32_t* __restrict__ gp, int G, int node) {
-  if (!gp || G <= 1) return 0;
-  int lo = 0, hi = G;  // gp[lo] <= node < gp[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (gp[mid] <= node) lo = mid; else hi = mid;
-  }
-  return lo;
-}
 
 // ---- node -> graph id table (one coalesced kernel instead of a dependent binary search per wavefront) ----
 __global__ void gat_node_graph_kernel(const int32_t* __restrict__ gp, int G, int nodes_per_graph, int N,
@@ -229,7 +210,7 @@ __global__ __launch_bounds__(256) void gat_aggregate_kernel(const float* __restr
       um = max(um, (unsigned)__builtin_amdgcn_update_dpp(0, (int)um, 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
       um = max(um, (unsigned)__builtin_amdgcn_update_dpp(0, (int)um, 0x141, 0xF, 0xF, true));   // row_half_mirror
       um = max(um, (unsigned)__builtin_amdgcn_update_dpp(0, (int)um, 0x140, 0xF, 0xF, true));   // row_mirror
-      const float pgm = um ? gat_dec_ordered(um) : -INFINITY;
+      const float pgm = um ? dec_ordered(um) : -INFINITY;
 #pragma unroll
       for (int rb = 0; rb < R; rb += RB) {
         // -- producer: lane (h, p) evaluates the weight of pair p = (row rb + pr, slot pk) for head h --

@@ -29,7 +29,6 @@
 
 namespace mgu {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __global__ __launch_bounds__(256) void gatb_edge_keys_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, int N,
                                                              int* __restrict__ keys, int* __restrict__ vals, int* __restrict__ tgt) {
@@ -243,14 +242,14 @@ __global__ __launch_bounds__(256) void gatb_max_term_kernel(const float* __restr
   }
   const float gm = (float)red[0], m = gm_f[g * heads + h];
   if (gm == 0.f) return;   // block-uniform
-  // arg-max edges: compared in the ENCODED domain the forward's reduction works in (gat_enc_ordered: the maximum went through
+  // arg-max edges: compared in the ENCODED domain the forward's reduction works in (enc_ordered: the maximum went through
   // encode -> atomicMax -> decode, a bijection on the bit pattern, so equal bits here == the edge that won there)
-  const unsigned m_enc = gat_enc_ordered(m);
+  const unsigned m_enc = enc_ordered(m);
   const int e0 = rowptr[n0], e1 = rowptr[n1];
   int mine = 0;
   for (int k = e0 + t; k < e1; k += 256) {
     const float z = st[(size_t)col[k] * H2 + h] + st[(size_t)tgt_e[k] * H2 + heads + h];
-    mine += (gat_enc_ordered(z > 0.f ? z : slope * z) == m_enc) ? 1 : 0;
+    mine += (enc_ordered(z > 0.f ? z : slope * z) == m_enc) ? 1 : 0;
   }
   if (mine) atomicAdd(&cnt, mine);
   __syncthreads();
@@ -264,7 +263,7 @@ __global__ __launch_bounds__(256) void gatb_max_term_kernel(const float* __restr
   if (cnt == 1) {   // the usual case: one arg-max edge, one writer per element
     for (int k = e0 + t; k < e1; k += 256) {
       const float z = st[(size_t)col[k] * H2 + h] + st[(size_t)tgt_e[k] * H2 + heads + h];
-      if (gat_enc_ordered(z > 0.f ? z : slope * z) == m_enc) {
+      if (enc_ordered(z > 0.f ? z : slope * z) == m_enc) {
         const float v = share * (z > 0.f ? 1.f : slope);
         gz_e[(size_t)k * heads + h] += v;
         gt[(size_t)tgt_e[k] * heads + h] += v;
@@ -273,7 +272,7 @@ __global__ __launch_bounds__(256) void gatb_max_term_kernel(const float* __restr
   } else if (t == 0) {   // ties: one thread walks the graph's edges in order, so ties that share a target add in a fixed order
     for (int k = e0; k < e1; ++k) {
       const float z = st[(size_t)col[k] * H2 + h] + st[(size_t)tgt_e[k] * H2 + heads + h];
-      if (gat_enc_ordered(z > 0.f ? z : slope * z) == m_enc) {
+      if (enc_ordered(z > 0.f ? z : slope * z) == m_enc) {
         const float v = share * (z > 0.f ? 1.f : slope);
         gz_e[(size_t)k * heads + h] += v;
         gt[(size_t)tgt_e[k] * heads + h] += v;

@@ -21,16 +21,9 @@
 #include "common.h"
 #include <atomic>
 #include "gat_common.h"
-#include "x3.h"
 
 namespace mgu {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float gf_dec_ordered(unsigned u) {
-  return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
-}
 
 // ---- st AND the per-(graph, head) max of the attention logits in ONE launch -------------------------------------------
 // The reference takes exp(e - max over ALL edges of the graph) (graph_attention.py:86).  The max needs s of an edge's SOURCE,
@@ -40,11 +33,7 @@ __device__ __forceinline__ float gf_dec_ordered(unsigned u) {
 // wave-reduces and issues one order-encoded atomicMax per (graph, head).  That removes the separate gat_st and gat_edge_max
 // launches and the dependent st[col[k]] round trip of the latter: a patch GAT layer is 2 launches instead of 4.
 // The node -> graph id (binary search over graph_ptr through the scalar cache) is written to node_graph for the aggregate kernel.
-__device__ __forceinline__ unsigned gf_enc_ordered(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
+// graph_of (device.h) without its `!gp || G <= 1` guard: the guard changes the instructions of both kernels below
 __device__ __forceinline__ int gf_graph_of(const int32_t* __restrict__ gp, int G, int node) {
   int lo = 0, hi = G;  // gp[lo] <= node < gp[hi]
   while (hi - lo > 1) {
@@ -226,7 +215,7 @@ __global__ __launch_bounds__(256) void gat_prep_kernel(const float* __restrict__
     }
   } else if (b < 2 * heads + nb_wx) {
     // Wx[item = h * NT + nt][ks][piece][lane (hk = lane >> 5, n = lane & 31)][8 bf16]: the B fragment of v_mfma_f32_32x32x16_bf16 of
-    // W[h * Fh + 32 nt + n][16 ks + 8 hk + e], split exactly into three bf16 pieces (x3.h); one thread per (item, ks, lane)
+    // W[h * Fh + 32 nt + n][16 ks + 8 hk + e], split exactly into three bf16 pieces (device.h); one thread per (item, ks, lane)
     const int i = (b - 2 * heads) * 256 + t;
     const int nks = Fin / 16, nnt = Fh / 32;
     if (i < heads * nnt * nks * 64) {
@@ -262,7 +251,7 @@ hipError_t launch_gat_prep(const float* W, const float* a, float* wa, unsigned* 
 //   * ONE softmax weight per (edge, head): lane q of a node's lane group evaluates slot q of the trip -- exp(LeakyReLU(s_src + t_tgt)
 //     - max_graph) for the H heads -- and the group shares the weights (and the source ids) through an LDS line; gat_fused_kernel
 //     evaluated every weight in all FIN/4 lanes of the group;
-//   * the linear layer on v_mfma_f32_32x32x16_bf16 with the exact three-way bf16 operand split of the Winograd kernels (x3.h): an
+//   * the linear layer on v_mfma_f32_32x32x16_bf16 with the exact three-way bf16 operand split of the Winograd kernels (device.h): an
 //     fp32 GEMM in accuracy, 6 x 32 cycles per 16 input features instead of 8 x 64 on the fp32 MFMA.  W_h^T pieces are packed in
 //     fragment order by gat_prep_kernel and stay in REGISTERS across the tiles of a persistent workgroup;
 //   * persistent workgroups (a few per CU) walking node tiles, so the weight pieces, the per-graph maxima and the launch overhead
@@ -270,7 +259,8 @@ hipError_t launch_gat_prep(const float* W, const float* a, float* wa, unsigned* 
 // Dependent global round trips per tile: rowptr -> col -> {x row, s} (three; the rows and the attention scalars travel together).
 // Workgroup = 4 wavefronts on a 32-node tile: gather by (node, 16-byte row slice) lanes, then the (head, n tile) GEMM items are
 // dealt to the waves, then ELU and the concat store or the head mean through LDS (fixed order: bitwise reproducible).
-// Workgroup barrier of gat_fused2_kernel.  With this toolchain __syncthreads() is `s_waitcnt lgkmcnt(0); s_barrier` -- the workgroup-
+// Workgroup barrier of gat_fused2_kernel: lds_barrier_fenced (device.h), i.e. __syncthreads().
+// With this toolchain __syncthreads() is `s_waitcnt lgkmcnt(0); s_barrier` -- the workgroup-
 // scope fence no longer drains vmcnt, so the prefetched rows of the next tile and the output stores of this one stay in flight across
 // it.  (An inline-asm barrier of the same two instructions gave the GEMM behind barrier A a different instruction order, and THAT
 // order produced one wrong row in about every fourth call on the configs[3] graphs -- single rows off by 1e-4 .. 1e-3, never with
@@ -286,7 +276,6 @@ hipError_t launch_gat_prep(const float* W, const float* a, float* wa, unsigned* 
 // s_barrier, fence): the asm statement's "memory" clobber orders only the compiler's view of memory, while the fences also pin
 // the backend's waitcnt bookkeeping to the barrier.  The hand-off is therefore kept on the fenced form BY CONSTRUCTION, not by
 // measurement; the cause of the round-4 failure at the ISA level remains unidentified (recorded as such in NOTES.md).
-__device__ __forceinline__ void lds_barrier() { __syncthreads(); }
 
 template <int FIN, int NT, int H>
 __global__ __launch_bounds__(256, FIN == 32 ? 3 : 2) void gat_fused2_kernel(const float* __restrict__ x, const float* __restrict__ st,
@@ -311,8 +300,8 @@ __global__ __launch_bounds__(256, FIN == 32 ? 3 : 2) void gat_fused2_kernel(cons
   constexpr int NGE = H < NG ? H : NG;     // groups that hold a head
   static_assert(H == 1 || H == 2 || H == 4, "heads");
   static_assert(NT == 1 || NT == 2, "n tiles");
-  typedef float fH __attribute__((ext_vector_type(4)));   // H <= 4 head values of a node / edge (unused tail lanes stay 0)
-  // aggregated input rows, already split into the three exact bf16 pieces of the GEMM's A operand (x3.h): [head][piece][node][FIN
+  using fH = f32x4;   // H <= 4 head values of a node / edge (unused tail lanes stay 0)
+  // aggregated input rows, already split into the three exact bf16 pieces of the GEMM's A operand (device.h): [head][piece][node][FIN
   // bf16 + 16 bytes of pad] -- the split is done ONCE by the lane that produced the values (both n-tile waves of a head read them)
   constexpr int APITCH = FIN * 2 + 16;   // bytes per node row: 16-byte reads one node apart fall on distinct banks
   __shared__ __attribute__((aligned(16))) unsigned char agg_s[H][3][32 * APITCH];
@@ -326,7 +315,6 @@ __global__ __launch_bounds__(256, FIN == 32 ? 3 : 2) void gat_fused2_kernel(cons
     if constexpr (H == 4) {
       v = *reinterpret_cast<const fH*>(p);
     } else if constexpr (H == 2) {
-      typedef float f32x2 __attribute__((ext_vector_type(2)));
       const f32x2 t = *reinterpret_cast<const f32x2*>(p);
       v[0] = t[0], v[1] = t[1];
     } else {
@@ -524,7 +512,6 @@ __global__ __launch_bounds__(256, FIN == 32 ? 3 : 2) void gat_fused2_kernel(cons
         unsigned p0a, p1a, p2a, p0b, p1b, p2b;
         split3_pack(a[0], a[1], p0a, p1a, p2a);
         split3_pack(a[2], a[3], p0b, p1b, p2b);
-        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
         *reinterpret_cast<u32x2*>(&agg_s[h][0][nl * APITCH + 8 * q]) = u32x2{p0a, p0b};
         *reinterpret_cast<u32x2*>(&agg_s[h][1][nl * APITCH + 8 * q]) = u32x2{p1a, p1b};
         *reinterpret_cast<u32x2*>(&agg_s[h][2][nl * APITCH + 8 * q]) = u32x2{p2a, p2b};
@@ -536,7 +523,7 @@ __global__ __launch_bounds__(256, FIN == 32 ? 3 : 2) void gat_fused2_kernel(cons
 #pragma unroll
     for (int p = 0; p < PASSES; ++p) m_nxt.rs[p] = m_nn.rs[p], m_nxt.deg[p] = m_nn.deg[p];
     meta_t(tile_n0(ti + 2 * wgx), m_nxt);   // (its t one tile ahead)
-    lds_barrier();   // (A) the aggregate tile is complete; every wave has left the previous tile's exchange reads
+    lds_barrier_fenced();   // (A) the aggregate tile is complete; every wave has left the previous tile's exchange reads
     // ---- (32 nodes x FIN) . W_h^T (FIN x 32) per (head, n tile) item on the bf16 matrix cores, exact three-way splits --------
     f32x16 c[HPW];
 #pragma unroll
@@ -597,7 +584,7 @@ __global__ __launch_bounds__(256, FIN == 32 ? 3 : 2) void gat_fused2_kernel(cons
           }
         }
       }
-      lds_barrier();   // (B) every wave has read its A operands: the next tile's aggregate may overwrite them
+      lds_barrier_fenced();   // (B) every wave has read its A operands: the next tile's aggregate may overwrite them
     } else {
       // mean over heads (:158): the heads of this wave are added in registers (fixed order); the NGE head groups meet in LDS as rows
       // [n tile][group][node][32 channels + pad], and thread (node, channel quad) adds the groups in the order 0 .. NGE - 1 and
@@ -617,7 +604,7 @@ __global__ __launch_bounds__(256, FIN == 32 ? 3 : 2) void gat_fused2_kernel(cons
           __builtin_amdgcn_sched_barrier(0);
         }
       }
-      lds_barrier();   // (B)
+      lds_barrier_fenced();   // (B)
       constexpr float invH = 1.f / H;
       const int row = et >> 3, qd = et & 7;        // 32 rows x 8 channel quads = 256 threads
 #pragma unroll

@@ -20,14 +20,11 @@
 //     channel pitch/offset so encoder outputs and the pixel-shuffled ConvTranspose outputs land
 //     directly in the two halves of the decoder's concat buffer (torch.cat never materialises).
 #include "common.h"
-#include "x3.h"
 #include <algorithm>
 #include <type_traits>
 
 namespace mgu {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 const Tuning& default_tuning() {
   static const Tuning t;
@@ -50,7 +47,6 @@ hipError_t ensure_dyn_lds(const void* func, size_t bytes, bool (&done)[64]) {
 // fp32 accumulation (v_mfma_f32_32x32x16_bf16).  All staging moves raw 16-byte chunks (4 floats or 8 bf16); an LDS
 // row holds NP such chunks of a pixel / output channel plus one chunk of padding (pitch 144 B for NP = 8, 80 B for
 // NP = 4: both map any 16 rows of a ds_read_b128 lane group to 16 distinct 4-bank slots).
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 template <typename T> struct Elem;
 template <> struct Elem<float> { static constexpr int VEC = 4; };
 template <> struct Elem<__bf16> { static constexpr int VEC = 8; };
@@ -476,17 +472,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(const IgemmDesc d,
     ++li;
   };
   // workgroup barrier.  GLDS: the raw form -- __syncthreads() drains vmcnt while an LDS-DMA is in flight (its fence), i.e. the weight
-  // tile requested at the top of the step would be waited for at once; the waits for the DMA are counted by hand below
-  // The raw form carries no fence of its own (s_barrier is IntrNoMem), so the two compiler-only ordering points keep every LDS access
-  // of the source on its side of the barrier -- the fragment reads of Bs / Hs must not rise above it, the halo stores must not sink
-  // below it -- without emitting a wait: an empty asm with a "memory" clobber generates no instruction and, unlike a workgroup fence,
-  // no vmcnt(0).
+  // tile requested at the top of the step would be waited for at once; the waits for the DMA are counted by hand below.
+  // lds_barrier_builtin (device.h) carries no fence; its compiler-only ordering points keep the fragment reads of Bs / Hs from rising
+  // above it and the halo stores from sinking below it without emitting a wait.
   auto wg_barrier = [&]() {
     if constexpr (GLDS) {
-      asm volatile("" ::: "memory");
-      __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0)
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
+      lds_barrier_builtin();
     } else {
       __syncthreads();
     }
@@ -525,7 +516,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(const IgemmDesc d,
     using SetLoad = std::integral_constant<int, DEEPH ? decltype(par_c)::value : 0>;        // receives item + 2 (item + 1)
     using SetStore = std::integral_constant<int, DEEPH ? (decltype(par_c)::value ^ 1) : 0>;  // holds item + 1
     const int cnext = c + 1 == nchunks ? 0 : c + 1;   // chunk of the next item
-    x3_static_for<0, SPI>([&](auto tap_c) {
+    static_for<0, SPI>([&](auto tap_c) {
       constexpr int tap = decltype(tap_c)::value;
       if constexpr (GLDS) {
         // this step's weight tile has landed: everything of this wave older than the operations issued BEHIND its DMA is complete.

@@ -166,7 +166,7 @@ __global__ __launch_bounds__(256) void sobel_mag2_kernel(const uint8_t* __restri
     local = max(local, (unsigned)m);
   }
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) local = max(local, (unsigned)__shfl_xor((int)local, off));
+  for (int off = 32; off > 0; off >>= 1) local = max(local, (unsigned)__shfl_xor((int)local, off));   // unsigned max: not wave_max
   if ((threadIdx.x & 63) == 0 && local) atomicMax(max2, local);
 }
 __global__ __launch_bounds__(256) void sobel_norm_kernel(const int* __restrict__ mag2, const unsigned* __restrict__ max2, int64_t n,
@@ -284,10 +284,6 @@ __global__ __launch_bounds__(256) void region_map_gather_kernel(const float* __r
 using namespace mgu;
 using namespace mgud;
 
-namespace {
-inline int nb(int64_t work) { return (int)std::max<int64_t>(1, std::min<int64_t>(256 * 8, (work + 255) / 256)); }
-}
-
 extern "C" {
 
 int mgu_resize_bilinear_nhwc(mgu_ctx* c, const void* in_dev, int ld_in, int B, int Hi, int Wi, int Cc, void* out_dev, int ld_out, int c_off,
@@ -298,7 +294,7 @@ int mgu_resize_bilinear_nhwc(mgu_ctx* c, const void* in_dev, int ld_in, int B, i
     return fail(c, MGU_ERR_INVALID, "bad resize_bilinear args (C, ld_in, ld_out, c_off multiples of 4)");
   HIPCHK(c, hipSetDevice(c->device));
   // aten area_pixel_compute_scale: scale = in / out in the accumulation type (float)
-  hipLaunchKernelGGL(resize_bilinear_kernel, dim3(nb((int64_t)B * Ho * Wo * (Cc >> 2))), dim3(256), 0, (hipStream_t)hip_stream,
+  hipLaunchKernelGGL(resize_bilinear_kernel, dim3(grid_for((int64_t)B * Ho * Wo * (Cc >> 2), 256, 256 * 8)), dim3(256), 0, (hipStream_t)hip_stream,
                      (const float*)in_dev, ld_in, B, Hi, Wi, Cc, (float*)out_dev, ld_out, c_off, Ho, Wo, (float)Hi / (float)Ho,
                      (float)Wi / (float)Wo);
   HIPCHK(c, hipGetLastError());
@@ -335,14 +331,14 @@ int preprocess_resize_u8(mgu_ctx* c, const uint8_t* img_dev, int Hs, int Ws, int
   int curW = Ws;
   if (need_h) {   // horizontal pass first, as ImagingResample
     uint8_t* tmp = (uint8_t*)(ws + o_tmp);
-    hipLaunchKernelGGL(pil_resample_pass_kernel, dim3(nb((int64_t)W * Hs * channels)), dim3(256), 0, s, cur, tmp, W, Hs, channels,
+    hipLaunchKernelGGL(pil_resample_pass_kernel, dim3(grid_for((int64_t)W * Hs * channels, 256, 256 * 8)), dim3(256), 0, s, cur, tmp, W, Hs, channels,
                        (int64_t)channels, (int64_t)Ws * channels, (int64_t)channels, (int64_t)W * channels, tab, tab + th.bounds.size(), th.ksize);
     cur = tmp, curW = W;
   }
   if (need_v) {
     uint8_t* fin = (uint8_t*)(ws + o_fin);
     const int* tb = tab + th.bounds.size() + th.kk.size();
-    hipLaunchKernelGGL(pil_resample_pass_kernel, dim3(nb((int64_t)H * curW * channels)), dim3(256), 0, s, cur, fin, H, curW, channels,
+    hipLaunchKernelGGL(pil_resample_pass_kernel, dim3(grid_for((int64_t)H * curW * channels, 256, 256 * 8)), dim3(256), 0, s, cur, fin, H, curW, channels,
                        (int64_t)curW * channels, (int64_t)channels, (int64_t)curW * channels, (int64_t)channels, tb, tb + tv.bounds.size(), tv.ksize);
     cur = fin;
   }
@@ -363,7 +359,7 @@ int mgu_preprocess_image_u8(mgu_ctx* c, const uint8_t* img_dev, int Hs, int Ws, 
   const uint8_t* cur = nullptr;
   int rc = preprocess_resize_u8(c, img_dev, Hs, Ws, channels, H, W, s, &cur);
   if (rc) return rc;
-  hipLaunchKernelGGL(to_tensor_normalize_kernel, dim3(nb((int64_t)H * W * 3)), dim3(256), 0, s, cur, H, W, channels, bgr, mean3[0], mean3[1],
+  hipLaunchKernelGGL(to_tensor_normalize_kernel, dim3(grid_for((int64_t)H * W * 3, 256, 256 * 8)), dim3(256), 0, s, cur, H, W, channels, bgr, mean3[0], mean3[1],
                      mean3[2], std3[0], std3[1], std3[2], (float*)out_dev, os_c, os_h, os_w);
   HIPCHK(c, hipGetLastError());
   return MGU_OK;
@@ -373,7 +369,7 @@ int mgu_preprocess_mask_u8(mgu_ctx* c, const uint8_t* mask_dev, int Hs, int Ws, 
   if (!c) return MGU_ERR_INVALID;
   if (!mask_dev || !out_dev || Hs < 1 || Ws < 1 || H < 1 || W < 1 || num_classes < 1) return fail(c, MGU_ERR_INVALID, "bad preprocess_mask args");
   HIPCHK(c, hipSetDevice(c->device));
-  hipLaunchKernelGGL(mask_nearest_kernel, dim3(nb((int64_t)H * W)), dim3(256), 0, (hipStream_t)hip_stream, mask_dev, Hs, Ws, out_dev, H, W,
+  hipLaunchKernelGGL(mask_nearest_kernel, dim3(grid_for((int64_t)H * W, 256, 256 * 8)), dim3(256), 0, (hipStream_t)hip_stream, mask_dev, Hs, Ws, out_dev, H, W,
                      num_classes);
   HIPCHK(c, hipGetLastError());
   return MGU_OK;
@@ -389,8 +385,8 @@ int mgu_sobel_edges_u8(mgu_ctx* c, const uint8_t* rgb_dev, int H, int W, uint8_t
   unsigned* max2 = (unsigned*)c->imgws;
   int* mag2 = (int*)((char*)c->imgws + 256);
   HIPCHK(c, hipMemsetAsync(max2, 0, sizeof(unsigned), s));
-  hipLaunchKernelGGL(sobel_mag2_kernel, dim3(nb((int64_t)H * W)), dim3(256), 0, s, rgb_dev, H, W, mag2, max2);
-  hipLaunchKernelGGL(sobel_norm_kernel, dim3(nb((int64_t)H * W)), dim3(256), 0, s, mag2, max2, (int64_t)H * W, out_dev);
+  hipLaunchKernelGGL(sobel_mag2_kernel, dim3(grid_for((int64_t)H * W, 256, 256 * 8)), dim3(256), 0, s, rgb_dev, H, W, mag2, max2);
+  hipLaunchKernelGGL(sobel_norm_kernel, dim3(grid_for((int64_t)H * W, 256, 256 * 8)), dim3(256), 0, s, mag2, max2, (int64_t)H * W, out_dev);
   HIPCHK(c, hipGetLastError());
   return MGU_OK;
 }
@@ -406,9 +402,9 @@ int mgu_equalize_hist_rgb_u8(mgu_ctx* c, const uint8_t* rgb_dev, int H, int W, u
   uint8_t* lut = (uint8_t*)(hist + 256);
   const int64_t n = (int64_t)H * W;
   HIPCHK(c, hipMemsetAsync(hist, 0, 256 * sizeof(unsigned), s));
-  hipLaunchKernelGGL(yuv_hist_kernel, dim3(std::min(1024, nb(n))), dim3(256), 0, s, rgb_dev, n, hist);
+  hipLaunchKernelGGL(yuv_hist_kernel, dim3(std::min(1024, grid_for(n, 256, 256 * 8))), dim3(256), 0, s, rgb_dev, n, hist);
   hipLaunchKernelGGL(equalize_lut_kernel, dim3(1), dim3(64), 0, s, hist, n, lut);
-  hipLaunchKernelGGL(equalize_apply_kernel, dim3(nb(n)), dim3(256), 0, s, rgb_dev, n, lut, out_dev);
+  hipLaunchKernelGGL(equalize_apply_kernel, dim3(grid_for(n, 256, 256 * 8)), dim3(256), 0, s, rgb_dev, n, lut, out_dev);
   HIPCHK(c, hipGetLastError());
   return MGU_OK;
 }
@@ -432,7 +428,7 @@ int mgu_region_map_gather_nhwc(mgu_ctx* c, const float* table_dev, int R, int D,
     return fail(c, MGU_ERR_INVALID, "bad region_map_gather args (D, ld_out, c_off multiples of 4)");
   HIPCHK(c, hipSetDevice(c->device));
   if (npix == 0) return MGU_OK;
-  hipLaunchKernelGGL(region_map_gather_kernel, dim3(nb(npix * (D >> 2))), dim3(256), 0, (hipStream_t)hip_stream, table_dev, R, D, ids_dev, npix,
+  hipLaunchKernelGGL(region_map_gather_kernel, dim3(grid_for(npix * (D >> 2), 256, 256 * 8)), dim3(256), 0, (hipStream_t)hip_stream, table_dev, R, D, ids_dev, npix,
                      out_dev, ld_out, c_off);
   HIPCHK(c, hipGetLastError());
   return MGU_OK;
@@ -444,7 +440,7 @@ int mgu_colorize_labels(mgu_ctx* c, const int64_t* labels_dev, int64_t npix, con
   if (!labels_dev || !palette_dev || !vis_dev || npix < 0 || num_classes < 1) return fail(c, MGU_ERR_INVALID, "bad colorize args");
   HIPCHK(c, hipSetDevice(c->device));
   if (npix == 0) return MGU_OK;
-  hipLaunchKernelGGL(colorize_kernel, dim3(nb(npix)), dim3(256), 0, (hipStream_t)hip_stream, labels_dev, npix, palette_dev, num_classes, vis_dev,
+  hipLaunchKernelGGL(colorize_kernel, dim3(grid_for(npix, 256, 256 * 8)), dim3(256), 0, (hipStream_t)hip_stream, labels_dev, npix, palette_dev, num_classes, vis_dev,
                      labels_u8_dev);
   HIPCHK(c, hipGetLastError());
   return MGU_OK;

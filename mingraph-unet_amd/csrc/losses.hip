@@ -16,23 +16,6 @@ namespace mgu {
 
 constexpr int LOSS_BLOCKS = 1024;   // upper bound of reduction workgroups (partial records)
 
-// fold K doubles of every thread of a 256-thread workgroup; thread 0 gets the totals
-template <int K>
-__device__ __forceinline__ void block_fold(double (&v)[K], double* sh /* [4][K] */) {
-#pragma unroll
-  for (int k = 0; k < K; ++k)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0)
-#pragma unroll
-    for (int k = 0; k < K; ++k) sh[wave * K + k] = v[k];
-  __syncthreads();
-  if (threadIdx.x == 0)
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = sh[k] + sh[K + k] + sh[2 * K + k] + sh[3 * K + k];
-}
-
 // ---- total variation ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void tv_partial_kernel(const float* __restrict__ x, int B, int Cc, int H, int W, int64_t sn, int64_t sc,
                                                          int64_t sh_, int64_t sw, double* __restrict__ part) {
@@ -384,12 +367,11 @@ int loss_scratch(mgu_ctx* c, size_t doubles, double** out) {
   *out = (double*)c->lossws;
   return MGU_OK;
 }
-inline int nblocks(int64_t work) { return (int)std::max<int64_t>(1, std::min<int64_t>(LOSS_BLOCKS, (work + 1023) / 1024)); }
 
 template <int MODE>
 int shape_loss(mgu_ctx* c, const void* src, int nobj, int H, int W, int Cc, int64_t sn, int64_t sc, int64_t sp, float eps, float* loss,
                hipStream_t s) {
-  const int nb = std::min(256, nblocks((int64_t)H * W));
+  const int nb = std::min(256, grid_for((int64_t)H * W, 1024, LOSS_BLOCKS));
   double* ws;
   int rc = loss_scratch(c, (size_t)nobj * nb * 6 + (size_t)nobj * 8 + (size_t)nobj * nb, &ws);
   if (rc) return rc;
@@ -412,7 +394,7 @@ int mgu_tv_loss(mgu_ctx* c, const void* x_dev, int B, int Cc, int H, int W, int6
   if (!x_dev || !loss_dev || B < 1 || Cc < 1 || H < 2 || W < 2) return fail(c, MGU_ERR_INVALID, "bad tv_loss args (H, W >= 2)");
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)hip_stream;
-  const int nb = nblocks((int64_t)B * Cc * H * W);
+  const int nb = grid_for((int64_t)B * Cc * H * W, 1024, LOSS_BLOCKS);
   double* ws;
   int rc = loss_scratch(c, (size_t)nb * 2, &ws);
   if (rc) return rc;
@@ -430,7 +412,7 @@ int mgu_dice_loss(mgu_ctx* c, const void* logits_dev, const int64_t* labels_dev,
     return fail(c, MGU_ERR_INVALID, "bad dice_loss args (1 <= num_classes <= 8)");
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)hip_stream;
-  const int nb = std::min(128, nblocks(HW));
+  const int nb = std::min(128, grid_for(HW, 1024, LOSS_BLOCKS));
   double* ws;
   int rc = loss_scratch(c, (size_t)B * nb * 24, &ws);
   if (rc) return rc;
@@ -459,7 +441,7 @@ int mgu_tv_loss_backward(mgu_ctx* c, const void* x_dev, int B, int Cc, int H, in
   if (!c) return MGU_ERR_INVALID;
   if (!x_dev || !dx_dev || B < 1 || Cc < 1 || H < 2 || W < 2) return fail(c, MGU_ERR_INVALID, "bad tv_loss_backward args (H, W >= 2)");
   HIPCHK(c, hipSetDevice(c->device));
-  const int nb = nblocks((int64_t)B * Cc * H * W);
+  const int nb = grid_for((int64_t)B * Cc * H * W, 1024, LOSS_BLOCKS);
   // weight * (h_tv / count_h + w_tv / count_w) / B, each difference d contributing 2 d to its end points
   const float kh = (float)(2.0 * weight / ((double)(H - 1) * W) / B), kw = (float)(2.0 * weight / ((double)H * (W - 1)) / B);
   hipLaunchKernelGGL(tv_bwd_kernel, dim3(nb), dim3(256), 0, (hipStream_t)hip_stream, (const float*)x_dev, B, Cc, H, W, xs_n, xs_c, xs_h,
@@ -476,7 +458,7 @@ int mgu_dice_loss_backward(mgu_ctx* c, const void* logits_dev, const int64_t* la
     return fail(c, MGU_ERR_INVALID, "bad dice_loss_backward args (1 <= num_classes <= 8)");
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)hip_stream;
-  const int nb = std::min(128, nblocks(HW));
+  const int nb = std::min(128, grid_for(HW, 1024, LOSS_BLOCKS));
   double* ws;
   int rc = loss_scratch(c, (size_t)B * nb * 24 + (size_t)B * 8, &ws);   // partial records + the coefficient table (floats)
   if (rc) return rc;
@@ -512,7 +494,7 @@ int mgu_feature_consistency_loss_backward(mgu_ctx* c, const void* f_unet_dev, co
     return fail(c, MGU_ERR_INVALID, "bad feature_consistency_loss_backward args (D a multiple of 4)");
   HIPCHK(c, hipSetDevice(c->device));
   const int64_t rows = (int64_t)B * N;
-  hipLaunchKernelGGL(featcons_bwd_kernel, dim3(nblocks(rows * 16)), dim3(256), 0, (hipStream_t)hip_stream, (const float*)f_unet_dev,
+  hipLaunchKernelGGL(featcons_bwd_kernel, dim3(grid_for(rows * 16, 1024, LOSS_BLOCKS)), dim3(256), 0, (hipStream_t)hip_stream, (const float*)f_unet_dev,
                      (const float*)f_graph_dev, (const float*)y_dev, rows, D, margin, grad_scale / (float)B, grad_scale_dev,
                      (float*)d_f_unet_dev, (float*)d_f_graph_dev);
   HIPCHK(c, hipGetLastError());
@@ -539,7 +521,7 @@ int mgu_feature_consistency_loss(mgu_ctx* c, const void* f_unet_dev, const void*
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)hip_stream;
   const int64_t rows = (int64_t)B * N;
-  const int nb = nblocks(rows * 16);
+  const int nb = grid_for(rows * 16, 1024, LOSS_BLOCKS);
   double* ws;
   int rc = loss_scratch(c, (size_t)nb, &ws);
   if (rc) return rc;

@@ -18,12 +18,6 @@ namespace mgu {
 
 constexpr int NCUT_MAX_K = 16;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
 // softmax over the K segment logits of a node (:190) and the hard label train_end_to_end.py:356 takes from it
 __global__ void ncut_softmax_kernel(const float* __restrict__ logits, int N, int K, float* __restrict__ soft,
                                     int32_t* __restrict__ hard) {
@@ -108,7 +102,6 @@ __global__ __launch_bounds__(256) void ncut_node_kernel(const float* __restrict_
 // D % 4 == 0 (every caller on the path: 64 features): SIXTEEN lanes own a node, each holding four features, so a wavefront
 // walks four nodes at once and a 256-byte feature row is one 16-byte load per lane.  The kernel is a chain of dependent
 // gathers (rowptr -> col -> rows); four nodes per wave quadruple the loads in flight per wave.
-typedef float f32x4n __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(256) void ncut_node16_kernel(const float* __restrict__ F, int N, int D, const float* __restrict__ P, int K,
                                                           const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                           double* __restrict__ acc) {
@@ -131,13 +124,13 @@ __global__ __launch_bounds__(256) void ncut_node16_kernel(const float* __restric
 #pragma unroll
     for (int u = 0; u < 4; ++u) t[u] = (e0 + eb + u < e1) ? col[e0 + eb + u] : (live ? i : 0);
     for (int c = gl * 4; c < D; c += 64) {
-      const f32x4n x = *reinterpret_cast<const f32x4n*>(fi + c);
-      f32x4n y[4];
+      const f32x4 x = *reinterpret_cast<const f32x4*>(fi + c);
+      f32x4 y[4];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) y[u] = *reinterpret_cast<const f32x4n*>(F + (size_t)t[u] * D + c);
+      for (int u = 0; u < 4; ++u) y[u] = *reinterpret_cast<const f32x4*>(F + (size_t)t[u] * D + c);
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        const f32x4n d = x - y[u];
+        const f32x4 d = x - y[u];
         d2[u] += d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3];
       }
     }

@@ -283,23 +283,6 @@ __global__ __launch_bounds__(OB_THREADS) void stats_init_kernel(const long long*
   }
 }
 
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-__device__ __forceinline__ int wave_min(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off));
-  return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off));
-  return v;
-}
-
 // one thread per pixel; the lanes of one object are summed inside the wave (up to LEADER_ROUNDS objects), the rest add directly
 template <int KIND>
 __global__ __launch_bounds__(OB_THREADS) void stats_kernel(const int* __restrict__ labels, const void* __restrict__ src, int C, int W, int64_t HW,
@@ -444,8 +427,6 @@ __global__ __launch_bounds__(64) void match_kernel(const long long* __restrict__
   }
 }
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace
 }  // namespace mgu
 
@@ -473,14 +454,15 @@ int mgu_connected_components(mgu_ctx* c, const void* src_dev, int src_kind, int 
     return MGU_OK;
   }
   const int64_t nch = (HW + CHUNK - 1) / CHUNK;
-  const size_t bP = align256((size_t)n * 4), bA = min_area > 0 ? align256((size_t)n * 4) : 0, bC = align256((size_t)nch * B * 4);
-  int rc = ensure(c, &c->objws, &c->objws_bytes, bP + bA + bC + (size_t)nch * B * 8);
+  Carve cv;
+  const size_t oP = cv.take((size_t)n * 4), oA = min_area > 0 ? cv.take((size_t)n * 4) : 0, oC = cv.take((size_t)nch * B * 4);
+  int rc = ensure(c, &c->objws, &c->objws_bytes, cv.off + (size_t)nch * B * 8);   // the last region ends the buffer: no padding behind it
   if (rc) return rc;
   char* ws = (char*)c->objws;
-  int* P = (int*)ws;
-  unsigned* area = min_area > 0 ? (unsigned*)(ws + bP) : nullptr;
-  int* cnt = (int*)(ws + bP + bA);
-  long long* choff = (long long*)(ws + bP + bA + bC);
+  int* P = (int*)(ws + oP);
+  unsigned* area = min_area > 0 ? (unsigned*)(ws + oA) : nullptr;
+  int* cnt = (int*)(ws + oC);
+  long long* choff = (long long*)(ws + cv.off);
   long long* counts = (long long*)counts_dev;
   long long* offsets = (long long*)offsets_dev;
   const long long bg = background, ncls = num_classes;

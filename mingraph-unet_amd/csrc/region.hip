@@ -11,7 +11,6 @@
 
 namespace mgu {
 
-typedef float f32x4r __attribute__((ext_vector_type(4)));
 
 // one workgroup per (image, segment); thread = channel quad x patch lane
 __global__ __launch_bounds__(256) void region_pool_kernel(const float* __restrict__ feats, const int32_t* __restrict__ hard, int Np, int D,
@@ -19,40 +18,40 @@ __global__ __launch_bounds__(256) void region_pool_kernel(const float* __restric
   extern __shared__ float red[];   // [lanes][D]
   const int b = blockIdx.x / K, k = blockIdx.x - b * K;
   const int q = D >> 2, cq = threadIdx.x % q, pl = threadIdx.x / q, npl = 256 / q;
-  f32x4r acc = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   int cnt = 0;
   if (pl < npl) {
     // four patches per trip, labels and rows loaded unconditionally (independent addresses: one round trip per trip)
     for (int p0 = pl; p0 < Np; p0 += 4 * npl) {
       int h[4];
-      f32x4r f[4];
+      f32x4 f[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int p = min(p0 + u * npl, Np - 1);
         h[u] = hard[(size_t)b * Np + p];
-        f[u] = *reinterpret_cast<const f32x4r*>(feats + ((size_t)b * Np + p) * D + cq * 4);
+        f[u] = *reinterpret_cast<const f32x4*>(feats + ((size_t)b * Np + p) * D + cq * 4);
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const bool in = (p0 + u * npl < Np) && h[u] == k;
-        acc += in ? f[u] : f32x4r{0.f, 0.f, 0.f, 0.f};
+        acc += in ? f[u] : f32x4{0.f, 0.f, 0.f, 0.f};
         cnt += in ? 1 : 0;
       }
     }
   }
   __shared__ int cnts[256];
   cnts[threadIdx.x] = (cq == 0 && pl < npl) ? cnt : 0;
-  if (pl < npl) *reinterpret_cast<f32x4r*>(red + (size_t)pl * D + cq * 4) = acc;
+  if (pl < npl) *reinterpret_cast<f32x4*>(red + (size_t)pl * D + cq * 4) = acc;
   __syncthreads();
   if (threadIdx.x < q) {
-    f32x4r s = {0.f, 0.f, 0.f, 0.f};
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
     int n = 0;
     for (int l = 0; l < npl; ++l) {
-      s += *reinterpret_cast<const f32x4r*>(red + (size_t)l * D + threadIdx.x * 4);
+      s += *reinterpret_cast<const f32x4*>(red + (size_t)l * D + threadIdx.x * 4);
       n += cnts[l * q];
     }
     const float inv = n > 0 ? 1.f / (float)n : 0.f;   // mask_k.sum() > 0 (:371-372)
-    *reinterpret_cast<f32x4r*>(out + ((size_t)b * K + k) * D + threadIdx.x * 4) = s * inv;
+    *reinterpret_cast<f32x4*>(out + ((size_t)b * K + k) * D + threadIdx.x * 4) = s * inv;
   }
 }
 
@@ -65,9 +64,9 @@ __global__ __launch_bounds__(256) void region_fuse_kernel(const float* __restric
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int cq = (int)(i % Q);
     const int64_t pix = i / Q;
-    f32x4r v;
+    f32x4 v;
     if (cq * 4 < Cu) {
-      v = *reinterpret_cast<const f32x4r*>(fu + pix * Cu + cq * 4);
+      v = *reinterpret_cast<const f32x4*>(fu + pix * Cu + cq * 4);
     } else {
       const int x = (int)(pix % W);
       const int64_t r = pix / W;
@@ -75,9 +74,9 @@ __global__ __launch_bounds__(256) void region_fuse_kernel(const float* __restric
       // torch 'nearest': src = min(floor(dst * (in / out)), in - 1), the scale formed in fp32 (:416-420)
       const int py = min((int)floorf((float)y * sy), nph - 1), px = min((int)floorf((float)x * sx), npw - 1);
       const int lbl = hard[(size_t)b * nph * npw + py * npw + px];
-      v = *reinterpret_cast<const f32x4r*>(emb + ((size_t)b * K + lbl) * D + (cq * 4 - Cu));
+      v = *reinterpret_cast<const f32x4*>(emb + ((size_t)b * K + lbl) * D + (cq * 4 - Cu));
     }
-    __builtin_nontemporal_store(v, reinterpret_cast<f32x4r*>(out + pix * (Cu + D) + cq * 4));   // write-once stream: keep it out of L2
+    __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(out + pix * (Cu + D) + cq * 4));   // write-once stream: keep it out of L2
   }
 }
 

@@ -19,23 +19,6 @@ constexpr int SE_TARGET_BLOCKS = 256;      // about one workgroup per CU: few at
 constexpr int SE_HIST_CELLS = 8192;        // LDS histogram up to C = 90 (32 KB); above: atomics straight to the caller's buffer
 constexpr long long IGNORE_INDEX = -100;   // nn.CrossEntropyLoss default
 
-// fold K doubles of every thread of a 256-thread workgroup; thread 0 gets the totals (fixed order)
-template <int K>
-__device__ __forceinline__ void fold_doubles(double (&v)[K], double* sh /* [4][K] */) {
-#pragma unroll
-  for (int k = 0; k < K; ++k)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0)
-#pragma unroll
-    for (int k = 0; k < K; ++k) sh[wave * K + k] = v[k];
-  __syncthreads();
-  if (threadIdx.x == 0)
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = sh[k] + sh[K + k] + sh[2 * K + k] + sh[3 * K + k];
-}
-
 // ---- C == 2 (configs/model.yaml): 16-byte loads, two pixels per lane and load -----------------------------------------------------
 // LOSS 0: counts (+ predictions) only, no exp/log.  1: + cross-entropy partials.  2: + dice partials.
 // Record of workgroup (b, blk): [ce_sum, counted, I0, I1, P0, P1, T0, T1] (LOSS 2) or [ce_sum, counted] (LOSS 1).
@@ -118,7 +101,7 @@ __global__ __launch_bounds__(SE_THREADS) void seg_eval_c2_kernel(const float* __
       if (a.bad && err_word) atomicOr(err_word, 1);
       unsigned cnt[4];
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
+      for (int k = 0; k < 4; ++k) {   // written out: wave_sum (device.h) here changes this kernel's register allocation
         cnt[k] = a.n[k];
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) cnt[k] += __shfl_xor(cnt[k], off);
@@ -127,7 +110,7 @@ __global__ __launch_bounds__(SE_THREADS) void seg_eval_c2_kernel(const float* __
 #pragma unroll
         for (int k = 0; k < 4; ++k) shn[tid >> 6][k] = cnt[k];
       double v[5] = {a.ce, a.I0, a.I1, a.P0, a.P1};
-      fold_doubles<5>(v, shd);   // its barrier also publishes shn
+      block_fold<5>(v, shd);   // its barrier also publishes shn
       if (tid == 0) {
         unsigned long long t[4];
         for (int k = 0; k < 4; ++k) t[k] = (unsigned long long)shn[0][k] + shn[1][k] + shn[2][k] + shn[3][k];
@@ -244,7 +227,7 @@ __global__ __launch_bounds__(SE_THREADS) void seg_eval_generic_kernel(const floa
     }
     if (LOSS > 0) {
       if (bad && err_word) atomicOr(err_word, 1);
-      fold_doubles<K>(v, shd);
+      block_fold<K>(v, shd);
       if (tid == 0) {
         const int S = LOSS == 2 ? 2 + 3 * C : 2;
         double* r = part + ((size_t)b * nb + blk) * S;
@@ -270,7 +253,7 @@ __global__ __launch_bounds__(SE_THREADS) void seg_eval_final_kernel(const double
   double v[2] = {0.0, 0.0};
   const int64_t nrec = (int64_t)B * nb;
   for (int64_t r = tid; r < nrec; r += SE_THREADS) v[0] += part[r * S], v[1] += part[r * S + 1];
-  fold_doubles<2>(v, shd);
+  block_fold<2>(v, shd);
   if (dice)
     for (int64_t t = tid; t < (int64_t)B * C; t += SE_THREADS) {
       const int64_t b = t / C;
@@ -317,7 +300,6 @@ __global__ __launch_bounds__(SE_THREADS) void confusion_kernel(const long long* 
   }
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 }  // namespace mgu

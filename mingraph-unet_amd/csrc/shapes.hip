@@ -28,12 +28,6 @@ __global__ __launch_bounds__(SH_THREADS) void moments_init_kernel(const long lon
   for (int64_t i = (int64_t)blockIdx.x * SH_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * SH_THREADS) mom[i] = 0;
 }
 
-__device__ __forceinline__ u64 wave_sum64(u64 v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
 // a lane adds its sums to object o on its own (zero sums -- a one-pixel object has only those -- cost nothing)
 __device__ __forceinline__ void flush_direct(u64* __restrict__ mom, long long o, const u64* acc) {
 #pragma unroll
@@ -88,7 +82,7 @@ __global__ __launch_bounds__(SH_THREADS) void moments_kernel(const int* __restri
     if (lane == 0) sh_obj[wave] = lo;
 #pragma unroll
     for (int k = 0; k < NMOM; ++k) {
-      const u64 s = wave_sum64(mine ? acc[k] : 0ull);
+      const u64 s = wave_sum(mine ? acc[k] : 0ull);
       if (lane == 0) sh_sum[wave][k] = s;
     }
     if (mine) pending = false;
@@ -114,7 +108,7 @@ __global__ __launch_bounds__(SH_THREADS) void moments_kernel(const int* __restri
     const bool mine = pending && cur == lo;
 #pragma unroll
     for (int k = 0; k < NMOM; ++k) {
-      const u64 s = wave_sum64(mine ? acc[k] : 0ull);
+      const u64 s = wave_sum(mine ? acc[k] : 0ull);
       if (lane == leader && s) atomicAdd(&mom[lo * NMOM + k], s);
     }
     if (mine) pending = false;
@@ -280,7 +274,7 @@ __global__ __launch_bounds__(SH_THREADS) void residual_kernel(const int* __restr
     const int leader = __ffsll((long long)act) - 1;
     const long long lo = __shfl(obj, leader);
     const bool mine = pending && obj == lo;
-    const u64 sum = wave_sum64(mine ? qv : 0ull);
+    const u64 sum = wave_sum(mine ? qv : 0ull);
     if (lane == leader) atomicAdd(&racc[lo], sum);
     if (mine) pending = false;
   }

@@ -7,14 +7,6 @@
 
 namespace mgu {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-static inline int nblk(int64_t work, int threads, int cap = 256 * 8) {
-  int64_t b = (work + threads - 1) / threads;
-  if (b < 1) b = 1;
-  if (b > cap) b = cap;
-  return (int)b;
-}
 
 // ------------------------------------------------------------------------------------------------
 // Per-channel reductions over the M pixels of an NHWC tensor.  Thread (q = t % (C/4), pl = t / (C/4))
@@ -341,14 +333,14 @@ __global__ void bn_apply_relu_pool_kernel(const float* __restrict__ z, const flo
 hipError_t launch_bn_apply_relu_pool(const float* z, const float* scale, const float* shift, float* y, int ldy, float* pooled, int B, int H,
                                      int W, int C, hipStream_t s) {
   if ((H & 1) || (W & 1) || (C & 3)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(bn_apply_relu_pool_kernel, dim3(nblk((int64_t)B * (H >> 1) * (W >> 1) * (C >> 2), 256)), dim3(256), 0, s, z, scale,
+  hipLaunchKernelGGL(bn_apply_relu_pool_kernel, dim3(grid_for((int64_t)B * (H >> 1) * (W >> 1) * (C >> 2), 256, 256 * 8)), dim3(256), 0, s, z, scale,
                      shift, y, ldy, pooled, B, H, W, C);
   return hipGetLastError();
 }
 
 hipError_t launch_bn_apply_relu(const float* z, const float* scale, const float* shift, float* y, int ldy, int64_t M, int C,
                                 hipStream_t s) {
-  hipLaunchKernelGGL(bn_apply_relu_kernel, dim3(nblk(M * (C >> 2), 256)), dim3(256), 0, s, z, scale, shift, y, ldy, M, C);
+  hipLaunchKernelGGL(bn_apply_relu_kernel, dim3(grid_for(M * (C >> 2), 256, 256 * 8)), dim3(256), 0, s, z, scale, shift, y, ldy, M, C);
   return hipGetLastError();
 }
 
@@ -393,7 +385,7 @@ hipError_t launch_maxpool2_bwd_add(const float* y, int ldy, const float* dpool, 
                                    int C, hipStream_t s) {
   const int64_t total = (int64_t)B * (H >> 1) * (W >> 1) * (C >> 2);
   if (total == 0) return hipSuccess;
-  hipLaunchKernelGGL(maxpool2_bwd_add_kernel, dim3(nblk(total, 256)), dim3(256), 0, s, y, ldy, dpool, dskip, ldd, B, H, W, C);
+  hipLaunchKernelGGL(maxpool2_bwd_add_kernel, dim3(grid_for(total, 256, 256 * 8)), dim3(256), 0, s, y, ldy, dpool, dskip, ldd, B, H, W, C);
   return hipGetLastError();
 }
 
@@ -407,7 +399,7 @@ __global__ void zero_pad_region_kernel(float* __restrict__ buf, int ld, int coff
   }
 }
 hipError_t launch_zero_pad_region(float* buf, int ld, int coff, int C, int B, int H, int W, int h2, int w2, hipStream_t s) {
-  hipLaunchKernelGGL(zero_pad_region_kernel, dim3(nblk((int64_t)B * H * W, 256)), dim3(256), 0, s, buf, ld, coff, C, B, H, W, h2, w2);
+  hipLaunchKernelGGL(zero_pad_region_kernel, dim3(grid_for((int64_t)B * H * W, 256, 256 * 8)), dim3(256), 0, s, buf, ld, coff, C, B, H, W, h2, w2);
   return hipGetLastError();
 }
 
@@ -480,8 +472,8 @@ hipError_t launch_ce(const float* logits, const int64_t* labels, int64_t M, int 
                      float* dlogits, int ldd, double* acc, int* err_word, float* loss_out, hipStream_t s) {
   hipError_t e = hipMemsetAsync(acc, 0, 2 * sizeof(double), s);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(ce_count_kernel, dim3(nblk(M, 256, 1024)), dim3(256), 0, s, labels, M, C, ignore_index, acc, err_word);
-  hipLaunchKernelGGL(ce_fwd_bwd_kernel, dim3(nblk(M, 256, 2048)), dim3(256), 0, s, logits, labels, M, C, ignore_index, grad_scale,
+  hipLaunchKernelGGL(ce_count_kernel, dim3(grid_for(M, 256, 1024)), dim3(256), 0, s, labels, M, C, ignore_index, acc, err_word);
+  hipLaunchKernelGGL(ce_fwd_bwd_kernel, dim3(grid_for(M, 256, 2048)), dim3(256), 0, s, logits, labels, M, C, ignore_index, grad_scale,
                      dlogits, ldd, acc);
   hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(1), 0, s, acc, loss_out);
   return hipGetLastError();
@@ -495,7 +487,7 @@ __global__ void pack_dgrad_w_kernel(const float* __restrict__ w, float* __restri
   pack_dgrad_w_body(w, wp, Cout, Cin, Cop, KS, Kp, blockIdx.x, gridDim.x);
 }
 hipError_t launch_pack_dgrad_w(const float* w, float* wp, int Cout, int Cin, int Cop, int KS, int Kp, hipStream_t s) {
-  hipLaunchKernelGGL(pack_dgrad_w_kernel, dim3(nblk((int64_t)Cin * Kp, 256)), dim3(256), 0, s, w, wp, Cout, Cin, Cop, KS, Kp);
+  hipLaunchKernelGGL(pack_dgrad_w_kernel, dim3(grid_for((int64_t)Cin * Kp, 256, 256 * 8)), dim3(256), 0, s, w, wp, Cout, Cin, Cop, KS, Kp);
   return hipGetLastError();
 }
 // ConvTranspose2d dgrad: dprev[m][ci] = sum_{q,co} dup[pix(m,q)][co] * W[ci][co][q]: panel [Cin][Kp], k = q*Cout + co
@@ -508,7 +500,7 @@ __global__ void pack_convt_dgrad_w_kernel(const float* __restrict__ w, float* __
   }
 }
 hipError_t launch_pack_convt_dgrad_w(const float* w, float* wp, int Cin, int Cout, int Kp, hipStream_t s) {
-  hipLaunchKernelGGL(pack_convt_dgrad_w_kernel, dim3(nblk((int64_t)Cin * Kp, 256)), dim3(256), 0, s, w, wp, Cin, Cout, Kp);
+  hipLaunchKernelGGL(pack_convt_dgrad_w_kernel, dim3(grid_for((int64_t)Cin * Kp, 256, 256 * 8)), dim3(256), 0, s, w, wp, Cin, Cout, Kp);
   return hipGetLastError();
 }
 
@@ -668,7 +660,7 @@ hipError_t launch_adam(float* p, const float* g, float* m, float* v, int64_t n, 
                        float wd, int step, float grad_scale, hipStream_t s) {
   const float bc1 = 1.f - powf(b1, (float)step);
   const float bc2 = 1.f - powf(b2, (float)step);
-  hipLaunchKernelGGL(adam_kernel, dim3(nblk(n, 256)), dim3(256), 0, s, p, g, m, v, n, lr, b1, b2, eps, wd, bc1, sqrtf(bc2),
+  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n, 256, 256 * 8)), dim3(256), 0, s, p, g, m, v, n, lr, b1, b2, eps, wd, bc1, sqrtf(bc2),
                      grad_scale);
   return hipGetLastError();
 }
@@ -689,7 +681,7 @@ __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, f
 }
 hipError_t launch_sgd(float* p, const float* g, float* buf, int64_t n, float lr, float momentum, float wd, int step, float grad_scale,
                       hipStream_t s) {
-  hipLaunchKernelGGL(sgd_kernel, dim3(nblk(n, 256)), dim3(256), 0, s, p, g, buf, n, lr, momentum, wd, step == 1 ? 1 : 0, grad_scale);
+  hipLaunchKernelGGL(sgd_kernel, dim3(grid_for(n, 256, 256 * 8)), dim3(256), 0, s, p, g, buf, n, lr, momentum, wd, step == 1 ? 1 : 0, grad_scale);
   return hipGetLastError();
 }
 

@@ -16,8 +16,6 @@
 
 namespace mgu {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int WG_MK = 32;    // pixels reduced per pipeline step
 constexpr int WG_BK = 128;   // k columns per workgroup

@@ -10,7 +10,6 @@
 
 namespace mgu {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ---- 1x1, N = 4:  thread = (pixel lane, channel quad) ------------------------------------------------------------
 template <int QC>   // channel quads per pixel (Cp / 4): 8 or 16

@@ -26,33 +26,15 @@
 //     small LDS exchange, and lanes store one channel each (32 lanes = one 128-byte line of a pixel).
 #include "common.h"
 #include "pack_small.h"
-#include "x3.h"
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 
 namespace mgu {
 
-// a * b + c as ONE v_fma_f32 the backend cannot pair with a neighbour into v_pk_fma_f32
-__device__ __forceinline__ float scalar_fma(float a, float b, float c) {
-  float d;
-  asm("v_fma_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-  return d;
-}
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
 
-// Workgroup barrier for LDS hand-offs ONLY.  __syncthreads() is a workgroup-scope fence + barrier, and the fence makes
-// hipcc wait for vmcnt(0): every outstanding global load AND store (CDNA4 counts stores in vmcnt).  In this kernel that
-// meant each epilogue barrier waited for the round trip of the output stores just issued, and each chunk barrier for the
-// weight-fragment prefetch.  LDS operations of a wave complete in order, so lgkmcnt(0) before s_barrier is all a producer
-// needs; the "memory" clobber keeps the compiler from moving LDS accesses across it.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// Barriers: lds_barrier (device.h), for LDS hand-offs ONLY.  With __syncthreads() each epilogue barrier of these kernels waited for
+// the round trip of the output stores just issued, and each chunk barrier for the weight-fragment prefetch.
 
 // max(x, 0) as ONE v_max_f32 (fmaxf() costs two: the backend first quiets a possible signalling NaN with v_max_f32 x, x, x).  Same
 // result as fmaxf for every input, NaN included (the instruction returns the other operand).
@@ -105,7 +87,6 @@ __device__ __forceinline__ void pack_wino_w_body(const float* __restrict__ w, fl
     // 16-byte lane entry of every (component, piece) fragment; lane & 31 = n & 31 and lane >> 5 = the 8-channel half, so a wave's
     // store instruction writes one contiguous 1-KB fragment (a thread per (n, c) wrote 2-byte pieces 1 KB apart: 1.1 TB/s on the
     // 164 MB a train step re-packs).
-    typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
     const int nC = Cp >> 4;
     const int64_t total8 = (int64_t)Np * (Cp >> 3);
     for (int64_t idx = vblock * (int64_t)blockDim.x + threadIdx.x; idx < total8; idx += (int64_t)vgrid * blockDim.x) {
@@ -126,7 +107,7 @@ __device__ __forceinline__ void pack_wino_w_body(const float* __restrict__ w, fl
               x = dgrad ? w[(((int64_t)c * Cout + n) * 3 + (2 - u)) * 3 + (2 - v)] : w[(((int64_t)n * Cin + c) * 3 + u) * 3 + v];
             g[e][u][v] = x;
           }
-      u32x4_t* dst = reinterpret_cast<u32x4_t*>(U) + ((int64_t)ntile * nC + c16) * 16 * 192 + lane;   // [comp][piece][64 lanes] x 16 B
+      u32x4* dst = reinterpret_cast<u32x4*>(U) + ((int64_t)ntile * nC + c16) * 16 * 192 + lane;   // [comp][piece][64 lanes] x 16 B
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -145,14 +126,14 @@ __device__ __forceinline__ void pack_wino_w_body(const float* __restrict__ w, fl
             const float r2 = r1 - __uint_as_float(b1);               // exact; 8 significant bits are left
             p0[e] = (unsigned short)(b0 >> 16), p1[e] = (unsigned short)(b1 >> 16), p2[e] = (unsigned short)(__float_as_uint(r2) >> 16);
           }
-          u32x4_t q0, q1, q2;
+          u32x4 q0, q1, q2;
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             q0[e] = (unsigned)p0[2 * e] | ((unsigned)p0[2 * e + 1] << 16);
             q1[e] = (unsigned)p1[2 * e] | ((unsigned)p1[2 * e + 1] << 16);
             q2[e] = (unsigned)p2[2 * e] | ((unsigned)p2[2 * e + 1] << 16);
           }
-          u32x4_t* q = dst + (i * 4 + j) * 192;
+          u32x4* q = dst + (i * 4 + j) * 192;
           q[0] = q0, q[64] = q1, q[128] = q2;
         }
     }
@@ -982,9 +963,9 @@ __global__ __launch_bounds__(512) void wino3x3_cp_kernel(const IgemmDesc d, cons
       float v[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float qx = scalar_fma(sgn, raw[set][hf][1][e], raw[set][hf][0][e]);
-        const float qy = scalar_fma(sgn, raw[set][hf][3][e], raw[set][hf][2][e]);
-        v[e] = scalar_fma(w, qy, qx);
+        const float qx = x3_fma(sgn, raw[set][hf][1][e], raw[set][hf][0][e]);
+        const float qy = x3_fma(sgn, raw[set][hf][3][e], raw[set][hf][2][e]);
+        v[e] = x3_fma(w, qy, qx);
       }
 #pragma unroll
       for (int e = 0; e < 2; ++e) {

@@ -25,12 +25,8 @@
 #include <type_traits>
 
 #include "common.h"
-#include "x3.h"
 
 namespace mgu {
-
-
-__device__ __forceinline__ void ww_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // ---- inverse transform dW = A^T M A, once per workgroup: every wave is past its last LDS operand read when it gets here ----------
 template <int CO_T, int CI_T>
@@ -45,7 +41,7 @@ __device__ __forceinline__ void ww_epilogue(const WgradDesc& d, float* smem, f32
   for (int ct = 0; ct < CO_T; ++ct) {
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
-      ww_barrier();   // previous pass consumed (first pass: every wave is past its last LDS operand read)
+      lds_barrier();   // previous pass consumed (first pass: every wave is past its last LDS operand read)
 #pragma unroll
       for (int rq = 0; rq < 4; ++rq) {
         f32x4 z;
@@ -58,7 +54,7 @@ __device__ __forceinline__ void ww_epilogue(const WgradDesc& d, float* smem, f32
         }
         *reinterpret_cast<f32x4*>(Zx + ((((wi * CI_T + wg) * 4 + rq) * 64) + lane) * 4) = z;
       }
-      ww_barrier();
+      lds_barrier();
       // wave i finishes accumulator registers 4i .. 4i+3: rows (co) 8i + 4*lh + (0..3) of output tile ct, column ci = lr
       const f32x4 z0 = *reinterpret_cast<const f32x4*>(Zx + ((((0 * CI_T + wg) * 4 + wi) * 64) + lane) * 4);
       const f32x4 z1 = *reinterpret_cast<const f32x4*>(Zx + ((((1 * CI_T + wg) * 4 + wi) * 64) + lane) * 4);
@@ -140,7 +136,7 @@ __device__ __forceinline__ void ww_x3_kstep(f32x16 (&acc)[4][CO_T], const HRead&
     prep(std::integral_constant<int, 0>{});
     __builtin_amdgcn_sched_barrier(0);
     constexpr int NS = 4 * CO_T;
-    x3_static_for<0, NS>([&](auto st_c) {
+    static_for<0, NS>([&](auto st_c) {
       constexpr int st = decltype(st_c)::value, ct = st >> 2, j = st & 3, sl = st & 1;
       f32x16 t = acc[j][ct];   // smallest products first
       t = mfma_bf16(sa[sl][2], vb[j][0], t);
@@ -248,9 +244,9 @@ __global__ __launch_bounds__(256 * CI_T, (X3 && CI_T == 1 && CO_T == 2) ? 2 : 1)
   if (PF) load_patch(p_begin);
   for (int pi = 0; pi < npatch; ++pi) {
     if (!PF) load_patch(p_begin + pi);
-    ww_barrier();            // every wave is done with the previous patch
+    lds_barrier();            // every wave is done with the previous patch
     store_patch();
-    ww_barrier();            // patch visible
+    lds_barrier();            // patch visible
     // prefetch into registers while this patch computes -- UNCONDITIONAL (the last trip re-reads its own patch): a branch
     // around the loads makes hipcc wait for them at the join, i.e. before the MFMA loop instead of after it
     if (PF) load_patch(p_begin + min(pi + 1, npatch - 1));
@@ -258,7 +254,7 @@ __global__ __launch_bounds__(256 * CI_T, (X3 && CI_T == 1 && CO_T == 2) ? 2 : 1)
       // Three-piece mode (the default): the SAME sums on the bf16 matrix pipe.  v_mfma_f32_32x32x16_bf16 reduces over 16 tiles per
       // instruction, a lane holding 8 of them per operand: lane half lh owns tiles (row 2ks + a, column 2u + lh), a = 0..1,
       // u = 0..3 -> k = 8 lh + 4a + u (the two halves stay two pixels apart, so the LDS reads keep their bank-half split).
-      // S and V are formed as above, each value is split exactly into three bf16 pieces (x3.h) and a product is the six piece
+      // S and V are formed as above, each value is split exactly into three bf16 pieces (device.h) and a product is the six piece
       // products of weight >= 2^-16: 24 CO_T MFMAs of 32 cycles per 16 tiles instead of 32 CO_T of 64, paid for with ~700 VALU
       // operations -- the fp32 MFMA blocks the VALU while it runs, the bf16 one does not.
 #pragma unroll 1

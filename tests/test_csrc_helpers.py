@@ -1,0 +1,37 @@
+"""Guard against the next paste: each shared device / launch helper of csrc/ has ONE definition, and the kernel files declare no
+vector typedefs of their own (csrc/device.h, common.h and ctx.h are where they live).  Source text only: no GPU, no build."""
+import glob
+import os
+import re
+
+CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "mingraph-unet_amd", "csrc")
+SOURCES = {os.path.basename(p): open(p).read() for p in sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.h")))}
+
+VECTOR_TYPES = ["f32x16", "f32x4", "f32x2", "u32x4", "u32x2", "bf16x8"]
+DEVICE_HELPERS = ["mfma_bf16", "split3_pack", "split3_pack_s", "x3_add", "x3_sub", "x3_fma", "static_for", "lds_barrier",
+                  "lds_barrier_builtin", "lds_barrier_fenced", "wave_sum", "wave_min", "wave_max", "block_fold", "enc_ordered",
+                  "dec_ordered", "graph_of"]
+HOST_HELPERS = ["grid_for", "aligned16", "rup", "ensure"]
+# names the private copies went by
+RETIRED = ["f32x4c", "f32x4n", "f32x4r", "u32x4_t", "x3_static_for", "scalar_fma", "ww_barrier", "gat_enc_ordered", "gat_dec_ordered",
+           "gf_enc_ordered", "gf_dec_ordered", "wave_sum64", "fold_doubles", "nblocks", "nblk", "nb", "al16", "align256"]
+
+
+def definitions(name):
+    """(file, line) of every function definition `name(...) {` or typedef / struct of that name"""
+    func = re.compile(r"^[^\n;=(]*?[\w>&*]\s+" + name + r"\s*\([^;{}]*\)\s*(?:const\s*)?\{", re.M)   # declarator at the start of a line, body follows
+    typ = re.compile(r"^\s*(?:typedef\b[^;]*\b" + name + r"\b[^;]*;|struct\s+" + name + r"\s*\{|using\s+" + name + r"\s*=)", re.M)
+    return [(f, t.count("\n", 0, m.start()) + 1) for f, t in SOURCES.items() for m in list(func.finditer(t)) + list(typ.finditer(t))]
+
+
+def test_each_shared_helper_is_defined_once():
+    where = {n: definitions(n) for n in VECTOR_TYPES + DEVICE_HELPERS + HOST_HELPERS + ["Carve"]}
+    assert {n: w for n, w in where.items() if len(w) != 1} == {}
+    assert {n: w for n, w in where.items() if n in VECTOR_TYPES + DEVICE_HELPERS and w[0][0] != "device.h"} == {}
+    assert {n: w for n, w in where.items() if n not in VECTOR_TYPES + DEVICE_HELPERS and w[0][0] not in ("common.h", "ctx.h")} == {}
+
+
+def test_kernel_files_declare_no_vector_types_and_retired_names_are_gone():
+    assert [f for f, t in SOURCES.items() if f.endswith(".hip") and "ext_vector_type" in t] == []
+    assert {n: definitions(n) for n in RETIRED if definitions(n)} == {}
+    assert [(f, n) for f, t in SOURCES.items() for n in RETIRED[:4] if re.search(r"\b" + n + r"\b", t)] == []
