@@ -578,6 +578,7 @@ double mgu_unet_mfma_flops(mgu_ctx* ctx, int B, int H, int W);
  * enable before the forward, read after.  Adds event records only (no syncs) while enabled. */
 int mgu_profile_enable(mgu_ctx* ctx, int on);
 /* Per kernel family, summed over the launches recorded since mgu_profile_enable(ctx, 1) (U-Net forward / backward convolutions,
+ * the mgu_conv2d_nhwc / mgu_conv2d_prepared_nhwc / mgu_conv_transpose2x2_nhwc building blocks -- name only, no FLOP counts --,
  * GAT kernels): time between HIP events recorded on the launch stream right around each launch, algorithmic FLOPs (2*MAC of the
  * operator) and the FLOPs actually issued on the matrix pipe (`pipe`: 0 fp32 MFMA, 1 bf16 MFMA, -1 none).  `name` is the kernel's
  * name as rocprofv3 --kernel-trace prints it (template arguments included where two instantiations are used).  A read CONSUMES the

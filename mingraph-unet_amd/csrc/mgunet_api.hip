@@ -609,8 +609,9 @@ static int conv2d_launch(mgu_ctx* c, const Layer& L, const void* in_dev, int B, 
     HIPCHK(c, launch_bias_tile((const float*)bias_dev, L.shift, L.Cout, 1, s));
     d.shift = L.shift;
   }
-  ProfScope ps(c, s);
-  HIPCHK(c, launch_igemm_f32(d, s));
+  const ConvKernel k = pick_conv(d, 0);
+  ProfScope ps(c, s, conv_kernel_name(k, d));   // the record names the kernel the pick chose, as run_layer's does
+  HIPCHK(c, launch_conv(d, k, 0, s));
   return MGU_OK;
 }
 
@@ -725,7 +726,7 @@ int mgu_conv_transpose2x2_nhwc(mgu_ctx* c, const void* in_dev, int B, int H, int
   }
   const ConvKernel k = pick_conv(d, 0);
   if (k == ConvKernel::ConvtX3) HIPCHK(c, launch_pack_convt_x3((const float*)w_dev, U.wu, Cin, Cout, s));
-  ProfScope ps(c, s);
+  ProfScope ps(c, s, conv_kernel_name(k, d));
   HIPCHK(c, launch_conv(d, k, 0, s));
   return MGU_OK;
 }

@@ -13,6 +13,7 @@ import torch
 import torch.nn.functional as F
 
 import mgunet_oracle as O
+import split_oracle as SO
 from mgunet import _lib
 
 pytestmark = pytest.mark.gpu
@@ -255,19 +256,33 @@ def _conv_fwd(cuda, ctx, x, w):
     return out.permute(0, 3, 1, 2).cpu()
 
 
-@pytest.mark.parametrize("case", ["cancellation", "wide_exponents", "integers", "bf16_exact", "tiny_residuals"])
+SPLIT_CASES = ["cancellation", "wide_exponents", "integers", "bf16_exact", "tiny_residuals", "full_mantissa", "positive_low_bits"]
+
+
+@pytest.mark.parametrize("case", SPLIT_CASES)
 def test_three_piece_split_adversarial(cuda, case):
+    three_piece_split_adversarial(cuda, case, 64, 64)
+
+
+@pytest.mark.parametrize("case", SPLIT_CASES)
+def test_three_piece_split_adversarial_32_channels(cuda, case):
+    """The 32-channel work split (wino3x3_cp_kernel<1>; the test above runs <2>)."""
+    three_piece_split_adversarial(cuda, case, 32, 32)
+
+
+def three_piece_split_adversarial(cuda, case, Cin, Cout):
     """MGU_WINO_PREC=1 (default) must be an fp32 multiply in effect: measured against float64 its error may not exceed the
-    exact-fp32 MFMA path's (MGU_WINO_PREC=0) by more than a rounding or two, on operands built to break a narrower product."""
+    exact-fp32 MFMA path's (MGU_WINO_PREC=0) by more than a rounding or two, on operands built to break a narrower product.
+    (tests/test_gpu_split_kernels.py bars every three-piece kernel family against emulated lost products.)"""
     g = torch.Generator().manual_seed(5)
-    B, Cin, Cout, H, W = 2, 64, 64, 24, 40
+    B, H, W = 2, 24, 40
     x = torch.randn((B, Cin, H, W), generator=g)
     w = torch.randn((Cout, Cin, 3, 3), generator=g) * 0.1
     if case == "cancellation":
-        # channel pairs (c, c + 32) carry +v and -v(1 + 2^-12) against equal weights: the k-sum cancels to ~2^-12 of its terms,
+        # channel pairs (c, c + Cin / 2) carry +v and -v(1 + 2^-12) against equal weights: the k-sum cancels to ~2^-12 of its terms,
         # so an operand error of 2^-16 (two pieces only) would show up as a 6 % error of the result
-        x[:, 32:] = -x[:, :32] * (1 + 2.0 ** -12)
-        w[:, 32:] = w[:, :32]
+        x[:, Cin // 2:] = -x[:, :Cin // 2] * (1 + 2.0 ** -12)
+        w[:, Cin // 2:] = w[:, :Cin // 2]
     elif case == "wide_exponents":
         e = torch.linspace(-60, 60, Cin).round()
         x = x * (2.0 ** e).view(1, Cin, 1, 1)
@@ -279,7 +294,11 @@ def test_three_piece_split_adversarial(cuda, case):
         x = x.bfloat16().float()                            # second and third pieces are exactly zero
         w = w.bfloat16().float()
     elif case == "tiny_residuals":
-        x = (x.bfloat16().float()) * (1 + 2.0 ** -23)       # mantissa 1...01: the third piece carries the last bit alone
+        # mantissa 1...01.  The split truncates, so the residual after the first piece is that last bit alone and the SECOND piece
+        # holds it; the third piece is zero (tests/test_split_host.py pins this).  full_mantissa is the case with a live third piece.
+        x = (x.bfloat16().float()) * (1 + 2.0 ** -23)
+    else:   # full_mantissa: every third piece nonzero; positive_low_bits: the lost terms of a narrower product share a sign
+        x, w = (torch.from_numpy(t) for t in SO.operands(case, tuple(x.shape), tuple(w.shape), 1, 1, seed=5))
     ref = F.conv2d(x.double(), w.double(), padding=1)
     scale = F.conv2d(x.double().abs(), w.double().abs(), padding=1)     # sum |a b|: the natural fp32 error scale
     with context(cuda, MGU_WINO_PREC=1) as c1:
