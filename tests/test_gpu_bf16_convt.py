@@ -6,6 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import bf16_oracle as B
 import mgunet
 import mgunet_oracle as O
 
@@ -46,7 +47,14 @@ def test_fragment_convtranspose_layer_vs_torch(cuda):
     cfg = (3, 2, 32, 1)
     p = O.make_unet_params(*cfg, seed=43)
     x = torch.from_numpy(O.formula_normal("ctb/x1", (2, 3, 48, 80), seed=9))
-    got = _forward(cuda, cfg, p, x.to(cuda))[0].cpu()
+    unet = mgunet.UNet(*cfg, compute_dtype=torch.bfloat16)
+    unet.load_state_dict(p)
+    lg, sk, ft = unet.to(cuda).eval()(x.to(cuda))
+    got = lg.float().cpu()
+    # the segment the layer sits in (feat0 <- skip0: bottleneck, ConvTranspose 64 -> 32, two convolutions) against its float64 reference
+    # from the HIP path's own skip, under the per-element bar of tests/bf16_oracle.py
+    ref, floor = B.segment(p, 1, "feat0", (sk[0].double().cpu(),), B.first_fp32_weights(3, 32))
+    B.check(ft[0].double().cpu(), ref, floor, "convt 64 -> 32, feat0 <- skip0", deep=True)
     with torch.no_grad():
         ref = O.unet_forward(p, x, cfg[3])[0]
     # bf16 storage of every activation: the reference's own bf16 run deviates by ~2-3 % of max|logit| (tests/test_gpu_parity.py pins it)
