@@ -20,7 +20,8 @@ C++ kernel -- with the register map and the instruction order of the chunk loop 
 Applicability (the launcher checks; everything else stays on the C++ kernel): inference epilogue (no statistics), H % 8 == 0,
 W % 32 == 0, N % 64 == 0, Cp % 32 == 0, channel pitches and offsets % 4 == 0, scale and shift present, x-fastest patch order.
 
-Usage: gen_wino_cp.py OUT.s
+Usage: gen_wino_cp.py OUT.s            (the three plain kernels)
+       gen_wino_cp.py --head OUT.s     (mgu_wino_cp1r2h_gfx950)
 """
 import sys
 
@@ -30,8 +31,10 @@ import sys
 def vr(b, n=1):
     return f"v{b}" if n == 1 else f"v[{b}:{b + n - 1}]"
 
-CFG = {"ntb": 2, "nc": None}          # kernel being emitted: output-channel tiles per workgroup; static chunk count (narrow kernels)
+CFG = {"ntb": 2, "nc": None, "head": False}   # kernel being emitted: output-channel tiles per workgroup; static chunk count (narrow
+#                                               kernels); head: the finishing pass also applies the 1x1 head and sums graph patches
 def NTB(): return CFG["ntb"]
+def HEAD(): return CFG["head"]
 def ACC(jj, nt, mi): return ((jj * 2 + nt) * 2 + mi) * 16 if CFG["ntb"] == 2 else (jj * 2 + mi) * 16
 # narrow kernels (NTB = 1): the layer's whole weight-piece slice of the wave stays in registers, two halo register sets
 def WN(c, jj, p): return 64 + ((c * 2 + jj) * 3 + p) * 4
@@ -107,6 +110,23 @@ def patch_coords(p):
     E(f"s_lshl_b32 s{S_Y0}, s{S_PY}, 3")
     E(f"s_lshl_b32 s{S_X0}, s{S_PX}, 5")
 
+
+# ---------------------------------------------------------------------------------------------------------------------
+# head-fused form of the 2-chunk narrow kernel (mgu_wino_cp1r2h_gfx950).  Registers the 2-chunk kernel leaves free: v112..v159 (the
+# weight pieces of chunks 2, 3 of the 4-chunk kernel); SGPRs that the narrow kernels need in the prologue only (weight descriptor,
+# sign / mask constants, weight offsets) or for the fused pool, which this form does not have (the launcher passes no pool).
+# ---------------------------------------------------------------------------------------------------------------------
+def WQ(k, e): return 112 + k * 4 + e        # head weight of class k, channel e of the lane's channel quad (lane constant)
+def BL(k): return 128 + k                   # bias of class k in the lanes of channel quad 0, 0 in the others (lane constant)
+def DL(k, p): return 132 + k * 4 + p        # logit of class k, pixel p of the lane's 2 x 2 tile (p = 2 * row + column)
+def SS(j): return 148 + j                   # store registers of a lane's output row: [column][class]
+VLG, VPS, VBP16, VBP32 = 156, 157, 158, 159   # byte offsets of the lane's logit row / patch-sum quad (out of range in the lanes that do
+#                                               not store), bpermute addresses of lane ^ 16 / lane ^ 32
+S_LOGP = 14         # s[14:15] logits (the pool pointer's registers)
+S_LGR = 84          # s[84:87] logits descriptor of the image (the pooled descriptor's registers)
+S_PSR = 48          # s[48:51] patch-sum descriptor (the weight descriptor's registers: the weight pieces are resident)
+S_NCLS, S_NCLS4, S_WNCLS4, S_LOGIMGB, S_NPW, S_NPIMG, S_NODE0 = 40, 52, 53, 54, 56, 78, 79
+HEAD_KERNARG = 160  # the plain kernels' 120 bytes + head weight, head bias, logits, patch sums (8 each), ncls, patch-sum bytes (4 each)
 
 S_VHST = S_PAD      # 1: the halo-offset registers hold the patch-independent offsets of an INTERIOR patch (kernarg pad word: 0 at entry)
 
@@ -658,6 +678,79 @@ def emit_chunk_n(jp, c):
         emit_step_n(jp, s, c)
 
 
+def emit_head_math(Y, P, Q, CQ):
+    """Head-fused finishing pass, behind the feature stores.  Y: the four pixels of the lane's 2 x 2 tile (p = 2 * row + column), four
+    channels each, after scale / shift / ReLU; the eight lanes of a tile hold its 32 channels.  P, Q: two free register quads.
+      * logits: per pixel and class a 4-term fma chain that starts from the bias in channel quad 0 and from 0 elsewhere, then an xor
+        fold over the tile's eight lanes (quad_perm 1, quad_perm 2, half mirror: every lane ends with the same sum);
+      * patch sums: (p0 + p1) + (p2 + p3) per channel, then an xor fold over the wave's eight tiles (row_ror 8, bpermute 16 and 32).
+    The four chains of a stage are interleaved (a DPP operand written by the VALU needs two wait states), and the two bpermute round
+    trips of the patch sums run under the logit arithmetic of classes 0 and 1."""
+    def fold_add():
+        E("s_waitcnt lgkmcnt(0)")
+        for e in (0, 2):
+            E(pk2("add", P + e, P + e, Q + e))
+    def fold_issue(vb):
+        for e in range(4):
+            E(f"ds_bpermute_b32 v{Q + e}, v{vb}, v{P + e}")
+    for e in (0, 2):
+        E(pk2("add", P + e, Y[0] + e, Y[1] + e))
+    for e in (0, 2):
+        E(pk2("add", Q + e, Y[2] + e, Y[3] + e))
+    for e in (0, 2):
+        E(pk2("add", P + e, P + e, Q + e))
+    E("s_nop 1")
+    for e in range(4):
+        E(f"v_add_f32_dpp v{P + e}, v{P + e}, v{P + e} row_ror:8 row_mask:0xf bank_mask:0xf")
+    fold_issue(VBP16)
+    lst = newlabel("hstore")
+    for k in range(4):
+        if k:
+            E(f"s_cmp_lt_u32 s{S_NCLS}, {k + 1}")
+            E(f"s_cbranch_scc1 {lst}")
+        for p in range(4):
+            E(f"v_fma_f32 v{DL(k, p)}, v{Y[p]}, v{WQ(k, 0)}, v{BL(k)}")
+        for e in range(1, 4):
+            for p in range(4):
+                E(f"v_fmac_f32_e32 v{DL(k, p)}, v{Y[p] + e}, v{WQ(k, e)}")
+        for ctl in ("quad_perm:[1,0,3,2]", "quad_perm:[2,3,0,1]", "row_half_mirror"):
+            for p in range(4):
+                E(f"v_add_f32_dpp v{DL(k, p)}, v{DL(k, p)}, v{DL(k, p)} {ctl} row_mask:0xf bank_mask:0xf")
+        if k == 0:
+            fold_add()
+            fold_issue(VBP32)
+    L(lst)
+    # the lane's output row: channel quad 0 takes pixels 0, 1, quad 1 pixels 2, 3; [column][class] is the NHWC order of the logits
+    E(f"v_cmp_eq_u32_e32 vcc, 1, v{CQ}")
+    ldone = newlabel("hdone")
+    for n in range(1, 5):
+        lnext = newlabel("hn")
+        if n < 4:
+            E(f"s_cmp_lg_u32 s{S_NCLS}, {n}")
+            E(f"s_cbranch_scc1 {lnext}")
+        for pp in range(2):
+            for k in range(n):
+                E(f"v_cndmask_b32_e32 v{SS(pp * (4 if n == 3 else n) + k)}, v{DL(k, pp)}, v{DL(k, 2 + pp)}, vcc")   # (register tuples are even-aligned)
+        d = f"v{VLG}, s[{S_LGR}:{S_LGR + 3}], 0 offen"
+        if n == 1:
+            E(f"buffer_store_dwordx2 {vr(SS(0), 2)}, {d}")
+        elif n == 2:
+            E(f"buffer_store_dwordx4 {vr(SS(0), 4)}, {d}")
+        elif n == 3:
+            E(f"buffer_store_dwordx3 {vr(SS(0), 3)}, {d}")
+            E(f"buffer_store_dwordx3 {vr(SS(4), 3)}, {d} offset:12")
+        else:
+            E(f"buffer_store_dwordx4 {vr(SS(0), 4)}, {d}")
+            E(f"buffer_store_dwordx4 {vr(SS(4), 4)}, {d} offset:16")
+        if n < 4:
+            E(f"s_branch {ldone}")
+            L(lnext)
+    L(ldone)
+    fold_add()
+    E("s_nop 0")
+    E(f"buffer_store_dwordx4 {vr(P, 4)}, v{VPS}, s[{S_PSR}:{S_PSR + 3}], 0 offen")
+
+
 def emit_epilogue_n(jp):
     # free registers as in emit_epilogue: the c quads of the raw halves (v208..v211, v224..v227) carry the next patch's step 0 inner
     # sums into its step 1
@@ -676,17 +769,30 @@ def emit_epilogue_n(jp):
     E(f"s_add_u32 s{S_OUTR}, s{S_OUT}, s{S_T[6]}")
     E(f"s_addc_u32 s{S_OUTR + 1}, s{S_OUT + 1}, s{S_T[7]}")
     E(f"s_and_b32 s{S_OUTR + 1}, s{S_OUTR + 1}, 0xffff")
-    E(f"s_lshr_b32 s{S_T[4]}, s{S_H}, 1")
-    E(f"s_lshr_b32 s{S_T[5]}, s{S_W}, 1")
-    E(f"s_mul_i32 s{S_T[4]}, s{S_T[4]}, s{S_T[5]}")
-    E(f"s_mul_i32 s{S_T[4]}, s{S_T[4]}, s{S_LDPOOL}")
-    E(f"s_lshl_b32 s{S_T[4]}, s{S_T[4]}, 2")
-    E(f"s_mov_b32 s{S_POOLR + 2}, s{S_T[4]}")
-    E(f"s_mul_i32 s{S_T[6]}, s{S_IMG}, s{S_T[4]}")
-    E(f"s_mul_hi_u32 s{S_T[7]}, s{S_IMG}, s{S_T[4]}")
-    E(f"s_add_u32 s{S_POOLR}, s{S_POOL}, s{S_T[6]}")
-    E(f"s_addc_u32 s{S_POOLR + 1}, s{S_POOL + 1}, s{S_T[7]}")
-    E(f"s_and_b32 s{S_POOLR + 1}, s{S_POOLR + 1}, 0xffff")
+    if HEAD():
+        E("; only-head {")
+        # logits descriptor of the image, first graph node of the image
+        E(f"s_mul_i32 s{S_T[6]}, s{S_IMG}, s{S_LOGIMGB}")
+        E(f"s_mul_hi_u32 s{S_T[7]}, s{S_IMG}, s{S_LOGIMGB}")
+        E(f"s_add_u32 s{S_LGR}, s{S_LOGP}, s{S_T[6]}")
+        E(f"s_addc_u32 s{S_LGR + 1}, s{S_LOGP + 1}, s{S_T[7]}")
+        E(f"s_and_b32 s{S_LGR + 1}, s{S_LGR + 1}, 0xffff")
+        E(f"s_mul_i32 s{S_NODE0}, s{S_IMG}, s{S_NPIMG}")
+        E("; }")
+    else:
+        E("; only-plain {")
+        E(f"s_lshr_b32 s{S_T[4]}, s{S_H}, 1")
+        E(f"s_lshr_b32 s{S_T[5]}, s{S_W}, 1")
+        E(f"s_mul_i32 s{S_T[4]}, s{S_T[4]}, s{S_T[5]}")
+        E(f"s_mul_i32 s{S_T[4]}, s{S_T[4]}, s{S_LDPOOL}")
+        E(f"s_lshl_b32 s{S_T[4]}, s{S_T[4]}, 2")
+        E(f"s_mov_b32 s{S_POOLR + 2}, s{S_T[4]}")
+        E(f"s_mul_i32 s{S_T[6]}, s{S_IMG}, s{S_T[4]}")
+        E(f"s_mul_hi_u32 s{S_T[7]}, s{S_IMG}, s{S_T[4]}")
+        E(f"s_add_u32 s{S_POOLR}, s{S_POOL}, s{S_T[6]}")
+        E(f"s_addc_u32 s{S_POOLR + 1}, s{S_POOL + 1}, s{S_T[7]}")
+        E(f"s_and_b32 s{S_POOLR + 1}, s{S_POOLR + 1}, 0xffff")
+        E("; }")
     E(f"v_and_b32_e32 v{CQ}, 7, v{VTID}")
     E(f"v_lshrrev_b32_e32 v{VT}, 3, v{VTID}")
     # per-channel scale / shift of the finishing unit's channel quad (n0 = nblock * 32 + cq * 4): requested first, used last
@@ -716,17 +822,51 @@ def emit_epilogue_n(jp):
     E(f"v_and_b32_e32 v{e2}, 15, v{VT}")
     E(f"v_lshl_add_u32 v{e2}, v{e2}, 1, s{S_X0}")
     E(f"v_mad_u32_u24 v{e3}, v{e1}, s{S_W}, v{e2}")
+    if HEAD():
+        E("; only-head {")
+        E(f"v_mul_lo_u32 v{VLG}, v{e3}, s{S_NCLS4}")                      # the tile's first pixel in the logits of the image (bytes)
+        E("; }")
     E(f"v_mul_lo_u32 v{e3}, v{e3}, s{S_LDOUT}")
     E(f"v_lshl_add_u32 v{e3}, v{CQ}, 2, v{e3}")
     E(f"v_lshlrev_b32_e32 v{VOUT}, 2, v{e3}")
     E(f"v_add_u32_e32 v{VOUT}, s{S_N64X4}, v{VOUT}")
-    E(f"v_lshrrev_b32_e32 v{e1}, 1, v{e1}")
-    E(f"v_lshrrev_b32_e32 v{e2}, 1, v{e2}")
-    E(f"v_mad_u32_u24 v{e3}, v{e1}, s{S_T[5]}, v{e2}")
-    E(f"v_mul_lo_u32 v{e3}, v{e3}, s{S_LDPOOL}")
-    E(f"v_lshl_add_u32 v{e3}, v{CQ}, 2, v{e3}")
-    E(f"v_lshlrev_b32_e32 v{VPOOL}, 2, v{e3}")
-    E(f"v_add_u32_e32 v{VPOOL}, s{S_N64X4}, v{VPOOL}")
+    if HEAD():
+        E("; only-head {")
+        # The eight lanes of a tile (channel quads 0..7) all hold its logits after the fold: quad 0 stores the upper row of the 2 x 2
+        # tile, quad 1 the lower row, the others get an offset past the descriptor's range (the store is dropped, as the halo loads
+        # of out-of-image pixels are)
+        E(f"v_mul_u32_u24_e32 v{VPS}, s{S_WNCLS4}, v{CQ}")
+        E(f"v_add_u32_e32 v{VLG}, v{VLG}, v{VPS}")
+        E(f"v_cmp_gt_u32_e32 vcc, 2, v{CQ}")
+        E(f"v_mov_b32_e32 v{VPS}, s{S_OOB}")
+        E("s_nop 1")
+        E(f"v_cndmask_b32_e32 v{VLG}, v{VPS}, v{VLG}, vcc")
+        # A wave's eight tiles are 2 rows x 16 columns of ONE graph patch (16 x 16 pixels): its partial sum goes to row pair
+        # (oy >> 1) & 7 of node (img, oy >> 4, ox >> 4) in the scratch [node][8 row pairs][32 channels], from the lanes of tile 0
+        E(f"v_lshrrev_b32_e32 v{e3}, 4, v{e1}")
+        E(f"v_lshrrev_b32_e32 v{VPS}, 4, v{e2}")
+        E(f"v_mad_u32_u24 v{e3}, v{e3}, s{S_NPW}, v{VPS}")
+        E(f"v_add_u32_e32 v{e3}, s{S_NODE0}, v{e3}")
+        E(f"v_bfe_u32 v{VPS}, v{e1}, 1, 3")
+        E(f"v_lshl_add_u32 v{e3}, v{e3}, 3, v{VPS}")
+        E(f"v_lshl_add_u32 v{e3}, v{e3}, 3, v{CQ}")
+        E(f"v_lshlrev_b32_e32 v{e3}, 4, v{e3}")
+        E(f"v_and_b32_e32 v{VPS}, 7, v{VT}")
+        E(f"v_cmp_eq_u32_e32 vcc, 0, v{VPS}")
+        E(f"v_mov_b32_e32 v{VPS}, s{S_OOB}")
+        E("s_nop 1")
+        E(f"v_cndmask_b32_e32 v{VPS}, v{VPS}, v{e3}, vcc")
+        E("; }")
+    else:
+        E("; only-plain {")
+        E(f"v_lshrrev_b32_e32 v{e1}, 1, v{e1}")
+        E(f"v_lshrrev_b32_e32 v{e2}, 1, v{e2}")
+        E(f"v_mad_u32_u24 v{e3}, v{e1}, s{S_T[5]}, v{e2}")
+        E(f"v_mul_lo_u32 v{e3}, v{e3}, s{S_LDPOOL}")
+        E(f"v_lshl_add_u32 v{e3}, v{CQ}, 2, v{e3}")
+        E(f"v_lshlrev_b32_e32 v{VPOOL}, 2, v{e3}")
+        E(f"v_add_u32_e32 v{VPOOL}, s{S_N64X4}, v{VPOOL}")
+        E("; }")
     E(f"s_lshl_b32 s{S_T[0]}, s{S_WI}, 13")
     if jp:
         E(f"s_add_u32 s{S_T[0]}, s{S_T[0]}, 0x{RAWB:x}")
@@ -787,18 +927,25 @@ def emit_epilogue_n(jp):
     E(f"buffer_store_dwordx4 {vr(ya1, 4)}, v{VOUT}, s[{S_OUTR}:{S_OUTR + 3}], s{S_LD4} offen nt")
     E(f"buffer_store_dwordx4 {vr(yb0, 4)}, v{VOUT}, s[{S_OUTR}:{S_OUTR + 3}], s{S_SW4} offen nt")
     E(f"buffer_store_dwordx4 {vr(yb1, 4)}, v{VOUT}, s[{S_OUTR}:{S_OUTR + 3}], s{S_SUMOFF} offen nt")
-    lnp = newlabel("nopool")
-    E(f"s_cmp_eq_u64 s[{S_POOL}:{S_POOL + 1}], 0")
-    E(f"s_cbranch_scc1 {lnp}")
-    pm = Z(0, 0, 0)
-    for e in range(4):
-        E(f"v_max_f32_e32 v{pm + e}, v{ya0 + e}, v{yb0 + e}")
-    for e in range(4):
-        E(f"v_max_f32_e32 v{Z(0, 0, 1) + e}, v{ya1 + e}, v{yb1 + e}")
-    for e in range(4):
-        E(f"v_max_f32_e32 v{pm + e}, v{pm + e}, v{Z(0, 0, 1) + e}")
-    E(f"buffer_store_dwordx4 {vr(pm, 4)}, v{VPOOL}, s[{S_POOLR}:{S_POOLR + 3}], 0 offen")
-    L(lnp)
+    if HEAD():
+        E("; only-head {")
+        emit_head_math([ya0, ya1, yb0, yb1], Z(0, 0, 0), Z(0, 0, 1), CQ)
+        E("; }")
+    else:
+        E("; only-plain {")
+        lnp = newlabel("nopool")
+        E(f"s_cmp_eq_u64 s[{S_POOL}:{S_POOL + 1}], 0")
+        E(f"s_cbranch_scc1 {lnp}")
+        pm = Z(0, 0, 0)
+        for e in range(4):
+            E(f"v_max_f32_e32 v{pm + e}, v{ya0 + e}, v{yb0 + e}")
+        for e in range(4):
+            E(f"v_max_f32_e32 v{Z(0, 0, 1) + e}, v{ya1 + e}, v{yb1 + e}")
+        for e in range(4):
+            E(f"v_max_f32_e32 v{pm + e}, v{pm + e}, v{Z(0, 0, 1) + e}")
+        E(f"buffer_store_dwordx4 {vr(pm, 4)}, v{VPOOL}, s[{S_POOLR}:{S_POOLR + 3}], 0 offen")
+        L(lnp)
+        E("; }")
     E("s_waitcnt lgkmcnt(0)")            # (no clearing of the accumulators: chunk 0's chains start from the constant 0)
     E("s_barrier")
 
@@ -972,6 +1119,10 @@ def emit_prologue():
             setup_load()
             L(lsk)
             halo_loads(setn)
+        if HEAD():
+            E("; only-head {")
+            emit_head_prologue()
+            E("; }")
         E("s_waitcnt lgkmcnt(0)")
         E("s_barrier")
         return
@@ -1002,6 +1153,52 @@ def emit_prologue():
                 E(weight_load(jj, nt, p))
     E("s_waitcnt lgkmcnt(0)")
     E("s_barrier")
+
+
+def emit_head_prologue():
+    """head-fused form: the arguments behind the plain kernels' block, the lane constants and the loop-invariant scalars.  Runs behind
+    the last weight-piece load, so the weight descriptor's and the prologue constants' registers are free.  Nothing waits for the
+    lane-constant loads here: the first finishing pass waits vmcnt(0) in front of its arithmetic."""
+    t = S_T
+    E(f"s_load_dwordx4 s[{t[0]}:{t[3]}], s[0:1], 0x78")          # head weight (ncls, 32), head bias
+    E(f"s_load_dwordx2 s[{S_LOGP}:{S_LOGP + 1}], s[0:1], 0x88")
+    E(f"s_load_dwordx2 s[{S_PSR}:{S_PSR + 1}], s[0:1], 0x90")
+    E(f"s_load_dword s{S_NCLS}, s[0:1], 0x98")
+    E(f"s_load_dword s{S_PSR + 2}, s[0:1], 0x9c")                # bytes of the patch-sum scratch
+    E("s_waitcnt lgkmcnt(0)")
+    E(f"s_mov_b32 s{t[4]}, s{t[0]}")
+    E(f"s_and_b32 s{t[5]}, s{t[1]}, 0xffff")
+    E(f"s_lshl_b32 s{t[6]}, s{S_NCLS}, 7")                        # a class past ncls reads zeros
+    E(f"s_mov_b32 s{t[7]}, 0x00020000")
+    E(f"v_and_b32_e32 v1, 7, v{VTID}")                            # channel quad of the finishing unit
+    E("v_lshlrev_b32_e32 v2, 4, v1")
+    for k in range(4):
+        E(f"buffer_load_dwordx4 {vr(WQ(k, 0), 4)}, v2, s[{t[4]}:{t[7]}], 0 offen offset:{k * 128}")
+    E(f"s_mov_b32 s{t[4]}, s{t[2]}")
+    E(f"s_and_b32 s{t[5]}, s{t[3]}, 0xffff")
+    E(f"s_lshl_b32 s{t[6]}, s{S_NCLS}, 2")
+    E("v_cmp_eq_u32_e32 vcc, 0, v1")
+    E(f"v_mov_b32_e32 v2, s{S_OOB}")
+    E("v_mov_b32_e32 v3, 0")
+    E("s_nop 1")
+    E("v_cndmask_b32_e32 v2, v2, v3, vcc")
+    for k in range(4):
+        E(f"buffer_load_dword v{BL(k)}, v2, s[{t[4]}:{t[7]}], 0 offen offset:{k * 4}")
+    E(f"s_lshl_b32 s{S_NCLS4}, s{S_NCLS}, 2")
+    E(f"s_mul_i32 s{S_WNCLS4}, s{S_W}, s{S_NCLS4}")
+    E(f"s_mul_i32 s{S_LOGIMGB}, s{S_H}, s{S_WNCLS4}")
+    E(f"s_mov_b32 s{S_LGR + 2}, s{S_LOGIMGB}")
+    E(f"s_mov_b32 s{S_LGR + 3}, 0x00020000")
+    E(f"s_lshr_b32 s{S_NPW}, s{S_W}, 4")
+    E(f"s_lshr_b32 s{S_NPIMG}, s{S_H}, 4")
+    E(f"s_mul_i32 s{S_NPIMG}, s{S_NPIMG}, s{S_NPW}")
+    E(f"s_and_b32 s{S_PSR + 1}, s{S_PSR + 1}, 0xffff")
+    E(f"s_mov_b32 s{S_PSR + 3}, 0x00020000")
+    E(f"v_and_b32_e32 v1, 63, v{VTID}")
+    E("v_xor_b32_e32 v2, 16, v1")
+    E(f"v_lshlrev_b32_e32 v{VBP16}, 2, v2")
+    E("v_xor_b32_e32 v2, 32, v1")
+    E(f"v_lshlrev_b32_e32 v{VBP32}, 2, v2")
 
 
 def emit_first_form(jp):
@@ -1045,7 +1242,7 @@ def emit_kernel(name):
 \t.amdhsa_kernel {name}
 \t\t.amdhsa_group_segment_fixed_size 163840
 \t\t.amdhsa_private_segment_fixed_size 0
-\t\t.amdhsa_kernarg_size 120
+\t\t.amdhsa_kernarg_size {HEAD_KERNARG if HEAD() else 120}
 \t\t.amdhsa_user_sgpr_count 2
 \t\t.amdhsa_user_sgpr_dispatch_ptr 0
 \t\t.amdhsa_user_sgpr_queue_ptr 0
@@ -1081,11 +1278,11 @@ def emit_kernel(name):
     META.append(f"""  - .agpr_count:     0
     .args:
       - .offset:         0
-        .size:           120
+        .size:           {HEAD_KERNARG if HEAD() else 120}
         .value_kind:     by_value
     .group_segment_fixed_size: 163840
     .kernarg_segment_align: 8
-    .kernarg_segment_size: 120
+    .kernarg_segment_size: {HEAD_KERNARG if HEAD() else 120}
     .max_flat_workgroup_size: 512
     .name:           {name}
     .private_segment_fixed_size: 0
@@ -1104,13 +1301,18 @@ END_LABEL = ".Lend"
 
 
 def main():
-    path = sys.argv[1]
+    head = sys.argv[1] == "--head"     # the head-fused kernel is a code object of its own
+    path = sys.argv[2 if head else 1]
     out.append('\t.amdgcn_target "amdgcn-amd-amdhsa--gfx950"')
-    CFG.update(ntb=2, nc=None)
-    emit_kernel("mgu_wino_cp2_gfx950")
-    for nc in (2, 4):            # the narrow kernels: 32 output channels, the layer's 2 / 4 chunks of weight pieces resident
-        CFG.update(ntb=1, nc=nc)
-        emit_kernel(f"mgu_wino_cp1r{nc}_gfx950")
+    if head:
+        CFG.update(ntb=1, nc=2, head=True)
+        emit_kernel("mgu_wino_cp1r2h_gfx950")
+    else:
+        CFG.update(ntb=2, nc=None)
+        emit_kernel("mgu_wino_cp2_gfx950")
+        for nc in (2, 4):            # the narrow kernels: 32 output channels, the layer's 2 / 4 chunks of weight pieces resident
+            CFG.update(ntb=1, nc=nc)
+            emit_kernel(f"mgu_wino_cp1r{nc}_gfx950")
     out.append("\t.amdgpu_metadata\n---\namdhsa.kernels:")
     out.extend(META)
     out.append("""amdhsa.target:   amdgcn-amd-amdhsa--gfx950

@@ -10,6 +10,8 @@ in-order counters and fails on:
   * an MFMA that reads a VGPR written by a VALU instruction fewer than 2 wait states earlier;
   * a non-MFMA read of an MFMA result fewer than 18 wait states after the MFMA that wrote it;
   * a VALU write of the data registers of a 16-byte LDS / buffer store in the very next instruction;
+  * a DPP instruction that reads a VGPR written by a VALU instruction fewer than 2 wait states earlier (the head-fused finishing
+    pass folds across lanes with v_add_f32_dpp; its ds_bpermute folds count in lgkmcnt like LDS reads);
   * an LDS add-TID store directly behind the s_mov that wrote M0; v_readfirstlane directly behind the VALU write of its source;
   * a transform's outer sum (v_add_f32 / v_sub_f32 of an inner sum) whose other operand is no longer an inner sum, or is the inner
     sum of an older read base: the jj = 1 forming takes the shared tile column's inner sum from the registers the jj = 0 forming
@@ -50,6 +52,8 @@ def classify(op, args):
         return regs(args[0]), regs(args[1]) | regs(args[2]) | regs(args[3]), "mfma"
     if op.startswith("ds_read"):
         return regs(args[0]), regs(args[1]), "lds_load"
+    if op.startswith("ds_bpermute") or op.startswith("ds_swizzle"):
+        return regs(args[0]), set().union(*[regs(a) for a in args[1:]]), "lds_load"
     if op.startswith("ds_write_addtid"):
         return set(), regs(args[0]), "lds_store_addtid"
     if op.startswith("ds_write"):
@@ -173,6 +177,10 @@ def replay(stream, errors, where, prime=()):
             for r in touched if kind in ("valu", "lds_store", "lds_store_addtid", "vm_store", "readlane") else src:
                 if r in src and mfma_age.get(r, 99) < 18:
                     errors.append(f"{where}: `{text}` reads MFMA result v{r} after {mfma_age[r]} wait states (18 required)")
+        if op.endswith("_dpp"):
+            for r in src:
+                if valu_age.get(r, 99) < 2:
+                    errors.append(f"{where}: `{text}` (DPP) reads v{r} {valu_age[r]} wait state(s) after a VALU write (2 required)")
         if kind == "valu" and prev and prev[0] in ("lds_store", "vm_store") and len(prev[1]) >= 4 and (dst & prev[1]):
             errors.append(f"{where}: `{text}` overwrites store data of the previous instruction `{prev[2]}`")
         if kind == "lds_store_addtid" and m0_fresh:

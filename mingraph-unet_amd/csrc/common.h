@@ -45,6 +45,8 @@ struct Tuning {
   bool wgrad_thin = true;   // MGU_NO_THIN_WGRAD=1
   bool wino_dgrad = true;   // MGU_NO_WINO_DGRAD=1
   bool gat_fused = true;    // MGU_NO_GAT_FUSED=1
+  bool head_fused = true;   // MGU_HEAD_FUSED=0: the 1x1 head and the patch means in their own pass over decoder feature 0 (patch_mean_kernel)
+                            // instead of the finishing pass of the convolution that writes it (WinoHead below; A/B and tests)
   bool wino_asm = true;     // MGU_WINO_ASM=0: the C++ component-pair kernels instead of their hand-scheduled assembly forms (wino_asm.hip; bitwise
                             // equal results)
 };
@@ -86,6 +88,20 @@ struct IgemmDesc {
   int ld2;
 };
 
+// Optional head-fused finishing pass of the narrow component-pair Winograd kernel (the launch that writes decoder feature 0, 32
+// channels): every pixel's 32 outputs also go through the final 1x1 conv (unet_decoder.py:117,143), and each wave adds its 2 x 16
+// pixels into the per-channel sum of their 16 x 16 graph patch -- one partial per row pair, plain stores into
+// psum[node][8 row pairs][32], which launch_patch_sum_combine adds in a fixed order (bit-repeatable; no atomics).
+struct WinoHead {
+  const float* w;     // (ncls, 32), the reference's layout
+  const float* b;     // (ncls)
+  float* logits;      // NHWC fp32 (B, H, W, ncls)
+  float* psum;        // scratch, wino_head_psum_bytes(B, H, W) bytes
+  int ncls;           // 1..4
+  int psum_bytes;
+};
+inline size_t wino_head_psum_bytes(int B, int H, int W) { return (size_t)B * (H / 16) * (W / 16) * 8 * 32 * sizeof(float); }
+
 inline const Tuning& tun(const IgemmDesc& d) { return d.tn ? *d.tn : default_tuning(); }
 // The kernel a convolution descriptor runs on.  pick_conv makes the choice once (it alone reads the conv switches of Tuning, through
 // the descriptor-level *_applicable tests in igemm.hip); the launch, the profiling label and cost, the fused epilogues and the weight
@@ -93,15 +109,20 @@ inline const Tuning& tun(const IgemmDesc& d) { return d.tn ? *d.tn : default_tun
 enum class ConvKernel {
   None,                                       // no kernel takes the descriptor: the launch returns hipErrorInvalidValue
   WinoAsmWide, WinoAsmCp1r2, WinoAsmCp1r4,    // mgu_wino_cp2 / cp1r2 / cp1r4_gfx950 (wino_asm.hip)
+  WinoAsmCp1r2Head,                           // mgu_wino_cp1r2h_gfx950: cp1r2 with the head-fused finishing pass (WinoHead)
   WinoCp2, WinoCp1, WinoCp2Stats, WinoCp1Stats,   // wino3x3_cp_kernel<2|1, STATS> (wino_f32.hip)
+  WinoCp1Head,                                // wino3x3_cp_kernel<1, HEAD>: the C++ twin of the head-fused form
   WinoF32Wide, WinoF32Narrow,                 // wino3x3_f32_kernel<0|1, 0>: fp32 MFMA operands (MGU_WINO_PREC=0)
   WinoX3Wide, WinoX3Narrow,                   // wino3x3_f32_kernel<0|1, 1>: three-piece bf16 operands
   HaloF32, HaloBf16Np8, HaloBf16Np4,          // conv3x3_halo_kernel
   TilesF32, TilesBf16,                        // igemm_kernel (KS, out_mode from the descriptor)
   ConvtX3, ConvtBf16f, ConvtX3Dgrad,          // convt2x2_x3_kernel, convt2x2_bf16_kernel, convt2x2_x3_kernel in its gather mode
 };
-ConvKernel pick_conv(const IgemmDesc& d, int dtype);   // dtype: 0 = fp32, 1 = bf16 storage (in / w / out point to bf16, sizes in elements)
-hipError_t launch_conv(const IgemmDesc& d, ConvKernel k, int dtype, hipStream_t s);   // k = pick_conv(d, dtype)
+// dtype: 0 = fp32, 1 = bf16 storage (in / w / out point to bf16, sizes in elements).  head: the caller would like the head-fused
+// finishing pass; the pick returns one of the *Head kernels only if the descriptor and the switches admit it
+ConvKernel pick_conv(const IgemmDesc& d, int dtype, const WinoHead* head = nullptr);
+hipError_t launch_conv(const IgemmDesc& d, ConvKernel k, int dtype, hipStream_t s, const WinoHead* head = nullptr);   // k = pick_conv(d, dtype, head)
+inline bool conv_fuses_head(ConvKernel k) { return k == ConvKernel::WinoAsmCp1r2Head || k == ConvKernel::WinoCp1Head; }
 inline hipError_t launch_igemm_f32(const IgemmDesc& d, hipStream_t s) { return launch_conv(d, pick_conv(d, 0), 0, s); }
 inline hipError_t launch_igemm_bf16(const IgemmDesc& d, hipStream_t s) { return launch_conv(d, pick_conv(d, 1), 1, s); }
 const char* conv_kernel_name(ConvKernel k, const IgemmDesc& d);   // profiling label of a forward launch
@@ -126,6 +147,9 @@ bool wino_dgrad_layer(const Tuning& t, int KS, int Cop);      // its data gradie
 bool convt_x3_layer(const Tuning& t, int Cin, int Cout);      // fp32 ConvTranspose on convt2x2_x3_kernel (launch_pack_convt_x3)
 bool convt_x3_dgrad_layer(const Tuning& t, int Cin, int Cout);   // its data gradient too (launch_pack_convt_x3_dgrad)
 bool convt_bf16f_layer(const Tuning& t, int Cin, int Cout);   // bf16-storage ConvTranspose on convt2x2_bf16_kernel
+// the convolution that writes a B x H x W x Cin feature may take the head-fused finishing pass (WinoHead) for a 1x1 head of ncls
+// classes and patch means at `patch`: the caller sizes WinoHead::psum on it, pick_conv repeats it on the descriptor
+bool wino_head_layer(const Tuning& t, int dtype, int Cin, int ncls, int patch, int B, int H, int W);
 // wino_f32.hip: work split of the Winograd kernels.  8 x 32 pixel patches; a workgroup covers 64 output channels of a wide layer
 // (N > 32), 32 of a narrow one, and walks ppb patches; item (n block, patch group) of XCD x is x * per_xcd + (workgroup / 8)
 inline bool wino_wide(const IgemmDesc& d) { return d.N > 32; }
@@ -186,9 +210,11 @@ struct WinoPackBatch {
 };
 bool wino_pack_batch_prepare(WinoPackBatch& b);   // fills Np / blk0 / total_blocks; false if an item cannot be packed
 hipError_t launch_pack_wino_w_multi(const WinoPackBatch* batch_dev, unsigned total_blocks, hipStream_t s);
-hipError_t launch_wino_f32(const IgemmDesc& d, ConvKernel k, hipStream_t s);   // k: one of the C++ Winograd kernels
+hipError_t launch_wino_f32(const IgemmDesc& d, ConvKernel k, hipStream_t s, const WinoHead* head = nullptr);   // k: one of the C++ Winograd kernels
+// patch means from the head-fused kernels' partial sums: out[node][c] = (psum[node][0][c] + ... + psum[node][7][c]) / 256
+hipError_t launch_patch_sum_combine(const float* psum, float* out, int nodes, hipStream_t s);
 // wino_asm.hip: the assembly forms of wino3x3_cp_kernel<2> and <1> (bitwise equal results; k: one of the WinoAsm* kernels)
-hipError_t launch_wino_cp_asm(const IgemmDesc& d, ConvKernel k, hipStream_t s);
+hipError_t launch_wino_cp_asm(const IgemmDesc& d, ConvKernel k, hipStream_t s, const WinoHead* head = nullptr);
 
 // wgrad_f32.hip:  Dw[n][k] += sum_m Z[m][n] * A(m,k)   (A = the forward kernels' im2col gather)
 struct WgradDesc {

@@ -75,6 +75,8 @@ struct mgu_ctx {
   int last_stat_rows = 0;   // accumulator rows the last statistics-fused conv launch wrote (run_layer)
   void* pm_out = nullptr;   // one-shot request (mgu_unet_request_patch_mean): patch means of decoder feature 0
   int pm_patch = 0;
+  void* pmws = nullptr;     // row-pair partial sums of the head-fused convolution (WinoHead::psum)
+  size_t pmws_bytes = 0;
   void* wuws = nullptr;     // Winograd weight scratch of the mgu_conv2d_nhwc building block
   size_t wuws_bytes = 0;
   unsigned long long* gmaxbuf = nullptr;   // GAT: [64 slots][gmax_cap] per-(graph, head) max accumulators, (generation, value) words
@@ -287,7 +289,8 @@ inline mgu::WgradDesc wgrad_desc(const mgu_ctx* c, const float* z, int ldz, cons
 int run_layer(mgu_ctx* c, const Layer& L, const void* in, int ldin, int B, int H, int W, void* out, int ldout, int coff,
               int relu, const float* scale, const float* shift, int Hout, int Wout, hipStream_t s,
               void* pool = nullptr, int ldpool = 0, bool* pool_fused = nullptr,   // optional fused MaxPool2d(2) output
-              double* stat_slots = nullptr, bool* stat_fused = nullptr);          // optional fused BatchNorm batch statistics
+              double* stat_slots = nullptr, bool* stat_fused = nullptr,           // optional fused BatchNorm batch statistics
+              const mgu::WinoHead* head = nullptr, bool* head_fused = nullptr);   // optional head-fused finishing pass (common.h)
 
 // GAT layer host code (gat_api.hip)
 void gat_destroy(mgu_ctx* c);

@@ -758,8 +758,7 @@ static bool wino_applicable(const IgemmDesc& d) {
 }
 
 // the assembly forms of wino3x3_cp_kernel (wino_asm.hip)
-static bool wino_asm_applicable(const IgemmDesc& d) {
-  if (!tun(d).wino_asm) return false;
+static bool wino_asm_shape(const IgemmDesc& d) {
   if (d.stat_slots) return false;   // (a missing scale / shift array is 1 / 0 in the kernels, as in the C++ epilogue)
   if (wino_wide(d)) {
     if (d.N & 63) return false;
@@ -773,6 +772,22 @@ static bool wino_asm_applicable(const IgemmDesc& d) {
   const WinoPlan p = wino_plan(d);
   if ((long)p.total * p.tiles_x * p.tiles_y >= (1l << 32) || (long)p.ngroups * p.nblk * p.ngroups >= (1l << 32)) return false;
   return true;
+}
+
+static bool wino_asm_applicable(const IgemmDesc& d) { return tun(d).wino_asm && wino_asm_shape(d); }
+
+// the head-fused finishing pass (both forms, so that MGU_WINO_ASM=0 stays on the fused route): the 2-chunk narrow kernel without a
+// fused pool, whole 16 x 16 graph patches, and every offset the kernels form in 32 bits below the out-of-range marker
+bool wino_head_layer(const Tuning& t, int dtype, int Cin, int ncls, int patch, int B, int H, int W) {
+  if (!t.head_fused || dtype != 0 || Cin != 32 || ncls < 1 || ncls > 4 || patch != 16 || B < 1 || (H & 15) || (W & 31)) return false;
+  return (long)H * W * ncls * 4 < 0x7fff0000l && wino_head_psum_bytes(B, H, W) < 0x7fff0000ul;
+}
+
+static bool wino_head_applicable(const IgemmDesc& d, const WinoHead& h) {
+  const int B = (int)(d.M / ((long)d.H * d.W));
+  if (!wino_head_layer(tun(d), 0, d.Cp, h.ncls, 16, B, d.H, d.W)) return false;
+  if (!wino_asm_shape(d) || wino_wide(d) || d.pool || d.ldout != 32 || d.coff) return false;
+  return h.w && h.b && h.logits && h.psum && (size_t)h.psum_bytes == wino_head_psum_bytes(B, d.H, d.W);
 }
 
 static bool convt_x3_applicable(const IgemmDesc& d) {
@@ -791,7 +806,7 @@ static bool convt_x3_dgrad_applicable(const IgemmDesc& d) {   // (N = the forwar
          !d.relu && !d.split_n && !d.pool && (long)d.M * d.ldout < (1l << 31) && (long)d.Hout * d.Wout * d.ldin < (1l << 31);
 }
 
-ConvKernel pick_conv(const IgemmDesc& d, int dtype) {
+ConvKernel pick_conv(const IgemmDesc& d, int dtype, const WinoHead* head) {
   using K = ConvKernel;
   if (d.M <= 0 || d.N <= 0) return K::None;   // (nothing to launch)
   if (dtype == 1) {
@@ -809,6 +824,7 @@ ConvKernel pick_conv(const IgemmDesc& d, int dtype) {
     // the component-pair kernels address the image through buffer descriptors: its bytes must stay below the out-of-image marker
     if (!t.wino_cp || (long)d.H * d.W * d.ldin * 4 >= 0x7fff0000l) return wide ? K::WinoX3Wide : K::WinoX3Narrow;
     if (d.stat_slots) return wide ? K::WinoCp2Stats : K::WinoCp1Stats;   // training forward: statistics in the epilogue
+    if (head && wino_head_applicable(d, *head)) return t.wino_asm ? K::WinoAsmCp1r2Head : K::WinoCp1Head;
     if (wino_asm_applicable(d)) return wide ? K::WinoAsmWide : d.Cp == 32 ? K::WinoAsmCp1r2 : K::WinoAsmCp1r4;
     return wide ? K::WinoCp2 : K::WinoCp1;
   }
@@ -821,6 +837,8 @@ const char* conv_kernel_name(ConvKernel k, const IgemmDesc& d) {
     case ConvKernel::WinoAsmWide: return "mgu_wino_cp2_gfx950 (asm form of wino3x3_cp_kernel<2>)";
     case ConvKernel::WinoAsmCp1r2: return "mgu_wino_cp1r2_gfx950 (asm form of wino3x3_cp_kernel<1>)";
     case ConvKernel::WinoAsmCp1r4: return "mgu_wino_cp1r4_gfx950 (asm form of wino3x3_cp_kernel<1>)";
+    case ConvKernel::WinoAsmCp1r2Head: return "mgu_wino_cp1r2h_gfx950 (asm form of wino3x3_cp_kernel<1, head>: + 1x1 head + patch sums)";
+    case ConvKernel::WinoCp1Head: return "wino3x3_cp_kernel<1, head> (+ 1x1 head + patch sums)";
     case ConvKernel::WinoCp2: case ConvKernel::WinoCp2Stats: return "wino3x3_cp_kernel<2>";
     case ConvKernel::WinoCp1: case ConvKernel::WinoCp1Stats: return "wino3x3_cp_kernel<1>";
     case ConvKernel::WinoF32Wide: return "wino3x3_f32_kernel<0,0>";
@@ -843,6 +861,7 @@ const char* conv_dgrad_name(ConvKernel k, const IgemmDesc& d) {
   switch (k) {
     case ConvKernel::WinoAsmWide: case ConvKernel::WinoCp2: case ConvKernel::WinoCp2Stats: return "wino3x3_cp_kernel<2> (dgrad)";
     case ConvKernel::WinoAsmCp1r2: case ConvKernel::WinoAsmCp1r4: case ConvKernel::WinoCp1: case ConvKernel::WinoCp1Stats:
+    case ConvKernel::WinoAsmCp1r2Head: case ConvKernel::WinoCp1Head:
       return "wino3x3_cp_kernel<1> (dgrad)";
     case ConvKernel::WinoX3Wide: case ConvKernel::WinoX3Narrow: return "wino3x3_f32_kernel<*,1> (dgrad)";
     case ConvKernel::WinoF32Wide: case ConvKernel::WinoF32Narrow: return "wino3x3_f32_kernel<*,0> (dgrad)";
@@ -866,15 +885,18 @@ ConvCost conv_cost(ConvKernel k, const IgemmDesc& d) {
   }
 }
 
-hipError_t launch_conv(const IgemmDesc& d, ConvKernel k, int dtype, hipStream_t s) {
+hipError_t launch_conv(const IgemmDesc& d, ConvKernel k, int dtype, hipStream_t s, const WinoHead* head) {
   if (d.M <= 0 || d.N <= 0) return hipSuccess;
   if (dtype == 1) {   // bf16 storage, fp32 accumulate (inference): Cp % 8 == 0, Kp % 64 == 0; scale/shift stay fp32
     if ((d.Cp & 7) || (d.ldin & 7) || (d.Kp % 64) || d.K > d.Kp || d.split_n) return hipErrorInvalidValue;
   } else {
     if ((d.Cp & 3) || (d.ldin & 3) || (d.Kp % 32) || d.K > d.Kp) return hipErrorInvalidValue;
   }
+  if (conv_fuses_head(k) != (head != nullptr)) return hipErrorInvalidValue;   // a head-fused kernel and its arguments go together
   switch (k) {
     case ConvKernel::WinoAsmWide: case ConvKernel::WinoAsmCp1r2: case ConvKernel::WinoAsmCp1r4: return launch_wino_cp_asm(d, k, s);
+    case ConvKernel::WinoAsmCp1r2Head: return launch_wino_cp_asm(d, k, s, head);
+    case ConvKernel::WinoCp1Head: return launch_wino_f32(d, k, s, head);
     case ConvKernel::WinoCp2: case ConvKernel::WinoCp1: case ConvKernel::WinoCp2Stats: case ConvKernel::WinoCp1Stats:
     case ConvKernel::WinoF32Wide: case ConvKernel::WinoF32Narrow: case ConvKernel::WinoX3Wide: case ConvKernel::WinoX3Narrow:
       return launch_wino_f32(d, k, s);

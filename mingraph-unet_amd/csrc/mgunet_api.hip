@@ -106,6 +106,7 @@ int mgu_create(int device_id, mgu_ctx** out) {
   t.wino_dgrad = !flag("MGU_NO_WINO_DGRAD");
   t.gat_fused = !flag("MGU_NO_GAT_FUSED");
   t.wino_asm = num("MGU_WINO_ASM", 1) > 0;
+  t.head_fused = num("MGU_HEAD_FUSED", 1) > 0;
   *out = c;
   return MGU_OK;
 }
@@ -118,6 +119,7 @@ void mgu_destroy(mgu_ctx* c) {
   if (c->arena) (void)hipFree(c->arena);
   if (c->ws) (void)hipFree(c->ws);
   if (c->gws) (void)hipFree(c->gws);
+  if (c->pmws) (void)hipFree(c->pmws);
   if (c->gbws) (void)hipFree(c->gbws);
   if (c->pack_dev) (void)hipFree(c->pack_dev);
   if (c->tws) (void)hipFree(c->tws);
@@ -394,8 +396,10 @@ int mgud::repack_weights(mgu_ctx* c, hipStream_t s) {
 
 int mgud::run_layer(mgu_ctx* c, const Layer& L, const void* in_v, int ldin, int B, int H, int W, void* out_v, int ldout,
                     int coff, int relu, const float* scale, const float* shift, int Hout, int Wout, hipStream_t s,
-                    void* pool, int ldpool, bool* pool_fused, double* stat_slots, bool* stat_fused) {
+                    void* pool, int ldpool, bool* pool_fused, double* stat_slots, bool* stat_fused, const WinoHead* head,
+                    bool* head_fused) {
   IgemmDesc d = layer_desc(c, L, in_v, ldin, B, H, W, out_v, ldout, coff);
+  if (head_fused) *head_fused = false;
   d.scale = scale, d.shift = shift, d.relu = relu, d.Hout = Hout, d.Wout = Wout;
   if (pool_fused) *pool_fused = false;
   if (stat_fused) *stat_fused = false;
@@ -411,7 +415,7 @@ int mgud::run_layer(mgu_ctx* c, const Layer& L, const void* in_v, int ldin, int 
     HIPCHK(c, launch_first_conv(c->dtype, in_v, L.wf, scale, shift, out_v, B, H, W, L.Cin, L.Cout, ldout, coff, relu, s));
     return MGU_OK;
   }
-  ConvKernel k = pick_conv(d, c->dtype);
+  ConvKernel k = pick_conv(d, c->dtype, head);
   // the Winograd epilogue also accumulates sum z, sum z^2: one accumulator row per workgroup, so only while the launch's grid fits
   // the table (>= 19 images of 512^2 or 5 of 1024^2 per GPU on the full-resolution 32-channel layer, or a small MGU_WINO_PPB_CAP, do
   // not: the caller then takes the separate statistics pass, launch_bn_stats)
@@ -424,25 +428,28 @@ int mgud::run_layer(mgu_ctx* c, const Layer& L, const void* in_v, int ldin, int 
     d.pool = (float*)pool, d.ldpool = ldpool;
     if (pool_fused) *pool_fused = true;
   }
-  if (d.stat_slots || d.pool) k = pick_conv(d, c->dtype);   // the fused epilogue narrows the choice (not every kernel form has it)
+  if (d.stat_slots || d.pool) k = pick_conv(d, c->dtype, head);   // the fused epilogue narrows the choice (not every kernel form has it)
+  if (!conv_fuses_head(k)) head = nullptr;   // the caller runs the head and the patch means in their own pass
+  else if (head_fused) *head_fused = true;
   if (L.wp_dirty && conv_reads_panel(k)) {   // falling back to the direct kernel: build its panel now
     if (L.convt) HIPCHK(c, launch_pack_convt_w(L.w_src, L.wp, c->dtype, L.Cin, L.Cout, L.Kp, s));
     else HIPCHK(c, launch_pack_conv_w(L.w_src, L.wp, c->dtype, L.Cout, L.Cin, L.Cp, L.KS, L.Kp, s));
     L.wp_dirty = false;
   }
   // profiling record: algorithmic 2*MAC of the operator and what the matrix pipe really issues
-  const double alg = L.convt ? 2.0 * d.M * (double)L.Cin * L.Cout * 4.0 : 2.0 * d.M * (double)L.KS * L.KS * L.Cin * L.Cout;
+  double alg = L.convt ? 2.0 * d.M * (double)L.Cin * L.Cout * 4.0 : 2.0 * d.M * (double)L.KS * L.KS * L.Cin * L.Cout;
+  if (head) alg += 2.0 * d.M * (double)L.Cout * head->ncls;   // the 1x1 head's work rides in this launch
   const ConvCost cost = conv_cost(k, d);
   ProfScope ps(c, s, conv_kernel_name(k, d), alg, cost.mfma, cost.pipe);
-  HIPCHK(c, launch_conv(d, k, c->dtype, s));
+  HIPCHK(c, launch_conv(d, k, c->dtype, s, head));
   return MGU_OK;
 }
 
 static int run_conv(mgu_ctx* c, const Layer& L, const void* in, int ldin, int B, int H, int W, void* out, int ldout,
                     int coff, int relu, int Hout, int Wout, hipStream_t s, void* pool = nullptr, int ldpool = 0,
-                    bool* pool_fused = nullptr) {  // eval: folded BN scale/shift
+                    bool* pool_fused = nullptr, const WinoHead* head = nullptr, bool* head_fused = nullptr) {  // eval: folded BN scale/shift
   return run_layer(c, L, in, ldin, B, H, W, out, ldout, coff, relu, L.bn.empty() ? nullptr : L.scale, L.shift, Hout, Wout, s,
-                   pool, ldpool, pool_fused, nullptr, nullptr);
+                   pool, ldpool, pool_fused, nullptr, nullptr, head, head_fused);
 }
 
 extern "C" {
@@ -466,6 +473,7 @@ int mgu_unet_forward(mgu_ctx* c, const void* x_dev, int B, int H, int W, int64_t
   if (training) {  // batch-statistics BatchNorm, running-stat update, activations kept for mgu_unet_backward
     int rc = unet_forward_train(c, (const float*)x_dev, xs_n, xs_c, xs_h, xs_w, B, H, W, (float*)logits_dev, cat_dev, feat_dev, s);
     if (rc == MGU_OK && c->pm_out) {   // a pending patch-mean request is served by the stand-alone kernel
+      ProfScope ps(c, s, "patch_mean_kernel", 0, 0, -1);
       HIPCHK(c, launch_patch_mean(feat_dev[0], 0, (float*)c->pm_out, B, H, W, c->feat, c->pm_patch, s));
       c->pm_out = nullptr;
     }
@@ -474,6 +482,17 @@ int mgu_unet_forward(mgu_ctx* c, const void* x_dev, int B, int H, int W, int64_t
   const WsPlan plan = plan_ws(c, B, H, W);
   int rc = ensure(c, &c->ws, &c->ws_bytes, plan.total);
   if (rc) return rc;
+  // A pending patch-mean request at the graph's 16-pixel patch: the convolution that writes decoder feature 0 also applies the final
+  // 1x1 conv and sums the graph patches in its finishing pass, if the pick admits it (wino_head_layer sizes the scratch, pick_conv
+  // decides on the complete descriptor); the second pass over the 32-channel feature map and the head kernel then fall away
+  const Layer& F = c->layers[c->head];
+  WinoHead head_args{};
+  bool head_done = false;
+  const bool head_wanted = c->pm_out && F.w_src && F.b_src && wino_head_layer(c->tn, c->dtype, F.Cin, c->ncls, c->pm_patch, B, H, W);
+  if (head_wanted) {
+    if ((rc = ensure(c, &c->pmws, &c->pmws_bytes, wino_head_psum_bytes(B, H, W)))) return rc;
+    head_args = WinoHead{F.w_src, F.b_src, (float*)logits_dev, (float*)c->pmws, c->ncls, (int)wino_head_psum_bytes(B, H, W)};
+  }
   if (c->fold_dirty) {  // eval BatchNorm: y = scale * conv + shift with the CURRENT running statistics
     for (auto& L : c->layers)
       if (!L.bn.empty()) HIPCHK(c, launch_bn_fold(L.b_src, L.gamma, L.beta, L.run_mean, L.run_var, 1e-5f, L.scale, L.shift, L.Cout, s));
@@ -534,19 +553,25 @@ int mgu_unet_forward(mgu_ctx* c, const void* x_dev, int B, int H, int W, int64_t
   }
   for (const Block& b : c->dec) {  // decoder, unet_decoder.py:139-141
     const int i = b.level, C = c->layers[b.conv1].Cout;
+    const bool last = head_wanted && i == 0;
     // ConvTranspose2d(k2,s2) -> pixel-shuffle store into channels [C, 2C) of the concat buffer (:36,:53)
     if ((rc = run_conv(c, c->layers[b.up], cur, cur_ld, B, hs[i + 1], wsz[i + 1], cat_dev[i], 2 * C, C, 0, hs[i], wsz[i], s)))
       return rc;
     if ((rc = run_conv(c, c->layers[b.conv1], cat_dev[i], 2 * C, B, hs[i], wsz[i], tmp, C, 0, 1, 0, 0, s))) return rc;
-    if ((rc = run_conv(c, c->layers[b.conv2], tmp, C, B, hs[i], wsz[i], feat_dev[i], C, 0, 1, 0, 0, s))) return rc;
+    if ((rc = run_conv(c, c->layers[b.conv2], tmp, C, B, hs[i], wsz[i], feat_dev[i], C, 0, 1, 0, 0, s, nullptr, 0, nullptr,
+                       last ? &head_args : nullptr, last ? &head_done : nullptr)))
+      return rc;
     cur = feat_dev[i];
     cur_ld = C;
   }
   // final 1x1 conv (:143): a few output channels -> HBM-bound head kernel reading the reference's (ncls, C) weight
-  const Layer& F = c->layers[c->head];
   {
     const int pm_dtype = c->dtype;   // decoder features are stored in the compute dtype
-    if (c->pm_out && F.w_src && F.b_src && patch_mean_head_fusable(pm_dtype, F.Cin, c->ncls) && F.Cin <= 256) {
+    if (head_done) {   // logits are written; the patch means are the fixed-order sum of the eight row-pair partials of every node
+      ProfScope ps(c, s, "patch_sum_combine_kernel", 0, 0, -1);
+      HIPCHK(c, launch_patch_sum_combine((const float*)c->pmws, (float*)c->pm_out, B * (H / 16) * (W / 16), s));
+      c->pm_out = nullptr;
+    } else if (c->pm_out && F.w_src && F.b_src && patch_mean_head_fusable(pm_dtype, F.Cin, c->ncls) && F.Cin <= 256) {
       // requested patch means + the 1x1 head in ONE pass over the decoder feature (both are pure bandwidth)
       ProfScope ps(c, s, "patch_mean_kernel (1x1 head + patch means)", 2.0 * B * H * W * F.Cin * c->ncls, 0, -1);
       HIPCHK(c, launch_patch_mean(cur, pm_dtype, (float*)c->pm_out, B, H, W, F.Cin, c->pm_patch, s, F.w_src, F.b_src,
@@ -561,6 +586,7 @@ int mgu_unet_forward(mgu_ctx* c, const void* x_dev, int B, int H, int W, int64_t
     }
   }
   if (c->pm_out) {   // request not served by the fused pass (head shape): separate kernel, same result
+    ProfScope ps(c, s, "patch_mean_kernel", 0, 0, -1);
     HIPCHK(c, launch_patch_mean(cur, c->dtype, (float*)c->pm_out, B, H, W, F.Cin, c->pm_patch, s));
     c->pm_out = nullptr;
   }

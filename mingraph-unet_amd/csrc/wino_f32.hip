@@ -780,9 +780,19 @@ constexpr int WINO_CP_RAWF = 8192;
 // URES (DEEP with exactly two chunks, i.e. 32 input channels): the two register sets of weight pieces hold the layer's WHOLE
 // transformed filter slice of this wave, so they are loaded once per workgroup and never again -- no weight-piece load sits in
 // the in-order memory pipe behind the halo loads and the epilogue's stores.
-template <int NTB, bool STATS, bool DEEP, bool URES = false>
+// HEAD (the 2-chunk narrow inference kernel only; every patch interior): the finishing pass also applies the final 1x1 conv to the
+// pixels it holds and adds them into their graph patch's sums (WinoHead, common.h) -- the C++ twin of mgu_wino_cp1r2h_gfx950
+// (asm/gen_wino_cp.py: emit_head_math), operation for operation: features, logits and partial sums are bitwise equal.
+// (The WinoHead argument is a parameter pack of zero or one element, so that only the head-fused instantiation carries it: the plain
+// instantiations keep their argument block and their code.)
+__device__ inline WinoHead wino_head_of() { return WinoHead{}; }
+__device__ inline WinoHead wino_head_of(const WinoHead& h) { return h; }
+template <int NTB, bool STATS, bool DEEP, bool URES = false, typename... HD>
 __global__ __launch_bounds__(512) void wino3x3_cp_kernel(const IgemmDesc d, const int tiles_x, const int tiles_y, const int total_patches,
-                        const int patches_per_block, const int ngroups, const int nitems, const int per_xcd) {
+                        const int patches_per_block, const int ngroups, const int nitems, const int per_xcd, const HD... hd_args) {
+  constexpr bool HEAD = sizeof...(HD) == 1;
+  const WinoHead hd = wino_head_of(hd_args...);
+  static_assert(!HEAD || (NTB == 1 && !STATS && URES), "the head-fused finishing pass belongs to the 2-chunk narrow inference kernel");
   constexpr int NWAVES = 8;
   constexpr int MT = 2;                          // both m tiles of the 8 x 32 pixel patch
   constexpr int NC = 32 * NTB;                   // output channels per workgroup
@@ -1232,6 +1242,46 @@ __global__ __launch_bounds__(512) void wino3x3_cp_kernel(const IgemmDesc d, cons
               }
           }
       }
+      if constexpr (HEAD) {
+        // pixel p = 2 * row + column of the unit's 2 x 2 tile; the eight lanes cq = 0..7 of a tile hold its 32 channels
+        const f32x4 Y[4] = {ya[0], ya[1], yb[0], yb[1]};
+        float lg[4][4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (k >= hd.ncls) break;   // (uniform)
+          const f32x4 wq = *reinterpret_cast<const f32x4*>(hd.w + k * 32 + cq * 4);
+          const float bl = cq == 0 ? hd.b[k] : 0.f;   // the bias enters the fold once, at the start of channel quad 0's chain
+#pragma unroll
+          for (int p = 0; p < 4; ++p) {
+            float ds = __builtin_fmaf(Y[p][0], wq[0], bl);
+            ds = __builtin_fmaf(Y[p][1], wq[1], ds);
+            ds = __builtin_fmaf(Y[p][2], wq[2], ds);
+            ds = __builtin_fmaf(Y[p][3], wq[3], ds);
+            ds += __shfl_xor(ds, 1);
+            ds += __shfl_xor(ds, 2);
+            ds += __shfl_xor(ds, 4);
+            lg[k][p] = ds;
+          }
+        }
+        if (cq < 2) {   // quad 0 stores the tile's upper row, quad 1 the lower one: [column][class] is the NHWC order
+          float* lp = hd.logits + ((size_t)(img * d.H + oy + cq) * d.W + ox) * hd.ncls;
+#pragma unroll
+          for (int pp = 0; pp < 2; ++pp)
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+              if (k < hd.ncls) lp[pp * hd.ncls + k] = cq ? lg[k][2 + pp] : lg[k][pp];
+        }
+        // the wave's eight tiles are 2 rows x 16 columns of one 16 x 16 graph patch: their sum is partial (oy >> 1) & 7 of the node
+        f32x4 ps = (Y[0] + Y[1]) + (Y[2] + Y[3]);
+#pragma unroll
+        for (int o = 8; o < 64; o <<= 1)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) ps[e] += __shfl_xor(ps[e], o);
+        if ((T & 7) == 0) {
+          const int node = (img * (d.H >> 4) + (oy >> 4)) * (d.W >> 4) + (ox >> 4);
+          *reinterpret_cast<f32x4*>(hd.psum + ((size_t)(node * 8 + ((oy >> 1) & 7)) * 32 + cq * 4)) = ps;
+        }
+      }
       if (d.pool) {
         // the 2x2 output tile IS a pooling window (floor semantics: only complete windows)
         f32x4 m;
@@ -1297,18 +1347,45 @@ WinoPlan wino_plan(const IgemmDesc& d) {
 
 int wino_grid_blocks(const IgemmDesc& d) { return 8 * wino_plan(d).per_xcd; }
 
-template <int NTB, bool STATS, bool DEEP = false, bool URES = false>
-static hipError_t launch_wino_cp(const IgemmDesc& d, hipStream_t s) {
+// one thread per (node, channel): the eight row-pair partials of the head-fused kernels in a fixed order, then the mean
+__global__ __launch_bounds__(256) void patch_sum_combine_kernel(const float* __restrict__ psum, float* __restrict__ out, const int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float* p = psum + (size_t)(i >> 5) * 256 + (i & 31);
+  float sum = p[0];
+#pragma unroll
+  for (int r = 1; r < 8; ++r) sum += p[r * 32];
+  out[i] = sum / 256.f;
+}
+
+hipError_t launch_patch_sum_combine(const float* psum, float* out, int nodes, hipStream_t s) {
+  const int n = nodes * 32;
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(patch_sum_combine_kernel, dim3((n + 255) / 256), dim3(256), 0, s, psum, out, n);
+  return hipGetLastError();
+}
+
+template <int NTB, bool STATS, bool DEEP = false, bool URES = false, bool HEAD = false>
+static hipError_t launch_wino_cp(const IgemmDesc& d, hipStream_t s, const WinoHead* head = nullptr) {
+  static_assert(!HEAD || (NTB == 1 && !STATS && DEEP && URES), "the head-fused entry point is the 2-chunk narrow inference kernel");
   constexpr int NWAVES = 8;
   const WinoPlan p = wino_plan(d);
   dim3 grid(8 * p.per_xcd, 1);
   if (d.stat_slots && grid.x > (unsigned)STAT_ROWS) return hipErrorInvalidValue;   // one accumulator row per workgroup (common.h)
   const size_t lds = (size_t)(5 * WINO_CP_RAWF) * sizeof(float);   // two raw buffers + three exchange regions = the CU's 160 KB
   static bool attr_done[64] = {};
-  hipError_t ae = ensure_dyn_lds(reinterpret_cast<const void*>(&wino3x3_cp_kernel<NTB, STATS, DEEP, URES>), lds, attr_done);
-  if (ae != hipSuccess) return ae;
-  hipLaunchKernelGGL((wino3x3_cp_kernel<NTB, STATS, DEEP, URES>), grid, dim3(64 * NWAVES), lds, s, d, p.tiles_x, p.tiles_y, p.total,
-                     p.ppb, p.ngroups, p.ngroups * p.nblk, p.per_xcd);
+  if (HEAD != (head != nullptr)) return hipErrorInvalidValue;
+  if constexpr (HEAD) {
+    hipError_t ae = ensure_dyn_lds(reinterpret_cast<const void*>(&wino3x3_cp_kernel<NTB, STATS, DEEP, URES, WinoHead>), lds, attr_done);
+    if (ae != hipSuccess) return ae;
+    hipLaunchKernelGGL((wino3x3_cp_kernel<NTB, STATS, DEEP, URES, WinoHead>), grid, dim3(64 * NWAVES), lds, s, d, p.tiles_x, p.tiles_y,
+                       p.total, p.ppb, p.ngroups, p.ngroups * p.nblk, p.per_xcd, *head);
+  } else {
+    hipError_t ae = ensure_dyn_lds(reinterpret_cast<const void*>(&wino3x3_cp_kernel<NTB, STATS, DEEP, URES>), lds, attr_done);
+    if (ae != hipSuccess) return ae;
+    hipLaunchKernelGGL((wino3x3_cp_kernel<NTB, STATS, DEEP, URES>), grid, dim3(64 * NWAVES), lds, s, d, p.tiles_x, p.tiles_y, p.total,
+                       p.ppb, p.ngroups, p.ngroups * p.nblk, p.per_xcd);
+  }
   return hipGetLastError();
 }
 
@@ -1329,8 +1406,9 @@ static hipError_t launch_wino_mode(const IgemmDesc& d, hipStream_t s) {
   return hipGetLastError();
 }
 
-hipError_t launch_wino_f32(const IgemmDesc& d, ConvKernel k, hipStream_t s) {
+hipError_t launch_wino_f32(const IgemmDesc& d, ConvKernel k, hipStream_t s, const WinoHead* head) {
   switch (k) {
+    case ConvKernel::WinoCp1Head: return launch_wino_cp<1, false, true, true, true>(d, s, head);
     // training forward (fused statistics): the one-chunk load lead (DEEP + RPF + statistics spills 4 registers)
     case ConvKernel::WinoCp2Stats: return launch_wino_cp<2, true>(d, s);
     case ConvKernel::WinoCp1Stats: return launch_wino_cp<1, true>(d, s);
