@@ -499,6 +499,38 @@ int mgu_tta_views(mgu_ctx* ctx, const float* img_dev, int B, int C, int H, int W
 int mgu_tta_merge(mgu_ctx* ctx, const float* logits0_dev, const float* logits1_dev, int B, int C, int H, int W, int K, const int32_t* views,
                   float* probs_dev, int64_t* labels_dev, float* conf_dev, void* hip_stream);
 
+/* ---- tiled inference: an image larger than the network's input runs as overlapping tiles blended into one canvas -----------------
+ * Grid, per axis (mgunet.tiled.tile_grid): image length L, tile T, overlap o with 0 <= o < T, stride S = T - o.  L <= T: one tile at
+ * origin 0.  Otherwise ceil((L - T) / S) + 1 tiles, origins k S and, for the last, L - T.  The grid of an (H, W) image is the product
+ * of the axes (nrows x ncols); tile t of a batch is image t / (nrows ncols), row-major within it.  Every entry point takes the tile
+ * (Th, Tw) and the overlaps; the tile counts and origins follow from them, H and W by the rule above, on the host and in the
+ * kernels alike (no origin table is passed); [t0, t0 + n) must lie inside B * nrows * ncols.  Refused (MGU_ERR_INVALID): an overlap
+ * outside [0, T), a tile range outside the grid, NULL buffers, sizes < 1, more than 2^30 tiles.
+ * Gather: writes tiles [t0, t0 + n) of the (B,C,H,W) fp32 batch img_dev (element (b,c,y,x) at [b*s[0] + c*s[1] + y*s[2] + x*s[3]],
+ * in_strides a HOST array of 4) as one contiguous NCHW batch out_dev (n, C, Th, Tw), 16-byte aligned.  A tile pixel past the image
+ * (only when L < T) reads it by reflect-101 folding, repeated as often as needed (numpy.pad(mode="reflect")); L = 1 reads index 0. */
+int mgu_tile_gather(mgu_ctx* ctx, const float* img_dev, int B, int C, int H, int W, const int64_t* in_strides, int Th, int Tw, int overlap_y,
+                    int overlap_x, int t0, int n, float* out_dev, void* hip_stream);
+/* The same from HWC uint8 images (B, H, W, 3) contiguous, through ToTensor (/255) and Normalize exactly as mgu_preprocess_image_u8
+ * applies them: channel c of the output reads byte 2 - c when bgr, mean3 / std3 HOST arrays of 3 floats.  out_dev (n, 3, Th, Tw). */
+int mgu_tile_gather_u8(mgu_ctx* ctx, const uint8_t* img_dev, int B, int H, int W, int bgr, const float* mean3, const float* std3, int Th, int Tw,
+                       int overlap_y, int overlap_x, int t0, int n, float* out_dev, void* hip_stream);
+/* Accumulate: adds tiles [t0, t0 + n) to the canvas acc_dev, NHWC fp32 (B,H,W,C), 16-byte aligned.  tiles_dev: NHWC fp32
+ * (n, Th, Tw, C), the forward's logits of the gathered chunk (is_prob 0: each pixel's softmax is taken in fp32, maximum subtracted,
+ * expf, as mgu_tta_merge takes it) or probabilities used as they are (is_prob 1).  wy_dev / wx_dev: DEVICE fp32 (nrows, Th) /
+ * (ncols, Tw), the per-axis window weights already divided by their sum over the tiles covering each image coordinate
+ * (mgunet.tiled.tile_weights); a pixel's weight is the fp32 product of its two entries.  For every pixel of the image that a tile
+ * of the chunk covers: acc = (its first covering tile of the whole grid lies in the chunk ? 0 : acc_dev) + sum of weight * p over
+ * the chunk's covering tiles in ascending tile number; other pixels (and tile pixels past the image) are not touched.  So chunks
+ * must be given in ascending order, each tile once; the canvas needs no clearing, and the result is bitwise the same however the
+ * tiles are split into chunks.  No atomics.  labels_dev int64 (B,H,W) / conf_dev fp32 (B,H,W), both or neither: a pixel whose last
+ * covering tile lies in the chunk also gets its first maximal class and that class's value (mgu_tile_finish's result).  C <= 16. */
+int mgu_tile_accumulate(mgu_ctx* ctx, const float* tiles_dev, int is_prob, int B, int C, int H, int W, int Th, int Tw, int overlap_y, int overlap_x,
+                        const float* wy_dev, const float* wx_dev, int t0, int n, float* acc_dev,
+                        int64_t* labels_dev, float* conf_dev, void* hip_stream);
+/* Finish, for a canvas accumulated without labels_dev / conf_dev: the first maximal class and its value at every pixel.  C <= 16. */
+int mgu_tile_finish(mgu_ctx* ctx, const float* acc_dev, int B, int C, int H, int W, int64_t* labels_dev, float* conf_dev, void* hip_stream);
+
 /* ---- resize / gather building blocks of FeatureFusion (model/fusion_detection/feature_fusion.py:43-162) ----------------------------
  * F.interpolate(mode='bilinear', align_corners=False) (:69-76, :140-144) of an NHWC fp32 map (B,Hi,Wi,C) with pixel pitch ld_in into
  * channels [c_off, c_off + C) of a (B,Ho,Wo,ld_out) buffer -- i.e. straight into its slice of the fused tensor. */

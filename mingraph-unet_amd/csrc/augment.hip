@@ -119,9 +119,7 @@ __global__ __launch_bounds__(256) void to_tensor_normalize_aug_kernel(const uint
     const bool ok = aug_src(rot.a0, rot.a1, rot.a2, rot.a3, rot.a4, rot.a5, rot.flip, x, y, W, H, &xs, &ys);
     const int sc = Cin == 1 ? 0 : (bgr ? 2 - c : c);
     const uint8_t u = ok ? in[((int64_t)ys * W + xs) * Cin + sc] : (uint8_t)0;
-    const float v = (float)u / 255.f;
-    const float mean = c == 0 ? m0 : (c == 1 ? m1 : m2), sd = c == 0 ? s0 : (c == 1 ? s1 : s2);
-    out[c * os_c + y * os_h + x * os_w] = (v - mean) / sd;
+    out[c * os_c + y * os_h + x * os_w] = u8_normalize(u, c, m0, m1, m2, s0, s1, s2);
   }
 }
 

@@ -1,6 +1,6 @@
 // Device helpers shared by the kernel files: each is defined here and nowhere else under csrc/ (tests/test_csrc_helpers.py).
 //   vector types | three-way bf16 operand split and the bf16 MFMA | LDS hand-off barriers | wave and workgroup reductions |
-//   order-preserving float encoding | node -> graph search
+//   order-preserving float encoding | per-pixel softmax and byte normalisation | node -> graph search
 // common.h includes this header, so every translation unit sees it.  The GAT-specific slotted max accumulators and the DPP
 // reductions built on them are in gat_common.h.
 #pragma once
@@ -133,6 +133,35 @@ __device__ __forceinline__ unsigned enc_ordered(float f) {
 }
 __device__ __forceinline__ float dec_ordered(unsigned u) {
   return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
+}
+
+// ---- per-pixel arithmetic shared by the inference glue (tta.hip, tiled.hip; imageops.hip, augment.hip) --------------------------
+// the softmax of one pixel's C <= CM logits at p, up to its normalisation: e[c] = expf(p[c] - max) in fp32, returns their sum; the
+// probability of class c is e[c] / sum
+template <int CM>
+__device__ __forceinline__ float pixel_softmax(const float* p, int C, float (&e)[CM]) {
+  float l[CM];
+  float m = p[0];
+#pragma unroll
+  for (int c = 0; c < CM; ++c)
+    if (c < C) {
+      l[c] = p[c];
+      m = fmaxf(m, l[c]);
+    }
+  float sum = 0.f;
+#pragma unroll
+  for (int c = 0; c < CM; ++c)
+    if (c < C) {
+      e[c] = expf(l[c] - m);
+      sum += e[c];
+    }
+  return sum;
+}
+// torchvision's ToTensor (/255) and Normalize of one byte of channel c in {0, 1, 2}, given the three means and standard deviations
+__device__ __forceinline__ float u8_normalize(uint8_t u, int c, float m0, float m1, float m2, float s0, float s1, float s2) {
+  const float v = (float)u / 255.f;
+  const float mean = c == 0 ? m0 : (c == 1 ? m1 : m2), sd = c == 0 ? s0 : (c == 1 ? s1 : s2);
+  return (v - mean) / sd;
 }
 
 // graph of a node: binary search over graph_ptr (gp[g] <= node < gp[g + 1]); no graph_ptr or one graph: 0

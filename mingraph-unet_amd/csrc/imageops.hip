@@ -120,9 +120,7 @@ __global__ __launch_bounds__(256) void to_tensor_normalize_kernel(const uint8_t*
     const int64_t pix = i / 3;
     const int x = (int)(pix % W), y = (int)(pix / W);
     const int sc = Cin == 1 ? 0 : (bgr ? 2 - c : c);       // grey -> three equal channels (cv2.COLOR_GRAY2RGB, :79-80)
-    const float v = (float)in[pix * Cin + sc] / 255.f;
-    const float mean = c == 0 ? m0 : (c == 1 ? m1 : m2), sd = c == 0 ? s0 : (c == 1 ? s1 : s2);
-    out[c * os_c + y * os_h + x * os_w] = (v - mean) / sd;
+    out[c * os_c + y * os_h + x * os_w] = u8_normalize(in[pix * Cin + sc], c, m0, m1, m2, s0, s1, s2);
   }
 }
 

@@ -90,22 +90,8 @@ __global__ __launch_bounds__(TTA_T * TTA_T) void tta_merge_kernel(TtaGroups g, i
     int i, j;
     tta_to_view(a, bb, r, H, W, &i, &j);
     const float* p = g.p[grp] + (((int64_t)(slot * B + b) * Hg + i) * Wg + j) * C;
-    float l[CM];
-    float m = p[0];
-#pragma unroll
-    for (int c = 0; c < CM; ++c)
-      if (c < C) {
-        l[c] = p[c];
-        m = fmaxf(m, l[c]);
-      }
     float e[CM];
-    float sum = 0.f;
-#pragma unroll
-    for (int c = 0; c < CM; ++c)
-      if (c < C) {
-        e[c] = expf(l[c] - m);
-        sum += e[c];
-      }
+    const float sum = pixel_softmax<CM>(p, C, e);
 #pragma unroll
     for (int c = 0; c < CM; ++c)
       if (c < C) acc[c] += e[c] / sum;
