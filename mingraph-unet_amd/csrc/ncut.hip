@@ -42,13 +42,16 @@ constexpr int NCUT_SLOTS = 64;
 __global__ __launch_bounds__(256) void ncut_node_kernel(const float* __restrict__ F, int N, int D, const float* __restrict__ P, int K,
                                                         const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                         double* __restrict__ acc) {
-  __shared__ float part[4][2 * NCUT_MAX_K];
+  __shared__ double part[4][2 * NCUT_MAX_K];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = blockIdx.x * 4 + wave;
-  float cutp[NCUT_MAX_K];
+  // the node's sums are kept in double (each product stays one fp32 operation): cut_k / assoc_k enters EVERY edge's gradient
+  // through alpha_k (1 - P) + beta_k, which cancels, so a rounding of a hub's 70-term fp32 sum came back as the same error on all
+  // edges of a node in the backward (6e-6 of max|dX| on a 50-node graph with one hub of out-degree 75, 1.5e-6 with these sums)
+  double cutp[NCUT_MAX_K];
 #pragma unroll
-  for (int k = 0; k < NCUT_MAX_K; ++k) cutp[k] = 0.f;
-  float deg = 0.f;
+  for (int k = 0; k < NCUT_MAX_K; ++k) cutp[k] = 0.0;
+  double deg = 0.0;
   if (i < N) {   // wave-uniform
     const int e0 = rowptr[i], e1 = rowptr[i + 1];
     const float* fi = F + (size_t)i * D;
@@ -75,17 +78,17 @@ __global__ __launch_bounds__(256) void ncut_node_kernel(const float* __restrict_
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const float w = (e + u < e1) ? expf(-0.5f * d2[u]) : 0.f;
-        deg += w;
+        deg += (double)w;
 #pragma unroll
         for (int k = 0; k < NCUT_MAX_K; ++k)
-          if (k < K) cutp[k] += w * (1.f - P[(size_t)t[u] * K + k]);
+          if (k < K) cutp[k] += (double)(w * (1.f - P[(size_t)t[u] * K + k]));
       }
     }
   }
   if (lane == 0) {
 #pragma unroll
     for (int k = 0; k < NCUT_MAX_K; ++k) {
-      const float p = (i < N && k < K) ? P[(size_t)i * K + k] : 0.f;
+      const double p = (i < N && k < K) ? (double)P[(size_t)i * K + k] : 0.0;
       part[wave][k] = p * cutp[k];
       part[wave][NCUT_MAX_K + k] = p * deg;
     }
@@ -93,8 +96,8 @@ __global__ __launch_bounds__(256) void ncut_node_kernel(const float* __restrict_
   __syncthreads();
   if (threadIdx.x < 2 * K) {
     const int which = threadIdx.x / K, k = threadIdx.x - which * K;
-    const double s = (double)part[0][which * NCUT_MAX_K + k] + (double)part[1][which * NCUT_MAX_K + k] +
-                     (double)part[2][which * NCUT_MAX_K + k] + (double)part[3][which * NCUT_MAX_K + k];
+    const double s = part[0][which * NCUT_MAX_K + k] + part[1][which * NCUT_MAX_K + k] + part[2][which * NCUT_MAX_K + k] +
+                     part[3][which * NCUT_MAX_K + k];
     atomicAdd(acc + (size_t)(blockIdx.x % NCUT_SLOTS) * 2 * K + which * K + k, s);
   }
 }
@@ -105,14 +108,14 @@ __global__ __launch_bounds__(256) void ncut_node_kernel(const float* __restrict_
 __global__ __launch_bounds__(256) void ncut_node16_kernel(const float* __restrict__ F, int N, int D, const float* __restrict__ P, int K,
                                                           const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                           double* __restrict__ acc) {
-  __shared__ float part[16][2 * NCUT_MAX_K + 1];
+  __shared__ double part[16][2 * NCUT_MAX_K + 1];
   const int gl = threadIdx.x & 15, grp = threadIdx.x >> 4;
   const int i = blockIdx.x * 16 + grp;
   const bool live = i < N;
-  float cutp[NCUT_MAX_K];
+  double cutp[NCUT_MAX_K];   // per-node sums in double, see ncut_node_kernel
 #pragma unroll
-  for (int k = 0; k < NCUT_MAX_K; ++k) cutp[k] = 0.f;
-  float deg = 0.f;
+  for (int k = 0; k < NCUT_MAX_K; ++k) cutp[k] = 0.0;
+  double deg = 0.0;
   const int e0 = live ? rowptr[i] : 0, e1 = live ? rowptr[i + 1] : 0;
   const float* fi = F + (size_t)(live ? i : 0) * D;
   int emax = e1 - e0;   // the longest edge list of the wave decides the trip count (shuffles need all lanes)
@@ -141,16 +144,16 @@ __global__ __launch_bounds__(256) void ncut_node16_kernel(const float* __restric
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const float w = (e0 + eb + u < e1) ? expf(-0.5f * d2[u]) : 0.f;
-      deg += w;
+      deg += (double)w;
 #pragma unroll
       for (int k = 0; k < NCUT_MAX_K; ++k)
-        if (k < K) cutp[k] += w * (1.f - P[(size_t)t[u] * K + k]);
+        if (k < K) cutp[k] += (double)(w * (1.f - P[(size_t)t[u] * K + k]));
     }
   }
   if (gl == 0) {
 #pragma unroll
     for (int k = 0; k < NCUT_MAX_K; ++k) {
-      const float p = (live && k < K) ? P[(size_t)i * K + k] : 0.f;
+      const double p = (live && k < K) ? (double)P[(size_t)i * K + k] : 0.0;
       part[grp][k] = p * cutp[k];
       part[grp][NCUT_MAX_K + k] = p * deg;
     }
@@ -160,7 +163,7 @@ __global__ __launch_bounds__(256) void ncut_node16_kernel(const float* __restric
     const int which = threadIdx.x / K, k = threadIdx.x - which * K;
     double s = 0.0;
 #pragma unroll
-    for (int g = 0; g < 16; ++g) s += (double)part[g][which * NCUT_MAX_K + k];
+    for (int g = 0; g < 16; ++g) s += part[g][which * NCUT_MAX_K + k];
     atomicAdd(acc + (size_t)(blockIdx.x % NCUT_SLOTS) * 2 * K + which * K + k, s);
   }
 }
@@ -198,10 +201,12 @@ __global__ void ncut_coef_kernel(const double* __restrict__ acc, int K, const fl
   if (k >= K) return;
   double c = 0.0, a = 0.0;
   for (int sl = 0; sl < NCUT_SLOTS; ++sl) c += acc[(size_t)sl * 2 * K + k], a += acc[(size_t)sl * 2 * K + K + k];
-  const float cut = (float)c, assoc = (float)a, g = gloss ? *gloss : 1.f;
-  const bool kept = assoc > 1e-8f;   // :152
-  coef[k] = kept ? g / assoc : 0.f;
-  coef[NCUT_MAX_K + k] = kept ? -g * cut / (assoc * assoc) : 0.f;
+  const double g = gloss ? (double)*gloss : 1.0;
+  const bool kept = (float)a > 1e-8f;   // :152
+  // formed in double from the double sums and rounded once: alpha (1 - P) + beta cancels, and an error of alpha or beta is the
+  // same for every edge of a node, so it adds up along a hub's edge list (see the per-node sums of ncut_node_kernel)
+  coef[k] = kept ? (float)(g / a) : 0.f;
+  coef[NCUT_MAX_K + k] = kept ? (float)(-g * c / (a * a)) : 0.f;
 }
 
 __global__ __launch_bounds__(256) void ncut_bwd_node_kernel(const float* __restrict__ F, int N, int D, const float* __restrict__ P, int K,
