@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Static check of the hand-counted waits and wait states of the generated Winograd assembly (asm/gen_wino_cp.py).
+"""Static check of the hand-counted waits and wait states of the generated Winograd assembly (asm/gen_wino_cp.py: generate(head)).
 
 The hand-written kernels carry no compiler-inserted s_waitcnt / s_nop: every wait is counted by the generator.  This checker
 replays the instruction stream of each kernel's steady-state loops (the loop bodies repeated, branches taken as straight-line code) with the machine's

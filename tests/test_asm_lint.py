@@ -2,27 +2,9 @@
 every wait state is the generator's.  csrc/asm/lint_wino_asm.py replays the generated stream with the machine's in-order counters;
 this test (CPU only: it needs neither a GPU nor the assembler) runs it on what the generator emits now and on deliberately broken
 streams -- the lint must pass the first and catch the seeded faults."""
-import importlib.util
-import os
 import re
-import subprocess
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ASM = os.path.join(ROOT, "mingraph-unet_amd", "csrc", "asm")
-
-
-def _load(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ASM, name + ".py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
-
-
-def _generate(tmp_path):
-    out = tmp_path / "k.s"
-    subprocess.run([sys.executable, os.path.join(ASM, "gen_wino_cp.py"), str(out)], check=True)
-    return out.read_text()
+from asm_gen import load as _load, run_cli as _generate
 
 
 def test_generated_streams_pass_the_lint(tmp_path):

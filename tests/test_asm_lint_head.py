@@ -1,27 +1,13 @@
 """The head-fused form of the 2-chunk narrow Winograd kernel (csrc/asm/gen_wino_cp.py --head) is a stream of its own: the same lint
 (csrc/asm/lint_wino_asm.py) replays it, its main loop is the plain kernel's instruction for instruction, and the rules its
 cross-lane folds add (two wait states in front of a DPP operand, ds_bpermute results counted in lgkmcnt) catch seeded faults.  CPU only."""
-import importlib.util
-import os
 import re
-import subprocess
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ASM = os.path.join(ROOT, "mingraph-unet_amd", "csrc", "asm")
+from asm_gen import load, run_cli as _generate
 
 
 def _lint():
-    spec = importlib.util.spec_from_file_location("lint_wino_asm", os.path.join(ASM, "lint_wino_asm.py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
-
-
-def _generate(tmp_path, *flags):
-    out = tmp_path / ("k" + "".join(flags) + ".s")
-    subprocess.run([sys.executable, os.path.join(ASM, "gen_wino_cp.py"), *flags, str(out)], check=True)
-    return out.read_text()
+    return load("lint_wino_asm")
 
 
 def _kernel(text, name):

@@ -2,34 +2,13 @@
 order (jj, mi) = (0,0), (1,0), (0,1), (1,1), the jj = 0 forming leaves the column both components of a pair share in the raw
 registers, and the jj = 1 forming of the same mi reuses it.  Counts of the generated loops, and the lint rule
 (csrc/asm/lint_wino_asm.py) that catches a shared sum overwritten before the jj = 1 forming reads it."""
-import importlib.util
-import os
 import re
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ASM = os.path.join(ROOT, "mingraph-unet_amd", "csrc", "asm")
-
-
-def _load(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ASM, name + ".py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
+from asm_gen import generate, load as _load
 
 
 def _generate(tmp_path, patch=None):
-    gen = _load("gen_wino_cp")               # a fresh module: the generator keeps its output in module state
-    if patch:
-        patch(gen)
-    out = tmp_path / "k.s"
-    argv = sys.argv
-    sys.argv = ["gen_wino_cp.py", str(out)]
-    try:
-        gen.main()
-    finally:
-        sys.argv = argv
-    return out.read_text(), gen
+    return generate(patch=patch)            # in this process: the seeded faults hook the module
 
 
 def _kernels(text):
@@ -37,7 +16,11 @@ def _kernels(text):
 
 
 def test_generator_is_deterministic(tmp_path):
-    assert _generate(tmp_path)[0] == _generate(tmp_path)[0]
+    text, gen = _generate(tmp_path)
+    # the same module again, the other code object in between: a generation leaves nothing behind (label numbers restart)
+    head = gen.generate(True)
+    assert gen.generate(False) == text and gen.generate(True) == head
+    assert _generate(tmp_path)[0] == text      # and a fresh module writes the same
 
 
 def test_jj1_steps_read_and_form_only_their_own_column(tmp_path):
@@ -91,13 +74,13 @@ def test_lint_catches_an_overwritten_shared_sum(tmp_path):
 
     def epilogue_on_c_quad(gen):
         # seeded fault: the patch epilogue's temporaries on raw half 1's c quad (the register map before the column was shared)
-        orig = gen.emit_epilogue
+        orig = gen.emit_epilogue_wide
 
-        def emit_epilogue(jp):
-            n0 = len(gen.out)
-            orig(jp)
-            gen.out[n0:] = [re.sub(r"\bv212\b", "v224", ln) for ln in gen.out[n0:]]
-        gen.emit_epilogue = emit_epilogue
+        def emit_epilogue_wide(kn, jp):
+            n0 = len(kn.o.lines)
+            orig(kn, jp)
+            kn.o.lines[n0:] = [re.sub(r"\bv212\b", "v224", ln) for ln in kn.o.lines[n0:]]
+        gen.emit_epilogue_wide = emit_epilogue_wide
     bad, _ = _generate(tmp_path, epilogue_on_c_quad)
     errs = lint.check(bad)[0]
     assert any("combines an inner sum" in e and "v224" in e for e in errs), errs[:3]
