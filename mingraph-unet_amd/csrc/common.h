@@ -58,7 +58,7 @@ struct IgemmDesc {
   const Tuning* tn;    // nullptr = default_tuning()
   const float* in;
   const float* w;
-  const float* wu;     // optional: Winograd-transformed 3x3 weights (launch_pack_wino_w); enables wino_f32.hip
+  const float* wu;     // optional: Winograd-transformed 3x3 weights (pack_wino, pack.hip); enables wino_f32.hip
   const float* scale;  // may be nullptr (== 1)
   const float* shift;  // may be nullptr (== 0)
   float* out;
@@ -142,10 +142,10 @@ inline bool conv_reads_panel(ConvKernel k) {   // the kernel reads the direct pa
 // Layer-level forms of the same choice, for the places that size or pack a weight form before a descriptor exists: the layer's
 // shape and switches admit the kernel (the descriptor-level test in pick_conv checks the rest; a caller that holds no such form
 // leaves d.wu null)
-bool wino_layer(const Tuning& t, int KS, int Cp);             // fp32 3x3 conv on the Winograd kernels (U: launch_pack_wino_w)
+bool wino_layer(const Tuning& t, int KS, int Cp);             // fp32 3x3 conv on the Winograd kernels (U: pack_wino)
 bool wino_dgrad_layer(const Tuning& t, int KS, int Cop);      // its data gradient too (Cop = Cout rounded up to 4)
-bool convt_x3_layer(const Tuning& t, int Cin, int Cout);      // fp32 ConvTranspose on convt2x2_x3_kernel (launch_pack_convt_x3)
-bool convt_x3_dgrad_layer(const Tuning& t, int Cin, int Cout);   // its data gradient too (launch_pack_convt_x3_dgrad)
+bool convt_x3_layer(const Tuning& t, int Cin, int Cout);      // fp32 ConvTranspose on convt2x2_x3_kernel (pack_convt_x3)
+bool convt_x3_dgrad_layer(const Tuning& t, int Cin, int Cout);   // its data gradient too (pack_convt_x3, dgrad = 1)
 bool convt_bf16f_layer(const Tuning& t, int Cin, int Cout);   // bf16-storage ConvTranspose on convt2x2_bf16_kernel
 // the convolution that writes a B x H x W x Cin feature may take the head-fused finishing pass (WinoHead) for a 1x1 head of ncls
 // classes and patch means at `patch`: the caller sizes WinoHead::psum on it, pick_conv repeats it on the descriptor
@@ -160,61 +160,65 @@ WinoPlan wino_plan(const IgemmDesc& d);
 int wino_grid_blocks(const IgemmDesc& d);   // workgroups of the Winograd launch for d (= accumulator rows of its statistics)
 // convt_x3.hip: fp32 ConvTranspose2d(k2,s2) on the bf16 matrix cores with exact three-way operand splits (IgemmDesc::wu =
 // fragment-ordered weight pieces)
-size_t convt_x3_floats(int Cin, int Cout);
-hipError_t launch_pack_convt_x3(const float* w, float* Wx, int Cin, int Cout, hipStream_t s);
 hipError_t launch_convt_x3(const IgemmDesc& d, hipStream_t s);
 // convt_bf16.hip: the bf16-storage ConvTranspose2d(k2,s2) on fragment-ordered bf16 weights (IgemmDesc::wu), 16-byte transposed stores
-size_t convt_bf16f_floats(int Cin, int Cout);
-hipError_t launch_pack_convt_bf16f(const float* w, float* Wf, int Cin, int Cout, hipStream_t s);
 hipError_t launch_convt_bf16f(const IgemmDesc& d, hipStream_t s);
-// the same kernel as the layer's data gradient (KS = 2 gather descriptors whose d.wu holds launch_pack_convt_x3_dgrad's panel)
-size_t convt_x3_dgrad_floats(int Cin, int Cout);
-hipError_t launch_pack_convt_x3_dgrad(const float* w, float* Wx, int Cin, int Cout, hipStream_t s);
+// the same kernel as the layer's data gradient (KS = 2 gather descriptors whose d.wu holds pack_convt_x3's data-gradient form)
 hipError_t launch_convt_x3_dgrad(const IgemmDesc& d, hipStream_t s);
-// elementwise.hip: first convolution (<= 4 input channels on the packed NHWC4 input), VALU + scalar-cache weights
-hipError_t launch_pack_first_w(const float* w, float* wf, int Cout, int Cin, hipStream_t s);
 // first_mfma.hip: the same layer on the bf16 matrix cores (Cin <= 3, Cout == 32)
-size_t first_mfma_floats();
 bool first_mfma_applicable(int dtype, int Cin, int Cp, int Cout, int ldout, int coff, int64_t H, int64_t W);
-hipError_t launch_pack_first_mfma(const float* w, float* wfm, int Cout, int Cin, hipStream_t s);
 hipError_t launch_first_mfma(int dtype, const void* in, const float* wfm, const float* scale, const float* shift, void* out, int B, int H,
                              int W, int ldout, int coff, int relu, hipStream_t s);
 hipError_t launch_first_mfma_direct(int dtype, const float* x, int64_t sn, int64_t sc, int64_t sh, int64_t sw, int cin, const float* wfm,
                                     const float* scale, const float* shift, void* out, int B, int H, int W, int ldout, int coff, int relu,
                                     hipStream_t s);
+// elementwise.hip: first convolution (<= 4 input channels on the packed NHWC4 input), VALU + scalar-cache weights
 bool first_conv_applicable(int dtype, int Cin, int Cp, int Cout, int ldout, int coff);
 hipError_t launch_first_conv(int dtype, const void* in, const float* wf, const float* scale, const float* shift, void* out, int B, int H, int W,
                              int Cin, int Cout, int ldout, int coff, int relu, hipStream_t s);
 // wino_f32.hip: Winograd F(2x2,3x3) for fp32 3x3 layers with Cp % 16 == 0
-size_t wino_u_floats(int Cout, int Cp);
-hipError_t launch_pack_wino_w(const float* w, float* U, int Cout, int Cin, int Cp, int dgrad, int prec, hipStream_t s);
-// several Winograd weight sets in one launch (wino_f32.hip): w (Cout, Cin, 3, 3) [dgrad: roles swapped, see pack_wino_w_kernel]
-// kind 0: a Winograd set.  The small per-layer forms ride in the same launch (pack_small.h): kind 1 = first-conv weights (w, U = wf,
-// Cout, Cin); 2 = three-piece ConvTranspose fragments (w, U = Wx, Cin, Cout, dgrad = forward / data gradient); 3 = bias tile (w = bias,
-// U = shift, Cout = C, Cin = reps); 4 = direct data-gradient panel (w, U = wp, Cout, Cin, Cp = Cop, Np = Kp, dgrad = KS)
-enum { PACK_WINO = 0, PACK_FIRST_W = 1, PACK_CONVT_X3 = 2, PACK_BIAS_TILE = 3, PACK_DGRAD_W = 4, PACK_FIRST_MFMA = 5 };   // 5: (w, U = wfm, Cout, Cin)
-struct WinoPackItem {
-  const float* w;
-  float* U;
-  int Cout, Cin, Cp, Np, dgrad;
-  unsigned blk0;   // Np (kind 0), blk0: filled by the launcher
-  int kind;
-  int reserved;    // no padding bytes: repack_weights compares the tables with memcmp to skip the upload
-};
-static_assert(sizeof(WinoPackItem) == 48, "WinoPackItem must have no padding");
-constexpr int WINO_PACK_MAX = 64;
-struct WinoPackBatch {
-  int n, prec;
-  unsigned total_blocks;
-  WinoPackItem it[WINO_PACK_MAX];
-};
-bool wino_pack_batch_prepare(WinoPackBatch& b);   // fills Np / blk0 / total_blocks; false if an item cannot be packed
-hipError_t launch_pack_wino_w_multi(const WinoPackBatch* batch_dev, unsigned total_blocks, hipStream_t s);
 hipError_t launch_wino_f32(const IgemmDesc& d, ConvKernel k, hipStream_t s, const WinoHead* head = nullptr);   // k: one of the C++ Winograd kernels
 // patch means from the head-fused kernels' partial sums: out[node][c] = (psum[node][0][c] + ... + psum[node][7][c]) / 256
 hipError_t launch_patch_sum_combine(const float* psum, float* out, int nodes, hipStream_t s);
 // wino_asm.hip: the assembly forms of wino3x3_cp_kernel<2> and <1> (bitwise equal results; k: one of the WinoAsm* kernels)
 hipError_t launch_wino_cp_asm(const IgemmDesc& d, ConvKernel k, hipStream_t s, const WinoHead* head = nullptr);
+
+// pack.hip: every packed weight form.  A PackItem names one form to write: built by the form's constructor, run alone
+// (launch_pack_one) or as an entry of a PackBatch table, many forms in one launch (launch_pack_batch).  w: the parameter tensor in the
+// reference's layout, Conv2d (Cout, Cin, KS, KS) or ConvTranspose2d (Cin, Cout, 2, 2); dtype: MGU_DTYPE_* of a typed panel.
+struct PackItem {
+  const float* w;
+  float* U;
+  int Cout, Cin, Cp, Np, dgrad;   // as the Winograd set reads them; the other forms' use: their constructors (pack.hip)
+  unsigned blk0;   // first workgroup of the item in its batch (pack_batch_prepare)
+  int kind;
+  int mode;        // Winograd prec / dtype of a typed panel.  No padding bytes: repack_weights compares the tables with memcmp to skip the upload
+};
+static_assert(sizeof(PackItem) == 48, "PackItem must have no padding");
+PackItem pack_wino(const float* w, float* U, int Cout, int Cin, int Cp, int dgrad, int prec);   // dgrad: roles swapped, see pack_wino_w_body
+PackItem pack_first_w(const float* w, float* wf, int Cout, int Cin);
+PackItem pack_first_mfma(const float* w, float* wfm, int Cout, int Cin);
+PackItem pack_convt_x3(const float* w, float* Wx, int Cin, int Cout, int dgrad);
+PackItem pack_bias_tile(const float* bias, float* shift, int C, int reps);
+PackItem pack_dgrad_panel(const float* w, float* wp, int Cout, int Cin, int Cop, int KS, int Kp);
+PackItem pack_conv_panel(const float* w, void* wp, int dtype, int Cout, int Cin, int Cp, int KS, int Kp);
+PackItem pack_convt_panel(const float* w, void* wp, int dtype, int Cin, int Cout, int Kp);
+PackItem pack_convt_bf16f(const float* w, float* Wf, int Cin, int Cout);
+PackItem pack_convt_dgrad_panel(const float* w, float* wp, int Cin, int Cout, int Kp);
+size_t wino_u_floats(int Cout, int Cp);
+size_t convt_x3_floats(int Cin, int Cout);
+size_t convt_x3_dgrad_floats(int Cin, int Cout);
+size_t convt_bf16f_floats(int Cin, int Cout);
+size_t first_mfma_floats();
+constexpr int PACK_MAX = 64;
+struct PackBatch {
+  int n;
+  unsigned total_blocks;
+  PackItem it[PACK_MAX];
+};
+bool pack_batch_prepare(PackBatch& b);   // fills blk0 / total_blocks; false if an item's shape does not fit its form
+hipError_t launch_pack_batch(const PackBatch* batch_dev, unsigned total_blocks, hipStream_t s);
+hipError_t launch_pack_one(const PackItem& it, hipStream_t s);   // hipErrorInvalidValue: the item's shape does not fit its form
 
 // wgrad_f32.hip:  Dw[n][k] += sum_m Z[m][n] * A(m,k)   (A = the forward kernels' im2col gather)
 struct WgradDesc {
@@ -291,8 +295,6 @@ hipError_t launch_maxpool2_bwd_add(const float* y, int ldy, const float* dpool, 
 hipError_t launch_zero_pad_region(float* buf, int ld, int coff, int C, int B, int H, int W, int h2, int w2, hipStream_t s);
 hipError_t launch_ce(const float* logits, const int64_t* labels, int64_t M, int C, long long ignore_index, float grad_scale,
                      float* dlogits, int ldd, double* acc, int* err_word, float* loss_out, hipStream_t s);
-hipError_t launch_pack_dgrad_w(const float* w, float* wp, int Cout, int Cin, int Cop, int KS, int Kp, hipStream_t s);
-hipError_t launch_pack_convt_dgrad_w(const float* w, float* wp, int Cin, int Cout, int Kp, hipStream_t s);
 hipError_t launch_unpack_conv_grad(const float* dwp, int groups, size_t panel_stride, float* g, int Cout, int Cin, int Cp, int KS,
                                    int Kp, hipStream_t s, double* fold_slots = nullptr, int fold_rows = 0, int fold_n = 0, float* fold_out = nullptr);
 hipError_t launch_unpack_convt_grad(const float* dwp, int groups, size_t panel_stride, float* g, int Cin, int Cout, int Kp, hipStream_t s);
@@ -309,11 +311,8 @@ hipError_t launch_maxpool2(const void* in, int ldin, void* out, int dtype, int B
 bool patch_mean_head_fusable(int dtype, int C, int ncls);
 hipError_t launch_patch_mean(const void* feat, int dtype, float* out, int B, int H, int W, int C, int patch, hipStream_t s,
                              const float* head_w = nullptr, const float* head_b = nullptr, float* logits = nullptr, int ncls = 0);
-hipError_t launch_pack_conv_w(const float* w_oihw, void* wp, int dtype, int Cout, int Cin, int Cp, int KS, int Kp, hipStream_t s);
-hipError_t launch_pack_convt_w(const float* w_iohw, void* wp, int dtype, int Cin, int Cout, int Kp, hipStream_t s);
 hipError_t launch_bn_fold(const float* bias, const float* gamma, const float* beta, const float* mean, const float* var,
                           float eps, float* scale, float* shift, int C, hipStream_t s);
-hipError_t launch_bias_tile(const float* bias, float* shift, int C, int reps, hipStream_t s);
 hipError_t launch_conv1x1_head(const void* in, int dtype, int ldin, int C, const float* w, const float* bias, float* out,
                                int ldout, int ncls, int64_t npix, hipStream_t s);
 hipError_t launch_argmax(const float* logits, int64_t npix, int C, int64_t* pred, hipStream_t s);

@@ -6,7 +6,7 @@
 // straight from global memory, 32-byte row segments per K slice, had measured slower than that kernel: mgunet_api.hip.)  Here:
 //   * A: the 128 x 64 bf16 tile of a K = 64 step is read ONCE per workgroup in whole 128-byte rows (8 lanes x 16 B per row), one step
 //     ahead in registers, and parked in a double-buffered LDS tile with 144-byte rows (conflict-free ds_read_b128 fragments);
-//   * B: weights converted and laid out per lane at load time (pack_convt_bf16f_kernel): a wave's fragment of a K = 16 half step is one
+//   * B: weights converted and laid out per lane at load time (pack_convt_bf16f_body, pack.hip): a wave's fragment of a K = 16 half step is one
 //     16-byte load from a block every workgroup of the same n tile reads (L2 resident), one half step ahead;
 //   * epilogue: bias add in fp32, conversion to bf16, then a wave-private LDS transpose so that every lane stores 16 BYTES (eight
 //     consecutive output channels of one output pixel): whole 64- or 128-byte runs per pixel instead of 2-byte lanes;
@@ -25,20 +25,7 @@ namespace mgu {
 namespace {
 
 
-// Wf[n / 128][k / 16][(n / 32) & 3][lane = 32 * ((k / 8) & 1) + (n & 31)][k & 7] = bf16(w[ci = k][co][dy][dx]),  n = (dy*2+dx)*Cout + co:
-// the B fragment of v_mfma_f32_32x32x16_bf16, one 16-byte lane load
-__global__ void pack_convt_bf16f_kernel(const float* __restrict__ w, __bf16* __restrict__ Wf, int Cin, int Cout) {
-  const int64_t total = (int64_t)Cin * Cout * 4;
-  const int ksteps = Cin >> 4;
-  for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-    const int k = (int)(idx % Cin), n = (int)(idx / Cin);
-    const int q = n / Cout, co = n - q * Cout;
-    const float x = w[(((int64_t)k * Cout + co) * 2 + (q >> 1)) * 2 + (q & 1)];
-    const int lane = ((k >> 3) & 1) * 32 + (n & 31);
-    Wf[(((((int64_t)(n >> 7) * ksteps + (k >> 4)) * 4 + ((n >> 5) & 3))) * 64 + lane) * 8 + (k & 7)] = (__bf16)x;
-  }
-}
-
+// Wf: the layout pack_convt_bf16f_body writes, in pack.hip
 __global__ __launch_bounds__(256, 2) void convt2x2_bf16_kernel(const __bf16* __restrict__ in, const int ldin, const __bf16* __restrict__ Wf,
                                                                const float* __restrict__ shift, __bf16* __restrict__ out, const int M, const int H,
                                                                const int W, const int Cin, const int Cout, const int ldout, const int coff,
@@ -160,16 +147,7 @@ __global__ __launch_bounds__(256, 2) void convt2x2_bf16_kernel(const __bf16* __r
 
 }  // namespace
 
-size_t convt_bf16f_floats(int Cin, int Cout) { return (size_t)Cin * Cout * 2; }   // 4 Cout columns x Cin x 2 bytes
-
-hipError_t launch_pack_convt_bf16f(const float* w, float* Wf, int Cin, int Cout, hipStream_t s) {
-  if ((Cin & 63) || (Cout & 31)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(pack_convt_bf16f_kernel, dim3((unsigned)std::min<int64_t>(4096, ((int64_t)Cin * Cout * 4 + 255) / 256)), dim3(256), 0, s, w,
-                     reinterpret_cast<__bf16*>(Wf), Cin, Cout);
-  return hipGetLastError();
-}
-
-// d: the ConvTranspose descriptor of the bf16 mode (in / out point to bf16; d.wu = launch_pack_convt_bf16f's fragments)
+// d: the ConvTranspose descriptor of the bf16 mode (in / out point to bf16; d.wu = pack_convt_bf16f's fragments)
 hipError_t launch_convt_bf16f(const IgemmDesc& d, hipStream_t s) {
   const int mtiles = (d.M + 127) / 128, ntn = d.N / 128;
   const int nb = mtiles * ntn;

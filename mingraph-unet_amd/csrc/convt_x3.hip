@@ -11,7 +11,7 @@
 // Structure: no LDS tiles and no barrier in the main loop.  Both operands reach the registers already in MFMA fragment order:
 //   A: lane (r = lane & 31, h = lane >> 5) of an m tile needs in[row r][k = 16 s + 8 h .. + 7] = 32 contiguous bytes of an NHWC
 //      pixel: two 16-byte global loads, split into three bf16x8 pieces in registers (5.5 VALU per value);
-//   B: the weights are split and laid out per lane at load time (pack_convt_x3), so a wave's six fragments of a K = 16 step are
+//   B: the weights are split and laid out per lane at load time (pack_convt_x3_body, pack.hip), so a wave's six fragments of a K = 16 step are
 //      six 16-byte loads from a contiguous 6 KB block that every workgroup of the same n tile reads (L2 resident).
 // Workgroup = 4 waves on a 128 pixel x 128 column tile, wave tile 64 x 64 (2 x 2 MFMA tiles, 24 MFMAs per K = 16 step),
 // register double buffering one step ahead.  Workgroup ids are remapped so that the n tiles of one pixel tile run on the same
@@ -23,18 +23,13 @@
 #include <type_traits>
 
 #include "common.h"
-#include "pack_small.h"
 
 namespace mgu {
 
 
 namespace {
 
-// weights in fragment order: pack_convt_x3_body (pack_small.h)
-__global__ void pack_convt_x3_kernel(const float* __restrict__ w, uint16_t* __restrict__ Wx, int Cin, int Cout) {
-  pack_convt_x3_body(w, Wx, Cin, Cout, 0, blockIdx.x, gridDim.x);
-}
-
+// Wx: the layout pack_convt_x3_body writes, in pack.hip
 // MODE 0: the forward layer.  Rows = input pixels (contiguous NHWC rows, K = Cin), columns n = (dy*2+dx)*Cout + co, pixel-shuffle store.
 // MODE 1: its data gradient (loss.backward() through unet_decoder.py:36): din[(y,x)][ci] = sum_{q,co} dout[(2y+qy, 2x+qx)][co] w[ci][co][q].
 //         Rows = pixels of the H x W input grid, K = 4 Cout with k = q*Cout + co: the K = 32 step s reads 32 channels of ONE of the four
@@ -244,30 +239,8 @@ __global__ __launch_bounds__(256, 2) void convt2x2_x3_kernel(const float* __rest
 
 }  // namespace
 
-size_t convt_x3_floats(int Cin, int Cout) { return (size_t)Cin * Cout * 6; }   // 4 Cout columns x Cin x 3 pieces x 2 bytes
-
-
-namespace {
-
-// Weights of the data gradient in the same fragment layout: k = q * Cout + co (q = qy*2 + qx), n = ci.  Columns past Cin inside the last
-// 128-column block are never read (a 64-column workgroup tile reads its own half).
-__global__ void pack_convt_x3_dgrad_kernel(const float* __restrict__ w, uint16_t* __restrict__ Wx, int Cin, int Cout) {
-  pack_convt_x3_body(w, Wx, Cin, Cout, 1, blockIdx.x, gridDim.x);
-}
-
-}  // namespace
-
-size_t convt_x3_dgrad_floats(int Cin, int Cout) { return (size_t)((Cin + 127) / 128 * 128) * Cout * 6; }   // x 4 taps x 3 pieces x 2 B / 4
-
-hipError_t launch_pack_convt_x3_dgrad(const float* w, float* Wx, int Cin, int Cout, hipStream_t s) {
-  if ((Cin & 63) || (Cout & 31)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(pack_convt_x3_dgrad_kernel, dim3((unsigned)std::min<int64_t>(4096, ((int64_t)Cin * Cout * 4 + 255) / 256)), dim3(256), 0, s, w,
-                     reinterpret_cast<uint16_t*>(Wx), Cin, Cout);
-  return hipGetLastError();
-}
-
 // d: the KS = 2 gather descriptor of the generic path (in = dout + c_off with pitch ldin, Cp = the layer's Cout, N = the layer's Cin,
-// H x W the input grid, Hout x Wout the grid of dout), d.wu = launch_pack_convt_x3_dgrad's panel
+// H x W the input grid, Hout x Wout the grid of dout), d.wu = pack_convt_x3's data-gradient form
 hipError_t launch_convt_x3_dgrad(const IgemmDesc& d, hipStream_t s) {
   const bool wide = (d.N & 127) == 0;
   const int mtiles = (d.M + 127) / 128, ntn = d.N / (wide ? 128 : 64);
@@ -279,13 +252,6 @@ hipError_t launch_convt_x3_dgrad(const IgemmDesc& d, hipStream_t s) {
   else
     hipLaunchKernelGGL((convt2x2_x3_kernel<1, 1>), dim3(chunk * 8), dim3(256), 0, s, d.in, d.ldin, reinterpret_cast<const uint16_t*>(d.wu),
                        (const float*)nullptr, d.out, d.M, d.H, d.W, d.Cp, d.N, d.ldout, d.coff, d.Hout, d.Wout, ntn, nb);
-  return hipGetLastError();
-}
-
-hipError_t launch_pack_convt_x3(const float* w, float* Wx, int Cin, int Cout, hipStream_t s) {
-  if ((Cin & 15) || (Cout & 31)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(pack_convt_x3_kernel, dim3((unsigned)std::min<int64_t>(4096, ((int64_t)Cin * Cout * 4 + 255) / 256)), dim3(256), 0, s, w, reinterpret_cast<uint16_t*>(Wx), Cin,
-                     Cout);
   return hipGetLastError();
 }
 

@@ -63,8 +63,8 @@ struct mgu_ctx {
   mgu::Tuning tn;           // kernel-selection switches of THIS context (MGU_* environment at mgu_create)
   std::string err;
   bool configured = false, loaded = false;
-  std::vector<mgu::WinoPackBatch> pack_host;   // the Winograd pack tables as last uploaded (repack_weights)
-  mgu::WinoPackBatch* pack_dev = nullptr;
+  std::vector<mgu::PackBatch> pack_host;   // the pack tables as last uploaded (repack_weights)
+  mgu::PackBatch* pack_dev = nullptr;
   int pack_dev_cap = 0;
   bool want_train = false;  // a training forward has run on this context: weight refreshes also build the data-gradient forms
   bool fold_dirty = false;  // BN running stats / affine changed since the eval scale/shift were folded

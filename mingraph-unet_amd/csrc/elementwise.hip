@@ -1,7 +1,6 @@
-// HBM-bound helper kernels around the implicit-GEMM: layout packing, 2x2 max-pool, patch mean,
-// weight repacking, BatchNorm folding, class argmax.  All NHWC, 16-byte lanes where channels allow.
+// HBM-bound helper kernels around the implicit-GEMM: input packing, 2x2 max-pool, patch mean,
+// BatchNorm folding, class argmax (the weight forms: pack.hip).  All NHWC, 16-byte lanes where channels allow.
 #include "common.h"
-#include "pack_small.h"
 
 namespace mgu {
 
@@ -213,44 +212,6 @@ hipError_t launch_patch_mean(const void* feat, int dtype, float* out, int B, int
   return hipGetLastError();
 }
 
-// ---- weights: OIHW (Cout,Cin,KS,KS) -> panel [Cout][Kp], k = (r*KS+s)*Cp + c (zero padded) ------------
-template <typename T>
-__global__ void pack_conv_w_kernel(const float* __restrict__ w, T* __restrict__ wp, int Cout, int Cin, int Cp, int KS, int Kp) {
-  const int64_t total = (int64_t)Cout * Kp;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int n = (int)(i / Kp), k = (int)(i - (int64_t)n * Kp);
-    const int tap = k / Cp, c = k - tap * Cp;
-    float v = 0.f;
-    if (tap < KS * KS && c < Cin) v = w[((int64_t)n * Cin + c) * KS * KS + tap];
-    wp[i] = (T)v;
-  }
-}
-
-hipError_t launch_pack_conv_w(const float* w, void* wp, int dtype, int Cout, int Cin, int Cp, int KS, int Kp, hipStream_t s) {
-  dim3 g(grid_for((int64_t)Cout * Kp, 256, 256 * 16)), b(256);
-  if (dtype == 0) hipLaunchKernelGGL(pack_conv_w_kernel<float>, g, b, 0, s, w, (float*)wp, Cout, Cin, Cp, KS, Kp);
-  else hipLaunchKernelGGL(pack_conv_w_kernel<__bf16>, g, b, 0, s, w, (__bf16*)wp, Cout, Cin, Cp, KS, Kp);
-  return hipGetLastError();
-}
-
-// ---- ConvTranspose2d weight (Cin,Cout,2,2) -> panel [(dy*2+dx)*Cout + co][Kp], k = ci ----------------
-template <typename T>
-__global__ void pack_convt_w_kernel(const float* __restrict__ w, T* __restrict__ wp, int Cin, int Cout, int Kp) {
-  const int64_t total = (int64_t)4 * Cout * Kp;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int n = (int)(i / Kp), k = (int)(i - (int64_t)n * Kp);
-    const int q = n / Cout, co = n - q * Cout;
-    wp[i] = (T)((k < Cin) ? w[((int64_t)k * Cout + co) * 4 + q] : 0.f);
-  }
-}
-
-hipError_t launch_pack_convt_w(const float* w, void* wp, int dtype, int Cin, int Cout, int Kp, hipStream_t s) {
-  dim3 g(grid_for((int64_t)4 * Cout * Kp, 256, 256 * 16)), b(256);
-  if (dtype == 0) hipLaunchKernelGGL(pack_convt_w_kernel<float>, g, b, 0, s, w, (float*)wp, Cin, Cout, Kp);
-  else hipLaunchKernelGGL(pack_convt_w_kernel<__bf16>, g, b, 0, s, w, (__bf16*)wp, Cin, Cout, Kp);
-  return hipGetLastError();
-}
-
 // ---- eval BatchNorm + conv bias -> y = scale*acc + shift (unet_encoder.py:12-13,17-24) ----------------
 __global__ void bn_fold_kernel(const float* bias, const float* gamma, const float* beta, const float* mean,
                                const float* var, float eps, float* scale, float* shift, int C) {
@@ -266,13 +227,6 @@ hipError_t launch_bn_fold(const float* bias, const float* gamma, const float* be
                           float eps, float* scale, float* shift, int C, hipStream_t s) {
   hipLaunchKernelGGL(bn_fold_kernel, dim3((C + 255) / 256), dim3(256), 0, s, bias, gamma, beta, mean, var, eps, scale,
                      shift, C);
-  return hipGetLastError();
-}
-
-__global__ void bias_tile_kernel(const float* bias, float* shift, int C, int reps) { bias_tile_body(bias, shift, C, reps, blockIdx.x, gridDim.x); }
-
-hipError_t launch_bias_tile(const float* bias, float* shift, int C, int reps, hipStream_t s) {
-  hipLaunchKernelGGL(bias_tile_kernel, dim3((C * reps + 255) / 256), dim3(256), 0, s, bias, shift, C, reps);
   return hipGetLastError();
 }
 
@@ -421,16 +375,6 @@ __global__ __launch_bounds__(256) void conv3x3_first_kernel(const T* __restrict_
       if (p0 + px < npix) *reinterpret_cast<bf16x8*>(out + (p0 + px) * ldout + coff + 8 * qd) = o;
     }
   }
-}
-
-// wf[tap][c][co] = w[co][c][tap] (OIHW), zero for c >= Cin
-__global__ void pack_first_w_kernel(const float* __restrict__ w, float* __restrict__ wf, int Cout, int Cin) {
-  pack_first_w_body(w, wf, Cout, Cin, blockIdx.x, gridDim.x);
-}
-
-hipError_t launch_pack_first_w(const float* w, float* wf, int Cout, int Cin, hipStream_t s) {
-  hipLaunchKernelGGL(pack_first_w_kernel, dim3((9 * 4 * Cout + 255) / 256), dim3(256), 0, s, w, wf, Cout, Cin);
-  return hipGetLastError();
 }
 
 bool first_conv_applicable(int dtype, int Cin, int Cp, int Cout, int ldout, int coff) {

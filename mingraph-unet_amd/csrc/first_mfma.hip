@@ -10,13 +10,12 @@
 //   * a workgroup owns a 16 x 16 pixel patch: the 18 x 18 halo of packed pixels (one 16-byte load each: NHWC4 fp32 or NHWC8 bf16,
 //     pack_input_kernel) goes to LDS once; a lane (pixel r = lane & 31 of a 2 x 16 pixel m tile, half h = lane >> 5) reads FIVE
 //     16-byte pixels -- taps 0..4 (h = 0) or 5..8 (h = 1) -- which fill its 16 k slots: slot j of half h = (tap 5h + j / 3,
-//     channel j % 3), slots past the 27 real values are zero; the weights are packed in the same slot order (pack_first_mfma_body);
+//     channel j % 3), slots past the 27 real values are zero; the weights are packed in the same slot order (pack_first_mfma_body, pack.hip);
 //   * no barrier after the staging one, many small workgroups per CU cover each other's latencies; the epilogue stores 128 (64) bytes
 //     of one pixel per half wave and instruction through a buffer descriptor (the halo kernel's form).
 #include <algorithm>
 
 #include "common.h"
-#include "pack_small.h"
 
 namespace mgu {
 
@@ -204,21 +203,10 @@ __global__ __launch_bounds__(256, 4) void conv3x3_first_mfma_kernel(const T* __r
   }   // patch walk
 }
 
-__global__ void pack_first_mfma_kernel(const float* __restrict__ w, float* __restrict__ wfm, int Cout, int Cin) {
-  pack_first_mfma_body(w, reinterpret_cast<uint16_t*>(wfm), Cout, Cin, blockIdx.x, gridDim.x);
-}
-
-size_t first_mfma_floats() { return 2 * 3 * 64 * 4; }   // [k step][piece][lane][4 dwords]
-
 bool first_mfma_applicable(int dtype, int Cin, int Cp, int Cout, int ldout, int coff, int64_t H, int64_t W) {
   const int v = dtype == 0 ? 4 : 8;
   return Cp == v && Cin >= 1 && Cin <= 3 && Cout == 32 && (ldout % v) == 0 && (coff % v) == 0 &&
          H * W * ldout * (dtype == 0 ? 4 : 2) < 0x7ffffff0l;   // one image within the output descriptor's reach
-}
-
-hipError_t launch_pack_first_mfma(const float* w, float* wfm, int Cout, int Cin, hipStream_t s) {
-  hipLaunchKernelGGL(pack_first_mfma_kernel, dim3(1), dim3(256), 0, s, w, wfm, Cout, Cin);
-  return hipGetLastError();
 }
 
 hipError_t launch_first_mfma(int dtype, const void* in, const float* wfm, const float* scale, const float* shift, void* out, int B, int H,

@@ -36,7 +36,7 @@ int mgud::gat_pack_panel(mgu_ctx* c, const float* W, const float* a, float* pane
   // W^T a_src / W^T a_tgt so the same GEMM emits the attention scalars s, t (graph_attention.py:53,57-64)
   const int HF = heads * Fh, Kp = rup(Fin, 32);
   if (clear) HIPCHK(c, hipMemsetAsync(panel, 0, gat_panel_floats(heads, Fh, Fin) * sizeof(float), s));
-  HIPCHK(c, launch_pack_conv_w(W, panel, 0, HF, Fin, Fin, 1, Kp, s));
+  HIPCHK(c, launch_pack_one(pack_conv_panel(W, panel, 0, HF, Fin, Fin, 1, Kp), s));
   HIPCHK(c, launch_gat_wa_rows(W, a, panel, HF, heads, Fh, Fin, Kp, s));
   return MGU_OK;
 }

@@ -325,72 +325,72 @@ int mgu_unet_reserve(mgu_ctx* c, int B, int H, int W, int training) {
 // optimizer step through the flat buffer).  All Winograd sets -- and, once the context has trained, the data-gradient sets --
 // go out in one launch; the eval BatchNorm fold stays lazy.
 int mgud::repack_weights(mgu_ctx* c, hipStream_t s) {
-  std::vector<WinoPackItem> items;   // every form goes out in the one pack_wino_w_multi_kernel launch (kinds: common.h)
+  std::vector<PackItem> items;   // every form goes out in the one pack_batch_kernel launch (pack.hip)
   for (auto& L : c->layers) {
     const float *w = L.w_src, *b = L.b_src;
     L.wxg_valid = false;
     if (L.convt) {
       // the generic panel is read by the fallback kernels only: built on first use when the layer runs on its three-piece fragments
       L.wp_dirty = L.ctx3;
-      if (!L.ctx3) HIPCHK(c, launch_pack_convt_w(w, L.wp, c->dtype, L.Cin, L.Cout, L.Kp, s));
-      if (L.ctb) HIPCHK(c, launch_pack_convt_bf16f(w, L.wu, L.Cin, L.Cout, s));
-      if (L.ctx3) items.push_back(WinoPackItem{w, L.wu, L.Cout, L.Cin, 0, 0, 0, 0, PACK_CONVT_X3});
-      items.push_back(WinoPackItem{b, L.shift, L.Cout, 4, 0, 0, 0, 0, PACK_BIAS_TILE});   // scale unused (nullptr at launch)
+      if (!L.ctx3) items.push_back(pack_convt_panel(w, L.wp, c->dtype, L.Cin, L.Cout, L.Kp));
+      if (L.ctb) items.push_back(pack_convt_bf16f(w, L.wu, L.Cin, L.Cout));
+      if (L.ctx3) items.push_back(pack_convt_x3(w, L.wu, L.Cin, L.Cout, 0));
+      items.push_back(pack_bias_tile(b, L.shift, L.Cout, 4));   // scale unused (nullptr at launch)
       if (L.wxg && c->want_train && convt_x3_dgrad_layer(c->tn, L.Cin, L.Cout)) {
-        items.push_back(WinoPackItem{w, L.wxg, L.Cout, L.Cin, 0, 0, 1, 0, PACK_CONVT_X3});
+        items.push_back(pack_convt_x3(w, L.wxg, L.Cin, L.Cout, 1));
         L.wxg_valid = true;
       }
     } else {
       // a layer that runs as Winograd / first-conv / 1x1 head kernel reads wu / wf / w_src; its direct panel is packed lazily, only
       // if a launch ever falls back to the implicit-GEMM kernel (run_layer)
       L.wp_dirty = true;
-      if (L.wu) items.push_back(WinoPackItem{w, L.wu, L.Cout, L.Cin, L.Cp, 0, 0, 0, PACK_WINO});
+      if (L.wu) items.push_back(pack_wino(w, L.wu, L.Cout, L.Cin, L.Cp, 0, c->tn.wino_prec));
       L.wug_valid = false;
       if (L.wug && c->want_train && wino_dgrad_layer(c->tn, L.KS, rup(L.Cout, 4))) {
-        items.push_back(WinoPackItem{w, L.wug, L.Cin, L.Cout, rup(L.Cout, 4), 0, 1, 0, PACK_WINO});
+        items.push_back(pack_wino(w, L.wug, L.Cin, L.Cout, rup(L.Cout, 4), 1, c->tn.wino_prec));
         L.wug_valid = true;
       }
       const bool head_kernel = L.bn.empty() && c->ncls <= 4;   // conv1x1_head_kernel reads the reference's (ncls, C) weight itself
       if (!L.wu && !L.first && !head_kernel) {
-        HIPCHK(c, launch_pack_conv_w(w, L.wp, c->dtype, L.Cout, L.Cin, L.Cp, L.KS, L.Kp, s));
+        items.push_back(pack_conv_panel(w, L.wp, c->dtype, L.Cout, L.Cin, L.Cp, L.KS, L.Kp));
         L.wp_dirty = false;
       }
-      if (L.wf) items.push_back(WinoPackItem{w, L.wf, L.Cout, L.Cin, 0, 0, 0, 0, PACK_FIRST_W});
-      if (L.wfm && L.Cout == 32 && L.Cin <= 3) items.push_back(WinoPackItem{w, L.wfm, L.Cout, L.Cin, 0, 0, 0, 0, PACK_FIRST_MFMA});
+      if (L.wf) items.push_back(pack_first_w(w, L.wf, L.Cout, L.Cin));
+      if (L.wfm && L.Cout == 32 && L.Cin <= 3) items.push_back(pack_first_mfma(w, L.wfm, L.Cout, L.Cin));
       if (!L.bn.empty()) c->fold_dirty = true;   // eval scale/shift are folded lazily by the next eval forward (training never reads them)
-      else items.push_back(WinoPackItem{b, L.shift, L.Cout, 1, 0, 0, 0, 0, PACK_BIAS_TILE});
+      else items.push_back(pack_bias_tile(b, L.shift, L.Cout, 1));
       if (L.bn.empty() && L.wxg && c->want_train) {   // final conv: panel of its data gradient (mgu_unet_backward)
         const int Cop = rup(L.Cout, 4);
-        items.push_back(WinoPackItem{w, L.wxg, L.Cout, L.Cin, Cop, rup(L.KS * L.KS * Cop, 32), L.KS, 0, PACK_DGRAD_W});
+        items.push_back(pack_dgrad_panel(w, L.wxg, L.Cout, L.Cin, Cop, L.KS, rup(L.KS * L.KS * Cop, 32)));
         L.wxg_valid = true;
       }
     }
   }
-  // batches of <= WINO_PACK_MAX items; the tables are uploaded only when they differ from what the device already holds (a
+  // batches of <= PACK_MAX items; the tables are uploaded only when they differ from what the device already holds (a
   // refresh after an optimizer step finds them unchanged: same tensors, same buffers)
-  std::vector<WinoPackBatch> batches;
-  for (size_t i0 = 0; i0 < items.size(); i0 += WINO_PACK_MAX) {
-    WinoPackBatch b;
+  std::vector<PackBatch> batches;
+  for (size_t i0 = 0; i0 < items.size(); i0 += PACK_MAX) {
+    PackBatch b;
     memset(&b, 0, sizeof b);
-    b.n = (int)std::min<size_t>(WINO_PACK_MAX, items.size() - i0), b.prec = c->tn.wino_prec;
+    b.n = (int)std::min<size_t>(PACK_MAX, items.size() - i0);
     for (int i = 0; i < b.n; ++i) b.it[i] = items[i0 + i];
-    if (!wino_pack_batch_prepare(b)) return fail(c, MGU_ERR_STATE, "internal: a Winograd layer is not packable");
+    if (!pack_batch_prepare(b)) return fail(c, MGU_ERR_STATE, "internal: a weight form is not packable");
     batches.push_back(b);
   }
   const bool same = batches.size() == c->pack_host.size() &&
-                    (batches.empty() || memcmp(batches.data(), c->pack_host.data(), batches.size() * sizeof(WinoPackBatch)) == 0);
+                    (batches.empty() || memcmp(batches.data(), c->pack_host.data(), batches.size() * sizeof(PackBatch)) == 0);
   if (!same) {
     if ((int)batches.size() > c->pack_dev_cap) {
       if (c->pack_dev) HIPCHK(c, hipFree(c->pack_dev));
       c->pack_dev = nullptr;
-      HIPCHK(c, hipMalloc((void**)&c->pack_dev, batches.size() * sizeof(WinoPackBatch)));
+      HIPCHK(c, hipMalloc((void**)&c->pack_dev, batches.size() * sizeof(PackBatch)));
       c->pack_dev_cap = (int)batches.size();
     }
     HIPCHK(c, hipStreamSynchronize(s));   // an earlier launch may still read the old table
-    HIPCHK(c, hipMemcpy(c->pack_dev, batches.data(), batches.size() * sizeof(WinoPackBatch), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->pack_dev, batches.data(), batches.size() * sizeof(PackBatch), hipMemcpyHostToDevice));
     c->pack_host = batches;
   }
-  for (size_t k = 0; k < batches.size(); ++k) HIPCHK(c, launch_pack_wino_w_multi(c->pack_dev + k, batches[k].total_blocks, s));
+  for (size_t k = 0; k < batches.size(); ++k) HIPCHK(c, launch_pack_batch(c->pack_dev + k, batches[k].total_blocks, s));
   return MGU_OK;
 }
 
@@ -432,8 +432,8 @@ int mgud::run_layer(mgu_ctx* c, const Layer& L, const void* in_v, int ldin, int 
   if (!conv_fuses_head(k)) head = nullptr;   // the caller runs the head and the patch means in their own pass
   else if (head_fused) *head_fused = true;
   if (L.wp_dirty && conv_reads_panel(k)) {   // falling back to the direct kernel: build its panel now
-    if (L.convt) HIPCHK(c, launch_pack_convt_w(L.w_src, L.wp, c->dtype, L.Cin, L.Cout, L.Kp, s));
-    else HIPCHK(c, launch_pack_conv_w(L.w_src, L.wp, c->dtype, L.Cout, L.Cin, L.Cp, L.KS, L.Kp, s));
+    HIPCHK(c, launch_pack_one(L.convt ? pack_convt_panel(L.w_src, L.wp, c->dtype, L.Cin, L.Cout, L.Kp)
+                                      : pack_conv_panel(L.w_src, L.wp, c->dtype, L.Cout, L.Cin, L.Cp, L.KS, L.Kp), s));
     L.wp_dirty = false;
   }
   // profiling record: algorithmic 2*MAC of the operator and what the matrix pipe really issues
@@ -632,7 +632,7 @@ static int conv2d_launch(mgu_ctx* c, const Layer& L, const void* in_dev, int B, 
     d.scale = (const float*)scale_dev;
     d.shift = (const float*)shift_dev;
   } else if (bias_dev) {
-    HIPCHK(c, launch_bias_tile((const float*)bias_dev, L.shift, L.Cout, 1, s));
+    HIPCHK(c, launch_pack_one(pack_bias_tile((const float*)bias_dev, L.shift, L.Cout, 1), s));
     d.shift = L.shift;
   }
   const ConvKernel k = pick_conv(d, 0);
@@ -659,10 +659,10 @@ int mgu_conv2d_prepare(mgu_ctx* c, const void* w_dev, int Cout, int Cin, int ksi
   }
   L.shift = L.wp + panel;
   e = hipMemsetAsync(L.wp, 0, (panel + L.Np) * sizeof(float), s);
-  if (e == hipSuccess) e = launch_pack_conv_w((const float*)w_dev, L.wp, 0, Cout, Cin, Cin, ksize, L.Kp, s);
+  if (e == hipSuccess) e = launch_pack_one(pack_conv_panel((const float*)w_dev, L.wp, 0, Cout, Cin, Cin, ksize, L.Kp), s);
   if (e == hipSuccess && wino) {
     L.wu = L.shift + L.Np;
-    e = launch_pack_wino_w((const float*)w_dev, L.wu, Cout, Cin, Cin, 0, c->tn.wino_prec, s);
+    e = launch_pack_one(pack_wino((const float*)w_dev, L.wu, Cout, Cin, Cin, 0, c->tn.wino_prec), s);
   }
   if (e != hipSuccess) {
     (void)hipFree(L.wp);
@@ -712,11 +712,11 @@ int mgu_conv2d_nhwc(mgu_ctx* c, const void* in_dev, int B, int H, int W, int Cin
   L.wp = (float*)c->gws;
   L.shift = L.wp + (size_t)L.Np * L.Kp + L.Np;
   HIPCHK(c, hipMemsetAsync(c->gws, 0, need, s));
-  HIPCHK(c, launch_pack_conv_w((const float*)w_dev, L.wp, 0, Cout, Cin, Cin, ksize, L.Kp, s));
+  HIPCHK(c, launch_pack_one(pack_conv_panel((const float*)w_dev, L.wp, 0, Cout, Cin, Cin, ksize, L.Kp), s));
   if (wino_layer(c->tn, ksize, Cin)) {   // same routing as the model's layers: Winograd F(2x2,3x3)
     if ((rc = ensure(c, &c->wuws, &c->wuws_bytes, wino_u_floats(Cout, Cin) * sizeof(float)))) return rc;
     L.wu = (float*)c->wuws;
-    HIPCHK(c, launch_pack_wino_w((const float*)w_dev, L.wu, Cout, Cin, Cin, 0, c->tn.wino_prec, s));
+    HIPCHK(c, launch_pack_one(pack_wino((const float*)w_dev, L.wu, Cout, Cin, Cin, 0, c->tn.wino_prec), s));
   }
   return conv2d_launch(c, L, in_dev, B, H, W, bias_dev, scale_dev, shift_dev, relu, out_dev, ld_out, c_off, s);
 }
@@ -743,15 +743,15 @@ int mgu_conv_transpose2x2_nhwc(mgu_ctx* c, const void* in_dev, int B, int H, int
   U.shift = U.wp + (size_t)U.Np * U.Kp + U.Np;
   U.wu = x3_shape ? U.wp + panel : nullptr;
   HIPCHK(c, hipMemsetAsync(c->gws, 0, panel * sizeof(float), s));
-  HIPCHK(c, launch_pack_convt_w((const float*)w_dev, U.wp, 0, Cin, Cout, U.Kp, s));
+  HIPCHK(c, launch_pack_one(pack_convt_panel((const float*)w_dev, U.wp, 0, Cin, Cout, U.Kp), s));
   IgemmDesc d = layer_desc(c, U, in_dev, Cin, B, H, W, out_dev, ld_out, c_off);
   d.Hout = 2 * H, d.Wout = 2 * W;
   if (bias_dev) {
-    HIPCHK(c, launch_bias_tile((const float*)bias_dev, U.shift, Cout, 4, s));
+    HIPCHK(c, launch_pack_one(pack_bias_tile((const float*)bias_dev, U.shift, Cout, 4), s));
     d.shift = U.shift;
   }
   const ConvKernel k = pick_conv(d, 0);
-  if (k == ConvKernel::ConvtX3) HIPCHK(c, launch_pack_convt_x3((const float*)w_dev, U.wu, Cin, Cout, s));
+  if (k == ConvKernel::ConvtX3) HIPCHK(c, launch_pack_one(pack_convt_x3((const float*)w_dev, U.wu, Cin, Cout, 0), s));
   ProfScope ps(c, s, conv_kernel_name(k, d));
   HIPCHK(c, launch_conv(d, k, 0, s));
   return MGU_OK;

@@ -180,12 +180,12 @@ int mgud::conv_dgrad(mgu_ctx* c, const Layer& L, const float* dz, float* out, in
   const ConvKernel k = pick_conv(d, 0);
   if (conv_is_wino(k)) {
     if (!L.wug_valid) {
-      HIPCHK(c, launch_pack_wino_w(L.w_src, L.wug, L.Cin, L.Cout, Cop, 1, c->tn.wino_prec, s));
+      HIPCHK(c, launch_pack_one(pack_wino(L.w_src, L.wug, L.Cin, L.Cout, Cop, 1, c->tn.wino_prec), s));
       L.wug_valid = true;
     }
   } else if (!L.wxg_valid) {
     if (w.clear) HIPCHK(c, hipMemsetAsync(w.dgp, 0, (size_t)rup(L.Cin, 128) * d.Kp * sizeof(float), s));   // panel rows are padded to 128
-    HIPCHK(c, launch_pack_dgrad_w(L.w_src, w.dgp, L.Cout, L.Cin, Cop, L.KS, d.Kp, s));
+    HIPCHK(c, launch_pack_one(pack_dgrad_panel(L.w_src, w.dgp, L.Cout, L.Cin, Cop, L.KS, d.Kp), s));
   }
   const double alg = 2.0 * d.M * (double)L.KS * L.KS * L.Cin * L.Cout;
   const ConvCost cost = conv_cost(k, d);
@@ -204,9 +204,9 @@ int mgud::convt_dgrad(mgu_ctx* c, const Layer& U, const float* dout, int ld_d, i
   const ConvKernel k = pick_conv(q, 0);
   if (k != ConvKernel::ConvtX3Dgrad) {
     if (w.clear) HIPCHK(c, hipMemsetAsync(w.dgp, 0, (size_t)rup(U.Cin, 128) * q.Kp * sizeof(float), s));
-    HIPCHK(c, launch_pack_convt_dgrad_w(U.w_src, w.dgp, U.Cin, U.Cout, q.Kp, s));
+    HIPCHK(c, launch_pack_one(pack_convt_dgrad_panel(U.w_src, w.dgp, U.Cin, U.Cout, q.Kp), s));
   } else if (!U.wxg_valid) {
-    HIPCHK(c, launch_pack_convt_x3_dgrad(U.w_src, w.dgp, U.Cin, U.Cout, s));   // else: packed by the last weight refresh
+    HIPCHK(c, launch_pack_one(pack_convt_x3(U.w_src, w.dgp, U.Cin, U.Cout, 1), s));   // else: packed by the last weight refresh
   }
   const double alg = 2.0 * q.M * (double)q.K * U.Cin;
   const ConvCost cost = conv_cost(k, q);

@@ -1,9 +1,8 @@
 // HBM-bound kernels of the training step (scripts/train_segmentation.py:117-137): train-mode
 // BatchNorm (batch statistics, running-stat update, backward), ReLU mask, MaxPool backward,
-// softmax cross-entropy forward+backward, weight-panel packing for dgrad, gradient unpacking, Adam.
+// softmax cross-entropy forward+backward, gradient unpacking, Adam.
 // All tensors NHWC fp32 with an explicit pixel pitch (ld) so channel slices of the concat buffers work.
 #include "common.h"
-#include "pack_small.h"
 
 namespace mgu {
 
@@ -476,31 +475,6 @@ hipError_t launch_ce(const float* logits, const int64_t* labels, int64_t M, int 
   hipLaunchKernelGGL(ce_fwd_bwd_kernel, dim3(grid_for(M, 256, 2048)), dim3(256), 0, s, logits, labels, M, C, ignore_index, grad_scale,
                      dlogits, ldd, acc);
   hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(1), 0, s, acc, loss_out);
-  return hipGetLastError();
-}
-
-// ---- dgrad weight panels -----------------------------------------------------------------------------
-// conv3x3 / 1x1: din = conv(dz, W') with W'[ci][(2-r,2-s), co] = W[co][ci][r][s]:
-// panel [Cin][Kp], k = tap'*Cop + co  (Cop = Cout rounded up to 4, zero padded)
-__global__ void pack_dgrad_w_kernel(const float* __restrict__ w, float* __restrict__ wp, int Cout, int Cin, int Cop, int KS,
-                                    int Kp) {
-  pack_dgrad_w_body(w, wp, Cout, Cin, Cop, KS, Kp, blockIdx.x, gridDim.x);
-}
-hipError_t launch_pack_dgrad_w(const float* w, float* wp, int Cout, int Cin, int Cop, int KS, int Kp, hipStream_t s) {
-  hipLaunchKernelGGL(pack_dgrad_w_kernel, dim3(grid_for((int64_t)Cin * Kp, 256, 256 * 8)), dim3(256), 0, s, w, wp, Cout, Cin, Cop, KS, Kp);
-  return hipGetLastError();
-}
-// ConvTranspose2d dgrad: dprev[m][ci] = sum_{q,co} dup[pix(m,q)][co] * W[ci][co][q]: panel [Cin][Kp], k = q*Cout + co
-__global__ void pack_convt_dgrad_w_kernel(const float* __restrict__ w, float* __restrict__ wp, int Cin, int Cout, int Kp) {
-  const int64_t total = (int64_t)Cin * Kp;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int ci = (int)(i / Kp), k = (int)(i - (int64_t)ci * Kp);
-    const int q = k / Cout, co = k - q * Cout;
-    wp[i] = (q < 4) ? w[((int64_t)ci * Cout + co) * 4 + q] : 0.f;
-  }
-}
-hipError_t launch_pack_convt_dgrad_w(const float* w, float* wp, int Cin, int Cout, int Kp, hipStream_t s) {
-  hipLaunchKernelGGL(pack_convt_dgrad_w_kernel, dim3(grid_for((int64_t)Cin * Kp, 256, 256 * 8)), dim3(256), 0, s, w, wp, Cin, Cout, Kp);
   return hipGetLastError();
 }
 

@@ -19,13 +19,12 @@
 //     fewer than writing V to LDS and reading it back -- with no barrier between transform and MFMA;
 //   * raw columns are stored split by parity ([row][x & 1][x >> 1][20 floats]): tile tx touches entries tx, tx+1 of
 //     each parity plane, so the 16 lanes of a ds_read_b128 group are 80 bytes apart -> conflict free;
-//   * U = G g G^T is precomputed (pack_wino_w_kernel) in MFMA-fragment order: the four components of a wave are one
+//   * U = G g G^T is precomputed (pack_wino_w_body, pack.hip) in MFMA-fragment order: the four components of a wave are one
 //     contiguous 4 KB block per 8 input channels, loaded straight from L2 into VGPRs (coalesced 16-byte lanes).
 //     Only one wave of the workgroup uses a given component, so staging U through LDS would buy nothing;
 //   * inverse transform: each wave folds its own row (M[i][.] A) in registers, the four row waves meet through a
 //     small LDS exchange, and lanes store one channel each (32 lanes = one 128-byte line of a pixel).
 #include "common.h"
-#include "pack_small.h"
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
@@ -73,200 +72,9 @@ __device__ __forceinline__ void lds_store4_addtid(const unsigned m0v, const floa
 //      K = 16 (6 x 32 cycles) against 8 fp32 MFMAs of K = 2 (8 x 64 cycles) -- and, measured (tools/ubench/
 //      mfma_valu.hip), the fp32 MFMA blocks the VALU while it runs whereas the bf16 MFMA does not, so the input
 //      transform hides under the matrix pipe here.
-// (Tuning::wino_prec; the packed U layout follows it, so launch_pack_wino_w takes the same value.)
+// (Tuning::wino_prec; the packed U layout follows it, so pack_wino takes the same value.)
 
-// U[ntile][cin/8][i*4+j][lane (h = lane>>5, r = lane&31)][t]  =  (G g G^T)[i][j]  of  cout = 32*ntile + r,
-// cin = 8*(cin/8) + 4*h + t.   dgrad = 1: the data-gradient conv, g'[u][v] = w[c][n][2-u][2-v] (roles swapped).
-//
-// prec = 1 (three bf16 pieces):  Ux[ntile][cin/16][i*4+j][piece][lane (h = lane>>5, r = lane&31)][e]  (uint16),
-// cout = 32*ntile + r, cin = 16*(cin/16) + 8*h + e: the B fragment of v_mfma_f32_32x32x16_bf16, one 16-byte lane load.
-__device__ __forceinline__ void pack_wino_w_body(const float* __restrict__ w, float* __restrict__ U, int Cout, int Cin, int Cp, int Np,
-                                                 int dgrad, int prec, unsigned vblock, unsigned vgrid) {
-  if (prec == 1) {
-    // Three-piece layout, store-coalesced: a thread owns output channel n and EIGHT consecutive input channels, i.e. one whole
-    // 16-byte lane entry of every (component, piece) fragment; lane & 31 = n & 31 and lane >> 5 = the 8-channel half, so a wave's
-    // store instruction writes one contiguous 1-KB fragment (a thread per (n, c) wrote 2-byte pieces 1 KB apart: 1.1 TB/s on the
-    // 164 MB a train step re-packs).
-    const int nC = Cp >> 4;
-    const int64_t total8 = (int64_t)Np * (Cp >> 3);
-    for (int64_t idx = vblock * (int64_t)blockDim.x + threadIdx.x; idx < total8; idx += (int64_t)vgrid * blockDim.x) {
-      const int lane = (int)(idx & 63);
-      const int64_t grp = idx >> 6;
-      const int c16 = (int)(grp % nC), ntile = (int)(grp / nC);
-      const int n = ntile * 32 + (lane & 31), c0 = c16 * 16 + (lane >> 5) * 8;
-      float g[8][3][3];
-#pragma unroll
-      for (int e = 0; e < 8; ++e)
-#pragma unroll
-        for (int u = 0; u < 3; ++u)
-#pragma unroll
-          for (int v = 0; v < 3; ++v) {
-            const int c = c0 + e;
-            float x = 0.f;
-            if (n < Cout && c < Cin)
-              x = dgrad ? w[(((int64_t)c * Cout + n) * 3 + (2 - u)) * 3 + (2 - v)] : w[(((int64_t)n * Cin + c) * 3 + u) * 3 + v];
-            g[e][u][v] = x;
-          }
-      u32x4* dst = reinterpret_cast<u32x4*>(U) + ((int64_t)ntile * nC + c16) * 16 * 192 + lane;   // [comp][piece][64 lanes] x 16 B
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          unsigned short p0[8], p1[8], p2[8];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            float t3[3];   // row i of G g: t[i][v]
-#pragma unroll
-            for (int v = 0; v < 3; ++v)
-              t3[v] = i == 0 ? g[e][0][v] : i == 3 ? g[e][2][v] : 0.5f * (g[e][0][v] + (i == 1 ? g[e][1][v] : -g[e][1][v]) + g[e][2][v]);
-            const float uv = j == 0 ? t3[0] : j == 3 ? t3[2] : 0.5f * (t3[0] + (j == 1 ? t3[1] : -t3[1]) + t3[2]);
-            const unsigned b0 = __float_as_uint(uv) & 0xffff0000u;
-            const float r1 = uv - __uint_as_float(b0);               // exact
-            const unsigned b1 = __float_as_uint(r1) & 0xffff0000u;
-            const float r2 = r1 - __uint_as_float(b1);               // exact; 8 significant bits are left
-            p0[e] = (unsigned short)(b0 >> 16), p1[e] = (unsigned short)(b1 >> 16), p2[e] = (unsigned short)(__float_as_uint(r2) >> 16);
-          }
-          u32x4 q0, q1, q2;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            q0[e] = (unsigned)p0[2 * e] | ((unsigned)p0[2 * e + 1] << 16);
-            q1[e] = (unsigned)p1[2 * e] | ((unsigned)p1[2 * e + 1] << 16);
-            q2[e] = (unsigned)p2[2 * e] | ((unsigned)p2[2 * e + 1] << 16);
-          }
-          u32x4* q = dst + (i * 4 + j) * 192;
-          q[0] = q0, q[64] = q1, q[128] = q2;
-        }
-    }
-    return;
-  }
-  const int64_t total = (int64_t)Np * Cp;
-  for (int64_t idx = vblock * (int64_t)blockDim.x + threadIdx.x; idx < total; idx += (int64_t)vgrid * blockDim.x) {
-    const int c = (int)(idx % Cp), n = (int)(idx / Cp);
-    float g[3][3];
-#pragma unroll
-    for (int u = 0; u < 3; ++u)
-#pragma unroll
-      for (int v = 0; v < 3; ++v) {
-        float x = 0.f;
-        if (n < Cout && c < Cin) {
-          // forward: w is (Cout, Cin, 3, 3) and n = cout, c = cin.  dgrad: the layer's weight is (C_layer_out = Cin here,
-          // C_layer_in = Cout here, 3, 3): output channel n of the dgrad conv is the layer's input channel.
-          x = dgrad ? w[(((int64_t)c * Cout + n) * 3 + (2 - u)) * 3 + (2 - v)] : w[(((int64_t)n * Cin + c) * 3 + u) * 3 + v];
-        }
-        g[u][v] = x;
-      }
-    float t[4][3];
-#pragma unroll
-    for (int v = 0; v < 3; ++v) {
-      t[0][v] = g[0][v];
-      t[1][v] = 0.5f * (g[0][v] + g[1][v] + g[2][v]);
-      t[2][v] = 0.5f * (g[0][v] - g[1][v] + g[2][v]);
-      t[3][v] = g[2][v];
-    }
-    float u[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      u[i][0] = t[i][0];
-      u[i][1] = 0.5f * (t[i][0] + t[i][1] + t[i][2]);
-      u[i][2] = 0.5f * (t[i][0] - t[i][1] + t[i][2]);
-      u[i][3] = t[i][2];
-    }
-    if (prec == 0) {
-      float* dst = U + (((int64_t)(n >> 5) * (Cp >> 3) + (c >> 3)) * 16) * 256 + ((((c >> 2) & 1) * 32 + (n & 31)) * 4 + (c & 3));
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) dst[(i * 4 + j) * 256] = u[i][j];
-    } else {
-      uint16_t* dst = reinterpret_cast<uint16_t*>(U) + (((int64_t)(n >> 5) * (Cp >> 4) + (c >> 4)) * 16) * (3 * 512) +
-                      ((((c >> 3) & 1) * 32 + (n & 31)) * 8 + (c & 7));
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const unsigned b0 = __float_as_uint(u[i][j]) & 0xffff0000u;
-          const float r1 = u[i][j] - __uint_as_float(b0);            // exact
-          const unsigned b1 = __float_as_uint(r1) & 0xffff0000u;
-          const float r2 = r1 - __uint_as_float(b1);                 // exact; 8 significant bits are left
-          uint16_t* q = dst + (i * 4 + j) * (3 * 512);
-          q[0] = (uint16_t)(b0 >> 16);
-          q[512] = (uint16_t)(b1 >> 16);
-          q[1024] = (uint16_t)(__float_as_uint(r2) >> 16);
-        }
-    }
-  }
-}
-
-__global__ void pack_wino_w_kernel(const float* __restrict__ w, float* __restrict__ U, int Cout, int Cin, int Cp, int Np,
-                                   int dgrad, int prec) {
-  pack_wino_w_body(w, U, Cout, Cin, Cp, Np, dgrad, prec, blockIdx.x, gridDim.x);
-}
-
-// Every Winograd weight set of a model in ONE launch (a train step re-packs 17 forward + 17 data-gradient sets after each
-// optimizer step: 34 launches of ~5 us, most of them smaller than a launch gap).  The item table lives in device memory (the launcher uploads it when it changes: a
-// 1.6 KB by-value kernel argument cost ~100 us of host time per launch).
-__global__ void pack_wino_w_multi_kernel(const WinoPackBatch* __restrict__ bp) {
-  const WinoPackBatch& b = *bp;
-  int i = 0;
-  while (i + 1 < b.n && blockIdx.x >= b.it[i + 1].blk0) ++i;   // <= 40 items: a linear scan of the block prefix
-  const WinoPackItem& t = b.it[i];
-  const unsigned vgrid = (i + 1 < b.n ? b.it[i + 1].blk0 : b.total_blocks) - t.blk0, vblock = blockIdx.x - t.blk0;
-  switch (t.kind) {   // block-uniform
-    case PACK_WINO: pack_wino_w_body(t.w, t.U, t.Cout, t.Cin, t.Cp, t.Np, t.dgrad, b.prec, vblock, vgrid); break;
-    case PACK_FIRST_W: pack_first_w_body(t.w, t.U, t.Cout, t.Cin, vblock, vgrid); break;
-    case PACK_CONVT_X3: pack_convt_x3_body(t.w, reinterpret_cast<uint16_t*>(t.U), t.Cin, t.Cout, t.dgrad, vblock, vgrid); break;
-    case PACK_BIAS_TILE: bias_tile_body(t.w, t.U, t.Cout, t.Cin, vblock, vgrid); break;
-    case PACK_DGRAD_W: pack_dgrad_w_body(t.w, t.U, t.Cout, t.Cin, t.Cp, t.dgrad, t.Np, vblock, vgrid); break;
-    case PACK_FIRST_MFMA: pack_first_mfma_body(t.w, reinterpret_cast<uint16_t*>(t.U), t.Cout, t.Cin, vblock, vgrid); break;
-    default: break;
-  }
-}
-
-// n tiles padded to pairs; 6 bytes per value in the three-piece layout (sized for either)
-size_t wino_u_floats(int Cout, int Cp) { return (size_t)((Cout + 63) / 64 * 64) * Cp * 24; }
-
-// fills the launcher-owned fields of a batch (Np, block prefix); false if an item is not packable
-bool wino_pack_batch_prepare(WinoPackBatch& b) {
-  unsigned blk = 0;
-  for (int i = 0; i < b.n; ++i) {
-    WinoPackItem& t = b.it[i];
-    t.blk0 = blk;
-    int64_t work;   // threads' worth of elements
-    switch (t.kind) {
-      case PACK_WINO:
-        if (t.Cp & (b.prec ? 15 : 7)) return false;
-        t.Np = (t.Cout + 63) / 64 * 64;
-        work = (int64_t)t.Np * t.Cp / (b.prec ? 8 : 1);
-        break;
-      case PACK_FIRST_W: work = 9 * 4 * (int64_t)t.Cout; break;
-      case PACK_CONVT_X3:
-        if ((t.Cin & 31) || (t.Cout & 31)) return false;
-        work = (int64_t)t.Cin * t.Cout * 4;
-        break;
-      case PACK_BIAS_TILE: work = (int64_t)t.Cout * t.Cin; break;
-      case PACK_DGRAD_W: work = (int64_t)t.Cin * t.Np; break;
-      case PACK_FIRST_MFMA: work = 2 * 64 * 8; break;
-      default: return false;
-    }
-    blk += (unsigned)std::max<int64_t>(1, std::min<int64_t>(2048, (work + 255) / 256));
-  }
-  b.total_blocks = blk;
-  return true;
-}
-hipError_t launch_pack_wino_w_multi(const WinoPackBatch* batch_dev, unsigned total_blocks, hipStream_t s) {
-  if (total_blocks == 0) return hipSuccess;
-  hipLaunchKernelGGL(pack_wino_w_multi_kernel, dim3(total_blocks), dim3(256), 0, s, batch_dev);
-  return hipGetLastError();
-}
-
-hipError_t launch_pack_wino_w(const float* w, float* U, int Cout, int Cin, int Cp, int dgrad, int prec, hipStream_t s) {
-  if (Cp & (prec ? 15 : 7)) return hipErrorInvalidValue;
-  const int Np = (Cout + 63) / 64 * 64;
-  int64_t blocks = ((int64_t)Np * Cp + 255) / 256;
-  if (blocks > 65535) blocks = 65535;
-  hipLaunchKernelGGL(pack_wino_w_kernel, dim3((unsigned)blocks), dim3(256), 0, s, w, U, Cout, Cin, Cp, Np, dgrad, prec);
-  return hipGetLastError();
-}
+// The kernels read U in the layout pack_wino_w_body writes, in pack.hip.
 
 // Work split (MODE):
 //   0: 8 wavefronts, 64 output channels; wave (i, g) owns transform row i, n tile g and both m tiles of the patch

@@ -1,4 +1,4 @@
-"""numpy restatement of the three-piece bf16 product of the fp32 kernels (csrc/device.h: split3_pack; csrc/pack_small.h: the weight
+"""numpy restatement of the three-piece bf16 product of the fp32 kernels (csrc/device.h: split3_pack; csrc/pack.hip: the weight
 packs), shared by tests/test_split_host.py (CPU) and tests/test_gpu_split_kernels.py (GPU).
 
 An fp32 operand is cut into three bf16 pieces by TRUNCATION, a = p0 + p1 + p2 exactly, and a kernel keeps six of the nine piece

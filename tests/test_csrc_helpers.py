@@ -35,3 +35,19 @@ def test_kernel_files_declare_no_vector_types_and_retired_names_are_gone():
     assert [f for f, t in SOURCES.items() if f.endswith(".hip") and "ext_vector_type" in t] == []
     assert {n: definitions(n) for n in RETIRED if definitions(n)} == {}
     assert [(f, n) for f, t in SOURCES.items() for n in RETIRED[:4] if re.search(r"\b" + n + r"\b", t)] == []
+
+
+PACK_BODIES = ["pack_wino_w_body", "pack_first_w_body", "pack_first_mfma_body", "pack_convt_x3_body", "pack_bias_tile_body",
+               "pack_dgrad_w_body", "pack_conv_w_body", "pack_convt_w_body", "pack_convt_bf16f_body", "pack_convt_dgrad_w_body"]
+
+
+def test_weight_form_packers_live_in_pack_hip_only():
+    """every element loop of a weight form and their dispatcher are defined once, in pack.hip, and no other kernel file launches a
+    packer of its own (elementwise.hip keeps pack_input_kernel: activations, not weights)"""
+    where = {n: definitions(n) for n in PACK_BODIES + ["pack_item"]}
+    assert {n: w for n, w in where.items() if [f for f, _ in w] != ["pack.hip"]} == {}
+    found = set(re.findall(r"\b(pack_\w+_body)\b", "".join(SOURCES.values())))
+    assert found == set(PACK_BODIES)
+    kernels = {f: re.findall(r"__global__\s[^;{(]*?\b(pack_\w*)\s*\(", t) for f, t in SOURCES.items() if f.endswith(".hip")}
+    assert {f: k for f, k in kernels.items() if k and f != "pack.hip"} == {"elementwise.hip": ["pack_input_kernel"]}
+    assert sorted(kernels["pack.hip"]) == ["pack_batch_kernel", "pack_one_kernel"]

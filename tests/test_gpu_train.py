@@ -163,6 +163,33 @@ def test_c5_step_record_from_reference(cuda, golden, tag, shape):
     assert np.abs(sd["encoder.bottleneck.bn2.running_var"].cpu().numpy() - g[f"{tag}_bn_rv_b"]).max() <= 1e-5
 
 
+def test_one_off_and_batched_weight_packs_write_the_same_bytes(cuda):
+    """The two launch paths of csrc/pack.hip fill a form with the same bytes.  After load_state_dict the first backward of a context
+    packs its data-gradient forms one at a time (launch_pack_one: the Winograd U of every 3x3 layer, the three-piece fragments of
+    both ConvTranspose layers, the final conv's panel), because the context had not trained when the weights were loaded; after a
+    refresh with unchanged parameters the same forms come from the one batched launch.  Channels 32 / 64 / 128 admit the Winograd
+    data gradient on every layer and the three-piece data gradient on both up-convolutions; 24 x 40 has edge patches at all three
+    levels.  The sums of a step are repeatable, so the steps must agree bit for bit: (b) == (c) first, which tells "not repeatable"
+    from "the paths differ"."""
+    cfg, shape = (3, 2, 32, 2), (2, 3, 24, 40)
+    model = build(cfg, 31, cuda)
+    x = torch.from_numpy(O.formula_normal("pack/x", shape, seed=31)).to(cuda)
+    y = torch.from_numpy(O.formula_labels("pack/y", (shape[0], shape[2], shape[3]), cfg[1], seed=32)).to(cuda)
+    tr = mgunet.Trainer(model)
+
+    def step():
+        loss = tr.forward_backward(x, y)
+        return loss.clone(), tr.grad.clone()
+
+    a = step()                             # forms of the data gradient packed lazily, one launch each
+    model.refresh_packed_weights(cuda)     # every form in the batched launch
+    b = step()
+    c = step()
+    assert float(b[1].abs().max()) > 0 and bool(torch.isfinite(b[1]).all())
+    assert torch.equal(b[0], c[0]) and torch.equal(b[1], c[1])
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+
+
 def test_adam_kernel_exact(cuda):
     """mgu_adam_step against torch.optim.Adam(lr, weight_decay) semantics evaluated in float64 on the host."""
     from mgunet import _lib

@@ -2,7 +2,8 @@
 """isa_compare.py OLD_CSRC NEW_CSRC -- did a change to csrc/ change any device code?  Needs hipcc, no GPU.
 
 Every .hip of both trees is compiled for the device only with its own Makefile's flags (hipcc $(CXXFLAGS) --offload-device-only
--S), the lines naming the per-compile __hip_cuid_ symbol are dropped and the text is cut per symbol: a function's instruction
+-S), the lines naming the per-compile __hip_cuid_ symbol are dropped, the per-file numbering of local labels is taken out (in the
+loop comments too) and the text is cut per symbol: a function's instruction
 stream (label .. .Lfunc_end, with its .amdhsa_kernel block) and its entry in the .amdgpu_metadata note.  What is left over (LDS
 and constant symbols, file-scope directives) is compared as one more piece per file.  Prints every kernel that differs; exit
 status 1 if any does or if the sets of symbols differ."""
@@ -13,7 +14,7 @@ import sys
 import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
-LOCAL = re.compile(r"\.L(BB|func_end|func_begin|tmp|JTI)\d+")   # local labels carry the function's index in its file
+LOCAL = re.compile(r"(\.L(?:BB|func_end|func_begin|tmp|JTI)|\bBB)\d+")   # local labels, and the loop comments naming them, carry the function's index in its file
 
 
 def make_var(mk, name):
@@ -27,7 +28,8 @@ def device_asm(csrc, hip, out):
                        capture_output=True, text=True)
     if r.returncode:
         sys.exit(f"{csrc}/{hip}: {r.stderr[-2000:]}")
-    return [LOCAL.sub(lambda m: ".L" + m.group(1), l) for l in open(out) if "__hip_cuid_" not in l]
+    # (the comment column after a label moves with the number of digits taken out of it)
+    return [re.sub(r"[ \t]+;", " ;", LOCAL.sub(lambda m: m.group(1), l)) for l in open(out) if "__hip_cuid_" not in l]
 
 
 def pieces(lines, hip):
