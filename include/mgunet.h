@@ -581,6 +581,34 @@ int mgu_equalize_hist_rgb_u8(mgu_ctx* ctx, const uint8_t* rgb_dev, int H, int W,
  * padded bottom / right; per_channel = 0: one value per patch over all channels, 1: one per channel.  out (nph*npw, 1 | channels). */
 int mgu_patch_mean_u8(mgu_ctx* ctx, const uint8_t* img_dev, int H, int W, int channels, int patch, int per_channel, float* out_dev,
                       void* hip_stream);
+/* ---- graph-branch inputs for a whole batch: the node features scripts/graph_refinement.py:72-113 defines and the patch labels
+ *      scripts/train_end_to_end.py:340 describes (the training script draws both from torch's RNG, :326 / :342) -----------------------
+ * Node features.  rgb (B,H,W,3) uint8 -> rows (B*nph*npw, ld_out) fp32, nph = ceil(H / patch), npw = ceil(W / patch), patches zero
+ * padded bottom / right as image_to_patches pads them, image b's patches at rows [b*nph*npw, (b+1)*nph*npw) in raster order.  Columns:
+ *   [0, repeat)         patches.mean(dim=[1,2,3]) repeated (:78; the script's repeat is 16) of the normalised fp32 image (B,3,H,W) whose
+ *                       element (b,c,y,x) is img_dev[b*is_n + c*is_c + y*is_h + x*is_w] (NCHW or NHWC storage): double accumulation in a
+ *                       fixed order over the patch's real pixels (pad pixels are zeros), / (3 patch^2), rounded once.  Skipped (no
+ *                       columns) when img_dev is NULL or repeat is 0.
+ *   next unet_cols      a copy of row i of unet_rows_dev (B*nph*npw, unet_cols) fp32 -- e.g. what mgu_unet_request_patch_mean or
+ *                       mgu_patch_mean wrote.  Skipped when unet_rows_dev is NULL.
+ *   next 1              mean byte of mgu_sobel_edges_u8(image b) over the patch (:89, :97-98)
+ *   next 3 | 1          mean bytes of mgu_equalize_hist_rgb_u8(image b): per channel (per_channel 1; :101-103) or over all three (0)
+ *   up to ld_out        zeros (ld_out >= the used columns; it lets a caller meet the GAT's Fin % 4 == 0 without another copy)
+ * The two byte blocks equal mgu_patch_mean_u8 of the per-image maps bit for bit, but no map is written: one memset and three launches
+ * whatever B is (per-image histogram + largest gradient; B equalisation tables; one workgroup, or one wave, per patch).  patch 1..64,
+ * H*W < 2^31, B*nph*npw < 2^31.  Deterministic. */
+int mgu_patch_node_features_u8(mgu_ctx* ctx, const uint8_t* rgb_dev, int B, int H, int W, int patch, const float* img_dev, int64_t is_n,
+                               int64_t is_c, int64_t is_h, int64_t is_w, int repeat, const float* unet_rows_dev, int unet_cols, int per_channel,
+                               float* out_dev, int ld_out, void* hip_stream);
+/* Patch labels: one class per patch x patch window (the same grid, padding and row order as above) of B images.  src_kind as in
+ * mgu_connected_components: 0 = int64 class map (B,H,W); 1 = NHWC fp32 logits (B,H,W,C) -- what mgu_unet_forward writes -- whose
+ * per-pixel class is the first maximal channel (bit-identical to mgu_argmax_classes).  counts_dev (NULL: skipped): int32 (B*Np, C)
+ * class histogram over the patch's REAL pixels -- pad pixels are not counted, and map values outside [0, C) (-100 ignore labels) are
+ * counted nowhere; labels_dev: int64 (B*Np) the class with the largest count, the lowest such class on ties; purity_dev (NULL:
+ * skipped): fp32 (B*Np) (float)((double)that count / (double)real pixels of the patch).  A patch with no counted pixel gets label 0
+ * and purity 0.  1 <= C <= 32 (beyond: MGU_ERR_INVALID), patch 1..4096.  One launch; integer counts: exact and deterministic. */
+int mgu_patch_labels(mgu_ctx* ctx, const void* src_dev, int src_kind, int B, int H, int W, int C, int patch, int32_t* counts_dev,
+                     int64_t* labels_dev, float* purity_dev, void* hip_stream);
 /* postprocess_segmentation (scripts/infer_segmentation.py:20-51, :123): class labels int64 -> colour map uint8 (npix, 3) through a
  * palette (num_classes, 3) the caller provides (the reference's BGR list), labels outside [0, num_classes) stay black; and, if
  * labels_u8_dev != NULL, the uint8 label map written next to it. */

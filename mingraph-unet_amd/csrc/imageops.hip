@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "imgmath.h"
 
 namespace mgu {
 
@@ -139,10 +140,7 @@ __global__ __launch_bounds__(256) void mask_nearest_kernel(const uint8_t* __rest
 
 // ---- Sobel edge magnitude (edge_detection.py:28-44): RGB2GRAY (14-bit fixed point), 3x3 Sobel with reflect-101 borders in exact
 // integers, sqrt(gx^2 + gy^2) / max * 255 in double, truncated to uint8 -------------------------------------------------------------------
-// cv2.COLOR_RGB2GRAY on 8-bit data: OpenCV 3.4 / 4.x use 15-bit coefficients (RY15 9798, GY15 19235, BY15 3735, gray_shift 15); only
-// the YUV / YCrCb conversions below keep the 14-bit ones (yuv_shift 14)
-__device__ __forceinline__ int cv_gray(const uint8_t* p) { return (p[0] * 9798 + p[1] * 19235 + p[2] * 3735 + (1 << 14)) >> 15; }
-__device__ __forceinline__ int reflect101(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
+// (cv_gray, reflect101, sobel_mag2, sobel_norm_u8: imgmath.h, shared with the batched per-patch path of patch_inputs.hip)
 __global__ __launch_bounds__(256) void sobel_mag2_kernel(const uint8_t* __restrict__ rgb, int H, int W, int* __restrict__ mag2,
                                                          unsigned* __restrict__ max2) {
   unsigned local = 0;
@@ -157,9 +155,7 @@ __global__ __launch_bounds__(256) void sobel_mag2_kernel(const uint8_t* __restri
         const int yy = H > 1 ? reflect101(y + dy - 1, H) : 0, xx = W > 1 ? reflect101(x + dx - 1, W) : 0;
         g[dy][dx] = cv_gray(rgb + ((size_t)yy * W + xx) * 3);
       }
-    const int gx = (g[0][2] + 2 * g[1][2] + g[2][2]) - (g[0][0] + 2 * g[1][0] + g[2][0]);
-    const int gy = (g[2][0] + 2 * g[2][1] + g[2][2]) - (g[0][0] + 2 * g[0][1] + g[0][2]);
-    const int m = gx * gx + gy * gy;
+    const int m = sobel_mag2(g);
     mag2[i] = m;
     local = max(local, (unsigned)m);
   }
@@ -171,17 +167,11 @@ __global__ __launch_bounds__(256) void sobel_norm_kernel(const int* __restrict__
                                                          uint8_t* __restrict__ out) {
   const double mx = sqrt((double)*max2);
   for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-    out[i] = mx > 0.0 ? (uint8_t)(sqrt((double)mag2[i]) / mx * 255.0) : (uint8_t)0;   // (e / max * 255).astype(uint8): truncation
+    out[i] = sobel_norm_u8(mag2[i], mx);
 }
 
 // ---- histogram equalisation of the luminance (histogram_equalization.py:27-35): cv2 RGB2YUV / equalizeHist / YUV2RGB ----------------
-__device__ __forceinline__ int cv_descale14(int v) { return (v + (1 << 13)) >> 14; }
-__device__ __forceinline__ int sat8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
-__device__ __forceinline__ void cv_rgb2yuv(const uint8_t* p, int& Y, int& U, int& V) {
-  Y = cv_descale14(p[0] * 4899 + p[1] * 9617 + p[2] * 1868);
-  U = sat8(cv_descale14((p[2] - Y) * 8061 + (128 << 14)));    // B2UF = 0.492
-  V = sat8(cv_descale14((p[0] - Y) * 14369 + (128 << 14)));   // R2VF = 0.877
-}
+// (cv_rgb2yuv, cv_yuv2rgb, equalize_lut_build: imgmath.h)
 __global__ __launch_bounds__(256) void yuv_hist_kernel(const uint8_t* __restrict__ rgb, int64_t n, unsigned* __restrict__ hist) {
   __shared__ unsigned h[256];
   h[threadIdx.x] = 0;
@@ -195,35 +185,18 @@ __global__ __launch_bounds__(256) void yuv_hist_kernel(const uint8_t* __restrict
   if (h[threadIdx.x]) atomicAdd(&hist[threadIdx.x], h[threadIdx.x]);
 }
 __global__ void equalize_lut_kernel(const unsigned* __restrict__ hist, int64_t total, uint8_t* __restrict__ lut) {
-  // cv::equalizeHist: first non-empty bin i0; scale = 255 / (total - hist[i0]); lut[i] = saturate(round(cumsum_{i0 < j <= i} * scale))
-  if (threadIdx.x != 0) return;
-  int i0 = 0;
-  while (i0 < 256 && !hist[i0]) ++i0;
-  if (i0 == 256 || hist[i0] == total) {
-    for (int i = 0; i < 256; ++i) lut[i] = (uint8_t)(i0 < 256 ? i0 : i);   // a constant image maps to itself
-    return;
-  }
-  const float scale = 255.f / (float)(total - hist[i0]);
-  int sum = 0;
-  for (int i = 0; i < 256; ++i) {
-    if (i <= i0) {
-      lut[i] = 0;
-      continue;
-    }
-    sum += hist[i];
-    lut[i] = (uint8_t)sat8((int)rintf((float)sum * scale));
-  }
+  if (threadIdx.x == 0) equalize_lut_build(hist, total, lut);
 }
 __global__ __launch_bounds__(256) void equalize_apply_kernel(const uint8_t* __restrict__ rgb, int64_t n, const uint8_t* __restrict__ lut,
                                                              uint8_t* __restrict__ out) {
   for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     int Y, U, V;
     cv_rgb2yuv(rgb + i * 3, Y, U, V);
-    Y = lut[Y];
-    const int u = U - 128, v = V - 128;
-    out[i * 3 + 0] = (uint8_t)sat8(Y + cv_descale14(v * 18678));                  // V2RI = 1.140
-    out[i * 3 + 1] = (uint8_t)sat8(Y + cv_descale14(u * -6472 + v * -9519));      // U2GI = -0.395, V2GI = -0.581
-    out[i * 3 + 2] = (uint8_t)sat8(Y + cv_descale14(u * 33292));                  // U2BI = 2.032
+    int r, g, b;
+    cv_yuv2rgb(lut[Y], U, V, r, g, b);
+    out[i * 3 + 0] = (uint8_t)r;
+    out[i * 3 + 1] = (uint8_t)g;
+    out[i * 3 + 2] = (uint8_t)b;
   }
 }
 

@@ -489,6 +489,7 @@ class E2ETrainer:
         self.graph_opt = FlatAdam([patch_gat, segment_predictor, *self.extra_modules], lr=unet_trainer.lr, weight_decay=unet_trainer.wd,
                                   betas=unet_trainer.betas, eps=unet_trainer.eps, exclude=tuple(untouched_params))
         self._batch_graph = None
+        self._graphs = {}   # step_images: one PatchGraphConstructor per patch size (its edge lists are cached per shape)
 
     def _block_diagonal(self, edge_index: torch.Tensor, Np: int, B: int):
         """(edge_index of the B-image batch, graph_ptr): image b's nodes are [b * Np, (b + 1) * Np).  Cached per (edge_index, B)."""
@@ -538,3 +539,22 @@ class E2ETrainer:
         total = loss_seg.detach() + self.wf * lf.detach() + self.wp * lp.detach()
         return {"total": total, "l_unet_seg": loss_seg.detach(), "l_shape": torch.zeros((), device=images.device),
                 "l_feature": lf.detach(), "l_partition": lp.detach(), "l_smooth": torch.zeros((), device=images.device)}
+
+    def step_images(self, images, masks, images_u8, f_unet_patches, edge_index=None, patch_size: int = 16) -> dict:
+        """`step` on inputs derived from the batch itself instead of placeholders: patch_features = patch_node_features(images_u8, p,
+        images=images) (scripts/graph_refinement.py:72-113: patch pixel mean x 16 | Sobel mean | equalised-image means, 20 columns),
+        patch_labels = patch_labels(masks, p) (the ground-truth form of train_end_to_end.py:340) and, when none is given, edge_index from
+        PatchGraphConstructor(p).  images_u8: the batch's (B, H, W, 3) RGB bytes.  f_unet_patches stays an argument: the reference never
+        defines it (its width has to equal the patch GAT's output width)."""
+        from .patch_inputs import feature_width, patch_labels, patch_node_features
+        p = int(patch_size)
+        B, _, H, W = images.shape
+        want = self.patch_gat.gat_layers[0].heads[0].W.weight.shape[1]
+        have = feature_width()
+        if want != have:
+            raise ValueError(f"the patch GAT takes {want} input features but patch_node_features rows are {have} wide")
+        X = patch_node_features(images_u8, p, images=images)
+        Y = patch_labels(masks, p, num_classes=self.unet.model.num_classes)
+        if edge_index is None:
+            edge_index = self._graphs.setdefault(p, PatchGraphConstructor(p)).edge_index(H, W, images.device)
+        return self.step(images, masks, X.view(B, -1, have), f_unet_patches, Y, edge_index)
