@@ -167,6 +167,28 @@ int mgu_bn_relu_train_nhwc(mgu_ctx* ctx, const void* z_dev, const void* gamma_de
 int mgu_bn_relu_backward_nhwc(mgu_ctx* ctx, const void* dy_dev, int ld_dy, const void* z_dev, const void* gamma_dev, const void* beta_dev,
                               const void* mean_dev, const void* invstd_dev, int64_t M, int C, void* dz_dev, void* dgamma_dev,
                               void* dbeta_dev, void* dbias_dev, void* hip_stream);
+/* ---- train-step building blocks: half a ConvBlock (unet_encoder.py:7-25) exactly as the training step runs it -- the functions
+ *      mgu_unet_forward(training=1) / mgu_unet_backward call per layer, on caller-provided tensors ----------------------------------
+ * Conv2d(k=3, pad=1, bias) -> BatchNorm2d(train: eps 1e-5, momentum 0.1) -> ReLU [-> MaxPool2d(2)].  in: (B,H,W,ld_in) NHWC, ld_in % 4 ==
+ * 0, channels [Cin, ld_in) zero; w (Cout,Cin,3,3); Cout % 4 == 0.  Writes z = conv + bias (B,H,W,Cout) dense, y = relu(bn(z)) with
+ * pitch ld_y, pooled_dev (B,H/2,W/2,Cout) dense unless NULL, the batch mean / 1/sqrt(biased var + eps), and updates run_mean / run_var
+ * in place (unbiased variance).  *stats_fused_out (may be NULL): 1 if the batch statistics were accumulated by the convolution's
+ * epilogue, 0 if by a pass over z; *pool_fused_out: 1 if the pooled tensor was written by the BatchNorm apply pass (even H and W), 0 if
+ * by the pool kernel (or not at all). */
+int mgu_conv_bn_relu_train_nhwc(mgu_ctx* ctx, const void* in_dev, int ld_in, int B, int H, int W, int Cin, const void* w_oihw_dev,
+                                const void* bias_dev, const void* gamma_dev, const void* beta_dev, int Cout, void* z_dev, void* y_dev,
+                                int ld_y, void* pooled_dev, void* mean_dev, void* invstd_dev, void* run_mean_dev, void* run_var_dev,
+                                int* stats_fused_out, int* pool_fused_out, void* hip_stream);
+/* ... and its backward: BatchNorm + ReLU backward (dy (B,H,W,ld_dy) -> dz (B,H,W,Cout) dense, dgamma, dbeta; the ReLU mask is recomputed
+ * from z), the weight gradient dw (Cout,Cin,3,3), whose unpack launch also folds the column sums of dz into dbias (analytically 0), and
+ * -- din_dev != NULL -- the data gradient din (B,H,W,ld_din >= Cin).  in / z / mean / invstd: the forward's tensors. */
+int mgu_bn_relu_conv_backward_nhwc(mgu_ctx* ctx, const void* in_dev, int ld_in, const void* z_dev, const void* dy_dev, int ld_dy,
+                                   const void* gamma_dev, const void* beta_dev, const void* mean_dev, const void* invstd_dev,
+                                   const void* w_oihw_dev, int B, int H, int W, int Cin, int Cout, void* dz_dev, void* dgamma_dev,
+                                   void* dbeta_dev, void* dbias_dev, void* dw_oihw_dev, void* din_dev, int ld_din, void* hip_stream);
+/* Test hook: synchronises hip_stream and writes the largest |value| in the ctx's per-channel reduction slots to *absmax_out (host).
+ * Every reduction clears the rows it folded, so between calls of this ABI the answer is 0 (0 also before the first reduction). */
+int mgu_reduction_slots_absmax(mgu_ctx* ctx, double* absmax_out, void* hip_stream);
 /* MaxPool2d(2,2) backward ACCUMULATED into dskip (the skip tensor also receives the decoder-side gradient): y (B,H,W,ld_y) the
  * pooled tensor's input, dpool (B,H/2,W/2,C) dense, dskip (B,H,W,ld_d) += routed gradient (first maximum wins, as aten). */
 int mgu_maxpool2x2_backward_nhwc(mgu_ctx* ctx, const void* y_dev, int ld_y, const void* dpool_dev, void* dskip_dev, int ld_d, int B, int H,

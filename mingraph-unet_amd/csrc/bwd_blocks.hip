@@ -6,6 +6,7 @@
 // Kernel selection is the launchers' own (pick_conv, pick_wgrad), on the context's switches (MGU_NO_WINO_WGRAD, MGU_NO_WGRAD_HALO,
 // MGU_NO_THIN_WGRAD, MGU_NO_WINO_DGRAD, MGU_NO_WINOGRAD, ... read at mgu_create), so a test reaches every variant.
 #include <algorithm>
+#include <cmath>
 
 #include "ctx.h"
 
@@ -36,11 +37,7 @@ int get_scratch(mgu_ctx* c, size_t panel_floats, size_t dgp_floats, size_t wug_f
   const size_t o_sums = k.take(sizeof(double) * 2 * (size_t)std::max(Cmax, 64) + 64);
   int rc = ensure(c, &c->gws, &c->gws_bytes, k.off);
   if (rc) return rc;
-  const size_t need = chan_reduce_work_bytes(std::max(Cmax, 64));
-  if (c->redws_bytes < need) {   // the slots must be zero between reductions: a fresh allocation is cleared once
-    if ((rc = ensure(c, &c->redws, &c->redws_bytes, need))) return rc;
-    HIPCHK(c, hipMemset(c->redws, 0, need));
-  }
+  if ((rc = ensure_red(c, Cmax))) return rc;
   char* g = (char*)c->gws;
   out->dwp = (float*)(g + o_dwp), out->dgp = (float*)(g + o_dgp), out->wug = (float*)(g + o_wug);
   out->dwp_floats = dwp_floats, out->dgp_floats = std::max<size_t>(dgp_floats, 64);
@@ -175,6 +172,115 @@ int mgu_bn_relu_backward_nhwc(mgu_ctx* c, const void* dy_dev, int ld_dy, const v
   HIPCHK(c, launch_bn_bwd_apply((const float*)dy_dev, ld_dy, tscale, tshift, (const float*)z_dev, (const float*)mean_dev,
                                 (const float*)invstd_dev, (const float*)gamma_dev, sc.sums, M, C, (float*)dz_dev, sc.red,
                                 (float*)dbias_dev, s));
+  return MGU_OK;
+}
+
+int mgu_conv_bn_relu_train_nhwc(mgu_ctx* c, const void* in_dev, int ld_in, int B, int H, int W, int Cin, const void* w_oihw_dev,
+                                const void* bias_dev, const void* gamma_dev, const void* beta_dev, int Cout, void* z_dev, void* y_dev,
+                                int ld_y, void* pooled_dev, void* mean_dev, void* invstd_dev, void* run_mean_dev, void* run_var_dev,
+                                int* stats_fused_out, int* pool_fused_out, void* hip_stream) {
+  if (!c) return MGU_ERR_INVALID;
+  if (!in_dev || !w_oihw_dev || !bias_dev || !gamma_dev || !beta_dev || !z_dev || !y_dev || !mean_dev || !invstd_dev || !run_mean_dev ||
+      !run_var_dev || B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 4 || (Cout & 3) || Cout > 1024 || ld_y < Cout || (ld_y & 3))
+    return fail(c, MGU_ERR_INVALID, "bad conv_bn_relu_train args (4 <= Cout <= 1024, Cout and ld_y multiples of 4)");
+  if (ld_in < rup(Cin, 4) || (ld_in & 3)) return fail(c, MGU_ERR_INVALID, "ld_in must be a multiple of 4 and >= Cin rounded up to 4");
+  if ((int64_t)B * H * W >= (1ll << 31) || (int64_t)B * H * W < 2) return fail(c, MGU_ERR_INVALID, "B*H*W must be in [2, 2^31)");
+  if (pooled_dev && (H < 2 || W < 2)) return fail(c, MGU_ERR_INVALID, "the pooled output needs H, W >= 2");
+  if (c->dtype != MGU_DTYPE_F32) return fail(c, MGU_ERR_STATE, "training runs in fp32 only (bf16 storage is an inference mode)");
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)hip_stream;
+  // the caller's tensors as a model layer (mgu_unet_configure / repack_weights): the direct panel is packed by run_layer if its
+  // pick reads it, the Winograd set and the first convolution's forms here
+  Layer L = caller_layer(Cin, Cout, 3, false, B, H, W);
+  L.N = Cout, L.Np = rup(Cout, 128);
+  L.w_src = (const float*)w_oihw_dev, L.b_src = (const float*)bias_dev, L.gamma = (const float*)gamma_dev, L.beta = (const float*)beta_dev;
+  L.run_mean = (float*)run_mean_dev, L.run_var = (float*)run_var_dev, L.mean = (float*)mean_dev, L.invstd = (float*)invstd_dev;
+  L.wino = wino_layer(c->tn, 3, L.Cp);
+  L.first = first_conv_applicable(MGU_DTYPE_F32, Cin, L.Cp, Cout, 8, 0);
+  Carve k;
+  const size_t panel = (size_t)L.Np * L.Kp;
+  const size_t o_wp = k.take(panel * 4), o_ts = k.take(2 * (size_t)Cout * 4), o_sums = k.take(sizeof(double) * 2 * (size_t)Cout);
+  const size_t o_wf = k.take(L.first ? 9 * 4 * (size_t)Cout * 4 : 0), o_wfm = k.take(L.first ? first_mfma_floats() * 4 : 0);
+  int rc = ensure(c, &c->gws, &c->gws_bytes, k.off);
+  if (rc) return rc;
+  if ((rc = ensure_red(c, Cout))) return rc;
+  char* g = (char*)c->gws;
+  L.wp = (float*)(g + o_wp), L.wp_dirty = true;
+  L.tscale = (float*)(g + o_ts), L.tshift = L.tscale + Cout;
+  HIPCHK(c, hipMemsetAsync(L.wp, 0, panel * 4, s));   // the panel's padding is read as zeros
+  if (L.wino) {
+    if ((rc = ensure(c, &c->wuws, &c->wuws_bytes, wino_u_floats(Cout, L.Cp) * sizeof(float)))) return rc;
+    L.wu = (float*)c->wuws;
+    HIPCHK(c, launch_pack_one(pack_wino(L.w_src, L.wu, Cout, Cin, L.Cp, 0, c->tn.wino_prec), s));
+  }
+  if (L.first) {
+    L.wf = (float*)(g + o_wf);
+    HIPCHK(c, launch_pack_one(pack_first_w(L.w_src, L.wf, Cout, Cin), s));
+    if (Cout == 32 && Cin <= 3) {
+      L.wfm = (float*)(g + o_wfm);
+      HIPCHK(c, launch_pack_one(pack_first_mfma(L.w_src, L.wfm, Cout, Cin), s));
+    }
+  }
+  bool pool_fused = false, stats_fused = false;
+  rc = conv_bn_relu_train(c, L, (const float*)in_dev, ld_in, B, H, W, (float*)z_dev, (float*)y_dev, ld_y, (double*)(g + o_sums),
+                          (double*)c->redws, s, (float*)pooled_dev, &pool_fused, &stats_fused);
+  if (stats_fused_out) *stats_fused_out = stats_fused;
+  if (pool_fused_out) *pool_fused_out = pool_fused;
+  // an error return between the epilogue's sums and their fold would leave rows of the slots non-zero: clear them
+  if (rc != MGU_OK) (void)hipMemsetAsync(c->redws, 0, c->redws_bytes, s);
+  return rc;
+}
+
+int mgu_bn_relu_conv_backward_nhwc(mgu_ctx* c, const void* in_dev, int ld_in, const void* z_dev, const void* dy_dev, int ld_dy,
+                                   const void* gamma_dev, const void* beta_dev, const void* mean_dev, const void* invstd_dev,
+                                   const void* w_oihw_dev, int B, int H, int W, int Cin, int Cout, void* dz_dev, void* dgamma_dev,
+                                   void* dbeta_dev, void* dbias_dev, void* dw_oihw_dev, void* din_dev, int ld_din, void* hip_stream) {
+  if (!c) return MGU_ERR_INVALID;
+  if (!in_dev || !z_dev || !dy_dev || !gamma_dev || !beta_dev || !mean_dev || !invstd_dev || !w_oihw_dev || !dz_dev || !dgamma_dev ||
+      !dbeta_dev || !dbias_dev || !dw_oihw_dev || B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 4 || (Cout & 3) || Cout > 1024 ||
+      ld_dy < Cout || (ld_dy & 3))
+    return fail(c, MGU_ERR_INVALID, "bad bn_relu_conv_backward args (4 <= Cout <= 1024, Cout and ld_dy multiples of 4)");
+  if (ld_in < rup(Cin, 4) || (ld_in & 3)) return fail(c, MGU_ERR_INVALID, "ld_in must be a multiple of 4 and >= Cin rounded up to 4");
+  if (din_dev && ld_din < Cin) return fail(c, MGU_ERR_INVALID, "ld_din %d < Cin %d", ld_din, Cin);
+  if ((int64_t)B * H * W >= (1ll << 31) || (int64_t)B * H * W < 2) return fail(c, MGU_ERR_INVALID, "B*H*W must be in [2, 2^31)");
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)hip_stream;
+  Layer L = caller_layer(Cin, Cout, 3, false, B, H, W);
+  L.t_in = (const float*)in_dev, L.t_ldin = ld_in, L.t_z = (float*)const_cast<void*>(z_dev);
+  L.w_src = (const float*)w_oihw_dev, L.gamma = (const float*)gamma_dev, L.beta = (const float*)beta_dev;
+  L.mean = (float*)const_cast<void*>(mean_dev), L.invstd = (float*)const_cast<void*>(invstd_dev);
+  const bool wino = din_dev && wino_dgrad_layer(c->tn, 3, Cout);
+  const size_t dpanel = din_dev ? (size_t)rup(Cin, 128) * rup(9 * Cout, 32) : 0;
+  Scratch sc;
+  int rc = get_scratch(c, (size_t)rup(Cout, 128) * L.Kp, dpanel + 2 * (size_t)Cout, wino ? wino_u_floats(Cin, Cout) : 0, Cout, &sc);
+  if (rc) return rc;
+  L.wug = wino ? sc.wug : nullptr;   // the Winograd set, when the pick takes that kernel, is packed into the scratch
+  // forward scale / shift behind the data-gradient panel (the ReLU mask is recomputed from z): scale = gamma*invstd, shift = beta - mean*scale
+  L.tscale = sc.dgp + dpanel, L.tshift = L.tscale + Cout;
+  hipLaunchKernelGGL(fold_batch_stats_kernel, dim3((Cout + 255) / 256), dim3(256), 0, s, L.gamma, L.beta, L.mean, L.invstd, L.tscale, L.tshift,
+                     Cout);
+  HIPCHK(c, hipGetLastError());
+  LayerGrads g;
+  g.dw = (float*)dw_oihw_dev, g.dbias = (float*)dbias_dev, g.dgamma = (float*)dgamma_dev, g.dbeta = (float*)dbeta_dev;
+  rc = conv_bn_relu_backward(c, L, (const float*)dy_dev, ld_dy, (float*)dz_dev, g, (float*)din_dev, ld_din, sc, s);
+  // an error return between the deferred column sums and their fold would leave rows of the slots non-zero: clear them
+  if (rc != MGU_OK) (void)hipMemsetAsync(c->redws, 0, c->redws_bytes, s);
+  return rc;
+}
+
+int mgu_reduction_slots_absmax(mgu_ctx* c, double* absmax_out, void* hip_stream) {
+  if (!c || !absmax_out) return MGU_ERR_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize((hipStream_t)hip_stream));
+  std::vector<double> host(c->redws_bytes / sizeof(double));
+  if (!host.empty()) HIPCHK(c, hipMemcpy(host.data(), c->redws, host.size() * sizeof(double), hipMemcpyDeviceToHost));
+  double m = 0.0;
+  for (double v : host) {
+    if (std::fabs(v) <= m) continue;
+    m = std::fabs(v);
+    if (m != m) break;   // a NaN is the answer
+  }
+  *absmax_out = m;
   return MGU_OK;
 }
 

@@ -328,11 +328,27 @@ struct BwdScratch {
 int conv_dgrad(mgu_ctx* c, const Layer& L, const float* dz, float* out, int ldout, const BwdScratch& w, bool record, hipStream_t s);
 int convt_dgrad(mgu_ctx* c, const Layer& U, const float* dout, int ld_d, int Hout, int Wout, float* out, const BwdScratch& w, bool record,
                 hipStream_t s);
-// dz dense with pitch rup(Cout, 4); fold_rows != nullptr: also folds the bias-gradient column sums pending in w.red (bn_relu_bwd)
+// dz dense with pitch rup(Cout, 4); fold_rows != nullptr: also folds the bias-gradient column sums pending in w.red (conv_bn_relu_backward)
 int conv_wgrad(mgu_ctx* c, const Layer& L, const float* dz, float* dw, const BwdScratch& w, bool record, hipStream_t s,
                int* fold_rows = nullptr, float* dbias = nullptr);
 int convt_wgrad(mgu_ctx* c, const Layer& U, const float* dout, int ld_d, int c_off, int Hout, int Wout, float* dw, const BwdScratch& w,
                 hipStream_t s);
+// the context's reduction slots (mgu_ctx::redws) sized for layers of up to Cmax channels; a fresh allocation is cleared, once
+int ensure_red(mgu_ctx* c, int Cmax);
+// One conv -> BatchNorm(train) -> ReLU of the training forward on layer L (z dense with pitch Cout, y with pitch ldy): the batch
+// statistics come from the convolution's epilogue where its kernel accumulates them (*stats_fused), else from a pass over z.  pooled
+// != nullptr: also MaxPool2d(2) of y, in the apply pass for even H and W (*pool_fused), else by the pool kernel on y.
+int conv_bn_relu_train(mgu_ctx* c, Layer& L, const float* in, int ldin, int B, int H, int W, float* z, float* y, int ldy, double* sums,
+                       double* red, hipStream_t s, float* pooled = nullptr, bool* pool_fused = nullptr, bool* stats_fused = nullptr);
+// Where the backward of that half block writes the layer's parameter gradients
+struct LayerGrads {
+  float *dw = nullptr, *dbias = nullptr, *dgamma = nullptr, *dbeta = nullptr;
+};
+// ... and its backward on the tensors recorded in L.t_*: BatchNorm + ReLU backward (dy with pitch lddy -> dz dense; the column sums of
+// dz stay in the reduction slots), the weight gradient, whose unpack launch folds those sums into the bias gradient, and -- din !=
+// nullptr -- the data gradient (pitch ld_din)
+int conv_bn_relu_backward(mgu_ctx* c, const Layer& L, const float* dy, int lddy, float* dz, const LayerGrads& g, float* din, int ld_din,
+                          const BwdScratch& w, hipStream_t s);
 size_t train_ws_bytes(const mgu_ctx* c, int B, int H, int W);
 int unet_forward_train(mgu_ctx* c, const float* x, int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w, int B, int H,
                        int W, float* logits, void* const* cat_dev, void* const* feat_dev, hipStream_t s);

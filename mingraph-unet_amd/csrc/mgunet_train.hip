@@ -69,10 +69,36 @@ TPlan plan_train(const mgu_ctx* c, int B, int H, int W) {
   return p;
 }
 
+inline float* at(mgu_ctx* c, size_t off) { return (float*)((char*)c->tws + off); }
+
+struct Bwd : BwdScratch {
+  mgu_ctx* c;
+  hipStream_t s;
+  float *ta, *tb, *flat;
+};
+
+// where layer L's parameter gradients live in the flat gradient vector
+LayerGrads flat_grads(const Bwd& w, const Layer& L) {
+  LayerGrads g;
+  g.dw = w.flat + L.off_w, g.dbias = w.flat + L.off_b, g.dgamma = w.flat + L.off_gamma, g.dbeta = w.flat + L.off_beta;
+  return g;
+}
+
+// ConvBlock backward (unet_encoder.py:15-25 reversed).  dy has pitch lddy; dinput may be null.
+int block_backward(Bwd& w, const Block& b, const float* dy, int lddy, float* dinput, int ld_dinput) {
+  mgu_ctx* c = w.c;
+  const Layer &L1 = c->layers[b.conv1], &L2 = c->layers[b.conv2];
+  int rc;
+  if ((rc = conv_bn_relu_backward(c, L2, dy, lddy, w.ta, flat_grads(w, L2), w.tb, L2.Cin, w, w.s))) return rc;   // d(y1), dense pitch C
+  return conv_bn_relu_backward(c, L1, w.tb, L2.Cin, w.ta, flat_grads(w, L1), dinput, ld_dinput, w, w.s);
+}
+
+}  // namespace
+
 // The reduction slots are zero between launches: slot_reduce_kernel clears what it read, so only a fresh allocation
 // needs a memset (instead of one before each of the ~60 per-channel reductions of a step).
-int ensure_red(mgu_ctx* c) {
-  const size_t need = chan_reduce_work_bytes(std::max(c->feat << c->depth, 64));
+int mgud::ensure_red(mgu_ctx* c, int Cmax) {
+  const size_t need = chan_reduce_work_bytes(std::max(Cmax, 64));
   if (c->redws_bytes >= need) return MGU_OK;
   int rc = ensure(c, &c->redws, &c->redws_bytes, need);
   if (rc) return rc;
@@ -80,16 +106,15 @@ int ensure_red(mgu_ctx* c) {
   return MGU_OK;
 }
 
-inline float* at(mgu_ctx* c, size_t off) { return (float*)((char*)c->tws + off); }
-
 // conv (+bias) -> z ; batch statistics ; y = relu(bn(z)) written with pitch ldy
-int conv_bn_relu_train(mgu_ctx* c, Layer& L, const float* in, int ldin, int B, int H, int W, float* z, float* y, int ldy,
-                       double* sums, double* red, hipStream_t s, float* pooled = nullptr, bool* pool_done = nullptr) {
+int mgud::conv_bn_relu_train(mgu_ctx* c, Layer& L, const float* in, int ldin, int B, int H, int W, float* z, float* y, int ldy,
+                             double* sums, double* red, hipStream_t s, float* pooled, bool* pool_fused, bool* stats_fused) {
   const int64_t M = (int64_t)B * H * W;
   const int C = L.Cout;
   bool stats_done = false;   // Winograd layers accumulate sum z / sum z^2 in the conv epilogue
   int rc = run_layer(c, L, in, ldin, B, H, W, z, C, 0, 0, nullptr, L.b_src, 0, 0, s, nullptr, 0, nullptr, red, &stats_done);  // unet_encoder.py:16 / :20
   if (rc) return rc;
+  if (stats_fused) *stats_fused = stats_done;
   if (stats_done) {
     HIPCHK(c, launch_bn_finalize_slots(red, c->last_stat_rows, sums, M, 1e-5f, 0.1f, L.gamma, L.beta, L.mean, L.invstd, L.tscale, L.tshift, L.run_mean,
                                        L.run_var, C, s));  // nn.BatchNorm2d defaults, unet_encoder.py:12-13
@@ -98,54 +123,34 @@ int conv_bn_relu_train(mgu_ctx* c, Layer& L, const float* in, int ldin, int B, i
     HIPCHK(c, launch_bn_finalize(sums, sums + C, M, 1e-5f, 0.1f, L.gamma, L.beta, L.mean, L.invstd, L.tscale, L.tshift,
                                  L.run_mean, L.run_var, C, s));
   }
-  if (pool_done) *pool_done = false;
+  if (pool_fused) *pool_fused = false;
   if (pooled && !(H & 1) && !(W & 1)) {   // MaxPool2d(2) of y in the same pass (even sizes: windows tile the image)
     HIPCHK(c, launch_bn_apply_relu_pool(z, L.tscale, L.tshift, y, ldy, pooled, B, H, W, C, s));
-    if (pool_done) *pool_done = true;
+    if (pool_fused) *pool_fused = true;
   } else {
     HIPCHK(c, launch_bn_apply_relu(z, L.tscale, L.tshift, y, ldy, M, C, s));
+    if (pooled) HIPCHK(c, launch_maxpool2(y, ldy, pooled, 0, B, H, W, C, s));   // odd sizes: floor-mode windows leave a row / column out
   }
   L.t_in = in, L.t_ldin = ldin, L.t_z = z, L.t_y = y, L.t_ldy = ldy, L.t_B = B, L.t_H = H, L.t_W = W;
   return MGU_OK;
 }
 
-struct Bwd : BwdScratch {
-  mgu_ctx* c;
-  hipStream_t s;
-  float *ta, *tb, *flat;
-  int pend_rows = 0;   // rows of `red` holding the column sums of the last bn_relu_bwd (= the conv bias gradient), folded by the layer's
-                       // gradient unpack launch (conv_wgrad)
-};
-
-// BN(train) + ReLU backward: dy (pitch lddy) -> dz (dense) ; fills dgamma, dbeta, conv bias grad
-int bn_relu_bwd(Bwd& w, const Layer& L, const float* dy, int lddy, float* dz) {
-  mgu_ctx* c = w.c;
+// BN(train) + ReLU backward, weight gradient (+ the bias gradient's fold), data gradient of one conv -> BN -> ReLU
+int mgud::conv_bn_relu_backward(mgu_ctx* c, const Layer& L, const float* dy, int lddy, float* dz, const LayerGrads& g, float* din,
+                                int ld_din, const BwdScratch& w, hipStream_t s) {
   const int64_t M = (int64_t)L.t_B * L.t_H * L.t_W;
   const int C = L.Cout;
-  HIPCHK(c, launch_bn_bwd_reduce(dy, lddy, L.tscale, L.tshift, L.t_z, C, L.mean, L.invstd, M, C, w.red, w.sums,
-                                 w.flat + L.off_beta, w.flat + L.off_gamma, w.s));
+  HIPCHK(c, launch_bn_bwd_reduce(dy, lddy, L.tscale, L.tshift, L.t_z, C, L.mean, L.invstd, M, C, w.red, w.sums, g.dbeta, g.dgamma, s));
   // dz and, fused, the column sums of dz (the conv bias gradient, analytically ~0 under BatchNorm): they stay in the reduction slots
-  // until conv_wgrad of the SAME layer -- always the next user of the slots -- folds them inside its unpack launch
+  // until conv_wgrad -- the next user of the slots -- folds them inside its unpack launch
+  int pend_rows = 0;
   HIPCHK(c, launch_bn_bwd_apply_deferred(dy, lddy, L.tscale, L.tshift, L.t_z, L.mean, L.invstd, L.gamma, w.sums, M, C, dz, w.red,
-                                         &w.pend_rows, w.s));
-  return MGU_OK;
-}
-
-// ConvBlock backward (unet_encoder.py:15-25 reversed).  dy has pitch lddy; dinput may be null.
-int block_backward(Bwd& w, const Block& b, const float* dy, int lddy, float* dinput, int ld_dinput) {
-  mgu_ctx* c = w.c;
-  const Layer &L1 = c->layers[b.conv1], &L2 = c->layers[b.conv2];
+                                         &pend_rows, s));
   int rc;
-  if ((rc = bn_relu_bwd(w, L2, dy, lddy, w.ta))) return rc;
-  if ((rc = conv_wgrad(c, L2, w.ta, w.flat + L2.off_w, w, true, w.s, &w.pend_rows, w.flat + L2.off_b))) return rc;
-  if ((rc = conv_dgrad(c, L2, w.ta, w.tb, L2.Cin, w, true, w.s))) return rc;   // d(y1), dense pitch C
-  if ((rc = bn_relu_bwd(w, L1, w.tb, L2.Cin, w.ta))) return rc;
-  if ((rc = conv_wgrad(c, L1, w.ta, w.flat + L1.off_w, w, true, w.s, &w.pend_rows, w.flat + L1.off_b))) return rc;
-  if (dinput && (rc = conv_dgrad(c, L1, w.ta, dinput, ld_dinput, w, true, w.s))) return rc;
+  if ((rc = conv_wgrad(c, L, dz, g.dw, w, true, s, &pend_rows, g.dbias))) return rc;
+  if (din && (rc = conv_dgrad(c, L, dz, din, ld_din, w, true, s))) return rc;
   return MGU_OK;
 }
-
-}  // namespace
 
 // weight gradient of a conv layer: Z = dz (dense, pitch rup(Cout, 4)), A = gather of the layer's input
 int mgud::conv_wgrad(mgu_ctx* c, const Layer& L, const float* dz, float* dw, const BwdScratch& w, bool record, hipStream_t s,
@@ -163,7 +168,7 @@ int mgud::conv_wgrad(mgu_ctx* c, const Layer& L, const float* dz, float* dw, con
     HIPCHK(c, launch_unpack_conv_grad(w.dwp, d.groups, (size_t)d.N * d.Kp, dw, L.Cout, L.Cin, L.Cp, L.KS, L.Kp, s));
     return MGU_OK;
   }
-  // ... and, in the same launch, the fold of the bias gradient's column sums that bn_relu_bwd left in the reduction slots
+  // ... and, in the same launch, the fold of the bias gradient's column sums that conv_bn_relu_backward left in the reduction slots
   HIPCHK(c, launch_unpack_conv_grad(w.dwp, d.groups, (size_t)d.N * d.Kp, dw, L.Cout, L.Cin, L.Cp, L.KS, L.Kp, s, w.red, *fold_rows,
                                     L.Cout, dbias));
   *fold_rows = 0;
@@ -238,7 +243,7 @@ int mgud::unet_forward_train(mgu_ctx* c, const float* x, int64_t xs_n, int64_t x
   c->fold_dirty = true;    // this forward updates the BatchNorm running statistics in place: the eval fold is stale
   int rc = ensure(c, &c->tws, &c->tws_bytes, p.total);
   if (rc) return rc;
-  if ((rc = ensure_red(c))) return rc;
+  if ((rc = ensure_red(c, c->feat << c->depth))) return rc;
   std::vector<int> hs, ws;
   level_dims(H, W, c->depth, hs, ws);
   double* sums = (double*)((char*)c->tws + p.sums);
@@ -252,13 +257,12 @@ int mgud::unet_forward_train(mgu_ctx* c, const float* x, int64_t xs_n, int64_t x
   HIPCHK(c, launch_pack_input(x, xin, 0, B, c->in_ch, c->Cp0, H, W, xs_n, xs_c, xs_h, xs_w, s));
 
   // conv1 -> BN -> ReLU -> conv2 -> BN -> ReLU of block b on its level, output y with pitch ldy (and, fused where it can be, pooled)
-  auto block = [&](const Block& b, const float* in, int ldin, float* y, int ldy, float* pooled, bool* pooled_done) {
+  auto block = [&](const Block& b, const float* in, int ldin, float* y, int ldy, float* pooled) {
     Layer &L1 = c->layers[b.conv1], &L2 = c->layers[b.conv2];
     const int i = b.level, C = L1.Cout;
     int r = conv_bn_relu_train(c, L1, in, ldin, B, hs[i], ws[i], at(c, p.z[b.conv1]), at(c, p.y1[b.conv1]), C, sums, red, s);
     if (r) return r;
-    return conv_bn_relu_train(c, L2, at(c, p.y1[b.conv1]), C, B, hs[i], ws[i], at(c, p.z[b.conv2]), y, ldy, sums, red, s, pooled,
-                              pooled_done);
+    return conv_bn_relu_train(c, L2, at(c, p.y1[b.conv1]), C, B, hs[i], ws[i], at(c, p.z[b.conv2]), y, ldy, sums, red, s, pooled);
   };
   c->t_cat.assign(c->depth, nullptr);
   c->t_feat.assign(c->depth, nullptr);
@@ -269,16 +273,14 @@ int mgud::unet_forward_train(mgu_ctx* c, const float* x, int64_t xs_n, int64_t x
     const int i = b.level, C = c->layers[b.conv1].Cout;
     float* cat = (float*)cat_dev[i];
     float* pooled = at(c, p.pooled[i]);
-    bool pooled_done = false;
-    if ((rc = block(b, cur, ld, cat, 2 * C, pooled, &pooled_done))) return rc;
-    if (!pooled_done) HIPCHK(c, launch_maxpool2(cat, 2 * C, pooled, 0, B, hs[i], ws[i], C, s));
+    if ((rc = block(b, cur, ld, cat, 2 * C, pooled))) return rc;
     c->t_cat[i] = cat, c->t_pooled[i] = pooled;
     cur = pooled, ld = C;
   }
   {  // bottleneck
     float* bott = at(c, p.bott);
     const int C = c->layers[c->bott.conv1].Cout;
-    if ((rc = block(c->bott, cur, ld, bott, C, nullptr, nullptr))) return rc;
+    if ((rc = block(c->bott, cur, ld, bott, C, nullptr))) return rc;
     cur = bott, ld = C;
   }
   for (const Block& b : c->dec) {  // decoder
@@ -288,7 +290,7 @@ int mgud::unet_forward_train(mgu_ctx* c, const float* x, int64_t xs_n, int64_t x
     Layer& U = c->layers[b.up];
     if ((rc = run_layer(c, U, cur, ld, B, hs[i + 1], ws[i + 1], cat, 2 * C, C, 0, nullptr, U.shift, hs[i], ws[i], s))) return rc;
     U.t_in = cur, U.t_ldin = ld, U.t_B = B, U.t_H = hs[i + 1], U.t_W = ws[i + 1];
-    if ((rc = block(b, cat, 2 * C, feat, C, nullptr, nullptr))) return rc;
+    if ((rc = block(b, cat, 2 * C, feat, C, nullptr))) return rc;
     c->t_feat[i] = feat;
     cur = feat, ld = C;
   }

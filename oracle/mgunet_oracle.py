@@ -152,10 +152,13 @@ def make_unet_params(in_channels=3, num_classes=2, init_features=32, depth=4, se
 # --------------------------------------------------------------------------------------
 # U-Net forward (model/unet/*.py)
 # --------------------------------------------------------------------------------------
-def _conv_block(p, prefix, x, training, momentum, eps, new_stats):
+def _conv_block(p, prefix, x, training, momentum, eps, new_stats, z_ratio=None):
     """ConvBlock.forward, model/unet/unet_encoder.py:15-25 (conv1-bn1-relu-conv2-bn2-relu)."""
     for c, bn in (("conv1", "bn1"), ("conv2", "bn2")):
         x = F.conv2d(x, p[prefix + c + ".weight"], p[prefix + c + ".bias"], padding=1)  # :7-8
+        if z_ratio is not None:  # per channel |mean| / std of the BatchNorm's input
+            with torch.no_grad():
+                z_ratio[prefix + bn] = x.mean((0, 2, 3)).abs() / x.std((0, 2, 3), unbiased=False)
         rm, rv = p[prefix + bn + ".running_mean"], p[prefix + bn + ".running_var"]
         if training:
             rm, rv = rm.clone(), rv.clone()
@@ -168,19 +171,20 @@ def _conv_block(p, prefix, x, training, momentum, eps, new_stats):
     return x
 
 
-def unet_forward(p, x, depth=4, training=False, momentum=0.1, eps=1e-5, new_stats=None):
+def unet_forward(p, x, depth=4, training=False, momentum=0.1, eps=1e-5, new_stats=None, z_ratio=None):
     """UNet.forward, model/unet/unet_model.py:34-36.
 
     Returns (logits, skips shallow->deep, decoder feats shallow->deep) exactly as the
-    reference's 3-tuple.  `new_stats` (dict) receives updated BN running stats in training.
+    reference's 3-tuple.  `new_stats` (dict) receives updated BN running stats in training, `z_ratio` (dict) every BatchNorm
+    layer's per-channel |mean| / std of its input z (what the raw-moment variance of the HIP statistics is sensitive to).
     """
     skips = []
     cur = x
     for i in range(depth):  # unet_encoder.py:67-70
-        cur = _conv_block(p, f"encoder.encoder_blocks.{i}.", cur, training, momentum, eps, new_stats)
+        cur = _conv_block(p, f"encoder.encoder_blocks.{i}.", cur, training, momentum, eps, new_stats, z_ratio)
         skips.append(cur)
         cur = F.max_pool2d(cur, kernel_size=2, stride=2)  # :48
-    cur = _conv_block(p, "encoder.bottleneck.", cur, training, momentum, eps, new_stats)  # :72
+    cur = _conv_block(p, "encoder.bottleneck.", cur, training, momentum, eps, new_stats, z_ratio)  # :72
     feats = []
     for bi in range(depth):  # unet_decoder.py:139-141
         skip = skips[depth - 1 - bi]  # reversed_skips, :134
@@ -189,10 +193,19 @@ def unet_forward(p, x, depth=4, training=False, momentum=0.1, eps=1e-5, new_stat
         dy, dx = skip.shape[2] - up.shape[2], skip.shape[3] - up.shape[3]  # :41-42
         up = F.pad(up, [dx // 2, dx - dx // 2, dy // 2, dy - dy // 2])  # :46-47
         cur = torch.cat([skip, up], dim=1)  # :53 skip FIRST
-        cur = _conv_block(p, pre + "conv_block.", cur, training, momentum, eps, new_stats)  # :55
+        cur = _conv_block(p, pre + "conv_block.", cur, training, momentum, eps, new_stats, z_ratio)  # :55
         feats.append(cur)
     logits = F.conv2d(cur, p["decoder.final_conv.weight"], p["decoder.final_conv.bias"])  # :143
     return logits, skips, feats[::-1]  # :149
+
+
+def bn_input_ratio(p, x, depth=4) -> float:
+    """Largest |mean| / std over every BatchNorm layer's input channels in the float64 train-mode forward."""
+    q = {k: (v.double() if v.dtype.is_floating_point else v) for k, v in p.items()}
+    ratios = {}
+    with torch.no_grad():
+        unet_forward(q, x.double(), depth, training=True, new_stats={}, z_ratio=ratios)
+    return max(float(r.max()) for r in ratios.values())
 
 
 def _bf16(x: torch.Tensor) -> torch.Tensor:
