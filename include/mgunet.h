@@ -631,6 +631,45 @@ int mgu_patch_node_features_u8(mgu_ctx* ctx, const uint8_t* rgb_dev, int B, int 
  * and purity 0.  1 <= C <= 32 (beyond: MGU_ERR_INVALID), patch 1..4096.  One launch; integer counts: exact and deterministic. */
 int mgu_patch_labels(mgu_ctx* ctx, const void* src_dev, int src_kind, int B, int H, int W, int C, int patch, int32_t* counts_dev,
                      int64_t* labels_dev, float* purity_dev, void* hip_stream);
+/* ---- exact binary s-t min cut of the patch graph (csrc/graphcut.hip) ------------------------------------------
+ * The solver of the energy MinCutRefinement's constructor arguments parameterise (mincut_refinement.py:9-25; the reference has none):
+ *   E(S) = sum_i D_i(S_i) + smoothness * sum over undirected (i,j) of w_ij [S_i != S_j],  D_i(fg) = -log p_i,  D_i(bg) = -log(1 - p_i),
+ *   p clamped to [1e-6, 1 - 1e-6],  w_ij = exp(-(I_i - I_j)^2 / (2 sigma_intensity^2)) + gamma exp(-|f_i - f_j|^2 / (2 sigma_features^2)),
+ * quantised to integer capacities q(x) = min(lrintf(x * unit), 2^20).  B graphs share ONE topology: the COO list (2, E) int64 of one
+ * graph, holding both directions of every edge; node i of graph b is row b*N + i, edge k of graph b is entry b*E + k (COO order).
+ *
+ * Reverse-edge index over the CSR BY SOURCE of that list (mgu_coo_to_csr_device of the flipped list: rows = sources, col = targets,
+ * rows not sorted by column).  For COO edge k = (u -> v) at CSR position p: perm_dev[p] = k, rev_dev[p] = position of (v -> u).
+ * *status_dev (device int) gets bit 1: a reverse edge is missing; 2: a duplicate (u, v); 4: a self loop; 8: an id outside [0, N) or an
+ * edge the CSR does not hold.  The caller decides when to read it (once per new graph). */
+int mgu_graphcut_rev_index(mgu_ctx* ctx, const int64_t* coo_dev, int64_t E, int num_nodes, const int32_t* rowptr_dev, const int32_t* col_dev,
+                           int32_t* rev_dev, int32_t* perm_dev, int* status_dev, void* hip_stream);
+/* One launch: cap_source[b*N+i] = q(D_i(bg)), cap_sink[b*N+i] = q(D_i(fg)), cap_edge[b*E+k] = q(smoothness * w) (all int32).  The prior is
+ * EITHER prior_dev fp32 (B*N) probabilities OR counts_dev int32 (B*N, num_classes) class counts as mgu_patch_labels writes them with
+ * p = (n_fg + 1) / (n_all + 2) for class fg_class; the other pointer NULL.  intensity_dev fp32 (B*N) on the 0..255 scale and feat_dev
+ * fp32 (B*N, D) are optional: a term of w whose input is NULL is dropped (neither: every cap_edge is 0).  fp32 logf / expf, the
+ * squared feature distance in double; both directions of an edge form it from the lower to the higher node id, so cap_edge is
+ * bitwise symmetric.  An edge with an id outside [0, N) gets capacity 0. */
+int mgu_graphcut_capacities(mgu_ctx* ctx, int B, int N, const int64_t* coo_dev, int64_t E, const float* prior_dev, const int32_t* counts_dev,
+                            int num_classes, int fg_class, const float* intensity_dev, const float* feat_dev, int D, float gamma,
+                            float sigma_intensity, float sigma_features, float smoothness, float unit, int32_t* cap_source_dev,
+                            int32_t* cap_sink_dev, int32_t* cap_edge_dev, void* hip_stream);
+/* The cut: phase 1 of push-relabel in lock step, one workgroup per graph, the residual graph in LDS (20 N + 4 E + 40 bytes, checked
+ * against the device's shared memory per block: a larger graph is MGU_ERR_INVALID before anything is launched).  Capacities are int32
+ * in the layout above (negative values count as 0) and are not written.  labels_dev uint8 (B*N): 1 = foreground (source side) iff
+ * the sink cannot be reached from the node in the residual graph -- the same set for every maximum preflow, i.e. among cuts of equal
+ * cost the one with the LARGEST foreground; flow_dev int64 (B): the flow into the sink = E(labels) in capacity units; rounds_dev int32
+ * (B): push / relabel rounds taken (deterministic); converged_dev int32 (B): 0 when max_rounds ended the solve first (labels and flow
+ * are then no cut).  relabel_period: rounds between global relabels, threads: workgroup size (a multiple of 64 up to 1024); 0 = the
+ * measured defaults.  No host synchronisation. */
+int mgu_graphcut_solve(mgu_ctx* ctx, int B, int N, int64_t E, const int32_t* rowptr_dev, const int32_t* col_dev, const int32_t* rev_dev,
+                       const int32_t* perm_dev, const int32_t* cap_source_dev, const int32_t* cap_sink_dev, const int32_t* cap_edge_dev,
+                       int max_rounds, int relabel_period, int threads, uint8_t* labels_dev, int64_t* flow_dev, int32_t* rounds_dev,
+                       int32_t* converged_dev, void* hip_stream);
+/* energy_dev int64 (B): cap_sink over the nodes labelled non-zero (foreground) + cap_source over the others + cap_edge[k] over the COO
+ * edges from a foreground to a background node.  Integer sums: exact, order-free.  B <= 65535. */
+int mgu_graphcut_energy(mgu_ctx* ctx, int B, int N, const int64_t* coo_dev, int64_t E, const uint8_t* labels_dev, const int32_t* cap_source_dev,
+                        const int32_t* cap_sink_dev, const int32_t* cap_edge_dev, int64_t* energy_dev, void* hip_stream);
 /* postprocess_segmentation (scripts/infer_segmentation.py:20-51, :123): class labels int64 -> colour map uint8 (npix, 3) through a
  * palette (num_classes, 3) the caller provides (the reference's BGR list), labels outside [0, num_classes) stay black; and, if
  * labels_u8_dev != NULL, the uint8 label map written next to it. */

@@ -54,19 +54,30 @@ class MinGraphUNetE2E(nn.Module):
     deterministic node features: U-Net -> patch-mean node features -> patch GAT -> segment predictor +
     normalized-cut loss (mean over images, :425) -> region stage -> FeatureFusion with the shallowest decoder feature ->
     DetectionHead.  Returns a dict with the tensors the loop produces: logits, node embeddings, loss_partition, soft /
-    hard patch assignments, region embeddings, fused features, boxes, confidence (and class scores)."""
+    hard patch assignments, region embeddings, fused features, boxes, confidence (and class scores).
+    partition="predictor" (default): the hard patch labels are the arg-max of the segment predictor.  partition="mincut"
+    (num_segments == 2): they are the exact min cut of MinCutRefinement's energy (MinCutRefinement.refine_patches on the logits, the
+    uint8 batch passed as forward(x, images_u8=...) and the node embeddings); the region stage runs on them, soft_assignments /
+    loss_partition stay the predictor's, and the dict gains cut_labels (B*Np,) int64 and cut_energy (B,)."""
 
     def __init__(self, unet: UNet, patch_gat: GATNetwork, segment_predictor, mincut, region_gat: GATNetwork, detection_head,
-                 num_segments: int, patch_size: int = 16):
+                 num_segments: int, patch_size: int = 16, partition: str = "predictor", foreground: int = 1):
         super().__init__()
+        if partition not in ("predictor", "mincut"):
+            raise ValueError(f'partition must be "predictor" or "mincut", got {partition!r}')
+        if partition == "mincut" and num_segments != 2:
+            raise ValueError(f'partition="mincut" is a binary cut: num_segments must be 2, got {num_segments}')
+        self.partition, self.foreground = partition, foreground
         self.core = MinGraphUNet(unet, patch_gat, patch_size)
         self.segment_predictor, self.mincut, self.region_gat, self.detection_head = segment_predictor, mincut, region_gat, detection_head
         self.num_segments = num_segments
 
     @torch.no_grad()   # a pipeline of forward values (the pooling / cut / fuse kernels between the modules carry no autograd graph)
-    def forward(self, x):
+    def forward(self, x, images_u8=None):
         from .region import region_stage
         B, _, H, W = x.shape
+        if self.partition == "mincut" and images_u8 is None:
+            raise ValueError('partition="mincut" needs the uint8 batch: forward(x, images_u8=...)')
         logits, skips, feats, emb = self.core(x)
         graph = self.core.graph
         nph, npw = graph.grid(H, W)
@@ -79,6 +90,10 @@ class MinGraphUNetE2E(nn.Module):
         else:
             seg_logits = self.segment_predictor(emb)
         losses, soft, hard = self.mincut.forward_batched(emb, ei_one, B, K, seg_logits.contiguous())
+        cut = None
+        if self.partition == "mincut":
+            cut = self.mincut.refine_patches(logits, images_u8, emb, graph.patch_size, self.foreground)
+            hard = cut[0]
         region_emb, fused = region_stage(emb, hard, B, K, self.region_gat, nph, npw, H, W, f_u=feats[0])
         det = self.detection_head(fused)
         out = {"logits": logits, "skips": skips, "decoder_feats": feats, "node_embeddings": emb, "loss_partition": losses.mean(),
@@ -86,6 +101,8 @@ class MinGraphUNetE2E(nn.Module):
                "bboxes": det[0], "confidence": det[1]}
         if len(det) > 2:
             out["class_scores"] = det[2]
+        if cut is not None:
+            out["cut_labels"], out["cut_energy"] = cut[0], cut[1]
         return out
 
 

@@ -143,7 +143,8 @@ class PatchSegmentPredictor(nn.Module):
 
 class MinCutRefinement(nn.Module):
     """mincut_refinement.py:5-205.  The constructor arguments parameterise the energy E(S) of a solver the reference
-    never implements (:9-16); like there, they are stored and unused."""
+    never implements (:9-16).  Here `solve` / `refine_patches` minimise that energy exactly with them (mgunet.graphcut: this build's
+    definition of E(S), taken from the reference's parameter documentation); the normalized-cut loss below does not use them."""
 
     def __init__(self, gamma_unet_priors=0.5, sigma_intensity=10.0, sigma_features=1.0):
         super().__init__()
@@ -166,6 +167,44 @@ class MinCutRefinement(nn.Module):
             rowptr, col = coo_to_csr_device(edge_index.to(dev), N)   # rows = targets, col = sources (the backward's second gather)
             ent = self.__dict__["_csr_t"] = (key, rowptr, col, edge_index)
         return ent[1], ent[2]
+
+    def solve(self, prior, edge_index, intensity=None, features=None, batch=1, smoothness=1.0, counts_foreground=None):
+        """Exact min cut of E(S) (mgunet.graphcut) for `batch` graphs over edge_index, with gamma_unet_priors, sigma_intensity and
+        sigma_features as the energy's gamma and sigmas.  prior: float32 (B*N) foreground probabilities (or int32 class counts with
+        counts_foreground=, as cut_capacities takes them); intensity (B*N) on the 0..255 scale and features (B*N, D) are optional.
+        -> (hard labels (B*N,) int64, 1 = foreground; E(S) (B,) float64 = flow / unit; the GraphCut).  Nothing is read back:
+        GraphCut.check() reports a graph that did not converge."""
+        from .graphcut import cut_capacities, graph_cut
+        unit = 1024
+        cs, ct, ce = cut_capacities(prior, edge_index, intensity, features, counts_foreground=counts_foreground, gamma=self.gamma_unet_priors,
+                                    sigma_intensity=self.sigma_intensity, sigma_features=self.sigma_features, smoothness=smoothness,
+                                    unit=unit, batch=batch)
+        cut = graph_cut(edge_index, cs, ct, ce, batch=batch)
+        return cut.labels.reshape(-1).to(torch.int64), cut.flow.to(torch.float64) / unit, cut
+
+    def refine_patches(self, logits, images_u8, node_features, patch_size, foreground=1):
+        """The patch partition of a batch by the cut, with no trained predictor: the prior is the U-Net's own vote per patch
+        (patch_labels(logits, return_counts=True): p = (n_fg + 1) / (n_all + 2) for class `foreground`), the intensity the patch means
+        of the uint8 images (patch_features_u8), the features the given node features (B*Np, D) -- the GAT embeddings are the
+        intended ones -- and the topology PatchGraphConstructor's.  logits (B, C, H, W) float, images_u8 (B, H, W, 3) uint8.
+        -> what `solve` returns."""
+        from .patch_graph import PatchGraphConstructor
+        from .patch_inputs import patch_labels
+        from .preprocess import _to_dev_u8, patch_features_u8
+        _lib.require_hip(logits, "mgunet MinCut")
+        B, _, H, W = logits.shape
+        u8, _ = _to_dev_u8(images_u8)
+        if u8.dim() == 3:
+            u8 = u8.unsqueeze(0)
+        if tuple(u8.shape[:3]) != (B, H, W):
+            raise ValueError(f"images_u8 must be ({B}, {H}, {W}, 3) like the logits, got {tuple(u8.shape)}")
+        p = int(patch_size)
+        graphs = self.__dict__.setdefault("_patch_graphs", {})
+        graph = graphs.get(p) or graphs.setdefault(p, PatchGraphConstructor(p))
+        _, counts = patch_labels(logits, p, return_counts=True)
+        intensity = torch.cat([patch_features_u8(img, p) for img in u8]).reshape(-1)
+        feats = node_features.detach().to(torch.float32).reshape(intensity.numel(), -1)
+        return self.solve(counts, graph.edge_index(H, W, logits.device), intensity, feats, batch=B, counts_foreground=int(foreground))
 
     def compute_edge_weights_for_ncut(self, node_features, edge_index):
         """(E,) weights exp(-|f_i - f_j|^2 / 2) in edge order (:30-52)."""
