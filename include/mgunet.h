@@ -641,7 +641,8 @@ int mgu_patch_labels(mgu_ctx* ctx, const void* src_dev, int src_kind, int B, int
  * Reverse-edge index over the CSR BY SOURCE of that list (mgu_coo_to_csr_device of the flipped list: rows = sources, col = targets,
  * rows not sorted by column).  For COO edge k = (u -> v) at CSR position p: perm_dev[p] = k, rev_dev[p] = position of (v -> u).
  * *status_dev (device int) gets bit 1: a reverse edge is missing; 2: a duplicate (u, v); 4: a self loop; 8: an id outside [0, N) or an
- * edge the CSR does not hold.  The caller decides when to read it (once per new graph). */
+ * edge the CSR does not hold; 16 (no error of the list): a node of degree >= 4095, which only mgu_graphcut_expand cannot take.  The caller
+ * decides when to read it (once per new graph). */
 int mgu_graphcut_rev_index(mgu_ctx* ctx, const int64_t* coo_dev, int64_t E, int num_nodes, const int32_t* rowptr_dev, const int32_t* col_dev,
                            int32_t* rev_dev, int32_t* perm_dev, int* status_dev, void* hip_stream);
 /* One launch: cap_source[b*N+i] = q(D_i(bg)), cap_sink[b*N+i] = q(D_i(fg)), cap_edge[b*E+k] = q(smoothness * w) (all int32).  The prior is
@@ -670,6 +671,35 @@ int mgu_graphcut_solve(mgu_ctx* ctx, int B, int N, int64_t E, const int32_t* row
  * edges from a foreground to a background node.  Integer sums: exact, order-free.  B <= 65535. */
 int mgu_graphcut_energy(mgu_ctx* ctx, int B, int N, const int64_t* coo_dev, int64_t E, const uint8_t* labels_dev, const int32_t* cap_source_dev,
                         const int32_t* cap_sink_dev, const int32_t* cap_edge_dev, int64_t* energy_dev, void* hip_stream);
+/* ---- K labels over the same graph: alpha-expansion (csrc/graphcut.hip) -------------------------------------------
+ *   E(L) = sum_i U_i(L_i) + sum over pairs {i,j} of w_ij [L_i != L_j],  L_i in {0 .. K-1},  U_i(k) = q(-log p_i(k)), p clamped to [1e-6, 1],
+ * w_ij = cap_edge of the arc from the LOWER to the HIGHER node id as mgu_graphcut_capacities writes it (the other direction is not read;
+ * that kernel writes both bitwise equal).  Costs and weights count as clamped to [0, 2^20].  For K = 2, cap_source = U(., 0) and
+ * cap_sink = U(., 1) this is E(S) above.
+ *
+ * One launch: costs_dev int32 (rows, K) from EITHER prob_dev fp32 (rows, K) probabilities OR counts_dev int32 (rows, K) class counts as
+ * mgu_patch_labels writes them, p = (n_k + 1) / (n_all + K); the other pointer NULL.  Evaluated in double: the count path is exact. */
+int mgu_graphcut_label_costs(mgu_ctx* ctx, int64_t rows, int K, const float* prob_dev, const int32_t* counts_dev, float unit, int32_t* costs_dev,
+                             void* hip_stream);
+/* The whole expansion in one launch, one workgroup per graph, topology arrays as for mgu_graphcut_solve.  Start: init_dev uint8 (B*N), a
+ * value >= K replaced by the node's cheapest label; NULL: every node's cheapest label (the lowest on ties).  A move on alpha builds the
+ * binary cut "x_i = 1: node i takes alpha" of the current labelling in LDS (pair i < j, a = L_i, b = L_j, A = w[a != b], B = w[a != alpha],
+ * C = w[alpha != b]: sink(i) += max(C - A, 0), source(i) += max(A - C, 0), source(j) += C, arc j -> i = B + C - A; U_i(alpha) on the sink
+ * arc, U_i(L_i) on the source arc), solves it by the rounds of mgu_graphcut_solve from zero heights and takes the largest set of nodes
+ * that may switch at minimal cost.  The move is accepted iff it lowers E strictly (integer sums: exact).  alpha runs 0 .. K-1
+ * cyclically; K rejected moves in a row end the loop with converged 1.  max_cycles * K moves, or a move whose solve reaches max_rounds,
+ * end it with converged 0 and the last accepted labelling.  Outputs per graph: labels_dev uint8 (B*N), energy_dev int64 = E(labels),
+ * moves_dev / accepted_dev / rounds_dev (summed over the moves) / converged_dev int32.  costs_dev and cap_edge_dev are not written.
+ * LDS: 20 N + 4 E + 48 + (N rounded up to 8) bytes against the device's shared memory per block, MGU_ERR_INVALID beyond it before
+ * anything is launched.  A move's residual sink word is 32 bits and can reach (1 + degree) 2^20: the topology must not carry status
+ * bit 16 of mgu_graphcut_rev_index (the caller checks; such a word saturates at 2^32 - 1).  1 <= K <= 255, 0 <= max_cycles <= 2^20. */
+int mgu_graphcut_expand(mgu_ctx* ctx, int B, int N, int64_t E, int K, const int32_t* rowptr_dev, const int32_t* col_dev, const int32_t* rev_dev,
+                        const int32_t* perm_dev, const int32_t* costs_dev, const int32_t* cap_edge_dev, const uint8_t* init_dev, int max_cycles,
+                        int max_rounds, int relabel_period, int threads, uint8_t* labels_dev, int64_t* energy_dev, int32_t* moves_dev,
+                        int32_t* accepted_dev, int32_t* rounds_dev, int32_t* converged_dev, void* hip_stream);
+/* energy_dev int64 (B): E(L) above of any labelling labels_dev uint8 (B*N); a label >= K counts as K - 1.  Integer sums: exact.  B <= 65535. */
+int mgu_graphcut_energy_multi(mgu_ctx* ctx, int B, int N, const int64_t* coo_dev, int64_t E, int K, const uint8_t* labels_dev, const int32_t* costs_dev,
+                              const int32_t* cap_edge_dev, int64_t* energy_dev, void* hip_stream);
 /* postprocess_segmentation (scripts/infer_segmentation.py:20-51, :123): class labels int64 -> colour map uint8 (npix, 3) through a
  * palette (num_classes, 3) the caller provides (the reference's BGR list), labels outside [0, num_classes) stay black; and, if
  * labels_u8_dev != NULL, the uint8 label map written next to it. */

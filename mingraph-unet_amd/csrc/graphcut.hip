@@ -12,6 +12,8 @@
 //                             bitwise symmetric: the squared distances are formed from the lower to the higher node id)
 //   mgu_graphcut_solve        phase 1 of push-relabel in lock step, ONE workgroup per graph, the whole residual graph in LDS
 //   mgu_graphcut_energy       E of any labelling in capacity units (integer sums: exact)
+//   mgu_graphcut_label_costs / mgu_graphcut_expand / mgu_graphcut_energy_multi   the same energy over K labels, minimised by
+//                             alpha-expansion: every move is one binary cut by the rounds of mgu_graphcut_solve, the whole loop one launch
 // The solver.  LDS per graph: 64-bit excess (N + 1 words, the last one the flow into the sink), residual arc capacities (E, CSR
 // order), height, residual sink capacity and one scratch word per node -- 130 KB + 16 KB for the 64 x 64 patch grid (N = 4096,
 // E = 16128) of a 1024^2 image, inside gfx950's 160 KiB.  rowptr / col / rev are read-only and stay in global memory (L2).  A round is
@@ -37,6 +39,7 @@ namespace {
 
 constexpr int GC_THREADS = 256;
 constexpr int GC_CAP_MAX = 1 << 20;
+constexpr int GC_WIDE_DEGREE = 4095;   // from this degree on (1 + degree) 2^20 no longer fits the 32-bit residual sink word of a move
 // Defaults of the solver, from the measured table in DESIGN.md section 3 (tools/graphcut_bench.py): at N = 1024 and N = 4096 the largest
 // workgroup and a period of 32 rounds (against 2 .. 16 and 64) were fastest.  Smaller graphs get one thread per node, and a period of about sqrt(N)
 // rounds -- the sweeps of one global relabel on a grid -- so that a 5 x 7 graph does not wait 32 rounds for its second relabel.
@@ -62,6 +65,7 @@ __global__ __launch_bounds__(GC_THREADS) void graphcut_rev_kernel(const int64_t*
     return;
   }
   if (u == v) atomicOr(status, 4);
+  if (rowptr[u + 1] - rowptr[u] >= GC_WIDE_DEGREE) atomicOr(status, 16);   // not an error: only the multi-label solver refuses it
   int p = -1, q = -1, np = 0;
   for (int i = rowptr[u]; i < rowptr[u + 1]; ++i)
     if (col[i] == (int)v) {
@@ -201,6 +205,92 @@ __device__ void gc_bfs(const GcGraph& g, int& seq) {
   }
 }
 
+// Push-relabel rounds on the residual graph in LDS until no node is active (-> 1) or max_rounds rounds are done (-> 0).  On entry
+// excess / sres / cap hold the capacities and h is 0; `rounds` and `to_sink` (this thread's share of the flow into the sink) are added to.
+__device__ int gc_rounds(const GcGraph& g, unsigned long long* excess, int* h, const int32_t* __restrict__ rev, int period, int max_rounds,
+                         int& seq, int& aseq, int& rounds, unsigned long long& to_sink) {
+  const int N = g.N, E = g.E, T = g.T, t = g.t, far = N + 1;
+  unsigned* cap = g.cap;
+  unsigned* sres = g.sres;
+  int* dist = g.dist;
+  int* flag = g.flag;
+  int converged = 0;
+  for (int r = 0;; ++r) {
+    if (r % period == 0) {                           // global relabel; heights only ever rise
+      gc_bfs(g, seq);
+      for (int i = t; i < N; i += T) h[i] = max(h[i], dist[i]);
+      __syncthreads();
+    }
+    // snapshot
+    const int cur = 3 + aseq % 3;
+    if (t == 0) flag[3 + (aseq + 1) % 3] = 0;
+    ++aseq;
+    bool any = false;
+    for (int i = t; i < N; i += T) {
+      const long long e = (long long)excess[i];
+      const bool act = e > 0 && h[i] < far;
+      dist[i] = act ? (int)min(e, (long long)INT_MAX) : 0;
+      any |= act;
+    }
+    if (any) flag[cur] = 1;
+    __syncthreads();
+    if (!flag[cur]) {
+      converged = 1;
+      break;
+    }
+    if (r >= max_rounds) break;
+    ++rounds;
+    // push
+    for (int i = t; i < N; i += T) {
+      const unsigned snap = (unsigned)dist[i];
+      if (!snap) continue;
+      unsigned rem = snap;
+      const int hi_ = h[i];
+      if (hi_ == 1 && sres[i]) {
+        const unsigned d = min(rem, sres[i]);
+        sres[i] -= d;
+        rem -= d;
+        to_sink += d;
+      }
+      int lo, hi;
+      gc_row(g, i, lo, hi);
+      for (int p = lo; p < hi && rem; ++p) {
+        const int v = g.col[p];
+        if ((unsigned)v >= (unsigned)N || h[v] + 1 != hi_) continue;
+        const unsigned c = cap[p];
+        const int rp = rev[p];
+        if (!c || (unsigned)rp >= (unsigned)E) continue;
+        const unsigned d = min(rem, c);
+        cap[p] = c - d;
+        cap[rp] += d;
+        atomicAdd(&excess[v], (unsigned long long)d);
+        rem -= d;
+      }
+      if (rem != snap) atomicAdd(&excess[i], 0ull - (unsigned long long)(snap - rem));
+    }
+    __syncthreads();
+    // relabel from the frozen heights ...
+    for (int i = t; i < N; i += T) {
+      int nh = h[i];
+      if ((long long)excess[i] > 0 && nh < far) {
+        int m = sres[i] ? 1 : far, lo, hi;
+        gc_row(g, i, lo, hi);
+        for (int p = lo; p < hi; ++p) {
+          const int v = g.col[p];
+          if (cap[p] && (unsigned)v < (unsigned)N) m = min(m, h[v] + 1);
+        }
+        nh = max(nh, min(m, far));
+      }
+      dist[i] = nh;
+    }
+    __syncthreads();
+    // ... then commit
+    for (int i = t; i < N; i += T) h[i] = dist[i];
+    __syncthreads();
+  }
+  return converged;
+}
+
 __global__ __launch_bounds__(GC_MAX_THREADS) void graphcut_solve_kernel(const SolveArgs a) {
   extern __shared__ unsigned long long gc_lds[];
   const int N = a.N, E = a.E, T = blockDim.x, t = threadIdx.x, b = blockIdx.x, far = N + 1;
@@ -227,81 +317,9 @@ __global__ __launch_bounds__(GC_MAX_THREADS) void graphcut_solve_kernel(const So
   if (t == 0) excess[N] = 0;
   __syncthreads();
 
-  int seq = 0, aseq = 0, rounds = 0, converged = 0;
+  int seq = 0, aseq = 0, rounds = 0;
   unsigned long long to_sink = 0;
-  for (int r = 0;; ++r) {
-    if (r % a.period == 0) {                           // global relabel; heights only ever rise
-      gc_bfs(g, seq);
-      for (int i = t; i < N; i += T) h[i] = max(h[i], dist[i]);
-      __syncthreads();
-    }
-    // snapshot
-    const int cur = 3 + aseq % 3;
-    if (t == 0) flag[3 + (aseq + 1) % 3] = 0;
-    ++aseq;
-    bool any = false;
-    for (int i = t; i < N; i += T) {
-      const long long e = (long long)excess[i];
-      const bool act = e > 0 && h[i] < far;
-      dist[i] = act ? (int)min(e, (long long)INT_MAX) : 0;
-      any |= act;
-    }
-    if (any) flag[cur] = 1;
-    __syncthreads();
-    if (!flag[cur]) {
-      converged = 1;
-      break;
-    }
-    if (r >= a.max_rounds) break;
-    ++rounds;
-    // push
-    for (int i = t; i < N; i += T) {
-      const unsigned snap = (unsigned)dist[i];
-      if (!snap) continue;
-      unsigned rem = snap;
-      const int hi_ = h[i];
-      if (hi_ == 1 && sres[i]) {
-        const unsigned d = min(rem, sres[i]);
-        sres[i] -= d;
-        rem -= d;
-        to_sink += d;
-      }
-      int lo, hi;
-      gc_row(g, i, lo, hi);
-      for (int p = lo; p < hi && rem; ++p) {
-        const int v = a.col[p];
-        if ((unsigned)v >= (unsigned)N || h[v] + 1 != hi_) continue;
-        const unsigned c = cap[p];
-        const int rp = rev[p];
-        if (!c || (unsigned)rp >= (unsigned)E) continue;
-        const unsigned d = min(rem, c);
-        cap[p] = c - d;
-        cap[rp] += d;
-        atomicAdd(&excess[v], (unsigned long long)d);
-        rem -= d;
-      }
-      if (rem != snap) atomicAdd(&excess[i], 0ull - (unsigned long long)(snap - rem));
-    }
-    __syncthreads();
-    // relabel from the frozen heights ...
-    for (int i = t; i < N; i += T) {
-      int nh = h[i];
-      if ((long long)excess[i] > 0 && nh < far) {
-        int m = sres[i] ? 1 : far, lo, hi;
-        gc_row(g, i, lo, hi);
-        for (int p = lo; p < hi; ++p) {
-          const int v = a.col[p];
-          if (cap[p] && (unsigned)v < (unsigned)N) m = min(m, h[v] + 1);
-        }
-        nh = max(nh, min(m, far));
-      }
-      dist[i] = nh;
-    }
-    __syncthreads();
-    // ... then commit
-    for (int i = t; i < N; i += T) h[i] = dist[i];
-    __syncthreads();
-  }
+  const int converged = gc_rounds(g, excess, h, rev, a.period, a.max_rounds, seq, aseq, rounds, to_sink);
   gc_bfs(g, seq);                                      // the sink side of the cut: whoever still reaches the sink
   for (int i = t; i < N; i += T) a.labels[(size_t)b * N + i] = dist[i] >= far ? 1 : 0;
   if (to_sink) atomicAdd(&excess[N], to_sink);
@@ -311,6 +329,189 @@ __global__ __launch_bounds__(GC_MAX_THREADS) void graphcut_solve_kernel(const So
     a.rounds[b] = rounds;
     a.converged[b] = converged;
   }
+}
+
+// ---- K labels: alpha-expansion over the rounds above ------------------------------------------------------------------------------
+//   E(L) = sum_i U_i(L_i) + sum over pairs {i,j} of w_ij [L_i != L_j],  U (B*N, K) int32,  w_ij = cap_edge of the arc from the LOWER to
+//   the HIGHER node id (the other direction is not read); both count as clamped to [0, 2^20].
+// A move on alpha is the binary cut "x_i = 1: node i takes alpha" of the current labelling, built in LDS by each node's own thread
+// (for the pair i < j with a = L_i, b = L_j: A = w[a != b], B = w[a != alpha], C = w[alpha != b]; sink(i) += max(C - A, 0),
+// source(i) += max(A - C, 0), source(j) += C, arc j -> i = B + C - A >= 0, arc i -> j = 0; plus U_i(alpha) on the sink and U_i(L_i) on
+// the source arc), solved by gc_rounds from h = 0 and read off by gc_bfs.  It is accepted iff it lowers E strictly, alpha runs
+// 0 .. K-1 cyclically, K rejected moves in a row end the loop.  LDS: the solver's arrays, one label byte per node and one 64-bit sum.
+inline size_t gcm_lds_bytes(int64_t N, int64_t E) { return (size_t)(N + 2) * 8 + (size_t)E * 4 + (size_t)N * 12 + 32 + (size_t)(N + 7) / 8 * 8; }
+
+__device__ __forceinline__ int gcm_clamp(int x) { return min(max(x, 0), GC_CAP_MAX); }
+
+struct ExpandArgs {
+  int N, E, K, max_moves, max_rounds, period;
+  const int32_t *rowptr, *col, *rev, *perm;
+  const int32_t *costs, *cap_edge;
+  const uint8_t* init;     // (B, N) or NULL
+  uint8_t* labels;
+  long long* energy;
+  int32_t *moves, *accepted, *rounds, *converged;
+};
+
+// the weight of the pair that CSR position p of row i stands for
+__device__ __forceinline__ int gcm_pair_weight(const ExpandArgs& a, const int32_t* __restrict__ ce, int i, int v, int p) {
+  const int q = i < v ? p : a.rev[p];
+  const int k = (unsigned)q < (unsigned)a.E ? a.perm[q] : -1;
+  return (unsigned)k < (unsigned)a.E ? gcm_clamp(ce[k]) : 0;
+}
+
+// E of the labelling "alpha where dist >= far, else lab" (alpha < 0: of lab itself): every node's thread sums its unary and the pairs
+// towards its higher neighbours; integer sums, so the order of the atomic adds does not show.  Every thread returns the total.
+__device__ long long gcm_energy(const ExpandArgs& a, const GcGraph& g, const int32_t* __restrict__ U, const int32_t* __restrict__ ce,
+                                const uint8_t* lab, unsigned long long* acc, int alpha) {
+  const int far = g.N + 1;
+  if (g.t == 0) *acc = 0;
+  __syncthreads();
+  long long s = 0;
+  for (int i = g.t; i < g.N; i += g.T) {
+    const int li = alpha >= 0 && g.dist[i] >= far ? alpha : lab[i];
+    s += gcm_clamp(U[(size_t)i * a.K + li]);
+    int lo, hi;
+    gc_row(g, i, lo, hi);
+    for (int p = lo; p < hi; ++p) {
+      const int v = g.col[p];
+      if (v <= i || v >= g.N) continue;
+      const int lv = alpha >= 0 && g.dist[v] >= far ? alpha : lab[v];
+      if (li != lv) s += gcm_pair_weight(a, ce, i, v, p);
+    }
+  }
+  s = wave_sum(s);
+  if ((g.t & 63) == 0 && s) atomicAdd(acc, (unsigned long long)s);
+  __syncthreads();
+  const long long total = (long long)*acc;
+  __syncthreads();
+  return total;
+}
+
+__global__ __launch_bounds__(GC_MAX_THREADS) void graphcut_expand_kernel(const ExpandArgs a) {
+  extern __shared__ unsigned long long gc_lds[];
+  const int N = a.N, E = a.E, K = a.K, T = blockDim.x, t = threadIdx.x, b = blockIdx.x, far = N + 1;
+  unsigned long long* excess = gc_lds;                 // [N] excess, [N] unused here, [N + 1] the energy sum
+  unsigned long long* acc = excess + N + 1;
+  unsigned* cap = (unsigned*)(excess + N + 2);
+  int* h = (int*)(cap + E);
+  unsigned* sres = (unsigned*)(h + N);
+  int* dist = (int*)(sres + N);
+  int* flag = dist + N;
+  uint8_t* lab = (uint8_t*)(flag + 8);
+  const GcGraph g = {N, E, T, t, a.rowptr, a.col, cap, sres, dist, flag};
+  const int32_t* U = a.costs + (size_t)b * N * K;
+  const int32_t* ce = a.cap_edge + (size_t)b * E;      // never dereferenced when E == 0
+
+  // start: the caller's labels, or the cheapest label of the node (the lowest on ties) where none or none below K is given
+  for (int i = t; i < N; i += T) {
+    int l = a.init ? a.init[(size_t)b * N + i] : K;
+    if (l >= K) {
+      l = 0;
+      int best = gcm_clamp(U[(size_t)i * K]);
+      for (int k = 1; k < K; ++k) {
+        const int u = gcm_clamp(U[(size_t)i * K + k]);
+        if (u < best) best = u, l = k;
+      }
+    }
+    lab[i] = (uint8_t)l;
+  }
+  if (t < 8) flag[t] = 0;
+  if (t == 0) excess[N] = 0;
+  __syncthreads();
+  long long energy = gcm_energy(a, g, U, ce, lab, acc, -1);
+
+  int seq = 0, aseq = 0, rounds = 0, moves = 0, accepted = 0, idle = 0, converged = 0;
+  unsigned long long to_sink = 0;
+  for (int move = 0; move < a.max_moves; ++move) {
+    const int alpha = move % K;
+    // the move's residual graph; each thread writes only its own nodes' words and arcs
+    for (int i = t; i < N; i += T) {
+      const int li = lab[i];
+      unsigned long long so = (unsigned long long)gcm_clamp(U[(size_t)i * K + li]), si = (unsigned long long)gcm_clamp(U[(size_t)i * K + alpha]);
+      int lo, hi;
+      gc_row(g, i, lo, hi);
+      for (int p = lo; p < hi; ++p) {
+        const int v = g.col[p];
+        unsigned c = 0;
+        if ((unsigned)v < (unsigned)N && v != i) {
+          const int w = gcm_pair_weight(a, ce, i, v, p), lv = lab[v];
+          if (i < v) {                                 // this node is the pair's lower end
+            const int A = li != lv ? w : 0, C = alpha != lv ? w : 0;
+            if (C > A) si += (unsigned)(C - A);
+            else so += (unsigned)(A - C);
+          } else {                                     // the higher end: a = lv, b = li
+            const int A = lv != li ? w : 0, B = lv != alpha ? w : 0, C = alpha != li ? w : 0;
+            so += (unsigned)C;
+            c = (unsigned)(B + C - A);
+          }
+        }
+        cap[p] = c;
+      }
+      excess[i] = so;
+      sres[i] = (unsigned)min(si, (unsigned long long)UINT_MAX);   // not reached below degree GC_WIDE_DEGREE, which the caller refuses
+      h[i] = 0;
+    }
+    __syncthreads();
+    ++moves;
+    const int done = gc_rounds(g, excess, h, a.rev, a.period, a.max_rounds, seq, aseq, rounds, to_sink);
+    if (!done) break;                                  // the round cap: the labels stay the last accepted ones
+    gc_bfs(g, seq);                                    // dist >= far: the node takes alpha
+    const long long cand = gcm_energy(a, g, U, ce, lab, acc, alpha);
+    if (cand < energy) {
+      for (int i = t; i < N; i += T)
+        if (dist[i] >= far) lab[i] = (uint8_t)alpha;
+      energy = cand;
+      ++accepted;
+      idle = 0;
+      __syncthreads();
+    } else if (++idle >= K) {
+      converged = 1;
+      break;
+    }
+  }
+  for (int i = t; i < N; i += T) a.labels[(size_t)b * N + i] = lab[i];
+  if (t == 0) {
+    a.energy[b] = energy;
+    a.moves[b] = moves;
+    a.accepted[b] = accepted;
+    a.rounds[b] = rounds;
+    a.converged[b] = converged;
+  }
+}
+
+// ---- label costs and the energy of a K-label labelling -----------------------------------------------------------------------------
+// U[r][k] = q(-log p), p = prob[r][k] or (n_k + 1) / (n_all + K) from counts, clamped to [1e-6, 1]; in double, so the count path is exact
+__global__ __launch_bounds__(GC_THREADS) void graphcut_label_costs_kernel(int64_t rows, int K, const float* __restrict__ prob,
+                                                                          const int32_t* __restrict__ counts, float unit, int32_t* __restrict__ out) {
+  const int64_t r = blockIdx.x * (int64_t)GC_THREADS + threadIdx.x;
+  if (r >= rows) return;
+  long long all = 0;
+  if (counts)
+    for (int k = 0; k < K; ++k) all += max(counts[r * K + k], 0);
+  for (int k = 0; k < K; ++k) {
+    double p = counts ? (double)((long long)max(counts[r * K + k], 0) + 1) / (double)(all + K) : (double)prob[r * K + k];
+    p = fmin(fmax(p, 1e-6), 1.0);                      // NaN counts as 1e-6
+    out[r * K + k] = (int)fmin(rint(fmax(-log(p) * (double)unit, 0.0)), (double)GC_CAP_MAX);
+  }
+}
+
+__global__ __launch_bounds__(GC_THREADS) void graphcut_energy_multi_kernel(int N, int64_t E, int K, const int64_t* __restrict__ coo,
+                                                                           const uint8_t* __restrict__ labels, const int32_t* __restrict__ U,
+                                                                           const int32_t* __restrict__ ce, unsigned long long* __restrict__ out) {
+  const int b = blockIdx.y;
+  const uint8_t* lab = labels + (size_t)b * N;
+  long long s = 0;
+  for (int64_t i = blockIdx.x * (int64_t)GC_THREADS + threadIdx.x; i < N + E; i += (int64_t)gridDim.x * GC_THREADS) {
+    if (i < N) {
+      s += gcm_clamp(U[((size_t)b * N + i) * K + min((int)lab[i], K - 1)]);
+    } else {
+      const int64_t k = i - N, u = coo[k], v = coo[E + k];
+      if (u >= 0 && u < v && v < N && lab[u] != lab[v]) s += gcm_clamp(ce[(size_t)b * E + k]);
+    }
+  }
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0 && s) atomicAdd(&out[b], (unsigned long long)s);
 }
 
 // ---- energy of a labelling ------------------------------------------------------------------------------------------------------
@@ -430,6 +631,73 @@ int mgu_graphcut_energy(mgu_ctx* c, int B, int N, const int64_t* coo_dev, int64_
   const unsigned chunks = (unsigned)std::min<int64_t>(64, (N + E + GC_THREADS - 1) / GC_THREADS);
   hipLaunchKernelGGL(graphcut_energy_kernel, dim3(chunks, B), dim3(GC_THREADS), 0, s, N, E, coo_dev, labels_dev, cap_source_dev, cap_sink_dev,
                      cap_edge_dev, (unsigned long long*)energy_dev);
+  HIPCHK(c, hipGetLastError());
+  return MGU_OK;
+}
+
+int mgu_graphcut_label_costs(mgu_ctx* c, int64_t rows, int K, const float* prob_dev, const int32_t* counts_dev, float unit, int32_t* costs_dev,
+                             void* hip_stream) {
+  if (!c) return MGU_ERR_INVALID;
+  if (rows < 1 || K < 1 || K > 255 || rows > INT_MAX / K || !costs_dev || !(unit > 0.f))
+    return fail(c, MGU_ERR_INVALID, "bad graphcut_label_costs args (1 <= K <= 255, rows * K < 2^31, unit > 0)");
+  if (!prob_dev == !counts_dev) return fail(c, MGU_ERR_INVALID, "graphcut_label_costs: give the prior as probabilities OR as class counts");
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)hip_stream;
+  hipLaunchKernelGGL(graphcut_label_costs_kernel, dim3((unsigned)((rows + GC_THREADS - 1) / GC_THREADS)), dim3(GC_THREADS), 0, s, rows, K, prob_dev,
+                     counts_dev, unit, costs_dev);
+  HIPCHK(c, hipGetLastError());
+  return MGU_OK;
+}
+
+int mgu_graphcut_expand(mgu_ctx* c, int B, int N, int64_t E, int K, const int32_t* rowptr_dev, const int32_t* col_dev, const int32_t* rev_dev,
+                        const int32_t* perm_dev, const int32_t* costs_dev, const int32_t* cap_edge_dev, const uint8_t* init_dev, int max_cycles,
+                        int max_rounds, int relabel_period, int threads, uint8_t* labels_dev, int64_t* energy_dev, int32_t* moves_dev,
+                        int32_t* accepted_dev, int32_t* rounds_dev, int32_t* converged_dev, void* hip_stream) {
+  if (!c) return MGU_ERR_INVALID;
+  if (B < 1 || N < 1 || E < 0 || max_rounds < 0 || !rowptr_dev || !costs_dev || !labels_dev || !energy_dev || !moves_dev || !accepted_dev ||
+      !rounds_dev || !converged_dev || (E > 0 && (!col_dev || !rev_dev || !perm_dev || !cap_edge_dev)))
+    return fail(c, MGU_ERR_INVALID, "bad graphcut_expand args");
+  if (K < 1 || K > 255) return fail(c, MGU_ERR_INVALID, "graphcut_expand: %d labels, a label is one byte: 1 <= K <= 255", K);
+  if (max_cycles < 0 || max_cycles > (1 << 20)) return fail(c, MGU_ERR_INVALID, "graphcut_expand: 0 <= max_cycles <= 2^20");
+  if (relabel_period == 0) relabel_period = gc_default_period(N);
+  if (threads == 0) threads = gc_default_threads(N);
+  if (relabel_period < 1 || threads < 64 || threads > 1024 || threads % 64)
+    return fail(c, MGU_ERR_INVALID, "graphcut_expand: relabel_period >= 1, threads a multiple of 64 in [64, 1024]");
+  HIPCHK(c, hipSetDevice(c->device));
+  int budget = 0;
+  HIPCHK(c, hipDeviceGetAttribute(&budget, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device));
+  const size_t lds = gcm_lds_bytes(N, E);
+  if (E > INT_MAX / 2 || N > INT_MAX / 2 || (int64_t)N * K > INT_MAX || lds > (size_t)budget)
+    return fail(c, MGU_ERR_INVALID,
+                "graphcut_expand: a graph of %d nodes and %lld directed edges needs %zu bytes of LDS (20 N + 4 E + 48 + N rounded up to 8), the "
+                "device gives one workgroup %d",
+                N, (long long)E, lds, budget);
+  static bool attr_done[64] = {};
+  if (lds > 65536) HIPCHK(c, ensure_dyn_lds(reinterpret_cast<const void*>(&graphcut_expand_kernel), (size_t)budget, attr_done));
+  hipStream_t s = (hipStream_t)hip_stream;
+  ExpandArgs a;
+  a.N = N, a.E = (int)E, a.K = K, a.max_moves = max_cycles * K, a.max_rounds = max_rounds, a.period = relabel_period;
+  a.rowptr = rowptr_dev, a.col = col_dev, a.rev = rev_dev, a.perm = perm_dev;
+  a.costs = costs_dev, a.cap_edge = cap_edge_dev, a.init = init_dev;
+  a.labels = labels_dev, a.energy = (long long*)energy_dev, a.moves = moves_dev, a.accepted = accepted_dev, a.rounds = rounds_dev,
+  a.converged = converged_dev;
+  ProfScope ps(c, s, "graphcut_expand_kernel");
+  hipLaunchKernelGGL(graphcut_expand_kernel, dim3(B), dim3(threads), lds, s, a);
+  HIPCHK(c, hipGetLastError());
+  return MGU_OK;
+}
+
+int mgu_graphcut_energy_multi(mgu_ctx* c, int B, int N, const int64_t* coo_dev, int64_t E, int K, const uint8_t* labels_dev, const int32_t* costs_dev,
+                              const int32_t* cap_edge_dev, int64_t* energy_dev, void* hip_stream) {
+  if (!c) return MGU_ERR_INVALID;
+  if (B < 1 || N < 1 || E < 0 || B > 65535 || K < 1 || K > 255 || !labels_dev || !costs_dev || !energy_dev || (E > 0 && (!coo_dev || !cap_edge_dev)))
+    return fail(c, MGU_ERR_INVALID, "bad graphcut_energy_multi args (1 <= B <= 65535, 1 <= K <= 255)");
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)hip_stream;
+  HIPCHK(c, hipMemsetAsync(energy_dev, 0, (size_t)B * sizeof(int64_t), s));
+  const unsigned chunks = (unsigned)std::min<int64_t>(64, (N + E + GC_THREADS - 1) / GC_THREADS);
+  hipLaunchKernelGGL(graphcut_energy_multi_kernel, dim3(chunks, B), dim3(GC_THREADS), 0, s, N, E, K, coo_dev, labels_dev, costs_dev, cap_edge_dev,
+                     (unsigned long long*)energy_dev);
   HIPCHK(c, hipGetLastError());
   return MGU_OK;
 }

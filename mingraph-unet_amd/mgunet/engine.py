@@ -58,15 +58,19 @@ class MinGraphUNetE2E(nn.Module):
     partition="predictor" (default): the hard patch labels are the arg-max of the segment predictor.  partition="mincut"
     (num_segments == 2): they are the exact min cut of MinCutRefinement's energy (MinCutRefinement.refine_patches on the logits, the
     uint8 batch passed as forward(x, images_u8=...) and the node embeddings); the region stage runs on them, soft_assignments /
-    loss_partition stay the predictor's, and the dict gains cut_labels (B*Np,) int64 and cut_energy (B,)."""
+    loss_partition stay the predictor's, and the dict gains cut_labels (B*Np,) int64 and cut_energy (B,).  partition="expansion"
+    (any num_segments >= 2, equal to the U-Net's class count): the same with the K-label cut of
+    MinCutRefinement.refine_patches_multi (alpha-expansion over all classes of the U-Net's vote)."""
 
     def __init__(self, unet: UNet, patch_gat: GATNetwork, segment_predictor, mincut, region_gat: GATNetwork, detection_head,
                  num_segments: int, patch_size: int = 16, partition: str = "predictor", foreground: int = 1):
         super().__init__()
-        if partition not in ("predictor", "mincut"):
-            raise ValueError(f'partition must be "predictor" or "mincut", got {partition!r}')
+        if partition not in ("predictor", "mincut", "expansion"):
+            raise ValueError(f'partition must be "predictor", "mincut" or "expansion", got {partition!r}')
         if partition == "mincut" and num_segments != 2:
             raise ValueError(f'partition="mincut" is a binary cut: num_segments must be 2, got {num_segments}')
+        if partition == "expansion" and num_segments < 2:
+            raise ValueError(f'partition="expansion" needs num_segments >= 2, got {num_segments}')
         self.partition, self.foreground = partition, foreground
         self.core = MinGraphUNet(unet, patch_gat, patch_size)
         self.segment_predictor, self.mincut, self.region_gat, self.detection_head = segment_predictor, mincut, region_gat, detection_head
@@ -76,9 +80,12 @@ class MinGraphUNetE2E(nn.Module):
     def forward(self, x, images_u8=None):
         from .region import region_stage
         B, _, H, W = x.shape
-        if self.partition == "mincut" and images_u8 is None:
-            raise ValueError('partition="mincut" needs the uint8 batch: forward(x, images_u8=...)')
+        if self.partition != "predictor" and images_u8 is None:
+            raise ValueError(f'partition="{self.partition}" needs the uint8 batch: forward(x, images_u8=...)')
         logits, skips, feats, emb = self.core(x)
+        if self.partition == "expansion" and logits.shape[1] != self.num_segments:
+            raise ValueError(f'partition="expansion" labels the patches with the U-Net\'s classes: the logits have {logits.shape[1]} classes, '
+                             f"num_segments is {self.num_segments}")
         graph = self.core.graph
         nph, npw = graph.grid(H, W)
         K = self.num_segments
@@ -93,6 +100,9 @@ class MinGraphUNetE2E(nn.Module):
         cut = None
         if self.partition == "mincut":
             cut = self.mincut.refine_patches(logits, images_u8, emb, graph.patch_size, self.foreground)
+            hard = cut[0]
+        elif self.partition == "expansion":
+            cut = self.mincut.refine_patches_multi(logits, images_u8, emb, graph.patch_size)
             hard = cut[0]
         region_emb, fused = region_stage(emb, hard, B, K, self.region_gat, nph, npw, H, W, f_u=feats[0])
         det = self.detection_head(fused)

@@ -20,7 +20,21 @@ That set is the same for every maximum preflow, so among cuts of equal cost the 
 edge_index is the (2, E) int64 list of ONE graph and must hold both directions of every edge, no duplicate and no self loop
 (ValueError otherwise); cap_edge follows its order, node i of graph b is row b*N + i, edge k of graph b is entry b*E + k.  A graph
 must fit one workgroup's LDS: 20 N + 4 E + 40 bytes against the device's shared memory per block (160 KiB on gfx950: a 64 x 64
-patch grid uses 143 KiB); a larger one is a ValueError naming the budget."""
+patch grid uses 143 KiB); a larger one is a ValueError naming the budget.
+
+K labels (alpha-expansion over the same solver, one launch per batch):
+
+    E(L) = sum_i U_i(L_i) + sum over pairs {i,j} of w_ij [L_i != L_j],   L_i in {0 .. K-1}
+    U_i(k) = q(-log p_i(k)), p clamped to [1e-6, 1];   w_ij = cap_edge of the arc from the lower to the higher node id
+
+    label_costs       class probabilities (or patch_labels' class counts, p = (n_k + 1) / (n_all + K)) -> U (B*N, K) int32
+    graph_cut_multi   alpha = 0 .. K-1 cyclically; each move is one binary cut "node takes alpha" built and solved in LDS, accepted iff
+                      it lowers E strictly; K rejected moves in a row end the loop
+    cut_energy_multi  E(L) of any labelling
+
+cap_edge is cut_capacities' (it does not depend on the prior); the direction from the higher to the lower id is not read (cut_capacities
+writes both bitwise equal).  Costs and weights count as clamped to [0, 2^20].  For K = 2 with cap_source = U[:, 0] and cap_sink =
+U[:, 1], E(L) is E(S).  LDS per graph: 20 N + 4 E + 48 + (N rounded up to 8) bytes -- 147 KiB for the 64 x 64 grid."""
 from __future__ import annotations
 
 from collections import OrderedDict
@@ -34,9 +48,14 @@ _TOPOLOGY = OrderedDict()   # edge_index identity -> (rowptr, col, rev, perm, ed
 _TOPOLOGY_SLOTS = 8
 
 
-def _topology(edge_index: torch.Tensor, N: int):
+_WIDE = ("graph_cut_multi: a node of degree >= 4095: a move's 32-bit residual sink capacity can reach (1 + degree) * 2^20 and would "
+         "overflow (the binary graph_cut takes such a graph)")
+
+
+def _topology(edge_index: torch.Tensor, N: int, multi: bool = False):
     """CSR by source of one graph's edge list plus, per CSR position, the position of the reverse arc and the COO index (cached per
-    edge_index tensor: ONE synchronisation per new tensor).  ValueError on a missing reverse edge, a duplicate edge or a self loop."""
+    edge_index tensor: ONE synchronisation per new tensor).  ValueError on a missing reverse edge, a duplicate edge or a self loop, and
+    -- for the K-label functions only (multi) -- on a node of degree >= 4095, which the same pass finds."""
     if not isinstance(edge_index, torch.Tensor) or edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_index.dtype != torch.int64:
         raise ValueError("edge_index must be an int64 (2, E) tensor")
     _lib.require_hip(edge_index, "mgunet graph cut")
@@ -45,6 +64,8 @@ def _topology(edge_index: torch.Tensor, N: int):
     ent = _TOPOLOGY.get(key)
     if ent is not None:
         _TOPOLOGY.move_to_end(key)
+        if multi and ent[6]:
+            raise ValueError(_WIDE)
         return ent[:4]
     ei = edge_index.contiguous()
     E = ei.shape[1]
@@ -54,13 +75,15 @@ def _topology(edge_index: torch.Tensor, N: int):
     status = torch.empty(1, dtype=torch.int32, device=dev)
     _lib.call("mgu_graphcut_rev_index", dev, ei if E else None, E, N, rowptr, col if E else None, rev if E else None, perm if E else None, status)
     st = int(status.item())
-    if st:
+    if st & 15:
         what = [m for bit, m in ((1, "an edge without its reverse edge"), (2, "a duplicate edge"), (4, "a self loop"), (8, "an edge outside the graph"))
                 if st & bit]
         raise ValueError("graph cut: edge_index holds " + ", ".join(what) + " (it must list both directions of every edge once)")
-    _TOPOLOGY[key] = (rowptr, col, rev, perm, ei, edge_index)
+    _TOPOLOGY[key] = (rowptr, col, rev, perm, ei, edge_index, bool(st & 16))
     while len(_TOPOLOGY) > _TOPOLOGY_SLOTS:
         _TOPOLOGY.popitem(last=False)
+    if multi and st & 16:
+        raise ValueError(_WIDE)
     return rowptr, col, rev, perm
 
 
@@ -193,4 +216,126 @@ def cut_energy(labels, edge_index, cap_source, cap_sink, cap_edge, batch=1) -> t
     ce = _caps(cap_edge, B * E, "cap_edge", dev) if E else None
     out = torch.empty(B, dtype=torch.int64, device=dev)
     _lib.call("mgu_graphcut_energy", dev, B, N, edge_index.contiguous() if E else None, E, lab, cs, ct, ce, out)
+    return out
+
+
+# ---- K labels --------------------------------------------------------------------------------------------------------------------
+class MultiCut:
+    """Result of graph_cut_multi, all on the device: labels (B, N) uint8, energy (B,) int64 = E(labels) in capacity units, moves,
+    accepted, rounds (summed over the moves), converged: (B,) int32.  Nothing is read back until check()."""
+
+    def __init__(self, labels, energy, moves, accepted, rounds, converged, max_cycles, max_rounds):
+        self.labels, self.energy, self.moves, self.accepted, self.rounds, self.converged = labels, energy, moves, accepted, rounds, converged
+        self.max_cycles, self.max_rounds = max_cycles, max_rounds
+
+    def check(self) -> "MultiCut":
+        """Synchronise and raise RuntimeError if a graph reached max_cycles, or a move of it max_rounds, before the expansion converged
+        (its labels are then the last accepted labelling, not a local minimum)."""
+        bad = (self.converged == 0).nonzero().flatten().tolist()
+        if bad:
+            raise RuntimeError(f"graph_cut_multi: graph(s) {bad} did not converge within max_cycles = {self.max_cycles} "
+                               f"(max_rounds = {self.max_rounds} per move)")
+        return self
+
+
+def _costs(costs, B: int, what: str):
+    """-> (contiguous (B*N, K) int32 costs, N, K)"""
+    if not isinstance(costs, torch.Tensor):
+        raise TypeError(f"{what}: costs must be a device tensor")
+    _lib.require_hip(costs, what)
+    if costs.dtype != torch.int32:
+        raise TypeError(f"{what}: costs must be int32 (label_costs gives them), got {costs.dtype}")
+    if costs.dim() not in (2, 3):
+        raise ValueError(f"{what}: costs must be (B*N, K) or (B, N, K)")
+    K = costs.shape[-1]
+    if not 1 <= K <= 255:
+        raise ValueError(f"{what}: {K} labels, a label is one byte: 1 <= K <= 255")
+    rows = costs.numel() // K
+    if B < 1 or rows < B or rows % B:
+        raise ValueError(f"{what}: {rows} cost rows do not split into {B} graphs")
+    return costs.reshape(rows, K).contiguous(), rows // B, K
+
+
+def label_costs(prior, batch=1, unit=1024) -> torch.Tensor:
+    """U (B*N, K) int32 = q(-log p), p clamped to [1e-6, 1].  prior: float32 (B*N, K) class probabilities, or int32 (B*N, K) /
+    (B, N, K) class counts as patch_labels(return_counts=True) gives them, p = (n_k + 1) / (n_all + K).  One launch, evaluated in
+    double: the count path is exact."""
+    B = int(batch)
+    if not isinstance(prior, torch.Tensor):
+        raise TypeError("prior must be a device tensor")
+    _lib.require_hip(prior, "mgunet.label_costs")
+    if prior.dtype == torch.float32:
+        if prior.dim() != 2:
+            raise ValueError("class probabilities must be a float32 (B*N, K) tensor")
+    elif prior.dtype == torch.int32:
+        if prior.dim() not in (2, 3):
+            raise ValueError("class counts must be an int32 (B*N, K) or (B, N, K) tensor")
+    else:
+        raise TypeError(f"prior must be float32 probabilities or int32 class counts, got {prior.dtype}")
+    K = prior.shape[-1]
+    if not 1 <= K <= 255:
+        raise ValueError(f"label_costs: {K} labels, a label is one byte: 1 <= K <= 255")
+    rows = prior.numel() // K
+    if B < 1 or rows < B or rows % B:
+        raise ValueError(f"{rows} prior rows do not split into {B} graphs")
+    if not unit > 0:
+        raise ValueError("unit must be positive")
+    p = prior.contiguous()
+    out = torch.empty((rows, K), dtype=torch.int32, device=prior.device)
+    is_prob = prior.dtype == torch.float32
+    _lib.call("mgu_graphcut_label_costs", prior.device, rows, K, p if is_prob else None, None if is_prob else p, float(unit), out)
+    return out
+
+
+def graph_cut_multi(edge_index, costs, cap_edge, batch=1, init=None, max_cycles=None, max_rounds=None, *, relabel_period=None,
+                    threads=None) -> MultiCut:
+    """Alpha-expansion of `batch` graphs over one topology, the whole loop in one launch.  costs: int32 (batch * N, K) (or (batch, N, K)),
+    1 <= K <= 255; cap_edge: int32 (batch * E) in edge_index order, of which the arc from the lower to the higher node id is the
+    pair's weight.  init: optional uint8 (batch, N) start labels (a value >= K is replaced by the node's cheapest label); None: every
+    node's cheapest label, the lowest on ties.  max_cycles (default 32) and max_rounds (per move, default 8 N + 64) are caps, not tuning
+    values: reaching one is reported by MultiCut.converged / check(), and the labels are then the last accepted labelling.
+    relabel_period / threads as in graph_cut: they change nothing but `rounds`.  The inputs are not modified; no host read inside the
+    call (beyond the one-off topology check of a new edge_index).  ValueError for a graph beyond one workgroup's LDS or with a node
+    of degree >= 4095."""
+    B = int(batch)
+    U, N, K = _costs(costs, B, "graph_cut_multi")
+    dev = U.device
+    if isinstance(edge_index, torch.Tensor) and edge_index.device != dev:
+        raise ValueError("costs and edge_index must be on the same device")
+    rowptr, col, rev, perm = _topology(edge_index, N, multi=True)
+    E = edge_index.shape[1]
+    ce = _caps(cap_edge, B * E, "cap_edge", dev) if E else None
+    if init is not None:
+        if not isinstance(init, torch.Tensor) or init.dtype != torch.uint8 or init.device != dev or init.numel() != B * N:
+            raise TypeError(f"init must be a uint8 tensor of {B * N} labels on the device of edge_index")
+        init = init.contiguous()
+    mc = 32 if max_cycles is None else int(max_cycles)
+    mr = 8 * N + 64 if max_rounds is None else int(max_rounds)
+    if mc < 0 or mr < 0:
+        raise ValueError("max_cycles and max_rounds must not be negative")
+    labels = torch.empty((B, N), dtype=torch.uint8, device=dev)
+    energy = torch.empty(B, dtype=torch.int64, device=dev)
+    moves, accepted, rounds, conv = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(4))
+    _lib.call("mgu_graphcut_expand", dev, B, N, E, K, rowptr, col if E else None, rev if E else None, perm if E else None, U, ce, init, mc, mr,
+              int(relabel_period or 0), int(threads or 0), labels, energy, moves, accepted, rounds, conv)
+    return MultiCut(labels, energy, moves, accepted, rounds, conv, mc, mr)
+
+
+def cut_energy_multi(labels, edge_index, costs, cap_edge, batch=1) -> torch.Tensor:
+    """E(L) of a labelling (B, N) / (B*N,), any integer dtype with values in [0, K), in capacity units -> int64 (B,).  For the labels
+    of graph_cut_multi it equals MultiCut.energy."""
+    B = int(batch)
+    if not isinstance(labels, torch.Tensor) or labels.is_floating_point() or labels.dtype == torch.bool:
+        raise TypeError("labels must be an integer device tensor")
+    _lib.require_hip(labels, "mgunet.cut_energy_multi")
+    U, N, K = _costs(costs, B, "cut_energy_multi")
+    dev = labels.device
+    if U.device != dev or labels.numel() != B * N:
+        raise ValueError(f"labels must hold {B * N} entries on the device of costs")
+    _topology(edge_index, N)
+    E = edge_index.shape[1]
+    lab = labels.clamp(0, 255).to(torch.uint8).contiguous()
+    ce = _caps(cap_edge, B * E, "cap_edge", dev) if E else None
+    out = torch.empty(B, dtype=torch.int64, device=dev)
+    _lib.call("mgu_graphcut_energy_multi", dev, B, N, edge_index.contiguous() if E else None, E, K, lab, U, ce, out)
     return out

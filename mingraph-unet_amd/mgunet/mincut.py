@@ -144,7 +144,8 @@ class PatchSegmentPredictor(nn.Module):
 class MinCutRefinement(nn.Module):
     """mincut_refinement.py:5-205.  The constructor arguments parameterise the energy E(S) of a solver the reference
     never implements (:9-16).  Here `solve` / `refine_patches` minimise that energy exactly with them (mgunet.graphcut: this build's
-    definition of E(S), taken from the reference's parameter documentation); the normalized-cut loss below does not use them."""
+    definition of E(S), taken from the reference's parameter documentation) and `solve_multi` / `refine_patches_multi` its K-label form
+    by alpha-expansion; the normalized-cut loss below does not use them."""
 
     def __init__(self, gamma_unet_priors=0.5, sigma_intensity=10.0, sigma_features=1.0):
         super().__init__()
@@ -182,12 +183,22 @@ class MinCutRefinement(nn.Module):
         cut = graph_cut(edge_index, cs, ct, ce, batch=batch)
         return cut.labels.reshape(-1).to(torch.int64), cut.flow.to(torch.float64) / unit, cut
 
-    def refine_patches(self, logits, images_u8, node_features, patch_size, foreground=1):
-        """The patch partition of a batch by the cut, with no trained predictor: the prior is the U-Net's own vote per patch
-        (patch_labels(logits, return_counts=True): p = (n_fg + 1) / (n_all + 2) for class `foreground`), the intensity the patch means
-        of the uint8 images (patch_features_u8), the features the given node features (B*Np, D) -- the GAT embeddings are the
-        intended ones -- and the topology PatchGraphConstructor's.  logits (B, C, H, W) float, images_u8 (B, H, W, 3) uint8.
-        -> what `solve` returns."""
+    def solve_multi(self, prior, edge_index, intensity=None, features=None, batch=1, smoothness=1.0):
+        """The K-label form of `solve`: alpha-expansion (mgunet.graph_cut_multi) on E(L) = sum_i U_i(L_i) + sum_pairs w_ij [L_i != L_j]
+        with the same w_ij.  prior: float32 (B*N, K) class probabilities, or int32 (B*N, K) / (B, N, K) class counts.
+        -> (labels (B*N,) int64 in [0, K); E(L) (B,) float64 = energy / unit; the MultiCut).  Nothing is read back: MultiCut.check()
+        reports a graph that did not converge."""
+        from .graphcut import cut_capacities, graph_cut_multi, label_costs
+        unit = 1024
+        costs = label_costs(prior, batch=batch, unit=unit)
+        half = torch.full((costs.shape[0],), 0.5, dtype=torch.float32, device=costs.device)   # cap_edge does not depend on the prior
+        ce = cut_capacities(half, edge_index, intensity, features, gamma=self.gamma_unet_priors, sigma_intensity=self.sigma_intensity,
+                            sigma_features=self.sigma_features, smoothness=smoothness, unit=unit, batch=batch)[2]
+        cut = graph_cut_multi(edge_index, costs, ce, batch=batch)
+        return cut.labels.reshape(-1).to(torch.int64), cut.energy.to(torch.float64) / unit, cut
+
+    def _patch_inputs(self, logits, images_u8, node_features, patch_size):
+        """what the two refine_patches feed their solve: (class counts, one image's edge_index, intensity, features, B)"""
         from .patch_graph import PatchGraphConstructor
         from .patch_inputs import patch_labels
         from .preprocess import _to_dev_u8, patch_features_u8
@@ -204,7 +215,22 @@ class MinCutRefinement(nn.Module):
         _, counts = patch_labels(logits, p, return_counts=True)
         intensity = torch.cat([patch_features_u8(img, p) for img in u8]).reshape(-1)
         feats = node_features.detach().to(torch.float32).reshape(intensity.numel(), -1)
-        return self.solve(counts, graph.edge_index(H, W, logits.device), intensity, feats, batch=B, counts_foreground=int(foreground))
+        return counts, graph.edge_index(H, W, logits.device), intensity, feats, B
+
+    def refine_patches_multi(self, logits, images_u8, node_features, patch_size):
+        """`refine_patches` over ALL C classes of the U-Net's vote: the label costs come from the per-patch class counts
+        (p = (n_k + 1) / (n_all + C)), intensity, features and topology as there.  -> what `solve_multi` returns."""
+        counts, ei, intensity, feats, B = self._patch_inputs(logits, images_u8, node_features, patch_size)
+        return self.solve_multi(counts, ei, intensity, feats, batch=B)
+
+    def refine_patches(self, logits, images_u8, node_features, patch_size, foreground=1):
+        """The patch partition of a batch by the cut, with no trained predictor: the prior is the U-Net's own vote per patch
+        (patch_labels(logits, return_counts=True): p = (n_fg + 1) / (n_all + 2) for class `foreground`), the intensity the patch means
+        of the uint8 images (patch_features_u8), the features the given node features (B*Np, D) -- the GAT embeddings are the
+        intended ones -- and the topology PatchGraphConstructor's.  logits (B, C, H, W) float, images_u8 (B, H, W, 3) uint8.
+        -> what `solve` returns."""
+        counts, ei, intensity, feats, B = self._patch_inputs(logits, images_u8, node_features, patch_size)
+        return self.solve(counts, ei, intensity, feats, batch=B, counts_foreground=int(foreground))
 
     def compute_edge_weights_for_ncut(self, node_features, edge_index):
         """(E,) weights exp(-|f_i - f_j|^2 / 2) in edge order (:30-52)."""
