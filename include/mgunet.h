@@ -460,6 +460,39 @@ int mgu_match_objects(mgu_ctx* ctx, int B, const int64_t* gt_offsets_dev, const 
 int mgu_object_scores(mgu_ctx* ctx, const int32_t* labels_dev, const float* probs_dev, int B, int H, int W, int C, const int64_t* offsets_dev,
                       int64_t capacity, const int64_t* class_dev, const int64_t* area_dev, float* scores_dev, void* hip_stream);
 
+/* ---- splitting touching objects: exact distance transform, one seed per inscribed disc, power diagram of the discs -----------------
+ * Two fruits whose masks touch are one connected component; this stage sits between "label" and "count".  All in exact integers (no
+ * float anywhere), so the results are deterministic: bitwise repeatable whatever order the atomics land in.  It is not a flooding
+ * watershed: cells are cut along radical axes, not along grey-level ridges.
+ * labels_dev: int32 (B,H,W) as mgu_connected_components writes it, 0 = background; a "component" is the set of pixels of one image
+ * holding the same non-zero label (it need not be connected).
+ * Squared Euclidean distance transform.  d2_dev int32 (B,H,W): for a foreground pixel p the minimum of |p - q|^2 over the pixels q of
+ * the same image with labels[q] != labels[p] -- background counts, a touching object with another label counts, pixels outside the
+ * image do not (scipy.ndimage.distance_transform_edt of the label's mask); MGU_D2_NONE when the image holds no such q; 0 on
+ * background.  Any int32 label map is legal here.  Two launches (columns, then rows with the row in LDS).  H, W <= 16384 (the row
+ * buffer is 8 bytes of LDS per pixel, and every real distance stays below MGU_D2_NONE), B <= 65535, B*(H*W+1) < 2^31. */
+#define MGU_D2_NONE (1 << 30)
+int mgu_distance_transform(mgu_ctx* ctx, const int32_t* labels_dev, int B, int H, int W, int32_t* d2_dev, void* hip_stream);
+/* Split every component at the necks between its inscribed discs (limits as above; labels outside [0, H*W] read as background).
+ *   Seeds.  With r = min_distance (1..16), a foreground pixel p is a seed iff D2(p) >= min_radius_sq (>= 1) and D2(p) >= D2(q) for
+ *     every q of p's label within Chebyshev distance r (pixels outside the image and other labels take no part).
+ *   Seed groups.  h = (r + 1) / 2; the zone map Z(p) = labels[p] if a seed of p's label lies within Chebyshev distance h of p, else 0;
+ *     the groups are the 8-connected same-value components of Z, and a seed belongs to the group that contains it.  Equal peaks of one
+ *     component closer than about r are one object, peaks farther apart are two.
+ *   Assignment.  A pixel p of a component with seeds goes to the group of the seed s of its component minimising |p - s|^2 - D2(s)
+ *     (int64), ties to the smaller y*W + x of s: the power diagram of the inscribed discs, whose cell boundary between two
+ *     overlapping discs is the chord through their intersection points.  A component without a seed (thinner than min_radius_sq)
+ *     stays one object.
+ *   Output.  labels_out_dev int32 (B,H,W) (may be labels_dev itself): the new objects 1..n'_b per image in raster order of their
+ *     first pixel (a cell need not be connected); objects of fewer than min_area pixels become background and the rest are
+ *     renumbered; counts_dev int64 (B), offsets_dev int64 (B+1) as mgu_connected_components writes them.  d2_out_dev int32 (B,H,W)
+ *     and seeds_out_dev uint8 (B,H,W) (1 = seed) receive the distance transform and the seed mask; either may be NULL.
+ * 16 kernel launches and 2 fills (3 with a min_area), whatever B, the objects and the seeds; no host synchronisation; scratch from
+ * the context (about 45 bytes per pixel). */
+int mgu_split_objects(mgu_ctx* ctx, const int32_t* labels_dev, int B, int H, int W, int min_distance, int64_t min_radius_sq, int min_area,
+                      int32_t* labels_out_dev, int64_t* counts_dev, int64_t* offsets_dev, int32_t* d2_out_dev, uint8_t* seeds_out_dev,
+                      void* hip_stream);
+
 /* ---- object shape: per-object moments, fitted ellipse and the per-instance form of EllipticalShapeLoss (model/unet/shape_loss.py
  *      :155-180 over the instances :42-48 and :85-92 ask for) straight from the label map: no dense masks, no per-object launches,
  *      no host synchronisation; the launch count does not depend on the number of objects ------------------------------------------

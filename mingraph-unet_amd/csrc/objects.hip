@@ -10,6 +10,8 @@
 // union hooks the larger root under the smaller one with atomicMin, so each root ends as its component's smallest linear index:
 // whatever order the atomics land in, the trees' roots, and so the numbering, are the same -- the labels are deterministic.
 // All accumulations are integer atomics (exact, order-free); runs of equal labels are summed inside a wave before the atomic.
+// split.hip labels its int32 zone map through steps (1)-(3) (cc_roots_i32) and numbers its own objects through (3)-(4)
+// (cc_number_roots, the tail of mgu_connected_components); both are declared in ctx.h.
 #include <climits>
 
 #include "ctx.h"
@@ -24,11 +26,14 @@ constexpr int CHUNK = 4 * OB_THREADS;         // root numbering: 1024 consecutiv
 constexpr int SCAN_THREADS = 1024;
 constexpr int LEADER_ROUNDS = 4;              // wave pre-aggregation: distinct labels summed per wave before the rest go direct
 
-// value of pixel g: the class map's entry, or the first maximal class of the logits (bit-identical to argmax_kernel)
+// value of pixel g: the class map's entry (KIND 0 int64; 2 int32, the internal form of split.hip's zone map), or the first maximal
+// class of the logits (KIND 1, bit-identical to argmax_kernel)
 template <int KIND>
 __device__ __forceinline__ long long pix_key(const void* src, int64_t g, int C) {
   if constexpr (KIND == 0) {
     return reinterpret_cast<const long long*>(src)[g];
+  } else if constexpr (KIND == 2) {
+    return reinterpret_cast<const int*>(src)[g];
   } else {
     const float* p = reinterpret_cast<const float*>(src) + g * C;
     float best = p[0];
@@ -433,6 +438,37 @@ __global__ __launch_bounds__(64) void match_kernel(const long long* __restrict__
 using namespace mgu;
 using namespace mgud;
 
+namespace mgud {
+
+int64_t cc_chunks(int64_t HW) { return (HW + CHUNK - 1) / CHUNK; }
+
+int cc_roots_i32(mgu_ctx* c, const int32_t* map, int B, int H, int W, int* P, hipStream_t s) {
+  const dim3 tiles((W + TILE - 1) / TILE, (H + TILE - 1) / TILE, B);
+  const int64_t n = (int64_t)B * H * W;
+  hipLaunchKernelGGL((cc_local_kernel<2, true>), tiles, dim3(OB_THREADS), 0, s, map, H, W, 0, 0ll, 0ll, P);
+  hipLaunchKernelGGL((cc_border_kernel<2, true>), tiles, dim3(128), 0, s, map, H, W, 0, P);
+  hipLaunchKernelGGL(cc_flatten_kernel, dim3((unsigned)((n + OB_THREADS - 1) / OB_THREADS)), dim3(OB_THREADS), 0, s, P, n, (unsigned*)nullptr);
+  HIPCHK(c, hipGetLastError());
+  return MGU_OK;
+}
+
+int cc_number_roots(mgu_ctx* c, int* P, unsigned* area, int min_area, int B, int64_t HW, int* cnt, long long* choff, int32_t* labels,
+                    int64_t* counts, int64_t* offsets, hipStream_t s) {
+  const int64_t n = (int64_t)B * HW, nch = cc_chunks(HW);
+  if (area) HIPCHK(c, hipMemsetAsync(area, 0, (size_t)n * 4, s));
+  const unsigned pixblocks = (unsigned)((n + OB_THREADS - 1) / OB_THREADS);
+  hipLaunchKernelGGL(cc_flatten_kernel, dim3(pixblocks), dim3(OB_THREADS), 0, s, P, n, area);
+  const dim3 chunks((unsigned)nch, B);
+  hipLaunchKernelGGL(cc_count_kernel, chunks, dim3(OB_THREADS), 0, s, P, area, min_area, HW, cnt);
+  hipLaunchKernelGGL(cc_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, s, cnt, nch, B, choff, (long long*)counts, (long long*)offsets);
+  hipLaunchKernelGGL(cc_number_kernel, chunks, dim3(OB_THREADS), 0, s, P, area, min_area, HW, choff, (const long long*)offsets, (int*)labels);
+  hipLaunchKernelGGL(cc_relabel_kernel, dim3(pixblocks), dim3(OB_THREADS), 0, s, P, area, min_area, n, (int*)labels);
+  HIPCHK(c, hipGetLastError());
+  return MGU_OK;
+}
+
+}  // namespace mgud
+
 extern "C" {
 
 int mgu_connected_components(mgu_ctx* c, const void* src_dev, int src_kind, int B, int H, int W, int C, int connectivity, int64_t background,
@@ -453,7 +489,7 @@ int mgu_connected_components(mgu_ctx* c, const void* src_dev, int src_kind, int 
     HIPCHK(c, hipMemsetAsync(offsets_dev, 0, (size_t)(B + 1) * sizeof(int64_t), s));
     return MGU_OK;
   }
-  const int64_t nch = (HW + CHUNK - 1) / CHUNK;
+  const int64_t nch = cc_chunks(HW);
   Carve cv;
   const size_t oP = cv.take((size_t)n * 4), oA = min_area > 0 ? cv.take((size_t)n * 4) : 0, oC = cv.take((size_t)nch * B * 4);
   int rc = ensure(c, &c->objws, &c->objws_bytes, cv.off + (size_t)nch * B * 8);   // the last region ends the buffer: no padding behind it
@@ -461,10 +497,6 @@ int mgu_connected_components(mgu_ctx* c, const void* src_dev, int src_kind, int 
   char* ws = (char*)c->objws;
   int* P = (int*)(ws + oP);
   unsigned* area = min_area > 0 ? (unsigned*)(ws + oA) : nullptr;
-  int* cnt = (int*)(ws + oC);
-  long long* choff = (long long*)(ws + cv.off);
-  long long* counts = (long long*)counts_dev;
-  long long* offsets = (long long*)offsets_dev;
   const long long bg = background, ncls = num_classes;
   const dim3 tiles((W + TILE - 1) / TILE, (H + TILE - 1) / TILE, B);
 #define MGU_CC(KIND, C8)                                                                                                \
@@ -480,16 +512,7 @@ int mgu_connected_components(mgu_ctx* c, const void* src_dev, int src_kind, int 
     else MGU_CC(1, false);
   }
 #undef MGU_CC
-  if (area) HIPCHK(c, hipMemsetAsync(area, 0, (size_t)n * 4, s));
-  const unsigned pixblocks = (unsigned)((n + OB_THREADS - 1) / OB_THREADS);
-  hipLaunchKernelGGL(cc_flatten_kernel, dim3(pixblocks), dim3(OB_THREADS), 0, s, P, n, area);
-  const dim3 chunks((unsigned)nch, B);
-  hipLaunchKernelGGL(cc_count_kernel, chunks, dim3(OB_THREADS), 0, s, P, area, min_area, HW, cnt);
-  hipLaunchKernelGGL(cc_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, s, cnt, nch, B, choff, counts, offsets);
-  hipLaunchKernelGGL(cc_number_kernel, chunks, dim3(OB_THREADS), 0, s, P, area, min_area, HW, choff, offsets, (int*)labels_dev);
-  hipLaunchKernelGGL(cc_relabel_kernel, dim3(pixblocks), dim3(OB_THREADS), 0, s, P, area, min_area, n, (int*)labels_dev);
-  HIPCHK(c, hipGetLastError());
-  return MGU_OK;
+  return cc_number_roots(c, P, area, min_area, B, HW, (int*)(ws + oC), (long long*)(ws + cv.off), labels_dev, counts_dev, offsets_dev, s);
 }
 
 int mgu_object_stats(mgu_ctx* c, const int32_t* labels_dev, const void* src_dev, int src_kind, int B, int H, int W, int C,

@@ -7,7 +7,8 @@ from .gat import GATNetwork, GraphAttentionLayer, MultiHeadGATLayer, seed_dropou
 from .losses import EllipticalShapeLoss, FeatureConsistencyLoss, TVLoss, dice_loss  # noqa: F401
 from .preprocess import EdgeDetector, HistogramEqualizer, ImagePreprocessor, RandomFlipRotate, draw_flip_rotate, patch_features_u8, pil_rotation_fixed, postprocess_segmentation  # noqa: F401
 from .metrics import SegmentationEvaluator, allreduce_eval_state, evaluate_segmentation, metrics_from_confusion, segmentation_metrics  # noqa: F401
-from .objects import ObjectShapes, ObjectTable, YieldEvaluator, connected_components, evaluate_yield, object_shapes, yield_estimation_metrics  # noqa: F401
+from .objects import (ObjectShapes, ObjectTable, YieldEvaluator, connected_components, distance_transform, evaluate_yield,  # noqa: F401
+                      object_shapes, split_objects, yield_estimation_metrics)
 from .tta import object_scores, predict_tta  # noqa: F401
 from .tiled import predict_tiled, tile_grid, tile_weights  # noqa: F401
 from .graphcut import GraphCut, MultiCut, cut_capacities, cut_energy, cut_energy_multi, graph_cut, graph_cut_multi, label_costs  # noqa: F401

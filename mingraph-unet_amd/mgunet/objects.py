@@ -5,9 +5,11 @@ Connected components, per-object statistics and the reference's greedy box match
 YieldEvaluator accumulates per-image counts and matching totals across batches without a host synchronisation, and the host only
 turns them into the reference's dictionary with the reference's own arithmetic (bitwise equal results).  object_shapes adds the
 per-object shape (csrc/shapes.hip): exact integer moments of the label map, a fitted ellipse and the per-instance term of
-EllipticalShapeLoss (model/unet/shape_loss.py:155-180).  There is no scipy or skimage dependency."""
+EllipticalShapeLoss (model/unet/shape_loss.py:155-180).  split_objects cuts touching objects apart (csrc/split.hip): exact integer
+distance transform, one seed per inscribed disc, the power diagram of the discs.  There is no scipy or skimage dependency."""
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 
 import numpy as np
@@ -120,6 +122,85 @@ def connected_components(x: torch.Tensor, connectivity: int = 2, background: int
     if N:
         _stats(labels, src, kind, B, H, W, C, offsets, N, cls, bbox, area, sums)
     return ObjectTable(labels, counts, offsets, cls, area, bbox, sums)
+
+
+def distance_transform(labels) -> torch.Tensor:
+    """int32 (B, H, W): the exact squared Euclidean distance of every foreground pixel of an integer label map (H, W) or (B, H, W),
+    or of an ObjectTable's labels, to the nearest pixel of its image holding another label (background or another object; pixels
+    outside the image do not count: scipy.ndimage.distance_transform_edt(labels == k) ** 2 on the pixels of label k).  0 on
+    background, 2 ** 30 where the image holds no other label.  H, W <= 16384.  The labels are read as int32: every value of a wider
+    map must fit it (connected_components' labels do), or distinct labels may wrap onto each other or onto 0."""
+    lab = labels.labels if isinstance(labels, ObjectTable) else labels
+    _lib.require_hip(lab, "distance_transform")
+    if lab.is_floating_point() or lab.dtype == torch.bool or lab.dim() not in (2, 3):
+        raise TypeError("a label map must be an integer (H, W) or (B, H, W) tensor")
+    lab = lab.reshape((1,) + tuple(lab.shape)) if lab.dim() == 2 else lab
+    lab = lab.to(torch.int32).contiguous()
+    B, H, W = lab.shape
+    d2 = torch.empty((B, H, W), device=lab.device, dtype=torch.int32)
+    _lib.call("mgu_distance_transform", lab.device, lab, B, H, W, d2)
+    return d2
+
+
+def _split_params(min_distance, min_radius, min_area):
+    """(min_distance, min_radius_sq, min_area) as mgu_split_objects takes them: the radius is squared here."""
+    if int(min_distance) != min_distance or not 1 <= min_distance <= 16:
+        raise ValueError(f"min_distance must be an integer in 1..16, got {min_distance}")
+    if not min_radius > 0:
+        raise ValueError("min_radius must be > 0")
+    if min_area < 0:
+        raise ValueError("min_area must be >= 0")
+    return int(min_distance), max(1, math.ceil(min_radius * min_radius)), int(min_area)
+
+
+def _split(labels, B, H, W, params, out, counts, offsets, d2=None, seeds=None):
+    _lib.call("mgu_split_objects", labels.device, labels, B, H, W, *params, out, counts, offsets, d2, seeds)
+
+
+def split_objects(x, min_distance: int = 5, min_radius: float = 3, connectivity: int = 2, background: int = 0, min_area: int = 0,
+                  return_seeds: bool = False):
+    """connected_components(x, connectivity, background) with touching objects cut apart, on the device.  x: whatever
+    connected_components takes, or an ObjectTable (its labels are split; connectivity and background are not used then).
+
+    Every object gets the exact squared distance transform D2 of its mask.  A pixel is a seed when D2 >= min_radius ** 2 and no pixel
+    of its object within Chebyshev distance min_distance (1..16) has a larger D2; seeds whose (min_distance + 1) // 2 neighbourhoods
+    touch are one group.  Each pixel goes to the group of the seed s minimising |p - s|^2 - D2(s): the power diagram of the inscribed
+    discs, which cuts two overlapping discs along the chord through their intersection points.  An object thinner than min_radius
+    stays whole.  Objects under min_area pixels are dropped after the split.  This is not a flooding watershed: a ring of three
+    mutually overlapping discs can yield a fourth cell at the enclosed centre peak (raise min_radius), and strongly non-convex blobs
+    over-split, as under any prominence-free seed rule.  All integer arithmetic: bitwise repeatable.  Synchronises once, to size the
+    per-object arrays.  return_seeds: also return the bool (B, H, W) seed mask."""
+    _check_args(connectivity, min_area)
+    params = _split_params(min_distance, min_radius, min_area)
+    parent = x if isinstance(x, ObjectTable) else None
+    if parent is not None:
+        _lib.require_hip(parent.labels, "split_objects")
+        B, H, W = parent.labels.shape
+        comp, dev = parent.labels, parent.labels.device
+        src, kind, C = parent.labels.to(torch.int64), 0, 0   # the statistics' "class" of a new object: its parent's label
+    else:
+        src, kind, B, H, W, C = _source(x)
+        dev = src.device
+        comp = torch.empty((B, H, W), device=dev, dtype=torch.int32)
+        _label(src, kind, B, H, W, C, connectivity, background, 0, 0, comp, torch.empty(B, device=dev, dtype=torch.int64),
+               torch.empty(B + 1, device=dev, dtype=torch.int64))
+    labels = torch.empty((B, H, W), device=dev, dtype=torch.int32)
+    counts = torch.empty(B, device=dev, dtype=torch.int64)
+    offsets = torch.empty(B + 1, device=dev, dtype=torch.int64)
+    seeds = torch.empty((B, H, W), device=dev, dtype=torch.uint8) if return_seeds else None
+    _split(comp, B, H, W, params, labels, counts, offsets, None, seeds)
+    N = int(offsets[B].item())
+    cls = torch.empty(N, device=dev, dtype=torch.int64)
+    area = torch.empty(N, device=dev, dtype=torch.int64)
+    bbox = torch.empty((N, 4), device=dev, dtype=torch.int32)
+    sums = torch.empty((N, 2), device=dev, dtype=torch.int64)
+    if N:
+        _stats(labels, src, kind, B, H, W, C, offsets, N, cls, bbox, area, sums)
+        if parent is not None:   # parent label -> the parent's row -> its class
+            image = torch.repeat_interleave(torch.arange(B, device=dev), counts, output_size=N)
+            cls = parent.class_id[parent.offsets[image] + cls - 1]
+    table = ObjectTable(labels, counts, offsets, cls, area, bbox, sums)
+    return (table, seeds.bool()) if return_seeds else table
 
 
 @dataclass
@@ -259,10 +340,19 @@ class YieldEvaluator:
     labelling) and the GT objects (mask values in [1, num_classes); 0, -100 and anything out of range are background), appends the
     per-image counts to device buffers and accumulates the matching totals; it never blocks the host.  min_area applies to the
     predicted objects.  compute() synchronises once and returns yield_estimation_metrics' dictionary -- equal to calling it on the
-    per-image counts and to_dicts() of the same batches."""
+    per-image counts and to_dicts() of the same batches.  split: a dict of split_objects' min_distance / min_radius / min_area; the
+    predicted and the GT objects alike are then cut apart (mgunet.split_objects) before they are counted and matched, still without
+    a host synchronisation.  None: objects are the connected components."""
 
-    def __init__(self, num_classes: int, device, connectivity: int = 2, min_area: int = 0, iou_thresh: float = 0.5, smooth: float = 1e-6):
+    def __init__(self, num_classes: int, device, connectivity: int = 2, min_area: int = 0, iou_thresh: float = 0.5, smooth: float = 1e-6,
+                 split: dict = None):
         _check_args(connectivity, min_area)
+        self._split = None
+        if split is not None:
+            extra = set(split) - {"min_distance", "min_radius", "min_area"}
+            if extra:
+                raise ValueError(f"split takes min_distance, min_radius and min_area, not {sorted(extra)}")
+            self._split = _split_params(split.get("min_distance", 5), split.get("min_radius", 3), split.get("min_area", 0))
         self.num_classes, self.device = int(num_classes), torch.device(device)
         if self.num_classes < 1:
             raise ValueError("num_classes must be >= 1")
@@ -306,6 +396,8 @@ class YieldEvaluator:
             counts[side] = torch.empty(B, device=self.device, dtype=torch.int64)
             offsets[side] = torch.empty(B + 1, device=self.device, dtype=torch.int64)
             _label(s, k, B, H, W, cc, self.connectivity, 0, ncls, amin, lab, counts[side], offsets[side])
+            if self._split is not None:   # in place: the split has read the components before it writes the objects
+                _split(lab, B, H, W, self._split, lab, counts[side], offsets[side])
             _stats(lab, s, k, B, H, W, cc, offsets[side], self._cap, cls, bbox)
         (gl, gc, gb), (pl, pc, pb) = bufs["gt"], bufs["pred"]
         _lib.call("mgu_match_objects", self.device, B, offsets["gt"], gc, gb, self._cap, offsets["pred"], pc, pb, self._cap, self.iou_thresh,
@@ -323,12 +415,13 @@ class YieldEvaluator:
         return _yield_dict(gt, pred, (n_gt, n_match, 0, 0), self.smooth)
 
 
-def evaluate_yield(model, loader, num_classes=None, connectivity=2, min_area=0, iou_thresh=0.5, smooth=1e-6) -> dict:
+def evaluate_yield(model, loader, num_classes=None, connectivity=2, min_area=0, iou_thresh=0.5, smooth=1e-6, split=None) -> dict:
     """Yield estimation over `loader`'s (images, masks) batches: logits = model(images) under torch.no_grad() in eval mode, objects
-    labelled and matched on the device.  Returns yield_estimation_metrics' dictionary; the model's training flag is restored."""
+    labelled (and, with `split`, cut apart: see YieldEvaluator) and matched on the device.  Returns yield_estimation_metrics'
+    dictionary; the model's training flag is restored."""
     dev = next(model.parameters()).device
     C = int(num_classes if num_classes is not None else model.num_classes)
-    ev = YieldEvaluator(C, dev, connectivity=connectivity, min_area=min_area, iou_thresh=iou_thresh, smooth=smooth)
+    ev = YieldEvaluator(C, dev, connectivity=connectivity, min_area=min_area, iou_thresh=iou_thresh, smooth=smooth, split=split)
     was_training = model.training
     model.eval()
     try:
