@@ -493,6 +493,58 @@ int mgu_split_objects(mgu_ctx* ctx, const int32_t* labels_dev, int B, int H, int
                       int32_t* labels_out_dev, int64_t* counts_dev, int64_t* offsets_dev, int32_t* d2_out_dev, uint8_t* seeds_out_dev,
                       void* hip_stream);
 
+/* ---- instance evaluation: mask overlaps of two label maps, mask-IoU matching, panoptic totals ---------------------------------------
+ * The objects of both sides are what mgu_connected_components / mgu_split_objects (labels, offsets) and mgu_object_stats (class,
+ * area) write for the same B images: "gt" and "pred".  Object capacities are the lengths of the per-object arrays; an image whose
+ * objects pass one of them (offsets[b+1] > capacity) is skipped as a whole, as mgu_object_stats / mgu_match_objects skip it.
+ * Overlap table.  For every pair (GT object g, predicted object p) sharing at least one pixel, the number of shared pixels, in CSR
+ * form by predicted object, all indices batch-wide:
+ *   pair_ptr_dev    int64 (pred_capacity + 1): row p is [pair_ptr[p], pair_ptr[p+1]); every entry is written, rows of no object are
+ *                   empty, pair_ptr[pred_capacity] = the number of distinct pairs (the true prefix sums, also on overflow)
+ *   pair_gt_dev     int64 (pair_capacity): GT index, ASCENDING inside a row
+ *   pair_inter_dev  int64 (pair_capacity): pixels carrying both labels, >= 1
+ *   status_dev      int32 scalar, OR-ed (the caller clears it): 1 = more distinct pairs than pair_capacity -- entries whose place is
+ *                   >= pair_capacity are dropped, nothing is written past the arrays, and mgu_match_masks / mgu_panoptic_totals
+ *                   given the same pair_capacity read only what exists; 2 = an image was skipped (it contributes no pairs)
+ * Entries [0, min(pairs, pair_capacity)) of pair_gt / pair_inter are written.  Distinct pairs <= B*H*W, so pair_capacity = B*H*W
+ * never overflows; there is no dense n_gt x n_pred table.  Labels outside 1..n_b of their image read as background.  Every output
+ * word is a pure function of the inputs: counts are integer atomics and the order inside a row is a rank, so the result is bitwise
+ * repeatable.  Construction: an open-addressing hash table of 2*B*H*W + 64 slots keyed by (p << 32 | g) (64-bit compare-and-swap
+ * insert, integer add of pixel counts, combined over 4 pixels per lane and over runs of lanes inside a wave before the atomic), a
+ * scan of the row degrees, a pour into the rows and a rank pass.  6 kernel launches and 2 fills whatever the objects; no host
+ * synchronisation; scratch from the context, about 40 bytes per pixel plus 4 per pair_ptr entry.  B*H*W < 2^31, capacities < 2^31. */
+int mgu_object_overlaps(mgu_ctx* ctx, const int32_t* gt_labels_dev, const int64_t* gt_offsets_dev, int64_t gt_capacity,
+                        const int32_t* pred_labels_dev, const int64_t* pred_offsets_dev, int64_t pred_capacity, int B, int H, int W,
+                        int64_t pair_capacity, int64_t* pair_ptr_dev, int64_t* pair_gt_dev, int64_t* pair_inter_dev, int32_t* status_dev,
+                        void* hip_stream);
+/* The greedy matching of metrics.py:215-240 on MASK IoU, in confidence order, for T thresholds at once (1 <= T <= 16;
+ * thresholds_dev: T doubles on the device), every threshold with its own used flags as COCO evaluates.  Per image: the predictions
+ * are visited by descending scores_dev (fp32 as mgu_object_scores writes them; equal scores, -0 = +0 included: the smaller object
+ * index first; NaN last; scores_dev NULL: list order).  Each scans its row of the overlap table; candidates are the GT objects of
+ * its class not yet used at that threshold; IoU = (double)inter / (double)(area_p + area_g - inter), the fp64 expression of
+ * mgu_match_objects (= Python's int / int); the strictly larger IoU wins, an equal IoU goes to the smaller GT index; it is a match
+ * if IoU > 0 and IoU >= t.  One workgroup per image; 2 launches (1 without scores).
+ *   match_gt_dev   int64 (T, pred_capacity): the batch-wide GT index, or -1
+ *   match_iou_dev  double (T, pred_capacity): the matched IoU, else 0
+ *   totals_dev     int64 (T, 3) ACCUMULATED: [GT objects, predicted objects, matched], as mgu_match_objects accumulates
+ * Only the rows of the objects present (of images not skipped) are written.  Uses the context's object scratch (T bytes per GT
+ * capacity row, 4 per predicted one).  B <= 65535. */
+int mgu_match_masks(mgu_ctx* ctx, int B, const int64_t* pair_ptr_dev, const int64_t* pair_gt_dev, const int64_t* pair_inter_dev,
+                    int64_t pair_capacity, const int64_t* gt_offsets_dev, const int64_t* gt_class_dev, const int64_t* gt_area_dev,
+                    int64_t gt_capacity, const int64_t* pred_offsets_dev, const int64_t* pred_class_dev, const int64_t* pred_area_dev,
+                    int64_t pred_capacity, const float* scores_dev, const double* thresholds_dev, int T, int64_t* match_gt_dev,
+                    double* match_iou_dev, int64_t* totals_dev, void* hip_stream);
+/* The matching of panoptic quality on the same table: a pair is a true positive when the classes agree and
+ * 2 * inter > area_p + area_g - inter (IoU > 1/2, tested exactly in int64, strict).  That holds for at most one partner per object,
+ * so there is no order and no threshold.  pq_dev: uint64 (num_classes, 4) ACCUMULATED, row c = [TP, FP, FN, sum over the TP of
+ * round_half_even(IoU * 2^32)] with IoU the fp64 quotient above: an integer sum, exact and order-free (the trick of
+ * mgu_object_scores).  FP = predicted objects of class c - TP, FN = GT objects of class c - TP; objects whose class lies outside
+ * [0, num_classes) are ignored on both sides, images skipped for a capacity too.  One launch.  B <= 65535. */
+int mgu_panoptic_totals(mgu_ctx* ctx, int B, const int64_t* pair_ptr_dev, const int64_t* pair_gt_dev, const int64_t* pair_inter_dev,
+                        int64_t pair_capacity, const int64_t* gt_offsets_dev, const int64_t* gt_class_dev, const int64_t* gt_area_dev,
+                        int64_t gt_capacity, const int64_t* pred_offsets_dev, const int64_t* pred_class_dev, const int64_t* pred_area_dev,
+                        int64_t pred_capacity, int num_classes, uint64_t* pq_dev, void* hip_stream);
+
 /* ---- object shape: per-object moments, fitted ellipse and the per-instance form of EllipticalShapeLoss (model/unet/shape_loss.py
  *      :155-180 over the instances :42-48 and :85-92 ask for) straight from the label map: no dense masks, no per-object launches,
  *      no host synchronisation; the launch count does not depend on the number of objects ------------------------------------------
