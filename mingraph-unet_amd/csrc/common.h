@@ -49,6 +49,10 @@ struct Tuning {
                             // instead of the finishing pass of the convolution that writes it (WinoHead below; A/B and tests)
   bool wino_asm = true;     // MGU_WINO_ASM=0: the C++ component-pair kernels instead of their hand-scheduled assembly forms (wino_asm.hip; bitwise
                             // equal results)
+  int fwd_groups = 2;       // MGU_FWD_GROUPS: 2 (default) = the eval U-Net forward of a batch of >= 2 images as two half-batch walks, the
+                            // second on the context's side stream, so that one half's workgroups fill the CUs while the other half's
+                            // kernel drains and its next packet is handed over; 1 = the whole batch on the caller's stream
+                            // (mgu_unet_forward; bitwise equal results, profiles/forward_groups_ab.txt)
 };
 const Tuning& default_tuning();
 // The >64 KB dynamic-LDS opt-in is a per-DEVICE function attribute: set it once per (kernel, device).

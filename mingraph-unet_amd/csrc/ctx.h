@@ -131,6 +131,11 @@ struct mgu_ctx {
   std::vector<ProfRec> prec;
   int ev_used = 0;
   hipEvent_t ev_total[2] = {nullptr, nullptr};
+  // grouped eval forward (Tuning::fwd_groups): the second image group's stream and the fork / join events that order it against the
+  // caller's stream; created on first use
+  hipStream_t fwd_stream = nullptr;
+  hipEvent_t fwd_ev[2] = {nullptr, nullptr};
+  int panel_packs = 0;   // direct panels run_layer has packed on first use so far (a grouped forward orders its second group after one)
 };
 
 namespace mgud {

@@ -15,9 +15,14 @@ std::string g_create_err;
 namespace {
 
 struct WsPlan {
-  size_t xin, tmp, bott, total;
+  size_t xin, tmp, tmp_slice, bott, total;
   std::vector<size_t> pooled;
 };
+
+// Image groups of an eval forward (Tuning::fwd_groups): two once the batch has an image for each.  Group g walks images
+// [g * group_images, ...) of the batch.
+int fwd_groups(const mgu_ctx* c, int B) { return c->tn.fwd_groups >= 2 && B >= 2 ? 2 : 1; }
+int group_images(const mgu_ctx* c, int B) { return (B + fwd_groups(c, B) - 1) / fwd_groups(c, B); }
 
 WsPlan plan_ws(const mgu_ctx* c, int B, int H, int W) {
   std::vector<int> hs, wsz;
@@ -30,7 +35,11 @@ WsPlan plan_ws(const mgu_ctx* c, int B, int H, int W) {
   p.xin = k.take((size_t)B * H * W * c->Cp0 * es);
   size_t tmax = out(c->bott, c->bott.level);
   for (const Block& b : c->enc) tmax = std::max(tmax, out(b, b.level));
-  p.tmp = k.take(tmax * es);
+  // the conv1 temporary: one fixed slice per image group, each holding group_images images of the largest level (the groups are on
+  // different levels at the same time, so a region indexed by global image number with each level's geometry would overlap)
+  const int G = fwd_groups(c, B);
+  p.tmp_slice = (tmax / B * group_images(c, B) * es + 255) / 256 * 256;
+  p.tmp = k.take(G == 1 ? tmax * es : G * p.tmp_slice);
   for (const Block& b : c->enc) p.pooled.push_back(k.take(out(b, b.level + 1) * es));
   p.bott = k.take(out(c->bott, c->bott.level) * es);
   p.total = k.off;
@@ -107,6 +116,7 @@ int mgu_create(int device_id, mgu_ctx** out) {
   t.gat_fused = !flag("MGU_NO_GAT_FUSED");
   t.wino_asm = num("MGU_WINO_ASM", 1) > 0;
   t.head_fused = num("MGU_HEAD_FUSED", 1) > 0;
+  t.fwd_groups = num("MGU_FWD_GROUPS", t.fwd_groups) >= 2 ? 2 : 1;
   *out = c;
   return MGU_OK;
 }
@@ -134,6 +144,9 @@ void mgu_destroy(mgu_ctx* c) {
   for (auto e : c->ev) (void)hipEventDestroy(e);
   for (auto e : c->ev_total)
     if (e) (void)hipEventDestroy(e);
+  for (auto e : c->fwd_ev)
+    if (e) (void)hipEventDestroy(e);
+  if (c->fwd_stream) (void)hipStreamDestroy(c->fwd_stream);
   delete c;
 }
 
@@ -435,6 +448,7 @@ int mgud::run_layer(mgu_ctx* c, const Layer& L, const void* in_v, int ldin, int 
     HIPCHK(c, launch_pack_one(L.convt ? pack_convt_panel(L.w_src, L.wp, c->dtype, L.Cin, L.Cout, L.Kp)
                                       : pack_conv_panel(L.w_src, L.wp, c->dtype, L.Cout, L.Cin, L.Cp, L.KS, L.Kp), s));
     L.wp_dirty = false;
+    ++c->panel_packs;
   }
   // profiling record: algorithmic 2*MAC of the operator and what the matrix pipe really issues
   double alg = L.convt ? 2.0 * d.M * (double)L.Cin * L.Cout * 4.0 : 2.0 * d.M * (double)L.KS * L.KS * L.Cin * L.Cout;
@@ -501,7 +515,6 @@ int mgu_unet_forward(mgu_ctx* c, const void* x_dev, int B, int H, int W, int64_t
   char* ws = (char*)c->ws;
   const size_t es = c->dtype == MGU_DTYPE_BF16 ? 2 : 4;
   void* xin = ws + plan.xin;
-  void* tmp = ws + plan.tmp;
   void* bott = ws + plan.bott;
   std::vector<int> hs, wsz;
   level_dims(H, W, depth, hs, wsz);
@@ -525,45 +538,86 @@ int mgu_unet_forward(mgu_ctx* c, const void* x_dev, int B, int H, int W, int64_t
                             (int64_t)B * H * W < (1ll << 31);
   if (!first_direct) HIPCHK(c, launch_pack_input((const float*)x_dev, xin, c->dtype, B, c->in_ch, c->Cp0, H, W, xs_n, xs_c, xs_h, xs_w, s));
 
-  const void* cur = xin;
-  int cur_ld = c->Cp0;
-  for (const Block& b : c->enc) {  // encoder, unet_encoder.py:67-70
-    const int i = b.level, C = c->layers[b.conv1].Cout;
-    if (&b == &c->enc.front() && first_direct) {
-      if (c->fold_dirty) return fail(c, MGU_ERR_STATE, "internal: eval scale/shift not folded");
-      const double alg = 2.0 * B * H * W * 9.0 * L0.Cin * L0.Cout;
-      ProfScope ps(c, s, "conv3x3_first_mfma_kernel", alg, 2.0 * B * H * W * 32.0 * 32.0 * (c->dtype == MGU_DTYPE_F32 ? 6.0 : 3.0), 1);
-      HIPCHK(c, launch_first_mfma_direct(c->dtype, (const float*)x_dev, xs_n, xs_c, xs_h, xs_w, c->in_ch, L0.wfm, L0.bn.empty() ? nullptr : L0.scale,
-                                         L0.shift, tmp, B, H, W, C, 0, 1, s));
-    } else if ((rc = run_conv(c, c->layers[b.conv1], cur, cur_ld, B, hs[i], wsz[i], tmp, C, 0, 1, 0, 0, s))) return rc;
-    void* pooled = ws + plan.pooled[i];
-    bool fused = false;   // MaxPool2d(2) (unet_encoder.py:48) rides in the conv2 epilogue on the Winograd path
-    if ((rc = run_conv(c, c->layers[b.conv2], tmp, C, B, hs[i], wsz[i], cat_dev[i], 2 * C, 0, 1, 0, 0, s, pooled, C, &fused))) return rc;
-    if (!fused) HIPCHK(c, launch_maxpool2(cat_dev[i], 2 * C, pooled, c->dtype, B, hs[i], wsz[i], C, s));
-    cur = pooled;
-    cur_ld = C;
+  // One image group's walk of the network: images [img0, img0 + nb) on stream gs, the shared conv1 temporary in the group's own
+  // slice `tmp` (images indexed locally).  Every other buffer is dedicated to its level and batch-major, so the group starts at its
+  // first image; the head-fused launch gets the group's part of the logits and of the row-pair partial sums.
+  auto walk = [&](hipStream_t gs, int img0, int nb, void* tmp, bool* head_done) -> int {
+    auto at = [&](const void* base, int level, int ch) { return (char*)base + (size_t)img0 * hs[level] * wsz[level] * ch * es; };
+    WinoHead head = head_args;
+    if (head_wanted) {
+      head.logits += (size_t)img0 * H * W * c->ncls;
+      head.psum = (float*)((char*)head.psum + wino_head_psum_bytes(img0, H, W));
+      head.psum_bytes = (int)wino_head_psum_bytes(nb, H, W);
+    }
+    const void* cur = at(xin, 0, c->Cp0);
+    int cur_ld = c->Cp0;
+    for (const Block& b : c->enc) {  // encoder, unet_encoder.py:67-70
+      const int i = b.level, C = c->layers[b.conv1].Cout;
+      if (&b == &c->enc.front() && first_direct) {
+        if (c->fold_dirty) return fail(c, MGU_ERR_STATE, "internal: eval scale/shift not folded");
+        const double alg = 2.0 * nb * H * W * 9.0 * L0.Cin * L0.Cout;
+        ProfScope ps(c, gs, "conv3x3_first_mfma_kernel", alg, 2.0 * nb * H * W * 32.0 * 32.0 * (c->dtype == MGU_DTYPE_F32 ? 6.0 : 3.0), 1);
+        HIPCHK(c, launch_first_mfma_direct(c->dtype, (const float*)x_dev + (int64_t)img0 * xs_n, xs_n, xs_c, xs_h, xs_w, c->in_ch, L0.wfm,
+                                           L0.bn.empty() ? nullptr : L0.scale, L0.shift, tmp, nb, H, W, C, 0, 1, gs));
+      } else if ((rc = run_conv(c, c->layers[b.conv1], cur, cur_ld, nb, hs[i], wsz[i], tmp, C, 0, 1, 0, 0, gs))) return rc;
+      void* pooled = at(ws + plan.pooled[i], i + 1, C);
+      bool fused = false;   // MaxPool2d(2) (unet_encoder.py:48) rides in the conv2 epilogue on the Winograd path
+      if ((rc = run_conv(c, c->layers[b.conv2], tmp, C, nb, hs[i], wsz[i], at(cat_dev[i], i, 2 * C), 2 * C, 0, 1, 0, 0, gs, pooled, C, &fused)))
+        return rc;
+      if (!fused) HIPCHK(c, launch_maxpool2(at(cat_dev[i], i, 2 * C), 2 * C, pooled, c->dtype, nb, hs[i], wsz[i], C, gs));
+      cur = pooled;
+      cur_ld = C;
+    }
+    {  // bottleneck, :72
+      const Block& b = c->bott;
+      const int i = b.level, C = c->layers[b.conv1].Cout;
+      if ((rc = run_conv(c, c->layers[b.conv1], cur, cur_ld, nb, hs[i], wsz[i], tmp, C, 0, 1, 0, 0, gs))) return rc;
+      if ((rc = run_conv(c, c->layers[b.conv2], tmp, C, nb, hs[i], wsz[i], at(bott, i, C), C, 0, 1, 0, 0, gs))) return rc;
+      cur = at(bott, i, C);
+      cur_ld = C;
+    }
+    for (const Block& b : c->dec) {  // decoder, unet_decoder.py:139-141
+      const int i = b.level, C = c->layers[b.conv1].Cout;
+      const bool last = head_wanted && i == 0;
+      // ConvTranspose2d(k2,s2) -> pixel-shuffle store into channels [C, 2C) of the concat buffer (:36,:53)
+      if ((rc = run_conv(c, c->layers[b.up], cur, cur_ld, nb, hs[i + 1], wsz[i + 1], at(cat_dev[i], i, 2 * C), 2 * C, C, 0, hs[i], wsz[i], gs)))
+        return rc;
+      if ((rc = run_conv(c, c->layers[b.conv1], at(cat_dev[i], i, 2 * C), 2 * C, nb, hs[i], wsz[i], tmp, C, 0, 1, 0, 0, gs))) return rc;
+      if ((rc = run_conv(c, c->layers[b.conv2], tmp, C, nb, hs[i], wsz[i], at(feat_dev[i], i, C), C, 0, 1, 0, 0, gs, nullptr, 0, nullptr,
+                         last ? &head : nullptr, last ? head_done : nullptr)))
+        return rc;
+      cur = at(feat_dev[i], i, C);
+      cur_ld = C;
+    }
+    return MGU_OK;
+  };
+  // Two image groups (Tuning::fwd_groups): group 0 on the caller's stream, group 1 on the side stream between a fork and a join event,
+  // so that everything before and after this call on the caller's stream stays ordered against both.  With profiling on the batch
+  // walks as one group: event pairs around overlapped launches would charge a kernel for the time it waits for CUs.
+  const int G = c->prof ? 1 : fwd_groups(c, B);
+  if (G == 1) {
+    if ((rc = walk(s, 0, B, ws + plan.tmp, &head_done))) return rc;
+  } else {
+    if (!c->fwd_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->fwd_stream, hipStreamNonBlocking));
+    for (auto& e : c->fwd_ev)
+      if (!e) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    const int n0 = group_images(c, B), packs = c->panel_packs;
+    bool done1 = false;
+    HIPCHK(c, hipEventRecord(c->fwd_ev[0], s));
+    HIPCHK(c, hipStreamWaitEvent(c->fwd_stream, c->fwd_ev[0], 0));
+    rc = walk(s, 0, n0, ws + plan.tmp, &head_done);
+    if (rc == MGU_OK && c->panel_packs != packs) {   // group 0 built a direct panel on first use: group 1 reads it too
+      HIPCHK(c, hipEventRecord(c->fwd_ev[0], s));
+      HIPCHK(c, hipStreamWaitEvent(c->fwd_stream, c->fwd_ev[0], 0));
+    }
+    const int rc1 = rc == MGU_OK ? walk(c->fwd_stream, n0, B - n0, ws + plan.tmp + plan.tmp_slice, &done1) : MGU_OK;
+    HIPCHK(c, hipEventRecord(c->fwd_ev[1], c->fwd_stream));   // the join also closes a walk that failed half-way
+    HIPCHK(c, hipStreamWaitEvent(s, c->fwd_ev[1], 0));
+    if (rc || rc1) return rc ? rc : rc1;
+    if (done1 != head_done) return fail(c, MGU_ERR_STATE, "internal: the image groups disagree on the head-fused kernel");
   }
-  {  // bottleneck, :72
-    const Block& b = c->bott;
-    const int i = b.level, C = c->layers[b.conv1].Cout;
-    if ((rc = run_conv(c, c->layers[b.conv1], cur, cur_ld, B, hs[i], wsz[i], tmp, C, 0, 1, 0, 0, s))) return rc;
-    if ((rc = run_conv(c, c->layers[b.conv2], tmp, C, B, hs[i], wsz[i], bott, C, 0, 1, 0, 0, s))) return rc;
-    cur = bott;
-    cur_ld = C;
-  }
-  for (const Block& b : c->dec) {  // decoder, unet_decoder.py:139-141
-    const int i = b.level, C = c->layers[b.conv1].Cout;
-    const bool last = head_wanted && i == 0;
-    // ConvTranspose2d(k2,s2) -> pixel-shuffle store into channels [C, 2C) of the concat buffer (:36,:53)
-    if ((rc = run_conv(c, c->layers[b.up], cur, cur_ld, B, hs[i + 1], wsz[i + 1], cat_dev[i], 2 * C, C, 0, hs[i], wsz[i], s)))
-      return rc;
-    if ((rc = run_conv(c, c->layers[b.conv1], cat_dev[i], 2 * C, B, hs[i], wsz[i], tmp, C, 0, 1, 0, 0, s))) return rc;
-    if ((rc = run_conv(c, c->layers[b.conv2], tmp, C, B, hs[i], wsz[i], feat_dev[i], C, 0, 1, 0, 0, s, nullptr, 0, nullptr,
-                       last ? &head_args : nullptr, last ? &head_done : nullptr)))
-      return rc;
-    cur = feat_dev[i];
-    cur_ld = C;
-  }
+  const void* cur = feat_dev[0];
+  const int cur_ld = c->layers[c->dec.back().conv1].Cout;
   // final 1x1 conv (:143): a few output channels -> HBM-bound head kernel reading the reference's (ncls, C) weight
   {
     const int pm_dtype = c->dtype;   // decoder features are stored in the compute dtype
