@@ -320,7 +320,8 @@ int gat_prologue(mgu_ctx* c, const float* X, int N, int Fin, const float* panel,
 // the 8-connected same-value component of g in an int32 map (B, H, W), -1 where the map is 0.  cc_number_roots: given P with every
 // foreground pixel pointing (directly or through a chain) at its object's first pixel, the tail of mgu_connected_components: objects
 // numbered per image in raster order of that pixel, the min_area filter (area: n counters, or nullptr with min_area 0), counts and
-// offsets.  cnt: cc_chunks(HW) * B ints, choff: as many int64.
+// offsets.  cnt: cc_chunks(HW) * B ints, choff: as many int64.  (The device and host helpers the object-level files share beyond
+// these two entry points are in objects_common.h.)
 int64_t cc_chunks(int64_t HW);
 int cc_roots_i32(mgu_ctx* c, const int32_t* map, int B, int H, int W, int* P, hipStream_t s);
 int cc_number_roots(mgu_ctx* c, int* P, unsigned* area, int min_area, int B, int64_t HW, int* cnt, long long* choff, int32_t* labels,

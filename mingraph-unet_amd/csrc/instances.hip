@@ -14,7 +14,7 @@
 // holds 4 consecutive pixels (one 16-byte load per map) and folds equal neighbours in registers; lanes whose 4 pixels all carry one
 // pair form runs inside the wave (ballot arithmetic) and only a run's first lane issues one add of the run's pixel count.  The keys
 // are batch-wide object indices, which differ between images, so a run never joins pixels of two images.
-#include "ctx.h"
+#include "objects_common.h"
 
 namespace mgu {
 namespace {
@@ -22,8 +22,6 @@ namespace {
 constexpr int IN_THREADS = 256;
 constexpr int PIXG = 4;                         // pixels per lane in the counting pass
 constexpr int ROWCHUNK = 4 * IN_THREADS;        // degree scan: 1024 consecutive rows per workgroup
-constexpr int SCAN_THREADS = 1024;
-constexpr int LEADER_ROUNDS = 4;                // distinct classes summed per wave before the rest add directly
 constexpr unsigned long long EMPTY = ~0ull;     // a free slot; no pair has this key (both indices stay below 2^31)
 
 struct PairTable {
@@ -122,24 +120,6 @@ __global__ __launch_bounds__(IN_THREADS) void overlap_count_kernel(const int* __
   }
 }
 
-// exclusive prefix sum over a 256-thread workgroup; *total gets the sum (sh: 4 ints)
-__device__ __forceinline__ int block_exclusive_scan(int v, int* sh, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int u = __shfl_up(inc, off);
-    if (lane >= off) inc += u;
-  }
-  if (lane == 63) sh[wave] = inc;
-  __syncthreads();
-  int before = 0;
-  for (int w = 0; w < wave; ++w) before += sh[w];
-  *total = sh[0] + sh[1] + sh[2] + sh[3];
-  __syncthreads();
-  return before + inc - v;
-}
-
 // (2a) degrees per chunk of ROWCHUNK rows; rows past the table's (no object can have them) have degree 0
 __global__ __launch_bounds__(IN_THREADS) void degree_count_kernel(const int* __restrict__ deg, int64_t rows, int* __restrict__ csum) {
   __shared__ int sh[4];
@@ -157,31 +137,14 @@ __global__ __launch_bounds__(SCAN_THREADS) void degree_scan_kernel(const int* __
                                                                    long long* __restrict__ total_out, int64_t pair_cap, int B,
                                                                    const long long* __restrict__ goff, const long long* __restrict__ poff,
                                                                    int64_t gcap, int64_t pcap, int* __restrict__ status) {
-  __shared__ long long sh[SCAN_THREADS];
   const int tid = threadIdx.x;
-  const int64_t seg = (nch + SCAN_THREADS - 1) / SCAN_THREADS;
-  const int64_t k0 = tid * seg < nch ? tid * seg : nch, k1 = k0 + seg < nch ? k0 + seg : nch;
-  long long s = 0;
-  for (int64_t k = k0; k < k1; ++k) s += csum[k];
-  sh[tid] = s;
-  __syncthreads();
-  for (int off = 1; off < SCAN_THREADS; off <<= 1) {   // inclusive Hillis-Steele over the segment sums
-    const long long u = tid >= off ? sh[tid - off] : 0;
-    __syncthreads();
-    sh[tid] += u;
-    __syncthreads();
-  }
-  long long run = sh[tid] - s;
-  for (int64_t k = k0; k < k1; ++k) {
-    choff[k] = run;
-    run += csum[k];
-  }
+  const long long pairs = chunk_sum_scan(csum, nch, choff);
   int bits = 0;
   for (int b = tid; b < B; b += SCAN_THREADS)
     if (goff[b + 1] > gcap || poff[b + 1] > pcap) bits |= 2;
   if (tid == SCAN_THREADS - 1) {
-    *total_out = sh[tid];
-    if (sh[tid] > pair_cap) bits |= 1;
+    *total_out = pairs;
+    if (pairs > pair_cap) bits |= 1;
   }
   if (bits) atomicOr(status, bits);
 }
@@ -305,33 +268,23 @@ __global__ __launch_bounds__(64) void mask_match_kernel(const long long* __restr
 }
 
 // ---- panoptic quality ------------------------------------------------------------------------------------------------------------
-// add one record per lane to pq[cls] (cls < 0: none): the lanes of one class are summed inside the wave, up to LEADER_ROUNDS classes
+// add one record per lane to pq[cls] (cls < 0: none): the lanes of one class are summed inside the wave (wave_by_key)
 __device__ __forceinline__ void class_add(unsigned long long* pq, long long cls, unsigned long long v0, unsigned long long v1,
                                           unsigned long long v2, unsigned long long v3) {
-  const int lane = threadIdx.x & 63;
-  bool pending = cls >= 0;
-  for (int it = 0; it < LEADER_ROUNDS; ++it) {
-    const unsigned long long act = __ballot(pending);
-    if (!act) break;
-    const int leader = __ffsll((long long)act) - 1;
-    const long long lc = __shfl(cls, leader);
-    const bool mine = pending && cls == lc;
-    const unsigned long long s0 = wave_sum<unsigned long long>(mine ? v0 : 0ull), s1 = wave_sum<unsigned long long>(mine ? v1 : 0ull);
-    const unsigned long long s2 = wave_sum<unsigned long long>(mine ? v2 : 0ull), s3 = wave_sum<unsigned long long>(mine ? v3 : 0ull);
-    if (lane == leader) {
-      if (s0) atomicAdd(&pq[4 * lc], s0);
-      if (s1) atomicAdd(&pq[4 * lc + 1], s1);
-      if (s2) atomicAdd(&pq[4 * lc + 2], s2);
-      if (s3) atomicAdd(&pq[4 * lc + 3], s3);
-    }
-    if (mine) pending = false;
-  }
-  if (pending) {
-    if (v0) atomicAdd(&pq[4 * cls], v0);
-    if (v1) atomicAdd(&pq[4 * cls + 1], v1);
-    if (v2) atomicAdd(&pq[4 * cls + 2], v2);
-    if (v3) atomicAdd(&pq[4 * cls + 3], v3);
-  }
+  auto add = [=](long long k, unsigned long long s0, unsigned long long s1, unsigned long long s2, unsigned long long s3) {
+    if (s0) atomicAdd(&pq[4 * k], s0);
+    if (s1) atomicAdd(&pq[4 * k + 1], s1);
+    if (s2) atomicAdd(&pq[4 * k + 2], s2);
+    if (s3) atomicAdd(&pq[4 * k + 3], s3);
+  };
+  wave_by_key(
+      cls,
+      [=](long long lc, bool mine, bool lead) {
+        const unsigned long long s0 = wave_sum<unsigned long long>(mine ? v0 : 0ull), s1 = wave_sum<unsigned long long>(mine ? v1 : 0ull);
+        const unsigned long long s2 = wave_sum<unsigned long long>(mine ? v2 : 0ull), s3 = wave_sum<unsigned long long>(mine ? v3 : 0ull);
+        if (lead) add(lc, s0, s1, s2, s3);
+      },
+      [=] { add(cls, v0, v1, v2, v3); });
 }
 
 // grid (x, images): thread i of an image takes its i-th predicted object (TP with its IoU, or FP) and its i-th GT object (one FN;
@@ -389,7 +342,7 @@ int mgu_object_overlaps(mgu_ctx* c, const int32_t* gt_labels_dev, const int64_t*
       gt_capacity < 0 || pred_capacity < 0 || pair_capacity < 0)
     return fail(c, MGU_ERR_INVALID, "bad object_overlaps args (null pointer or negative size)");
   if (pair_capacity > 0 && (!pair_gt_dev || !pair_inter_dev)) return fail(c, MGU_ERR_INVALID, "object_overlaps: pair arrays are needed for a nonzero pair_capacity");
-  if ((double)B * H * W >= 2147483647.0) return fail(c, MGU_ERR_INVALID, "object_overlaps: B*H*W must stay below 2^31");
+  if (int rc = check_pixel_count(c, "object_overlaps", B, H, W)) return rc;
   if (pred_capacity >= 2147483647ll || gt_capacity >= 2147483647ll) return fail(c, MGU_ERR_INVALID, "object_overlaps: capacities must stay below 2^31");
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)hip_stream;
@@ -415,7 +368,7 @@ int mgu_object_overlaps(mgu_ctx* c, const int32_t* gt_labels_dev, const int64_t*
   HIPCHK(c, hipMemsetAsync(t.keys, 0xFF, (size_t)t.slots * 8, s));
   HIPCHK(c, hipMemsetAsync(t.cnt, 0, zero_bytes, s));
   if (n > 0) {
-    const unsigned blocks = (unsigned)((n + (int64_t)IN_THREADS * PIXG - 1) / ((int64_t)IN_THREADS * PIXG));
+    const unsigned blocks = grid_for(n, IN_THREADS * PIXG, INT_MAX);
     const bool vec = (((uintptr_t)gt_labels_dev | (uintptr_t)pred_labels_dev) & 15) == 0;
     if (vec)
       hipLaunchKernelGGL(overlap_count_kernel<true>, dim3(blocks), dim3(IN_THREADS), 0, s, gt_labels_dev, pred_labels_dev, n, HW, goff, poff,
@@ -428,9 +381,9 @@ int mgu_object_overlaps(mgu_ctx* c, const int32_t* gt_labels_dev, const int64_t*
   hipLaunchKernelGGL(degree_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, s, csum, nch, choff, total, pair_capacity, B, goff, poff, gt_capacity,
                      pred_capacity, (int*)status_dev);
   hipLaunchKernelGGL(degree_write_kernel, dim3((unsigned)nch), dim3(IN_THREADS), 0, s, t.deg, t.rows, nptr, choff, (long long*)pair_ptr_dev);
-  const unsigned slotblocks = (unsigned)std::min<int64_t>(4096, ((int64_t)t.slots + IN_THREADS - 1) / IN_THREADS);
+  const unsigned slotblocks = grid_for(t.slots, IN_THREADS, 4096);
   hipLaunchKernelGGL(pair_pour_kernel, dim3(slotblocks), dim3(IN_THREADS), 0, s, t, (const long long*)pair_ptr_dev, tp, tg, tc);
-  const unsigned pairblocks = (unsigned)std::min<int64_t>(4096, (n + IN_THREADS) / IN_THREADS);
+  const unsigned pairblocks = grid_for(n + 1, IN_THREADS, 4096);   // the pairs are counted on the device: at most n
   hipLaunchKernelGGL(pair_place_kernel, dim3(pairblocks), dim3(IN_THREADS), 0, s, total, (const long long*)pair_ptr_dev, tp, tg, tc, pair_capacity,
                      (long long*)pair_gt_dev, (long long*)pair_inter_dev);
   HIPCHK(c, hipGetLastError());

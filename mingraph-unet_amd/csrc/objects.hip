@@ -11,10 +11,9 @@
 // whatever order the atomics land in, the trees' roots, and so the numbering, are the same -- the labels are deterministic.
 // All accumulations are integer atomics (exact, order-free); runs of equal labels are summed inside a wave before the atomic.
 // split.hip labels its int32 zone map through steps (1)-(3) (cc_roots_i32) and numbers its own objects through (3)-(4)
-// (cc_number_roots, the tail of mgu_connected_components); both are declared in ctx.h.
-#include <climits>
-
-#include "ctx.h"
+// (cc_number_roots, the tail of mgu_connected_components); both are declared in ctx.h.  The wave pre-aggregation (wave_by_key), the
+// scans and the pixel -> object rule are objects_common.h's, shared with shapes.hip and instances.hip.
+#include "objects_common.h"
 
 namespace mgu {
 namespace {
@@ -23,8 +22,6 @@ constexpr int OB_THREADS = 256;
 constexpr int TILE = 32;                      // labelling tile: TILE x TILE pixels, 4 per thread
 constexpr int TILE_PIX = TILE * TILE;
 constexpr int CHUNK = 4 * OB_THREADS;         // root numbering: 1024 consecutive pixels of one image per workgroup
-constexpr int SCAN_THREADS = 1024;
-constexpr int LEADER_ROUNDS = 4;              // wave pre-aggregation: distinct labels summed per wave before the rest go direct
 
 // value of pixel g: the class map's entry (KIND 0 int64; 2 int32, the internal form of split.hip's zone map), or the first maximal
 // class of the logits (KIND 1, bit-identical to argmax_kernel)
@@ -159,41 +156,17 @@ __global__ __launch_bounds__(OB_THREADS) void cc_flatten_kernel(int* __restrict_
     P[g] = r;
   }
   if (!area) return;
-  const int lane = threadIdx.x & 63;
-  bool pending = r >= 0;
-  for (int it = 0; it < LEADER_ROUNDS; ++it) {
-    const unsigned long long act = __ballot(pending);
-    if (!act) break;
-    const int leader = __ffsll((long long)act) - 1;
-    const int lr = __shfl(r, leader);
-    const bool mine = pending && r == lr;
-    const unsigned long long m = __ballot(mine);
-    if (lane == leader) atomicAdd(&area[lr], (unsigned)__popcll(m));
-    if (mine) pending = false;
-  }
-  if (pending) atomicAdd(&area[r], 1u);
+  wave_by_key(
+      r,
+      [=](int lr, bool mine, bool lead) {
+        const unsigned long long m = __ballot(mine);
+        if (lead) atomicAdd(&area[lr], (unsigned)__popcll(m));
+      },
+      [=] { atomicAdd(&area[r], 1u); });
 }
 
 __device__ __forceinline__ bool is_root(const int* P, const unsigned* area, int min_area, int64_t g) {
   return P[g] == (int)g && (!area || area[g] >= (unsigned)min_area);
-}
-
-// exclusive prefix sum over a 256-thread workgroup; *total gets the sum (sh: 4 ints)
-__device__ __forceinline__ int block_exclusive_scan(int v, int* sh, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int u = __shfl_up(inc, off);
-    if (lane >= off) inc += u;
-  }
-  if (lane == 63) sh[wave] = inc;
-  __syncthreads();
-  int before = 0;
-  for (int w = 0; w < wave; ++w) before += sh[w];
-  *total = sh[0] + sh[1] + sh[2] + sh[3];
-  __syncthreads();
-  return before + inc - v;
 }
 
 // (4a) roots per chunk of CHUNK consecutive pixels of one image (grid: chunks x images)
@@ -213,29 +186,13 @@ __global__ __launch_bounds__(OB_THREADS) void cc_count_kernel(const int* __restr
 // and offsets (the first object of image b is offsets[b]; offsets[B] = all objects of the batch)
 __global__ __launch_bounds__(SCAN_THREADS) void cc_scan_kernel(const int* __restrict__ cnt, int64_t nch, int B, long long* __restrict__ choff,
                                                                long long* __restrict__ counts, long long* __restrict__ offsets) {
-  __shared__ long long sh[SCAN_THREADS];
-  const int tid = threadIdx.x;
-  const int64_t total = nch * B, seg = (total + SCAN_THREADS - 1) / SCAN_THREADS;
-  const int64_t k0 = tid * seg < total ? tid * seg : total, k1 = k0 + seg < total ? k0 + seg : total;
-  long long s = 0;
-  for (int64_t k = k0; k < k1; ++k) s += cnt[k];
-  sh[tid] = s;
+  const long long all = chunk_sum_scan(cnt, nch * B, choff);
   __syncthreads();
-  for (int off = 1; off < SCAN_THREADS; off <<= 1) {   // inclusive Hillis-Steele over the segment sums
-    const long long u = tid >= off ? sh[tid - off] : 0;
-    __syncthreads();
-    sh[tid] += u;
-    __syncthreads();
+  for (int b = threadIdx.x; b <= B; b += SCAN_THREADS) {   // image b starts at its first chunk
+    const long long first = b < B ? choff[b * nch] : all;
+    offsets[b] = first;
+    if (b < B) counts[b] = (b + 1 < B ? choff[(b + 1) * nch] : all) - first;
   }
-  long long run = sh[tid] - s;
-  for (int64_t k = k0; k < k1; ++k) {
-    choff[k] = run;
-    if (k % nch == 0) offsets[k / nch] = run;
-    run += cnt[k];
-  }
-  if (tid == SCAN_THREADS - 1) offsets[B] = sh[tid];
-  __syncthreads();
-  for (int b = tid; b < B; b += SCAN_THREADS) counts[b] = (b + 1 < B ? offsets[b + 1] : sh[SCAN_THREADS - 1]) - offsets[b];
 }
 
 // (4c) number the roots of a chunk in raster order: label = object index - offsets[b] + 1, written at the root pixel
@@ -280,7 +237,7 @@ __global__ __launch_bounds__(OB_THREADS) void cc_relabel_kernel(const int* __res
 // ---- per-object statistics -------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(OB_THREADS) void stats_init_kernel(const long long* __restrict__ offsets, int B, int64_t cap, long long* __restrict__ area,
                                                                 int* __restrict__ bbox, long long* __restrict__ sums) {
-  const int64_t n = offsets[B] < cap ? offsets[B] : cap;
+  const int64_t n = objects_recorded(offsets, B, cap);
   for (int64_t i = (int64_t)blockIdx.x * OB_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * OB_THREADS) {
     if (area) area[i] = 0;
     bbox[4 * i] = INT_MAX, bbox[4 * i + 1] = INT_MAX, bbox[4 * i + 2] = 0, bbox[4 * i + 3] = 0;
@@ -288,57 +245,46 @@ __global__ __launch_bounds__(OB_THREADS) void stats_init_kernel(const long long*
   }
 }
 
-// one thread per pixel; the lanes of one object are summed inside the wave (up to LEADER_ROUNDS objects), the rest add directly
+// one thread per pixel; the lanes of one object are summed inside the wave (wave_by_key), the rest add directly
 template <int KIND>
 __global__ __launch_bounds__(OB_THREADS) void stats_kernel(const int* __restrict__ labels, const void* __restrict__ src, int C, int W, int64_t HW,
                                                            int64_t n, const long long* __restrict__ offsets, int64_t cap,
                                                            long long* __restrict__ cls, long long* __restrict__ area, int* __restrict__ bbox,
                                                            long long* __restrict__ sums) {
   const int64_t g = (int64_t)blockIdx.x * OB_THREADS + threadIdx.x;
-  const int lane = threadIdx.x & 63;
   long long obj = -1;
   int x = 0, y = 0;
   if (g < n) {
     const int lab = labels[g];
     const int64_t b = g / HW, i = g - b * HW;
     y = (int)(i / W), x = (int)(i - (int64_t)y * W);
-    if (lab > 0) obj = offsets[b] + lab - 1;
-    if (obj >= cap) obj = -1;
+    obj = object_index(lab, offsets, b, cap);
   }
-  bool pending = obj >= 0;
-  for (int it = 0; it < LEADER_ROUNDS; ++it) {
-    const unsigned long long act = __ballot(pending);
-    if (!act) break;
-    const int leader = __ffsll((long long)act) - 1;
-    const long long lo = __shfl(obj, leader);
-    const bool mine = pending && obj == lo;
-    const int x0 = wave_min(mine ? x : INT_MAX), y0 = wave_min(mine ? y : INT_MAX);
-    const int x1 = wave_max(mine ? x + 1 : 0), y1 = wave_max(mine ? y + 1 : 0);
-    unsigned long long sx = 0, sy = 0;
-    if (sums) sx = wave_sum<unsigned long long>(mine ? x : 0), sy = wave_sum<unsigned long long>(mine ? y : 0);
-    const int cnt = __popcll(__ballot(mine));
-    if (lane == leader) {
-      cls[lo] = pix_key<KIND>(src, g, C);   // every pixel of an object holds its class: a plain store
-      if (area) atomicAdd((unsigned long long*)&area[lo], (unsigned long long)cnt);
-      atomicMin(&bbox[4 * lo], x0), atomicMin(&bbox[4 * lo + 1], y0);
-      atomicMax(&bbox[4 * lo + 2], x1), atomicMax(&bbox[4 * lo + 3], y1);
-      if (sums) atomicAdd((unsigned long long*)&sums[2 * lo], sx), atomicAdd((unsigned long long*)&sums[2 * lo + 1], sy);
-    }
-    if (mine) pending = false;
-  }
-  if (pending) {
-    cls[obj] = pix_key<KIND>(src, g, C);
-    if (area) atomicAdd((unsigned long long*)&area[obj], 1ull);
-    atomicMin(&bbox[4 * obj], x), atomicMin(&bbox[4 * obj + 1], y);
-    atomicMax(&bbox[4 * obj + 2], x + 1), atomicMax(&bbox[4 * obj + 3], y + 1);
-    if (sums) atomicAdd((unsigned long long*)&sums[2 * obj], (unsigned long long)x), atomicAdd((unsigned long long*)&sums[2 * obj + 1], (unsigned long long)y);
-  }
+  // one object's record: its class (every pixel of an object holds it: a plain store), pixel count, bbox corners, coordinate sums
+  auto add = [=](long long o, unsigned long long cnt, int x0, int y0, int x1, int y1, unsigned long long sx, unsigned long long sy) {
+    cls[o] = pix_key<KIND>(src, g, C);
+    if (area) atomicAdd((unsigned long long*)&area[o], cnt);
+    atomicMin(&bbox[4 * o], x0), atomicMin(&bbox[4 * o + 1], y0);
+    atomicMax(&bbox[4 * o + 2], x1), atomicMax(&bbox[4 * o + 3], y1);
+    if (sums) atomicAdd((unsigned long long*)&sums[2 * o], sx), atomicAdd((unsigned long long*)&sums[2 * o + 1], sy);
+  };
+  wave_by_key(
+      obj,
+      [=](long long lo, bool mine, bool lead) {
+        const int x0 = wave_min(mine ? x : INT_MAX), y0 = wave_min(mine ? y : INT_MAX);
+        const int x1 = wave_max(mine ? x + 1 : 0), y1 = wave_max(mine ? y + 1 : 0);
+        unsigned long long sx = 0, sy = 0;
+        if (sums) sx = wave_sum<unsigned long long>(mine ? x : 0), sy = wave_sum<unsigned long long>(mine ? y : 0);
+        const int cnt = __popcll(__ballot(mine));
+        if (lead) add(lo, (unsigned long long)cnt, x0, y0, x1, y1, sx, sy);
+      },
+      [=] { add(obj, 1ull, x, y, x + 1, y + 1, (unsigned long long)x, (unsigned long long)y); });
 }
 
 // ---- per-object confidence: mean probability of the object's class over its pixels ----------------------------------------------
 __global__ __launch_bounds__(OB_THREADS) void scores_init_kernel(const long long* __restrict__ offsets, int B, int64_t cap,
                                                                  unsigned long long* __restrict__ acc) {
-  const int64_t n = offsets[B] < cap ? offsets[B] : cap;
+  const int64_t n = objects_recorded(offsets, B, cap);
   for (int64_t i = (int64_t)blockIdx.x * OB_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * OB_THREADS) acc[i] = 0;
 }
 
@@ -348,39 +294,30 @@ __global__ __launch_bounds__(OB_THREADS) void scores_kernel(const int* __restric
                                                             int64_t n, const long long* __restrict__ offsets, int64_t cap,
                                                             const long long* __restrict__ cls, unsigned long long* __restrict__ acc) {
   const int64_t g = (int64_t)blockIdx.x * OB_THREADS + threadIdx.x;
-  const int lane = threadIdx.x & 63;
   long long obj = -1;
   unsigned long long q = 0;
   if (g < n) {
-    const int lab = labels[g];
-    const int64_t b = g / HW;
-    if (lab > 0) obj = offsets[b] + lab - 1;
-    if (obj >= cap) obj = -1;
+    obj = object_index(labels[g], offsets, g / HW, cap);
     if (obj >= 0) {
       const long long k = cls[obj];
       const float p = (k >= 0 && k < C) ? fminf(fmaxf(probs[g * C + k], 0.f), 1.f) : 0.f;
       q = __double2ull_rn((double)p * 4294967296.0);
     }
   }
-  bool pending = obj >= 0;
-  for (int it = 0; it < LEADER_ROUNDS; ++it) {
-    const unsigned long long act = __ballot(pending);
-    if (!act) break;
-    const int leader = __ffsll((long long)act) - 1;
-    const long long lo = __shfl(obj, leader);
-    const bool mine = pending && obj == lo;
-    const unsigned long long s = wave_sum<unsigned long long>(mine ? q : 0ull);
-    if (lane == leader) atomicAdd(&acc[lo], s);
-    if (mine) pending = false;
-  }
-  if (pending) atomicAdd(&acc[obj], q);
+  wave_by_key(
+      obj,
+      [=](long long lo, bool mine, bool lead) {
+        const unsigned long long s = wave_sum<unsigned long long>(mine ? q : 0ull);
+        if (lead) atomicAdd(&acc[lo], s);
+      },
+      [=] { atomicAdd(&acc[obj], q); });
 }
 
 // score = (acc * 2^-32) / area in fp64, rounded to fp32
 __global__ __launch_bounds__(OB_THREADS) void scores_finish_kernel(const long long* __restrict__ offsets, int B, int64_t cap,
                                                                    const unsigned long long* __restrict__ acc, const long long* __restrict__ area,
                                                                    float* __restrict__ scores) {
-  const int64_t n = offsets[B] < cap ? offsets[B] : cap;
+  const int64_t n = objects_recorded(offsets, B, cap);
   for (int64_t i = (int64_t)blockIdx.x * OB_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * OB_THREADS)
     scores[i] = area[i] > 0 ? (float)(((double)acc[i] * 0x1p-32) / (double)area[i]) : 0.f;
 }
@@ -447,7 +384,7 @@ int cc_roots_i32(mgu_ctx* c, const int32_t* map, int B, int H, int W, int* P, hi
   const int64_t n = (int64_t)B * H * W;
   hipLaunchKernelGGL((cc_local_kernel<2, true>), tiles, dim3(OB_THREADS), 0, s, map, H, W, 0, 0ll, 0ll, P);
   hipLaunchKernelGGL((cc_border_kernel<2, true>), tiles, dim3(128), 0, s, map, H, W, 0, P);
-  hipLaunchKernelGGL(cc_flatten_kernel, dim3((unsigned)((n + OB_THREADS - 1) / OB_THREADS)), dim3(OB_THREADS), 0, s, P, n, (unsigned*)nullptr);
+  hipLaunchKernelGGL(cc_flatten_kernel, dim3(grid_for(n, OB_THREADS, INT_MAX)), dim3(OB_THREADS), 0, s, P, n, (unsigned*)nullptr);
   HIPCHK(c, hipGetLastError());
   return MGU_OK;
 }
@@ -456,7 +393,7 @@ int cc_number_roots(mgu_ctx* c, int* P, unsigned* area, int min_area, int B, int
                     int64_t* counts, int64_t* offsets, hipStream_t s) {
   const int64_t n = (int64_t)B * HW, nch = cc_chunks(HW);
   if (area) HIPCHK(c, hipMemsetAsync(area, 0, (size_t)n * 4, s));
-  const unsigned pixblocks = (unsigned)((n + OB_THREADS - 1) / OB_THREADS);
+  const unsigned pixblocks = grid_for(n, OB_THREADS, INT_MAX);
   hipLaunchKernelGGL(cc_flatten_kernel, dim3(pixblocks), dim3(OB_THREADS), 0, s, P, n, area);
   const dim3 chunks((unsigned)nch, B);
   hipLaunchKernelGGL(cc_count_kernel, chunks, dim3(OB_THREADS), 0, s, P, area, min_area, HW, cnt);
@@ -480,15 +417,11 @@ int mgu_connected_components(mgu_ctx* c, const void* src_dev, int src_kind, int 
   if (src_kind == 1 && C < 1) return fail(c, MGU_ERR_INVALID, "connected_components: logits need C >= 1");
   if (connectivity != 1 && connectivity != 2) return fail(c, MGU_ERR_INVALID, "connected_components: connectivity %d (1 or 2)", connectivity);
   if (B > 65535) return fail(c, MGU_ERR_INVALID, "connected_components: at most 65535 images per call");
-  if ((double)B * H * W >= (double)INT_MAX) return fail(c, MGU_ERR_INVALID, "connected_components: B*H*W must stay below 2^31");
+  if (int rc = check_pixel_count(c, "connected_components", B, H, W)) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)hip_stream;
   const int64_t HW = (int64_t)H * W, n = (int64_t)B * HW;
-  if (n == 0) {   // no pixels: every count is 0
-    HIPCHK(c, hipMemsetAsync(counts_dev, 0, (size_t)B * sizeof(int64_t), s));
-    HIPCHK(c, hipMemsetAsync(offsets_dev, 0, (size_t)(B + 1) * sizeof(int64_t), s));
-    return MGU_OK;
-  }
+  if (n == 0) return clear_counts(c, B, counts_dev, offsets_dev, s);
   const int64_t nch = cc_chunks(HW);
   Carve cv;
   const size_t oP = cv.take((size_t)n * 4), oA = min_area > 0 ? cv.take((size_t)n * 4) : 0, oC = cv.take((size_t)nch * B * 4);
@@ -523,7 +456,7 @@ int mgu_object_stats(mgu_ctx* c, const int32_t* labels_dev, const void* src_dev,
     return fail(c, MGU_ERR_INVALID, "bad object_stats args (null pointer or negative size)");
   if (src_kind != 0 && src_kind != 1) return fail(c, MGU_ERR_INVALID, "object_stats: src_kind %d (0 int64 class map, 1 fp32 logits)", src_kind);
   if (src_kind == 1 && C < 1) return fail(c, MGU_ERR_INVALID, "object_stats: logits need C >= 1");
-  if ((double)B * H * W >= (double)INT_MAX) return fail(c, MGU_ERR_INVALID, "object_stats: B*H*W must stay below 2^31");
+  if (int rc = check_pixel_count(c, "object_stats", B, H, W)) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)hip_stream;
   const int64_t HW = (int64_t)H * W, n = (int64_t)B * HW;
@@ -531,9 +464,9 @@ int mgu_object_stats(mgu_ctx* c, const int32_t* labels_dev, const void* src_dev,
   const long long* off = (const long long*)offsets_dev;
   long long* ar = (long long*)area_dev;
   long long* su = (long long*)sums_dev;
-  const unsigned initblocks = (unsigned)std::min<int64_t>(1024, (capacity + OB_THREADS - 1) / OB_THREADS);
+  const unsigned initblocks = grid_for(capacity, OB_THREADS, 1024);
   hipLaunchKernelGGL(stats_init_kernel, dim3(initblocks), dim3(OB_THREADS), 0, s, off, B, capacity, ar, bbox_dev, su);
-  const unsigned pixblocks = (unsigned)((n + OB_THREADS - 1) / OB_THREADS);
+  const unsigned pixblocks = grid_for(n, OB_THREADS, INT_MAX);
   if (src_kind == 0)
     hipLaunchKernelGGL(stats_kernel<0>, dim3(pixblocks), dim3(OB_THREADS), 0, s, labels_dev, src_dev, C, W, HW, n, off, capacity,
                        (long long*)class_dev, ar, bbox_dev, su);
@@ -549,7 +482,7 @@ int mgu_object_scores(mgu_ctx* c, const int32_t* labels_dev, const float* probs_
   if (!c) return MGU_ERR_INVALID;
   if (!labels_dev || !probs_dev || !offsets_dev || !class_dev || !area_dev || !scores_dev || B < 0 || H < 0 || W < 0 || C < 1 || capacity < 0)
     return fail(c, MGU_ERR_INVALID, "bad object_scores args (null pointer, negative size or C < 1)");
-  if ((double)B * H * W >= (double)INT_MAX) return fail(c, MGU_ERR_INVALID, "object_scores: B*H*W must stay below 2^31");
+  if (int rc = check_pixel_count(c, "object_scores", B, H, W)) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)hip_stream;
   const int64_t HW = (int64_t)H * W, n = (int64_t)B * HW;
@@ -558,10 +491,10 @@ int mgu_object_scores(mgu_ctx* c, const int32_t* labels_dev, const float* probs_
   if (rc) return rc;
   unsigned long long* acc = (unsigned long long*)c->objws;
   const long long* off = (const long long*)offsets_dev;
-  const unsigned objblocks = (unsigned)std::min<int64_t>(1024, (capacity + OB_THREADS - 1) / OB_THREADS);
+  const unsigned objblocks = grid_for(capacity, OB_THREADS, 1024);
   hipLaunchKernelGGL(scores_init_kernel, dim3(objblocks), dim3(OB_THREADS), 0, s, off, B, capacity, acc);
   if (n > 0) {
-    const unsigned pixblocks = (unsigned)((n + OB_THREADS - 1) / OB_THREADS);
+    const unsigned pixblocks = grid_for(n, OB_THREADS, INT_MAX);
     hipLaunchKernelGGL(scores_kernel, dim3(pixblocks), dim3(OB_THREADS), 0, s, labels_dev, probs_dev, C, HW, n, off, capacity,
                        (const long long*)class_dev, acc);
   }

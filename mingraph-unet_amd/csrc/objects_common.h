@@ -1,0 +1,113 @@
+// Helpers shared by the object-level kernel files (objects.hip, shapes.hip, split.hip, instances.hip): each is defined here and
+// nowhere else under csrc/ (tests/test_csrc_helpers.py).  device.h keeps what every kernel file shares.
+//   device: wave_by_key | block_exclusive_scan | chunk_sum_scan | object_index | objects_recorded
+//   host:   check_pixel_count | clear_counts
+#pragma once
+#include <climits>
+
+#include "ctx.h"
+
+namespace mgu {
+
+// ---- wave pre-aggregation ---------------------------------------------------------------------------------------------------------
+// Every lane holds one record for `key` (key < 0: nothing to add).  The lanes of a wave that share a key are served together: for up
+// to ROUNDS distinct keys the first pending lane is the leader, and the WHOLE wave calls group(k, mine, lead) with k = the leader's
+// key, mine = this lane holds k, lead = this lane is the leader -- the callback reduces over the lanes with `mine` and lets the lane
+// with `lead` issue one atomic for all of them.  It may use wave_sum, wave_min, wave_max or __ballot, which need every lane of the
+// wave: so wave_by_key itself must be reached by the whole wave (never under a per-lane branch; a lane without a record passes a
+// negative key), and the callback is called convergently here.  Lanes still pending after ROUNDS keys call single() and add their
+// own record directly.  The key keeps the caller's type: a 32-bit key costs one ds_bpermute per round, a 64-bit one two.  Callbacks
+// capture by value ([=]; they only read, the adds go through pointers): with nested by-reference captures the compiler still sees
+// stack slots when it sizes this loop and unrolls it four times, which doubled stats_kernel and panoptic_kernel.
+template <int ROUNDS = 4, typename K, typename G, typename S>
+__device__ __forceinline__ void wave_by_key(K key, G&& group, S&& single) {
+  const int lane = threadIdx.x & 63;
+  bool pending = key >= 0;
+  for (int it = 0; it < ROUNDS; ++it) {
+    const unsigned long long act = __ballot(pending);
+    if (!act) break;
+    const int leader = __ffsll((long long)act) - 1;
+    const K k = __shfl(key, leader);
+    const bool mine = pending && key == k;
+    group(k, mine, lane == leader);
+    if (mine) pending = false;
+  }
+  if (pending) single();
+}
+
+// ---- scans ------------------------------------------------------------------------------------------------------------------------
+// exclusive prefix sum over a 256-thread workgroup; *total gets the sum (sh: 4 ints)
+__device__ __forceinline__ int block_exclusive_scan(int v, int* sh, int* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int inc = v;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int u = __shfl_up(inc, off);
+    if (lane >= off) inc += u;
+  }
+  if (lane == 63) sh[wave] = inc;
+  __syncthreads();
+  int before = 0;
+  for (int w = 0; w < wave; ++w) before += sh[w];
+  *total = sh[0] + sh[1] + sh[2] + sh[3];
+  __syncthreads();
+  return before + inc - v;
+}
+
+// One workgroup of SCAN_THREADS threads scans the n sums the chunk kernels left in cnt: choff[k] = cnt[0] + ... + cnt[k - 1].  A
+// thread sums its segment of consecutive chunks, an inclusive Hillis-Steele scan over the segment sums gives every segment its
+// start, and the thread walks its segment again.  Every thread gets the grand total; a caller that reads choff entries of other
+// threads puts a __syncthreads() first.
+constexpr int SCAN_THREADS = 1024;
+__device__ __forceinline__ long long chunk_sum_scan(const int* __restrict__ cnt, int64_t n, long long* __restrict__ choff) {
+  __shared__ long long sh[SCAN_THREADS];
+  const int tid = threadIdx.x;
+  const int64_t seg = (n + SCAN_THREADS - 1) / SCAN_THREADS;
+  const int64_t k0 = tid * seg < n ? tid * seg : n, k1 = k0 + seg < n ? k0 + seg : n;
+  long long s = 0;
+  for (int64_t k = k0; k < k1; ++k) s += cnt[k];
+  sh[tid] = s;
+  __syncthreads();
+  for (int off = 1; off < SCAN_THREADS; off <<= 1) {
+    const long long u = tid >= off ? sh[tid - off] : 0;
+    __syncthreads();
+    sh[tid] += u;
+    __syncthreads();
+  }
+  long long run = sh[tid] - s;
+  for (int64_t k = k0; k < k1; ++k) {
+    choff[k] = run;
+    run += cnt[k];
+  }
+  return sh[SCAN_THREADS - 1];
+}
+
+// ---- the per-object arrays --------------------------------------------------------------------------------------------------------
+// row of the per-object arrays of a pixel of image b holding label `lab`: offsets[b] + lab - 1; -1 on background and for an object
+// past the arrays' capacity (it was not recorded)
+__device__ __forceinline__ long long object_index(int lab, const long long* __restrict__ offsets, int64_t b, int64_t cap) {
+  const long long o = lab > 0 ? offsets[b] + lab - 1 : -1;
+  return o < cap ? o : -1;
+}
+// rows of the per-object arrays in use: every object of the batch, or as many as the arrays hold
+__device__ __forceinline__ int64_t objects_recorded(const long long* __restrict__ offsets, int B, int64_t cap) {
+  return offsets[B] < cap ? offsets[B] : cap;
+}
+
+}  // namespace mgu
+
+namespace mgud {
+
+// the kernels index pixels with 32-bit integers; fn: the entry point's name as its messages spell it
+inline int check_pixel_count(mgu_ctx* c, const char* fn, int B, int H, int W) {
+  if ((double)B * H * W >= (double)INT_MAX) return fail(c, MGU_ERR_INVALID, "%s: B*H*W must stay below 2^31", fn);
+  return MGU_OK;
+}
+// a batch without pixels: every count and offset is 0
+inline int clear_counts(mgu_ctx* c, int B, int64_t* counts, int64_t* offsets, hipStream_t s) {
+  HIPCHK(c, hipMemsetAsync(counts, 0, (size_t)B * sizeof(int64_t), s));
+  HIPCHK(c, hipMemsetAsync(offsets, 0, (size_t)(B + 1) * sizeof(int64_t), s));
+  return MGU_OK;
+}
+
+}  // namespace mgud

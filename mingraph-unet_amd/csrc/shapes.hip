@@ -10,21 +10,18 @@
 // The term needs no second sweep: with m_j = iyy dy^2 + 2 ixy dy dx + ixx dx^2 (the inverse of cov + eps I applied to the centred
 // pixel), sum (m - 1)^2 = sum m^2 - 2 sum m + n is a fixed combination of the central moments of orders 2 and 4, and those follow
 // from the raw ones by the binomial shift.
-#include <climits>
-
-#include "ctx.h"
+#include "objects_common.h"
 
 namespace mgu {
 namespace {
 
 constexpr int SH_THREADS = 256;
 constexpr int SH_ROWS = 16;                   // rows per tile: a lane keeps one object's sums in registers down its column
-constexpr int SH_ROUNDS = 4;                  // wave pre-aggregation at the end: distinct objects summed per wave, the rest add directly
 constexpr int NMOM = 12;                      // x^2 xy y^2 | x^3 x^2y xy^2 y^3 | x^4 x^3y x^2y^2 xy^3 y^4
 typedef unsigned long long u64;
 
 __global__ __launch_bounds__(SH_THREADS) void moments_init_kernel(const long long* __restrict__ offsets, int B, int64_t cap, u64* __restrict__ mom) {
-  const int64_t n = (offsets[B] < cap ? offsets[B] : cap) * NMOM;
+  const int64_t n = objects_recorded(offsets, B, cap) * NMOM;
   for (int64_t i = (int64_t)blockIdx.x * SH_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * SH_THREADS) mom[i] = 0;
 }
 
@@ -37,8 +34,9 @@ __device__ __forceinline__ void flush_direct(u64* __restrict__ mom, long long o,
 
 // A workgroup takes a tile of 256 columns x SH_ROWS rows of one image; a lane walks down one column, so it mostly stays inside one
 // object and adds to 12 registers (background in between does not end the object).  A lane meeting another object adds the sums of
-// the one it leaves directly.  What the lanes hold at the end is summed per object inside the wave; each wave's first object then
-// meets those of the consecutive waves in LDS, so an image-sized object receives one atomic per sum and tile rather than one per pixel.
+// the one it leaves directly.  What the lanes hold at the end is summed per object inside the wave (the first object here, the next
+// three by wave_by_key); each wave's first object then meets those of the consecutive waves in LDS, so an image-sized object receives
+// one atomic per sum and tile rather than one per pixel.
 __global__ __launch_bounds__(SH_THREADS) void moments_kernel(const int* __restrict__ labels, int H, int W, const long long* __restrict__ offsets,
                                                              int64_t cap, const int* __restrict__ bbox, u64* __restrict__ mom) {
   __shared__ long long sh_obj[SH_THREADS / 64];
@@ -49,6 +47,8 @@ __global__ __launch_bounds__(SH_THREADS) void moments_kernel(const int* __restri
   int lab[SH_ROWS];
 #pragma unroll
   for (int r = 0; r < SH_ROWS; ++r) lab[r] = (xx < W && yb + r < H) ? labels[img + (int64_t)(yb + r) * W + xx] : 0;
+  // object_index's rule with the image's offset read once for the lane's 16 rows: calling it per row costs this kernel two more
+  // VGPRs or a scalar load in every row
   const long long first = offsets[b];
   long long cur = -1;
   u64 x = 0;
@@ -100,20 +100,16 @@ __global__ __launch_bounds__(SH_THREADS) void moments_kernel(const int* __restri
     }
     if (o >= 0 && s) atomicAdd(&mom[o * NMOM + tid], s);
   }
-  for (int r = 1; r < SH_ROUNDS; ++r) {
-    const unsigned long long act = __ballot(pending);
-    if (!act) break;
-    const int leader = __ffsll((long long)act) - 1;
-    const long long lo = __shfl(cur, leader);
-    const bool mine = pending && cur == lo;
+  wave_by_key<3>(
+      pending ? cur : -1,
+      [=](long long lo, bool mine, bool lead) {
 #pragma unroll
-    for (int k = 0; k < NMOM; ++k) {
-      const u64 s = wave_sum(mine ? acc[k] : 0ull);
-      if (lane == leader && s) atomicAdd(&mom[lo * NMOM + k], s);
-    }
-    if (mine) pending = false;
-  }
-  if (pending) flush_direct(mom, cur, acc);
+        for (int k = 0; k < NMOM; ++k) {
+          const u64 s = wave_sum(mine ? acc[k] : 0ull);
+          if (lead && s) atomicAdd(&mom[lo * NMOM + k], s);
+        }
+      },
+      [=] { flush_direct(mom, cur, acc); });
 }
 
 // ---- second moments as exact integers -------------------------------------------------------------------------------------------
@@ -161,7 +157,7 @@ __global__ __launch_bounds__(SH_THREADS) void shapes_kernel(const long long* __r
                                                             float* __restrict__ cov, float* __restrict__ axes, float* __restrict__ angle,
                                                             float* __restrict__ fill, float* __restrict__ term, unsigned char* __restrict__ status,
                                                             u64* __restrict__ racc) {
-  const int64_t N = offsets[B] < cap ? offsets[B] : cap;
+  const int64_t N = objects_recorded(offsets, B, cap);
   for (int64_t o = (int64_t)blockIdx.x * SH_THREADS + threadIdx.x; o < N; o += (int64_t)gridDim.x * SH_THREADS) {
     const long long n = area[o];
     const int bx0 = bbox[4 * o], by0 = bbox[4 * o + 1], bw = bbox[4 * o + 2] - bx0, bh = bbox[4 * o + 3] - by0;
@@ -246,14 +242,13 @@ __global__ __launch_bounds__(SH_THREADS) void residual_kernel(const int* __restr
                                                               const u64* __restrict__ mom, double eps, const float* __restrict__ term,
                                                               u64* __restrict__ racc) {
   const int64_t g = (int64_t)blockIdx.x * SH_THREADS + threadIdx.x;
-  const int lane = threadIdx.x & 63;
   long long obj = -1;
   u64 qv = 0;
   if (g < n) {
     const int lab = labels[g];
     const int64_t b = g / HW, i = g - b * HW;
-    if (lab > 0) obj = offsets[b] + lab - 1;
-    if (obj >= cap || (obj >= 0 && term[obj] == term[obj])) obj = -1;   // only objects whose term is NaN
+    obj = object_index(lab, offsets, b, cap);
+    if (obj >= 0 && term[obj] == term[obj]) obj = -1;   // only objects whose term is NaN
     if (obj >= 0) {
       const Second s = second_moments(obj, area, bbox, sums, mom);
       const int y = (int)(i / W), x = (int)(i - (int64_t)y * W);
@@ -267,24 +262,19 @@ __global__ __launch_bounds__(SH_THREADS) void residual_kernel(const int* __restr
       qv = __double2ull_rn(fmin((m - 1.0) * (m - 1.0) * (double)(1ull << residual_shift(s.n)), 4.0e18));
     }
   }
-  bool pending = obj >= 0;
-  for (int it = 0; it < SH_ROUNDS; ++it) {
-    const unsigned long long act = __ballot(pending);
-    if (!act) break;
-    const int leader = __ffsll((long long)act) - 1;
-    const long long lo = __shfl(obj, leader);
-    const bool mine = pending && obj == lo;
-    const u64 sum = wave_sum(mine ? qv : 0ull);
-    if (lane == leader) atomicAdd(&racc[lo], sum);
-    if (mine) pending = false;
-  }
-  if (pending) atomicAdd(&racc[obj], qv);
+  wave_by_key(
+      obj,
+      [=](long long lo, bool mine, bool lead) {
+        const u64 sum = wave_sum(mine ? qv : 0ull);
+        if (lead) atomicAdd(&racc[lo], sum);
+      },
+      [=] { atomicAdd(&racc[obj], qv); });
 }
 
 __global__ __launch_bounds__(SH_THREADS) void residual_finish_kernel(const long long* __restrict__ offsets, int B, int64_t cap,
                                                                      const long long* __restrict__ area, const u64* __restrict__ racc,
                                                                      float* __restrict__ term) {
-  const int64_t N = offsets[B] < cap ? offsets[B] : cap;
+  const int64_t N = objects_recorded(offsets, B, cap);
   for (int64_t o = (int64_t)blockIdx.x * SH_THREADS + threadIdx.x; o < N; o += (int64_t)gridDim.x * SH_THREADS)
     if (term[o] != term[o]) term[o] = (float)((double)racc[o] / (double)(1ull << residual_shift(area[o])) / (double)area[o]);
 }
@@ -295,7 +285,7 @@ __global__ __launch_bounds__(SH_THREADS) void shape_loss_kernel(const long long*
                                                                 long long keep, float* __restrict__ loss) {
   __shared__ double ssum[SH_THREADS];
   __shared__ long long scnt[SH_THREADS];
-  const int64_t N = offsets[B] < cap ? offsets[B] : cap;
+  const int64_t N = objects_recorded(offsets, B, cap);
   double s = 0.0;
   long long cnt = 0;
   for (int64_t o = threadIdx.x; o < N; o += SH_THREADS)
@@ -322,14 +312,14 @@ int mgu_object_moments(mgu_ctx* c, const int32_t* labels_dev, int B, int H, int 
   if (!c) return MGU_ERR_INVALID;
   if (!labels_dev || !offsets_dev || B < 0 || H < 0 || W < 0 || capacity < 0 || (capacity > 0 && (!bbox_dev || !moments_dev)))
     return fail(c, MGU_ERR_INVALID, "bad object_moments args (null pointer or negative size)");
-  if ((double)B * H * W >= (double)INT_MAX) return fail(c, MGU_ERR_INVALID, "object_moments: B*H*W must stay below 2^31");
+  if (int rc = check_pixel_count(c, "object_moments", B, H, W)) return rc;
   if (B > 65535 || (H + SH_ROWS - 1) / SH_ROWS > 65535) return fail(c, MGU_ERR_INVALID, "object_moments: at most 65535 images and %d rows per call", 65535 * SH_ROWS);
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)hip_stream;
   if (capacity == 0) return MGU_OK;
   const int64_t n = (int64_t)B * H * W;
   const long long* off = (const long long*)offsets_dev;
-  const unsigned initblocks = (unsigned)std::min<int64_t>(1024, (capacity * NMOM + SH_THREADS - 1) / SH_THREADS);
+  const unsigned initblocks = grid_for(capacity * NMOM, SH_THREADS, 1024);
   hipLaunchKernelGGL(moments_init_kernel, dim3(initblocks), dim3(SH_THREADS), 0, s, off, B, capacity, (u64*)moments_dev);
   if (n > 0)
     hipLaunchKernelGGL(moments_kernel, dim3((W + SH_THREADS - 1) / SH_THREADS, (H + SH_ROWS - 1) / SH_ROWS, B), dim3(SH_THREADS), 0, s, labels_dev, H, W,
@@ -350,7 +340,7 @@ int mgu_object_shapes(mgu_ctx* c, const int32_t* labels_dev, int B, int H, int W
     return fail(c, MGU_ERR_INVALID, "object_shapes: every per-object array is needed for a nonzero capacity");
   if (!(epsilon >= 0.f)) return fail(c, MGU_ERR_INVALID, "object_shapes: epsilon must be >= 0");
   if (min_pixels < 0) return fail(c, MGU_ERR_INVALID, "object_shapes: min_pixels must be >= 0");
-  if ((double)B * H * W >= (double)INT_MAX) return fail(c, MGU_ERR_INVALID, "object_shapes: B*H*W must stay below 2^31");
+  if (int rc = check_pixel_count(c, "object_shapes", B, H, W)) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   if (capacity == 0) return MGU_OK;
   int rc = ensure(c, &c->objws, &c->objws_bytes, (size_t)capacity * 8);
@@ -359,12 +349,12 @@ int mgu_object_shapes(mgu_ctx* c, const int32_t* labels_dev, int B, int H, int W
   hipStream_t s = (hipStream_t)hip_stream;
   const long long* off = (const long long*)offsets_dev;
   const int64_t HW = (int64_t)H * W, n = (int64_t)B * HW;
-  const unsigned blocks = (unsigned)std::min<int64_t>(1024, (capacity + SH_THREADS - 1) / SH_THREADS);
+  const unsigned blocks = grid_for(capacity, SH_THREADS, 1024);
   hipLaunchKernelGGL(shapes_kernel, dim3(blocks), dim3(SH_THREADS), 0, s, off, B, capacity, (const long long*)area_dev, bbox_dev,
                      (const long long*)sums_dev, (const u64*)moments_dev, (double)epsilon, min_pixels, centroid_dev, cov_dev, axes_dev, angle_dev,
                      fill_dev, term_dev, status_dev, racc);
   if (n > 0)
-    hipLaunchKernelGGL(residual_kernel, dim3((unsigned)((n + SH_THREADS - 1) / SH_THREADS)), dim3(SH_THREADS), 0, s, labels_dev, W, HW, n, off, capacity,
+    hipLaunchKernelGGL(residual_kernel, dim3(grid_for(n, SH_THREADS, INT_MAX)), dim3(SH_THREADS), 0, s, labels_dev, W, HW, n, off, capacity,
                        (const long long*)area_dev, bbox_dev, (const long long*)sums_dev, (const u64*)moments_dev, (double)epsilon, term_dev, racc);
   hipLaunchKernelGGL(residual_finish_kernel, dim3(blocks), dim3(SH_THREADS), 0, s, off, B, capacity, (const long long*)area_dev, racc, term_dev);
   HIPCHK(c, hipGetLastError());

@@ -10,9 +10,7 @@
 // union-find (cc_roots_i32), (5) seeds bucketed per component (count, bucket start, scatter), (6) every foreground pixel scans its
 // component's bucket, staged through LDS, (7) the first pixel of every new object by atomicMin, then objects.hip's numbering tail.
 // The launch count is fixed: it depends on no size, object count or seed count.
-#include <climits>
-
-#include "ctx.h"
+#include "objects_common.h"
 
 namespace mgu {
 namespace {
@@ -292,11 +290,7 @@ int mgu_split_objects(mgu_ctx* c, const int32_t* labels_dev, int B, int H, int W
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)hip_stream;
   const int64_t HW = (int64_t)H * W, n = (int64_t)B * HW, nslots = n + B, nch = cc_chunks(HW);
-  if (n == 0) {
-    HIPCHK(c, hipMemsetAsync(counts_dev, 0, (size_t)B * sizeof(int64_t), s));
-    HIPCHK(c, hipMemsetAsync(offsets_dev, 0, (size_t)(B + 1) * sizeof(int64_t), s));
-    return MGU_OK;
-  }
+  if (n == 0) return clear_counts(c, B, counts_dev, offsets_dev, s);
   Carve cv;
   const size_t oG = cv.take((size_t)n * 4);                          // column distances, then the provisional objects
   const size_t oD = d2_out_dev ? 0 : cv.take((size_t)n * 4);
@@ -333,15 +327,15 @@ int mgu_split_objects(mgu_ctx* c, const int32_t* labels_dev, int B, int H, int W
   hipLaunchKernelGGL(zone_kernel, tiles, dim3(SP_THREADS), 0, s, labels_dev, seeds, H, W, maxlab, h, zone);
   rc = cc_roots_i32(c, zone, B, H, W, zroot, s);
   if (rc) return rc;
-  hipLaunchKernelGGL(bucket_kernel, dim3((unsigned)((nslots + SP_THREADS - 1) / SP_THREADS)), dim3(SP_THREADS), 0, s, cnt, nslots, cnt + nslots,
+  hipLaunchKernelGGL(bucket_kernel, dim3(grid_for(nslots, SP_THREADS, INT_MAX)), dim3(SP_THREADS), 0, s, cnt, nslots, cnt + nslots,
                      cursor);
-  const dim3 runs((unsigned)((HW + SP_THREADS - 1) / SP_THREADS), B);
+  const dim3 runs(grid_for(HW, SP_THREADS, INT_MAX), B);
   hipLaunchKernelGGL(scatter_kernel, runs, dim3(SP_THREADS), 0, s, labels_dev, d2, seeds, W, HW, maxlab, cursor, list);
   HIPCHK(c, hipMemsetAsync(first, 0xff, (size_t)(n + nslots) * 4, s));
   int* prov = g;
   hipLaunchKernelGGL(assign_kernel, runs, dim3(SP_THREADS), 0, s, labels_dev, W, HW, n, maxlab, cnt, cursor, list, zroot, prov, first);
   int* P = zone;
-  hipLaunchKernelGGL(point_kernel, dim3((unsigned)((n + SP_THREADS - 1) / SP_THREADS)), dim3(SP_THREADS), 0, s, prov, first, n, P);
+  hipLaunchKernelGGL(point_kernel, dim3(grid_for(n, SP_THREADS, INT_MAX)), dim3(SP_THREADS), 0, s, prov, first, n, P);
   HIPCHK(c, hipGetLastError());
   return cc_number_roots(c, P, area, min_area, B, HW, (int*)(ws + oC), (long long*)(ws + cv.off), labels_out_dev, counts_dev, offsets_dev, s);
 }

@@ -13,7 +13,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .objects import ObjectTable, _check_args, _iou, _label, _source, _split, _split_params, _stats
+from .metrics import _evaluate
+from .objects import ObjectTable, _iou, _ObjectEvaluator
 
 DEFAULT_THRESHOLDS = np.linspace(0.5, 0.95, 10)   # COCO's 0.50:0.05:0.95
 
@@ -248,7 +249,7 @@ def object_detection_mAP(gt_boxes_list, pred_boxes_list, iou_threshold=0.5, num_
     return _class_mean(ap[0])
 
 
-class InstanceEvaluator:
+class InstanceEvaluator(_ObjectEvaluator):
     """Device-side instance evaluation over a test set, in the shape of YieldEvaluator.  update(logits, masks) labels the predicted
     objects (argmax fused; min_area applies to them) and the GT objects (connected components of the mask values in
     [1, num_classes); with `split` both are cut apart as YieldEvaluator does), takes per-object classes and areas, scores every
@@ -260,25 +261,12 @@ class InstanceEvaluator:
 
     def __init__(self, num_classes: int, device, connectivity: int = 2, min_area: int = 0, thresholds=None, split: dict = None,
                  smooth: float = 1e-6):
-        _check_args(connectivity, min_area)
-        self._split = None
-        if split is not None:
-            extra = set(split) - {"min_distance", "min_radius", "min_area"}
-            if extra:
-                raise ValueError(f"split takes min_distance, min_radius and min_area, not {sorted(extra)}")
-            self._split = _split_params(split.get("min_distance", 5), split.get("min_radius", 3), split.get("min_area", 0))
-        self.num_classes, self.device = int(num_classes), torch.device(device)
-        if self.num_classes < 1:
-            raise ValueError("num_classes must be >= 1")
-        _lib.require_hip(self.device, "InstanceEvaluator")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self.connectivity, self.min_area, self.smooth = connectivity, int(min_area), smooth
+        super().__init__(num_classes, device, connectivity, min_area, split)
+        self.smooth = smooth
         self.thresholds = _thresholds(thresholds)
         T = self.thresholds.size
         self._thr = torch.from_numpy(self.thresholds).to(self.device)
         self._bit = (2 ** torch.arange(T, dtype=torch.int32)).view(T, 1).to(self.device)
-        self._bufs, self._cap = None, -1
         self.reset()
 
     def reset(self) -> None:
@@ -301,28 +289,10 @@ class InstanceEvaluator:
 
     def update(self, logits_nchw: torch.Tensor, masks: torch.Tensor) -> None:
         """Add one batch: logits (B, C, H, W) float32 -- the view UNet.forward returns -- and integer masks (B, H, W)."""
-        if not logits_nchw.is_cuda or logits_nchw.device != self.device:
-            raise RuntimeError(f"logits must live on {self.device}")
-        src, kind, B, H, W, C = _source(logits_nchw)
-        if kind != 1:
-            raise TypeError("expected (B, C, H, W) float32 logits")
-        if C != self.num_classes:
-            raise ValueError(f"logits have {C} classes, the evaluator {self.num_classes}")
-        if tuple(masks.shape) != (B, H, W):
-            raise ValueError(f"masks shape {tuple(masks.shape)} does not match logits {(B, H, W)}")
-        masks = masks.to(self.device, torch.int64).contiguous()
+        src, masks, B, H, W, C = self._batch(logits_nchw, masks)
         n = B * H * W
         bufs, cap = self._buffers(n), self._cap
-        offsets = {}
-        for side, s, k, cc, ncls, amin in (("gt", masks, 0, 0, self.num_classes, 0), ("pred", src, 1, C, 0, self.min_area)):
-            lab, cls, bbox, area = bufs[side]
-            lab = lab[:n].view(B, H, W)
-            counts = torch.empty(B, device=self.device, dtype=torch.int64)
-            offsets[side] = torch.empty(B + 1, device=self.device, dtype=torch.int64)
-            _label(s, k, B, H, W, cc, self.connectivity, 0, ncls, amin, lab, counts, offsets[side])
-            if self._split is not None:   # in place: the split has read the components before it writes the objects
-                _split(lab, B, H, W, self._split, lab, counts, offsets[side])
-            _stats(lab, s, k, B, H, W, cc, offsets[side], cap, cls, bbox, area)
+        _, offsets = self._label_sides(src, masks, B, H, W, C, bufs)
         (gl, gc, _, ga), (pl, pc, _, pa) = bufs["gt"], bufs["pred"]
         probs = torch.softmax(src, dim=-1)   # NHWC, as mgu_object_scores reads it
         _lib.call("mgu_object_scores", self.device, pl, probs, B, H, W, C, offsets["pred"], cap, pc, pa, bufs["scores"])
@@ -356,17 +326,5 @@ class InstanceEvaluator:
 def evaluate_instances(model, loader, num_classes=None, connectivity=2, min_area=0, thresholds=None, split=None, smooth=1e-6) -> dict:
     """Instance evaluation over `loader`'s (images, masks) batches: logits = model(images) under torch.no_grad() in eval mode, then
     InstanceEvaluator.  Returns instance_metrics' dictionary; the model's training flag is restored."""
-    dev = next(model.parameters()).device
-    C = int(num_classes if num_classes is not None else model.num_classes)
-    ev = InstanceEvaluator(C, dev, connectivity=connectivity, min_area=min_area, thresholds=thresholds, split=split, smooth=smooth)
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            for images, masks in loader:
-                out = model(images.to(dev))
-                logits = out[0] if isinstance(out, (tuple, list)) else out
-                ev.update(logits, masks.to(dev))
-        return ev.compute()
-    finally:
-        model.train(was_training)
+    return _evaluate(model, loader, num_classes, lambda C, dev: InstanceEvaluator(
+        C, dev, connectivity=connectivity, min_area=min_area, thresholds=thresholds, split=split, smooth=smooth))

@@ -176,14 +176,12 @@ class SegmentationEvaluator:
         return res
 
 
-def evaluate_segmentation(model, loader, num_classes=None, loss=None, smooth=1e-6) -> dict:
-    """The evaluation loop of segmentation_performance.py:125-151 (no file I/O): for each (images, masks) batch of `loader`,
-    logits = model(images) under torch.no_grad() in eval mode, then argmax + confusion counts (+ loss) on the device.  Returns
-    segmentation_metrics' dictionary over the whole loader (+ 'loss').  The model's training flag is restored afterwards, so a
-    training script can validate between epochs (also on a model whose parameters a Trainer has re-homed)."""
+def _evaluate(model, loader, num_classes, make_evaluator) -> dict:
+    """The loop the evaluate_* functions share: ev = make_evaluator(classes, device), then for each (images, masks) batch of `loader`
+    logits = model(images) under torch.no_grad() in eval mode and ev.update(logits, masks); returns ev.compute().  The classes default
+    to model.num_classes; the model's training flag is restored."""
     dev = next(model.parameters()).device
-    C = int(num_classes if num_classes is not None else model.num_classes)
-    ev = SegmentationEvaluator(C, dev, loss=loss, smooth=smooth)
+    ev = make_evaluator(int(num_classes if num_classes is not None else model.num_classes), dev)
     was_training = model.training
     model.eval()
     try:
@@ -195,3 +193,11 @@ def evaluate_segmentation(model, loader, num_classes=None, loss=None, smooth=1e-
         return ev.compute()
     finally:
         model.train(was_training)
+
+
+def evaluate_segmentation(model, loader, num_classes=None, loss=None, smooth=1e-6) -> dict:
+    """The evaluation loop of segmentation_performance.py:125-151 (no file I/O): for each (images, masks) batch of `loader`,
+    logits = model(images) under torch.no_grad() in eval mode, then argmax + confusion counts (+ loss) on the device.  Returns
+    segmentation_metrics' dictionary over the whole loader (+ 'loss').  The model's training flag is restored afterwards, so a
+    training script can validate between epochs (also on a model whose parameters a Trainer has re-homed)."""
+    return _evaluate(model, loader, num_classes, lambda C, dev: SegmentationEvaluator(C, dev, loss=loss, smooth=smooth))

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .metrics import _evaluate
 
 
 @dataclass
@@ -100,6 +101,20 @@ def _check_args(connectivity, min_area):
         raise ValueError("min_area must be >= 0")
 
 
+def _table(labels, counts, offsets, src, kind, C) -> ObjectTable:
+    """The ObjectTable of a labelled batch: per-object arrays sized from offsets[B] (one synchronisation) and filled by _stats."""
+    B, H, W = labels.shape
+    dev = labels.device
+    N = int(offsets[B].item())
+    cls = torch.empty(N, device=dev, dtype=torch.int64)
+    area = torch.empty(N, device=dev, dtype=torch.int64)
+    bbox = torch.empty((N, 4), device=dev, dtype=torch.int32)
+    sums = torch.empty((N, 2), device=dev, dtype=torch.int64)
+    if N:
+        _stats(labels, src, kind, B, H, W, C, offsets, N, cls, bbox, area, sums)
+    return ObjectTable(labels, counts, offsets, cls, area, bbox, sums)
+
+
 def connected_components(x: torch.Tensor, connectivity: int = 2, background: int = 0, min_area: int = 0) -> ObjectTable:
     """skimage.measure.label(x, connectivity, background) per image, plus per-object statistics, on the device.
 
@@ -114,14 +129,7 @@ def connected_components(x: torch.Tensor, connectivity: int = 2, background: int
     counts = torch.empty(B, device=dev, dtype=torch.int64)
     offsets = torch.empty(B + 1, device=dev, dtype=torch.int64)
     _label(src, kind, B, H, W, C, connectivity, background, 0, min_area, labels, counts, offsets)
-    N = int(offsets[B].item())
-    cls = torch.empty(N, device=dev, dtype=torch.int64)
-    area = torch.empty(N, device=dev, dtype=torch.int64)
-    bbox = torch.empty((N, 4), device=dev, dtype=torch.int32)
-    sums = torch.empty((N, 2), device=dev, dtype=torch.int64)
-    if N:
-        _stats(labels, src, kind, B, H, W, C, offsets, N, cls, bbox, area, sums)
-    return ObjectTable(labels, counts, offsets, cls, area, bbox, sums)
+    return _table(labels, counts, offsets, src, kind, C)
 
 
 def distance_transform(labels) -> torch.Tensor:
@@ -189,17 +197,11 @@ def split_objects(x, min_distance: int = 5, min_radius: float = 3, connectivity:
     offsets = torch.empty(B + 1, device=dev, dtype=torch.int64)
     seeds = torch.empty((B, H, W), device=dev, dtype=torch.uint8) if return_seeds else None
     _split(comp, B, H, W, params, labels, counts, offsets, None, seeds)
-    N = int(offsets[B].item())
-    cls = torch.empty(N, device=dev, dtype=torch.int64)
-    area = torch.empty(N, device=dev, dtype=torch.int64)
-    bbox = torch.empty((N, 4), device=dev, dtype=torch.int32)
-    sums = torch.empty((N, 2), device=dev, dtype=torch.int64)
-    if N:
-        _stats(labels, src, kind, B, H, W, C, offsets, N, cls, bbox, area, sums)
-        if parent is not None:   # parent label -> the parent's row -> its class
-            image = torch.repeat_interleave(torch.arange(B, device=dev), counts, output_size=N)
-            cls = parent.class_id[parent.offsets[image] + cls - 1]
-    table = ObjectTable(labels, counts, offsets, cls, area, bbox, sums)
+    table = _table(labels, counts, offsets, src, kind, C)
+    N = table.class_id.numel()
+    if N and parent is not None:   # parent label -> the parent's row -> its class
+        image = torch.repeat_interleave(torch.arange(B, device=dev), counts, output_size=N)
+        table.class_id = parent.class_id[parent.offsets[image] + table.class_id - 1]
     return (table, seeds.bool()) if return_seeds else table
 
 
@@ -335,17 +337,11 @@ def yield_estimation_metrics(gt_counts, pred_counts, gt_objects_list=None, pred_
     return _yield_dict(gt_counts, pred_counts, match, smooth)
 
 
-class YieldEvaluator:
-    """Device-side yield estimation over a test set.  update(logits, masks) labels the predicted objects (argmax fused into the
-    labelling) and the GT objects (mask values in [1, num_classes); 0, -100 and anything out of range are background), appends the
-    per-image counts to device buffers and accumulates the matching totals; it never blocks the host.  min_area applies to the
-    predicted objects.  compute() synchronises once and returns yield_estimation_metrics' dictionary -- equal to calling it on the
-    per-image counts and to_dicts() of the same batches.  split: a dict of split_objects' min_distance / min_radius / min_area; the
-    predicted and the GT objects alike are then cut apart (mgunet.split_objects) before they are counted and matched, still without
-    a host synchronisation.  None: objects are the connected components."""
+class _ObjectEvaluator:
+    """What YieldEvaluator and InstanceEvaluator (instances.py) share: the constructor's checks, update()'s checks of a batch, and the
+    objects of its two sides."""
 
-    def __init__(self, num_classes: int, device, connectivity: int = 2, min_area: int = 0, iou_thresh: float = 0.5, smooth: float = 1e-6,
-                 split: dict = None):
+    def __init__(self, num_classes, device, connectivity, min_area, split):
         _check_args(connectivity, min_area)
         self._split = None
         if split is not None:
@@ -356,12 +352,55 @@ class YieldEvaluator:
         self.num_classes, self.device = int(num_classes), torch.device(device)
         if self.num_classes < 1:
             raise ValueError("num_classes must be >= 1")
-        _lib.require_hip(self.device, "YieldEvaluator")
+        _lib.require_hip(self.device, type(self).__name__)
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.connectivity, self.min_area = connectivity, int(min_area)
-        self.iou_thresh, self.smooth = float(iou_thresh), smooth
         self._bufs, self._cap = None, -1
+
+    def _batch(self, logits_nchw, masks):
+        """(NHWC logits, int64 masks on the device, B, H, W, C) of update()'s arguments, checked."""
+        if not logits_nchw.is_cuda or logits_nchw.device != self.device:
+            raise RuntimeError(f"logits must live on {self.device}")
+        src, kind, B, H, W, C = _source(logits_nchw)
+        if kind != 1:
+            raise TypeError("expected (B, C, H, W) float32 logits")
+        if C != self.num_classes:
+            raise ValueError(f"logits have {C} classes, the evaluator {self.num_classes}")
+        if tuple(masks.shape) != (B, H, W):
+            raise ValueError(f"masks shape {tuple(masks.shape)} does not match logits {(B, H, W)}")
+        return src, masks.to(self.device, torch.int64).contiguous(), B, H, W, C
+
+    def _label_sides(self, src, masks, B, H, W, C, bufs):
+        """Label, split (when asked) and take the statistics of the GT objects (mask values in [1, num_classes)) and of the predicted
+        objects (argmax fused, min_area) into bufs[side] = (labels, class, bbox[, area]), worst-case buffers of self._cap rows: no
+        host synchronisation.  Returns the two sides' counts and offsets."""
+        counts, offsets = {}, {}
+        for side, s, k, cc, ncls, amin in (("gt", masks, 0, 0, self.num_classes, 0), ("pred", src, 1, C, 0, self.min_area)):
+            lab, cls, bbox, *area = bufs[side]
+            lab = lab[:B * H * W].view(B, H, W)
+            counts[side] = torch.empty(B, device=self.device, dtype=torch.int64)
+            offsets[side] = torch.empty(B + 1, device=self.device, dtype=torch.int64)
+            _label(s, k, B, H, W, cc, self.connectivity, 0, ncls, amin, lab, counts[side], offsets[side])
+            if self._split is not None:   # in place: the split has read the components before it writes the objects
+                _split(lab, B, H, W, self._split, lab, counts[side], offsets[side])
+            _stats(lab, s, k, B, H, W, cc, offsets[side], self._cap, cls, bbox, *area)
+        return counts, offsets
+
+
+class YieldEvaluator(_ObjectEvaluator):
+    """Device-side yield estimation over a test set.  update(logits, masks) labels the predicted objects (argmax fused into the
+    labelling) and the GT objects (mask values in [1, num_classes); 0, -100 and anything out of range are background), appends the
+    per-image counts to device buffers and accumulates the matching totals; it never blocks the host.  min_area applies to the
+    predicted objects.  compute() synchronises once and returns yield_estimation_metrics' dictionary -- equal to calling it on the
+    per-image counts and to_dicts() of the same batches.  split: a dict of split_objects' min_distance / min_radius / min_area; the
+    predicted and the GT objects alike are then cut apart (mgunet.split_objects) before they are counted and matched, still without
+    a host synchronisation.  None: objects are the connected components."""
+
+    def __init__(self, num_classes: int, device, connectivity: int = 2, min_area: int = 0, iou_thresh: float = 0.5, smooth: float = 1e-6,
+                 split: dict = None):
+        super().__init__(num_classes, device, connectivity, min_area, split)
+        self.iou_thresh, self.smooth = float(iou_thresh), smooth
         self.reset()
 
     def reset(self) -> None:
@@ -378,27 +417,9 @@ class YieldEvaluator:
 
     def update(self, logits_nchw: torch.Tensor, masks: torch.Tensor) -> None:
         """Add one batch: logits (B, C, H, W) float32 -- the view UNet.forward returns -- and integer masks (B, H, W)."""
-        if not logits_nchw.is_cuda or logits_nchw.device != self.device:
-            raise RuntimeError(f"logits must live on {self.device}")
-        src, kind, B, H, W, C = _source(logits_nchw)
-        if kind != 1:
-            raise TypeError("expected (B, C, H, W) float32 logits")
-        if C != self.num_classes:
-            raise ValueError(f"logits have {C} classes, the evaluator {self.num_classes}")
-        if tuple(masks.shape) != (B, H, W):
-            raise ValueError(f"masks shape {tuple(masks.shape)} does not match logits {(B, H, W)}")
-        masks = masks.to(self.device, torch.int64).contiguous()
+        src, masks, B, H, W, C = self._batch(logits_nchw, masks)
         bufs = self._buffers(B, H, W)
-        counts, offsets = {}, {}
-        for side, s, k, cc, ncls, amin in (("gt", masks, 0, 0, self.num_classes, 0), ("pred", src, 1, C, 0, self.min_area)):
-            lab, cls, bbox = bufs[side]
-            lab = lab[:B * H * W].view(B, H, W)
-            counts[side] = torch.empty(B, device=self.device, dtype=torch.int64)
-            offsets[side] = torch.empty(B + 1, device=self.device, dtype=torch.int64)
-            _label(s, k, B, H, W, cc, self.connectivity, 0, ncls, amin, lab, counts[side], offsets[side])
-            if self._split is not None:   # in place: the split has read the components before it writes the objects
-                _split(lab, B, H, W, self._split, lab, counts[side], offsets[side])
-            _stats(lab, s, k, B, H, W, cc, offsets[side], self._cap, cls, bbox)
+        counts, offsets = self._label_sides(src, masks, B, H, W, C, bufs)
         (gl, gc, gb), (pl, pc, pb) = bufs["gt"], bufs["pred"]
         _lib.call("mgu_match_objects", self.device, B, offsets["gt"], gc, gb, self._cap, offsets["pred"], pc, pb, self._cap, self.iou_thresh,
                   self.totals)
@@ -419,17 +440,5 @@ def evaluate_yield(model, loader, num_classes=None, connectivity=2, min_area=0, 
     """Yield estimation over `loader`'s (images, masks) batches: logits = model(images) under torch.no_grad() in eval mode, objects
     labelled (and, with `split`, cut apart: see YieldEvaluator) and matched on the device.  Returns yield_estimation_metrics'
     dictionary; the model's training flag is restored."""
-    dev = next(model.parameters()).device
-    C = int(num_classes if num_classes is not None else model.num_classes)
-    ev = YieldEvaluator(C, dev, connectivity=connectivity, min_area=min_area, iou_thresh=iou_thresh, smooth=smooth, split=split)
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            for images, masks in loader:
-                out = model(images.to(dev))
-                logits = out[0] if isinstance(out, (tuple, list)) else out
-                ev.update(logits, masks.to(dev))
-        return ev.compute()
-    finally:
-        model.train(was_training)
+    return _evaluate(model, loader, num_classes, lambda C, dev: YieldEvaluator(
+        C, dev, connectivity=connectivity, min_area=min_area, iou_thresh=iou_thresh, smooth=smooth, split=split))

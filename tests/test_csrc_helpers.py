@@ -1,5 +1,6 @@
 """Guard against the next paste: each shared device / launch helper of csrc/ has ONE definition, and the kernel files declare no
-vector typedefs of their own (csrc/device.h, common.h and ctx.h are where they live).  Source text only: no GPU, no build."""
+vector typedefs of their own (csrc/device.h, common.h and ctx.h are where they live; objects_common.h for what only the object-level
+kernel files share).  Source text only: no GPU, no build."""
 import glob
 import os
 import re
@@ -12,9 +13,12 @@ DEVICE_HELPERS = ["mfma_bf16", "split3_pack", "split3_pack_s", "x3_add", "x3_sub
                   "lds_barrier_builtin", "lds_barrier_fenced", "wave_sum", "wave_min", "wave_max", "block_fold", "enc_ordered",
                   "dec_ordered", "graph_of"]
 HOST_HELPERS = ["grid_for", "aligned16", "rup", "ensure"]
+# objects.hip, shapes.hip, split.hip, instances.hip: the wave group-by, the two scans, the pixel -> object rule (objects_common.h)
+OBJECT_HELPERS = ["wave_by_key", "block_exclusive_scan", "chunk_sum_scan", "object_index", "objects_recorded"]
 # names the private copies went by
 RETIRED = ["f32x4c", "f32x4n", "f32x4r", "u32x4_t", "x3_static_for", "scalar_fma", "ww_barrier", "gat_enc_ordered", "gat_dec_ordered",
-           "gf_enc_ordered", "gf_dec_ordered", "wave_sum64", "fold_doubles", "nblocks", "nblk", "nb", "al16", "align256"]
+           "gf_enc_ordered", "gf_dec_ordered", "wave_sum64", "fold_doubles", "nblocks", "nblk", "nb", "al16", "align256", "LEADER_ROUNDS",
+           "SH_ROUNDS"]
 
 
 def definitions(name):
@@ -35,6 +39,17 @@ def test_kernel_files_declare_no_vector_types_and_retired_names_are_gone():
     assert [f for f, t in SOURCES.items() if f.endswith(".hip") and "ext_vector_type" in t] == []
     assert {n: definitions(n) for n in RETIRED if definitions(n)} == {}
     assert [(f, n) for f, t in SOURCES.items() for n in RETIRED[:4] if re.search(r"\b" + n + r"\b", t)] == []
+
+
+def test_object_helpers_live_in_objects_common_h_only():
+    """one definition each, in objects_common.h; the private round counts of the wave group-by copies are gone (they were constants,
+    so the text is searched), and no kernel file spells the group-by's loop or a Hillis-Steele scan of its own"""
+    where = {n: definitions(n) for n in OBJECT_HELPERS}
+    assert {n: w for n, w in where.items() if [f for f, _ in w] != ["objects_common.h"]} == {}
+    assert [(f, n) for f, t in SOURCES.items() for n in RETIRED[-2:] if re.search(r"\b" + n + r"\b", t)] == []
+    family = ["objects.hip", "shapes.hip", "split.hip", "instances.hip"]
+    assert [f for f in family if '#include "objects_common.h"' not in SOURCES[f]] == []
+    assert [f for f in family if re.search(r"for \([^)]*\) \{\s*const unsigned long long act = __ballot|SCAN_THREADS\s*=|sh\[tid - off\]", SOURCES[f])] == []
 
 
 PACK_BODIES = ["pack_wino_w_body", "pack_first_w_body", "pack_first_mfma_body", "pack_convt_x3_body", "pack_bias_tile_body",
