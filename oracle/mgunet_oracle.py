@@ -672,39 +672,46 @@ def feature_consistency_loss(f_unet: torch.Tensor, f_graph: torch.Tensor, y: tor
     return per.sum(dim=1).mean()  # :123
 
 
-def _ellipse_object_term(mask: torch.Tensor, eps: float):
+def _ellipse_object_term(mask: torch.Tensor, eps: float, dtype=torch.float32):
     """One object of EllipticalShapeLoss (shape_loss.py:100-144 / :155-175): mean over its pixels of (p^T S^-1 p - 1)^2 with S the
-    sample covariance (torch.cov: divisor N - 1) of the centred (row, col) coordinates plus eps I; None if it is skipped."""
+    sample covariance (torch.cov: divisor N - 1) of the centred (row, col) coordinates plus eps I; None if it is skipped.
+    dtype = float32 is the reference's own arithmetic, N x N product included; any other dtype (float64: the yardstick of the
+    kernel tests) runs the same steps in it and takes the diagonal of that product row by row, without forming the N x N matrix."""
     if mask.sum() < 10:  # :96, :100, :157
         return None
-    coords = torch.nonzero(mask, as_tuple=False).float()  # :104
+    coords = torch.nonzero(mask, as_tuple=False).to(dtype)  # :104
     centred = coords - coords.mean(dim=0)  # :110-113
     cov = torch.cov(centred.T)  # :131
-    inv = torch.inverse(cov + eps * torch.eye(2))  # :137
-    mah = torch.diag(centred @ inv @ centred.T)  # :143
+    inv = torch.inverse(cov + eps * torch.eye(2, dtype=dtype))  # :137
+    if dtype == torch.float32:
+        mah = torch.diag(centred @ inv @ centred.T)  # :143
+    else:
+        mah = ((centred @ inv) * centred).sum(dim=1)  # the same diagonal entries
     return torch.mean((mah - 1.0) ** 2)  # :145
 
 
-def elliptical_shape_loss(segmentation_probs: torch.Tensor = None, object_masks_list=None, eps: float = 1e-6) -> torch.Tensor:
+def elliptical_shape_loss(segmentation_probs: torch.Tensor = None, object_masks_list=None, eps: float = 1e-6,
+                          dtype=torch.float32) -> torch.Tensor:
     """EllipticalShapeLoss.forward, model/unet/shape_loss.py:17-180: with masks, every listed object; without, the arg-max == 1
-    region of each image as ONE object (:61-98); objects under 10 pixels are skipped; mean over the processed objects, 0 if none."""
+    region of each image as ONE object (:61-98); objects under 10 pixels are skipped; mean over the processed objects, 0 if none.
+    `dtype`: the precision of every object's term (see _ellipse_object_term)."""
     terms = []
     if object_masks_list is None:
         B, C, _, _ = segmentation_probs.shape
         if C <= 1:
-            return torch.tensor(0.0)  # :63-64
+            return torch.tensor(0.0, dtype=dtype)  # :63-64
         labels = torch.argmax(segmentation_probs, dim=1)  # :74
         for b in range(B):
-            t = _ellipse_object_term(labels[b] == 1, eps)  # :68, :94-98
+            t = _ellipse_object_term(labels[b] == 1, eps, dtype)  # :68, :94-98
             if t is not None:
                 terms.append(t)
     else:
         for masks in object_masks_list:
             for m in masks:
-                t = _ellipse_object_term(m, eps)
+                t = _ellipse_object_term(m, eps, dtype)
                 if t is not None:
                     terms.append(t)
-    return torch.stack(terms).sum() / len(terms) if terms else torch.tensor(0.0)  # :147, :177
+    return torch.stack(terms).sum() / len(terms) if terms else torch.tensor(0.0, dtype=dtype)  # :147, :177
 
 
 # --------------------------------------------------------------------------------------

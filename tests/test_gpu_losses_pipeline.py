@@ -147,9 +147,9 @@ def test_elliptical_shape_loss_vs_reference_fixture(cuda, golden):
     # a full-size case: four 512 x 512 objects, against the float64 oracle
     yy, xx = np.mgrid[0:512, 0:512]
     big = [[torch.from_numpy(((yy - 250) / (60 + 30 * k)) ** 2 + ((xx - 260) / (150 - 20 * k)) ** 2 <= 1) for k in range(4)]]
-    ref = O.elliptical_shape_loss(None, [[m for m in big[0]]], 1e-6)
+    ref = O.elliptical_shape_loss(None, [[m for m in big[0]]], 1e-6, dtype=torch.float64)
     got = mgunet.EllipticalShapeLoss()(None, object_masks_list=[[m.to(cuda) for m in big[0]]])
-    assert close(got, ref, 1e-3), (float(got), float(ref))      # fp32 reference: its N x N Mahalanobis product loses digits at 5e4 pixels
+    assert close(got, ref, 5e-7), (float(got), float(ref))      # double arithmetic cast to float (the fp32 oracle loses digits at 5e4 pixels)
 
 
 def test_feature_fusion_resize_and_region_map_vs_reference_fixture(cuda, golden):
