@@ -493,6 +493,31 @@ int mgu_split_objects(mgu_ctx* ctx, const int32_t* labels_dev, int B, int H, int
                       int32_t* labels_out_dev, int64_t* counts_dev, int64_t* offsets_dev, int32_t* d2_out_dev, uint8_t* seeds_out_dev,
                       void* hip_stream);
 
+/* ---- mask cleanup: close gaps, fill holes, open away spurs --------------------------------------------------------------------------
+ * The stage between "argmax" and "label": a pin hole inside an object collapses its inscribed disc and mgu_split_objects then counts
+ * the object several times.  Integer and bit arithmetic only: bitwise repeatable.
+ * Input: src_dev / src_kind / C as mgu_connected_components takes them (0: int64 class map (B,H,W) with num_classes given; 1: NHWC
+ * fp32 logits with the argmax fused, first maximal class, bit-identical to mgu_argmax_classes; num_classes is then C).  Foreground
+ * classes are 1 .. num_classes-1 (2 <= num_classes <= 32); every other value (0, -100, out of range) reads as background, and
+ * background is written as 0.  out_dev: int64 (B,H,W) class map; it must not overlap the input.  Images never interact.
+ * A disc of squared radius r2 is D = {d in Z^2 : |d|^2 <= r2}, 0 <= r2 <= 64; r2 = 0 skips the stage.  Three stages, in this order:
+ *   1. Close (close_radius_sq).  For each foreground class c, A_c = {m = c}, on an infinite plane whose pixels outside the image are
+ *      background: Dil_c = A_c (+) D, Clo_c = {p inside the image : p + D inside Dil_c}.  A background pixel takes the smallest c
+ *      with p in Clo_c; foreground pixels never change.
+ *   2. Fill holes (fill_holes != 0).  The 4-connected components of the background of the stage-1 result (the complement of
+ *      8-connected foreground, as scipy.ndimage.binary_fill_holes).  A component is a hole when it has no pixel on the image border,
+ *      its area is <= max_hole_area (when max_hole_area > 0) and every foreground 4-neighbour of its pixels holds one class c; a
+ *      hole becomes c.  A pocket bordered by two classes stays; an island inside a hole is untouched.
+ *   3. Open (open_radius_sq).  For each class c of the stage-2 result, E_c = {p in A_c : no pixel q of the image with value != c has
+ *      |p - q|^2 <= r2}: pixels outside the image do not erode, as in mgu_distance_transform, so an object cut by the frame keeps
+ *      its edge.  A pixel p of A_c stays c iff some q in E_c has |p - q|^2 <= r2, else it becomes 0.
+ * counts_dev (may be NULL): int64 (B,3), set to the pixels [gained by closing, filled, removed by opening] of every image.
+ * Close and open work on 64-pixel words of one class plane (tiles with a halo in LDS, below 64 KiB); fill labels the background with
+ * mgu_connected_components' union-find.  At most 8 kernel launches and 1 fill, whatever B, the classes and the holes; no host
+ * synchronisation; scratch from the context (18 bytes per pixel with fill_holes, else 2).  B <= 65535, B*H*W < 2^31. */
+int mgu_clean_masks(mgu_ctx* ctx, const void* src_dev, int src_kind, int B, int H, int W, int C, int64_t num_classes, int close_radius_sq,
+                    int fill_holes, int64_t max_hole_area, int open_radius_sq, int64_t* out_dev, int64_t* counts_dev, void* hip_stream);
+
 /* ---- instance evaluation: mask overlaps of two label maps, mask-IoU matching, panoptic totals ---------------------------------------
  * The objects of both sides are what mgu_connected_components / mgu_split_objects (labels, offsets) and mgu_object_stats (class,
  * area) write for the same B images: "gt" and "pred".  Object capacities are the lengths of the per-object arrays; an image whose

@@ -91,7 +91,8 @@ struct mgu_ctx {
   size_t ncws_bytes = 0;
   void* objws = nullptr;    // connected-component parents, areas, chunk counts and matching flags (objects.hip); the distance
                             // transform's column distances and the seed buckets and first-pixel tables of the split (split.hip);
-                            // the pair hash table, row degrees and unsorted pairs of the overlap table (instances.hip)
+                            // the pair hash table, row degrees and unsorted pairs of the overlap table (instances.hip); the uint8
+                            // class maps between the stages, the background labels and the per-hole counters of clean.hip
   size_t objws_bytes = 0;
   int in_ch = 0, ncls = 0, feat = 0, depth = 0, dtype = 0, Cp0 = 0;
   std::vector<Layer> layers;  // enc[i].conv1, enc[i].conv2 ..., bott.conv1, bott.conv2, dec[b].up, dec[b].conv1, dec[b].conv2 ..., final
@@ -316,14 +317,14 @@ int gat_prologue(mgu_ctx* c, const float* X, int N, int Fin, const float* panel,
                  int64_t E, const int32_t* gp, int G, float alpha, unsigned long long* gmax, unsigned gen, float* wh, float* st,
                  int32_t* node_graph, float* gm, bool record, hipStream_t s);
 
-// object labelling (objects.hip), shared with split.hip.  cc_roots_i32: P[g] = the smallest linear index (over the whole batch) of
-// the 8-connected same-value component of g in an int32 map (B, H, W), -1 where the map is 0.  cc_number_roots: given P with every
+// object labelling (objects.hip), shared with split.hip and clean.hip.  cc_roots_i32: P[g] = the smallest linear index (over the whole
+// batch) of the 8-connected (conn8 false: 4-connected) same-value component of g in an int32 map (B, H, W), -1 where the map is 0.  cc_number_roots: given P with every
 // foreground pixel pointing (directly or through a chain) at its object's first pixel, the tail of mgu_connected_components: objects
 // numbered per image in raster order of that pixel, the min_area filter (area: n counters, or nullptr with min_area 0), counts and
 // offsets.  cnt: cc_chunks(HW) * B ints, choff: as many int64.  (The device and host helpers the object-level files share beyond
 // these two entry points are in objects_common.h.)
 int64_t cc_chunks(int64_t HW);
-int cc_roots_i32(mgu_ctx* c, const int32_t* map, int B, int H, int W, int* P, hipStream_t s);
+int cc_roots_i32(mgu_ctx* c, const int32_t* map, int B, int H, int W, int* P, hipStream_t s, bool conn8 = true);
 int cc_number_roots(mgu_ctx* c, int* P, unsigned* area, int min_area, int B, int64_t HW, int* cnt, long long* choff, int32_t* labels,
                     int64_t* counts, int64_t* offsets, hipStream_t s);
 

@@ -99,6 +99,11 @@ __device__ __forceinline__ T wave_sum(T v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
   return v;
 }
+__device__ __forceinline__ unsigned wave_or(unsigned v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v |= __shfl_xor(v, off);
+  return v;
+}
 __device__ __forceinline__ int wave_min(int v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off));

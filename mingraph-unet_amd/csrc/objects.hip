@@ -11,8 +11,9 @@
 // whatever order the atomics land in, the trees' roots, and so the numbering, are the same -- the labels are deterministic.
 // All accumulations are integer atomics (exact, order-free); runs of equal labels are summed inside a wave before the atomic.
 // split.hip labels its int32 zone map through steps (1)-(3) (cc_roots_i32) and numbers its own objects through (3)-(4)
-// (cc_number_roots, the tail of mgu_connected_components); both are declared in ctx.h.  The wave pre-aggregation (wave_by_key), the
-// scans and the pixel -> object rule are objects_common.h's, shared with shapes.hip and instances.hip.
+// (cc_number_roots, the tail of mgu_connected_components); clean.hip labels the background of a class map through (1)-(3) with
+// 4-neighbours; both are declared in ctx.h.  The wave pre-aggregation (wave_by_key), the scans, the pixel -> object rule and the
+// value of a pixel (pix_key) are objects_common.h's, shared with shapes.hip, instances.hip and clean.hip.
 #include "objects_common.h"
 
 namespace mgu {
@@ -22,27 +23,6 @@ constexpr int OB_THREADS = 256;
 constexpr int TILE = 32;                      // labelling tile: TILE x TILE pixels, 4 per thread
 constexpr int TILE_PIX = TILE * TILE;
 constexpr int CHUNK = 4 * OB_THREADS;         // root numbering: 1024 consecutive pixels of one image per workgroup
-
-// value of pixel g: the class map's entry (KIND 0 int64; 2 int32, the internal form of split.hip's zone map), or the first maximal
-// class of the logits (KIND 1, bit-identical to argmax_kernel)
-template <int KIND>
-__device__ __forceinline__ long long pix_key(const void* src, int64_t g, int C) {
-  if constexpr (KIND == 0) {
-    return reinterpret_cast<const long long*>(src)[g];
-  } else if constexpr (KIND == 2) {
-    return reinterpret_cast<const int*>(src)[g];
-  } else {
-    const float* p = reinterpret_cast<const float*>(src) + g * C;
-    float best = p[0];
-    int bi = 0;
-    for (int c = 1; c < C; ++c)
-      if (p[c] > best) {
-        best = p[c];
-        bi = c;
-      }
-    return bi;
-  }
-}
 
 // foreground: not the background value and, with a class range (ncls > 0), inside [0, ncls)
 __device__ __forceinline__ bool is_fg(long long v, long long bg, long long ncls) { return v != bg && (ncls <= 0 || (v >= 0 && v < ncls)); }
@@ -379,11 +359,16 @@ namespace mgud {
 
 int64_t cc_chunks(int64_t HW) { return (HW + CHUNK - 1) / CHUNK; }
 
-int cc_roots_i32(mgu_ctx* c, const int32_t* map, int B, int H, int W, int* P, hipStream_t s) {
+int cc_roots_i32(mgu_ctx* c, const int32_t* map, int B, int H, int W, int* P, hipStream_t s, bool conn8) {
   const dim3 tiles((W + TILE - 1) / TILE, (H + TILE - 1) / TILE, B);
   const int64_t n = (int64_t)B * H * W;
-  hipLaunchKernelGGL((cc_local_kernel<2, true>), tiles, dim3(OB_THREADS), 0, s, map, H, W, 0, 0ll, 0ll, P);
-  hipLaunchKernelGGL((cc_border_kernel<2, true>), tiles, dim3(128), 0, s, map, H, W, 0, P);
+  if (conn8) {
+    hipLaunchKernelGGL((cc_local_kernel<2, true>), tiles, dim3(OB_THREADS), 0, s, map, H, W, 0, 0ll, 0ll, P);
+    hipLaunchKernelGGL((cc_border_kernel<2, true>), tiles, dim3(128), 0, s, map, H, W, 0, P);
+  } else {
+    hipLaunchKernelGGL((cc_local_kernel<2, false>), tiles, dim3(OB_THREADS), 0, s, map, H, W, 0, 0ll, 0ll, P);
+    hipLaunchKernelGGL((cc_border_kernel<2, false>), tiles, dim3(128), 0, s, map, H, W, 0, P);
+  }
   hipLaunchKernelGGL(cc_flatten_kernel, dim3(grid_for(n, OB_THREADS, INT_MAX)), dim3(OB_THREADS), 0, s, P, n, (unsigned*)nullptr);
   HIPCHK(c, hipGetLastError());
   return MGU_OK;

@@ -1,6 +1,6 @@
-// Helpers shared by the object-level kernel files (objects.hip, shapes.hip, split.hip, instances.hip): each is defined here and
+// Helpers shared by the object-level kernel files (objects.hip, shapes.hip, split.hip, instances.hip, clean.hip): each is defined here and
 // nowhere else under csrc/ (tests/test_csrc_helpers.py).  device.h keeps what every kernel file shares.
-//   device: wave_by_key | block_exclusive_scan | chunk_sum_scan | object_index | objects_recorded
+//   device: wave_by_key | block_exclusive_scan | chunk_sum_scan | object_index | objects_recorded | pix_key
 //   host:   check_pixel_count | clear_counts
 #pragma once
 #include <climits>
@@ -92,6 +92,30 @@ __device__ __forceinline__ long long object_index(int lab, const long long* __re
 // rows of the per-object arrays in use: every object of the batch, or as many as the arrays hold
 __device__ __forceinline__ int64_t objects_recorded(const long long* __restrict__ offsets, int B, int64_t cap) {
   return offsets[B] < cap ? offsets[B] : cap;
+}
+
+// ---- the value of a pixel ---------------------------------------------------------------------------------------------------------
+// value of pixel g: the class map's entry (KIND 0 int64; 2 int32, the internal form of split.hip's zone map; 3 uint8, the internal
+// form of clean.hip's class maps), or the first maximal class of the logits (KIND 1, bit-identical to argmax_kernel)
+template <int KIND>
+__device__ __forceinline__ long long pix_key(const void* src, int64_t g, int C) {
+  if constexpr (KIND == 0) {
+    return reinterpret_cast<const long long*>(src)[g];
+  } else if constexpr (KIND == 2) {
+    return reinterpret_cast<const int*>(src)[g];
+  } else if constexpr (KIND == 3) {
+    return reinterpret_cast<const unsigned char*>(src)[g];
+  } else {
+    const float* p = reinterpret_cast<const float*>(src) + g * C;
+    float best = p[0];
+    int bi = 0;
+    for (int c = 1; c < C; ++c)
+      if (p[c] > best) {
+        best = p[c];
+        bi = c;
+      }
+    return bi;
+  }
 }
 
 }  // namespace mgu

@@ -257,11 +257,12 @@ class InstanceEvaluator(_ObjectEvaluator):
     at every threshold in score order and accumulates the panoptic totals; the per-prediction records (class, score, one TP bit per
     threshold) are kept on the device and the host is never blocked.  Every buffer is sized once for the worst case (every pixel its
     own object), the records included: 12 bytes per pixel of every batch until reset().  compute() synchronises once and returns
-    instance_metrics' dictionary; it raises if the overlap table's status is non-zero."""
+    instance_metrics' dictionary; it raises if the overlap table's status is non-zero.  clean: as YieldEvaluator's -- the predicted
+    class map is cleaned (mgunet.clean_masks) before it is labelled and split; scores still come from the logits."""
 
     def __init__(self, num_classes: int, device, connectivity: int = 2, min_area: int = 0, thresholds=None, split: dict = None,
-                 smooth: float = 1e-6):
-        super().__init__(num_classes, device, connectivity, min_area, split)
+                 smooth: float = 1e-6, clean: dict = None):
+        super().__init__(num_classes, device, connectivity, min_area, split, clean)
         self.smooth = smooth
         self.thresholds = _thresholds(thresholds)
         T = self.thresholds.size
@@ -284,6 +285,8 @@ class InstanceEvaluator(_ObjectEvaluator):
             b["scores"] = mk(n, torch.float32)
             b["pairs"] = (mk(n + 1, torch.int64), mk(n, torch.int64), mk(n, torch.int64))
             b["match"] = (mk((T, n), torch.int64), mk((T, n), torch.float64))
+            if self._clean is not None:
+                b["clean"] = mk(n, torch.int64)
             self._bufs, self._cap = b, n
         return self._bufs
 
@@ -323,8 +326,9 @@ class InstanceEvaluator(_ObjectEvaluator):
         return instance_metrics(cls, score, tp, gt_per_class, pq, self.thresholds, self.smooth)
 
 
-def evaluate_instances(model, loader, num_classes=None, connectivity=2, min_area=0, thresholds=None, split=None, smooth=1e-6) -> dict:
+def evaluate_instances(model, loader, num_classes=None, connectivity=2, min_area=0, thresholds=None, split=None, smooth=1e-6,
+                       clean=None) -> dict:
     """Instance evaluation over `loader`'s (images, masks) batches: logits = model(images) under torch.no_grad() in eval mode, then
     InstanceEvaluator.  Returns instance_metrics' dictionary; the model's training flag is restored."""
     return _evaluate(model, loader, num_classes, lambda C, dev: InstanceEvaluator(
-        C, dev, connectivity=connectivity, min_area=min_area, thresholds=thresholds, split=split, smooth=smooth))
+        C, dev, connectivity=connectivity, min_area=min_area, thresholds=thresholds, split=split, smooth=smooth, clean=clean))

@@ -6,7 +6,8 @@ YieldEvaluator accumulates per-image counts and matching totals across batches w
 turns them into the reference's dictionary with the reference's own arithmetic (bitwise equal results).  object_shapes adds the
 per-object shape (csrc/shapes.hip): exact integer moments of the label map, a fitted ellipse and the per-instance term of
 EllipticalShapeLoss (model/unet/shape_loss.py:155-180).  split_objects cuts touching objects apart (csrc/split.hip): exact integer
-distance transform, one seed per inscribed disc, the power diagram of the discs.  There is no scipy or skimage dependency."""
+distance transform, one seed per inscribed disc, the power diagram of the discs.  clean_masks tidies the class map before any of
+this (csrc/clean.hip): closing, hole filling and opening on bit planes.  There is no scipy or skimage dependency."""
 from __future__ import annotations
 
 import math
@@ -83,6 +84,57 @@ def _source(x: torch.Tensor):
     m = x.reshape((1,) + tuple(x.shape)) if x.dim() == 2 else x
     B, H, W = m.shape
     return m.to(torch.int64).contiguous(), 0, B, H, W, 0
+
+
+def _clean_params(close_radius=0, fill_holes=True, max_hole_area=0, open_radius=0):
+    """(close_radius_sq, fill_holes, max_hole_area, open_radius_sq) as mgu_clean_masks takes them: floor(radius^2), 0..64 (a hair
+    is added before the floor, so that math.sqrt(13) squares to 13 and not to 12)."""
+    r2 = []
+    for name, r in (("close_radius", close_radius), ("open_radius", open_radius)):
+        if not r >= 0:
+            raise ValueError(f"{name} must be >= 0")
+        r2.append(math.floor(r * r + 1e-9))
+        if r2[-1] > 64:
+            raise ValueError(f"{name} {r}: the squared radius must stay within 64")
+    if max_hole_area < 0:
+        raise ValueError("max_hole_area must be >= 0")
+    return r2[0], int(bool(fill_holes)), int(max_hole_area), r2[1]
+
+
+def _clean(src, kind, B, H, W, C, num_classes, params, out, counts=None):
+    _lib.call("mgu_clean_masks", src.device, src, kind, B, H, W, C, int(num_classes), *params, out, counts)
+
+
+def clean_masks(x: torch.Tensor, num_classes: int = None, close_radius: float = 0, fill_holes: bool = True, max_hole_area: int = 0,
+                open_radius: float = 0, return_counts: bool = False):
+    """The class map of x with gaps closed, holes filled and spurs opened away, on the device: the stage between argmax and
+    connected_components / split_objects, whose distance transform a single pin hole inside a fruit breaks.
+
+    x: whatever connected_components takes -- an integer class map (H, W) or (B, H, W), for which num_classes is required, or
+    (B, C, H, W) float32 logits (argmax fused; num_classes is C).  Classes 1 .. num_classes - 1 (num_classes <= 32) are foreground;
+    every other value is background and comes out as 0.  Returns the int64 (B, H, W) class map; an (H, W) map is a batch of one.
+
+    With D(r) the disc {d : |d|^2 <= floor(r^2)}, r <= 8, three stages in this order, each skipped when its parameter is 0 / False:
+    close_radius -- a background pixel p takes the smallest class c whose dilation by D covers p + D (pixels outside the image are
+    background; foreground never changes); fill_holes -- a 4-connected background component that touches no image border, has at most
+    max_hole_area pixels (when > 0) and whose foreground 4-neighbours all hold one class becomes that class (a pocket between two
+    classes stays, an island inside a hole is untouched); open_radius -- a pixel of class c stays iff a pixel q of class c within D
+    of it has no image pixel of another value within D of q (pixels outside the image do not erode: an object cut by the frame keeps
+    its edge).  Not a per-object convex hull and no grey-level morphology.  Integer and bit arithmetic: bitwise repeatable; a fixed
+    number of launches and no host synchronisation.  return_counts: also the int64 (B, 3) pixels [gained by closing, filled, removed
+    by opening] per image."""
+    params = _clean_params(close_radius, fill_holes, max_hole_area, open_radius)
+    src, kind, B, H, W, C = _source(x)
+    if kind == 0 and num_classes is None:
+        raise ValueError("clean_masks: num_classes is required for a class map")
+    ncls = C if kind == 1 else int(num_classes)
+    if not 2 <= ncls <= 32:
+        raise ValueError(f"clean_masks: num_classes must be in 2..32, got {ncls}")
+    out = torch.empty((B, H, W), device=src.device, dtype=torch.int64)
+    counts = torch.zeros((B, 3), device=src.device, dtype=torch.int64) if return_counts else None
+    if out.numel():   # a batch without pixels has no storage to point at
+        _clean(src, kind, B, H, W, C, ncls, params, out, counts)
+    return (out, counts) if return_counts else out
 
 
 def _label(src, kind, B, H, W, C, connectivity, background, num_classes, min_area, labels, counts, offsets):
@@ -341,8 +393,16 @@ class _ObjectEvaluator:
     """What YieldEvaluator and InstanceEvaluator (instances.py) share: the constructor's checks, update()'s checks of a batch, and the
     objects of its two sides."""
 
-    def __init__(self, num_classes, device, connectivity, min_area, split):
+    def __init__(self, num_classes, device, connectivity, min_area, split, clean=None):
         _check_args(connectivity, min_area)
+        self._clean = None
+        if clean is not None:
+            extra = set(clean) - {"close_radius", "fill_holes", "max_hole_area", "open_radius"}
+            if extra:
+                raise ValueError(f"clean takes close_radius, fill_holes, max_hole_area and open_radius, not {sorted(extra)}")
+            self._clean = _clean_params(**clean)
+            if not 2 <= int(num_classes) <= 32:
+                raise ValueError("clean needs 2 <= num_classes <= 32")
         self._split = None
         if split is not None:
             extra = set(split) - {"min_distance", "min_radius", "min_area"}
@@ -374,9 +434,15 @@ class _ObjectEvaluator:
     def _label_sides(self, src, masks, B, H, W, C, bufs):
         """Label, split (when asked) and take the statistics of the GT objects (mask values in [1, num_classes)) and of the predicted
         objects (argmax fused, min_area) into bufs[side] = (labels, class, bbox[, area]), worst-case buffers of self._cap rows: no
-        host synchronisation.  Returns the two sides' counts and offsets."""
+        host synchronisation.  With `clean`, the predicted side is the cleaned class map (bufs["clean"], mgunet.clean_masks) in the
+        place of the logits; the GT stays as annotated.  Returns the two sides' counts and offsets."""
         counts, offsets = {}, {}
-        for side, s, k, cc, ncls, amin in (("gt", masks, 0, 0, self.num_classes, 0), ("pred", src, 1, C, 0, self.min_area)):
+        pred = (src, 1, C, 0)
+        if self._clean is not None:
+            cm = bufs["clean"][:B * H * W].view(B, H, W)
+            _clean(src, 1, B, H, W, C, C, self._clean, cm)
+            pred = (cm, 0, 0, self.num_classes)
+        for side, s, k, cc, ncls, amin in (("gt", masks, 0, 0, self.num_classes, 0), ("pred", *pred, self.min_area)):
             lab, cls, bbox, *area = bufs[side]
             lab = lab[:B * H * W].view(B, H, W)
             counts[side] = torch.empty(B, device=self.device, dtype=torch.int64)
@@ -395,11 +461,13 @@ class YieldEvaluator(_ObjectEvaluator):
     predicted objects.  compute() synchronises once and returns yield_estimation_metrics' dictionary -- equal to calling it on the
     per-image counts and to_dicts() of the same batches.  split: a dict of split_objects' min_distance / min_radius / min_area; the
     predicted and the GT objects alike are then cut apart (mgunet.split_objects) before they are counted and matched, still without
-    a host synchronisation.  None: objects are the connected components."""
+    a host synchronisation.  None: objects are the connected components.  clean: a dict of clean_masks' close_radius / fill_holes /
+    max_hole_area / open_radius; the predicted class map is then cleaned (mgunet.clean_masks) before it is labelled (min_area) and
+    split -- the GT stays as annotated -- still without a host synchronisation.  None: the argmax map is labelled as it is."""
 
     def __init__(self, num_classes: int, device, connectivity: int = 2, min_area: int = 0, iou_thresh: float = 0.5, smooth: float = 1e-6,
-                 split: dict = None):
-        super().__init__(num_classes, device, connectivity, min_area, split)
+                 split: dict = None, clean: dict = None):
+        super().__init__(num_classes, device, connectivity, min_area, split, clean)
         self.iou_thresh, self.smooth = float(iou_thresh), smooth
         self.reset()
 
@@ -412,6 +480,8 @@ class YieldEvaluator(_ObjectEvaluator):
         if n > self._cap:   # per-object arrays sized for the worst case (every pixel its own object): no host synchronisation
             mk = lambda shape, dt: torch.empty(shape, device=self.device, dtype=dt)  # noqa: E731
             self._bufs = {s: (mk(n, torch.int32), mk(n, torch.int64), mk((n, 4), torch.int32)) for s in ("gt", "pred")}
+            if self._clean is not None:
+                self._bufs["clean"] = mk(n, torch.int64)
             self._cap = n
         return self._bufs
 
@@ -436,9 +506,9 @@ class YieldEvaluator(_ObjectEvaluator):
         return _yield_dict(gt, pred, (n_gt, n_match, 0, 0), self.smooth)
 
 
-def evaluate_yield(model, loader, num_classes=None, connectivity=2, min_area=0, iou_thresh=0.5, smooth=1e-6, split=None) -> dict:
-    """Yield estimation over `loader`'s (images, masks) batches: logits = model(images) under torch.no_grad() in eval mode, objects
-    labelled (and, with `split`, cut apart: see YieldEvaluator) and matched on the device.  Returns yield_estimation_metrics'
-    dictionary; the model's training flag is restored."""
+def evaluate_yield(model, loader, num_classes=None, connectivity=2, min_area=0, iou_thresh=0.5, smooth=1e-6, split=None, clean=None) -> dict:
+    """Yield estimation over `loader`'s (images, masks) batches: logits = model(images) under torch.no_grad() in eval mode, the
+    predicted class map cleaned (with `clean`), objects labelled (and, with `split`, cut apart: see YieldEvaluator) and matched on the
+    device.  Returns yield_estimation_metrics' dictionary; the model's training flag is restored."""
     return _evaluate(model, loader, num_classes, lambda C, dev: YieldEvaluator(
-        C, dev, connectivity=connectivity, min_area=min_area, iou_thresh=iou_thresh, smooth=smooth, split=split))
+        C, dev, connectivity=connectivity, min_area=min_area, iou_thresh=iou_thresh, smooth=smooth, split=split, clean=clean))
