@@ -3,7 +3,9 @@ against the oracle's per-head forward (model/gat/graph_attention.py:40-118, 150-
   aggregate-first (Fin <= F': gat_stmax_kernel + gat_fused2_kernel, 2 launches) and the Wh-row gather (GEMM + gat_edge_max +
   gat_aggregate, forced with MGU_NO_GAT_FUSED=1 in a context of its own), on block-diagonal patch graphs (the fast path of the
   gather kernel: every row <= 4 in-edges), a ragged random graph (rows with 0..11 in-edges, isolated nodes, a tail that is not
-  a multiple of the kernels' row groups) and repeated calls (the two alternating per-graph max arrays)."""
+  a multiple of the kernels' row groups) and repeated calls (the two alternating per-graph max arrays).
+Every other template instance of both schedules, hubs of up to 129 in-edges, heads up to 32 and the bar against float64 are in
+tests/test_gpu_gat_f64.py (cases: tests/gat_cases.py)."""
 import ctypes as C
 import os
 

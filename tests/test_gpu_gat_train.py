@@ -1,7 +1,9 @@
 """GAT training on the HIP path: mgu_gat_layer_backward behind the autograd nodes of mgunet.GATNetwork, against the gradients
 the REFERENCE GATNetwork produced under torch autograd (tests/golden/gat_grad.npz; eval-mode dropout: the reference's train-mode
 dropout draws from torch's RNG stream).  Tolerance: relative to max|gradient|, 2e-5 + 20 x the deviation of
-the reference's own fp32 gradients from float64 (the wide-logit case is conditioned like 5e-6)."""
+the reference's own fp32 gradients from float64 (the wide-logit case is conditioned like 5e-6).
+The backward at hubs, concat with several heads, tied arg-max edges, three row blocks and padded module widths, against float64, is
+in tests/test_gpu_gat_f64.py (cases: tests/gat_cases.py)."""
 import numpy as np
 import pytest
 import torch
