@@ -623,7 +623,8 @@ int mgu_elliptical_shape_loss_objects(mgu_ctx* ctx, int B, const int64_t* offset
 int mgu_tta_views(mgu_ctx* ctx, const float* img_dev, int B, int C, int H, int W, const int64_t* in_strides, int G, const int32_t* views,
                   float* out_dev, void* hip_stream);
 /* Merge: for every output pixel (b, y, x) and view k (in order), the softmax (fp32, maximum subtracted, expf) of the C logits of the
- * view pixel that the view's transform moved (y, x) to, summed in fp32 and multiplied by 1/K.  The logits are the NHWC output of the
+ * view pixel that the view's transform moved (y, x) to, summed in fp64 and multiplied by 1/K (exact), rounded to fp32 once:
+ * the mean of the views' fp32 softmaxes with one fp32 rounding; equal softmaxes average to themselves.  The logits are the NHWC output of the
  * forward of each shape group: group 0 = the views with r even (every view when H == W), (G0*B, H, W, C); group 1 = the views with r
  * odd when H != W, (G1*B, W, H, C) (logits1_dev may be NULL when no view is in it).  views: HOST int32 (K, 4) rows {group, slot, flip,
  * r}: view k is image slot*B + b of its group.  K in {1, 2, 4, 8}, C <= 16.  Writes probs_dev NHWC fp32 (B,H,W,C), labels_dev

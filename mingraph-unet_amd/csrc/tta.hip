@@ -6,7 +6,9 @@
 // Quarter turns 1 and 3 swap H and W, so for H != W a view belongs to the (H, W) group (r even) or the (W, H) group (r odd); each group
 // is one forward.  Both kernels are per-pixel gathers with the index arithmetic of mgunet.tta.view_source_index / view_inverse_index:
 // the views kernel reads the source pixel of every view pixel, the merge kernel reads the view pixel of every output pixel.  Each
-// output value depends on one pixel's C logits per view only, summed in view order: the result does not depend on the launch shape.
+// output value depends on one pixel's C logits per view only: the result does not depend on the launch shape.  The views' fp32
+// softmaxes are added in fp64, which has 29 bits to spare over a sum of 8 fp32 values, and the mean is rounded to fp32 once: equal
+// softmaxes average to themselves for every K (a sequential fp32 sum of 8 times fl(1/3) is 1 ulp off 8 fl(1/3)), whatever the order.
 #include <algorithm>
 
 #include "ctx.h"
@@ -70,9 +72,10 @@ __global__ __launch_bounds__(TTA_T * TTA_T) void tta_views_kernel(const float* _
 }
 
 // one thread per output pixel: for each view (in order) the softmax of the mapped pixel's C logits (fp32, maximum subtracted, expf),
-// summed in fp32, times 1/K; then the first maximal class and its probability.  NC > 0: C == NC; NC == 0: C <= TTA_MAX_C at run time.
+// summed in fp64, times 1/K (exact), rounded to fp32 once; then the first maximal class and its probability.  NC > 0: C == NC;
+// NC == 0: C <= TTA_MAX_C at run time.
 template <int NC>
-__global__ __launch_bounds__(TTA_T * TTA_T) void tta_merge_kernel(TtaGroups g, int B, int Crt, int H, int W, int K, TtaViews views, float invK,
+__global__ __launch_bounds__(TTA_T * TTA_T) void tta_merge_kernel(TtaGroups g, int B, int Crt, int H, int W, int K, TtaViews views, double invK,
                                                                   float* __restrict__ probs, long long* __restrict__ labels,
                                                                   float* __restrict__ conf) {
   constexpr int CM = NC > 0 ? NC : TTA_MAX_C;
@@ -80,9 +83,9 @@ __global__ __launch_bounds__(TTA_T * TTA_T) void tta_merge_kernel(TtaGroups g, i
   const int b = blockIdx.z;
   const int x = blockIdx.x * TTA_T + (threadIdx.x & (TTA_T - 1)), y = blockIdx.y * TTA_T + (threadIdx.x / TTA_T);
   if (y >= H || x >= W) return;
-  float acc[CM];
+  double acc[CM];
 #pragma unroll
-  for (int c = 0; c < CM; ++c) acc[c] = 0.f;
+  for (int c = 0; c < CM; ++c) acc[c] = 0.0;
   for (int v = 0; v < K; ++v) {
     const int code = views.code[v], flip = code & 3, r = (code >> 2) & 3, slot = (code >> 4) & 15, grp = code >> 8;
     const int Wg = (r & 1) ? H : W, Hg = (r & 1) ? W : H;
@@ -94,7 +97,7 @@ __global__ __launch_bounds__(TTA_T * TTA_T) void tta_merge_kernel(TtaGroups g, i
     const float sum = pixel_softmax<CM>(p, C, e);
 #pragma unroll
     for (int c = 0; c < CM; ++c)
-      if (c < C) acc[c] += e[c] / sum;
+      if (c < C) acc[c] += (double)(e[c] / sum);
   }
   const int64_t pix = ((int64_t)b * H + y) * W + x;
   float best = 0.f;
@@ -102,7 +105,7 @@ __global__ __launch_bounds__(TTA_T * TTA_T) void tta_merge_kernel(TtaGroups g, i
 #pragma unroll
   for (int c = 0; c < CM; ++c)
     if (c < C) {
-      const float q = acc[c] * invK;
+      const float q = (float)(acc[c] * invK);
       probs[pix * C + c] = q;
       if (c == 0 || q > best) best = q, bi = c;
     }
@@ -163,7 +166,7 @@ int mgu_tta_merge(mgu_ctx* c, const float* logits0_dev, const float* logits1_dev
   const dim3 grid((W + TTA_T - 1) / TTA_T, (H + TTA_T - 1) / TTA_T, B);
   hipStream_t s = (hipStream_t)hip_stream;
   long long* lab = (long long*)labels_dev;
-  const float invK = 1.f / (float)K;
+  const double invK = 1.0 / (double)K;
   switch (C) {
     case 1: hipLaunchKernelGGL(tta_merge_kernel<1>, grid, dim3(TTA_T * TTA_T), 0, s, g, B, C, H, W, K, v, invK, probs_dev, lab, conf_dev); break;
     case 2: hipLaunchKernelGGL(tta_merge_kernel<2>, grid, dim3(TTA_T * TTA_T), 0, s, g, B, C, H, W, K, v, invK, probs_dev, lab, conf_dev); break;

@@ -10,6 +10,7 @@ import torch
 import mgunet
 import mgunet_oracle as O
 import tiled_oracle as TO
+import tta_oracle as VO
 from mgunet import _lib
 from mgunet.tiled import TilePlan
 
@@ -97,13 +98,23 @@ def test_gather_u8_is_the_preprocessor_crop(cuda, B, H, W, tile, overlap, bgr):
 
 # ---- 2. merge on exact data --------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("Cls", [2, 3, 4, 5])
+@pytest.mark.parametrize("Cls", [1, 2, 3, 4, 5, 8, 16])
 def test_merge_exact_on_one_hot_tiles(cuda, Cls):
     """24 x 24 images, 16 x 16 tiles, overlap 8, flat window: coverage 1, 2 and 4, weights 1, 1/2 and 1/4.  Logits 0 / -200 make the
     fp32 softmax exactly one-hot (expf(-200) = 0), so every probability is a multiple of 1/4 and must come out bit for bit."""
-    B, H, W, T, o = 2, 24, 24, 16, 8
+    one_hot_tiles_exact(cuda, Cls, 24)
+
+
+def test_merge_exact_on_one_hot_tiles_odd_width(cuda):
+    """The same on 24 x 23 images (column origins [0, 7]): two classes at an odd width run tile_accumulate_kernel<2, 1>, the one
+    instantiation the even width above leaves to the random logits."""
+    one_hot_tiles_exact(cuda, 2, 23)
+
+
+def one_hot_tiles_exact(cuda, Cls, W):
+    B, H, T, o = 2, 24, 16, 8
     plan = TilePlan(B, H, W, T, o, "flat", cuda)
-    assert (plan.origins_y, plan.origins_x) == ([0, 8], [0, 8])
+    assert (plan.origins_y, plan.origins_x) == ([0, 8], [0, W - T])
     cover = np.outer(TO.coverage(H, T, plan.origins_y), TO.coverage(W, T, plan.origins_x))
     assert sorted(set(cover.ravel())) == [1, 2, 4]
     rng = np.random.default_rng(Cls)
@@ -123,11 +134,16 @@ def test_merge_exact_on_one_hot_tiles(cuda, Cls):
 # ---- 3. merge on random logits -----------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("window", ["ramp", "flat"])
-@pytest.mark.parametrize("Cls,W", [(2, 76), (2, 75), (3, 75), (4, 75), (7, 76)])
+@pytest.mark.parametrize("Cls,W", [(2, 76), (2, 75), (3, 75), (4, 75), (7, 76), (1, 75), (8, 76), (16, 75)])
 def test_merge_random_logits_against_float64(cuda, window, Cls, W):
     """52 x W images, 32 x 48 tiles, overlap 10: origins [0, 20] and [0, W - 48], both last tiles shifted back, at most four tiles
     per pixel.  Bound 3e-6: the 2e-6 test_none_is_the_plain_softmax allows an fp32 softmax against float64, plus at most four
-    weighted additions and two weight roundings at <= 2^-24 each on values <= 1."""
+    weighted additions and two weight roundings at <= 2^-24 each on values <= 1.
+    The same at 16 classes, counted as tests/tta_oracle.py's bound() counts: one tile's fp32 softmax is within (C + 3) 2^-24 of
+    float64 (0.37 for the subtraction of the maximum, 2 ulp of expf, the (C - 1)-term sum, one division) = 19 * 2^-24 = 1.13e-6,
+    and a weighted mean with weights summing to 1 keeps that; each of at most four tiles adds a product and a sum rounding on
+    values <= 1 (8), and the weight is a rounded product of two rounded table entries (3): 30 * 2^-24 = 1.8e-6 <= 3e-6, so the
+    bar stays."""
     B, H, Th, Tw, o = 2, 52, 32, 48, 10
     plan = TilePlan(B, H, W, (Th, Tw), o, window, cuda)
     assert plan.origins_y == [0, 20] and plan.origins_x == [0, W - Tw] and 20 % (Th - o) and (W - Tw) % (Tw - o)
@@ -142,9 +158,32 @@ def test_merge_random_logits_against_float64(cuda, window, Cls, W):
     assert torch.equal(labels, probs.argmax(1)) and torch.equal(conf, probs.amax(1))
 
 
+@pytest.mark.parametrize("case", ["spread", "huge", "dead"])
+@pytest.mark.parametrize("Cls", [2, 5])
+def test_merge_extreme_logits_against_float64(cuda, case, Cls):
+    """test_merge_random_logits_against_float64's geometry (W = 75) and bar on the logits that drive the shared pixel_softmax to
+    expf underflow (spread), to magnitudes of 3e4 (huge) and to classes at -1e30 (dead: their canvas values are exactly 0)."""
+    B, H, W, Th, Tw, o = 2, 52, 75, 32, 48, 10
+    plan = TilePlan(B, H, W, (Th, Tw), o, "ramp", cuda)
+    logits = VO.logits(case, [(plan.ntiles, Th, Tw)], Cls, seed=Cls + len(case))[0]
+    ref = TO.merge(TO.softmax64(logits.numpy()), B, H, W, Th, Tw, o, "ramp")
+    canvas, labels, conf = run_chunks(plan, logits.to(cuda), 3, Cls, cuda)
+    assert not torch.isnan(canvas).any() and int(labels.min()) >= 0
+    d = float(np.abs(canvas.cpu().numpy().astype(np.float64) - ref).max())
+    print(f"[tiled merge {case} C={Cls}] max|probs - oracle| = {d:.2e}")
+    assert d <= 3e-6
+    if case == "dead":
+        for c in VO.dead_classes(Cls):
+            assert bool((canvas[..., c] == 0.0).all()), c
+    probs = canvas.permute(0, 3, 1, 2)
+    assert torch.equal(labels, probs.argmax(1)) and torch.equal(conf, probs.amax(1))
+
+
 # ---- 4. chunk invariance -----------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("Cls,W,is_prob", [(2, 100, False), (2, 99, False), (4, 99, False), (6, 100, False), (3, 99, True)])
+@pytest.mark.parametrize("Cls,W,is_prob", [(2, 100, False), (2, 99, False), (4, 99, False), (6, 100, False), (3, 99, True),
+                                           (1, 99, False), (16, 100, False), (2, 100, True), (4, 99, True), (8, 100, True),
+                                           (1, 99, True), (2, 99, True)])
 def test_chunking_does_not_change_a_bit(cuda, Cls, W, is_prob):
     B, H, T, o = 2, 70, 32, 12
     plan = TilePlan(B, H, W, T, o, "ramp", cuda)

@@ -167,7 +167,8 @@ def test_refusals(cuda):
 
 
 def scores_numpy(table, probs):
-    """object_scores restated: sum of round_half_even(p * 2^32) per object in uint64, (sum * 2^-32) / area in float64, to float32."""
+    """object_scores restated: sum of round_half_even(p * 2^32) per object in uint64, (sum * 2^-32) / area in float64, to float32.
+    p is clamped to [0, 1] first, and a NaN counts as 0 (the kernel's fminf(fmaxf(p, 0), 1) returns the non-NaN operand)."""
     lab = table.labels.cpu().numpy().reshape(-1).astype(np.int64)
     B, C, H, W = probs.shape
     p = probs.permute(0, 2, 3, 1).cpu().numpy().reshape(-1, C)
@@ -175,7 +176,9 @@ def scores_numpy(table, probs):
     b = np.arange(lab.size) // (H * W)
     fg = lab > 0
     obj = off[b[fg]] + lab[fg] - 1
-    q = np.rint(np.clip(p[fg, cls[obj]], 0, 1).astype(np.float64) * 2.0 ** 32).astype(np.uint64)
+    pv = p[fg, cls[obj]]
+    pv = np.where(np.isnan(pv), np.float32(0), pv)
+    q = np.rint(np.clip(pv, 0, 1).astype(np.float64) * 2.0 ** 32).astype(np.uint64)
     acc = np.zeros(cls.size, np.uint64)
     np.add.at(acc, obj, q)
     return ((acc.astype(np.float64) * 2.0 ** -32) / area.astype(np.float64)).astype(np.float32), obj, p[fg, cls[obj]]
@@ -203,6 +206,44 @@ def test_object_scores(cuda, shape):
     dicts = table.to_dicts(scores=s1)
     flat = [d["confidence"] for img in dicts for d in img]
     assert flat == got.tolist()
+
+
+def test_object_scores_clamp_and_nan(cuda):
+    """Probabilities outside [0, 1] are clamped, NaN counts as 0, and an object of 90 000 pixels at exactly 1.0 scores exactly 1.0
+    (90 000 * 2^32 fits the uint64 sum and the fp64 finish).  The table comes from a synthetic 3-class map."""
+    H, W = 320, 400
+    cmap = torch.zeros((1, H, W), dtype=torch.int64)
+    cmap[0, 5:305, 10:310] = 1        # 300 x 300: all ones
+    cmap[0, 0:40, 330:380] = 2        # below 0 and in range
+    cmap[0, 60:100, 330:380] = 1      # above 1 and in range
+    cmap[0, 120:160, 330:380] = 2     # NaN and in range
+    cmap[0, 180:200, 330:380] = 1     # NaN only
+    cmap[0, 220:240, 330:380] = 2     # above 1 only
+    cmap[0, 260:280, 330:380] = 1     # below 0 only
+    table = mgunet.connected_components(cmap.to(cuda))
+    at = {y0: i for i, (_, y0, _, _) in enumerate(table.bbox.tolist())}       # object index by the first row of its box
+    big, lo, hi, nan, nan_only, above, below = (at[y] for y in (5, 0, 60, 120, 180, 220, 260))
+    assert table.area[big] == 90000 and table.class_id.tolist() == [[2, 1, 1, 2, 1, 2, 1][at[y]] for y in (0, 5, 60, 120, 180, 220, 260)]
+    g = torch.Generator().manual_seed(9)
+    p = torch.rand((1, H, W, 3), generator=g)
+    p[0, 5:305, 10:310, 1] = 1.0
+    p[0, 0:20, 330:380, 2] = -torch.rand((20, 50), generator=g) * 1e3 - 1e-9
+    p[0, 0, 330, 2] = float("-inf")
+    p[0, 60:80, 330:380, 1] = 1.0 + torch.rand((20, 50), generator=g) * 1e3 + 1e-6
+    p[0, 60, 330, 1] = float("inf")
+    p[0, 120:140, 330:380, 2] = float("nan")
+    p[0, 180:200, 330:380, 1] = float("nan")
+    p[0, 220:240, 330:380, 2] = 1.5
+    p[0, 260:280, 330:380, 1] = -0.5
+    probs = p.to(cuda).permute(0, 3, 1, 2)
+    s = mgunet.object_scores(table, probs)
+    ref, obj, pv = scores_numpy(table, probs)
+    got = s.cpu().numpy()
+    assert np.array_equal(got.view(np.uint32), ref.view(np.uint32))
+    assert got[big] == np.float32(1.0) and got[nan_only] == 0.0 and got[above] == np.float32(1.0) and got[below] == 0.0
+    # half of each of these objects is clamped to 0 or 1 per pixel, the other half contributes its mean
+    m_lo, m_hi, m_nan = (float(p[0, y:y + 20, 330:380, c].double().mean()) for y, c in ((20, 2), (80, 1), (140, 2)))
+    assert abs(got[lo] - m_lo / 2) <= 1e-6 and abs(got[hi] - (1 + m_hi) / 2) <= 1e-6 and abs(got[nan] - m_nan / 2) <= 1e-6
 
 
 def test_confidence_order_decides_matching(cuda):

@@ -5,26 +5,9 @@ import torch
 
 import mgunet
 from mgunet import tta
+from tta_oracle import unview as torch_unview, view as torch_view   # the views as the issue defines them, through torch.flip / torch.rot90
 
 SHAPES = [(8, 8), (6, 10), (10, 6), (7, 13), (1, 5), (1, 1)]
-
-
-def torch_view(x, flip, turns):
-    """The view as the issue defines it: fW = torch.flip(x, (-1,)), fH = torch.flip(x, (-2,)), then torch.rot90(., turns, (-2, -1))."""
-    if flip & 1:
-        x = torch.flip(x, (-1,))
-    if flip & 2:
-        x = torch.flip(x, (-2,))
-    return torch.rot90(x, turns, (-2, -1))
-
-
-def torch_unview(v, flip, turns):
-    x = torch.rot90(v, -turns, (-2, -1))
-    if flip & 2:
-        x = torch.flip(x, (-2,))
-    if flip & 1:
-        x = torch.flip(x, (-1,))
-    return x
 
 
 def test_transform_lists():
