@@ -714,6 +714,26 @@ int mgu_equalize_hist_rgb_u8(mgu_ctx* ctx, const uint8_t* rgb_dev, int H, int W,
  * padded bottom / right; per_channel = 0: one value per patch over all channels, 1: one per channel.  out (nph*npw, 1 | channels). */
 int mgu_patch_mean_u8(mgu_ctx* ctx, const uint8_t* img_dev, int H, int W, int channels, int patch, int per_channel, float* out_dev,
                       void* hip_stream);
+/* GaussianSmoother.smooth (preprocessing/graph_feature_processing/gaussian_smoothing.py:23-34: cv2.GaussianBlur on uint8), csrc/gaussian.hip.
+ * img (B,H,W,channels) interleaved uint8, channels 1..4 -> out of the same shape.  THIS BUILD'S DEFINITION, integers only, per channel:
+ *   h[y][x] = sum_d kx[d] * src[y][r(x + d - kw/2, W)]          (at most 65280: 16 bits)
+ *   v       = sum_d ky[d] * h[r(y + d - kh/2, H)][x]
+ *   out     = (v + 32768) >> 16                                  (at most 255: no clamp)
+ * r = reflect-101 applied repeatedly until the index is inside (a radius may exceed the image side); n == 1 gives 0.  kx_host / ky_host:
+ * HOST arrays of kw / kh Q8.8 weights (passed to the kernel by value), kw and kh odd and in 1..31, every weight >= 0, each axis summing
+ * to exactly 256 -- what mgunet.preprocess.gaussian_kernel_q8 makes from a float64 Gaussian (OpenCV's small tables for sigma <= 0 and
+ * k <= 7) by rounding half to even with the error carried to the next tap and the centre taking the rest.  This follows the bit-exact
+ * fixed-point scheme OpenCV 4.x publishes for 8-bit GaussianBlur; cv2 is absent from this build, so equality with a cv2 build is NOT
+ * verified.  MGU_ERR_INVALID: even or out-of-range sizes, weights that are negative or do not sum to 256, out_dev overlapping img_dev,
+ * H*W >= 2^31.  One launch whatever B is, no workspace, no floating point on the device: bitwise reproducible. */
+int mgu_gaussian_blur_u8(mgu_ctx* ctx, const uint8_t* img_dev, int B, int H, int W, int channels, const int32_t* kx_host, int kw,
+                         const int32_t* ky_host, int kh, uint8_t* out_dev, void* hip_stream);
+/* The "Smooth" column block of the node features (scripts/graph_refinement.py:81): columns [col0, col0 + (per_channel ? 3 : 1)) of rows
+ * (B*nph*npw, ld_out) fp32 get, bit for bit, what mgu_patch_mean_u8 gives on mgu_gaussian_blur_u8 of image b of rgb (B,H,W,3) -- same
+ * zero padding bottom / right, row order and mean expression -- without writing a blurred image.  Other columns are not touched.  One
+ * launch; patch 1..64, weights as above. */
+int mgu_patch_smooth_mean_u8(mgu_ctx* ctx, const uint8_t* rgb_dev, int B, int H, int W, int patch, const int32_t* kx_host, int kw,
+                             const int32_t* ky_host, int kh, int per_channel, float* out_dev, int ld_out, int col0, void* hip_stream);
 /* ---- graph-branch inputs for a whole batch: the node features scripts/graph_refinement.py:72-113 defines and the patch labels
  *      scripts/train_end_to_end.py:340 describes (the training script draws both from torch's RNG, :326 / :342) -----------------------
  * Node features.  rgb (B,H,W,3) uint8 -> rows (B*nph*npw, ld_out) fp32, nph = ceil(H / patch), npw = ceil(W / patch), patches zero

@@ -13,6 +13,12 @@ namespace mgu {
 // the YUV / YCrCb conversions below keep the 14-bit ones (yuv_shift 14)
 __device__ __forceinline__ int cv_gray(const uint8_t* p) { return (p[0] * 9798 + p[1] * 19235 + p[2] * 3735 + (1 << 14)) >> 15; }
 __device__ __forceinline__ int reflect101(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
+// reflect-101 applied until the index lies inside [0, n): a kernel radius may exceed the image side (radius 15 on a 2-pixel row); n == 1 -> 0
+__device__ __forceinline__ int reflect101_loop(int i, int n) {
+  if (n == 1) return 0;
+  while (i < 0 || i >= n) i = i < 0 ? -i : 2 * n - 2 - i;
+  return i;
+}
 // squared 3x3 Sobel magnitude gx^2 + gy^2 of the grey neighbourhood g[dy][dx] (exact integers)
 __device__ __forceinline__ int sobel_mag2(const int (&g)[3][3]) {
   const int gx = (g[0][2] + 2 * g[1][2] + g[2][2]) - (g[0][0] + 2 * g[1][0] + g[2][0]);

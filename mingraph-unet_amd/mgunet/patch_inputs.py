@@ -1,6 +1,7 @@
 """The graph branch's inputs for a whole batch, on the device:
 
-    patch_node_features      scripts/graph_refinement.py:72-113   (patch pixel mean x 16 | Sobel mean | equalised-image means)
+    patch_node_features      scripts/graph_refinement.py:72-113   (patch pixel mean x 16 | Sobel mean | equalised-image means
+                                                                   [| smoothed-image means])
     patch_labels             scripts/train_end_to_end.py:340      ("argmax of initial_seg_logits_single, pooled over patch regions")
 
 The training script draws both from torch's RNG (train_end_to_end.py:326, :342).  patch_node_features replaces the per-image
@@ -12,7 +13,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from .preprocess import _to_dev_u8
+from .preprocess import _to_dev_u8, patch_smooth_features_u8
 
 MAX_CLASSES = 32   # mgu_patch_labels: lane c of a wave counts class c
 
@@ -23,21 +24,29 @@ def _grid(H: int, W: int, p: int):
     return (H + p - 1) // p, (W + p - 1) // p
 
 
-def feature_width(repeat: int = 16, unet_cols: int = 0, per_channel: bool = True, pad_to: int = 4, with_images: bool = True) -> int:
-    """Row width patch_node_features returns: the used columns rounded up to a multiple of pad_to."""
-    used = (int(repeat) if with_images else 0) + int(unet_cols) + 1 + (3 if per_channel else 1)
+def _used_columns(repeat, unet_cols, per_channel, with_images, smooth=False) -> int:
+    return (int(repeat) if with_images else 0) + int(unet_cols) + 1 + (3 if per_channel else 1) * (2 if smooth else 1)
+
+
+def feature_width(repeat: int = 16, unet_cols: int = 0, per_channel: bool = True, pad_to: int = 4, with_images: bool = True,
+                  smooth: bool = False) -> int:
+    """Row width patch_node_features returns: the used columns (with the smoothed-image block when smooth) rounded up to a multiple of
+    pad_to."""
+    used = _used_columns(repeat, unet_cols, per_channel, with_images, smooth)
     pad_to = max(1, int(pad_to))
     return (used + pad_to - 1) // pad_to * pad_to
 
 
 def patch_node_features(images_u8, patch_size: int, images: torch.Tensor = None, repeat: int = 16, unet_patch_feats: torch.Tensor = None,
-                        per_channel: bool = True, pad_to: int = 4, out: torch.Tensor = None) -> torch.Tensor:
+                        per_channel: bool = True, pad_to: int = 4, out: torch.Tensor = None, smoother=None) -> torch.Tensor:
     """images_u8: (H, W, 3) or (B, H, W, 3) RGB uint8, numpy or tensor -> (B*Np, F) float32 rows on the device, image b's patches at rows
     [b*Np, (b+1)*Np) in raster order (zero padded bottom / right, as image_to_patches).  Columns: the mean of the normalised float
     batch `images` (B, 3, H, W) -- NCHW or the U-Net's NHWC-storage view, read by strides, no copy -- over the patch and its channels,
     repeated `repeat` times (none without `images`); `unet_patch_feats` (B*Np, Cu) copied (e.g. the rows mgu_unet_request_patch_mean
     wrote); the mean Sobel byte; the mean equalised bytes per channel (or over all three); zeros up to F = the used columns rounded up
-    to a multiple of pad_to (the GAT wants Fin % 4 == 0)."""
+    to a multiple of pad_to (the GAT wants Fin % 4 == 0).  With `smoother` (a GaussianSmoother) the "Smooth" block of
+    graph_refinement.py:81 follows the equalised columns: the mean bytes of smoother.smooth(image b), per channel or over all three as
+    per_channel says -- one more launch, no smoothed image written; without it the output and the launches are unchanged."""
     if images is not None:
         if not isinstance(images, torch.Tensor) or images.dtype != torch.float32:
             raise TypeError("images must be a float32 (B, 3, H, W) tensor")
@@ -68,13 +77,15 @@ def patch_node_features(images_u8, patch_size: int, images: torch.Tensor = None,
             raise ValueError(f"unet_patch_feats must be float32 ({rows}, Cu) rows on the device of images_u8")
         unet_patch_feats = f.reshape(rows, -1).contiguous()
         cu = unet_patch_feats.shape[1]
-    F = feature_width(repeat, cu, per_channel, pad_to, images is not None)
+    F = feature_width(repeat, cu, per_channel, pad_to, images is not None, smoother is not None)
     if out is None:
         out = torch.empty((rows, F), device=dev, dtype=torch.float32)
     elif tuple(out.shape) != (rows, F) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
         raise ValueError(f"`out` must be a contiguous float32 ({rows}, {F}) tensor on the images' device")
     _lib.call("mgu_patch_node_features_u8", dev, u8, B, H, W, p, images, *strides, int(repeat) if images is not None else 0,
               unet_patch_feats, cu, 1 if per_channel else 0, out, F)
+    if smoother is not None:     # after the call above, which zeroes every column past its own
+        patch_smooth_features_u8(u8, p, smoother, per_channel, out=out, col0=_used_columns(repeat, cu, per_channel, images is not None))
     return out
 
 

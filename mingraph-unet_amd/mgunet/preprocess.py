@@ -3,6 +3,7 @@
     ImagePreprocessor        preprocessing/image_preprocessing/image_preprocess.py:6-126
     EdgeDetector             preprocessing/graph_feature_processing/edge_detection.py:4-44
     HistogramEqualizer       preprocessing/graph_feature_processing/histogram_equalization.py:4-49
+    GaussianSmoother         preprocessing/graph_feature_processing/gaussian_smoothing.py:4-34
     patch_features_u8        scripts/graph_refinement.py:97-104   (image_to_patches(...).mean(...))
     postprocess_segmentation scripts/infer_segmentation.py:20-51
 
@@ -265,6 +266,110 @@ class HistogramEqualizer:
     def equalize_histogram_rgb(self, image_array_rgb):
         """(H, W, 3) RGB uint8 -> (H, W, 3): luminance histogram equalised in YUV."""
         return _rgb_op("mgu_equalize_hist_rgb_u8", image_array_rgb, 3)
+
+
+MAX_GAUSSIAN_KSIZE = 31   # mgu_gaussian_blur_u8: the tile and its halo live in LDS
+
+_SMALL_GAUSSIAN = {1: [1.0], 3: [0.25, 0.5, 0.25], 5: [0.0625, 0.25, 0.375, 0.25, 0.0625],
+                   7: [0.03125, 0.109375, 0.21875, 0.28125, 0.21875, 0.109375, 0.03125]}   # cv::getGaussianKernel for sigma <= 0
+
+
+def gaussian_kernel_f64(ksize: int, sigma: float) -> np.ndarray:
+    """The float64 weights of one axis as cv::getGaussianKernel defines them: for sigma <= 0 the fixed tables up to ksize 7, else
+    sigma = 0.3 ((ksize - 1) 0.5 - 1) + 0.8; exp(-x^2 / (2 sigma^2)) at x = i - (ksize - 1) / 2, divided by the sum."""
+    k = int(ksize)
+    if k < 1 or k % 2 == 0:
+        raise ValueError("Kernel size must be positive and odd.")
+    s = float(sigma)
+    if s <= 0 and k <= 7:
+        return np.asarray(_SMALL_GAUSSIAN[k], np.float64)
+    if s <= 0:
+        s = 0.3 * ((k - 1) * 0.5 - 1) + 0.8
+    x = np.arange(k, dtype=np.float64) - (k - 1) / 2
+    w = np.exp(-(x * x) / (2.0 * s * s))
+    return w / w.sum()
+
+
+def gaussian_kernel_q8(ksize: int, sigma: float) -> np.ndarray:
+    """The int32 Q8.8 weights of one axis that mgu_gaussian_blur_u8 takes: 256 gaussian_kernel_f64 rounded half to even from the
+    outside in, each rounding error carried into the next tap, the centre tap taking what is left of 256.  Symmetric, non-negative,
+    the sum exactly 256 (a constant image stays constant), every weight within 1 of 256 w.  (5, 1.0) -> [14, 62, 104, 62, 14]."""
+    w = gaussian_kernel_f64(ksize, sigma)
+    k = w.size
+    q = np.zeros(k, np.int64)
+    err = 0.0
+    for i in range(k // 2):
+        a = 256.0 * float(w[i]) + err
+        q[i] = q[k - 1 - i] = int(np.rint(a))
+        err = a - float(q[i])
+    q[k // 2] = 256 - 2 * int(q[:k // 2].sum())
+    return q.astype(np.int32)
+
+
+class GaussianSmoother:
+    """cv2.GaussianBlur on uint8 as this build defines it (include/mgunet.h, mgu_gaussian_blur_u8): separable Q8.8 integer weights,
+    reflect-101 borders, integers only on the device.  It follows OpenCV 4.x's published fixed-point scheme for 8-bit images; cv2 is
+    not a dependency, and equality with an actual cv2 build is not verified."""
+
+    def __init__(self, kernel_size=(5, 5), sigma_x=1.0, sigma_y=None):
+        self.kernel_size = kernel_size   # (width, height)
+        self.sigma_x = sigma_x
+        self.sigma_y = sigma_y if sigma_y is not None else sigma_x
+        if not (self.kernel_size[0] > 0 and self.kernel_size[0] % 2 == 1 and self.kernel_size[1] > 0 and self.kernel_size[1] % 2 == 1):
+            raise ValueError("Kernel size must be positive and odd.")
+        if max(self.kernel_size[0], self.kernel_size[1]) > MAX_GAUSSIAN_KSIZE:
+            raise NotImplementedError(f"the HIP path implements Gaussian kernels of up to {MAX_GAUSSIAN_KSIZE} x {MAX_GAUSSIAN_KSIZE} taps")
+
+    def kernels(self):
+        """-> (kx, ky) int32 Q8.8 weights; sigma_y <= 0 takes sigma_x, as cv2.GaussianBlur."""
+        sx = float(self.sigma_x)
+        sy = float(self.sigma_y) if self.sigma_y is not None else sx
+        if sy <= 0:
+            sy = sx
+        return gaussian_kernel_q8(int(self.kernel_size[0]), sx), gaussian_kernel_q8(int(self.kernel_size[1]), sy)
+
+    def _taps(self):
+        kx, ky = self.kernels()
+        return (C.c_int32 * kx.size)(*kx.tolist()), int(kx.size), (C.c_int32 * ky.size)(*ky.tolist()), int(ky.size)
+
+    def smooth(self, image_array):
+        """(H, W) or (H, W, C) uint8, C <= 4 -> the same shape; a (B, H, W, C) tensor is one launch.  numpy in -> numpy out, device
+        tensor in -> device tensor out."""
+        if (isinstance(image_array, np.ndarray) and image_array.dtype != np.uint8) or \
+                (isinstance(image_array, torch.Tensor) and image_array.dtype != torch.uint8):
+            raise NotImplementedError(f"the HIP path smooths uint8 images, got {image_array.dtype}")
+        img, was_np = _to_dev_u8(image_array)
+        if img.dim() not in (2, 3, 4) or (img.dim() >= 3 and not 1 <= img.shape[-1] <= 4) or img.numel() == 0:
+            raise ValueError("expected a non-empty (H, W), (H, W, C) or (B, H, W, C) uint8 image with C <= 4")
+        B = img.shape[0] if img.dim() == 4 else 1
+        H, W = (img.shape[0], img.shape[1]) if img.dim() < 4 else (img.shape[1], img.shape[2])
+        ch = 1 if img.dim() == 2 else img.shape[-1]
+        out = torch.empty_like(img)
+        _lib.call("mgu_gaussian_blur_u8", img.device, img, B, H, W, ch, *self._taps(), out)
+        return out.cpu().numpy() if was_np else out
+
+
+def patch_smooth_features_u8(images_u8, patch_size: int, smoother: GaussianSmoother, per_channel: bool = False, out: torch.Tensor = None,
+                             col0: int = 0) -> torch.Tensor:
+    """patch_features_u8(smoother.smooth(image b), patch_size, per_channel) for every image of an (H, W, 3) / (B, H, W, 3) RGB uint8
+    batch, bit for bit, in one launch and without the smoothed images: (B*Np, 3 | 1) float32, or columns [col0, col0 + (3 | 1)) of the
+    contiguous float32 (B*Np, F) tensor `out`, whose other columns are left alone."""
+    u8, _ = _to_dev_u8(images_u8)
+    if u8.dim() == 3:
+        u8 = u8.unsqueeze(0)
+    if u8.dim() != 4 or u8.shape[3] != 3:
+        raise ValueError("Input image must be an RGB image (H, W, 3) or a batch (B, H, W, 3).")
+    B, H, W, _c = u8.shape
+    p = int(patch_size)
+    if p < 1:
+        raise ValueError(f"patch_size must be positive, got {p}")
+    rows, n = B * ((H + p - 1) // p) * ((W + p - 1) // p), 3 if per_channel else 1
+    if out is None:
+        out, col0 = torch.empty((rows, n), device=u8.device, dtype=torch.float32), 0
+    elif out.dim() != 2 or out.shape[0] != rows or out.dtype != torch.float32 or out.device != u8.device or not out.is_contiguous():
+        raise ValueError(f"`out` must be a contiguous float32 ({rows}, F) tensor on the images' device")
+    _lib.call("mgu_patch_smooth_mean_u8", u8.device, u8, B, H, W, p, *smoother._taps(), 1 if per_channel else 0, out, out.shape[1], int(col0))
+    return out
 
 
 def patch_features_u8(image, patch_size: int, per_channel: bool = False) -> torch.Tensor:
