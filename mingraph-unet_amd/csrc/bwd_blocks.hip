@@ -1,8 +1,9 @@
-// Backward building blocks behind the C-ABI: each entry point runs ONE stage of loss.backward()
-// (scripts/train_segmentation.py:133) on caller-provided tensors.  The convolution stages call the very functions mgu_unet_backward
-// runs (conv_wgrad, conv_dgrad, convt_wgrad, convt_dgrad in mgunet_train.hip) on a Layer that describes the caller's tensors.  They exist so that every backward kernel can be checked in isolation against a float64
-// reference on fixed (x, dz) -- where nothing is ill-conditioned -- instead of only through a whole train step whose
-// BatchNorm + ReLU + MaxPool chain amplifies rounding (tests/test_gpu_backward_kernels.py).
+// Backward building blocks behind the C-ABI: each entry point runs ONE stage of loss.backward() (scripts/train_segmentation.py:133)
+// on caller-provided tensors.  The convolution stages call the very functions mgu_unet_backward runs (conv_wgrad, conv_dgrad,
+// convt_wgrad, convt_dgrad in mgunet_train.hip) on a Layer of the caller's shape (fp32, input channels stored padded to 4) and a
+// FwdRecord of the caller's tensors.  They exist so that every backward kernel can be checked in isolation against a float64 reference
+// on fixed (x, dz) -- where nothing is ill-conditioned -- instead of only through a whole train step whose BatchNorm + ReLU + MaxPool
+// chain amplifies rounding (tests/test_gpu_backward_kernels.py).
 // Kernel selection is the launchers' own (pick_conv, pick_wgrad), on the context's switches (MGU_NO_WINO_WGRAD, MGU_NO_WGRAD_HALO,
 // MGU_NO_THIN_WGRAD, MGU_NO_WINO_DGRAD, MGU_NO_WINOGRAD, ... read at mgu_create), so a test reaches every variant.
 #include <algorithm>
@@ -47,15 +48,6 @@ int get_scratch(mgu_ctx* c, size_t panel_floats, size_t dgp_floats, size_t wug_f
   return MGU_OK;
 }
 
-// the caller's tensors as the layer whose backward runs: its shape and the grid its forward ran on (input grid of a ConvTranspose)
-Layer caller_layer(int Cin, int Cout, int KS, bool convt, int B, int H, int W) {
-  Layer L;
-  L.Cin = Cin, L.Cp = rup(Cin, 4), L.Cout = Cout, L.KS = KS, L.convt = convt;
-  L.K = KS * KS * L.Cp, L.Kp = rup(L.K, 32);
-  L.t_B = B, L.t_H = H, L.t_W = W;
-  return L;
-}
-
 }  // namespace
 
 extern "C" {
@@ -68,12 +60,12 @@ int mgu_conv2d_wgrad_nhwc(mgu_ctx* c, const void* in_dev, int ld_in, const void*
   if (ld_in < rup(Cin, 4) || (ld_in & 3)) return fail(c, MGU_ERR_INVALID, "ld_in must be a multiple of 4 and >= Cin rounded up to 4");
   if ((int64_t)B * H * W >= (1ll << 31)) return fail(c, MGU_ERR_INVALID, "B*H*W must be < 2^31");
   HIPCHK(c, hipSetDevice(c->device));
-  Layer L = caller_layer(Cin, Cout, ksize, false, B, H, W);
-  L.t_in = (const float*)in_dev, L.t_ldin = ld_in;   // dz rows are padded to a multiple of 4 channels (zeros)
+  const Layer L = make_layer(MGU_DTYPE_F32, Cin, rup(Cin, 4), Cout, ksize, false);
+  const FwdRecord r{.in = (const float*)in_dev, .ldin = ld_in, .B = B, .H = H, .W = W};   // dz rows are padded to a multiple of 4 channels (zeros)
   Scratch sc;
   int rc = get_scratch(c, (size_t)rup(rup(Cout, 4), 128) * L.Kp, 0, 0, 64, &sc);
   if (rc) return rc;
-  return conv_wgrad(c, L, (const float*)dz_dev, (float*)dw_oihw_dev, sc, false, (hipStream_t)hip_stream);
+  return conv_wgrad(c, L, r, (const float*)dz_dev, (float*)dw_oihw_dev, sc, false, (hipStream_t)hip_stream);
 }
 
 int mgu_conv2d_dgrad_nhwc(mgu_ctx* c, const void* dz_dev, const void* w_oihw_dev, int B, int H, int W, int Cin, int Cout, int ksize,
@@ -85,14 +77,14 @@ int mgu_conv2d_dgrad_nhwc(mgu_ctx* c, const void* dz_dev, const void* w_oihw_dev
   if ((int64_t)B * H * W >= (1ll << 31)) return fail(c, MGU_ERR_INVALID, "B*H*W must be < 2^31");
   HIPCHK(c, hipSetDevice(c->device));
   const int Cop = rup(Cout, 4);
-  Layer L = caller_layer(Cin, Cout, ksize, false, B, H, W);
+  Layer L = make_layer(MGU_DTYPE_F32, Cin, rup(Cin, 4), Cout, ksize, false);
   L.w_src = (const float*)w_oihw_dev;
   Scratch sc;
   const bool wino = wino_dgrad_layer(c->tn, ksize, Cop);
   int rc = get_scratch(c, 0, (size_t)rup(Cin, 128) * rup(ksize * ksize * Cop, 32), wino ? wino_u_floats(Cin, Cop) : 0, 64, &sc);
   if (rc) return rc;
   L.wug = sc.wug;   // the Winograd set, when the pick takes that kernel, is packed into the scratch
-  return conv_dgrad(c, L, (const float*)dz_dev, (float*)din_dev, ld_out, sc, false, (hipStream_t)hip_stream);
+  return conv_dgrad(c, L, {.B = B, .H = H, .W = W}, (const float*)dz_dev, (float*)din_dev, ld_out, sc, false, (hipStream_t)hip_stream);
 }
 
 int mgu_conv_transpose2x2_wgrad_nhwc(mgu_ctx* c, const void* in_dev, const void* dout_dev, int ld_d, int c_off, int B, int H, int W,
@@ -104,12 +96,12 @@ int mgu_conv_transpose2x2_wgrad_nhwc(mgu_ctx* c, const void* in_dev, const void*
   if ((int64_t)B * H * W * 4 >= (1ll << 31)) return fail(c, MGU_ERR_INVALID, "4*B*H*W must be < 2^31");
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)hip_stream;
-  Layer U = caller_layer(Cin, Cout, 1, true, B, H, W);
-  U.t_in = (const float*)in_dev, U.t_ldin = Cin;
+  const Layer U = make_layer(MGU_DTYPE_F32, Cin, Cin, Cout, 1, true);
+  const FwdRecord r{.in = (const float*)in_dev, .ldin = Cin, .B = B, .H = H, .W = W};
   Scratch sc;
   int rc = get_scratch(c, (size_t)rup(Cin, 128) * rup(4 * Cout, 32), 0, 0, Cout, &sc);
   if (rc) return rc;
-  if ((rc = convt_wgrad(c, U, (const float*)dout_dev, ld_d, c_off, 2 * H, 2 * W, (float*)dw_iohw_dev, sc, s))) return rc;
+  if ((rc = convt_wgrad(c, U, r, (const float*)dout_dev, ld_d, c_off, 2 * H, 2 * W, (float*)dw_iohw_dev, sc, s))) return rc;
   if (dbias_dev)
     HIPCHK(c, launch_colsum((const float*)dout_dev + c_off, ld_d, (int64_t)B * H * W * 4, Cout, sc.red, (float*)dbias_dev, s));
   return MGU_OK;
@@ -123,12 +115,13 @@ int mgu_conv_transpose2x2_dgrad_nhwc(mgu_ctx* c, const void* dout_dev, int ld_d,
   if (ld_d < c_off + Cout || (ld_d & 3) || (c_off & 3)) return fail(c, MGU_ERR_INVALID, "ld_d / c_off must be multiples of 4, ld_d >= c_off + Cout");
   if ((int64_t)B * H * W * 4 >= (1ll << 31)) return fail(c, MGU_ERR_INVALID, "4*B*H*W must be < 2^31");
   HIPCHK(c, hipSetDevice(c->device));
-  Layer U = caller_layer(Cin, Cout, 1, true, B, H, W);
+  Layer U = make_layer(MGU_DTYPE_F32, Cin, rup(Cin, 4), Cout, 1, true);
   U.w_src = (const float*)w_iohw_dev;
   Scratch sc;
   int rc = get_scratch(c, 0, std::max((size_t)rup(Cin, 128) * rup(4 * Cout, 32), convt_x3_dgrad_floats(Cin, Cout)), 0, 64, &sc);
   if (rc) return rc;
-  return convt_dgrad(c, U, (const float*)dout_dev + c_off, ld_d, 2 * H, 2 * W, (float*)din_dev, sc, false, (hipStream_t)hip_stream);
+  return convt_dgrad(c, U, {.B = B, .H = H, .W = W}, (const float*)dout_dev + c_off, ld_d, 2 * H, 2 * W, (float*)din_dev, sc, false,
+                     (hipStream_t)hip_stream);
 }
 
 int mgu_bn_relu_train_nhwc(mgu_ctx* c, const void* z_dev, const void* gamma_dev, const void* beta_dev, int64_t M, int C, void* y_dev,
@@ -191,8 +184,7 @@ int mgu_conv_bn_relu_train_nhwc(mgu_ctx* c, const void* in_dev, int ld_in, int B
   hipStream_t s = (hipStream_t)hip_stream;
   // the caller's tensors as a model layer (mgu_unet_configure / repack_weights): the direct panel is packed by run_layer if its
   // pick reads it, the Winograd set and the first convolution's forms here
-  Layer L = caller_layer(Cin, Cout, 3, false, B, H, W);
-  L.N = Cout, L.Np = rup(Cout, 128);
+  Layer L = make_layer(MGU_DTYPE_F32, Cin, rup(Cin, 4), Cout, 3, false);
   L.w_src = (const float*)w_oihw_dev, L.b_src = (const float*)bias_dev, L.gamma = (const float*)gamma_dev, L.beta = (const float*)beta_dev;
   L.run_mean = (float*)run_mean_dev, L.run_var = (float*)run_var_dev, L.mean = (float*)mean_dev, L.invstd = (float*)invstd_dev;
   L.wino = wino_layer(c->tn, 3, L.Cp);
@@ -221,14 +213,12 @@ int mgu_conv_bn_relu_train_nhwc(mgu_ctx* c, const void* in_dev, int ld_in, int B
       HIPCHK(c, launch_pack_one(pack_first_mfma(L.w_src, L.wfm, Cout, Cin), s));
     }
   }
-  bool pool_fused = false, stats_fused = false;
-  rc = conv_bn_relu_train(c, L, (const float*)in_dev, ld_in, B, H, W, (float*)z_dev, (float*)y_dev, ld_y, (double*)(g + o_sums),
-                          (double*)c->redws, s, (float*)pooled_dev, &pool_fused, &stats_fused);
-  if (stats_fused_out) *stats_fused_out = stats_fused;
-  if (pool_fused_out) *pool_fused_out = pool_fused;
-  // an error return between the epilogue's sums and their fold would leave rows of the slots non-zero: clear them
-  if (rc != MGU_OK) (void)hipMemsetAsync(c->redws, 0, c->redws_bytes, s);
-  return rc;
+  const FwdRecord r{(const float*)in_dev, ld_in, (float*)z_dev, (float*)y_dev, ld_y, B, H, W};
+  ConvTaken took;
+  rc = conv_bn_relu_train(c, L, r, (double*)(g + o_sums), (double*)c->redws, s, (float*)pooled_dev, &took);
+  if (stats_fused_out) *stats_fused_out = took.stats;
+  if (pool_fused_out) *pool_fused_out = took.pool;
+  return red_cleared_on_error(c, rc, s);   // the epilogue's sums may be waiting for their fold
 }
 
 int mgu_bn_relu_conv_backward_nhwc(mgu_ctx* c, const void* in_dev, int ld_in, const void* z_dev, const void* dy_dev, int ld_dy,
@@ -245,8 +235,8 @@ int mgu_bn_relu_conv_backward_nhwc(mgu_ctx* c, const void* in_dev, int ld_in, co
   if ((int64_t)B * H * W >= (1ll << 31) || (int64_t)B * H * W < 2) return fail(c, MGU_ERR_INVALID, "B*H*W must be in [2, 2^31)");
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)hip_stream;
-  Layer L = caller_layer(Cin, Cout, 3, false, B, H, W);
-  L.t_in = (const float*)in_dev, L.t_ldin = ld_in, L.t_z = (float*)const_cast<void*>(z_dev);
+  Layer L = make_layer(MGU_DTYPE_F32, Cin, rup(Cin, 4), Cout, 3, false);
+  const FwdRecord r{.in = (const float*)in_dev, .ldin = ld_in, .z = (float*)const_cast<void*>(z_dev), .B = B, .H = H, .W = W};
   L.w_src = (const float*)w_oihw_dev, L.gamma = (const float*)gamma_dev, L.beta = (const float*)beta_dev;
   L.mean = (float*)const_cast<void*>(mean_dev), L.invstd = (float*)const_cast<void*>(invstd_dev);
   const bool wino = din_dev && wino_dgrad_layer(c->tn, 3, Cout);
@@ -262,10 +252,8 @@ int mgu_bn_relu_conv_backward_nhwc(mgu_ctx* c, const void* in_dev, int ld_in, co
   HIPCHK(c, hipGetLastError());
   LayerGrads g;
   g.dw = (float*)dw_oihw_dev, g.dbias = (float*)dbias_dev, g.dgamma = (float*)dgamma_dev, g.dbeta = (float*)dbeta_dev;
-  rc = conv_bn_relu_backward(c, L, (const float*)dy_dev, ld_dy, (float*)dz_dev, g, (float*)din_dev, ld_din, sc, s);
-  // an error return between the deferred column sums and their fold would leave rows of the slots non-zero: clear them
-  if (rc != MGU_OK) (void)hipMemsetAsync(c->redws, 0, c->redws_bytes, s);
-  return rc;
+  rc = conv_bn_relu_backward(c, L, r, (const float*)dy_dev, ld_dy, (float*)dz_dev, g, (float*)din_dev, ld_din, sc, s);
+  return red_cleared_on_error(c, rc, s);   // the deferred column sums may be waiting for their fold
 }
 
 int mgu_reduction_slots_absmax(mgu_ctx* c, double* absmax_out, void* hip_stream) {

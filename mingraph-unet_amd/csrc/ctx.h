@@ -40,14 +40,17 @@ struct Layer {
   int64_t off_w = 0, off_b = 0, off_gamma = 0, off_beta = 0;
   // batch statistics of the last training forward (library scratch)
   float *mean = nullptr, *invstd = nullptr, *tscale = nullptr, *tshift = nullptr;
-  // tensors of the last training forward
-  const float* t_in = nullptr;  // conv input
-  int t_ldin = 0;
-  float* t_z = nullptr;         // raw conv output (dense, pitch Cout)
-  float* t_y = nullptr;         // relu(bn(z)) with pitch t_ldy
-  int t_ldy = 0;
-  int t_B = 0, t_H = 0, t_W = 0;  // grid the conv ran on (input grid for convT)
   int level = 0;                  // grid level the layer runs on (input grid for convT): H >> level after `level` MaxPool2d(2)
+};
+
+// What a layer's backward reads of its training forward (mgu_ctx::fwd: the model's; bwd_blocks.hip builds one of the caller's tensors)
+struct FwdRecord {
+  const float* in = nullptr;  // conv input
+  int ldin = 0;
+  float* z = nullptr;         // raw conv output (dense, pitch Cout)
+  float* y = nullptr;         // relu(bn(z)) with pitch ldy
+  int ldy = 0;
+  int B = 0, H = 0, W = 0;    // grid the conv ran on (input grid for convT)
 };
 
 // One ConvBlock of the network (unet_encoder.py:4-25) and, in a decoder block, the ConvTranspose2d in front of it: indices into
@@ -72,7 +75,6 @@ struct mgu_ctx {
                             // mgu_sync_check and, without a sync, at the entry of the next training call
   void* redws = nullptr;    // per-channel reduction slots (self-cleaning: zero between launches)
   size_t redws_bytes = 0;
-  int last_stat_rows = 0;   // accumulator rows the last statistics-fused conv launch wrote (run_layer)
   void* pm_out = nullptr;   // one-shot request (mgu_unet_request_patch_mean): patch means of decoder feature 0
   int pm_patch = 0;
   void* pmws = nullptr;     // row-pair partial sums of the head-fused convolution (WinoHead::psum)
@@ -113,8 +115,7 @@ struct mgu_ctx {
   // last training forward
   bool have_train_fwd = false;
   int tB = 0, tH = 0, tW = 0;
-  std::vector<float*> t_cat, t_feat, t_pooled;
-  float* t_logits = nullptr;
+  std::vector<FwdRecord> fwd;   // one per layer
   // gradient exchange (comm.hip): RCCL communicator owned by this context, its stream and a small pool of ordering events
   void* comm = nullptr;     // ncclComm_t
   int comm_world = 1, comm_rank = 0;
@@ -143,6 +144,16 @@ namespace mgud {
 
 inline int rup(int v, int m) { return (v + m - 1) / m * m; }
 extern std::string g_create_err;
+
+// The shape of a Conv2d (KS 1 / 3) or ConvTranspose2d(2, 2) (convt, KS 1) layer on Cin channels stored as Cp: GEMM depth K and
+// width N with their panel paddings (Kp: one 128-byte LDS row of k per pipeline step)
+inline Layer make_layer(int dtype, int Cin, int Cp, int Cout, int KS, bool convt) {
+  Layer L;
+  L.Cin = Cin, L.Cp = Cp, L.Cout = Cout, L.KS = KS, L.convt = convt;
+  L.K = KS * KS * Cp, L.Kp = rup(L.K, dtype == MGU_DTYPE_BF16 ? 64 : 32);
+  L.N = convt ? 4 * Cout : Cout, L.Np = rup(L.N, 128);
+  return L;
+}
 
 inline int fail(mgu_ctx* c, int code, const char* fmt, ...) {
   char buf[512];
@@ -249,17 +260,17 @@ inline mgu::IgemmDesc layer_desc(const mgu_ctx* c, const Layer& L, const void* i
   d.out_mode = L.convt ? 1 : 0, d.ct_cout = L.Cout;
   return d;
 }
-// The data gradient of layer L on the grid of its last forward (L.t_B, t_H, t_W) as a gather over dz (pitch lddz): KS 1 / 3 is the
+// The data gradient of layer L on the grid of its forward r as a gather over dz (pitch lddz): KS 1 / 3 is the
 // conv with the flipped, transposed weights (Cout rounded up to 4 channels), a ConvTranspose the 2x2 stride-2 gather from its
 // Hout x Wout output.  `panel` is the direct-panel form; the caller offers the other forms in d.wu.
-inline mgu::IgemmDesc dgrad_desc(const mgu_ctx* c, const Layer& L, const float* dz, int lddz, const float* panel, float* out, int ldout,
-                            int Hout = 0, int Wout = 0) {
+inline mgu::IgemmDesc dgrad_desc(const mgu_ctx* c, const Layer& L, const FwdRecord& r, const float* dz, int lddz, const float* panel,
+                            float* out, int ldout, int Hout = 0, int Wout = 0) {
   const int KS = L.convt ? 2 : L.KS, Cop = rup(L.Cout, 4);
   mgu::IgemmDesc d;
   memset(&d, 0, sizeof d);
   d.tn = &c->tn;
   d.in = dz, d.w = panel, d.out = out;
-  d.M = L.t_B * L.t_H * L.t_W, d.H = L.t_H, d.W = L.t_W;
+  d.M = r.B * r.H * r.W, d.H = r.H, d.W = r.W;
   d.Cp = Cop, d.ldin = lddz, d.KS = KS, d.K = KS * KS * Cop, d.Kp = rup(d.K, 32);
   d.N = L.Cin, d.ldout = ldout, d.Hout = Hout, d.Wout = Wout;
   return d;
@@ -293,12 +304,34 @@ inline mgu::WgradDesc wgrad_desc(const mgu_ctx* c, const float* z, int ldz, cons
   return d;
 }
 
-// one fused conv / convT / 1x1 launch described by a Layer (scale/shift chosen by the caller)
-int run_layer(mgu_ctx* c, const Layer& L, const void* in, int ldin, int B, int H, int W, void* out, int ldout, int coff,
-              int relu, const float* scale, const float* shift, int Hout, int Wout, hipStream_t s,
-              void* pool = nullptr, int ldpool = 0, bool* pool_fused = nullptr,   // optional fused MaxPool2d(2) output
-              double* stat_slots = nullptr, bool* stat_fused = nullptr,           // optional fused BatchNorm batch statistics
-              const mgu::WinoHead* head = nullptr, bool* head_fused = nullptr);   // optional head-fused finishing pass (common.h)
+// One fused conv / convT / 1x1 launch of a Layer: what it reads and writes (call sites name the fields they set, in this order) ...
+struct ConvReq {
+  const void* in = nullptr;   // pitch ldin, on a B x H x W grid
+  int ldin = 0, B = 0, H = 0, W = 0;
+  void* out = nullptr;        // pitch ldout, channels from coff
+  int ldout = 0, coff = 0, relu = 0;
+  const float *scale = nullptr, *shift = nullptr;   // chosen by the caller
+  int Hout = 0, Wout = 0;     // output grid of a ConvTranspose
+};
+// ... the epilogues it may fuse where the kernel the pick chooses has them ...
+struct ConvFusions {
+  void* pool = nullptr;             // MaxPool2d(2) output
+  int ldpool = 0;
+  double* stat_slots = nullptr;     // BatchNorm batch statistics
+  const mgu::WinoHead* head = nullptr;   // head-fused finishing pass (common.h)
+};
+// ... and which of them that kernel took: what it left out is the caller's to run in a pass of its own
+struct ConvTaken {
+  bool pool = false, stats = false, head = false;
+  int stat_rows = 0;   // accumulator rows the statistics epilogue wrote
+};
+int run_layer(mgu_ctx* c, const Layer& L, const ConvReq& q, hipStream_t s, const ConvFusions& f = {}, ConvTaken* took = nullptr);
+// Returns rc.  An error return may have come between a pass that leaves sums in the (otherwise self-cleaning) reduction slots and their
+// fold: clear the slots then, or rows would stay non-zero for every later reduction
+inline int red_cleared_on_error(mgu_ctx* c, int rc, hipStream_t s) {
+  if (rc != MGU_OK && c && c->redws) (void)hipMemsetAsync(c->redws, 0, c->redws_bytes, s);
+  return rc;
+}
 
 // GAT layer host code (gat_api.hip)
 void gat_destroy(mgu_ctx* c);
@@ -341,33 +374,34 @@ struct BwdScratch {
   double *red = nullptr, *sums = nullptr;
   bool clear = false;   // zero a direct panel before packing it (the building blocks)
 };
-// The four backward operations of a layer whose last forward is recorded in L.t_* (mgu_unet_backward, and the building blocks of
-// bwd_blocks.hip on a Layer describing the caller's tensors).  Each picks its kernel once, packs the weight form that kernel reads
-// -- unless the layer keeps a current one (L.wug, L.wxg) -- and launches; `record` adds a profiling record.
-int conv_dgrad(mgu_ctx* c, const Layer& L, const float* dz, float* out, int ldout, const BwdScratch& w, bool record, hipStream_t s);
-int convt_dgrad(mgu_ctx* c, const Layer& U, const float* dout, int ld_d, int Hout, int Wout, float* out, const BwdScratch& w, bool record,
-                hipStream_t s);
+// The four backward operations of layer L on the forward recorded in r (mgu_unet_backward on mgu_ctx::fwd, the building blocks of
+// bwd_blocks.hip on the caller's tensors).  Each picks its kernel once, packs the weight form that kernel reads -- unless the layer
+// keeps a current one (L.wug, L.wxg) -- and launches; `record` adds a profiling record.
+int conv_dgrad(mgu_ctx* c, const Layer& L, const FwdRecord& r, const float* dz, float* out, int ldout, const BwdScratch& w, bool record,
+               hipStream_t s);
+int convt_dgrad(mgu_ctx* c, const Layer& U, const FwdRecord& r, const float* dout, int ld_d, int Hout, int Wout, float* out,
+                const BwdScratch& w, bool record, hipStream_t s);
 // dz dense with pitch rup(Cout, 4); fold_rows != nullptr: also folds the bias-gradient column sums pending in w.red (conv_bn_relu_backward)
-int conv_wgrad(mgu_ctx* c, const Layer& L, const float* dz, float* dw, const BwdScratch& w, bool record, hipStream_t s,
+int conv_wgrad(mgu_ctx* c, const Layer& L, const FwdRecord& r, const float* dz, float* dw, const BwdScratch& w, bool record, hipStream_t s,
                int* fold_rows = nullptr, float* dbias = nullptr);
-int convt_wgrad(mgu_ctx* c, const Layer& U, const float* dout, int ld_d, int c_off, int Hout, int Wout, float* dw, const BwdScratch& w,
-                hipStream_t s);
+int convt_wgrad(mgu_ctx* c, const Layer& U, const FwdRecord& r, const float* dout, int ld_d, int c_off, int Hout, int Wout, float* dw,
+                const BwdScratch& w, hipStream_t s);
 // the context's reduction slots (mgu_ctx::redws) sized for layers of up to Cmax channels; a fresh allocation is cleared, once
 int ensure_red(mgu_ctx* c, int Cmax);
-// One conv -> BatchNorm(train) -> ReLU of the training forward on layer L (z dense with pitch Cout, y with pitch ldy): the batch
-// statistics come from the convolution's epilogue where its kernel accumulates them (*stats_fused), else from a pass over z.  pooled
-// != nullptr: also MaxPool2d(2) of y, in the apply pass for even H and W (*pool_fused), else by the pool kernel on y.
-int conv_bn_relu_train(mgu_ctx* c, Layer& L, const float* in, int ldin, int B, int H, int W, float* z, float* y, int ldy, double* sums,
-                       double* red, hipStream_t s, float* pooled = nullptr, bool* pool_fused = nullptr, bool* stats_fused = nullptr);
+// One conv -> BatchNorm(train) -> ReLU of the training forward on layer L and the tensors of r: the batch statistics come from the
+// convolution's epilogue where its kernel accumulates them (took->stats), else from a pass over z.  pooled != nullptr: also
+// MaxPool2d(2) of y, in the apply pass for even H and W (took->pool), else by the pool kernel on y.
+int conv_bn_relu_train(mgu_ctx* c, const Layer& L, const FwdRecord& r, double* sums, double* red, hipStream_t s, float* pooled = nullptr,
+                       ConvTaken* took = nullptr);
 // Where the backward of that half block writes the layer's parameter gradients
 struct LayerGrads {
   float *dw = nullptr, *dbias = nullptr, *dgamma = nullptr, *dbeta = nullptr;
 };
-// ... and its backward on the tensors recorded in L.t_*: BatchNorm + ReLU backward (dy with pitch lddy -> dz dense; the column sums of
-// dz stay in the reduction slots), the weight gradient, whose unpack launch folds those sums into the bias gradient, and -- din !=
-// nullptr -- the data gradient (pitch ld_din)
-int conv_bn_relu_backward(mgu_ctx* c, const Layer& L, const float* dy, int lddy, float* dz, const LayerGrads& g, float* din, int ld_din,
-                          const BwdScratch& w, hipStream_t s);
+// ... and its backward on the same record: BatchNorm + ReLU backward (dy with pitch lddy -> dz dense; the column sums of dz stay in the
+// reduction slots), the weight gradient, whose unpack launch folds those sums into the bias gradient, and -- din != nullptr -- the
+// data gradient (pitch ld_din)
+int conv_bn_relu_backward(mgu_ctx* c, const Layer& L, const FwdRecord& r, const float* dy, int lddy, float* dz, const LayerGrads& g,
+                          float* din, int ld_din, const BwdScratch& w, hipStream_t s);
 size_t train_ws_bytes(const mgu_ctx* c, int B, int H, int W);
 int unet_forward_train(mgu_ctx* c, const float* x, int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w, int B, int H,
                        int W, float* logits, void* const* cat_dev, void* const* feat_dev, hipStream_t s);

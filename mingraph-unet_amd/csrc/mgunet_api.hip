@@ -167,9 +167,8 @@ int mgu_unet_configure(mgu_ctx* c, int in_ch, int ncls, int feat, int depth, int
   c->enc.clear();
   c->dec.clear();
   auto add = [&](const std::string& prefix, const char* conv, const char* bn, int cin, int cp, int cout, int KS, bool convt, int level) {
-    Layer L;
-    L.prefix = prefix, L.conv = conv, L.bn = bn;
-    L.Cin = cin, L.Cp = cp, L.Cout = cout, L.KS = KS, L.convt = convt, L.level = level;
+    Layer L = make_layer(dtype, cin, cp, cout, KS, convt);
+    L.prefix = prefix, L.conv = conv, L.bn = bn, L.level = level;
     c->layers.push_back(L);
     return (int)c->layers.size() - 1;
   };
@@ -196,12 +195,7 @@ int mgu_unet_configure(mgu_ctx* c, int in_ch, int ncls, int feat, int depth, int
     prev = ci;
   }
   c->head = add("decoder.", "final_conv", "", prev, prev, ncls, 1, false, 0);  // unet_decoder.py:117
-  for (auto& L : c->layers) {
-    L.K = L.KS * L.KS * L.Cp;
-    L.Kp = rup(L.K, dtype == MGU_DTYPE_BF16 ? 64 : 32);   // one 128-byte LDS row of k per pipeline step
-    L.N = L.convt ? 4 * L.Cout : L.Cout;
-    L.Np = rup(L.N, 128);
-  }
+  c->fwd.assign(c->layers.size(), FwdRecord{});
   // flat parameter order = the reference's named_parameters(): per ConvBlock conv1.{w,b}, conv2.{w,b},
   // bn1.{w,b}, bn2.{w,b} (unet_encoder.py:7-13); decoder block: upsample.{w,b} then its conv_block; final.
   {
@@ -407,43 +401,39 @@ int mgud::repack_weights(mgu_ctx* c, hipStream_t s) {
   return MGU_OK;
 }
 
-int mgud::run_layer(mgu_ctx* c, const Layer& L, const void* in_v, int ldin, int B, int H, int W, void* out_v, int ldout,
-                    int coff, int relu, const float* scale, const float* shift, int Hout, int Wout, hipStream_t s,
-                    void* pool, int ldpool, bool* pool_fused, double* stat_slots, bool* stat_fused, const WinoHead* head,
-                    bool* head_fused) {
-  IgemmDesc d = layer_desc(c, L, in_v, ldin, B, H, W, out_v, ldout, coff);
-  if (head_fused) *head_fused = false;
-  d.scale = scale, d.shift = shift, d.relu = relu, d.Hout = Hout, d.Wout = Wout;
-  if (pool_fused) *pool_fused = false;
-  if (stat_fused) *stat_fused = false;
-  if (L.wfm && c->tn.first_mfma && ldin == L.Cp && first_mfma_applicable(c->dtype, L.Cin, L.Cp, L.Cout, ldout, coff, H, W)) {
+int mgud::run_layer(mgu_ctx* c, const Layer& L, const ConvReq& q, hipStream_t s, const ConvFusions& f, ConvTaken* took) {
+  IgemmDesc d = layer_desc(c, L, q.in, q.ldin, q.B, q.H, q.W, q.out, q.ldout, q.coff);
+  d.scale = q.scale, d.shift = q.shift, d.relu = q.relu, d.Hout = q.Hout, d.Wout = q.Wout;
+  ConvTaken t;
+  if (took) *took = t;
+  if (L.wfm && c->tn.first_mfma && q.ldin == L.Cp && first_mfma_applicable(c->dtype, L.Cin, L.Cp, L.Cout, q.ldout, q.coff, q.H, q.W)) {
     const double alg = 2.0 * d.M * 9.0 * L.Cin * L.Cout;
     ProfScope ps(c, s, "conv3x3_first_mfma_kernel", alg, 2.0 * d.M * 32.0 * 32.0 * (c->dtype == MGU_DTYPE_F32 ? 6.0 : 3.0), 1);
-    HIPCHK(c, launch_first_mfma(c->dtype, in_v, L.wfm, scale, shift, out_v, B, H, W, ldout, coff, relu, s));
+    HIPCHK(c, launch_first_mfma(c->dtype, q.in, L.wfm, q.scale, q.shift, q.out, q.B, q.H, q.W, q.ldout, q.coff, q.relu, s));
     return MGU_OK;
   }
-  if (L.wf && ldin == L.Cp && first_conv_applicable(c->dtype, L.Cin, L.Cp, L.Cout, ldout, coff) &&
-      (int64_t)B * H * W * std::max(ldout, 8) < (1ll << 31)) {
+  if (L.wf && q.ldin == L.Cp && first_conv_applicable(c->dtype, L.Cin, L.Cp, L.Cout, q.ldout, q.coff) &&
+      (int64_t)q.B * q.H * q.W * std::max(q.ldout, 8) < (1ll << 31)) {
     ProfScope ps(c, s, "conv3x3_first_kernel", 2.0 * d.M * 9.0 * L.Cin * L.Cout, 0, -1);
-    HIPCHK(c, launch_first_conv(c->dtype, in_v, L.wf, scale, shift, out_v, B, H, W, L.Cin, L.Cout, ldout, coff, relu, s));
+    HIPCHK(c, launch_first_conv(c->dtype, q.in, L.wf, q.scale, q.shift, q.out, q.B, q.H, q.W, L.Cin, L.Cout, q.ldout, q.coff, q.relu, s));
     return MGU_OK;
   }
-  ConvKernel k = pick_conv(d, c->dtype, head);
+  ConvKernel k = pick_conv(d, c->dtype, f.head);
   // the Winograd epilogue also accumulates sum z, sum z^2: one accumulator row per workgroup, so only while the launch's grid fits
   // the table (>= 19 images of 512^2 or 5 of 1024^2 per GPU on the full-resolution 32-channel layer, or a small MGU_WINO_PPB_CAP, do
   // not: the caller then takes the separate statistics pass, launch_bn_stats)
-  if (stat_slots && conv_is_wino(k) && wino_grid_blocks(d) <= STAT_ROWS) {
-    d.stat_slots = stat_slots;
-    c->last_stat_rows = wino_grid_blocks(d);
-    if (stat_fused) *stat_fused = true;
+  if (f.stat_slots && conv_is_wino(k) && wino_grid_blocks(d) <= STAT_ROWS) {
+    d.stat_slots = f.stat_slots;
+    t.stats = true, t.stat_rows = wino_grid_blocks(d);
   }
-  if (pool && conv_fuses_pool(k)) {   // the Winograd / halo epilogue also writes the 2x2 max-pooled tensor
-    d.pool = (float*)pool, d.ldpool = ldpool;
-    if (pool_fused) *pool_fused = true;
+  if (f.pool && conv_fuses_pool(k)) {   // the Winograd / halo epilogue also writes the 2x2 max-pooled tensor
+    d.pool = (float*)f.pool, d.ldpool = f.ldpool;
+    t.pool = true;
   }
-  if (d.stat_slots || d.pool) k = pick_conv(d, c->dtype, head);   // the fused epilogue narrows the choice (not every kernel form has it)
-  if (!conv_fuses_head(k)) head = nullptr;   // the caller runs the head and the patch means in their own pass
-  else if (head_fused) *head_fused = true;
+  if (d.stat_slots || d.pool) k = pick_conv(d, c->dtype, f.head);   // the fused epilogue narrows the choice (not every kernel form has it)
+  t.head = conv_fuses_head(k);   // else the caller runs the head and the patch means in their own pass
+  const WinoHead* head = t.head ? f.head : nullptr;
+  if (took) *took = t;
   if (L.wp_dirty && conv_reads_panel(k)) {   // falling back to the direct kernel: build its panel now
     HIPCHK(c, launch_pack_one(L.convt ? pack_convt_panel(L.w_src, L.wp, c->dtype, L.Cin, L.Cout, L.Kp)
                                       : pack_conv_panel(L.w_src, L.wp, c->dtype, L.Cout, L.Cin, L.Cp, L.KS, L.Kp), s));
@@ -457,13 +447,6 @@ int mgud::run_layer(mgu_ctx* c, const Layer& L, const void* in_v, int ldin, int 
   ProfScope ps(c, s, conv_kernel_name(k, d), alg, cost.mfma, cost.pipe);
   HIPCHK(c, launch_conv(d, k, c->dtype, s, head));
   return MGU_OK;
-}
-
-static int run_conv(mgu_ctx* c, const Layer& L, const void* in, int ldin, int B, int H, int W, void* out, int ldout,
-                    int coff, int relu, int Hout, int Wout, hipStream_t s, void* pool = nullptr, int ldpool = 0,
-                    bool* pool_fused = nullptr, const WinoHead* head = nullptr, bool* head_fused = nullptr) {  // eval: folded BN scale/shift
-  return run_layer(c, L, in, ldin, B, H, W, out, ldout, coff, relu, L.bn.empty() ? nullptr : L.scale, L.shift, Hout, Wout, s,
-                   pool, ldpool, pool_fused, nullptr, nullptr, head, head_fused);
 }
 
 extern "C" {
@@ -549,6 +532,12 @@ int mgu_unet_forward(mgu_ctx* c, const void* x_dev, int B, int H, int W, int64_t
       head.psum = (float*)((char*)head.psum + wino_head_psum_bytes(img0, H, W));
       head.psum_bytes = (int)wino_head_psum_bytes(nb, H, W);
     }
+    // layer l on the group's images at grid level lvl, with its folded BatchNorm scale / shift
+    auto conv = [&](int l, int lvl, ConvReq q, const ConvFusions& f = {}, ConvTaken* took = nullptr) {
+      const Layer& L = c->layers[l];
+      q.B = nb, q.H = hs[lvl], q.W = wsz[lvl], q.scale = L.bn.empty() ? nullptr : L.scale, q.shift = L.shift;
+      return run_layer(c, L, q, gs, f, took);
+    };
     const void* cur = at(xin, 0, c->Cp0);
     int cur_ld = c->Cp0;
     for (const Block& b : c->enc) {  // encoder, unet_encoder.py:67-70
@@ -559,35 +548,31 @@ int mgu_unet_forward(mgu_ctx* c, const void* x_dev, int B, int H, int W, int64_t
         ProfScope ps(c, gs, "conv3x3_first_mfma_kernel", alg, 2.0 * nb * H * W * 32.0 * 32.0 * (c->dtype == MGU_DTYPE_F32 ? 6.0 : 3.0), 1);
         HIPCHK(c, launch_first_mfma_direct(c->dtype, (const float*)x_dev + (int64_t)img0 * xs_n, xs_n, xs_c, xs_h, xs_w, c->in_ch, L0.wfm,
                                            L0.bn.empty() ? nullptr : L0.scale, L0.shift, tmp, nb, H, W, C, 0, 1, gs));
-      } else if ((rc = run_conv(c, c->layers[b.conv1], cur, cur_ld, nb, hs[i], wsz[i], tmp, C, 0, 1, 0, 0, gs))) return rc;
-      void* pooled = at(ws + plan.pooled[i], i + 1, C);
-      bool fused = false;   // MaxPool2d(2) (unet_encoder.py:48) rides in the conv2 epilogue on the Winograd path
-      if ((rc = run_conv(c, c->layers[b.conv2], tmp, C, nb, hs[i], wsz[i], at(cat_dev[i], i, 2 * C), 2 * C, 0, 1, 0, 0, gs, pooled, C, &fused)))
-        return rc;
-      if (!fused) HIPCHK(c, launch_maxpool2(at(cat_dev[i], i, 2 * C), 2 * C, pooled, c->dtype, nb, hs[i], wsz[i], C, gs));
-      cur = pooled;
-      cur_ld = C;
+      } else if ((rc = conv(b.conv1, i, {.in = cur, .ldin = cur_ld, .out = tmp, .ldout = C, .relu = 1}))) return rc;
+      void *cat = at(cat_dev[i], i, 2 * C), *pooled = at(ws + plan.pooled[i], i + 1, C);
+      ConvTaken took;   // MaxPool2d(2) (unet_encoder.py:48) rides in the conv2 epilogue on the Winograd path
+      if ((rc = conv(b.conv2, i, {.in = tmp, .ldin = C, .out = cat, .ldout = 2 * C, .relu = 1}, {.pool = pooled, .ldpool = C}, &took))) return rc;
+      if (!took.pool) HIPCHK(c, launch_maxpool2(cat, 2 * C, pooled, c->dtype, nb, hs[i], wsz[i], C, gs));
+      cur = pooled, cur_ld = C;
     }
     {  // bottleneck, :72
       const Block& b = c->bott;
       const int i = b.level, C = c->layers[b.conv1].Cout;
-      if ((rc = run_conv(c, c->layers[b.conv1], cur, cur_ld, nb, hs[i], wsz[i], tmp, C, 0, 1, 0, 0, gs))) return rc;
-      if ((rc = run_conv(c, c->layers[b.conv2], tmp, C, nb, hs[i], wsz[i], at(bott, i, C), C, 0, 1, 0, 0, gs))) return rc;
-      cur = at(bott, i, C);
-      cur_ld = C;
+      if ((rc = conv(b.conv1, i, {.in = cur, .ldin = cur_ld, .out = tmp, .ldout = C, .relu = 1}))) return rc;
+      if ((rc = conv(b.conv2, i, {.in = tmp, .ldin = C, .out = at(bott, i, C), .ldout = C, .relu = 1}))) return rc;
+      cur = at(bott, i, C), cur_ld = C;
     }
     for (const Block& b : c->dec) {  // decoder, unet_decoder.py:139-141
       const int i = b.level, C = c->layers[b.conv1].Cout;
       const bool last = head_wanted && i == 0;
       // ConvTranspose2d(k2,s2) -> pixel-shuffle store into channels [C, 2C) of the concat buffer (:36,:53)
-      if ((rc = run_conv(c, c->layers[b.up], cur, cur_ld, nb, hs[i + 1], wsz[i + 1], at(cat_dev[i], i, 2 * C), 2 * C, C, 0, hs[i], wsz[i], gs)))
-        return rc;
-      if ((rc = run_conv(c, c->layers[b.conv1], at(cat_dev[i], i, 2 * C), 2 * C, nb, hs[i], wsz[i], tmp, C, 0, 1, 0, 0, gs))) return rc;
-      if ((rc = run_conv(c, c->layers[b.conv2], tmp, C, nb, hs[i], wsz[i], at(feat_dev[i], i, C), C, 0, 1, 0, 0, gs, nullptr, 0, nullptr,
-                         last ? &head : nullptr, last ? head_done : nullptr)))
-        return rc;
-      cur = at(feat_dev[i], i, C);
-      cur_ld = C;
+      void *cat = at(cat_dev[i], i, 2 * C), *feat = at(feat_dev[i], i, C);
+      if ((rc = conv(b.up, i + 1, {.in = cur, .ldin = cur_ld, .out = cat, .ldout = 2 * C, .coff = C, .Hout = hs[i], .Wout = wsz[i]}))) return rc;
+      if ((rc = conv(b.conv1, i, {.in = cat, .ldin = 2 * C, .out = tmp, .ldout = C, .relu = 1}))) return rc;
+      ConvTaken took;
+      if ((rc = conv(b.conv2, i, {.in = tmp, .ldin = C, .out = feat, .ldout = C, .relu = 1}, {.head = last ? &head : nullptr}, &took))) return rc;
+      if (last) *head_done = took.head;
+      cur = feat, cur_ld = C;
     }
     return MGU_OK;
   };
@@ -635,7 +620,7 @@ int mgu_unet_forward(mgu_ctx* c, const void* x_dev, int B, int H, int W, int64_t
       ProfScope ps(c, s, "conv1x1_head_kernel", 2.0 * B * H * W * F.Cin * c->ncls, 0, -1);
       HIPCHK(c, launch_conv1x1_head(cur, c->dtype, cur_ld, F.Cin, F.w_src, F.b_src, (float*)logits_dev, c->ncls, c->ncls,
                                     (int64_t)B * H * W, s));   // logits are always fp32
-    } else if ((rc = run_conv(c, F, cur, cur_ld, B, H, W, logits_dev, c->ncls, 0, 0, 0, 0, s))) {
+    } else if ((rc = run_layer(c, F, {.in = cur, .ldin = cur_ld, .B = B, .H = H, .W = W, .out = logits_dev, .ldout = c->ncls, .shift = F.shift}, s))) {
       return rc;
     }
   }
@@ -669,14 +654,6 @@ struct mgu_conv_weights {
   Layer L;   // shape; L.wp, L.shift, L.wu in one allocation: [panel | bias-as-shift | U]
 };
 
-// the building blocks' layers: an fp32 Conv2d / ConvTranspose2d(2, 2) on Cin % 4 == 0 channels
-static Layer block_layer(int Cin, int Cout, int ksize, bool convt) {
-  Layer L;
-  L.Cin = L.Cp = Cin, L.Cout = Cout, L.KS = ksize, L.convt = convt;
-  L.K = ksize * ksize * Cin, L.Kp = rup(L.K, 32), L.N = convt ? 4 * Cout : Cout, L.Np = rup(L.N, 128);
-  return L;
-}
-
 // the Conv2d launch of both building blocks on the packed forms of L (L.shift: room for the bias)
 static int conv2d_launch(mgu_ctx* c, const Layer& L, const void* in_dev, int B, int H, int W, const void* bias_dev, const void* scale_dev,
                          const void* shift_dev, int relu, void* out_dev, int ld_out, int c_off, hipStream_t s) {
@@ -703,7 +680,7 @@ int mgu_conv2d_prepare(mgu_ctx* c, const void* w_dev, int Cout, int Cin, int ksi
   hipStream_t s = (hipStream_t)hip_stream;
   mgu_conv_weights* p = new mgu_conv_weights();
   Layer& L = p->L;
-  L = block_layer(Cin, Cout, ksize, false);
+  L = make_layer(MGU_DTYPE_F32, Cin, Cin, Cout, ksize, false);   // the building blocks run in fp32 on Cin % 4 == 0 channels
   const bool wino = wino_layer(c->tn, ksize, Cin);
   const size_t panel = (size_t)L.Np * L.Kp, total = panel + L.Np + (wino ? wino_u_floats(Cout, Cin) : 0);
   hipError_t e = hipMalloc((void**)&L.wp, total * sizeof(float));
@@ -759,7 +736,7 @@ int mgu_conv2d_nhwc(mgu_ctx* c, const void* in_dev, int B, int H, int W, int Cin
   if ((int64_t)B * H * W >= (1ll << 31)) return fail(c, MGU_ERR_INVALID, "B*H*W must be < 2^31");
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)hip_stream;
-  Layer L = block_layer(Cin, Cout, ksize, false);
+  Layer L = make_layer(MGU_DTYPE_F32, Cin, Cin, Cout, ksize, false);
   const size_t need = ((size_t)L.Np * L.Kp + 2 * (size_t)L.Np) * sizeof(float);   // panel + scale/shift
   int rc = ensure(c, &c->gws, &c->gws_bytes, need);
   if (rc) return rc;
@@ -784,7 +761,7 @@ int mgu_conv_transpose2x2_nhwc(mgu_ctx* c, const void* in_dev, int B, int H, int
   if ((int64_t)B * H * W * 4 >= (1ll << 31)) return fail(c, MGU_ERR_INVALID, "4*B*H*W must be < 2^31");
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)hip_stream;
-  Layer U = block_layer(Cin, Cout, 1, true);
+  Layer U = make_layer(MGU_DTYPE_F32, Cin, Cin, Cout, 1, true);
   // Two packed forms, each in a region of its own: the direct [4 Cout][Cin] panel the tile kernel reads (always built), and -- when
   // the layer shape is eligible and the context's switches allow it (MGU_NO_CONVT_FRAG, MGU_WINO_PREC) -- the fragment-order
   // three-piece weights of convt2x2_x3_kernel.  Which kernel runs is decided by pick_conv on the COMPLETE descriptor; a launch it

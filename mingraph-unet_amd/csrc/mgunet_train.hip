@@ -89,8 +89,8 @@ int block_backward(Bwd& w, const Block& b, const float* dy, int lddy, float* din
   mgu_ctx* c = w.c;
   const Layer &L1 = c->layers[b.conv1], &L2 = c->layers[b.conv2];
   int rc;
-  if ((rc = conv_bn_relu_backward(c, L2, dy, lddy, w.ta, flat_grads(w, L2), w.tb, L2.Cin, w, w.s))) return rc;   // d(y1), dense pitch C
-  return conv_bn_relu_backward(c, L1, w.tb, L2.Cin, w.ta, flat_grads(w, L1), dinput, ld_dinput, w, w.s);
+  if ((rc = conv_bn_relu_backward(c, L2, c->fwd[b.conv2], dy, lddy, w.ta, flat_grads(w, L2), w.tb, L2.Cin, w, w.s))) return rc;   // d(y1), dense pitch C
+  return conv_bn_relu_backward(c, L1, c->fwd[b.conv1], w.tb, L2.Cin, w.ta, flat_grads(w, L1), dinput, ld_dinput, w, w.s);
 }
 
 }  // namespace
@@ -107,56 +107,55 @@ int mgud::ensure_red(mgu_ctx* c, int Cmax) {
 }
 
 // conv (+bias) -> z ; batch statistics ; y = relu(bn(z)) written with pitch ldy
-int mgud::conv_bn_relu_train(mgu_ctx* c, Layer& L, const float* in, int ldin, int B, int H, int W, float* z, float* y, int ldy,
-                             double* sums, double* red, hipStream_t s, float* pooled, bool* pool_fused, bool* stats_fused) {
-  const int64_t M = (int64_t)B * H * W;
+int mgud::conv_bn_relu_train(mgu_ctx* c, const Layer& L, const FwdRecord& r, double* sums, double* red, hipStream_t s, float* pooled,
+                             ConvTaken* took) {
+  const int64_t M = (int64_t)r.B * r.H * r.W;
   const int C = L.Cout;
-  bool stats_done = false;   // Winograd layers accumulate sum z / sum z^2 in the conv epilogue
-  int rc = run_layer(c, L, in, ldin, B, H, W, z, C, 0, 0, nullptr, L.b_src, 0, 0, s, nullptr, 0, nullptr, red, &stats_done);  // unet_encoder.py:16 / :20
+  ConvTaken t;   // Winograd layers accumulate sum z / sum z^2 in the conv epilogue
+  int rc = run_layer(c, L, {.in = r.in, .ldin = r.ldin, .B = r.B, .H = r.H, .W = r.W, .out = r.z, .ldout = C, .shift = L.b_src}, s,
+                     {.stat_slots = red}, &t);  // unet_encoder.py:16 / :20
   if (rc) return rc;
-  if (stats_fused) *stats_fused = stats_done;
-  if (stats_done) {
-    HIPCHK(c, launch_bn_finalize_slots(red, c->last_stat_rows, sums, M, 1e-5f, 0.1f, L.gamma, L.beta, L.mean, L.invstd, L.tscale, L.tshift, L.run_mean,
+  if (took) *took = t;
+  if (t.stats) {
+    HIPCHK(c, launch_bn_finalize_slots(red, t.stat_rows, sums, M, 1e-5f, 0.1f, L.gamma, L.beta, L.mean, L.invstd, L.tscale, L.tshift, L.run_mean,
                                        L.run_var, C, s));  // nn.BatchNorm2d defaults, unet_encoder.py:12-13
   } else {
-    HIPCHK(c, launch_bn_stats(z, C, M, C, red, sums, s));
+    HIPCHK(c, launch_bn_stats(r.z, C, M, C, red, sums, s));
     HIPCHK(c, launch_bn_finalize(sums, sums + C, M, 1e-5f, 0.1f, L.gamma, L.beta, L.mean, L.invstd, L.tscale, L.tshift,
                                  L.run_mean, L.run_var, C, s));
   }
-  if (pool_fused) *pool_fused = false;
-  if (pooled && !(H & 1) && !(W & 1)) {   // MaxPool2d(2) of y in the same pass (even sizes: windows tile the image)
-    HIPCHK(c, launch_bn_apply_relu_pool(z, L.tscale, L.tshift, y, ldy, pooled, B, H, W, C, s));
-    if (pool_fused) *pool_fused = true;
+  if (pooled && !(r.H & 1) && !(r.W & 1)) {   // MaxPool2d(2) of y in the same pass (even sizes: windows tile the image)
+    HIPCHK(c, launch_bn_apply_relu_pool(r.z, L.tscale, L.tshift, r.y, r.ldy, pooled, r.B, r.H, r.W, C, s));
+    if (took) took->pool = true;
   } else {
-    HIPCHK(c, launch_bn_apply_relu(z, L.tscale, L.tshift, y, ldy, M, C, s));
-    if (pooled) HIPCHK(c, launch_maxpool2(y, ldy, pooled, 0, B, H, W, C, s));   // odd sizes: floor-mode windows leave a row / column out
+    HIPCHK(c, launch_bn_apply_relu(r.z, L.tscale, L.tshift, r.y, r.ldy, M, C, s));
+    if (pooled) HIPCHK(c, launch_maxpool2(r.y, r.ldy, pooled, 0, r.B, r.H, r.W, C, s));   // odd sizes: floor-mode windows leave a row / column out
   }
-  L.t_in = in, L.t_ldin = ldin, L.t_z = z, L.t_y = y, L.t_ldy = ldy, L.t_B = B, L.t_H = H, L.t_W = W;
   return MGU_OK;
 }
 
 // BN(train) + ReLU backward, weight gradient (+ the bias gradient's fold), data gradient of one conv -> BN -> ReLU
-int mgud::conv_bn_relu_backward(mgu_ctx* c, const Layer& L, const float* dy, int lddy, float* dz, const LayerGrads& g, float* din,
-                                int ld_din, const BwdScratch& w, hipStream_t s) {
-  const int64_t M = (int64_t)L.t_B * L.t_H * L.t_W;
+int mgud::conv_bn_relu_backward(mgu_ctx* c, const Layer& L, const FwdRecord& r, const float* dy, int lddy, float* dz, const LayerGrads& g,
+                                float* din, int ld_din, const BwdScratch& w, hipStream_t s) {
+  const int64_t M = (int64_t)r.B * r.H * r.W;
   const int C = L.Cout;
-  HIPCHK(c, launch_bn_bwd_reduce(dy, lddy, L.tscale, L.tshift, L.t_z, C, L.mean, L.invstd, M, C, w.red, w.sums, g.dbeta, g.dgamma, s));
+  HIPCHK(c, launch_bn_bwd_reduce(dy, lddy, L.tscale, L.tshift, r.z, C, L.mean, L.invstd, M, C, w.red, w.sums, g.dbeta, g.dgamma, s));
   // dz and, fused, the column sums of dz (the conv bias gradient, analytically ~0 under BatchNorm): they stay in the reduction slots
   // until conv_wgrad -- the next user of the slots -- folds them inside its unpack launch
   int pend_rows = 0;
-  HIPCHK(c, launch_bn_bwd_apply_deferred(dy, lddy, L.tscale, L.tshift, L.t_z, L.mean, L.invstd, L.gamma, w.sums, M, C, dz, w.red,
+  HIPCHK(c, launch_bn_bwd_apply_deferred(dy, lddy, L.tscale, L.tshift, r.z, L.mean, L.invstd, L.gamma, w.sums, M, C, dz, w.red,
                                          &pend_rows, s));
   int rc;
-  if ((rc = conv_wgrad(c, L, dz, g.dw, w, true, s, &pend_rows, g.dbias))) return rc;
-  if (din && (rc = conv_dgrad(c, L, dz, din, ld_din, w, true, s))) return rc;
+  if ((rc = conv_wgrad(c, L, r, dz, g.dw, w, true, s, &pend_rows, g.dbias))) return rc;
+  if (din && (rc = conv_dgrad(c, L, r, dz, din, ld_din, w, true, s))) return rc;
   return MGU_OK;
 }
 
 // weight gradient of a conv layer: Z = dz (dense, pitch rup(Cout, 4)), A = gather of the layer's input
-int mgud::conv_wgrad(mgu_ctx* c, const Layer& L, const float* dz, float* dw, const BwdScratch& w, bool record, hipStream_t s,
-                     int* fold_rows, float* dbias) {
+int mgud::conv_wgrad(mgu_ctx* c, const Layer& L, const FwdRecord& r, const float* dz, float* dw, const BwdScratch& w, bool record,
+                     hipStream_t s, int* fold_rows, float* dbias) {
   const int N = rup(L.Cout, 4);
-  WgradDesc d = wgrad_desc(c, dz, N, L.t_in, L.t_ldin, 0, L.Cp, L.KS, L.t_B, L.t_H, L.t_W, 0, 0, N, w.dwp, w.dwp_floats);
+  WgradDesc d = wgrad_desc(c, dz, N, r.in, r.ldin, 0, L.Cp, L.KS, r.B, r.H, r.W, 0, 0, N, w.dwp, w.dwp_floats);
   {
     const double alg = 2.0 * d.M * (double)L.KS * L.KS * L.Cin * L.Cout;
     const WgradKernel k = pick_wgrad(d);
@@ -176,9 +175,10 @@ int mgud::conv_wgrad(mgu_ctx* c, const Layer& L, const float* dz, float* dw, con
 }
 
 // data gradient of a conv layer: din = conv(dz, flipped/transposed W) -> out (pitch ldout)
-int mgud::conv_dgrad(mgu_ctx* c, const Layer& L, const float* dz, float* out, int ldout, const BwdScratch& w, bool record, hipStream_t s) {
+int mgud::conv_dgrad(mgu_ctx* c, const Layer& L, const FwdRecord& r, const float* dz, float* out, int ldout, const BwdScratch& w,
+                     bool record, hipStream_t s) {
   const int Cop = rup(L.Cout, 4);
-  IgemmDesc d = dgrad_desc(c, L, dz, Cop, L.wxg_valid ? L.wxg : w.dgp, out, ldout);
+  IgemmDesc d = dgrad_desc(c, L, r, dz, Cop, L.wxg_valid ? L.wxg : w.dgp, out, ldout);
   if (L.wug && wino_dgrad_layer(c->tn, L.KS, Cop)) d.wu = L.wug;   // same Winograd kernel, weights flipped + transposed
   // only the weight form the chosen kernel reads is built -- Winograd U or the direct flipped/transposed panel -- unless the layer
   // keeps a current one (normally packed with all the others by the last weight refresh, repack_weights)
@@ -202,9 +202,9 @@ int mgud::conv_dgrad(mgu_ctx* c, const Layer& L, const float* dz, float* out, in
 // ConvTranspose2d(2, 2) data gradient: the 2x2 stride-2 gather of d(out) (channels at dout, pitch ld_d, on its Hout x Wout grid) -> out
 // (dense, pitch Cin).  The forward layer's three-piece kernel in its gather mode (convt_x3.hip) where the shapes allow, else the
 // generic tile kernel.
-int mgud::convt_dgrad(mgu_ctx* c, const Layer& U, const float* dout, int ld_d, int Hout, int Wout, float* out, const BwdScratch& w,
-                      bool record, hipStream_t s) {
-  IgemmDesc q = dgrad_desc(c, U, dout, ld_d, w.dgp, out, U.Cin, Hout, Wout);
+int mgud::convt_dgrad(mgu_ctx* c, const Layer& U, const FwdRecord& r, const float* dout, int ld_d, int Hout, int Wout, float* out,
+                      const BwdScratch& w, bool record, hipStream_t s) {
+  IgemmDesc q = dgrad_desc(c, U, r, dout, ld_d, w.dgp, out, U.Cin, Hout, Wout);
   if (U.wxg_valid || convt_x3_dgrad_floats(U.Cin, U.Cout) <= w.dgp_floats) q.wu = U.wxg_valid ? U.wxg : w.dgp;
   const ConvKernel k = pick_conv(q, 0);
   if (k != ConvKernel::ConvtX3Dgrad) {
@@ -222,9 +222,9 @@ int mgud::convt_dgrad(mgu_ctx* c, const Layer& U, const float* dout, int ld_d, i
 
 // ConvTranspose2d(2, 2) weight gradient: the roles swap -- Z = the layer's INPUT (M, Cin), A = the 2x2 stride-2 gather of d(out)
 // (channels [c_off, c_off + Cout) of a pixel with pitch ld_d, on its Hout x Wout grid)
-int mgud::convt_wgrad(mgu_ctx* c, const Layer& U, const float* dout, int ld_d, int c_off, int Hout, int Wout, float* dw,
+int mgud::convt_wgrad(mgu_ctx* c, const Layer& U, const FwdRecord& r, const float* dout, int ld_d, int c_off, int Hout, int Wout, float* dw,
                       const BwdScratch& w, hipStream_t s) {
-  WgradDesc g = wgrad_desc(c, U.t_in, U.t_ldin, dout, ld_d, c_off, U.Cout, 2, U.t_B, U.t_H, U.t_W, Hout, Wout, U.Cin, w.dwp, w.dwp_floats);
+  WgradDesc g = wgrad_desc(c, r.in, r.ldin, dout, ld_d, c_off, U.Cout, 2, r.B, r.H, r.W, Hout, Wout, U.Cin, w.dwp, w.dwp_floats);
   HIPCHK(c, launch_wgrad_f32(g, s));
   HIPCHK(c, launch_unpack_convt_grad(w.dwp, g.groups, (size_t)g.N * g.Kp, dw, U.Cin, U.Cout, g.Kp, s));
   return MGU_OK;
@@ -258,15 +258,14 @@ int mgud::unet_forward_train(mgu_ctx* c, const float* x, int64_t xs_n, int64_t x
 
   // conv1 -> BN -> ReLU -> conv2 -> BN -> ReLU of block b on its level, output y with pitch ldy (and, fused where it can be, pooled)
   auto block = [&](const Block& b, const float* in, int ldin, float* y, int ldy, float* pooled) {
-    Layer &L1 = c->layers[b.conv1], &L2 = c->layers[b.conv2];
-    const int i = b.level, C = L1.Cout;
-    int r = conv_bn_relu_train(c, L1, in, ldin, B, hs[i], ws[i], at(c, p.z[b.conv1]), at(c, p.y1[b.conv1]), C, sums, red, s);
+    const int i = b.level, C = c->layers[b.conv1].Cout;
+    FwdRecord &r1 = c->fwd[b.conv1], &r2 = c->fwd[b.conv2];
+    r1 = FwdRecord{in, ldin, at(c, p.z[b.conv1]), at(c, p.y1[b.conv1]), C, B, hs[i], ws[i]};
+    r2 = FwdRecord{r1.y, C, at(c, p.z[b.conv2]), y, ldy, B, hs[i], ws[i]};
+    int r = conv_bn_relu_train(c, c->layers[b.conv1], r1, sums, red, s);
     if (r) return r;
-    return conv_bn_relu_train(c, L2, at(c, p.y1[b.conv1]), C, B, hs[i], ws[i], at(c, p.z[b.conv2]), y, ldy, sums, red, s, pooled);
+    return conv_bn_relu_train(c, c->layers[b.conv2], r2, sums, red, s, pooled);
   };
-  c->t_cat.assign(c->depth, nullptr);
-  c->t_feat.assign(c->depth, nullptr);
-  c->t_pooled.assign(c->depth, nullptr);
   const float* cur = xin;
   int ld = c->Cp0;
   for (const Block& b : c->enc) {  // encoder
@@ -274,7 +273,6 @@ int mgud::unet_forward_train(mgu_ctx* c, const float* x, int64_t xs_n, int64_t x
     float* cat = (float*)cat_dev[i];
     float* pooled = at(c, p.pooled[i]);
     if ((rc = block(b, cur, ld, cat, 2 * C, pooled))) return rc;
-    c->t_cat[i] = cat, c->t_pooled[i] = pooled;
     cur = pooled, ld = C;
   }
   {  // bottleneck
@@ -287,21 +285,21 @@ int mgud::unet_forward_train(mgu_ctx* c, const float* x, int64_t xs_n, int64_t x
     const int i = b.level, C = c->layers[b.conv1].Cout;
     float* cat = (float*)cat_dev[i];
     float* feat = (float*)feat_dev[i];
-    Layer& U = c->layers[b.up];
-    if ((rc = run_layer(c, U, cur, ld, B, hs[i + 1], ws[i + 1], cat, 2 * C, C, 0, nullptr, U.shift, hs[i], ws[i], s))) return rc;
-    U.t_in = cur, U.t_ldin = ld, U.t_B = B, U.t_H = hs[i + 1], U.t_W = ws[i + 1];
+    const Layer& U = c->layers[b.up];
+    if ((rc = run_layer(c, U, {.in = cur, .ldin = ld, .B = B, .H = hs[i + 1], .W = ws[i + 1], .out = cat, .ldout = 2 * C, .coff = C,
+                               .shift = U.shift, .Hout = hs[i], .Wout = ws[i]}, s)))
+      return rc;
+    c->fwd[b.up] = FwdRecord{cur, ld, nullptr, nullptr, 0, B, hs[i + 1], ws[i + 1]};
     if ((rc = block(b, cat, 2 * C, feat, C, nullptr))) return rc;
-    c->t_feat[i] = feat;
     cur = feat, ld = C;
   }
-  Layer& F = c->layers[c->head];
+  const Layer& F = c->layers[c->head];
+  c->fwd[c->head] = FwdRecord{cur, ld, nullptr, nullptr, 0, B, H, W};
   if (c->ncls <= 4) {
     HIPCHK(c, launch_conv1x1_head(cur, 0, ld, F.Cin, F.w_src, F.b_src, logits, c->ncls, c->ncls, (int64_t)B * H * W, s));
-  } else if ((rc = run_layer(c, F, cur, ld, B, H, W, logits, c->ncls, 0, 0, nullptr, F.shift, 0, 0, s))) {
+  } else if ((rc = run_layer(c, F, {.in = cur, .ldin = ld, .B = B, .H = H, .W = W, .out = logits, .ldout = c->ncls, .shift = F.shift}, s))) {
     return rc;
   }
-  F.t_in = cur, F.t_ldin = ld, F.t_B = B, F.t_H = H, F.t_W = W;
-  c->t_logits = logits;
   c->tB = B, c->tH = H, c->tW = W;
   c->have_train_fwd = true;
   return MGU_OK;
@@ -389,9 +387,9 @@ static int backward_body(mgu_ctx* c, const void* dlogits_dev, void* flat_grad_de
   const float* dlog = (const float*)dlogits_dev;
   HIPCHK(c, launch_colsum(dlog, ldd, (int64_t)B * H * W, ldd, w.red, (float*)w.sums, s));   // padded to ldd columns, then trimmed
   HIPCHK(c, hipMemcpyAsync(w.flat + F.off_b, w.sums, sizeof(float) * c->ncls, hipMemcpyDeviceToDevice, s));
-  if ((rc = conv_wgrad(c, F, dlog, w.flat + F.off_w, w, false, s))) return rc;
+  if ((rc = conv_wgrad(c, F, c->fwd[c->head], dlog, w.flat + F.off_w, w, false, s))) return rc;
   // the panel of the data gradient: normally already packed with every other weight form by the last refresh (repack_weights)
-  if ((rc = conv_dgrad(c, F, dlog, tc, F.Cin, w, false, s))) return rc;
+  if ((rc = conv_dgrad(c, F, c->fwd[c->head], dlog, tc, F.Cin, w, false, s))) return rc;
   const float* dy = tc;
   int lddy = F.Cin;
   if ((rc = block_done(F.off_w, false))) return rc;
@@ -407,8 +405,8 @@ static int backward_body(mgu_ctx* c, const void* dlogits_dev, void* flat_grad_de
     if (2 * hs[i + 1] != hs[i] || 2 * ws[i + 1] != ws[i])  // F.pad backward (unet_decoder.py:46-47) drops the pad row/col
       HIPCHK(c, launch_zero_pad_region(dcat, 2 * C, C, C, B, hs[i], ws[i], 2 * hs[i + 1], 2 * ws[i + 1], s));
     HIPCHK(c, launch_colsum(dcat + C, 2 * C, Mi, C, w.red, w.flat + U.off_b, s));
-    if ((rc = convt_wgrad(c, U, dcat, 2 * C, C, hs[i], ws[i], w.flat + U.off_w, w, s))) return rc;
-    if ((rc = convt_dgrad(c, U, dcat + C, 2 * C, hs[i], ws[i], tc, w, true, s))) return rc;
+    if ((rc = convt_wgrad(c, U, c->fwd[b->up], dcat, 2 * C, C, hs[i], ws[i], w.flat + U.off_w, w, s))) return rc;
+    if ((rc = convt_dgrad(c, U, c->fwd[b->up], dcat + C, 2 * C, hs[i], ws[i], tc, w, true, s))) return rc;
     dy = tc, lddy = U.Cin;
     if ((rc = block_done(U.off_w, false))) return rc;
   }
@@ -423,8 +421,9 @@ static int backward_body(mgu_ctx* c, const void* dlogits_dev, void* flat_grad_de
     const int i = b->level, C = c->layers[b->conv1].Cout;
     const bool first = b + 1 == c->enc.rend();
     float* dcat = at(c, p.dcat[i]);
-    // d(skip) = d(cat)[:, :C] (decoder path) + MaxPool backward of d(pooled)
-    HIPCHK(c, launch_maxpool2_bwd_add(c->t_cat[i], 2 * C, tc, dcat, 2 * C, B, hs[i], ws[i], C, s));
+    // d(skip) = d(cat)[:, :C] (decoder path) + MaxPool backward of d(pooled); the skip is conv2's y, in the concat buffer
+    const FwdRecord& r2 = c->fwd[b->conv2];
+    HIPCHK(c, launch_maxpool2_bwd_add(r2.y, r2.ldy, tc, dcat, 2 * C, B, hs[i], ws[i], C, s));
     const Layer& L1 = c->layers[b->conv1];
     if ((rc = block_backward(w, *b, dcat, 2 * C, first ? nullptr : tc, L1.Cin))) return rc;
     if ((rc = block_done(L1.off_w, first))) return rc;
@@ -434,12 +433,7 @@ static int backward_body(mgu_ctx* c, const void* dlogits_dev, void* flat_grad_de
 }
 
 static int backward_impl(mgu_ctx* c, const void* dlogits_dev, void* flat_grad_dev, void* hip_stream, int exchange) {
-  const int rc = backward_body(c, dlogits_dev, flat_grad_dev, hip_stream, exchange);
-  if (rc != MGU_OK && c && c->redws) {
-    // an error return between a deferred column-sum pass and its fold would leave rows of the (otherwise self-cleaning) reduction
-    // slots non-zero for every later reduction: clear them
-    (void)hipMemsetAsync(c->redws, 0, c->redws_bytes, (hipStream_t)hip_stream);
-  }
+  const int rc = red_cleared_on_error(c, backward_body(c, dlogits_dev, flat_grad_dev, hip_stream, exchange), (hipStream_t)hip_stream);
   if (rc != MGU_OK && exchange && c && c->comm) {
     // an error return after some buckets were issued: the caller's stream must still be ordered behind the communicator
     // stream (the buckets read and write flat_grad_dev), or the caller could free / reuse the buffer under a running collective

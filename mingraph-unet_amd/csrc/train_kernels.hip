@@ -10,9 +10,9 @@ namespace mgu {
 // ------------------------------------------------------------------------------------------------
 // Per-channel reductions over the M pixels of an NHWC tensor.  Thread (q = t % (C/4), pl = t / (C/4))
 // accumulates float4 channel quads over rows pl, pl+npl, ... of the block's slab in fp32, the block
-// combines through LDS and adds ONE double per channel into slot (blockIdx % RED_SLOTS) of a slotted
-// accumulator [RED_SLOTS][2*C] (same-line double atomics serialise at ~12 ns each -- MI355X_MICROARCH.md
-// "fanin" -- so the adds are spread over 64 x 2C addresses); slot_reduce_kernel then folds the slots.
+// combines through LDS and adds ONE double per channel into row blockIdx.x -- a row of its own, zero on entry -- of the table
+// [rows][2*C] (common.h; the launcher keeps the grid <= CHAN_REDUCE_ROWS).  slot_reduce_kernel then folds the rows in a fixed order
+// and clears what it read: the sums are bitwise repeatable and the table is zero again for the next reduction, without a memset.
 //   mode 0: acc0 = sum z,               acc1 = sum z*z                    (BatchNorm batch statistics)
 //   mode 1: g = dy * (y > 0); xh = (z - mean) * invstd;  acc0 = sum g, acc1 = sum g*xh   (BN backward)
 //           y = relu(scale*z + shift) is NOT read back: its sign is recomputed from z with the forward's scale/shift

@@ -66,3 +66,17 @@ def test_weight_form_packers_live_in_pack_hip_only():
     kernels = {f: re.findall(r"__global__\s[^;{(]*?\b(pack_\w*)\s*\(", t) for f, t in SOURCES.items() if f.endswith(".hip")}
     assert {f: k for f, k in kernels.items() if k and f != "pack.hip"} == {"elementwise.hip": ["pack_input_kernel"]}
     assert sorted(kernels["pack.hip"]) == ["pack_batch_kernel", "pack_one_kernel"]
+
+
+HOST_CONV_FILES = ["mgunet_api.hip", "mgunet_train.hip", "bwd_blocks.hip"]
+RETIRED_HOST = ["caller_layer", "block_layer", "last_stat_rows", "t_ldin", "t_ldy", "t_feat", "t_pooled", "t_logits"]
+
+
+def test_layer_shapes_come_from_one_builder_and_launches_report_in_a_struct():
+    """make_layer (ctx.h) is the only place that derives K, Kp, N, Np of a layer: the host files of the convolution path assign
+    neither padded size themselves.  The private builders, the forward record kept inside Layer and the value handed back through
+    the context are gone, and no function of ctx.h reports through a bool* out-parameter."""
+    assert [f for f, _ in definitions("make_layer")] == ["ctx.h"]
+    assert [(f, m.group(0)) for f in HOST_CONV_FILES for m in re.finditer(r"[.>](?:Kp|Np)\s*=(?!=)", SOURCES[f])] == []
+    assert [(f, n) for f, t in SOURCES.items() for n in RETIRED_HOST if re.search(r"\b" + n + r"\b", t)] == []
+    assert re.findall(r"\bbool\s*\*", SOURCES["ctx.h"]) == []

@@ -190,6 +190,75 @@ def test_one_off_and_batched_weight_packs_write_the_same_bytes(cuda):
     assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
 
 
+def backward_as_trainer(tr, logits, masks, dev):
+    """the cross-entropy and mgu_unet_backward calls exactly as Trainer.forward_backward issues them, on the logits of a train-mode
+    forward the caller has already run"""
+    from mgunet import _lib
+    ctx = tr.model._context(dev)
+    B, Cc, H, W = logits.shape
+    nhwc = logits.permute(0, 2, 3, 1)
+    assert nhwc.is_contiguous()
+    npix, ldd = B * H * W, (Cc + 3) // 4 * 4
+    dlogits = torch.empty((npix, ldd), device=dev, dtype=torch.float32)
+    _lib.call("mgu_cross_entropy", dev, nhwc, masks.contiguous(), npix, Cc, 1.0 / npix, dlogits, tr._loss, ctx=ctx)
+    _lib.call("mgu_unet_backward", dev, dlogits, tr.grad, ctx=ctx)
+    return tr.grad.clone()
+
+
+def test_backward_follows_the_latest_forward(cuda):
+    """The backward reads the record of the LAST train-mode forward of its context: a forward at another batch size and grid before
+    the step leaves nothing behind.  The reductions are fixed-order, so the gradients agree bit for bit."""
+    cfg = (3, 2, 8, 2)
+    x1 = torch.from_numpy(O.formula_normal("record/x1", (2, 3, 16, 16), seed=51)).to(cuda)
+    x2 = torch.from_numpy(O.formula_normal("record/x2", (1, 3, 24, 40), seed=52)).to(cuda)
+    y2 = torch.from_numpy(O.formula_labels("record/y2", (1, 24, 40), cfg[1], seed=53)).to(cuda)
+    grads = []
+    for earlier_forward in (True, False):
+        model = build(cfg, 51, cuda)
+        tr = mgunet.Trainer(model)
+        if earlier_forward:
+            model.train()
+            model(x1)
+        tr.forward_backward(x2, y2)
+        grads.append(tr.grad.clone())
+    assert float(grads[1].abs().max()) > 0 and bool(torch.isfinite(grads[1]).all())
+    assert torch.equal(grads[0], grads[1])
+
+
+def test_building_block_between_forward_and_backward_leaves_the_step_alone(cuda):
+    """A backward building block on the model's own context shares the reduction slots with the step, runs in the building-block
+    scratch and describes its forward with a record of its own: called between the train-mode forward and mgu_unet_backward it
+    changes no bit of the step's gradient."""
+    from mgunet import _lib
+    cfg, shape = (3, 2, 8, 2), (2, 3, 16, 16)
+    x = torch.from_numpy(O.formula_normal("record/x1", shape, seed=51)).to(cuda)
+    y = torch.from_numpy(O.formula_labels("record/y1", (2, 16, 16), cfg[1], seed=54)).to(cuda)
+    B, H, W, Cc = 1, 8, 8, 8
+    t = {k: torch.from_numpy(O.formula_normal("record/" + k, s, seed=55 + i)).to(cuda)
+         for i, (k, s) in enumerate({"in": (B, H, W, Cc), "z": (B, H, W, Cc), "dy": (B, H, W, Cc), "w": (Cc, Cc, 3, 3), "gamma": (Cc,),
+                                     "beta": (Cc,), "mean": (Cc,)}.items())}
+    t["invstd"] = torch.full((Cc,), 0.75, device=cuda)
+    grads = []
+    for interleave in (True, False):
+        model = build(cfg, 51, cuda)
+        tr = mgunet.Trainer(model)
+        model.train()
+        logits = model(x)[0]
+        if interleave:
+            ctx = model._context(cuda)
+            o = {k: torch.empty(s, device=cuda) for k, s in {"dz": (B, H, W, Cc), "dw": (Cc, Cc, 3, 3), "din": (B, H, W, Cc), "dgamma": (Cc,),
+                                                             "dbeta": (Cc,), "dbias": (Cc,)}.items()}
+            _lib.check(_lib.lib().mgu_bn_relu_conv_backward_nhwc(
+                ctx.handle, t["in"].data_ptr(), Cc, t["z"].data_ptr(), t["dy"].data_ptr(), Cc, t["gamma"].data_ptr(), t["beta"].data_ptr(),
+                t["mean"].data_ptr(), t["invstd"].data_ptr(), t["w"].data_ptr(), B, H, W, Cc, Cc, o["dz"].data_ptr(), o["dgamma"].data_ptr(),
+                o["dbeta"].data_ptr(), o["dbias"].data_ptr(), o["dw"].data_ptr(), o["din"].data_ptr(), Cc, _lib.current_stream_ptr(cuda)),
+                ctx.handle)
+            assert float(o["dw"].abs().max()) > 0 and all(bool(torch.isfinite(v).all()) for v in o.values())
+        grads.append(backward_as_trainer(tr, logits, y, cuda))
+    assert float(grads[1].abs().max()) > 0 and bool(torch.isfinite(grads[1]).all())
+    assert torch.equal(grads[0], grads[1])
+
+
 def test_adam_kernel_exact(cuda):
     """mgu_adam_step against torch.optim.Adam(lr, weight_decay) semantics evaluated in float64 on the host."""
     from mgunet import _lib

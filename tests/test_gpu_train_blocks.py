@@ -1,6 +1,6 @@
 """The train-mode half block -- Conv2d(3x3) -> BatchNorm2d(batch statistics) -> ReLU [-> MaxPool2d(2)] -- and its backward, each
 in isolation against FLOAT64 torch on the CPU, through the functions the training step itself runs per layer (include/mgunet.h
-"train-step building blocks": conv_bn_relu_train / conv_bn_relu_backward of mgunet_train.hip on the caller's tensors).  What the
+"train-step building blocks": conv_bn_relu_train / conv_bn_relu_backward of mgunet_train.hip on a FwdRecord of the caller's tensors).  What the
 whole-step tests (test_gpu_train.py) see only through 1e-3 logits and a gradient whose conditioning hides a 1 % kernel error is
 held here to the kernels' own bar, 2e-5 of the result's max: the statistics the six Winograd kernel forms accumulate in their
 epilogue, their fold (bn_finalize_slots_kernel), the pooled apply pass, the deferred bias-gradient fold of the gradient unpack
