@@ -518,6 +518,38 @@ int mgu_split_objects(mgu_ctx* ctx, const int32_t* labels_dev, int B, int H, int
 int mgu_clean_masks(mgu_ctx* ctx, const void* src_dev, int src_kind, int B, int H, int W, int C, int64_t num_classes, int close_radius_sq,
                     int fill_holes, int64_t max_hole_area, int open_radius_sq, int64_t* out_dev, int64_t* counts_dev, void* hip_stream);
 
+/* ---- boundary evaluation: surface-distance histograms and band counts behind the BF score, Boundary IoU, Hausdorff, HD95, ASSD -----
+ * How well the outline of every class in a predicted map follows the outline of the same class in the target map: what region IoU
+ * barely registers.  The reference has no boundary metric; the definitions below are this build's own (after Csurka et al. 2013 and
+ * Cheng et al. 2021, with the two deviations stated).  All in exact integers: bitwise repeatable, comparable with ==.
+ * Input: pred_dev / pred_kind / C as mgu_clean_masks reads its source (0: int64 class map (B,H,W); 1: NHWC fp32 logits with the argmax
+ * fused, first maximal class, bit-identical to mgu_argmax_classes; num_classes must then equal C).  target_dev: int64 class map
+ * (B,H,W).  Foreground classes are 1 .. num_classes-1 (2 <= num_classes <= 32); on both sides every other value (0, -100, out of
+ * range) reads as background.  Images never interact.  With X one of the maps P (prediction) and G (target) of one image:
+ *   Boundary.  dX_c = the pixels of class c in X that have a 4-neighbour INSIDE THE IMAGE holding another value.  Pixels outside the
+ *     image do not count, as in mgu_distance_transform and the opening of mgu_clean_masks: a fruit cut by the frame has no contour
+ *     along the frame, and a map that is entirely class c has an empty boundary.  (The published Boundary IoU code pads the mask with
+ *     background, so there an object keeps a contour along the frame: it differs here.)  Equivalently: D2_X(p) == 1.
+ *   Surface distance.  Direction 0 (prediction to target): for every p in dP_c, d2(p) = min |p - q|^2 over q in dG_c, exact, int32; p
+ *     is UNMATCHED when dG_c is empty in that image.  Direction 1 (target to prediction) is the converse.
+ *   Band.  X_c^r = {p of class c in X : D2_X(p) <= band_r2} (band_r2 >= 1), D2_X = mgu_distance_transform of X's class map: the pixels
+ *     within a Euclidean disc of the other values -- not the paper's iterated 3x3 erosion.
+ * Outputs, all int64 and SET (not accumulated), with K = num_classes-1 and class c at index c-1:
+ *   hist_dev  (B, K, 2, max_d2 + 2), 1 <= max_d2 <= 4096: bin k <= max_d2 counts the source boundary pixels of that direction with
+ *             d2 == k; the last bin counts those with d2 > max_d2 plus the unmatched ones.
+ *   stats_dev (B, K, 2, 4): [n = source boundary pixels, n_unmatched, the max d2 over the matched pixels (0 if none), the sum over the
+ *             matched pixels of floor(sqrt(d2 * 2^32)) = floor(2^16 sqrt(d2))].  The last is defined on integers (math.isqrt(d2 << 32));
+ *             the kernel's fp64 root is only a first guess that integer comparisons correct, so no rounding mode enters.
+ *   band_dev  (B, K, 3): [|P_c^r & G_c^r|, |P_c^r|, |G_c^r|].
+ * 6 kernel launches and 3 fills whatever B, the classes and the boundaries (class planes; the two launches of the distance transform;
+ * site columns; site rows, where only the boundary pixels walk and a row without any leaves at once; bands); no host synchronisation;
+ * scratch from the context: 24 + 4 K bytes per pixel of B*H*W.  The site rows keep 4 bytes of LDS per pixel of a row plus 4 per
+ * bin (at most 80 KiB).  H, W <= 16384, B <= 32767 (2B planes are a grid dimension), 2B*(H*W+1) < 2^31.  B*H*W == 0: MGU_OK, nothing
+ * is touched. */
+int mgu_boundary_tables(mgu_ctx* ctx, const void* pred_dev, int pred_kind, const int64_t* target_dev, int B, int H, int W, int C,
+                        int64_t num_classes, int max_d2, int band_r2, int64_t* hist_dev, int64_t* stats_dev, int64_t* band_dev,
+                        void* hip_stream);
+
 /* ---- instance evaluation: mask overlaps of two label maps, mask-IoU matching, panoptic totals ---------------------------------------
  * The objects of both sides are what mgu_connected_components / mgu_split_objects (labels, offsets) and mgu_object_stats (class,
  * area) write for the same B images: "gt" and "pred".  Object capacities are the lengths of the per-object arrays; an image whose

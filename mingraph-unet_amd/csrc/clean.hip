@@ -37,9 +37,6 @@ struct Disc {
   signed char h[CL_MAX_R + 1];
 };
 
-// a foreground class 1..ncls-1, or 0 (background, -100, out of range)
-__device__ __forceinline__ int clean_class(long long v, int ncls) { return (v >= 1 && v < ncls) ? (int)v : 0; }
-
 // bits of the 64-pixel word starting at x = xw of row y that lie inside the image
 __device__ __forceinline__ u64 inside_word(int y, int xw, int H, int W) {
   if (y < 0 || y >= H) return 0;
@@ -99,7 +96,7 @@ __global__ __launch_bounds__(CL_THREADS) void morph_kernel(const void* __restric
     for (int row = 0; row < rows; ++row) {
       const int y = yh0 + row;
       int v = 0;
-      if (colin && y >= 0 && y < H) v = clean_class(pix_key<KIN>(src, base + (int64_t)y * W + x, C), ncls);
+      if (colin && y >= 0 && y < H) v = foreground_class(pix_key<KIN>(src, base + (int64_t)y * W + x, C), ncls);
       cls[row][tid] = (unsigned char)v;
       seen |= 1u << v;
     }
@@ -160,7 +157,7 @@ __global__ __launch_bounds__(CL_THREADS) void morph_kernel(const void* __restric
 template <int KIN>
 __global__ __launch_bounds__(CL_THREADS) void clean_copy_kernel(const void* __restrict__ src, int64_t n, int C, int ncls, long long* __restrict__ out) {
   const int64_t g = (int64_t)blockIdx.x * CL_THREADS + threadIdx.x;
-  if (g < n) out[g] = clean_class(pix_key<KIN>(src, g, C), ncls);
+  if (g < n) out[g] = foreground_class(pix_key<KIN>(src, g, C), ncls);
 }
 
 // fill (1): the background mask for the union-find, the uint8 class map (KIN 3: src is that map already) and cleared counters
@@ -169,7 +166,7 @@ __global__ __launch_bounds__(CL_THREADS) void fill_prepare_kernel(const void* __
                                                                    int* __restrict__ bgmask, unsigned* __restrict__ area, unsigned* __restrict__ info) {
   const int64_t g = (int64_t)blockIdx.x * CL_THREADS + threadIdx.x;
   if (g >= n) return;
-  const int v = clean_class(pix_key<KIN>(src, g, C), ncls);
+  const int v = foreground_class(pix_key<KIN>(src, g, C), ncls);
   if (KIN != 3) cm[g] = (unsigned char)v;
   bgmask[g] = v == 0;
   area[g] = 0;

@@ -1,7 +1,7 @@
-// Helpers shared by the object-level kernel files (objects.hip, shapes.hip, split.hip, instances.hip, clean.hip): each is defined here and
-// nowhere else under csrc/ (tests/test_csrc_helpers.py).  device.h keeps what every kernel file shares.
-//   device: wave_by_key | block_exclusive_scan | chunk_sum_scan | object_index | objects_recorded | pix_key
-//   host:   check_pixel_count | clear_counts
+// Helpers shared by the object-level kernel files (objects.hip, shapes.hip, split.hip, instances.hip, clean.hip, boundary.hip): each is
+// defined here and nowhere else under csrc/ (tests/test_csrc_helpers.py).  device.h keeps what every kernel file shares.
+//   device: wave_by_key | block_exclusive_scan | chunk_sum_scan | object_index | objects_recorded | pix_key | foreground_class
+//   host:   check_pixel_count | clear_counts | distance_transform, distance_transform_dims (declared here, defined in split.hip)
 #pragma once
 #include <climits>
 
@@ -118,6 +118,9 @@ __device__ __forceinline__ long long pix_key(const void* src, int64_t g, int C) 
   }
 }
 
+// a foreground class 1..ncls-1 of clean.hip and boundary.hip, or 0 (background, -100, out of range)
+__device__ __forceinline__ int foreground_class(long long v, int ncls) { return (v >= 1 && v < ncls) ? (int)v : 0; }
+
 }  // namespace mgu
 
 namespace mgud {
@@ -127,6 +130,12 @@ inline int check_pixel_count(mgu_ctx* c, const char* fn, int B, int H, int W) {
   if ((double)B * H * W >= (double)INT_MAX) return fail(c, MGU_ERR_INVALID, "%s: B*H*W must stay below 2^31", fn);
   return MGU_OK;
 }
+// split.hip's exact squared distance transform, shared with boundary.hip: D2 of an int32 label map (B, H, W) into d2 (MGU_D2_NONE where
+// an image holds no other label, 0 on label 0), with the column distances in g (B*H*W ints of scratch): two launches.  maxlab >= 0
+// reads a label outside [0, maxlab] as 0; -1 takes every int32 label.  distance_transform_dims checks what its kernels need of the
+// sizes: H, W <= 16384, B <= 65535, B*(H*W+1) < 2^31.
+int distance_transform(mgu_ctx* c, const int32_t* labels, int B, int H, int W, int maxlab, int* g, int32_t* d2, hipStream_t s);
+int distance_transform_dims(mgu_ctx* c, const char* fn, int B, int H, int W);
 // a batch without pixels: every count and offset is 0
 inline int clear_counts(mgu_ctx* c, int B, int64_t* counts, int64_t* offsets, hipStream_t s) {
   HIPCHK(c, hipMemsetAsync(counts, 0, (size_t)B * sizeof(int64_t), s));

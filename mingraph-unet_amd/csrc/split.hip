@@ -240,8 +240,9 @@ bool g_row_lds[64];
 using namespace mgu;
 using namespace mgud;
 
-// D2 of labels into d2 with the column distances in g (n ints of scratch): two launches
-static int distance_transform(mgu_ctx* c, const int32_t* labels, int B, int H, int W, int maxlab, int* g, int32_t* d2, hipStream_t s) {
+// D2 of labels into d2 with the column distances in g (n ints of scratch): two launches (declared in objects_common.h: boundary.hip
+// runs it on its class planes)
+int mgud::distance_transform(mgu_ctx* c, const int32_t* labels, int B, int H, int W, int maxlab, int* g, int32_t* d2, hipStream_t s) {
   const size_t lds = (size_t)W * 8;
   if (lds > 65536) {   // the opt-in is set once per device: for the widest row, not for this call's
     int budget = 0;
@@ -255,7 +256,7 @@ static int distance_transform(mgu_ctx* c, const int32_t* labels, int B, int H, i
   return MGU_OK;
 }
 
-static int check_dims(mgu_ctx* c, const char* fn, int B, int H, int W) {
+int mgud::distance_transform_dims(mgu_ctx* c, const char* fn, int B, int H, int W) {
   if (B < 0 || H < 0 || W < 0) return fail(c, MGU_ERR_INVALID, "%s: negative size", fn);
   if (H > SP_MAX_DIM || W > SP_MAX_DIM) return fail(c, MGU_ERR_INVALID, "%s: H and W at most %d", fn, SP_MAX_DIM);
   if (B > 65535) return fail(c, MGU_ERR_INVALID, "%s: at most 65535 images per call", fn);
@@ -268,7 +269,7 @@ extern "C" {
 int mgu_distance_transform(mgu_ctx* c, const int32_t* labels_dev, int B, int H, int W, int32_t* d2_dev, void* hip_stream) {
   if (!c) return MGU_ERR_INVALID;
   if (!labels_dev || !d2_dev) return fail(c, MGU_ERR_INVALID, "bad distance_transform args (null pointer)");
-  int rc = check_dims(c, "distance_transform", B, H, W);
+  int rc = distance_transform_dims(c, "distance_transform", B, H, W);
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   const int64_t n = (int64_t)B * H * W;
@@ -283,7 +284,7 @@ int mgu_split_objects(mgu_ctx* c, const int32_t* labels_dev, int B, int H, int W
                       void* hip_stream) {
   if (!c) return MGU_ERR_INVALID;
   if (!labels_dev || !labels_out_dev || !counts_dev || !offsets_dev) return fail(c, MGU_ERR_INVALID, "bad split_objects args (null pointer)");
-  int rc = check_dims(c, "split_objects", B, H, W);
+  int rc = distance_transform_dims(c, "split_objects", B, H, W);
   if (rc) return rc;
   if (min_distance < 1 || min_distance > SP_MAX_R) return fail(c, MGU_ERR_INVALID, "split_objects: min_distance %d (1..%d)", min_distance, SP_MAX_R);
   if (min_radius_sq < 1 || min_area < 0) return fail(c, MGU_ERR_INVALID, "split_objects: min_radius_sq must be >= 1 and min_area >= 0");
