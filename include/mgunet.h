@@ -196,9 +196,10 @@ int mgu_maxpool2x2_backward_nhwc(mgu_ctx* ctx, const void* y_dev, int ld_y, cons
 
 /* torch.optim.Adam.step() with L2 weight decay folded into the gradient (train_segmentation.py:96):
  * g = grad_scale*grad + wd*p; m,v moments; p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps).  step t >= 1.
- * grad_scale lets the caller fold the 1/world_size of an all-reduce SUM into the update. */
+ * grad_scale lets the caller fold the 1/world_size of an all-reduce SUM into the update.  The betas are doubles, as torch keeps them:
+ * 1 - beta and 1 - beta^t are formed in double on the host and cast once (a beta2 rounded to fp32 puts both 1.3e-5 off). */
 int mgu_adam_step(mgu_ctx* ctx, void* flat_param_dev, const void* flat_grad_dev, void* exp_avg_dev, void* exp_avg_sq_dev,
-                  int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                  int64_t n, float lr, double beta1, double beta2, float eps, float weight_decay, int step,
                   float grad_scale, void* hip_stream);
 
 /* torch.optim.SGD(lr, momentum, weight_decay).step() on the flat buffers -- the other optimizer branch of the reference's train loop

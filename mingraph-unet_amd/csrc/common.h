@@ -304,7 +304,7 @@ hipError_t launch_unpack_conv_grad(const float* dwp, int groups, size_t panel_st
 hipError_t launch_unpack_convt_grad(const float* dwp, int groups, size_t panel_stride, float* g, int Cin, int Cout, int Kp, hipStream_t s);
 hipError_t launch_sgd(float* p, const float* g, float* buf, int64_t n, float lr, float momentum, float wd, int step, float grad_scale,
                       hipStream_t s);
-hipError_t launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps,
+hipError_t launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, double b1, double b2, float eps,
                        float wd, int step, float grad_scale, hipStream_t s);
 
 // elementwise.hip

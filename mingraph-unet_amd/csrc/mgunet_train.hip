@@ -457,7 +457,7 @@ int mgu_unet_backward_allreduce(mgu_ctx* c, const void* dlogits_dev, void* flat_
 }
 
 int mgu_adam_step(mgu_ctx* c, void* flat_param_dev, const void* flat_grad_dev, void* exp_avg_dev, void* exp_avg_sq_dev,
-                  int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                  int64_t n, float lr, double beta1, double beta2, float eps, float weight_decay, int step, float grad_scale,
                   void* hip_stream) {
   if (!c) return MGU_ERR_INVALID;
   if (!flat_param_dev || !flat_grad_dev || !exp_avg_dev || !exp_avg_sq_dev || n < 0 || step < 1)

@@ -21,11 +21,14 @@ constexpr long long IGNORE_INDEX = -100;   // nn.CrossEntropyLoss default
 
 // ---- C == 2 (configs/model.yaml): 16-byte loads, two pixels per lane and load -----------------------------------------------------
 // LOSS 0: counts (+ predictions) only, no exp/log.  1: + cross-entropy partials.  2: + dice partials.
-// Record of workgroup (b, blk): [ce_sum, counted, I0, I1, P0, P1, T0, T1] (LOSS 2) or [ce_sum, counted] (LOSS 1).
+// Record of workgroup (b, blk): [ce_sum, counted, D0, D1, P0, P1, T0, T1] (LOSS 2) or [ce_sum, counted] (LOSS 1).
+// Dice: with P = sum p_c and T = the label count, the dice term 1 - (2 I + s) / (P + T + s) is D / (P + T + s), D = P + T - 2 I = the
+// sum over the pixels of 1 - p_c where the label is c and of p_c elsewhere.  D is a sum of non-negative terms (PixelCE::miss forms
+// 1 - p_c without cancellation); 2 I + s against P + T + s cancels at 1, and a trained network's dice loss is 1e-5.
 template <int LOSS>
 struct C2Acc {
   unsigned n[4] = {0, 0, 0, 0};   // cm[y][p] at y * 2 + p
-  double ce = 0.0, I0 = 0.0, I1 = 0.0, P0 = 0.0, P1 = 0.0;
+  double ce = 0.0, D0 = 0.0, D1 = 0.0, P0 = 0.0, P1 = 0.0;
   bool bad = false;
   __device__ __forceinline__ int pixel(float l0, float l1, long long y) {
     const int p = l1 > l0 ? 1 : 0;   // first maximal index (strict >), as argmax_kernel
@@ -36,15 +39,17 @@ struct C2Acc {
     if constexpr (LOSS > 0) {
       const float mx = fmaxf(l0, l1);
       const float e0 = expf(l0 - mx), e1 = expf(l1 - mx);
-      const float se = e0 + e1;
+      PixelCE s;
+      s.add(0, e0);
+      s.add(1, e1);
       const bool counted = y == 0 || y == 1;
-      if (counted) ce += (double)(mx + logf(se) - (y ? l1 : l0));
+      if (counted) ce += (double)s.term(mx, y ? l1 : l0);
       else if (y != IGNORE_INDEX) ce += (double)__builtin_nanf(""), bad = true;   // mgu_cross_entropy's semantics
       if constexpr (LOSS == 2) {
         if (!counted) bad = true;   // F.one_hot raises on any label outside [0, C), -100 included (:34)
-        const float inv = 1.f / se, p0 = e0 * inv, p1 = e1 * inv;
-        I0 += y == 0 ? (double)p0 : 0.0;
-        I1 += y == 1 ? (double)p1 : 0.0;
+        const float inv = 1.f / s.se, p0 = e0 * inv, p1 = e1 * inv;
+        D0 += (double)(y == 0 ? s.miss(0, e0) : p0);
+        D1 += (double)(y == 1 ? s.miss(1, e1) : p1);
         P0 += (double)p0;
         P1 += (double)p1;
       }
@@ -109,7 +114,7 @@ __global__ __launch_bounds__(SE_THREADS) void seg_eval_c2_kernel(const float* __
       if ((tid & 63) == 0)
 #pragma unroll
         for (int k = 0; k < 4; ++k) shn[tid >> 6][k] = cnt[k];
-      double v[5] = {a.ce, a.I0, a.I1, a.P0, a.P1};
+      double v[5] = {a.ce, a.D0, a.D1, a.P0, a.P1};
       block_fold<5>(v, shd);   // its barrier also publishes shn
       if (tid == 0) {
         unsigned long long t[4];
@@ -143,7 +148,7 @@ __global__ __launch_bounds__(SE_THREADS) void seg_eval_c2_kernel(const float* __
 
 // ---- any C: scalar pixels, LDS histogram (or, past SE_HIST_CELLS, atomics to the caller's buffer) ---------------------------------
 // NC > 0: C <= NC, the logits of a pixel held in registers (LOSS 2 possible).  NC == 0: any C, LOSS 0 or 1.
-// Record of workgroup (b, blk): [ce_sum, counted, I[0..C), P[0..C), T[0..C)] (LOSS 2) or [ce_sum, counted].
+// Record of workgroup (b, blk): [ce_sum, counted, D[0..C), P[0..C), T[0..C)] (LOSS 2) or [ce_sum, counted].
 template <int NC, int LOSS>
 __global__ __launch_bounds__(SE_THREADS) void seg_eval_generic_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
                                                                       int B, int64_t HW, int C, long long* __restrict__ pred,
@@ -200,25 +205,25 @@ __global__ __launch_bounds__(SE_THREADS) void seg_eval_generic_kernel(const floa
         } else {
           for (int c = 1; c < C; ++c) mx = fmaxf(mx, p[c]);
         }
-        float se = 0.f;
+        PixelCE s;
         if (NC > 0) {
 #pragma unroll
           for (int c = 0; c < NC; ++c) {
             l[c] = c < C ? expf(l[c] - mx) : 0.f;
-            se += l[c];
+            if (c < C) s.add(c, l[c]);
           }
         } else {
-          for (int c = 0; c < C; ++c) se += expf(p[c] - mx);
+          for (int c = 0; c < C; ++c) s.add(c, expf(p[c] - mx));
         }
-        if (counted) v[0] += (double)(mx + logf(se) - p[y]), v[1] += 1.0;
+        if (counted) v[0] += (double)s.term(mx, p[y]), v[1] += 1.0;
         else if (y != IGNORE_INDEX) v[0] += (double)__builtin_nanf(""), bad = true;
         if constexpr (LOSS == 2) {
           if (!counted) bad = true;
-          const float inv = 1.f / se;
+          const float inv = 1.f / s.se;
 #pragma unroll
           for (int c = 0; c < (NC > 0 ? NC : 1); ++c) {
             const float pc = l[c] * inv;
-            v[2 + c] += y == c ? (double)pc : 0.0;
+            v[2 + c] += (double)(y == c ? s.miss(c, l[c]) : pc);
             v[2 + NC + c] += (double)pc;
             v[2 + 2 * NC + c] += y == c ? 1.0 : 0.0;
           }
@@ -258,12 +263,12 @@ __global__ __launch_bounds__(SE_THREADS) void seg_eval_final_kernel(const double
     for (int64_t t = tid; t < (int64_t)B * C; t += SE_THREADS) {
       const int64_t b = t / C;
       const int c = (int)(t - b * C);
-      double I = 0, P = 0, T = 0;
+      double D = 0, P = 0, T = 0;
       for (int k = 0; k < nb; ++k) {
         const double* r = part + (b * nb + k) * S;
-        I += r[2 + c], P += r[2 + C + c], T += r[2 + 2 * C + c];
+        D += r[2 + c], P += r[2 + C + c], T += r[2 + 2 * C + c];
       }
-      terms[t] = (2.0 * I + smooth) / (P + T + smooth);   // train_segmentation.py:39
+      terms[t] = D / (P + T + smooth);   // 1 - (2 I + smooth) / (P + T + smooth), train_segmentation.py:39
     }
   __syncthreads();
   if (tid == 0) {
@@ -271,7 +276,7 @@ __global__ __launch_bounds__(SE_THREADS) void seg_eval_final_kernel(const double
     if (dice) {
       double s = 0.0;
       for (int64_t t = 0; t < (int64_t)B * C; ++t) s += terms[t];
-      loss += (float)(1.0 - s / ((double)B * C));   // :40; loss_ce + loss_dice in fp32 (:130)
+      loss += (float)(s / ((double)B * C));   // :40, the mean of 1 - dice; loss_ce + loss_dice in fp32 (:130)
     }
     acc[0] += (double)loss;
     acc[1] += 1.0;

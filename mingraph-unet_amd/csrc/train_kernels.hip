@@ -443,15 +443,17 @@ __global__ __launch_bounds__(256) void ce_fwd_bwd_kernel(const float* __restrict
     const int y = counted ? (int)yl : 0;
     float mx = p[0];
     for (int c = 1; c < C; ++c) mx = fmaxf(mx, p[c]);
-    float se = 0.f;
-    for (int c = 0; c < C; ++c) se += expf(p[c] - mx);
-    const float lse = mx + logf(se);
-    if (counted) local += (double)(lse - p[y]);
+    PixelCE s;
+    for (int c = 0; c < C; ++c) s.add(c, expf(p[c] - mx));
+    if (counted) local += (double)s.term(mx, p[y]);
     else if (yl != ignore_index) local += (double)__builtin_nanf("");   // out-of-range label: the loss says so
-    const float inv = 1.f / se;
+    const float inv = 1.f / s.se;
     for (int c = 0; c < ldd; ++c) {
       float g = 0.f;
-      if (c < C && counted) g = (expf(p[c] - mx) * inv - (c == y ? 1.f : 0.f)) * gs;
+      if (c < C && counted) {   // softmax[c] - [c == y]; the label class as -(1 - softmax[y]) without the cancellation
+        const float e = expf(p[c] - mx);
+        g = (c == y ? -s.miss(c, e) : e * inv) * gs;
+      }
       dlogits[i * ldd + c] = g;
     }
   }
@@ -618,24 +620,27 @@ hipError_t launch_unpack_convt_grad(const float* dwp, int groups, size_t panel_s
 
 // ---- torch.optim.Adam (L2 weight decay folded into the gradient), train_segmentation.py:96 --------------
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                            int64_t n, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
-                            float grad_scale) {
+                            int64_t n, float lr, float b1, float omb1, float b2, float omb2, float eps, float wd, float bc1,
+                            float bc2_sqrt, float grad_scale) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const float pi = p[i];
     const float gi = g[i] * grad_scale + wd * pi;
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    const float mi = b1 * m[i] + omb1 * gi;
+    const float vi = b2 * v[i] + omb2 * gi * gi;
     m[i] = mi;
     v[i] = vi;
     p[i] = pi - (lr / bc1) * mi / (sqrtf(vi) / bc2_sqrt + eps);
   }
 }
-hipError_t launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps,
+// The betas arrive as doubles and everything that subtracts one from 1 is formed here in double and cast once, as torch.optim.Adam
+// does on the host: 1 - beta2 is 1e-3, and a beta2 rounded to fp32 (1.3e-8 above 0.999) puts 1 - beta2 and, for the first thousand
+// steps, 1 - beta2^step 1.3e-5 off; 1.f - powf(b2, step) in fp32 added the rounding of powf, 6e-8 against a difference of step * 1e-3.
+hipError_t launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, double b1, double b2, float eps,
                        float wd, int step, float grad_scale, hipStream_t s) {
-  const float bc1 = 1.f - powf(b1, (float)step);
-  const float bc2 = 1.f - powf(b2, (float)step);
-  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n, 256, 256 * 8)), dim3(256), 0, s, p, g, m, v, n, lr, b1, b2, eps, wd, bc1, sqrtf(bc2),
-                     grad_scale);
+  const double bc1 = 1.0 - pow(b1, (double)step);
+  const double bc2 = 1.0 - pow(b2, (double)step);
+  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n, 256, 256 * 8)), dim3(256), 0, s, p, g, m, v, n, lr, (float)b1, (float)(1.0 - b1),
+                     (float)b2, (float)(1.0 - b2), eps, wd, (float)bc1, (float)sqrt(bc2), grad_scale);
   return hipGetLastError();
 }
 
