@@ -28,7 +28,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .metrics import _evaluate
+from ._args import batched_map
+from .metrics import _Evaluator, _evaluate
 from .objects import _source
 
 _NAN = float("nan")   # the one nan object of every dictionary: lists and dictionaries compare by identity first, so equal tables give == results
@@ -116,9 +117,7 @@ def boundary_tables(pred: torch.Tensor, target: torch.Tensor, num_classes: int =
     if not 2 <= ncls <= 32:
         raise ValueError(f"boundary_tables: num_classes must be in 2..32, got {ncls}")
     _lib.require_hip(target, "boundary_tables")
-    if target.is_floating_point() or target.dtype == torch.bool or target.dim() not in (2, 3):
-        raise TypeError("the target must be an integer (H, W) or (B, H, W) tensor")
-    tgt = target.reshape((1,) + tuple(target.shape)) if target.dim() == 2 else target
+    tgt = batched_map(target, "the target")
     if tuple(tgt.shape) != (B, H, W):
         raise ValueError(f"target shape {tuple(target.shape)} does not match the prediction's {(B, H, W)}")
     if tgt.device != src.device:
@@ -197,27 +196,24 @@ def boundary_metrics(tables: BoundaryTables, tolerance: float = 2.0, quantile: f
     return out
 
 
-class BoundaryEvaluator:
+class BoundaryEvaluator(_Evaluator):
     """Device-side boundary evaluation over a test set.  update(logits, masks) runs boundary_tables on the batch (argmax fused; mask
     values in [1, num_classes) are foreground, 0, -100 and anything out of range background) and keeps its tables on the device; it
     never blocks the host.  compute() concatenates them, synchronises once and returns boundary_metrics' dictionary -- equal to
     boundary_metrics of the tables of the concatenated batches.  With band_radius None every batch takes 2 % of its own diagonal.
     One process: reducing the tables across ranks is out of scope (they are per image; gather them, do not add them)."""
 
+    CLASS_RANGE = (2, 32)
+
     def __init__(self, num_classes: int, device, tolerance: float = 2.0, max_distance: float = 64, band_radius: float = None,
                  quantile: float = 0.95):
-        self.num_classes, self.device = int(num_classes), torch.device(device)
-        if not 2 <= self.num_classes <= 32:
-            raise ValueError(f"num_classes must be in 2..32, got {num_classes}")
+        super().__init__(num_classes, device)
         self.max_d2 = _max_d2(max_distance)
         _tol2(tolerance, self.max_d2)
         _rank_fraction(quantile)
         if band_radius is not None:
             _band_r2(band_radius, 1, 1)
         self.tolerance, self.band_radius, self.quantile = tolerance, band_radius, quantile
-        _lib.require_hip(self.device, type(self).__name__)
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
         self.reset()
 
     def reset(self) -> None:
@@ -225,17 +221,9 @@ class BoundaryEvaluator:
 
     def update(self, logits_nchw: torch.Tensor, masks: torch.Tensor) -> None:
         """Add one batch: logits (B, C, H, W) float32 -- the view UNet.forward returns -- and integer masks (B, H, W)."""
-        if not logits_nchw.is_cuda or logits_nchw.device != self.device:
-            raise RuntimeError(f"logits must live on {self.device}")
-        src, kind, B, H, W, C = _source(logits_nchw)
-        if kind != 1:
-            raise TypeError("expected (B, C, H, W) float32 logits")
-        if C != self.num_classes:
-            raise ValueError(f"logits have {C} classes, the evaluator {self.num_classes}")
-        if tuple(masks.shape) != (B, H, W):
-            raise ValueError(f"masks shape {tuple(masks.shape)} does not match logits {(B, H, W)}")
+        src, masks, B, H, W, C = self._batch(logits_nchw, masks)
         band_r2 = _band_r2(self.band_radius, H, W)
-        self._tables.append(_tables(src, 1, masks.to(self.device, torch.int64).contiguous(), B, H, W, C, C, self.max_d2, band_r2))
+        self._tables.append(_tables(src, 1, masks, B, H, W, C, C, self.max_d2, band_r2))
         self._band_r2.add(band_r2)
 
     def tables(self) -> BoundaryTables:

@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._args import nhwc_storage
 
 
 class DetectionHead(nn.Module):
@@ -119,7 +120,7 @@ class DetectionHead(nn.Module):
             B, C, H, W = f_fused.shape
             if C % 16:
                 raise ValueError("in_features_channels must be a multiple of 16 (C/4 is a 16-byte NHWC pixel)")
-            x = f_fused.detach().permute(0, 2, 3, 1).contiguous()        # a no-op for mgunet's NHWC-stored feature maps
+            x = nhwc_storage(f_fused.detach())
             x = self._conv_prepared(x, prep["conv1"], True)                                                         # :33-34
             a1, c1 = prep["bn1"]
             x = self._affine(x.reshape(-1, C // 2), a1, c1, 0).reshape(B, H, W, C // 2)                           # :35

@@ -9,6 +9,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._args import check_masks, nhwc_storage
 from .gat import GATNetwork, _csr_cache, _layer_forward, _LayerCall
 from .patch_graph import PatchGraphConstructor
 from .unet import UNet
@@ -134,7 +135,7 @@ def argmax_classes(logits_nchw: torch.Tensor) -> torch.Tensor:
     """torch.argmax(seg_logits, dim=1) of segmentation_performance.py:141 on the GPU (NHWC logits)."""
     _lib.require_hip(logits_nchw, "argmax_classes")
     B, Cc, H, W = logits_nchw.shape
-    nhwc = logits_nchw.permute(0, 2, 3, 1).contiguous()
+    nhwc = nhwc_storage(logits_nchw)
     pred = torch.empty((B, H, W), device=logits_nchw.device, dtype=torch.int64)
     _lib.call("mgu_argmax_classes", logits_nchw.device, nhwc, B * H * W, Cc, pred)
     return pred
@@ -388,11 +389,9 @@ class Trainer:
         model.train()
         logits, _, _ = model(images)
         B, Cc, H, W = logits.shape
-        if tuple(masks.shape) != (B, H, W):
-            raise ValueError(f"masks shape {tuple(masks.shape)} does not match logits {(B, H, W)}")
+        check_masks(masks, B, H, W)
         ctx = model._context(dev)
-        nhwc = logits.permute(0, 2, 3, 1)
-        assert nhwc.is_contiguous()
+        nhwc = nhwc_storage(logits)   # the forward's own storage: no copy
         masks = masks.contiguous()
         npix = B * H * W
         ldd = (Cc + 3) // 4 * 4

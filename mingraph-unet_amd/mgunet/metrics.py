@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._args import logits_and_masks, resolve_device
 
 _LOSS_KINDS = {None: 0, "ce": 1, "ce+dice": 2}
 
@@ -119,7 +120,36 @@ def allreduce_eval_state(confusion: torch.Tensor, loss_acc: torch.Tensor = None,
     return cm, acc
 
 
-class SegmentationEvaluator:
+class _Evaluator:
+    """What the evaluators share -- SegmentationEvaluator, BoundaryEvaluator and, through objects._ObjectEvaluator, YieldEvaluator
+    and InstanceEvaluator: the class count and device of the constructor, the checks of update()'s batch, and the contract _evaluate
+    relies on: reset() forgets every batch, update(logits, masks) adds one without blocking the host, compute() synchronises and
+    returns the dictionary."""
+
+    CLASS_RANGE = (1, None)   # num_classes a subclass takes: (least, most or None)
+
+    def __init__(self, num_classes, device):
+        self.num_classes = int(num_classes)
+        lo, hi = self.CLASS_RANGE
+        if self.num_classes < lo or (hi is not None and self.num_classes > hi):
+            raise ValueError(f"num_classes must be >= {lo}" if hi is None else f"num_classes must be in {lo}..{hi}, got {num_classes}")
+        self.device = resolve_device(device, type(self).__name__)
+
+    def _batch(self, logits_nchw, masks):
+        """(NHWC logits, int64 masks on the device, B, H, W, C) of update()'s arguments, checked."""
+        return logits_and_masks(logits_nchw, masks, self.device, self.num_classes)
+
+    def reset(self) -> None:
+        raise NotImplementedError
+
+    def update(self, logits_nchw: torch.Tensor, masks: torch.Tensor):
+        raise NotImplementedError
+
+    def compute(self) -> dict:
+        raise NotImplementedError
+
+
+class SegmentationEvaluator(_Evaluator):
     """Device-side accumulation of the reference's evaluation (segmentation_performance.py:125-151) and of a validation loss
     (the block train_segmentation.py:145-151 leaves commented out).  update() never blocks the host; compute() synchronises
     once and returns segmentation_metrics' dictionary (+ 'loss': the mean per-batch loss when a loss was requested)."""
@@ -127,12 +157,7 @@ class SegmentationEvaluator:
     def __init__(self, num_classes: int, device, loss=None, dice_smooth: float = 1.0, smooth: float = 1e-6):
         if loss not in _LOSS_KINDS:
             raise ValueError(f"unknown loss {loss!r}: None, 'ce' or 'ce+dice'")
-        self.num_classes, self.device = int(num_classes), torch.device(device)
-        if self.num_classes < 1:
-            raise ValueError("num_classes must be >= 1")
-        _lib.require_hip(self.device, "SegmentationEvaluator")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        super().__init__(num_classes, device)
         self.loss, self.loss_kind = loss, _LOSS_KINDS[loss]
         self.dice_smooth, self.smooth = float(dice_smooth), smooth
         self.confusion = torch.zeros((self.num_classes, self.num_classes), device=self.device, dtype=torch.int64)
@@ -146,19 +171,7 @@ class SegmentationEvaluator:
     def update(self, logits_nchw: torch.Tensor, masks: torch.Tensor, return_pred: bool = False):
         """Add one batch: logits (B, C, H, W) -- the view UNet.forward returns, its NHWC storage read in place -- and int64 masks
         (B, H, W).  Returns the (B, H, W) int64 predictions if return_pred (= torch.argmax(logits, 1)), else None."""
-        if not logits_nchw.is_cuda or logits_nchw.device != self.device:
-            raise RuntimeError(f"logits must live on {self.device}")
-        if logits_nchw.dtype != torch.float32 or logits_nchw.dim() != 4:
-            raise TypeError("expected (B, C, H, W) float32 logits")
-        B, Cc, H, W = logits_nchw.shape
-        if Cc != self.num_classes:
-            raise ValueError(f"logits have {Cc} classes, the evaluator {self.num_classes}")
-        if tuple(masks.shape) != (B, H, W):
-            raise ValueError(f"masks shape {tuple(masks.shape)} does not match logits {(B, H, W)}")
-        masks = masks.to(self.device, torch.int64).contiguous()
-        nhwc = logits_nchw.permute(0, 2, 3, 1)
-        if not nhwc.is_contiguous():
-            nhwc = nhwc.contiguous()
+        nhwc, masks, B, H, W, Cc = self._batch(logits_nchw, masks)
         pred = torch.empty((B, H, W), device=self.device, dtype=torch.int64) if return_pred else None
         _lib.call("mgu_segmentation_eval", self.device, nhwc, masks, B, H * W, Cc, self.confusion, pred, self.loss_kind, self.dice_smooth,
                   self.loss_acc)

@@ -17,7 +17,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .metrics import _evaluate
+from ._args import batched_map, nhwc_storage
+from .metrics import _Evaluator, _evaluate
 
 
 @dataclass
@@ -75,13 +76,8 @@ def _source(x: torch.Tensor):
         if x.dim() != 4 or x.dtype != torch.float32:
             raise TypeError("logits must be (B, C, H, W) float32")
         B, C, H, W = x.shape
-        nhwc = x.permute(0, 2, 3, 1)
-        if not nhwc.is_contiguous():
-            nhwc = nhwc.contiguous()
-        return nhwc, 1, B, H, W, C
-    if x.dtype == torch.bool or x.dim() not in (2, 3):
-        raise TypeError("a class map must be an integer (H, W) or (B, H, W) tensor")
-    m = x.reshape((1,) + tuple(x.shape)) if x.dim() == 2 else x
+        return nhwc_storage(x), 1, B, H, W, C
+    m = batched_map(x, "a class map")
     B, H, W = m.shape
     return m.to(torch.int64).contiguous(), 0, B, H, W, 0
 
@@ -192,10 +188,7 @@ def distance_transform(labels) -> torch.Tensor:
     map must fit it (connected_components' labels do), or distinct labels may wrap onto each other or onto 0."""
     lab = labels.labels if isinstance(labels, ObjectTable) else labels
     _lib.require_hip(lab, "distance_transform")
-    if lab.is_floating_point() or lab.dtype == torch.bool or lab.dim() not in (2, 3):
-        raise TypeError("a label map must be an integer (H, W) or (B, H, W) tensor")
-    lab = lab.reshape((1,) + tuple(lab.shape)) if lab.dim() == 2 else lab
-    lab = lab.to(torch.int32).contiguous()
+    lab = batched_map(lab, "a label map").to(torch.int32).contiguous()
     B, H, W = lab.shape
     d2 = torch.empty((B, H, W), device=lab.device, dtype=torch.int32)
     _lib.call("mgu_distance_transform", lab.device, lab, B, H, W, d2)
@@ -389,9 +382,9 @@ def yield_estimation_metrics(gt_counts, pred_counts, gt_objects_list=None, pred_
     return _yield_dict(gt_counts, pred_counts, match, smooth)
 
 
-class _ObjectEvaluator:
-    """What YieldEvaluator and InstanceEvaluator (instances.py) share: the constructor's checks, update()'s checks of a batch, and the
-    objects of its two sides."""
+class _ObjectEvaluator(_Evaluator):
+    """What YieldEvaluator and InstanceEvaluator (instances.py) add to the evaluator base: the checks of the object parameters and the
+    objects of a batch's two sides."""
 
     def __init__(self, num_classes, device, connectivity, min_area, split, clean=None):
         _check_args(connectivity, min_area)
@@ -409,27 +402,9 @@ class _ObjectEvaluator:
             if extra:
                 raise ValueError(f"split takes min_distance, min_radius and min_area, not {sorted(extra)}")
             self._split = _split_params(split.get("min_distance", 5), split.get("min_radius", 3), split.get("min_area", 0))
-        self.num_classes, self.device = int(num_classes), torch.device(device)
-        if self.num_classes < 1:
-            raise ValueError("num_classes must be >= 1")
-        _lib.require_hip(self.device, type(self).__name__)
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        super().__init__(num_classes, device)
         self.connectivity, self.min_area = connectivity, int(min_area)
         self._bufs, self._cap = None, -1
-
-    def _batch(self, logits_nchw, masks):
-        """(NHWC logits, int64 masks on the device, B, H, W, C) of update()'s arguments, checked."""
-        if not logits_nchw.is_cuda or logits_nchw.device != self.device:
-            raise RuntimeError(f"logits must live on {self.device}")
-        src, kind, B, H, W, C = _source(logits_nchw)
-        if kind != 1:
-            raise TypeError("expected (B, C, H, W) float32 logits")
-        if C != self.num_classes:
-            raise ValueError(f"logits have {C} classes, the evaluator {self.num_classes}")
-        if tuple(masks.shape) != (B, H, W):
-            raise ValueError(f"masks shape {tuple(masks.shape)} does not match logits {(B, H, W)}")
-        return src, masks.to(self.device, torch.int64).contiguous(), B, H, W, C
 
     def _label_sides(self, src, masks, B, H, W, C, bufs):
         """Label, split (when asked) and take the statistics of the GT objects (mask values in [1, num_classes)) and of the predicted

@@ -13,6 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
+from ._args import nhwc_storage
 
 
 def _build(H: int, W: int, patch: int):
@@ -97,7 +98,7 @@ class PatchGraphConstructor:
         if feat_nchw.dtype not in (torch.float32, torch.bfloat16):
             raise TypeError(f"expected float32 or bfloat16 features, got {feat_nchw.dtype}")
         code = 1 if feat_nchw.dtype == torch.bfloat16 else 0
-        nhwc = feat_nchw.permute(0, 2, 3, 1).contiguous()  # no copy when storage is already NHWC
+        nhwc = nhwc_storage(feat_nchw)
         nph, npw = (H + self.patch_size - 1) // self.patch_size, (W + self.patch_size - 1) // self.patch_size
         out = torch.empty((B * nph * npw, Cc), device=feat_nchw.device, dtype=torch.float32)
         _lib.call("mgu_patch_mean", feat_nchw.device, nhwc, code, B, H, W, Cc, self.patch_size, out)

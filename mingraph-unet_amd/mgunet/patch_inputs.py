@@ -13,6 +13,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
+from ._args import nhwc_storage
 from .preprocess import _to_dev_u8, patch_smooth_features_u8
 
 MAX_CLASSES = 32   # mgu_patch_labels: lane c of a wave counts class c
@@ -105,7 +106,7 @@ def patch_labels(src: torch.Tensor, patch_size: int, num_classes: int = None, re
         B, C, H, W = src.shape
         if num_classes is not None and int(num_classes) != C:
             raise ValueError(f"num_classes {num_classes} but the logits have {C} channels")
-        data = src.float().permute(0, 2, 3, 1).contiguous()       # a no-op on the NHWC-storage view
+        data = nhwc_storage(src.float())
         kind = 1
     else:
         if src.dim() == 2:

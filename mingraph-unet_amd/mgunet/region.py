@@ -12,6 +12,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._args import nhwc_storage
 from .gat import GATNetwork
 
 
@@ -61,7 +62,7 @@ def region_fuse(f_u, region_emb: torch.Tensor, hard_labels: torch.Tensor, B: int
         if tuple(f_u.shape[0:1] + f_u.shape[2:]) != (B, H, W):
             raise ValueError(f"f_u must be (B, C, {H}, {W})")
         Cu = f_u.shape[1]
-        fu_nhwc = f_u.detach().permute(0, 2, 3, 1).contiguous()   # a no-op for mgunet's NHWC-stored feature maps
+        fu_nhwc = nhwc_storage(f_u.detach())
     h = hard_labels.to(device=dev, dtype=torch.int32).contiguous()
     emb = region_emb.detach().contiguous()
     out = torch.empty((B, H, W, Cu + D), device=dev, dtype=torch.float32)
@@ -109,7 +110,7 @@ class FeatureFusion(nn.Module):
         if (h, w) == (H, W):
             out_nhwc[..., c_off:c_off + Cs] = src_nchw.permute(0, 2, 3, 1)      # same size: a strided copy, no arithmetic
             return
-        src = src_nchw.detach().float().permute(0, 2, 3, 1).contiguous()        # a no-op for mgunet's NHWC-stored feature maps
+        src = nhwc_storage(src_nchw.detach().float())
         _lib.call("mgu_resize_bilinear_nhwc", src.device, src, Cs, B, h, w, Cs, out_nhwc, out_nhwc.shape[3], c_off, H, W)
 
     def forward(self, f_u_list, f_g, target_spatial_size=None, region_to_pixel_map=None):

@@ -13,6 +13,7 @@ import ctypes as C
 import torch
 
 from . import _lib
+from ._args import nhwc_storage
 from .objects import ObjectTable
 from .unet import UNet
 
@@ -130,8 +131,5 @@ def object_scores(table: ObjectTable, probs: torch.Tensor) -> torch.Tensor:
     scores = torch.empty(N, device=dev, dtype=torch.float32)
     if N == 0:
         return scores
-    nhwc = probs.permute(0, 2, 3, 1)
-    if not nhwc.is_contiguous():
-        nhwc = nhwc.contiguous()
-    _lib.call("mgu_object_scores", dev, table.labels, nhwc, B, H, W, Cls, table.offsets, N, table.class_id, table.area, scores)
+    _lib.call("mgu_object_scores", dev, table.labels, nhwc_storage(probs), B, H, W, Cls, table.offsets, N, table.class_id, table.area, scores)
     return scores

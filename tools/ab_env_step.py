@@ -6,14 +6,13 @@ to the first setting's.
 --graph: the headline step as bench.py runs it (U-Net + patch means + the patch GAT through mgunet.MinGraphUNet), which is what
 the switches of the head / patch-mean path act on, e.g.  python tools/ab_env_step.py --graph 4 MGU_HEAD_FUSED=0 MGU_HEAD_FUSED=1
 """
-import json
 import os
 import sys
 
+from benchkit import emit, timed  # first: benchkit sets the import path
 import torch
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "mingraph-unet_amd"))
-import mgunet  # noqa: E402
+import mgunet
 
 graph = len(sys.argv) > 1 and sys.argv[1] == "--graph"
 if graph:
@@ -37,18 +36,11 @@ for r in range(rounds):
         unet = mgunet.UNet(3, 2, 32, 4).to(dev).eval()
         if graph:
             unet = mgunet.MinGraphUNet(unet, mgunet.GATNetwork(32, 128, 64, 4, 1).to(dev).eval(), 16).eval()
-        for _ in range(3):
-            lg, sk, ft = unet(x)[:3]
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(20):
-            lg, sk, ft = unet(x)[:3]
-        e1.record()
-        torch.cuda.synchronize()
+        ms = timed(lambda: unet(x), 20, 3, park=False)   # the step as a caller paces it, as bench.py runs it
+        lg, sk, ft = unet(x)[:3]
         outs = [lg.clone()] + [t.clone() for t in ft]
         if first is None:
             first = outs
         same = all(torch.equal(a, b) for a, b in zip(first, outs))
-        print(json.dumps({"round": r, "env": s, "ms_per_step": round(e0.elapsed_time(e1) / 20, 4), "bitwise_equal_to_first": same}), flush=True)
+        emit(round=r, env=s, ms_per_step=round(ms, 4), bitwise_equal_to_first=same)
         del unet

@@ -7,41 +7,16 @@ Times are HIP events.  The batch call includes its host work (draws, coefficient
 the kernel alone by replaying one launch through the C ABI.  Prints one JSON line per measurement.  Run under
 `rocprofv3 --kernel-trace --stats -- python tools/augment_bench.py` for the per-kernel times (profiles/augment_kernel_stats.csv)."""
 import ctypes as C
-import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "mingraph-unet_amd"))
+from benchkit import emit, timed  # first: benchkit sets the import path
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import mgunet
+from mgunet import _lib
+from mgunet.gat import _context
 
-import mgunet  # noqa: E402
-from mgunet import _lib  # noqa: E402
-from mgunet.gat import _context  # noqa: E402
-
-
-def timed(fn, iters, warmup=5, queue_ahead=False):
-    """ms per call between HIP events.  queue_ahead: park the stream behind a spin kernel first, so that every call is
-    enqueued before the first one runs and the events time the GPU, not the host's launch rate."""
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    if queue_ahead:
-        torch.cuda._sleep(50_000_000)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / iters   # ms
-
-
-def emit(**kw):
-    print(json.dumps(kw), flush=True)
-
+WARMUP = 5
 
 def main():
     dev = torch.device("cuda:0")
@@ -51,7 +26,7 @@ def main():
     y = torch.randint(0, 2, (B, H, W), generator=g).to(dev)
     mbytes = (x.numel() * 4 + y.numel() * 8) * 2 / 1e6
     aug = mgunet.RandomFlipRotate(mask_fill=-100)
-    call = timed(lambda: aug(x, y, generator=g), 50)
+    call = timed(lambda: aug(x, y, generator=g), 50, WARMUP, park=False)
     # the kernel alone: one fixed table, launched through the ABI with preallocated outputs
     params = aug.draw(B, W, H, g).to(dev)
     ox, oy = torch.empty_like(x), torch.empty_like(y)
@@ -64,8 +39,8 @@ def main():
         _lib.check(L.mgu_augment_flip_rotate(ctx.handle, x.data_ptr(), ox.data_ptr(), B, Cc, H, W, si, so, fill, y.data_ptr(), oy.data_ptr(),
                                              -100, params.data_ptr(), stream), ctx.handle)
 
-    kern = timed(launch, 200, queue_ahead=True)
-    clone = timed(lambda: (x.clone(), y.clone()), 200, queue_ahead=True)
+    kern = timed(launch, 200, WARMUP)
+    clone = timed(lambda: (x.clone(), y.clone()), 200, WARMUP)
     emit(what="augment_batch", shape=[B, Cc, H, W], masks="int64", call_us=round(call * 1e3, 2), kernel_us=round(kern * 1e3, 2),
          clone_us=round(clone * 1e3, 2), kernel_over_clone=round(kern / clone, 3), moved_MB=round(mbytes, 1),
          kernel_TBps=round(mbytes / 1e6 / (kern * 1e-3), 2), clone_TBps=round(mbytes / 1e6 / (clone * 1e-3), 2))
@@ -74,8 +49,8 @@ def main():
     plain = mgunet.ImagePreprocessor(resize_dim=(H, W))
     augp = mgunet.ImagePreprocessor(resize_dim=(H, W), apply_augmentation=True)
     out = torch.empty((3, H, W), device=dev)
-    t0 = timed(lambda: plain.preprocess(img, out=out), 50)
-    t1 = timed(lambda: augp.preprocess(img, out=out), 50)
+    t0 = timed(lambda: plain.preprocess(img, out=out), 50, WARMUP, park=False)
+    t1 = timed(lambda: augp.preprocess(img, out=out), 50, WARMUP, park=False)
     emit(what="preprocess_1080p_to_512", plain_us=round(t0 * 1e3, 2), augmented_us=round(t1 * 1e3, 2), added_us=round((t1 - t0) * 1e3, 2))
 
 

@@ -1,6 +1,6 @@
 """Boundary evaluation at the flagship batch, one process, one GPU: B = 8 images of 512 x 512, C = 2 and C = 4 classes.
 
-  scene      the overlapping-ellipse scene of split_objects_bench.py (C = 4: a class per 64 x 64 cell) as the target against a copy
+  scene      the overlapping-ellipse scene of benchkit.ellipse_scene (C = 4: a class per 64 x 64 cell) as the target against a copy
              shifted by (2, 3) pixels as the prediction
   worst      the prediction is a checkerboard of 2 x 2 blocks -- every foreground pixel is a boundary pixel -- and the target one
              small object in the far corner: every query pixel walks until it has covered its distance to that corner
@@ -11,22 +11,14 @@ mgunet.distance_transform of the same 2B planes.  Also the host composition the 
 scipy oracle of the tables (tests/boundary_oracle.py), nothing copied back, wall clock, once; the device tables must equal it.  Prints
 one JSON line per measurement.  --quick: fewer iterations, no host run."""
 import argparse
-import os
-import statistics
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "mingraph-unet_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+from benchkit import ellipse_scene, emit, median_spread  # first: benchkit sets the import path
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-import mgunet  # noqa: E402
-from mgunet import boundary  # noqa: E402
-from split_objects_bench import ellipse_scene, emit, timed  # noqa: E402
+import mgunet
+from mgunet import boundary
 
 
 def shifted_scene(B, H, W, C, seed):
@@ -49,12 +41,6 @@ def worst_scene(B, H, W, C):
     for c in range(1, C):
         g[:, H - 8 * c:H - 8 * c + 6, W - 8:W - 2] = c
     return p, g
-
-
-def median_spread(fn, iters, runs):
-    """(median, min, max) in microseconds of `runs` timed loops of `iters` calls"""
-    us = [timed(fn, iters) * 1e3 for _ in range(runs)]
-    return round(statistics.median(us), 1), round(min(us), 1), round(max(us), 1)
 
 
 def host_tables(p_dev, g_dev, C, max_d2, band_r2):

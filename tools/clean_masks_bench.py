@@ -1,6 +1,6 @@
 """Mask cleanup at the flagship batch, one process, one GPU: B = 8 images of 512 x 512, logits of C = 2 and C = 4 classes.
 
-  scene      the overlapping-ellipse scene of split_objects_bench.py (C = 4: a class per cluster) with pin holes inside the fruits and
+  scene      the overlapping-ellipse scene of benchkit.ellipse_scene (C = 4: a class per cluster) with pin holes inside the fruits and
              one-pixel spurs sticking out of them
   worst      a checkerboard of single-pixel holes: every other pixel is a background component of its own (H*W/2 roots for the fill),
              and every plane word is half set
@@ -12,20 +12,17 @@ host composition the call replaces: the argmax map copied to the host, scipy's b
 labelled by scipy for the holes (tests/clean_oracle.py) and the copy back, wall clock, once; the device result must equal it.
 Prints one JSON line per measurement.  --quick: fewer iterations, no host run."""
 import argparse
-import os
-import sys
+import functools
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "mingraph-unet_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import benchkit
+import numpy as np
+import torch
+from benchkit import ellipse_scene, emit, logits_of
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+from mgunet import objects
 
-import mgunet  # noqa: E402
-from mgunet import objects  # noqa: E402
-from split_objects_bench import ellipse_scene, emit, timed  # noqa: E402
+timed = functools.partial(benchkit.timed, warmup=3)
 
 
 def defect_scene(B, H, W, C, seed):
@@ -50,13 +47,6 @@ def checker_scene(B, H, W, C):
     yy, xx = np.mgrid[0:H, 0:W]
     m[:] = np.where((yy + xx) % 2 == 0, 1 + (xx // 128) % (C - 1), 0)
     return m
-
-
-def logits_of(cmap, C, dev):
-    """(B, C, H, W) view of NHWC fp32 logits whose first maximal class is cmap"""
-    x = torch.zeros(tuple(cmap.shape) + (C,), dtype=torch.float32)
-    x.scatter_(-1, torch.from_numpy(cmap).unsqueeze(-1), 1.0)
-    return x.to(dev).permute(0, 3, 1, 2)
 
 
 def host_clean(logits, C, params):

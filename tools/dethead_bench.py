@@ -2,9 +2,8 @@
 """DetectionHead micro-benchmark: fused features (B, 96, 512, 512) -> boxes + confidence.
 Prints wall time per call, the algorithmic FLOPs of its two 3x3 convolutions and the oracle's CPU time on one image.
 Run under rocprofv3 for per-kernel durations."""
-import argparse, os, sys, time
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "mingraph-unet_amd")); sys.path.insert(0, os.path.join(ROOT, "oracle"))
+import argparse, os, time
+from benchkit import wall  # first: benchkit sets the import path
 import torch
 import mgunet, mgunet_oracle as O
 
@@ -21,14 +20,7 @@ sd["conv_block.2.num_batches_tracked"] = sd["conv_block.5.num_batches_tracked"] 
 m.load_state_dict(sd)
 m = m.to(dev).eval()
 x = torch.randn((B, H, W, C), device=dev).permute(0, 3, 1, 2)
-for _ in range(3):
-    m(x)
-torch.cuda.synchronize()
-t0 = time.perf_counter()
-for _ in range(a.iters):
-    m(x)
-torch.cuda.synchronize()
-dt = (time.perf_counter() - t0) / a.iters
+dt = wall(lambda: m(x), a.iters, 3) / 1e3          # seconds
 flops = 2.0 * B * H * W * 9 * (96 * 48 + 48 * 24)
 torch.set_num_threads(min(16, os.cpu_count() or 1))
 xc = x[:1].cpu().contiguous()

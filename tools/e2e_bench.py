@@ -2,9 +2,8 @@
 """Stages 1-7 of the reference's end-to-end forward (mgunet.MinGraphUNetE2E: U-Net, patch GAT, segment predictor +
 normalized-cut loss, region stage, fusion, detection head) on B x 3 x 512 x 512: wall time per call and the share of the
 U-Net + patch-GAT part (the headline metric of bench.py)."""
-import argparse, os, sys, time
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "mingraph-unet_amd")); sys.path.insert(0, os.path.join(ROOT, "oracle"))
+import argparse
+from benchkit import wall  # first: benchkit sets the import path
 import torch
 import mgunet, mgunet_oracle as O
 
@@ -25,21 +24,8 @@ sd["conv_block.2.num_batches_tracked"] = sd["conv_block.5.num_batches_tracked"] 
 det.load_state_dict(sd)
 model = mgunet.MinGraphUNetE2E(unet, pgat, pred, mgunet.MinCutRefinement(), rgat, det, num_segments=K).to(dev).eval()
 x = torch.randn((B, 3, H, W), device=dev)
-
-
-def timed(fn):
-    for _ in range(5):
-        fn()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(a.iters):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / a.iters
-
-
-t_all = timed(lambda: model(x))
-t_core = timed(lambda: model.core(x))
+t_all = wall(lambda: model(x), a.iters, 5) / 1e3          # seconds
+t_core = wall(lambda: model.core(x), a.iters, 5) / 1e3
 out = model(x)
 print(f"batch={B} e2e_ms={t_all*1e3:.3f} unet_plus_patch_gat_ms={t_core*1e3:.3f} later_stages_ms={(t_all-t_core)*1e3:.3f} "
       f"e2e_Mpix_per_s={B*H*W/t_all/1e6:.0f} loss_partition={float(out['loss_partition']):.5f} finite={bool(torch.isfinite(out['bboxes']).all())}")

@@ -2,9 +2,8 @@
 """GAT message-passing micro-benchmark: block-diagonal batch of B patch graphs (512x512 / patch 16 ->
 1024 nodes, 3968 edges each) or the C4 stress graph (2048 nodes, in-degree 8), GAT(Fin -> 64, 4 heads).
 Run under rocprofv3 (tools/gpu_gat.sh) to get per-kernel durations and HBM bytes."""
-import argparse, os, sys, time
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "mingraph-unet_amd")); sys.path.insert(0, os.path.join(ROOT, "oracle"))
+import argparse
+from benchkit import wall  # first: benchkit sets the import path
 import numpy as np, torch
 import mgunet, mgunet_oracle as O
 
@@ -30,14 +29,8 @@ gat = mgunet.GATNetwork(fin, 128, 64, 4, 1)
 gat.load_state_dict(O.make_gat_params(fin, 128, 64, 4, 1, seed=0))
 gat = gat.to(dev).eval()
 X = torch.randn(N * a.graphs, fin, device=dev)
-for _ in range(3):
-    y = mgunet.gat_forward_csr(gat, X, rowptr, col, gp)
-torch.cuda.synchronize()
-t0 = time.perf_counter()
-for _ in range(a.iters):
-    y = mgunet.gat_forward_csr(gat, X, rowptr, col, gp)
-torch.cuda.synchronize()
-dt = (time.perf_counter() - t0) / a.iters
+dt = wall(lambda: mgunet.gat_forward_csr(gat, X, rowptr, col, gp), a.iters, 3) / 1e3          # seconds
+y = mgunet.gat_forward_csr(gat, X, rowptr, col, gp)
 nodes, edges, HF, Fo = N * a.graphs, E * a.graphs, 256, 64
 comp = nodes * HF * 4 + (nodes + 1 + edges) * 4 + 2 * nodes * 4 * 4 + nodes * Fo * 4
 logical = edges * (4 + HF * 4 + 4)

@@ -3,16 +3,13 @@
 number of 32-node tiles -- is the fused kernel's time a function of the tiles per resident workgroup (rounds) or of the bytes?
     python tools/gat_tiles_sweep.py [graphs ...]"""
 import ctypes as C
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "mingraph-unet_amd"))
-sys.path.insert(0, os.path.join(ROOT, "oracle"))
-import torch  # noqa: E402
-import mgunet  # noqa: E402
-import mgunet_oracle as O  # noqa: E402
-from mgunet import _lib  # noqa: E402
+from benchkit import timed  # first: benchkit sets the import path
+import torch
+import mgunet
+import mgunet_oracle as O
+from mgunet import _lib
 
 dev = torch.device("cuda:0")
 L = _lib.lib()
@@ -34,17 +31,8 @@ for G in [int(v) for v in sys.argv[1:]] or [8, 16, 24, 32, 48, 64, 96, 128, 192,
     def run():
         _lib.check(L.mgu_gat_layer_forward_prepared(ctx.handle, hnd, X.data_ptr(), N, rowptr.data_ptr(), col.data_ptr(), E, gp.data_ptr(), G, 0, 0.2,
                                                     y.data_ptr(), s), ctx.handle)
-    for _ in range(5):
-        run()
-    torch.cuda.synchronize(dev)
     reps = 30
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        run()
-    e1.record()
-    torch.cuda.synchronize(dev)
-    layer = e0.elapsed_time(e1) * 1e3 / reps
+    layer = timed(run, reps, 5, park=False) * 1e3
     L.mgu_profile_enable(ctx.handle, 1)
     for _ in range(reps):
         run()

@@ -14,22 +14,19 @@ Device times are HIP events around calls queued behind a parked stream (they tim
 minimum over `--rounds` interleaved rounds.  The blur's bytes (read once + written once) over its time is printed as achieved GB/s.
 The device results must equal the host's.  Prints one JSON line per measurement.  --quick: fewer rounds, one host run."""
 import argparse
-import os
+import functools
 import statistics
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "mingraph-unet_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import benchkit
+import numpy as np
+import torch
+from benchkit import emit
+from scipy import ndimage
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-from scipy import ndimage  # noqa: E402
+import mgunet
 
-import mgunet  # noqa: E402
-from split_objects_bench import emit, timed  # noqa: E402
+timed = functools.partial(benchkit.timed, warmup=3)
 
 
 def host_blur(batch, kx, ky):

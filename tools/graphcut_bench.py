@@ -8,32 +8,16 @@ workload: the capacities launch, then the solve for every relabel period R x wor
 are HIP events around calls that were all queued behind a parked stream, so they time the GPU and not the host's launch rate; the
 solve is one launch, so its time is the kernel's.  Prints one JSON line per measurement.  --quick: fewer iterations and settings."""
 import argparse
-import json
-import os
-import sys
+import functools
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "mingraph-unet_amd"))
+import benchkit
+import numpy as np
+import torch
+from benchkit import emit
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import mgunet
 
-import mgunet  # noqa: E402
-
-
-def timed(fn, iters, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda._sleep(20_000_000)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / iters   # ms
-
+timed = functools.partial(benchkit.timed, warmup=3)
 
 def grid_edges(H, W):
     idx = np.arange(H * W).reshape(H, W)
@@ -56,10 +40,6 @@ def blobby(B, H, W, D, seed):
         inten.append(np.clip(60 + 120 * p + 12 * rng.randn(H, W), 0, 255).ravel())
     feats = rng.randn(B * H * W, D) * (0.7 / np.sqrt(D))
     return [np.concatenate(a).astype(np.float32) for a in (pri, inten)] + [feats.astype(np.float32)]
-
-
-def emit(**kw):
-    print(json.dumps(kw), flush=True)
 
 
 def main():

@@ -10,44 +10,16 @@ host read of the accept decision (the batch advances in lock step until every gr
 and energies are checked to equal the kernel's).  The kernel's times are HIP events around calls queued behind a parked stream; the
 composition synchronises every move, so it is timed by the wall clock around whole runs.  Prints one JSON line per measurement."""
 import argparse
-import json
-import os
-import sys
-import time
+import functools
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "mingraph-unet_amd"))
+import benchkit
+import numpy as np
+import torch
+from benchkit import emit, wall
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import mgunet
 
-import mgunet  # noqa: E402
-
-
-def timed(fn, iters, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda._sleep(20_000_000)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / iters   # ms
-
-
-def wall(fn, iters, warmup=1):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(iters):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3 / iters   # ms
-
+timed = functools.partial(benchkit.timed, warmup=3)
 
 def grid_edges(H, W):
     idx = np.arange(H * W).reshape(H, W)
@@ -120,10 +92,6 @@ def composed(ei, U, ce, B, max_cycles=32):
     return L.reshape(B, N).to(torch.uint8), en, moves
 
 
-def emit(**kw):
-    print(json.dumps(kw), flush=True)
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
@@ -151,7 +119,7 @@ def main():
              rounds_max=int(r.max()), energy_start_over_end=round(float(start.sum()) / max(float(ref.energy.sum()), 1.0), 3))
         L, en, moves = composed(ei, U, ce, B)
         same = bool(torch.equal(L, ref.labels) and torch.equal(en, ref.energy))
-        t_comp = wall(lambda: composed(ei, U, ce, B), 2 if args.quick else 5)
+        t_comp = wall(lambda: composed(ei, U, ce, B), 2 if args.quick else 5, 1)
         emit(what="composed", workload=tag, moves=moves, us=round(t_comp * 1e3, 1), same_labels_and_energy=same,
              over_kernel=round(t_comp / t_cut, 1))
 

@@ -1,17 +1,13 @@
 #!/usr/bin/env python3
 """Host time to ENQUEUE one forward / one train step (no synchronisation inside the timed loop) against the GPU time of the step: the
 reason the library does not capture its launch sequences in hipGraphs -- the stream never runs dry."""
-import os
-import sys
 import time
 
+import benchkit  # noqa: F401  (first: it sets the import path)
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "mingraph-unet_amd"))
-sys.path.insert(0, os.path.join(ROOT, "oracle"))
-import mgunet  # noqa: E402
-import mgunet_oracle as O  # noqa: E402
+import mgunet
+import mgunet_oracle as O
 
 dev = torch.device("cuda:0")
 model = mgunet.UNet(3, 2, 32, 4)

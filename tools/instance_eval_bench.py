@@ -1,6 +1,6 @@
 """Instance evaluation at the flagship batch, one process, one GPU: B = 8 images of 512 x 512.
 
-  scene      the overlapping ellipses of tools/split_objects_bench.py, split into objects, as the prediction; the same class map
+  scene      the overlapping ellipses of benchkit.ellipse_scene, split into objects, as the prediction; the same class map
              shifted by (3, 2) pixels with 1 % of its pixels cleared, split alike, as the ground truth
   worst      one full-image object on both sides: every pixel adds to ONE pair, the most contended counter there can be
 
@@ -11,21 +11,18 @@ composition the path replaces: both label maps copied to the host, np.unique ove
 threshold and the panoptic count (tests/instances_oracle.py), wall clock, once; the device results must equal it bit for bit.
 Prints one JSON line per measurement.  --quick: fewer iterations, no host run."""
 import argparse
-import os
-import sys
+import functools
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "mingraph-unet_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import benchkit
+import numpy as np
+import torch
+from benchkit import ellipse_scene, emit
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import mgunet
+from mgunet import _lib, instances
 
-import mgunet  # noqa: E402
-from mgunet import _lib, instances  # noqa: E402
-from split_objects_bench import ellipse_scene, emit, timed  # noqa: E402
+timed = functools.partial(benchkit.timed, warmup=3)
 
 
 def host_composition(tg, tp, scores, thresholds, C):

@@ -4,9 +4,8 @@ block-diagonal batch of B patch graphs (512x512 / patch 16 -> 1024 nodes, 3968 e
 Prints the wall time per call of the whole stage and of the loss alone, the algorithmic bytes of the loss kernel
 (rows gathered: E x D x 4 B + node rows N x D x 4 B + assignments + CSR) and the oracle's CPU time on a bounded sample.
 Run under rocprofv3 for the per-kernel durations (tools/README.md)."""
-import argparse, os, sys, time
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "mingraph-unet_amd")); sys.path.insert(0, os.path.join(ROOT, "oracle"))
+import argparse, os, time
+from benchkit import wall  # first: benchkit sets the import path
 import torch
 import mgunet, mgunet_oracle as O
 
@@ -26,22 +25,9 @@ pred = mgunet.PatchSegmentPredictor(D, K, hidden_dim=32, use_gnn=True, num_heads
 pred.load_state_dict(p)
 pred = pred.to(dev).eval()
 mc = mgunet.MinCutRefinement()
-
-
-def timed(fn):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(a.iters):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / a.iters
-
-
-t_stage = timed(lambda: mc(X, ei, K, pred))
+t_stage = wall(lambda: mc(X, ei, K, pred), a.iters, 3) / 1e3          # seconds
 soft = mc(X, ei, K, pred)[1]
-t_loss = timed(lambda: mc.normalized_cut_loss(X, ei, soft, K))
+t_loss = wall(lambda: mc.normalized_cut_loss(X, ei, soft, K), a.iters, 3) / 1e3
 alg = E * D * 4 + N * D * 4 + (E + N) * K * 4 + (N + 1 + E) * 4
 # CPU oracle (reference algorithm) on a bounded sample
 g = min(a.cpu_graphs, a.graphs)

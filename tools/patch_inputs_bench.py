@@ -9,18 +9,17 @@
 HIP events around warm calls, `--rounds` interleaved rounds of `--reps` calls of each variant in ONE process; median and minimum over
 the rounds' per-call times.  Prints one JSON line per measurement; the two results of each pair are compared first."""
 import argparse
-import json
-import os
+import functools
 import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "mingraph-unet_amd"))
+import benchkit
+import numpy as np
+import torch
+from benchkit import emit
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import mgunet
 
-import mgunet  # noqa: E402
+per_call_ms = functools.partial(benchkit.timed, warmup=0, park=False)   # host-paced, as the composed variants are used
 
 
 def composed_features(u8, x, p):
@@ -40,16 +39,6 @@ def composed_labels(masks, p, C):
     oh = torch.nn.functional.one_hot(masks, C).permute(0, 3, 1, 2).float()
     cnt = torch.nn.functional.avg_pool2d(oh, p, divisor_override=1)                                       # per-patch class counts
     return cnt.flatten(2).argmax(1)
-
-
-def per_call_ms(fn, reps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / reps
 
 
 def main():
@@ -79,10 +68,9 @@ def main():
         for _ in range(args.rounds):
             t["fused"].append(per_call_ms(fused, args.reps))
             t["composed"].append(per_call_ms(comp, args.reps))
-        print(json.dumps({"what": "patch_inputs_" + name, "B": B, "H": S, "W": S, "patch": p, "equal": bool(same),
-                          "fused_ms_median": round(statistics.median(t["fused"]), 4), "fused_ms_min": round(min(t["fused"]), 4),
-                          "composed_ms_median": round(statistics.median(t["composed"]), 4), "composed_ms_min": round(min(t["composed"]), 4)}),
-              flush=True)
+        emit(what="patch_inputs_" + name, B=B, H=S, W=S, patch=p, equal=bool(same),
+             fused_ms_median=round(statistics.median(t["fused"]), 4), fused_ms_min=round(min(t["fused"]), 4),
+             composed_ms_median=round(statistics.median(t["composed"]), 4), composed_ms_min=round(min(t["composed"]), 4))
 
 
 if __name__ == "__main__":

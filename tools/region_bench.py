@@ -3,9 +3,8 @@
 64-feature patch embeddings, 32-channel U-Net feature.  Prints wall time per call of the whole stage and of the fuse
 kernel alone with its algorithmic bytes (read F_u + write the fused NHWC tensor) and the oracle's CPU time on one image.
 Run under rocprofv3 for per-kernel durations."""
-import argparse, os, sys, time
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "mingraph-unet_amd")); sys.path.insert(0, os.path.join(ROOT, "oracle"))
+import argparse, os, time
+from benchkit import wall  # first: benchkit sets the import path
 import torch
 import mgunet, mgunet_oracle as O
 
@@ -24,22 +23,11 @@ gat = gat.to(dev).eval()
 feats = torch.randn((B * nph * npw, D), device=dev) * 0.5
 hard = torch.randint(0, K, (B * nph * npw,), device=dev)
 fu = torch.randn((B, H, W, Cu), device=dev).permute(0, 3, 1, 2)
+WARMUP = 10   # the first calls pay for the caching allocator's 805 MB output block
 
-
-def timed(fn):
-    for _ in range(10):   # the first calls pay for the caching allocator's 805 MB output block
-        fn()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(a.iters):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / a.iters
-
-
-t_stage = timed(lambda: mgunet.region_stage(feats, hard, B, K, gat, nph, npw, H, W, f_u=fu))
+t_stage = wall(lambda: mgunet.region_stage(feats, hard, B, K, gat, nph, npw, H, W, f_u=fu), a.iters, WARMUP) / 1e3   # seconds
 emb = mgunet.region_stage(feats, hard, B, K, gat, nph, npw, H, W, f_u=fu)[0]
-t_fuse = timed(lambda: mgunet.region_fuse(fu, emb, hard, B, H, W, nph, npw, K))
+t_fuse = wall(lambda: mgunet.region_fuse(fu, emb, hard, B, H, W, nph, npw, K), a.iters, WARMUP) / 1e3
 alg = B * H * W * (Cu + (Cu + D)) * 4
 torch.set_num_threads(min(16, os.cpu_count() or 1))
 fc, hc, fuc = feats[: nph * npw].cpu(), hard[: nph * npw].cpu(), fu[:1].cpu().contiguous()

@@ -5,43 +5,15 @@
 
 Prints one JSON line per measurement.  Run under `rocprofv3 --kernel-trace --stats -- python tools/seg_eval_bench.py` for the
 per-kernel times (profiles/seg_eval_kernel_stats.csv)."""
-import json
-import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(ROOT, "mingraph-unet_amd"), os.path.join(ROOT, "oracle")):
-    sys.path.insert(0, p)
+from benchkit import emit, timed  # first: benchkit sets the import path
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-import mgunet  # noqa: E402
-import mgunet_oracle as O  # noqa: E402
-from mgunet.metrics import confusion_matrix_host  # noqa: E402
-
-
-def timed(fn, iters, warmup=5, queue_ahead=False):
-    """ms per call between HIP events.  queue_ahead: park the stream behind a spin kernel first, so that every call is
-    enqueued before the first one runs and the events time the GPU, not the host's launch rate."""
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    if queue_ahead:
-        torch.cuda._sleep(50_000_000)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / iters   # ms
-
-
-def emit(**kw):
-    print(json.dumps(kw), flush=True)
-
+import mgunet
+import mgunet_oracle as O
+from mgunet.metrics import confusion_matrix_host
 
 def main():
     dev = torch.device("cuda:0")
@@ -55,8 +27,8 @@ def main():
     y = torch.randint(0, C, (B, H, W), generator=g).to(dev)
     ev = mgunet.SegmentationEvaluator(C, dev)
     with torch.no_grad():
-        fwd = timed(lambda: model(x), 20)
-        fwd_upd = timed(lambda: ev.update(model(x)[0], y), 20)
+        fwd = timed(lambda: model(x), 20, 5, park=False)
+        fwd_upd = timed(lambda: ev.update(model(x)[0], y), 20, 5, park=False)
         logits = model(x)[0]
     emit(what="forward", B=B, H=H, W=W, C=C, ms=round(fwd, 4))
     emit(what="forward+update", ms=round(fwd_upd, 4), overhead_ms=round(fwd_upd - fwd, 4))
@@ -64,7 +36,7 @@ def main():
     for loss in (None, "ce", "ce+dice"):
         e = mgunet.SegmentationEvaluator(C, dev, loss=loss)
         for pred in (False, True):
-            ms = timed(lambda: e.update(logits, y, return_pred=pred), 200, warmup=20, queue_ahead=True)
+            ms = timed(lambda: e.update(logits, y, return_pred=pred), 200, 20)
             extra = B * H * W * 8 if pred else 0
             emit(what="eval_kernels", loss=loss, pred_map=pred, us=round(ms * 1e3, 2), bytes=nbytes + extra,
                  tb_per_s=round((nbytes + extra) / (ms * 1e-3) / 1e12, 3))

@@ -14,29 +14,17 @@ Prints one JSON line per measurement (HIP events, the stream parked behind a spi
 number of times, so under `rocprofv3 --kernel-trace --stats -- python tools/shape_bench.py --case X` the launch counts of
 moments_init_kernel, moments_kernel, shapes_kernel, residual_kernel and residual_finish_kernel are comparable between the cases (profiles/shapes_kernel_times.txt)."""
 import argparse
-import json
-import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "mingraph-unet_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+from benchkit import emit, timed  # first: benchkit sets the import path
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-import mgunet  # noqa: E402
-from make_shape_golden import ellipse, scene  # noqa: E402
-from yield_bench import timed  # noqa: E402
+import mgunet
+from make_shape_golden import ellipse, scene
 
 B, H, W = 8, 512, 512
 WARMUP = 5
-
-
-def emit(**kw):
-    print(json.dumps(kw), flush=True)
-
 
 def maps_of(case):
     m = np.zeros((B, H, W), np.int64)

@@ -10,51 +10,18 @@ after.  For the scene also the host composition the call replaces: the label map
 distance_transform_edt per object, the numpy oracle's split (tests/split_objects_oracle.py) on those distances and the copy back,
 wall clock, once; the device result must equal it.  Prints one JSON line per measurement.  --quick: fewer iterations, no host run."""
 import argparse
-import json
-import os
-import sys
+import functools
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "mingraph-unet_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import benchkit
+import numpy as np
+import torch
+from benchkit import ellipse_scene, emit
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import mgunet
+from mgunet import objects
 
-import mgunet  # noqa: E402
-from mgunet import objects  # noqa: E402
-
-
-def timed(fn, iters, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda._sleep(20_000_000)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / iters   # ms
-
-
-def ellipse_scene(B, H, W, seed):
-    """int64 class maps: clusters of overlapping ellipses of class 1."""
-    rng = np.random.RandomState(seed)
-    ys, xs = np.mgrid[0:H, 0:W]
-    out = np.zeros((B, H, W), np.int64)
-    for b in range(B):
-        for _ in range(14):
-            cy, cx = rng.uniform(40, H - 40), rng.uniform(40, W - 40)
-            for _ in range(rng.randint(2, 5)):
-                a, e, t = rng.uniform(18, 30), rng.uniform(0.7, 1.0), rng.uniform(0, np.pi)
-                oy, ox = cy + rng.uniform(-30, 30), cx + rng.uniform(-30, 30)
-                u = (xs - ox) * np.cos(t) + (ys - oy) * np.sin(t)
-                v = -(xs - ox) * np.sin(t) + (ys - oy) * np.cos(t)
-                out[b][(u / a) ** 2 + (v / (a * e)) ** 2 <= 1.0] = 1
-    return out
+timed = functools.partial(benchkit.timed, warmup=3)
 
 
 def pierced_scene(B, H, W, pitch=16):
@@ -80,10 +47,6 @@ def host_split(labels_dev, r, r2):
     out = torch.from_numpy(np.stack(res)).to(labels_dev.device)
     torch.cuda.synchronize()
     return out, time.perf_counter() - t0
-
-
-def emit(**kw):
-    print(json.dumps(kw), flush=True)
 
 
 def main():

@@ -15,17 +15,17 @@ import csv
 import glob
 import json
 import os
+import functools
 import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "mingraph-unet_amd"))
+import benchkit
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import mgunet
+from mgunet import tiled
 
-import mgunet  # noqa: E402
-from mgunet import tiled  # noqa: E402
+median_ms = functools.partial(benchkit.timed_each, warmup=2)
 
 CFG = (3, 2, 32, 4)
 MEAN, STD = tiled.DEFAULT_MEAN, tiled.DEFAULT_STD
@@ -60,21 +60,6 @@ def chunk_bytes(H, W, T, o, per, C=CFG[1]):
         out.append({"t0": t0, "n": n, "gather_bytes": n * T * T * 3 * (1 + 4),
                     "accumulate_bytes": logits * C * 4 + (load + int(touched.sum())) * C * 4 + done * 12})
     return out
-
-
-def median_ms(fn, reps, warmup=2):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    out = []
-    for _ in range(reps):
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        out.append(a.elapsed_time(b))
-    return statistics.median(out)
 
 
 def torch_composition(model, img_u8, T, o, per):

@@ -9,34 +9,15 @@ under `rocprofv3 --kernel-trace --stats -- python tools/tta_bench.py` for the vi
 (tta_views_kernel, tta_merge_kernel); `--bytes` prints the bytes each of them moves per case instead of timing anything."""
 import argparse
 import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "mingraph-unet_amd"))
+from benchkit import timed_each  # first: benchkit sets the import path
+import torch
 
-import torch  # noqa: E402
-
-import mgunet  # noqa: E402
-from mgunet import tta  # noqa: E402
+import mgunet
+from mgunet import tta
 
 CFG = (3, 2, 32, 4)
-
-
-def median_ms(fn, reps, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    out = []
-    for _ in range(reps):
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        out.append(a.elapsed_time(b))
-    return statistics.median(out)
+WARMUP = 3
 
 
 def kernel_bytes(B, H, W, name, Cin=CFG[0], C=CFG[1]):
@@ -68,9 +49,9 @@ def main():
         for B in batches:
             x = torch.randn((B, CFG[0], H, W), generator=torch.Generator().manual_seed(B)).to(dev)
             with torch.no_grad():
-                fwd = median_ms(lambda: model(x), args.reps)
+                fwd = timed_each(lambda: model(x), args.reps, WARMUP)
             for name in ("none", "hflip", "d4"):
-                t = median_ms(lambda: tta.predict_tta(model, x, name), args.reps)
+                t = timed_each(lambda: tta.predict_tta(model, x, name), args.reps, WARMUP)
                 print(json.dumps({"what": "tta", "dtype": str(dtype).split(".")[-1], "B": B, "H": H, "W": W, "transforms": name,
                                   "views": len(tta.TRANSFORMS[name]), "tta_ms": round(t, 3), "forward_ms": round(fwd, 3),
                                   "ratio": round(t / fwd, 3), **kernel_bytes(B, H, W, name)}), flush=True)

@@ -6,38 +6,14 @@ per image, some touching) and the logits are one-hot on them:
 
 Prints one JSON line per measurement.  Run under `rocprofv3 --kernel-trace --stats -- python tools/yield_bench.py` for the
 per-kernel times (profiles/objects_kernel_stats.csv)."""
-import json
-import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "mingraph-unet_amd"))
+from benchkit import emit, timed  # first: benchkit sets the import path
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-import mgunet  # noqa: E402
-from mgunet import objects as mobj  # noqa: E402
-
-
-def timed(fn, iters, warmup=5):
-    """ms per call between HIP events, the stream parked behind a spin kernel so that the events time the GPU."""
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda._sleep(50_000_000)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / iters
-
-
-def emit(**kw):
-    print(json.dumps(kw), flush=True)
+import mgunet
+from mgunet import objects as mobj
 
 
 def discs(B, H, W, seed):
@@ -62,14 +38,14 @@ def main():
         labels = torch.empty((B, H, W), device=dev, dtype=torch.int32)
         counts = torch.empty(B, device=dev, dtype=torch.int64)
         offsets = torch.empty(B + 1, device=dev, dtype=torch.int64)
-        lab_map = timed(lambda: mobj._label(cmap, 0, B, H, W, 0, 2, 0, 0, 0, labels, counts, offsets), 50)
-        lab_fused = timed(lambda: mobj._label(nhwc, 1, B, H, W, C, 2, 0, 0, 0, labels, counts, offsets), 50)
+        lab_map = timed(lambda: mobj._label(cmap, 0, B, H, W, 0, 2, 0, 0, 0, labels, counts, offsets), 50, 5)
+        lab_fused = timed(lambda: mobj._label(nhwc, 1, B, H, W, C, 2, 0, 0, 0, labels, counts, offsets), 50, 5)
         N = int(offsets[B])
         cls = torch.empty(N, device=dev, dtype=torch.int64)
         area = torch.empty(N, device=dev, dtype=torch.int64)
         bbox = torch.empty((N, 4), device=dev, dtype=torch.int32)
         sums = torch.empty((N, 2), device=dev, dtype=torch.int64)
-        st = timed(lambda: mobj._stats(labels, nhwc, 1, B, H, W, C, offsets, N, cls, bbox, area, sums), 50)
+        st = timed(lambda: mobj._stats(labels, nhwc, 1, B, H, W, C, offsets, N, cls, bbox, area, sums), 50, 5)
         ev = mgunet.YieldEvaluator(C, dev)
         upd = timed(lambda: ev.update(logits, cmap), 20, warmup=2)
         emit(what="objects", B=B, H=H, W=W, C=C, objects_per_image=round(N / B, 1), label_classmap_us=round(lab_map * 1e3, 1),
