@@ -767,6 +767,36 @@ int mgu_gaussian_blur_u8(mgu_ctx* ctx, const uint8_t* img_dev, int B, int H, int
  * launch; patch 1..64, weights as above. */
 int mgu_patch_smooth_mean_u8(mgu_ctx* ctx, const uint8_t* rgb_dev, int B, int H, int W, int patch, const int32_t* kx_host, int kw,
                              const int32_t* ky_host, int kh, int per_channel, float* out_dev, int ld_out, int col0, void* hip_stream);
+/* ---- edge-aware refinement of class probabilities (csrc/refine.hip) ---------------------------------------------
+ * Every class plane is filtered `iterations` times with a joint bilateral kernel guided by the photograph, then argmax: cost-volume
+ * filtering (Hosni et al., PAMI 2013), the message-passing step of a dense CRF.  The reference has NO such stage: what follows is THIS
+ * BUILD'S DEFINITION, integers only after the first step, bitwise equal to tests/refine_oracle.py and from run to run.
+ *   src_dev    NHWC fp32 (B,H,W,C), 1 <= C <= 16: probabilities (is_prob 1) or logits (is_prob 0: each pixel's softmax in fp32, maximum
+ *              subtracted, expf, divided by its sum, exactly as mgu_tta_merge forms one view's softmax)
+ *   guide_dev  uint8 (B,H,W,G) contiguous, G 1 or 3 (the photograph at the probabilities' resolution; the channel order does not matter)
+ *   space_lut  HOST int32 (radius+1)*(radius+1), indexed [|dy|][|dx|];  range_lut  HOST int32 [1024];  every entry in [0, 256] and
+ *              space_lut[0][0] * range_lut[0] >= 128 (the centre weight is >= 1: no denominator is 0).  shift in [0, 18], radius in
+ *              [1, 7], iterations in [1, 16].  mgunet.bilateral_tables makes them from two sigmas.  Both are passed to the kernel by value.
+ * Per image (images never interact):
+ *   1. q0_k(p) = rint(clamp(x, 0, 1) * 65535): the product in fp32, rounded to nearest even, NaN -> 0; uint16, not renormalised.
+ *   2. weight of tap d = (dy, dx), |dy|, |dx| <= radius, p + d inside the image, with d2 = sum_g (I_g(p) - I_g(p + d))^2 <= 195075:
+ *        w = (space_lut[|dy|][|dx|] * range_lut[min(d2 >> shift, 1023)] + 128) >> 8          in [0, 256]
+ *      Taps outside the image are skipped in numerator and denominator alike.
+ *   3. num_k(p) = sum_d w q_k(p + d), den(p) = sum_d w, q'_k(p) = (num_k + (den >> 1)) / den (integer division).  radius <= 7 gives
+ *      num <= 225 * 256 * 65535 = 3 774 816 000 < 2^32: uint32 sums are exact, and w <= 256 keeps each product a 24-bit multiply.
+ *      That bound is why the radius stops at 7.
+ *   4. repeated `iterations` times; iteration t + 1 reads only iteration t's planes.
+ *   5. outputs, all SET: labels_dev int64 (B,H,W) the first maximal q_k (mgu_argmax_classes's tie rule); probs_dev fp32 NHWC (B,H,W,C)
+ *      (float)q_k / 65535.0f, correctly rounded -- the planes need NOT sum to 1; conf_dev fp32 (B,H,W) the label's value in probs;
+ *      changed_dev int64 (B) the pixels whose label differs from the first maximal q0_k (integer atomics).  probs_dev, conf_dev and
+ *      changed_dev may be NULL.
+ * Exactly `iterations` launches, plus one fill when changed_dev is given, whatever B, C and the contents; no host synchronisation.
+ * Scratch (the context's, grown on first use): none for one iteration, one uint16 plane set of 2 B H W C bytes for two, two sets beyond.
+ * MGU_ERR_INVALID, before anything is launched or written: a range violation above, G not 1 or 3, a NULL src_dev, guide_dev, labels_dev
+ * or table, an output overlapping the source or the guide, B > 65535, B*H*W >= 2^31.  B*H*W == 0: MGU_OK, nothing touched. */
+int mgu_refine_probs(mgu_ctx* ctx, const float* src_dev, int is_prob, const uint8_t* guide_dev, int B, int H, int W, int C, int G, int radius,
+                     const int32_t* space_lut, const int32_t* range_lut, int shift, int iterations, float* probs_dev, int64_t* labels_dev,
+                     float* conf_dev, int64_t* changed_dev, void* hip_stream);
 /* ---- graph-branch inputs for a whole batch: the node features scripts/graph_refinement.py:72-113 defines and the patch labels
  *      scripts/train_end_to_end.py:340 describes (the training script draws both from torch's RNG, :326 / :342) -----------------------
  * Node features.  rgb (B,H,W,3) uint8 -> rows (B*nph*npw, ld_out) fp32, nph = ceil(H / patch), npw = ceil(W / patch), patches zero

@@ -95,7 +95,8 @@ struct mgu_ctx {
                             // transform's column distances and the seed buckets and first-pixel tables of the split (split.hip);
                             // the pair hash table, row degrees and unsorted pairs of the overlap table (instances.hip); the uint8
                             // class maps between the stages, the background labels and the per-hole counters of clean.hip; the
-                            // class planes, their distance transform and the site column distances of boundary.hip
+                            // class planes, their distance transform and the site column distances of boundary.hip; the 16-bit
+                            // plane sets between the iterations of refine.hip
   size_t objws_bytes = 0;
   int in_ch = 0, ncls = 0, feat = 0, depth = 0, dtype = 0, Cp0 = 0;
   std::vector<Layer> layers;  // enc[i].conv1, enc[i].conv2 ..., bott.conv1, bott.conv2, dec[b].up, dec[b].conv1, dec[b].conv2 ..., final

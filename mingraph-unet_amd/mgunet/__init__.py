@@ -14,6 +14,7 @@ from .instances import (InstanceEvaluator, OverlapTable, evaluate_instances, ins
                         object_overlaps, panoptic_totals)
 from .boundary import BoundaryEvaluator, BoundaryTables, boundary_metrics, boundary_tables, evaluate_boundaries  # noqa: F401
 from .tiled import predict_tiled, tile_grid, tile_weights  # noqa: F401
+from .refine import EdgeRefiner, bilateral_tables, refine_probs  # noqa: F401
 from .graphcut import GraphCut, MultiCut, cut_capacities, cut_energy, cut_energy_multi, graph_cut, graph_cut_multi, label_costs  # noqa: F401
 from .mincut import MinCutRefinement, PatchSegmentPredictor  # noqa: F401
 from .patch_graph import PatchGraphConstructor  # noqa: F401
@@ -26,4 +27,4 @@ __all__ = ["TVLoss", "dice_loss", "FeatureConsistencyLoss", "EllipticalShapeLoss
            "patch_features_u8", "patch_node_features", "patch_labels", "postprocess_segmentation", "DetectionHead", "FeatureFusion", "region_stage", "region_mean_pool", "region_fuse", "region_edge_index", "MinCutRefinement", "PatchSegmentPredictor", "graph_cut", "cut_capacities", "cut_energy", "GraphCut", "graph_cut_multi", "label_costs", "cut_energy_multi", "MultiCut", "UNet", "UNetEncoder", "UNetDecoder", "ConvBlock", "DecoderBlock", "GATNetwork", "MultiHeadGATLayer",
            "GraphAttentionLayer", "PatchGraphConstructor", "MinGraphUNet", "MinGraphUNetE2E", "segment_batch", "argmax_classes",
            "gat_forward_csr", "shard_batch", "segmentation_metrics", "metrics_from_confusion", "SegmentationEvaluator", "evaluate_segmentation",
-           "allreduce_eval_state", "clean_masks", "connected_components", "ObjectTable", "yield_estimation_metrics", "YieldEvaluator", "evaluate_yield", "object_shapes", "ObjectShapes", "object_overlaps", "OverlapTable", "match_masks", "panoptic_totals", "instance_metrics", "object_detection_mAP", "InstanceEvaluator", "evaluate_instances", "boundary_tables", "BoundaryTables", "boundary_metrics", "BoundaryEvaluator", "evaluate_boundaries", "predict_tta", "object_scores", "predict_tiled", "tile_grid", "tile_weights", "Trainer", "E2ETrainer", "FlatAdam", "StepLR", "adam_state_dict", "allreduce_mean_", "load_config", "get_config_recursively", "build_from_config", "build", "lib"]
+           "allreduce_eval_state", "clean_masks", "connected_components", "ObjectTable", "yield_estimation_metrics", "YieldEvaluator", "evaluate_yield", "object_shapes", "ObjectShapes", "object_overlaps", "OverlapTable", "match_masks", "panoptic_totals", "instance_metrics", "object_detection_mAP", "InstanceEvaluator", "evaluate_instances", "boundary_tables", "BoundaryTables", "boundary_metrics", "BoundaryEvaluator", "evaluate_boundaries", "predict_tta", "object_scores", "predict_tiled", "tile_grid", "tile_weights", "refine_probs", "bilateral_tables", "EdgeRefiner", "Trainer", "E2ETrainer", "FlatAdam", "StepLR", "adam_state_dict", "allreduce_mean_", "load_config", "get_config_recursively", "build_from_config", "build", "lib"]

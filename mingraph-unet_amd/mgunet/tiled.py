@@ -15,6 +15,7 @@ import torch
 
 from . import _lib
 from .preprocess import _to_dev_u8
+from .refine import EdgeRefiner
 from .tta import MAX_CLASSES, TRANSFORMS, predict_tta
 from .unet import UNet
 
@@ -123,7 +124,7 @@ class TilePlan:
 
 
 def predict_tiled(model: UNet, images, tile=512, overlap: int = 64, window: str = "ramp", transforms: str = "none",
-                  tiles_per_batch: int = 8, mean=None, std=None, bgr: bool = False):
+                  tiles_per_batch: int = 8, mean=None, std=None, bgr: bool = False, refine: EdgeRefiner = None, guide=None):
     """Softmax probabilities of `model` over images of any size: the network runs on overlapping `tile`-sized crops (tile_grid),
     tiles_per_batch of them per forward, and every pixel gets the window-weighted mean (tile_weights) of the softmaxes of the tiles that
     cover it, added in tile order -- bitwise repeatable and independent of tiles_per_batch given the same tile logits.
@@ -131,6 +132,9 @@ def predict_tiled(model: UNet, images, tile=512, overlap: int = 64, window: str 
     tensor, normalised on the way with mean / std (default: ImagePreprocessor's) and read as BGR when `bgr`, so that a tile is bitwise
     the crop of ImagePreprocessor's output at native size.  An image smaller than the tile is reflect-padded; the padding is computed
     but never written.  transforms != "none": each chunk goes through predict_tta and its averaged probabilities are blended.
+    refine: an EdgeRefiner; the blended canvas then goes through it (mgunet.refine) before the return, guided by `guide` -- uint8
+    (B, H, W, G), (H, W, G) or (H, W) -- which defaults to uint8 `images` themselves (bgr does not matter to a colour distance) and is
+    required with float32 images.  Without `refine` nothing changes, and a `guide` is an error.
     Returns (probs, labels, confidence) with predict_tta's shapes, dtypes and NHWC storage."""
     if not isinstance(model, UNet):
         raise TypeError(f"predict_tiled needs an mgunet.UNet, got {type(model).__name__}")
@@ -140,6 +144,10 @@ def predict_tiled(model: UNet, images, tile=512, overlap: int = 64, window: str 
         raise ValueError(f"unknown transforms {transforms!r}; expected one of {sorted(TRANSFORMS)}")
     if window not in WINDOWS:
         raise ValueError(f"unknown window {window!r}; expected one of {list(WINDOWS)}")
+    if refine is not None and not isinstance(refine, EdgeRefiner):
+        raise TypeError(f"refine must be an mgunet.EdgeRefiner, got {type(refine).__name__}")
+    if refine is None and guide is not None:
+        raise ValueError("guide applies only with refine=EdgeRefiner(...)")
     Th, Tw = _pair(tile, "tile")
     overlap, per = int(overlap), int(tiles_per_batch)
     if overlap < 0 or overlap >= min(Th, Tw):
@@ -171,6 +179,8 @@ def predict_tiled(model: UNet, images, tile=512, overlap: int = 64, window: str 
         if mean is not None or std is not None or bgr:
             raise ValueError("mean, std and bgr apply to uint8 images only; a float32 batch is taken as already normalised")
         B, Cin, H, W = images.shape
+        if refine is not None and guide is None:
+            raise ValueError("refine with float32 images needs a uint8 guide: the normalised batch is no photograph")
     if Cin != model.in_channels:
         raise RuntimeError(f"expected {model.in_channels} input channels, got {Cin}")
     if B == 0 or H == 0 or W == 0:
@@ -189,4 +199,6 @@ def predict_tiled(model: UNet, images, tile=512, overlap: int = 64, window: str 
             else:
                 out, is_prob = predict_tta(model, buf, transforms)[0], True
             plan.accumulate(out.permute(0, 2, 3, 1), t0, probs, labels, conf, is_prob=is_prob)   # the NHWC storage, contiguous
+    if refine is not None:
+        return refine(probs.permute(0, 3, 1, 2), images if guide is None else guide)
     return probs.permute(0, 3, 1, 2), labels, conf
