@@ -552,7 +552,10 @@ int mgu_unet_forward(mgu_ctx* c, const void* x_dev, int B, int H, int W, int64_t
       void *cat = at(cat_dev[i], i, 2 * C), *pooled = at(ws + plan.pooled[i], i + 1, C);
       ConvTaken took;   // MaxPool2d(2) (unet_encoder.py:48) rides in the conv2 epilogue on the Winograd path
       if ((rc = conv(b.conv2, i, {.in = tmp, .ldin = C, .out = cat, .ldout = 2 * C, .relu = 1}, {.pool = pooled, .ldpool = C}, &took))) return rc;
-      if (!took.pool) HIPCHK(c, launch_maxpool2(cat, 2 * C, pooled, c->dtype, nb, hs[i], wsz[i], C, gs));
+      if (!took.pool) {   // (a pick without the fused epilogue: the tile kernels)
+        ProfScope ps(c, gs, "maxpool2", 0, 0, -1);
+        HIPCHK(c, launch_maxpool2(cat, 2 * C, pooled, c->dtype, nb, hs[i], wsz[i], C, gs));
+      }
       cur = pooled, cur_ld = C;
     }
     {  // bottleneck, :72

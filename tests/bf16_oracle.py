@@ -105,6 +105,24 @@ def ulp_bf16(t):
     return torch.where(m > 0, torch.ldexp(torch.ones_like(m), e - 8), torch.zeros_like(m))
 
 
+def ulp_fp32(t):
+    """Spacing of fp32 at |t| (0 at 0), float64."""
+    m, e = torch.frexp(t.to(F64).abs())
+    return torch.where(m > 0, torch.ldexp(torch.ones_like(m), e - 24), torch.zeros_like(m))
+
+
+class Storage:
+    """What a forward keeps its tensors in: the rounding of a stored weight, of a stored activation (from the fp32 value a kernel
+    holds), and the spacing of the format.  BF16 is the bf16-storage forward; FP32 (tests/fp32_oracle.py) stores what it computes."""
+
+    def __init__(self, name, weight, act, ulp):
+        self.name, self.weight, self.act, self.ulp = name, weight, act, ulp
+
+
+BF16 = Storage("bf16", O._bf16, bf16_rne, ulp_bf16)
+FP32 = Storage("fp32", lambda w: w, lambda v: v, ulp_fp32)
+
+
 # ---- geometry of the direct kernels (csrc/igemm.hip: launch_halo_tiles) -------------------------------------------------------------
 def patch_rows(N):
     return 8 if N > 64 else 16          # the 128-channel tile walks 8 x 16 patches, the others 16 x 16
@@ -148,6 +166,10 @@ class Ops:
     @staticmethod
     def store(v):
         return bf16_rne(v)
+
+    @staticmethod
+    def pool(x):
+        return F.max_pool2d(x, 2, 2)
 
     @staticmethod
     def place(up, H, W, bias):
@@ -289,7 +311,7 @@ def _quadrant_swap(x, w, b):
 
 def _pad_written(up, H, W, bias):
     dy, dx = H - up.shape[2], W - up.shape[3]
-    out = bf16_rne(bias)[None, :, None, None].expand(up.shape[0], -1, H, W).clone()      # ConvTranspose of nothing: the bias
+    out = bias[None, :, None, None].expand(up.shape[0], -1, H, W).clone()      # ConvTranspose of nothing: the (stored) bias
     out[:, :, dy // 2:dy // 2 + up.shape[2], dx // 2:dx // 2 + up.shape[3]] = up
     return out
 
@@ -314,50 +336,50 @@ INDEXING = ("lost_piece_last_col", "lost_piece_last_row", "bottom_halo_clamped",
 
 
 # ---- segments -----------------------------------------------------------------------------------------------------------------------
-def _block(p, prefix, cur, first_fp32, ops, eps=1e-5):
+def _block(p, prefix, cur, first_fp32, ops, eps=1e-5, st=BF16):
     """ConvBlock with the storage roundings; returns (stored output, unit floor per output channel of the block's second conv)."""
     dt = ops.dtype
     floor = None
     for ci, (c, bn) in enumerate((("conv1", "bn1"), ("conv2", "bn2"))):
         w = p[prefix + c + ".weight"]
         if not (first_fp32 and ci == 0):
-            w = O._bf16(w)
+            w = st.weight(w)
         scale = p[prefix + bn + ".weight"] / torch.sqrt(p[prefix + bn + ".running_var"] + eps)            # fp32, as the library folds
         shift = p[prefix + bn + ".bias"] + (p[prefix + c + ".bias"] - p[prefix + bn + ".running_mean"]) * scale
         if ci == 1:
             hmax = cur.abs().max().to(F64)
-            floor = scale.to(F64).abs() * w.to(F64).abs().amax(dim=(1, 2, 3)) * ulp_bf16(hmax)
+            floor = scale.to(F64).abs() * w.to(F64).abs().amax(dim=(1, 2, 3)) * st.ulp(hmax)
         z = ops.conv3(cur.to(dt), w.to(dt))
         cur = ops.store(F.relu(ops.fold(z, scale.to(dt), shift.to(dt)))).to(dt)
     return cur, floor
 
 
-def _decoder(p, bi, cur, skip, ops):
+def _decoder(p, bi, cur, skip, ops, eps=1e-5, st=BF16):
     pre = f"decoder.decoder_blocks.{bi}."
     dt = ops.dtype
     b = p[pre + "upsample.bias"].to(dt)
-    up = bf16_rne(ops.convt(cur.to(dt), O._bf16(p[pre + "upsample.weight"]).to(dt), b))
-    up = ops.place(up, skip.shape[2], skip.shape[3], b)
-    return _block(p, pre + "conv_block.", torch.cat([skip.to(dt), up], dim=1), False, ops)
+    up = st.act(ops.convt(cur.to(dt), st.weight(p[pre + "upsample.weight"]).to(dt), b))
+    up = ops.place(up, skip.shape[2], skip.shape[3], st.act(b))
+    return _block(p, pre + "conv_block.", torch.cat([skip.to(dt), up], dim=1), False, ops, eps, st)
 
 
 def segment_names(depth):
     return [f"skip{i}" for i in range(depth)] + [f"feat{i}" for i in range(depth - 1, -1, -1)]
 
 
-def segment(p, depth, name, src, first_fp32=False, ops=EXACT):
+def segment(p, depth, name, src, first_fp32=False, ops=EXACT, st=BF16, eps=1e-5):
     """Exposed tensor `name` from its exposed predecessors `src` (a tuple: (x,) for skip0, (skip_i-1,) for skip_i, (skip_depth-1,)
     for feat_depth-1, (feat_i+1, skip_i) for feat_i), in ops' arithmetic.  Returns (tensor in float64, unit floor per channel)."""
     i = int(name[4:])
     with torch.no_grad():
         if name.startswith("skip"):
-            cur = O._bf16(src[0].to(torch.float32)) if i == 0 else F.max_pool2d(src[0], 2, 2)
-            out, fl = _block(p, f"encoder.encoder_blocks.{i}.", cur, first_fp32 and i == 0, ops)
+            cur = st.weight(src[0].to(torch.float32)) if i == 0 else ops.pool(src[0])
+            out, fl = _block(p, f"encoder.encoder_blocks.{i}.", cur, first_fp32 and i == 0, ops, eps, st)
         elif i == depth - 1:
-            bott, _ = _block(p, "encoder.bottleneck.", F.max_pool2d(src[0], 2, 2), False, ops)
-            out, fl = _decoder(p, 0, bott, src[0], ops)
+            bott, _ = _block(p, "encoder.bottleneck.", ops.pool(src[0]), False, ops, eps, st)
+            out, fl = _decoder(p, 0, bott, src[0], ops, eps, st)
         else:
-            out, fl = _decoder(p, depth - 1 - i, src[0], src[1], ops)
+            out, fl = _decoder(p, depth - 1 - i, src[0], src[1], ops, eps, st)
     out = out.to(F64)
     if ops is EXACT and is_deep(depth, name):
         # four unexposed layers, not one: the floor of a deep segment is what two correct float32 evaluations are seen to differ from the
