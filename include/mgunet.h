@@ -141,6 +141,18 @@ int mgu_sync_check(mgu_ctx* ctx, void* hip_stream);
 /* loss.backward() (train_segmentation.py:133) for the last mgu_unet_forward(training=1): dlogits_dev as
  * produced by mgu_cross_entropy; every element of flat_grad_dev (mgu_unet_param_count floats) is written. */
 int mgu_unet_backward(mgu_ctx* ctx, const void* dlogits_dev, void* flat_grad_dev, void* hip_stream);
+/* Test hooks: what mgu_unet_backward reads of the last mgu_unet_forward(training=1) of this ctx, per layer, read-only.  `layer` is the
+ * state_dict prefix of a convolution: "encoder.encoder_blocks.0.conv1", "encoder.bottleneck.conv2",
+ * "decoder.decoder_blocks.1.conv_block.conv1", "decoder.decoder_blocks.1.upsample", "decoder.final_conv".
+ * mgu_unet_train_record_dims: the grid the layer ran on (a ConvTranspose's INPUT grid) and its channel counts.
+ * mgu_unet_train_record_copy: copies (pitched device-to-device copies on hip_stream) into caller-owned DENSE fp32 device tensors, each
+ * skipped when NULL: in (B,H,W,Cin) the layer's input (the first Cin channels of its pixels), z (B,H,W,Cout) the convolution's output
+ * in front of the BatchNorm, y (B,H,W,Cout) = relu(bn(z)), mean / invstd (Cout) the batch statistics.  An up-convolution and the final
+ * conv record their input only: asking them for z / y / mean / invstd is MGU_ERR_INVALID, as is an unknown or NULL name; without a
+ * train-mode forward both return MGU_ERR_STATE.  Neither allocates anything that outlives the call nor changes any state. */
+int mgu_unet_train_record_dims(mgu_ctx* ctx, const char* layer, int* B_out, int* H_out, int* W_out, int* Cin_out, int* Cout_out);
+int mgu_unet_train_record_copy(mgu_ctx* ctx, const char* layer, void* in_dev, void* z_dev, void* y_dev, void* mean_dev, void* invstd_dev,
+                               void* hip_stream);
 /* ---- backward building blocks: ONE stage of loss.backward() each, through exactly the launchers mgu_unet_backward uses,
  *      on caller-provided NHWC fp32 tensors (kernel-level parity tests against float64; also usable on their own) ------
  * Weight gradient of Conv2d(k=1|3, pad=k/2) (unet_encoder.py:7-8): dw[co][ci][r][s] = sum_{b,y,x} dz[b,y,x,co] *

@@ -456,6 +456,52 @@ int mgu_unet_backward_allreduce(mgu_ctx* c, const void* dlogits_dev, void* flat_
   return backward_impl(c, dlogits_dev, flat_grad_dev, hip_stream, 1);
 }
 
+// ---- test hook: the record of the last train-mode forward, read-only ---------------------------------------------------------------
+// the layer whose state_dict prefix (Layer::prefix + Layer::conv) is `name`, or -1
+static int record_layer(const mgu_ctx* c, const char* name) {
+  const std::string key(name);
+  for (size_t i = 0; i < c->layers.size(); ++i)
+    if (key == c->layers[i].prefix + c->layers[i].conv) return (int)i;
+  return -1;
+}
+
+int mgu_unet_train_record_dims(mgu_ctx* c, const char* layer, int* B_out, int* H_out, int* W_out, int* Cin_out, int* Cout_out) {
+  if (!c) return MGU_ERR_INVALID;
+  if (!layer || !B_out || !H_out || !W_out || !Cin_out || !Cout_out) return fail(c, MGU_ERR_INVALID, "NULL argument");
+  if (!c->have_train_fwd) return fail(c, MGU_ERR_STATE, "mgu_unet_train_record_dims needs a preceding mgu_unet_forward(training=1)");
+  const int i = record_layer(c, layer);
+  if (i < 0) return fail(c, MGU_ERR_INVALID, "no layer named '%s'", layer);
+  const FwdRecord& r = c->fwd[i];
+  *B_out = r.B, *H_out = r.H, *W_out = r.W, *Cin_out = c->layers[i].Cin, *Cout_out = c->layers[i].Cout;
+  return MGU_OK;
+}
+
+int mgu_unet_train_record_copy(mgu_ctx* c, const char* layer, void* in_dev, void* z_dev, void* y_dev, void* mean_dev, void* invstd_dev,
+                               void* hip_stream) {
+  if (!c) return MGU_ERR_INVALID;
+  if (!layer) return fail(c, MGU_ERR_INVALID, "NULL layer name");
+  if (!c->have_train_fwd) return fail(c, MGU_ERR_STATE, "mgu_unet_train_record_copy needs a preceding mgu_unet_forward(training=1)");
+  const int i = record_layer(c, layer);
+  if (i < 0) return fail(c, MGU_ERR_INVALID, "no layer named '%s'", layer);
+  const Layer& L = c->layers[i];
+  const FwdRecord& r = c->fwd[i];
+  if ((z_dev || y_dev || mean_dev || invstd_dev) && (L.bn.empty() || !r.z || !r.y))
+    return fail(c, MGU_ERR_INVALID, "layer '%s' has no BatchNorm: it records its input only", layer);
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)hip_stream;
+  const size_t M = (size_t)r.B * r.H * r.W, f = sizeof(float);
+  // M rows of n floats from pitch ld to a dense tensor
+  auto rows = [&](void* dst, const float* src, int ld, int n) {
+    return hipMemcpy2DAsync(dst, n * f, src, ld * f, n * f, M, hipMemcpyDeviceToDevice, s);
+  };
+  if (in_dev) HIPCHK(c, rows(in_dev, r.in, r.ldin, L.Cin));
+  if (z_dev) HIPCHK(c, rows(z_dev, r.z, L.Cout, L.Cout));
+  if (y_dev) HIPCHK(c, rows(y_dev, r.y, r.ldy, L.Cout));
+  if (mean_dev) HIPCHK(c, hipMemcpyAsync(mean_dev, L.mean, L.Cout * f, hipMemcpyDeviceToDevice, s));
+  if (invstd_dev) HIPCHK(c, hipMemcpyAsync(invstd_dev, L.invstd, L.Cout * f, hipMemcpyDeviceToDevice, s));
+  return MGU_OK;
+}
+
 int mgu_adam_step(mgu_ctx* c, void* flat_param_dev, const void* flat_grad_dev, void* exp_avg_dev, void* exp_avg_sq_dev,
                   int64_t n, float lr, double beta1, double beta2, float eps, float weight_decay, int step, float grad_scale,
                   void* hip_stream) {

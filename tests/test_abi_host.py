@@ -46,10 +46,25 @@ def test_prototypes_are_read_from_the_header(tmp_path):
     assert protos["mgu_version"][:2] == (C.c_char_p, [])
     assert protos["mgu_unet_load_weights"][1] == [C.c_void_p, C.POINTER(_lib.TensorDesc), C.c_int, C.c_void_p]
     assert protos["mgu_tv_loss"][1][6:11] == [C.c_int64] * 4 + [C.c_float]
+    # the train-record test hooks: a layer name as a C string, int* outputs / device tensors as plain pointers, the copy on a stream
+    assert protos["mgu_unet_train_record_dims"] == (C.c_int, [C.c_void_p, C.c_char_p] + [C.c_void_p] * 5, False)
+    assert protos["mgu_unet_train_record_copy"] == (C.c_int, [C.c_void_p, C.c_char_p] + [C.c_void_p] * 6, True)
+    assert protos["mgu_unet_param_offset"][:2] == (C.c_int64, [C.c_void_p, C.c_char_p])
     bad = tmp_path / "bad.h"
     bad.write_text("int mgu_fine(mgu_ctx* ctx, void* hip_stream);\nint mgu_bad(mgu_ctx* ctx, long n);\n")
     with pytest.raises(TypeError, match="mgu_bad"):
         _lib.parse_header(str(bad))
+
+
+def test_train_record_hooks_are_declared_as_test_hooks_and_refuse_a_null_context():
+    txt = open(os.path.join(ROOT, "include", "mgunet.h")).read()
+    at = txt.index("int mgu_unet_train_record_dims(")
+    comment = txt[txt.rindex("/*", 0, at):at]
+    assert comment.startswith("/* Test hooks:") and "mgu_unet_train_record_copy" in comment and "read-only" in comment
+    L = _lib.lib()
+    v = [C.c_int() for _ in range(5)]
+    assert L.mgu_unet_train_record_dims(None, b"encoder.bottleneck.conv1", *[C.byref(i) for i in v]) == _lib.MGU_ERR_INVALID
+    assert L.mgu_unet_train_record_copy(None, b"encoder.bottleneck.conv1", None, None, None, None, None, None) == _lib.MGU_ERR_INVALID
 
 
 def test_create_fails_loudly_without_gpu():
