@@ -406,6 +406,37 @@ int mgu_feature_consistency_loss_backward(mgu_ctx* ctx, const void* f_unet_dev, 
 /* Synchronise the stream and report (MGU_ERR_INVALID) a label outside [0, num_classes) met by mgu_dice_loss[_backward] on this
  * context since the last check: the place F.one_hot would have raised. */
 int mgu_loss_sync_check(mgu_ctx* ctx, void* hip_stream);
+/* Lovasz-Softmax loss (Berman, Triki, Blaschko, CVPR 2018; the build's own addition), the convex
+ * surrogate of 1 - IoU.  logits / labels / strides as mgu_dice_loss, num_classes <= 8.  A segment is one class over the batch
+ * (per_image 0) or one (image, class) pair (per_image 1); a pixel labelled ignore_index belongs to none (no rank, no term, zero
+ * gradient); any other label outside [0, num_classes) is flagged as mgu_dice_loss flags it (mgu_loss_sync_check) and the loss is
+ * NaN.  Per segment the errors e = 1 - p[c] (label c) / p[c] (else), p the fp32 softmax, are ranked in DESCENDING order, equal fp32
+ * errors in ascending pixel order (b, y, x): part of the interface.  With G the segment's foreground pixels, k the rank from 1 and
+ * F_k the foreground pixels among ranks 1..k, U_k = G + k - F_k: g_k = 1 / U_k (foreground), (G - F_k) / (U_k (U_k - 1))
+ * (background), G == 0: g_1 = 1, else 0 -- from the integer counts in double, rounded once.  Segment loss = sum_k e_(k) g_k in
+ * double in a fixed order (bitwise reproducible); loss = mean over the counted segments (classes_mode 0 "present": G > 0 only;
+ * 1 "all"), with per_image the mean over an image's counted classes, then over the B images (an image without one adds 0).
+ * errors_dev fp32 / ranks_dev int32, each (num_classes, B*HW), optional test hooks: the errors and the 0-based rank inside the
+ * segment (ignored pixel: error 0, rank -1).  Stream-ordered, no host synchronisation.
+ * Launches: 16 for the value, 17 with the gradient (four sort passes of histogram + scan + scatter over 8 + 8 + 8 + 7 key bits,
+ * foreground count, its scan, the closed forms, the finishing kernel, the per-pixel softmax backward), whatever num_classes,
+ * per_image and B are.  Scratch (the context's, grown on first use): with P = B*HW, G = per_image ? B : 1 and
+ * T = num_classes * G * ceil(P / G / mgu_lovasz_tile()) tiles: 16 * num_classes * P bytes of key / payload planes + 1024 * T
+ * of digit counts + 12 * T + 1040 * num_classes * G, each of the eleven regions rounded up to 256 bytes (68 172 544 bytes = 65.0 MiB
+ * at 8 x 512 x 512, 2 classes, over the batch).  num_classes > 8, an empty shape or B*HW >= 2^30 return MGU_ERR_INVALID and launch nothing. */
+int mgu_lovasz_softmax(mgu_ctx* ctx, const void* logits_dev, const int64_t* labels_dev, int B, int64_t HW, int num_classes, int64_t ls_n,
+                       int64_t ls_c, int64_t ls_p, int classes_mode, int per_image, int64_t ignore_index, float* loss_dev,
+                       float* errors_dev, int32_t* ranks_dev, void* hip_stream);
+/* d Lovasz-Softmax / d logits: dL/dp_i[c] = -+ g_rank / (counted segments of that mean [* B with per_image]) (foreground -,
+ * background +), through the softmax, times grad_scale (* *grad_scale_dev if given); element (b, c, p) at
+ * dlogits_dev[b*ds_n + c*ds_c + p*ds_p], accumulate != 0 ADDS (the trainer's "ce+lovasz": after mgu_cross_entropy on the same
+ * dlogits).  loss_dev (optional) receives the loss value of the same pass. */
+int mgu_lovasz_softmax_backward(mgu_ctx* ctx, const void* logits_dev, const int64_t* labels_dev, int B, int64_t HW, int num_classes,
+                                int64_t ls_n, int64_t ls_c, int64_t ls_p, int classes_mode, int per_image, int64_t ignore_index,
+                                float grad_scale, const float* grad_scale_dev, void* dlogits_dev, int64_t ds_n, int64_t ds_c, int64_t ds_p,
+                                int accumulate, float* loss_dev, void* hip_stream);
+/* Keys one workgroup ranks per sort pass of the Lovasz kernels (the tests size their segments around it). */
+int mgu_lovasz_tile(void);
 /* EllipticalShapeLoss.forward (model/unet/shape_loss.py:17-180).  _masks: the object_masks_list form, all masks of the batch
  * stacked (num_objects, H, W) uint8 (non-zero = object pixel).  _probs: the form without masks -- per image, the pixels whose
  * arg-max class is 1 are ONE object (:61-98); probabilities (B,C,H,W) at probs_dev[b*ps_n + c*ps_c + p*ps_p].  Objects under 10

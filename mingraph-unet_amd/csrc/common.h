@@ -53,6 +53,8 @@ struct Tuning {
                             // second on the context's side stream, so that one half's workgroups fill the CUs while the other half's
                             // kernel drains and its next packet is handed over; 1 = the whole batch on the caller's stream
                             // (mgu_unet_forward; bitwise equal results, profiles/forward_groups_ab.txt)
+  int lovasz_passes = 4;    // MGU_LOVASZ_PASSES: 4 (default) = the Lovasz sort's 31 key bits as 8 + 8 + 8 + 7, 3 = as 10 + 10 + 11 (lovasz.hip;
+                            // bitwise equal results, 2 - 3 % slower: profiles/lovasz_bench.txt)
 };
 const Tuning& default_tuning();
 // The >64 KB dynamic-LDS opt-in is a per-DEVICE function attribute: set it once per (kernel, device).

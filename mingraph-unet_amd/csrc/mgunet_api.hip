@@ -117,6 +117,7 @@ int mgu_create(int device_id, mgu_ctx** out) {
   t.wino_asm = num("MGU_WINO_ASM", 1) > 0;
   t.head_fused = num("MGU_HEAD_FUSED", 1) > 0;
   t.fwd_groups = num("MGU_FWD_GROUPS", t.fwd_groups) >= 2 ? 2 : 1;
+  t.lovasz_passes = num("MGU_LOVASZ_PASSES", t.lovasz_passes) == 3 ? 3 : 4;
   *out = c;
   return MGU_OK;
 }

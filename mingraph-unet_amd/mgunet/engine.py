@@ -11,8 +11,11 @@ import torch.nn as nn
 from . import _lib
 from ._args import check_masks, nhwc_storage
 from .gat import GATNetwork, _csr_cache, _layer_forward, _LayerCall
+from .losses import _LOVASZ_CLASSES
 from .patch_graph import PatchGraphConstructor
 from .unet import UNet
+
+LOSSES = ("ce", "ce+dice", "ce+lovasz", "ce+dice+lovasz")   # what Trainer(loss=...) accepts
 
 
 class MinGraphUNet(nn.Module):
@@ -222,7 +225,7 @@ class Trainer:
     own shard (DDP semantics)."""
 
     def __init__(self, model: UNet, lr=1e-3, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, process_group=None, comm="auto",
-                 loss="ce", dice_smooth=1.0, optimizer="adam", momentum=0.9):
+                 loss="ce", dice_smooth=1.0, optimizer="adam", momentum=0.9, lovasz_per_image=False, lovasz_classes="present"):
         """comm: "auto" (default) -- with more than one rank the gradient is mean-all-reduced by torch.distributed (RCCL when the
         backend is "nccl") after backward: the path exercised with two ranks.  "rccl" -- opt in to libmgunet's own RCCL
         communicator with the bucketed exchange overlapped with backward (mgu_unet_backward_allreduce); tests/test_gpu_rccl.py
@@ -230,11 +233,17 @@ class Trainer:
         loss: "ce" -- nn.CrossEntropyLoss() alone (train_segmentation.py:91,127); "ce+dice" -- the sum the script forms at
         :126-130, `criterion_ce(logits, masks) + dice_loss(logits, masks)`: the Dice gradient (through the softmax) is added to
         the cross-entropy gradient in the same dlogits buffer (mgu_dice_loss_backward, accumulate) before the one backward pass.
+        "ce+lovasz" / "ce+dice+lovasz" -- additionally the Lovasz-Softmax loss (losses.lovasz_softmax, the IoU surrogate; options
+        lovasz_per_image, lovasz_classes), added the same way after them: one mgu_lovasz_softmax_backward(accumulate) call.
         ("rccl" also creates the communicator for a single process: the collective then degenerates to a copy.)
         optimizer: "adam" (train_segmentation.py:96, the shipped configs/training.yaml) or "sgd" -- the script's other branch,
         optim.SGD(lr, momentum=sgd_momentum, weight_decay) (:97-98; training.yaml:5-6): one fused kernel on the flat buffers either way."""
         if optimizer not in ("adam", "sgd"):
             raise ValueError(f"unknown optimizer {optimizer!r}: 'adam' or 'sgd'")
+        if loss not in LOSSES:
+            raise ValueError(f"unknown loss {loss!r}: " + ", ".join(repr(k) for k in LOSSES[:-1]) + f" or {LOSSES[-1]!r}")
+        if lovasz_classes not in _LOVASZ_CLASSES:
+            raise ValueError(f"unknown lovasz_classes {lovasz_classes!r}: 'present' or 'all'")
         self.optimizer, self.momentum = optimizer, float(momentum)
         params = list(model.named_parameters())
         _lib.require_hip(params[0][1], "Trainer")
@@ -263,9 +272,9 @@ class Trainer:
         model.mark_parameters_changed()
         model._slots = None
         self.step_count = 0
-        if loss not in ("ce", "ce+dice"):
-            raise ValueError(f"unknown loss {loss!r}: 'ce' or 'ce+dice'")
         self.loss_kind, self.dice_smooth = loss, float(dice_smooth)
+        self.lovasz_mode, self.lovasz_per_image = _LOVASZ_CLASSES[lovasz_classes], int(bool(lovasz_per_image))
+        self._lovasz = torch.zeros(1, device=dev, dtype=torch.float32)
         self._loss = torch.zeros(1, device=dev, dtype=torch.float32)
         self._dice = torch.zeros(1, device=dev, dtype=torch.float32)
         self._rccl = False
@@ -398,10 +407,14 @@ class Trainer:
         dlogits = torch.empty((npix, ldd), device=dev, dtype=torch.float32)
         loss = self._loss
         _lib.call("mgu_cross_entropy", dev, nhwc, masks, npix, Cc, 1.0 / npix, dlogits, self._loss, ctx=ctx)
-        if self.loss_kind == "ce+dice":   # loss = loss_ce + loss_dice (:130): d(dice)/d(logits) is ADDED to the CE gradient
+        if "dice" in self.loss_kind:   # loss = loss_ce + loss_dice (:130): d(dice)/d(logits) is ADDED to the CE gradient
             _lib.call("mgu_dice_loss_backward", dev, nhwc, masks, B, H * W, Cc, H * W * Cc, 1, Cc, self.dice_smooth, 1.0, None, dlogits,
                       H * W * ldd, 1, ldd, 1, self._dice, ctx=ctx)
             loss = self._loss + self._dice
+        if "lovasz" in self.loss_kind:   # ... and so is d(lovasz)/d(logits)
+            _lib.call("mgu_lovasz_softmax_backward", dev, nhwc, masks, B, H * W, Cc, H * W * Cc, 1, Cc, self.lovasz_mode,
+                      self.lovasz_per_image, -100, 1.0, None, dlogits, H * W * ldd, 1, ldd, 1, self._lovasz, ctx=ctx)
+            loss = loss + self._lovasz
         _lib.call("mgu_unet_backward_allreduce" if exchange else "mgu_unet_backward", dev, dlogits, self.grad, ctx=ctx)
         return loss
 

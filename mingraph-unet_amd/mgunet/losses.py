@@ -1,6 +1,6 @@
 """Host-side mirrors of the reference's auxiliary losses, routed through libmgunet.so: same names,
 constructor arguments, call signatures and error messages.  Each call returns a 0-dim float32 tensor on the input's device.
-TVLoss, dice_loss and FeatureConsistencyLoss are differentiable (torch.autograd.Function nodes whose backward is a HIP kernel:
+TVLoss, dice_loss, lovasz_softmax and FeatureConsistencyLoss are differentiable (torch.autograd.Function nodes whose backward is a HIP kernel:
 mgu_*_backward), so `loss.backward()` as at scripts/train_segmentation.py:133 works on them; EllipticalShapeLoss has no gradient
 w.r.t. its input (a function of arg-max pixel coordinates; the reference loop pins loss_shape to 0, train_end_to_end.py:287).
 check_labels(device) synchronises and raises where F.one_hot would have raised on an out-of-range label.
@@ -9,6 +9,7 @@ check_labels(device) synchronises and raises where F.one_hot would have raised o
     dice_loss                scripts/train_segmentation.py:29-40
     FeatureConsistencyLoss   model/unet/feature_loss.py:5-125
     EllipticalShapeLoss      model/unet/shape_loss.py:6-180
+    lovasz_softmax           the build's own addition (the reference has no IoU surrogate): INTEGRATION.md section Q
 """
 from __future__ import annotations
 
@@ -95,6 +96,70 @@ def dice_loss(pred, target, smooth=1.):
     if pred.dim() != 4 or target.dim() != 3 or target.dtype != torch.int64:
         raise ValueError("expected logits (B, C, H, W) and an int64 target (B, H, W)")
     return _DiceFn.apply(pred, target, smooth)
+
+
+_LOVASZ_CLASSES = {"present": 0, "all": 1}
+
+
+def _pixel_strided(pd):
+    """pd with ONE stride for the pixel index (both NCHW and NHWC storage qualify; anything else is copied)"""
+    return pd if pd.stride(2) == pd.shape[3] * pd.stride(3) else pd.contiguous()
+
+
+class _LovaszFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx_, pred, target, mode, per_image, ignore_index):
+        pd = _pixel_strided(_f32(pred))
+        B, C_, H, W = pd.shape
+        target = target.contiguous()
+        out = torch.empty((), device=pd.device, dtype=torch.float32)
+        _lib.call("mgu_lovasz_softmax", pd.device, pd, target, B, H * W, C_, pd.stride(0), pd.stride(1), pd.stride(3), mode, per_image,
+                  ignore_index, out, None, None)
+        ctx_.save_for_backward(pd, target)
+        ctx_.opts, ctx_.in_dtype = (mode, per_image, ignore_index), pred.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx_, g):
+        pd, target = ctx_.saved_tensors
+        B, C_, H, W = pd.shape
+        d = torch.empty_strided(pd.shape, pd.stride(), device=pd.device, dtype=torch.float32)   # NHWC storage stays NHWC
+        g = g.detach().float().contiguous()
+        _lib.call("mgu_lovasz_softmax_backward", pd.device, pd, target, B, H * W, C_, pd.stride(0), pd.stride(1), pd.stride(3), *ctx_.opts,
+                  1.0, g, d, d.stride(0), d.stride(1), d.stride(3), 0, None)
+        return d.to(ctx_.in_dtype), None, None, None, None
+
+
+def _lovasz_args(pred, target, classes, per_image, ignore_index):
+    _lib.require_hip(pred, "mgunet lovasz_softmax")
+    if pred.dim() != 4 or target.dim() != 3 or target.dtype != torch.int64:
+        raise ValueError("expected logits (B, C, H, W) and an int64 target (B, H, W)")
+    if classes not in _LOVASZ_CLASSES:
+        raise ValueError(f"unknown classes {classes!r}: 'present' or 'all'")
+    return _LOVASZ_CLASSES[classes], int(bool(per_image)), int(ignore_index)
+
+
+def lovasz_softmax(pred, target, classes="present", per_image=False, ignore_index=-100):
+    """Lovasz-Softmax loss (Berman, Triki, Blaschko, CVPR 2018), the convex surrogate of 1 - IoU: pred
+    (B, C, H, W) logits with C <= 8 (any strides dice_loss accepts), target (B, H, W) int64.  classes: "present" averages over the
+    classes that occur in the target, "all" over every class; per_image: one loss per image, then their mean; pixels labelled
+    ignore_index take no part.  Differentiable w.r.t. pred.  Any other label outside [0, C) makes the loss NaN and is reported by
+    check_labels(pred.device) (no host sync inside the call)."""
+    return _LovaszFn.apply(pred, target, *_lovasz_args(pred, target, classes, per_image, ignore_index))
+
+
+def _lovasz_debug(pred, target, classes="present", per_image=False, ignore_index=-100):
+    """(loss, errors, ranks) through the test hooks of mgu_lovasz_softmax: errors fp32 and ranks int32, each (C, B, H, W): the
+    error of every pixel for every class and its 0-based rank inside its segment (-1: ignored pixel)."""
+    mode, per_image, ignore_index = _lovasz_args(pred, target, classes, per_image, ignore_index)
+    pd = _pixel_strided(_f32(pred))
+    B, C_, H, W = pd.shape
+    out = torch.empty((), device=pd.device, dtype=torch.float32)
+    errors = torch.empty((C_, B, H, W), device=pd.device, dtype=torch.float32)
+    ranks = torch.empty((C_, B, H, W), device=pd.device, dtype=torch.int32)
+    _lib.call("mgu_lovasz_softmax", pd.device, pd, target.contiguous(), B, H * W, C_, pd.stride(0), pd.stride(1), pd.stride(3), mode,
+              per_image, ignore_index, out, errors, ranks)
+    return out, errors, ranks
 
 
 class _FeatConsFn(torch.autograd.Function):
