@@ -978,6 +978,10 @@ typedef struct {
 } mgu_kernel_stat;
 int mgu_profile_read_kernels(mgu_ctx* ctx, mgu_kernel_stat* out, int cap, int* n_out);
 int mgu_profile_read(mgu_ctx* ctx, double* conv_ms, int* conv_launches, double* total_ms);
+/* ConvTranspose launches of this context since mgu_create that ran on the hand-scheduled assembly kernel mgu_convt_x3_gfx950
+ * (csrc/asm/gen_convt_x3.py).  The profiling records name it like the C++ kernel it replaces, convt2x2_x3_kernel (bitwise equal
+ * results): this count is how a test or a tool tells the two apart.  MGU_CONVT_ASM=0 at mgu_create keeps it at 0. */
+int64_t mgu_convt_asm_launches(mgu_ctx* ctx);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Static check of the hand-counted waits and wait states of the generated Winograd assembly (asm/gen_wino_cp.py: generate(head)).
+"""Static check of the hand-counted waits and wait states of the generated assembly: the Winograd kernels (asm/gen_wino_cp.py:
+generate(head)) and the ConvTranspose kernel (asm/gen_convt_x3.py: generate()).
 
 The hand-written kernels carry no compiler-inserted s_waitcnt / s_nop: every wait is counted by the generator.  This checker
 replays the instruction stream of each kernel's steady-state loops (the loop bodies repeated, branches taken as straight-line code) with the machine's
@@ -16,8 +17,9 @@ in-order counters and fails on:
   * a transform's outer sum (v_add_f32 / v_sub_f32 of an inner sum) whose other operand is no longer an inner sum, or is the inner
     sum of an older read base: the jj = 1 forming takes the shared tile column's inner sum from the registers the jj = 0 forming
     left it in, and nothing may overwrite them in between (the model tracks what each register holds: an LDS read, an inner sum
-    v_fmac_f32 of two of them, or anything else).
-Used by tests/test_asm_lint.py (CPU) and runnable by hand:  lint_wino_asm.py FILE.s
+    v_fmac_f32 of two of them, or anything else).  This rule is the Winograd transform's: check(text, shared_sum=False) leaves it
+    out for a stream that has no such sums (the ConvTranspose kernel; its v_sub_f32 are the split's).
+Used by tests/test_asm_lint.py, tests/test_asm_lint_convt.py (CPU) and runnable by hand:  lint_wino_asm.py [--no-shared-sum] FILE.s
 """
 import re
 import sys
@@ -112,7 +114,7 @@ def loop_bodies(lines):
     return bodies
 
 
-def replay(stream, errors, where, prime=()):
+def replay(stream, errors, where, prime=(), shared_sum=True):
     vm, lg = [], []                 # outstanding (dst regs, text) in issue order
     valu_age = {}                   # reg -> wait states since a VALU wrote it
     mfma_age = {}                   # reg -> wait states since an MFMA wrote it
@@ -187,7 +189,7 @@ def replay(stream, errors, where, prime=()):
             errors.append(f"{where}: `{text}` directly behind the write of M0")
         if kind == "readlane" and any(valu_age.get(r, 99) < 1 for r in src):
             errors.append(f"{where}: `{text}` directly behind the VALU write of its source")
-        if op in ("v_add_f32_e32", "v_sub_f32_e32"):
+        if shared_sum and op in ("v_add_f32_e32", "v_sub_f32_e32"):
             hs = [held.get(r) for a in args[1:3] for r in sorted(regs(a))]
             if len(hs) == 2 and any(h and h[0] == "sum" for h in hs):
                 if hs[0] and hs[1] and hs[0] != hs[1]:
@@ -232,19 +234,19 @@ def replay(stream, errors, where, prime=()):
         prev = (kind, data, text)
 
 
-def check(text):
+def check(text, shared_sum=True):
     errors = []
     ks = kernels(text)
     for name, lines in ks.items():
         # whole kernel once (prologue, one trip through everything), then every loop body three times in a row
-        replay(lines, errors, f"{name} (straight line)")
+        replay(lines, errors, f"{name} (straight line)", shared_sum=shared_sum)
         for lab, body in loop_bodies(lines):
-            replay(body * 3, errors, f"{name} loop {lab}")
+            replay(body * 3, errors, f"{name} loop {lab}", shared_sum=shared_sum)
     return errors, len(ks)
 
 
 if __name__ == "__main__":
-    errs, n = check(open(sys.argv[1]).read())
+    errs, n = check(open(sys.argv[-1]).read(), shared_sum="--no-shared-sum" not in sys.argv[1:-1])
     for e in errs[:40]:
         print(e)
     print(f"{n} kernels, {len(errs)} finding(s)")

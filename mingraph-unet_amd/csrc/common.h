@@ -49,6 +49,8 @@ struct Tuning {
                             // instead of the finishing pass of the convolution that writes it (WinoHead below; A/B and tests)
   bool wino_asm = true;     // MGU_WINO_ASM=0: the C++ component-pair kernels instead of their hand-scheduled assembly forms (wino_asm.hip; bitwise
                             // equal results)
+  bool convt_asm = true;    // MGU_CONVT_ASM=0: the C++ ConvTranspose kernel instead of its hand-scheduled assembly form (convt_x3.hip,
+                            // asm/gen_convt_x3.py; bitwise equal results)
   int fwd_groups = 2;       // MGU_FWD_GROUPS: 2 (default) = the eval U-Net forward of a batch of >= 2 images as two half-batch walks, the
                             // second on the context's side stream, so that one half's workgroups fill the CUs while the other half's
                             // kernel drains and its next packet is handed over; 1 = the whole batch on the caller's stream
@@ -123,6 +125,7 @@ enum class ConvKernel {
   HaloF32, HaloBf16Np8, HaloBf16Np4,          // conv3x3_halo_kernel
   TilesF32, TilesBf16,                        // igemm_kernel (KS, out_mode from the descriptor)
   ConvtX3, ConvtBf16f, ConvtX3Dgrad,          // convt2x2_x3_kernel, convt2x2_bf16_kernel, convt2x2_x3_kernel in its gather mode
+  ConvtX3Asm,                                 // mgu_convt_x3_gfx950: the assembly form of convt2x2_x3_kernel's forward (same weight form)
 };
 // dtype: 0 = fp32, 1 = bf16 storage (in / w / out point to bf16, sizes in elements).  head: the caller would like the head-fused
 // finishing pass; the pick returns one of the *Head kernels only if the descriptor and the switches admit it
@@ -143,7 +146,11 @@ inline bool conv_fuses_pool(ConvKernel k) {   // the epilogue can also write the
   return conv_is_wino(k) || (k >= ConvKernel::HaloF32 && k <= ConvKernel::HaloBf16Np4);
 }
 inline bool conv_reads_panel(ConvKernel k) {   // the kernel reads the direct panel d.w (the others read d.wu)
-  return !conv_is_wino(k) && k != ConvKernel::ConvtX3 && k != ConvKernel::ConvtBf16f && k != ConvKernel::ConvtX3Dgrad;
+  return !conv_is_wino(k) && k != ConvKernel::ConvtX3 && k != ConvKernel::ConvtX3Asm && k != ConvKernel::ConvtBf16f &&
+         k != ConvKernel::ConvtX3Dgrad;
+}
+inline bool conv_reads_convt_x3(ConvKernel k) {   // the forward kernels on pack_convt_x3's fragment-ordered pieces
+  return k == ConvKernel::ConvtX3 || k == ConvKernel::ConvtX3Asm;
 }
 // Layer-level forms of the same choice, for the places that size or pack a weight form before a descriptor exists: the layer's
 // shape and switches admit the kernel (the descriptor-level test in pick_conv checks the rest; a caller that holds no such form
@@ -167,6 +174,9 @@ int wino_grid_blocks(const IgemmDesc& d);   // workgroups of the Winograd launch
 // convt_x3.hip: fp32 ConvTranspose2d(k2,s2) on the bf16 matrix cores with exact three-way operand splits (IgemmDesc::wu =
 // fragment-ordered weight pieces)
 hipError_t launch_convt_x3(const IgemmDesc& d, hipStream_t s);
+// its hand-scheduled assembly form (asm/gen_convt_x3.py; bitwise equal results) and the shapes it covers
+bool convt_x3_asm_shape(const IgemmDesc& d);
+hipError_t launch_convt_x3_asm(const IgemmDesc& d, hipStream_t s);
 // convt_bf16.hip: the bf16-storage ConvTranspose2d(k2,s2) on fragment-ordered bf16 weights (IgemmDesc::wu), 16-byte transposed stores
 hipError_t launch_convt_bf16f(const IgemmDesc& d, hipStream_t s);
 // the same kernel as the layer's data gradient (KS = 2 gather descriptors whose d.wu holds pack_convt_x3's data-gradient form)

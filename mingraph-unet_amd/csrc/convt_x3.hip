@@ -20,9 +20,13 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <mutex>
 #include <type_traits>
 
 #include "common.h"
+
+extern "C" const unsigned char mgu_convt_x3_hsaco[];   // asm/gen_convt_x3.py, assembled and embedded by the Makefile
+extern "C" const unsigned mgu_convt_x3_hsaco_len;
 
 namespace mgu {
 
@@ -253,6 +257,72 @@ hipError_t launch_convt_x3_dgrad(const IgemmDesc& d, hipStream_t s) {
     hipLaunchKernelGGL((convt2x2_x3_kernel<1, 1>), dim3(chunk * 8), dim3(256), 0, s, d.in, d.ldin, reinterpret_cast<const uint16_t*>(d.wu),
                        (const float*)nullptr, d.out, d.M, d.H, d.W, d.Cp, d.N, d.ldout, d.coff, d.Hout, d.Wout, ntn, nb);
   return hipGetLastError();
+}
+
+// ---- the hand-scheduled assembly form of convt2x2_x3_kernel<0, 2> (asm/gen_convt_x3.py: mgu_convt_x3_gfx950) ------------------------
+// Same weight form, same arithmetic in the same order: bitwise equal outputs (tests/test_gpu_convt_asm.py).  Everything it does not
+// cover stays on the C++ kernel above, which is also the data-gradient kernel.
+namespace {
+struct ConvtAsmArgs {         // kernarg segment of mgu_convt_x3_gfx950 (asm/gen_convt_x3.py: emit_prologue)
+  const float* in;            //   0
+  const void* wx;             //   8
+  float* out;                 //  16  d.out + d.coff
+  const float* shift;         //  24  may be null
+  int W, ldin, ldout, Cin;    //  32
+  int Cout, nk, ntn, nblocks; //  48
+  int per_xcd, Wout;          //  64
+  unsigned mg_ntn, mg_w;      //  72  floor(2^32 / d) (0xffffffff for d == 1)
+  unsigned mg_cout, pad;      //  80
+};
+static_assert(sizeof(ConvtAsmArgs) == 88, "kernarg layout of mgu_convt_x3_gfx950");
+unsigned magic(unsigned d) { return d <= 1 ? 0xffffffffu : (unsigned)((1ull << 32) / d); }
+std::mutex g_mu;
+hipModule_t g_mod[64] = {};
+hipFunction_t g_fn[64] = {};   // per device, written once under g_mu
+}  // namespace
+
+// (pick_conv has checked convt_x3_applicable: fp32, forward, Cin % 32 == 0, Cout % 32 == 0, ldin % 4 == 0, no scale / ReLU)
+bool convt_x3_asm_shape(const IgemmDesc& d) {
+  if ((d.M & 127) || (d.Cp & 31) || (d.N & 127) || d.Hout != 2 * d.H || d.Wout != 2 * d.W) return false;
+  if ((d.ldin & 3) || (d.ldout & 3) || (d.coff & 3)) return false;
+  // the kernel addresses a tile's input rows and output pixels in 32-bit BYTES relative to the tile's first, and its output pixel
+  // index 4 m - 2 x in 32 bits
+  if (4l * d.M >= (1l << 31) || 128l * d.ldin * 4 >= (1l << 31) || (9l * 128 + 8l * d.Wout) * d.ldout * 4 >= (1l << 31)) return false;
+  // No layer shape is kept back: in the rocprofv3 kernel traces of the headline step (profiles/convt_asm_ab.txt) every one of the four
+  // ConvTranspose shapes is faster on the assembly kernel -- whole batch on one stream, C++ -> assembly: 53.4 -> 44.4, 58.9 -> 48.4,
+  // 74.5 -> 65.8, 100.8 -> 84.9 us (dec0.up .. dec3.up); as two half-batch groups on two streams, medians of two traces each:
+  // 59.4 -> 45.0, 64.6 -> 61.8, 101.5 -> 61.3, 95.4 -> 63.4 us.  A shape that measures slower belongs here, with its numbers.
+  return true;
+}
+
+hipError_t launch_convt_x3_asm(const IgemmDesc& d, hipStream_t s) {
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
+  hipFunction_t fn;
+  {
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (!g_mod[dev]) {
+      e = hipModuleLoadData(&g_mod[dev], mgu_convt_x3_hsaco);
+      if (e != hipSuccess) return e;
+    }
+    if (!g_fn[dev]) {
+      e = hipModuleGetFunction(&g_fn[dev], g_mod[dev], "mgu_convt_x3_gfx950");
+      if (e != hipSuccess) return e;
+    }
+    fn = g_fn[dev];
+  }
+  ConvtAsmArgs a;
+  a.in = d.in, a.wx = d.wu, a.out = d.out + d.coff, a.shift = d.shift;
+  a.W = d.W, a.ldin = d.ldin, a.ldout = d.ldout, a.Cin = d.Cp;
+  a.Cout = d.ct_cout, a.nk = d.Cp >> 5, a.ntn = d.N >> 7, a.nblocks = (d.M >> 7) * a.ntn;
+  a.per_xcd = (a.nblocks + 7) / 8, a.Wout = d.Wout;
+  a.mg_ntn = magic((unsigned)a.ntn), a.mg_w = magic((unsigned)d.W);
+  a.mg_cout = magic((unsigned)d.ct_cout), a.pad = 0;
+  size_t sz = sizeof(a);
+  void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
+  return hipModuleLaunchKernel(fn, (unsigned)(8 * a.per_xcd), 1, 1, 256, 1, 1, 0, s, nullptr, extra);
 }
 
 hipError_t launch_convt_x3(const IgemmDesc& d, hipStream_t s) {

@@ -139,6 +139,7 @@ struct mgu_ctx {
   // caller's stream; created on first use
   hipStream_t fwd_stream = nullptr;
   hipEvent_t fwd_ev[2] = {nullptr, nullptr};
+  int64_t convt_asm_launches = 0;   // ConvTranspose launches on mgu_convt_x3_gfx950 so far (mgu_convt_asm_launches)
   int panel_packs = 0;   // direct panels run_layer has packed on first use so far (a grouped forward orders its second group after one)
 };
 

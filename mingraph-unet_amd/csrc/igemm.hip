@@ -815,7 +815,11 @@ ConvKernel pick_conv(const IgemmDesc& d, int dtype, const WinoHead* head) {
     if (np) return np == 8 ? K::HaloBf16Np8 : K::HaloBf16Np4;
     return d.KS == 3 || d.KS == 1 ? K::TilesBf16 : K::None;
   }
-  if (d.out_mode == 1) return d.KS != 1 ? K::None : convt_x3_applicable(d) ? K::ConvtX3 : K::TilesF32;
+  if (d.out_mode == 1) {
+    if (d.KS != 1) return K::None;
+    if (!convt_x3_applicable(d)) return K::TilesF32;
+    return tun(d).convt_asm && convt_x3_asm_shape(d) ? K::ConvtX3Asm : K::ConvtX3;
+  }
   if (convt_x3_dgrad_applicable(d)) return K::ConvtX3Dgrad;
   if (wino_applicable(d)) {
     const Tuning& t = tun(d);
@@ -848,7 +852,7 @@ const char* conv_kernel_name(ConvKernel k, const IgemmDesc& d) {
     case ConvKernel::HaloF32: return "conv3x3_halo_kernel<f32>";
     case ConvKernel::HaloBf16Np8: case ConvKernel::HaloBf16Np4: return "conv3x3_halo_kernel<bf16>";
     case ConvKernel::TilesBf16: return d.out_mode == 1 ? "igemm_kernel<bf16> (ConvTranspose)" : "igemm_kernel<bf16>";
-    case ConvKernel::ConvtX3: return "convt2x2_x3_kernel";
+    case ConvKernel::ConvtX3: case ConvKernel::ConvtX3Asm: return "convt2x2_x3_kernel";   // (the assembly form counts with its C++ twin)
     case ConvKernel::ConvtBf16f: return "convt2x2_bf16_kernel";
     case ConvKernel::ConvtX3Dgrad: return "convt2x2_x3_kernel<dgrad>";
     case ConvKernel::TilesF32: case ConvKernel::None: break;
@@ -877,7 +881,7 @@ ConvCost conv_cost(ConvKernel k, const IgemmDesc& d) {
   switch (k) {
     case ConvKernel::WinoF32Wide: case ConvKernel::WinoF32Narrow:
       return {2.0 * (d.M / (d.H * d.W)) * ((d.H + 1) / 2) * ((d.W + 1) / 2) * 16.0 * d.Cp * d.N, 0};
-    case ConvKernel::ConvtX3: case ConvKernel::ConvtX3Dgrad: return {6.0 * direct, 1};
+    case ConvKernel::ConvtX3: case ConvKernel::ConvtX3Asm: case ConvKernel::ConvtX3Dgrad: return {6.0 * direct, 1};
     case ConvKernel::HaloBf16Np8: case ConvKernel::HaloBf16Np4: case ConvKernel::TilesBf16: case ConvKernel::ConvtBf16f: return {direct, 1};
     case ConvKernel::HaloF32: case ConvKernel::TilesF32: case ConvKernel::None: return {direct, 0};
     default:   // the three-piece Winograd kernels
@@ -913,6 +917,7 @@ hipError_t launch_conv(const IgemmDesc& d, ConvKernel k, int dtype, hipStream_t 
       if (d.KS == 3) return launch_tiles<__bf16, 3, 0>(d, s);
       return launch_tiles<__bf16, 1, 0>(d, s);
     case ConvKernel::ConvtX3: return launch_convt_x3(d, s);
+    case ConvKernel::ConvtX3Asm: return launch_convt_x3_asm(d, s);
     case ConvKernel::ConvtBf16f: return launch_convt_bf16f(d, s);
     case ConvKernel::ConvtX3Dgrad: return launch_convt_x3_dgrad(d, s);
     case ConvKernel::None: break;

@@ -115,6 +115,7 @@ int mgu_create(int device_id, mgu_ctx** out) {
   t.wino_dgrad = !flag("MGU_NO_WINO_DGRAD");
   t.gat_fused = !flag("MGU_NO_GAT_FUSED");
   t.wino_asm = num("MGU_WINO_ASM", 1) > 0;
+  t.convt_asm = num("MGU_CONVT_ASM", 1) > 0;
   t.head_fused = num("MGU_HEAD_FUSED", 1) > 0;
   t.fwd_groups = num("MGU_FWD_GROUPS", t.fwd_groups) >= 2 ? 2 : 1;
   t.lovasz_passes = num("MGU_LOVASZ_PASSES", t.lovasz_passes) == 3 ? 3 : 4;
@@ -447,6 +448,7 @@ int mgud::run_layer(mgu_ctx* c, const Layer& L, const ConvReq& q, hipStream_t s,
   const ConvCost cost = conv_cost(k, d);
   ProfScope ps(c, s, conv_kernel_name(k, d), alg, cost.mfma, cost.pipe);
   HIPCHK(c, launch_conv(d, k, c->dtype, s, head));
+  c->convt_asm_launches += k == ConvKernel::ConvtX3Asm;
   return MGU_OK;
 }
 
@@ -786,9 +788,10 @@ int mgu_conv_transpose2x2_nhwc(mgu_ctx* c, const void* in_dev, int B, int H, int
     d.shift = U.shift;
   }
   const ConvKernel k = pick_conv(d, 0);
-  if (k == ConvKernel::ConvtX3) HIPCHK(c, launch_pack_one(pack_convt_x3((const float*)w_dev, U.wu, Cin, Cout, 0), s));
+  if (conv_reads_convt_x3(k)) HIPCHK(c, launch_pack_one(pack_convt_x3((const float*)w_dev, U.wu, Cin, Cout, 0), s));
   ProfScope ps(c, s, conv_kernel_name(k, d));
   HIPCHK(c, launch_conv(d, k, 0, s));
+  c->convt_asm_launches += k == ConvKernel::ConvtX3Asm;
   return MGU_OK;
 }
 
@@ -869,6 +872,8 @@ int mgu_profile_read_kernels(mgu_ctx* c, mgu_kernel_stat* out, int cap, int* n_o
   c->ev_used = 0;   // a read consumes the records: with profiling left on, the next window starts from an empty table
   return MGU_OK;
 }
+
+int64_t mgu_convt_asm_launches(mgu_ctx* c) { return c ? c->convt_asm_launches : 0; }
 
 int mgu_profile_read(mgu_ctx* c, double* conv_ms, int* conv_launches, double* total_ms) {
   if (!c) return MGU_ERR_INVALID;
