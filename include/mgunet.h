@@ -840,6 +840,86 @@ int mgu_patch_smooth_mean_u8(mgu_ctx* ctx, const uint8_t* rgb_dev, int B, int H,
 int mgu_refine_probs(mgu_ctx* ctx, const float* src_dev, int is_prob, const uint8_t* guide_dev, int B, int H, int W, int C, int G, int radius,
                      const int32_t* space_lut, const int32_t* range_lut, int shift, int iterations, float* probs_dev, int64_t* labels_dev,
                      float* conf_dev, int64_t* changed_dev, void* hip_stream);
+/* ---- superpixel graphs (csrc/superpixels.hip) ------------------------------------------------------------------
+ * Per image of a uint8 batch: an over-segmentation, its region adjacency graph as a CSR, a node-feature table and the means of feature
+ * maps over the regions.  The reference has none of this (its region graph is a fully connected placeholder): what follows is THIS
+ * BUILD'S DEFINITION, integers throughout, bitwise equal to tests/superpixels_oracle.py and from run to run.  No entry point
+ * synchronises with the host; scratch comes from the context; MGU_ERR_INVALID is returned before anything is launched or written;
+ * B == 0 is MGU_OK with nothing touched (the pointers may then be NULL).  B <= 65535, B*H*W < 2^31 everywhere.
+ *
+ * Colour.  Three HOST tables (mgunet.lab_tables(); the context keeps a device copy and refreshes it when their contents change):
+ * lin_host uint16[256] = rint(4095 srgb_to_linear(v / 255)); m_host int32[9], row-major sRGB -> XYZ (D65) with every row scaled to
+ * sum to exactly 4096; f_host uint16[4096] = rint(1024 f(t / 4095)) with the CIELAB f.  Accepted: lin <= 4095, m >= 0 with rows
+ * summing to 4096, f <= 1024.  Per pixel, in int32:
+ *   xyz_c = (m[c][0] lin[r] + m[c][1] lin[g] + m[c][2] lin[b] + 2048) >> 12                      in 0..4095
+ *   L = (116 f[y] - 16384 + 128) >> 8,  a = (500 (f[x] - f[y]) + 128) >> 8,  b = (200 (f[y] - f[z]) + 128) >> 8
+ * in quarter Lab units; >> of a negative value is an arithmetic shift (floor).
+ *
+ * mgu_slic_labels: integer SLIC in the gSLIC formulation.  rgb_dev (B,H,W,3) contiguous uint8; step S in 4..128, mq = round(4 m) in
+ * 1..1024 (m: the compactness in Lab units), passes T in 1..32.  gx = ceil(W / S), gy = ceil(H / S); centre k = i gx + j starts at
+ * (min(j S + S/2, W-1), min(i S + S/2, H-1)) with that pixel's Lab.  An assignment pass gives pixel (x, y), home cell (y / S, x / S),
+ * to the centre of the up to nine cells (i + di, j + dj), di, dj in {-1, 0, 1}, inside the grid that minimises
+ *   D = (dL^2 + da^2 + db^2) S^2 + mq^2 (dx^2 + dy^2)        int64; |dx|, |dy| < 3 S, so D < 2^39
+ * against the centre's current integer [x, y, L, a, b]; an equal D goes to the smaller k.  A centre update sets each of the five to
+ * floor((2 sum + n) / (2 n)) over the n pixels just assigned (floor, not truncation: the sums of a and b are negative on green and
+ * blue images); n == 0 keeps the centre.  T passes with T - 1 updates in between; the labels of pass T are the output.
+ *   raw_labels_dev  int32 (B,H,W) in [0, gx gy)
+ *   centres_dev     optional int32 (B, gx gy, 6): [x, y, L, a, b, n] as the last pass read them, n = the pixels of the update that made
+ *                   them (0 for a centre that was kept, and everywhere when T == 1)
+ * Launches: 1 (Lab, packed 8 bytes per pixel) + 1 (centres) + T (assignment: a 32 x 32 tile per workgroup, its centres and the sums
+ * of the next update in LDS, lanes that share a centre combined before the LDS atomics, six int32 atomics per centre and tile to
+ * global memory; the last pass writes the label map instead) + T - 1 (update) = 2 T + 1, whatever B and the contents.  Scratch:
+ * 8 bytes per pixel + 48 per centre.
+ *
+ * mgu_regions_connect: raw_labels_dev int32 (B,H,W), values in [0, 2^31 - 2], e.g. mgu_slic_labels' output.  The 4-connected
+ * same-value components become regions (images never join; objects.hip's labelling passes).  Then `rounds` (0..8) merge rounds with
+ * min_area (>= 0): at the start of a round a region is small if its area < min_area; each small region merges into the 4-adjacent
+ * region of area >= min_area that shares the most pixel edges with it (a pixel edge: a horizontally or vertically adjacent pixel pair
+ * with one pixel in each region), ties to the one whose first pixel comes first in raster order; a small region without such a
+ * neighbour stays.  All merges of a round are decided from its starting state and applied together (small into large only: no
+ * chains); the regions are renumbered after every round.
+ *   labels_dev  int32 (B,H,W): every pixel in a region 0..n_b-1 of its image, numbered in raster order of the region's first pixel
+ *   counts_dev  int64 (B), offsets_dev int64 (B+1): as mgu_connected_components writes them; batch-wide node = offsets[b] + label
+ * Launches: 10 + 9 rounds, fills: 1 + 3 rounds, whatever B, the contents and whether a round merges anything.  Scratch: about 76 bytes
+ * per pixel.  An output overlapping raw_labels_dev or another output is MGU_ERR_INVALID.  H*W == 0 with B > 0: counts and offsets 0.
+ *
+ * mgu_regions_adjacency: any int32 label map with offsets (labels < 0 or >= n_b take no part: a mgu_connected_components output
+ * works after subtracting 1).  Nodes u != v of one image are adjacent when a pixel edge joins them; the weight is the number of such
+ * pixel edges.  Both directions are written, rows by batch-wide node index, columns ASCENDING inside a row, no self loops; a row may
+ * be empty.  int32 indices: what mgu_gat_layer_forward* consumes.
+ *   rowptr_dev  int32 (node_capacity + 1): every entry is written; the true prefix sums, also on overflow
+ *   col_dev, border_dev  int32 (edge_capacity): entries [0, min(edges, edge_capacity)); nothing is written past a capacity
+ *   status_dev  int32, OR-ed (the caller clears it): 1 = more directed edges than edge_capacity (the surplus is dropped); 2 = an
+ *               image's nodes pass node_capacity (offsets[b+1] > node_capacity): that image contributes nothing
+ * Construction: objects_common.h's pair hash table (keyed row << 32 | column) and its scan / pour / rank kernels, shared with
+ * mgu_object_overlaps.  6 launches and 2 fills.  Regions of mgu_regions_connect are connected, so their graph is planar: at most
+ * 6 N - 12 directed edges for N >= 3 nodes.  B*H*W < 2^29, capacities < 2^31 - 1.  Scratch: up to 144 bytes per pixel.
+ *
+ * mgu_regions_features_u8: per node, integer atomics give area, sum x, sum y and the sums of the quarter-unit L, a, b above; then one
+ * IEEE double expression per column, cast to fp32 once, into feat_dev (node_capacity, 8):
+ *   [sum L / (400 area), sum a / (512 area), sum b / (512 area), (2 sum x + area) / (2 area W), (2 sum y + area) / (2 area H),
+ *    area / (H W), 0, 0]
+ * (integer numerators and denominators, each converted to double exactly; columns 6, 7 pad to the GAT's Fin % 4 == 0).  Rows of no
+ * node, or of a node without a pixel, are zero.  stats_dev: optional int64 (node_capacity, 6) [area, sum x, sum y, sum L, sum a,
+ * sum b].  Nodes of an image whose nodes pass node_capacity are skipped.  3 launches.
+ *
+ * mgu_regions_pool_nhwc: the mean over every region of channels [c_off, c_off + D) of feat_dev fp32 (B,H,W,ld) (1 <= D <= 4096,
+ * c_off + D <= ld).  Each value adds q = round_half_even(clamp(v, -65536, 65536) * 2^20) (NaN -> 0; the product is exact in fp32) to
+ * an int64 sum with integer atomics (exact while the region's sum of |v| stays below 2^43); out_dev (node_capacity, D) fp32 =
+ * (float)((double)sum / (double)area * 2^-20), 0 for a row without pixels.  Order-free and bitwise reproducible; within
+ * 2^-21 + 2^-24 |mean| of the float64 mean of the unquantised values.  3 launches.  No backward. */
+int mgu_slic_labels(mgu_ctx* ctx, const uint8_t* rgb_dev, int B, int H, int W, int step, int mq, int passes, const uint16_t* lin_host,
+                    const int32_t* m_host, const uint16_t* f_host, int32_t* raw_labels_dev, int32_t* centres_dev, void* hip_stream);
+int mgu_regions_connect(mgu_ctx* ctx, const int32_t* raw_labels_dev, int B, int H, int W, int min_area, int rounds, int32_t* labels_dev,
+                        int64_t* counts_dev, int64_t* offsets_dev, void* hip_stream);
+int mgu_regions_adjacency(mgu_ctx* ctx, const int32_t* labels_dev, const int64_t* offsets_dev, int B, int H, int W, int64_t node_capacity,
+                          int64_t edge_capacity, int32_t* rowptr_dev, int32_t* col_dev, int32_t* border_dev, int32_t* status_dev,
+                          void* hip_stream);
+int mgu_regions_features_u8(mgu_ctx* ctx, const uint8_t* rgb_dev, const int32_t* labels_dev, const int64_t* offsets_dev, int B, int H, int W,
+                            const uint16_t* lin_host, const int32_t* m_host, const uint16_t* f_host, int64_t node_capacity, float* feat_dev,
+                            int64_t* stats_dev, void* hip_stream);
+int mgu_regions_pool_nhwc(mgu_ctx* ctx, const float* feat_dev, int ld, int c_off, int D, const int32_t* labels_dev, const int64_t* offsets_dev,
+                          int B, int H, int W, int64_t node_capacity, float* out_dev, void* hip_stream);
 /* ---- graph-branch inputs for a whole batch: the node features scripts/graph_refinement.py:72-113 defines and the patch labels
  *      scripts/train_end_to_end.py:340 describes (the training script draws both from torch's RNG, :326 / :342) -----------------------
  * Node features.  rgb (B,H,W,3) uint8 -> rows (B*nph*npw, ld_out) fp32, nph = ceil(H / patch), npw = ceil(W / patch), patches zero

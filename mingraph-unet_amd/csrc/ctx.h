@@ -98,6 +98,8 @@ struct mgu_ctx {
                             // class planes, their distance transform and the site column distances of boundary.hip; the 16-bit
                             // plane sets between the iterations of refine.hip
   size_t objws_bytes = 0;
+  void* labtab = nullptr;            // device copy of the fixed-point CIELAB tables (superpixels.hip) and the host bytes it was made from:
+  std::vector<unsigned char> labtab_host;   // refreshed when a call brings other contents
   int in_ch = 0, ncls = 0, feat = 0, depth = 0, dtype = 0, Cp0 = 0;
   std::vector<Layer> layers;  // enc[i].conv1, enc[i].conv2 ..., bott.conv1, bott.conv2, dec[b].up, dec[b].conv1, dec[b].conv2 ..., final
   std::vector<Block> enc, dec;   // encoder blocks shallow -> deep (level i), decoder blocks deep -> shallow (level depth-1-b)

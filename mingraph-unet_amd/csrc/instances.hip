@@ -21,47 +21,8 @@ namespace {
 
 constexpr int IN_THREADS = 256;
 constexpr int PIXG = 4;                         // pixels per lane in the counting pass
-constexpr int ROWCHUNK = 4 * IN_THREADS;        // degree scan: 1024 consecutive rows per workgroup
-constexpr unsigned long long EMPTY = ~0ull;     // a free slot; no pair has this key (both indices stay below 2^31)
-
-struct PairTable {
-  unsigned long long* keys;   // slots
-  unsigned* cnt;              // slots: pixels of the pair (B*H*W < 2^31, so 32 bits hold any count)
-  int* deg;                   // rows: distinct GT objects met by a predicted object
-  unsigned slots;
-  int64_t rows;
-};
-
-// the slot a key starts probing at: a 64-bit finaliser, then a multiply-shift onto [0, slots)
-__device__ __forceinline__ unsigned home_slot(unsigned long long k, unsigned slots) {
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdull;
-  k ^= k >> 33;
-  k *= 0xc4ceb9fe1a85ec53ull;
-  k ^= k >> 33;
-  return (unsigned)(((k & 0xffffffffull) * slots) >> 32);
-}
-
-// add c pixels to the pair `key`: linear probing; the table has more than twice as many slots as there can be pairs, so a free slot
-// is always met (the probe count is bounded all the same)
-__device__ __forceinline__ void pair_add(const PairTable& t, unsigned long long key, unsigned c) {
-  unsigned s = home_slot(key, t.slots);
-  for (unsigned probe = 0; probe < t.slots; ++probe) {
-    unsigned long long k = __hip_atomic_load(&t.keys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (k == EMPTY) {
-      k = atomicCAS(&t.keys[s], EMPTY, key);
-      if (k == EMPTY) {
-        atomicAdd(&t.deg[key >> 32], 1);
-        k = key;
-      }
-    }
-    if (k == key) {
-      atomicAdd(&t.cnt[s], c);
-      return;
-    }
-    s = s + 1 == t.slots ? 0 : s + 1;
-  }
-}
+constexpr int ROWCHUNK = PAIR_ROWCHUNK;         // the pair table, its probing and its degree / pour / place kernels: objects_common.h
+constexpr unsigned long long EMPTY = PAIR_EMPTY;
 
 // (1) one lane per PIXG consecutive pixels of the flat (B, H*W) maps
 template <bool VEC>
@@ -120,18 +81,6 @@ __global__ __launch_bounds__(IN_THREADS) void overlap_count_kernel(const int* __
   }
 }
 
-// (2a) degrees per chunk of ROWCHUNK rows; rows past the table's (no object can have them) have degree 0
-__global__ __launch_bounds__(IN_THREADS) void degree_count_kernel(const int* __restrict__ deg, int64_t rows, int* __restrict__ csum) {
-  __shared__ int sh[4];
-  const int64_t i0 = (int64_t)blockIdx.x * ROWCHUNK + 4 * threadIdx.x;
-  int c = 0;
-  for (int k = 0; k < 4; ++k)
-    if (i0 + k < rows) c += deg[i0 + k];
-  int total;
-  block_exclusive_scan(c, sh, &total);
-  if (threadIdx.x == 0) csum[blockIdx.x] = total;
-}
-
 // (2b) one workgroup: exclusive scan of the chunk sums; the number of pairs; the status bits
 __global__ __launch_bounds__(SCAN_THREADS) void degree_scan_kernel(const int* __restrict__ csum, int64_t nch, long long* __restrict__ choff,
                                                                    long long* __restrict__ total_out, int64_t pair_cap, int B,
@@ -147,52 +96,6 @@ __global__ __launch_bounds__(SCAN_THREADS) void degree_scan_kernel(const int* __
     if (pairs > pair_cap) bits |= 1;
   }
   if (bits) atomicOr(status, bits);
-}
-
-// (2c) pair_ptr[i], i in [0, pcap]: the chunk's offset plus the exclusive scan inside the chunk
-__global__ __launch_bounds__(IN_THREADS) void degree_write_kernel(const int* __restrict__ deg, int64_t rows, int64_t nptr,
-                                                                  const long long* __restrict__ choff, long long* __restrict__ pair_ptr) {
-  __shared__ int sh[4];
-  const int64_t i0 = (int64_t)blockIdx.x * ROWCHUNK + 4 * threadIdx.x;
-  int d[4], c = 0;
-  for (int k = 0; k < 4; ++k) {
-    d[k] = i0 + k < rows ? deg[i0 + k] : 0;
-    c += d[k];
-  }
-  int total;
-  long long at = choff[blockIdx.x] + block_exclusive_scan(c, sh, &total);
-  for (int k = 0; k < 4; ++k) {
-    if (i0 + k < nptr) pair_ptr[i0 + k] = at;
-    at += d[k];
-  }
-}
-
-// (3) every occupied slot takes the next free place of its row (the row's degree counts down: its final value is 0)
-__global__ __launch_bounds__(IN_THREADS) void pair_pour_kernel(PairTable t, const long long* __restrict__ pair_ptr, int* __restrict__ tp,
-                                                               unsigned* __restrict__ tg, unsigned* __restrict__ tc) {
-  for (int64_t s = (int64_t)blockIdx.x * IN_THREADS + threadIdx.x; s < t.slots; s += (int64_t)gridDim.x * IN_THREADS) {
-    const unsigned long long k = t.keys[s];
-    if (k == EMPTY) continue;
-    const int p = (int)(k >> 32);
-    const long long e = pair_ptr[p] + atomicSub(&t.deg[p], 1) - 1;
-    tp[e] = p, tg[e] = (unsigned)k, tc[e] = t.cnt[s];
-  }
-}
-
-// (4) entry e of row p goes to the row's place number |{entries of the row with a smaller GT index}|; places past pair_cap are dropped
-__global__ __launch_bounds__(IN_THREADS) void pair_place_kernel(const long long* __restrict__ total, const long long* __restrict__ pair_ptr,
-                                                                const int* __restrict__ tp, const unsigned* __restrict__ tg,
-                                                                const unsigned* __restrict__ tc, int64_t pair_cap, long long* __restrict__ pair_gt,
-                                                                long long* __restrict__ pair_inter) {
-  const long long n = *total;
-  for (long long e = (long long)blockIdx.x * IN_THREADS + threadIdx.x; e < n; e += (long long)gridDim.x * IN_THREADS) {
-    const int p = tp[e];
-    const unsigned g = tg[e];
-    const long long r0 = pair_ptr[p], r1 = pair_ptr[p + 1];
-    long long at = r0;
-    for (long long j = r0; j < r1; ++j) at += tg[j] < g;
-    if (at < pair_cap) pair_gt[at] = g, pair_inter[at] = tc[e];
-  }
 }
 
 // ---- confidence-ordered greedy matching on mask IoU ------------------------------------------------------------------------------
@@ -377,14 +280,14 @@ int mgu_object_overlaps(mgu_ctx* c, const int32_t* gt_labels_dev, const int64_t*
       hipLaunchKernelGGL(overlap_count_kernel<false>, dim3(blocks), dim3(IN_THREADS), 0, s, gt_labels_dev, pred_labels_dev, n, HW, goff, poff,
                          gt_capacity, pred_capacity, t);
   }
-  hipLaunchKernelGGL(degree_count_kernel, dim3((unsigned)nch), dim3(IN_THREADS), 0, s, t.deg, t.rows, csum);
+  hipLaunchKernelGGL(degree_count_kernel<0>, dim3((unsigned)nch), dim3(IN_THREADS), 0, s, t.deg, t.rows, csum);
   hipLaunchKernelGGL(degree_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, s, csum, nch, choff, total, pair_capacity, B, goff, poff, gt_capacity,
                      pred_capacity, (int*)status_dev);
-  hipLaunchKernelGGL(degree_write_kernel, dim3((unsigned)nch), dim3(IN_THREADS), 0, s, t.deg, t.rows, nptr, choff, (long long*)pair_ptr_dev);
+  hipLaunchKernelGGL(degree_write_kernel<long long>, dim3((unsigned)nch), dim3(IN_THREADS), 0, s, t.deg, t.rows, nptr, choff, (long long*)pair_ptr_dev);
   const unsigned slotblocks = grid_for(t.slots, IN_THREADS, 4096);
-  hipLaunchKernelGGL(pair_pour_kernel, dim3(slotblocks), dim3(IN_THREADS), 0, s, t, (const long long*)pair_ptr_dev, tp, tg, tc);
+  hipLaunchKernelGGL(pair_pour_kernel<long long>, dim3(slotblocks), dim3(IN_THREADS), 0, s, t, (const long long*)pair_ptr_dev, tp, tg, tc);
   const unsigned pairblocks = grid_for(n + 1, IN_THREADS, 4096);   // the pairs are counted on the device: at most n
-  hipLaunchKernelGGL(pair_place_kernel, dim3(pairblocks), dim3(IN_THREADS), 0, s, total, (const long long*)pair_ptr_dev, tp, tg, tc, pair_capacity,
+  hipLaunchKernelGGL((pair_place_kernel<long long, long long>), dim3(pairblocks), dim3(IN_THREADS), 0, s, total, (const long long*)pair_ptr_dev, tp, tg, tc, pair_capacity,
                      (long long*)pair_gt_dev, (long long*)pair_inter_dev);
   HIPCHK(c, hipGetLastError());
   return MGU_OK;

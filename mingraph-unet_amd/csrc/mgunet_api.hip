@@ -139,6 +139,7 @@ void mgu_destroy(mgu_ctx* c) {
   if (c->wuws) (void)hipFree(c->wuws);
   if (c->ncws) (void)hipFree(c->ncws);
   if (c->objws) (void)hipFree(c->objws);
+  if (c->labtab) (void)hipFree(c->labtab);
   if (c->lossws) (void)hipFree(c->lossws);
   if (c->imgws) (void)hipFree(c->imgws);
   gat_destroy(c);

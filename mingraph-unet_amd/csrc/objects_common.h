@@ -1,6 +1,7 @@
 // Helpers shared by the object-level kernel files (objects.hip, shapes.hip, split.hip, instances.hip, clean.hip, boundary.hip): each is
 // defined here and nowhere else under csrc/ (tests/test_csrc_helpers.py).  device.h keeps what every kernel file shares.
-//   device: wave_by_key | block_exclusive_scan | chunk_sum_scan | object_index | objects_recorded | pix_key | foreground_class
+//   device: wave_by_key | block_exclusive_scan | chunk_sum_scan | the pair table (PairTable, pair_add, degree / pour / place kernels;
+//           superpixels.hip shares it with instances.hip) | object_index | objects_recorded | pix_key | foreground_class
 //   host:   check_pixel_count | clear_counts | distance_transform, distance_transform_dims (declared here, defined in split.hip)
 #pragma once
 #include <climits>
@@ -80,6 +81,120 @@ __device__ __forceinline__ long long chunk_sum_scan(const int* __restrict__ cnt,
     run += cnt[k];
   }
   return sh[SCAN_THREADS - 1];
+}
+
+// ---- the pair table: (row, column) pairs with a count, poured into a CSR with ascending columns -----------------------------------
+// instances.hip (predicted object x GT object, shared pixels) and superpixels.hip (region x region, shared pixel edges) build their
+// sparse tables the same way: (1) their counting kernel calls pair_add(row << 32 | column, count) into an open-addressing hash table
+// in global scratch (64-bit compare-and-swap insert; the winner bumps the row's degree), (2) degree_count_kernel, a scan kernel of
+// the caller's (chunk_sum_scan plus its own status bits) and degree_write_kernel turn the degrees into the row pointers, (3)
+// pair_pour_kernel pours the occupied slots into their rows in whatever order the atomics land in, (4) pair_place_kernel stores every
+// entry at its rank inside its row (the number of smaller columns).  The slot of a pair varies from run to run; the outputs do not.
+// PTR is the row pointers' type, OUT the type of the column and count arrays.  The kernels are templates so that both files can
+// instantiate them from this one definition.
+constexpr int PAIR_THREADS = 256;
+constexpr int PAIR_ROWCHUNK = 4 * PAIR_THREADS;      // degree scan: 1024 consecutive rows per workgroup
+constexpr unsigned long long PAIR_EMPTY = ~0ull;     // a free slot; no pair has this key (both indices stay below 2^31)
+
+struct PairTable {
+  unsigned long long* keys;   // slots
+  unsigned* cnt;              // slots: the pair's count (B*H*W < 2^31 pixels or 2*B*H*W pixel edges: 32 bits hold any count)
+  int* deg;                   // rows: distinct columns met by a row; nullptr: degrees are not kept (no CSR is built of the table)
+  unsigned slots;
+  int64_t rows;
+};
+
+// the slot a key starts probing at: a 64-bit finaliser, then a multiply-shift onto [0, slots)
+__device__ __forceinline__ unsigned home_slot(unsigned long long k, unsigned slots) {
+  k ^= k >> 33;
+  k *= 0xff51afd7ed558ccdull;
+  k ^= k >> 33;
+  k *= 0xc4ceb9fe1a85ec53ull;
+  k ^= k >> 33;
+  return (unsigned)(((k & 0xffffffffull) * slots) >> 32);
+}
+
+// add c to the pair `key`: linear probing; the table has more than twice as many slots as there can be pairs, so a free slot
+// is always met (the probe count is bounded all the same)
+__device__ __forceinline__ void pair_add(const PairTable& t, unsigned long long key, unsigned c) {
+  unsigned s = home_slot(key, t.slots);
+  for (unsigned probe = 0; probe < t.slots; ++probe) {
+    unsigned long long k = __hip_atomic_load(&t.keys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (k == PAIR_EMPTY) {
+      k = atomicCAS(&t.keys[s], PAIR_EMPTY, key);
+      if (k == PAIR_EMPTY) {
+        if (t.deg) atomicAdd(&t.deg[key >> 32], 1);
+        k = key;
+      }
+    }
+    if (k == key) {
+      atomicAdd(&t.cnt[s], c);
+      return;
+    }
+    s = s + 1 == t.slots ? 0 : s + 1;
+  }
+}
+
+// (2a) degrees per chunk of PAIR_ROWCHUNK rows; rows past the table's (no row can have them) have degree 0
+template <int UNUSED = 0>
+__global__ __launch_bounds__(PAIR_THREADS) void degree_count_kernel(const int* __restrict__ deg, int64_t rows, int* __restrict__ csum) {
+  __shared__ int sh[4];
+  const int64_t i0 = (int64_t)blockIdx.x * PAIR_ROWCHUNK + 4 * threadIdx.x;
+  int c = 0;
+  for (int k = 0; k < 4; ++k)
+    if (i0 + k < rows) c += deg[i0 + k];
+  int total;
+  block_exclusive_scan(c, sh, &total);
+  if (threadIdx.x == 0) csum[blockIdx.x] = total;
+}
+
+// (2c) ptr[i], i in [0, nptr): the chunk's offset plus the exclusive scan inside the chunk
+template <typename PTR>
+__global__ __launch_bounds__(PAIR_THREADS) void degree_write_kernel(const int* __restrict__ deg, int64_t rows, int64_t nptr,
+                                                                    const long long* __restrict__ choff, PTR* __restrict__ ptr) {
+  __shared__ int sh[4];
+  const int64_t i0 = (int64_t)blockIdx.x * PAIR_ROWCHUNK + 4 * threadIdx.x;
+  int d[4], c = 0;
+  for (int k = 0; k < 4; ++k) {
+    d[k] = i0 + k < rows ? deg[i0 + k] : 0;
+    c += d[k];
+  }
+  int total;
+  long long at = choff[blockIdx.x] + block_exclusive_scan(c, sh, &total);
+  for (int k = 0; k < 4; ++k) {
+    if (i0 + k < nptr) ptr[i0 + k] = (PTR)at;
+    at += d[k];
+  }
+}
+
+// (3) every occupied slot takes the next free place of its row (the row's degree counts down: its final value is 0)
+template <typename PTR>
+__global__ __launch_bounds__(PAIR_THREADS) void pair_pour_kernel(PairTable t, const PTR* __restrict__ ptr, int* __restrict__ tp,
+                                                                 unsigned* __restrict__ tg, unsigned* __restrict__ tc) {
+  for (int64_t s = (int64_t)blockIdx.x * PAIR_THREADS + threadIdx.x; s < t.slots; s += (int64_t)gridDim.x * PAIR_THREADS) {
+    const unsigned long long k = t.keys[s];
+    if (k == PAIR_EMPTY) continue;
+    const int p = (int)(k >> 32);
+    const long long e = (long long)ptr[p] + atomicSub(&t.deg[p], 1) - 1;
+    tp[e] = p, tg[e] = (unsigned)k, tc[e] = t.cnt[s];
+  }
+}
+
+// (4) entry e of row p goes to the row's place number |{entries of the row with a smaller column}|; places past cap are dropped
+template <typename PTR, typename OUT>
+__global__ __launch_bounds__(PAIR_THREADS) void pair_place_kernel(const long long* __restrict__ total, const PTR* __restrict__ ptr,
+                                                                  const int* __restrict__ tp, const unsigned* __restrict__ tg,
+                                                                  const unsigned* __restrict__ tc, int64_t cap, OUT* __restrict__ out_col,
+                                                                  OUT* __restrict__ out_cnt) {
+  const long long n = *total;
+  for (long long e = (long long)blockIdx.x * PAIR_THREADS + threadIdx.x; e < n; e += (long long)gridDim.x * PAIR_THREADS) {
+    const int p = tp[e];
+    const unsigned g = tg[e];
+    const long long r0 = ptr[p], r1 = ptr[p + 1];
+    long long at = r0;
+    for (long long j = r0; j < r1; ++j) at += tg[j] < g;
+    if (at < cap) out_col[at] = (OUT)g, out_cnt[at] = (OUT)tc[e];
+  }
 }
 
 // ---- the per-object arrays --------------------------------------------------------------------------------------------------------

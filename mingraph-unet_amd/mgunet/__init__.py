@@ -15,6 +15,7 @@ from .instances import (InstanceEvaluator, OverlapTable, evaluate_instances, ins
 from .boundary import BoundaryEvaluator, BoundaryTables, boundary_metrics, boundary_tables, evaluate_boundaries  # noqa: F401
 from .tiled import predict_tiled, tile_grid, tile_weights  # noqa: F401
 from .refine import EdgeRefiner, bilateral_tables, refine_probs  # noqa: F401
+from .superpixels import SuperpixelGraph, connect_regions, lab_tables, region_adjacency, region_features, region_pool, slic_labels, superpixel_graph  # noqa: F401
 from .graphcut import GraphCut, MultiCut, cut_capacities, cut_energy, cut_energy_multi, graph_cut, graph_cut_multi, label_costs  # noqa: F401
 from .mincut import MinCutRefinement, PatchSegmentPredictor  # noqa: F401
 from .patch_graph import PatchGraphConstructor  # noqa: F401
@@ -23,7 +24,7 @@ from .region import FeatureFusion, region_edge_index, region_fuse, region_mean_p
 from .unet import ConvBlock, DecoderBlock, UNet, UNetDecoder, UNetEncoder  # noqa: F401
 from ._lib import build, lib  # noqa: F401
 
-__all__ = ["TVLoss", "dice_loss", "lovasz_softmax", "FeatureConsistencyLoss", "EllipticalShapeLoss", "ImagePreprocessor", "RandomFlipRotate", "draw_flip_rotate", "pil_rotation_fixed", "EdgeDetector", "HistogramEqualizer", "GaussianSmoother", "gaussian_kernel_q8", "patch_smooth_features_u8",
+__all__ = ["SuperpixelGraph", "connect_regions", "lab_tables", "region_adjacency", "region_features", "region_pool", "slic_labels", "superpixel_graph", "TVLoss", "dice_loss", "lovasz_softmax", "FeatureConsistencyLoss", "EllipticalShapeLoss", "ImagePreprocessor", "RandomFlipRotate", "draw_flip_rotate", "pil_rotation_fixed", "EdgeDetector", "HistogramEqualizer", "GaussianSmoother", "gaussian_kernel_q8", "patch_smooth_features_u8",
            "patch_features_u8", "patch_node_features", "patch_labels", "postprocess_segmentation", "DetectionHead", "FeatureFusion", "region_stage", "region_mean_pool", "region_fuse", "region_edge_index", "MinCutRefinement", "PatchSegmentPredictor", "graph_cut", "cut_capacities", "cut_energy", "GraphCut", "graph_cut_multi", "label_costs", "cut_energy_multi", "MultiCut", "UNet", "UNetEncoder", "UNetDecoder", "ConvBlock", "DecoderBlock", "GATNetwork", "MultiHeadGATLayer",
            "GraphAttentionLayer", "PatchGraphConstructor", "MinGraphUNet", "MinGraphUNetE2E", "segment_batch", "argmax_classes",
            "gat_forward_csr", "shard_batch", "segmentation_metrics", "metrics_from_confusion", "SegmentationEvaluator", "evaluate_segmentation",
