@@ -754,7 +754,8 @@ int mgu_region_map_gather_nhwc(mgu_ctx* ctx, const float* table_dev, int R, int 
  * The reference does these steps on the host with cv2 / PIL / torchvision.  Images are HWC uint8 in device memory.
  * ImagePreprocessor.preprocess (preprocessing/image_preprocessing/image_preprocess.py:26-31, 57-85): [BGR -> RGB | grey -> RGB] ->
  * torchvision Resize on a PIL image = PIL's antialiased BILINEAR resample in 8-bit fixed point (horizontal pass, then vertical, 22-bit
- * coefficients) -> ToTensor (/255) -> Normalize.  mean3 / std3: HOST arrays of 3 floats.  out element (c, y, x) at
+ * coefficients; vertical first where Image.resize does so: an image over 100 times taller than wide whose height shrinks)
+ * -> ToTensor (/255) -> Normalize.  mean3 / std3: HOST arrays of 3 floats.  out element (c, y, x) at
  * out_dev[c*os_c + y*os_h + x*os_w] (fp32): CHW as the reference returns it, or an NHWC slot of a batch. */
 int mgu_preprocess_image_u8(mgu_ctx* ctx, const uint8_t* img_dev, int Hs, int Ws, int channels /* 1 | 3 */, int bgr, int H, int W,
                             const float* mean3, const float* std3, void* out_dev, int64_t os_c, int64_t os_h, int64_t os_w, void* hip_stream);
@@ -781,7 +782,7 @@ int mgu_preprocess_image_u8_aug(mgu_ctx* ctx, const uint8_t* img_dev, int Hs, in
 /* mgu_preprocess_mask_u8 followed by the flip / rotation of the (H, W) label map; out-of-image pixels get mask_fill (not clipped). */
 int mgu_preprocess_mask_u8_aug(mgu_ctx* ctx, const uint8_t* mask_dev, int Hs, int Ws, int H, int W, int num_classes, int flip, const int32_t* fix6,
                                int64_t mask_fill, int64_t* out_dev, void* hip_stream);
-/* EdgeDetector.sobel_edges (preprocessing/graph_feature_processing/edge_detection.py:14-44), kernel size 3: RGB -> grey (14-bit fixed
+/* EdgeDetector.sobel_edges (preprocessing/graph_feature_processing/edge_detection.py:14-44), kernel size 3: RGB -> grey (15-bit fixed
  * point), Sobel x / y with reflect-101 borders, magnitude / max * 255 in double, truncated to uint8.  rgb (H,W,3) -> out (H,W). */
 int mgu_sobel_edges_u8(mgu_ctx* ctx, const uint8_t* rgb_dev, int H, int W, uint8_t* out_dev, void* hip_stream);
 /* HistogramEqualizer.equalize_histogram_rgb (histogram_equalization.py:13-35): RGB -> YUV, equalizeHist on Y, YUV -> RGB. */

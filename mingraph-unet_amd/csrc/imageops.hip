@@ -205,10 +205,10 @@ __global__ __launch_bounds__(256) void equalize_apply_kernel(const uint8_t* __re
 __global__ __launch_bounds__(256) void patch_mean_u8_kernel(const uint8_t* __restrict__ img, int H, int W, int Cc, int patch, int npw, int per_channel,
                                                             float* __restrict__ out) {
   const int pidx = blockIdx.x, py = pidx / npw, px = pidx - py * npw;
-  __shared__ unsigned acc[4];
+  __shared__ unsigned long long acc[4];   // 64 bits: 255 * 4096^2 * 4 channels does not fit 32
   if (threadIdx.x < 4) acc[threadIdx.x] = 0;
   __syncthreads();
-  unsigned s[4] = {0, 0, 0, 0};
+  unsigned long long s[4] = {0, 0, 0, 0};
   for (int i = threadIdx.x; i < patch * patch; i += 256) {
     const int y = py * patch + i / patch, x = px * patch + i % patch;
     if (y < H && x < W)
@@ -281,9 +281,13 @@ namespace mgu {
 int preprocess_resize_u8(mgu_ctx* c, const uint8_t* img_dev, int Hs, int Ws, int channels, int H, int W, hipStream_t s, const uint8_t** out) {
   const bool need_h = W != Ws, need_v = H != Hs;
   const ResampleTable th = need_h ? pil_bilinear_coeffs(Ws, W) : ResampleTable(), tv = need_v ? pil_bilinear_coeffs(Hs, H) : ResampleTable();
-  // scratch: [tables (int)] [horizontal result Hs x W x C] [final H x W x C]
+  // Image.resize shrinks the height of a tall, narrow image first (`self.size[1] > self.size[0] * 100 and size[1] < self.size[1]`):
+  // two ImagingResample calls, vertical then horizontal, each rounding to bytes.  Every other image: horizontal, then vertical.
+  const bool v_first = need_h && need_v && (int64_t)Hs > (int64_t)Ws * 100 && H < Hs;
+  // scratch: [tables (int)] [first pass's result, Hs x W x C or H x Ws x C] [final H x W x C]
   const size_t n_tab = th.bounds.size() + th.kk.size() + tv.bounds.size() + tv.kk.size();
-  const size_t o_tmp = (n_tab * sizeof(int) + 255) / 256 * 256, o_fin = o_tmp + ((size_t)Hs * W * channels + 255) / 256 * 256;
+  const size_t n_tmp = v_first ? (size_t)H * Ws * channels : (size_t)Hs * W * channels;
+  const size_t o_tmp = (n_tab * sizeof(int) + 255) / 256 * 256, o_fin = o_tmp + (n_tmp + 255) / 256 * 256;
   int rc = ensure(c, &c->imgws, &c->imgws_bytes, o_fin + (size_t)H * W * channels + 256);
   if (rc) return rc;
   char* ws = (char*)c->imgws;
@@ -299,19 +303,22 @@ int preprocess_resize_u8(mgu_ctx* c, const uint8_t* img_dev, int Hs, int Ws, int
     HIPCHK(c, hipStreamSynchronize(s));   // `host` is a stack vector: the copy must have left it (tables are tiny; once per image)
   }
   const uint8_t* cur = img_dev;
-  int curW = Ws;
-  if (need_h) {   // horizontal pass first, as ImagingResample
-    uint8_t* tmp = (uint8_t*)(ws + o_tmp);
-    hipLaunchKernelGGL(pil_resample_pass_kernel, dim3(grid_for((int64_t)W * Hs * channels, 256, 256 * 8)), dim3(256), 0, s, cur, tmp, W, Hs, channels,
-                       (int64_t)channels, (int64_t)Ws * channels, (int64_t)channels, (int64_t)W * channels, tab, tab + th.bounds.size(), th.ksize);
-    cur = tmp, curW = W;
-  }
-  if (need_v) {
-    uint8_t* fin = (uint8_t*)(ws + o_fin);
-    const int* tb = tab + th.bounds.size() + th.kk.size();
-    hipLaunchKernelGGL(pil_resample_pass_kernel, dim3(grid_for((int64_t)H * curW * channels, 256, 256 * 8)), dim3(256), 0, s, cur, fin, H, curW, channels,
-                       (int64_t)curW * channels, (int64_t)channels, (int64_t)curW * channels, (int64_t)channels, tb, tb + tv.bounds.size(), tv.ksize);
-    cur = fin;
+  int curH = Hs, curW = Ws;
+  const int n_pass = (need_h ? 1 : 0) + (need_v ? 1 : 0);
+  for (int pass = 0; pass < n_pass; ++pass) {
+    const bool horizontal = need_h && (!need_v || (pass == 0) != v_first);
+    uint8_t* dst = (uint8_t*)(ws + (pass == n_pass - 1 ? o_fin : o_tmp));
+    if (horizontal) {
+      hipLaunchKernelGGL(pil_resample_pass_kernel, dim3(grid_for((int64_t)W * curH * channels, 256, 256 * 8)), dim3(256), 0, s, cur, dst, W, curH, channels,
+                         (int64_t)channels, (int64_t)curW * channels, (int64_t)channels, (int64_t)W * channels, tab, tab + th.bounds.size(), th.ksize);
+      curW = W;
+    } else {
+      const int* tb = tab + th.bounds.size() + th.kk.size();
+      hipLaunchKernelGGL(pil_resample_pass_kernel, dim3(grid_for((int64_t)H * curW * channels, 256, 256 * 8)), dim3(256), 0, s, cur, dst, H, curW, channels,
+                         (int64_t)curW * channels, (int64_t)channels, (int64_t)curW * channels, (int64_t)channels, tb, tb + tv.bounds.size(), tv.ksize);
+      curH = H;
+    }
+    cur = dst;
   }
   *out = cur;
   return MGU_OK;

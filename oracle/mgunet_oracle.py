@@ -717,7 +717,10 @@ def elliptical_shape_loss(segmentation_probs: torch.Tensor = None, object_masks_
 # --------------------------------------------------------------------------------------
 # Input / output pipeline.  cv2 and torchvision are absent, so these restate the library calls of
 # modules that cannot be imported: PIL (present) does the resize torchvision.transforms.Resize delegates to; the cv2 steps
-# follow OpenCV's documented fixed-point implementations.  No reference-generated fixture pins them.
+# follow OpenCV's documented fixed-point implementations.  No reference-generated fixture pins them.  tests/image_io_cases.py holds
+# what can be checked without cv2: Sobel against scipy and an exact integer rule, the resize against PIL itself, and for the colour
+# conversions, equalizeHist and the nearest-neighbour index rule adversarial inputs with the wrong variants each one rejects -- those
+# three remain unverified against the library.
 # --------------------------------------------------------------------------------------
 def preprocess_image(image_u8: np.ndarray, resize_dim, mean, std, bgr: bool = True) -> torch.Tensor:
     """ImagePreprocessor.preprocess, image_preprocess.py:57-85 with the transforms of :26-31: BGR->RGB (or grey -> 3 channels),
