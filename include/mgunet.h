@@ -437,6 +437,44 @@ int mgu_lovasz_softmax_backward(mgu_ctx* ctx, const void* logits_dev, const int6
                                 int accumulate, float* loss_dev, void* hip_stream);
 /* Keys one workgroup ranks per sort pass of the Lovasz kernels (the tests size their segments around it). */
 int mgu_lovasz_tile(void);
+/* Imbalance-aware pixel-wise cross-entropy (the build's own: INTEGRATION.md section S): class weights, label smoothing, the focal
+ * term (Lin et al., ICCV 2017) and hard-pixel mining (bootstrapped cross-entropy, Wu et al. 2016; OHEM) in one loss.  Logits element
+ * (b, c, p) at logits_dev[b*ls_n + c*ls_c + p*ls_p] (fp32, num_classes <= 8), labels (B, HW) int64.  A pixel labelled ignore_index is
+ * not counted; any other label outside [0, num_classes) is never used as an index, makes the loss NaN and is flagged as mgu_dice_loss
+ * flags it (mgu_loss_sync_check).  class_weight_dev: num_classes floats >= 0 on the device, NULL = ones.  Per counted pixel, lp the
+ * fp32 log-softmax and p the softmax:
+ *   focal_gamma == 0:  l = (1 - label_smoothing) w_y (-lp_y) + (label_smoothing / C) sum_c w_c (-lp_c)   [F.cross_entropy per pixel]
+ *   focal_gamma >= 1:  l = w_y (1 - p_y)^focal_gamma (-lp_y), label_smoothing must be 0; 1 - p_y is formed without cancellation
+ * clamped to >= +0.0f; its fp32 bits are the ranking key.  A group is the batch (per_image 0) or one image; with n its counted pixels
+ * K = min(n, max(min_kept, ceil(keep_fraction * n))) (product and ceil in IEEE double) and KEPT are the K pixels of largest l, among
+ * equal fp32 l the lower pixel index (b, y, x) first: part of the interface.  keep_fraction == 1 keeps every counted pixel (no select).
+ *   loss = sum_kept l / sum_kept w_y    one numerator and one denominator over all groups, both in double in a fixed order (bitwise
+ * reproducible); a denominator of 0 gives NaN.  Without mining and with focal_gamma 0 this is torch's mean reduction with weights.
+ * pixel_loss_dev fp32 (B*HW) / kept_dev int32 (B*HW), optional test hooks: l (0 where not counted) and 1 kept / 0 dropped / -1 not
+ * counted.  Stream-ordered, no host synchronisation, no host read of n or K.
+ * Launches, whatever B, num_classes, per_image and the data are: keep_fraction == 1: 2 for the value, 3 with the gradient;
+ * keep_fraction < 1: 8 / 9 (pixel losses + top digit counts, three counting passes over 8 + 8 + 8 + 7 key bits, tie counts, tie scan,
+ * sums, finish, gradient rows) after one memset of the digit counters.  Scratch (the context's, grown on first use), P = B*HW,
+ * G = per_image ? B : 1, T = G * ceil(P / G / mgu_pixel_ce_tile()): 16 * T + 16 bytes, with the select also 4 * P + 4096 * G + 4 * T
+ * + 8 * G, every region rounded up to 256 bytes (8 403 456 bytes = 8.0 MiB at 8 x 512 x 512 over the batch).
+ * num_classes > 8, an empty shape, B*HW >= 2^30, label_smoothing outside [0, 1), focal_gamma in (0, 1) or < 0, focal_gamma > 0 with
+ * label_smoothing > 0, keep_fraction outside (0, 1] or min_kept < 0 return MGU_ERR_INVALID and launch nothing. */
+int mgu_pixel_ce(mgu_ctx* ctx, const void* logits_dev, const int64_t* labels_dev, int B, int64_t HW, int num_classes, int64_t ls_n,
+                 int64_t ls_c, int64_t ls_p, const float* class_weight_dev, float label_smoothing, float focal_gamma,
+                 double keep_fraction, int64_t min_kept, int per_image, int64_t ignore_index, float* loss_dev, float* pixel_loss_dev,
+                 int32_t* kept_dev, void* hip_stream);
+/* d loss / d logits of exactly that expression with the kept set held fixed, times grad_scale (* *grad_scale_dev if given; no
+ * npix / count rescaling as in mgu_cross_entropy: grad_scale 1 is L.backward()): element (b, c, p) at dlogits_dev[b*ds_n + c*ds_c +
+ * p*ds_p].  Pixels that are not counted or not kept get exact zeros.  accumulate != 0 ADDS to dlogits_dev; with accumulate == 0 and
+ * zero_to > num_classes the classes [num_classes, zero_to) of every pixel are written 0 at the same strides (the trainer's 4-padded
+ * rows).  loss_dev (optional) receives the loss value of the same pass. */
+int mgu_pixel_ce_backward(mgu_ctx* ctx, const void* logits_dev, const int64_t* labels_dev, int B, int64_t HW, int num_classes,
+                          int64_t ls_n, int64_t ls_c, int64_t ls_p, const float* class_weight_dev, float label_smoothing,
+                          float focal_gamma, double keep_fraction, int64_t min_kept, int per_image, int64_t ignore_index,
+                          float grad_scale, const float* grad_scale_dev, void* dlogits_dev, int64_t ds_n, int64_t ds_c, int64_t ds_p,
+                          int accumulate, int zero_to, float* loss_dev, void* hip_stream);
+/* Keys one workgroup counts per pass of the pixel cross-entropy's select (the tests size their groups around it). */
+int mgu_pixel_ce_tile(void);
 /* EllipticalShapeLoss.forward (model/unet/shape_loss.py:17-180).  _masks: the object_masks_list form, all masks of the batch
  * stacked (num_objects, H, W) uint8 (non-zero = object pixel).  _probs: the form without masks -- per image, the pixels whose
  * arg-max class is 1 are ONE object (:61-98); probabilities (B,C,H,W) at probs_dev[b*ps_n + c*ps_c + p*ps_p].  Objects under 10

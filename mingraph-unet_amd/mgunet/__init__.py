@@ -4,7 +4,8 @@ from .config import build_from_config, get_config_recursively, load_config  # no
 from .detection import DetectionHead  # noqa: F401
 from .engine import E2ETrainer, FlatAdam, MinGraphUNet, MinGraphUNetE2E, StepLR, Trainer, adam_state_dict, allreduce_mean_, argmax_classes, gat_forward_csr, segment_batch, shard_batch  # noqa: F401
 from .gat import GATNetwork, GraphAttentionLayer, MultiHeadGATLayer, seed_dropout  # noqa: F401
-from .losses import EllipticalShapeLoss, FeatureConsistencyLoss, TVLoss, dice_loss, lovasz_softmax  # noqa: F401
+from .losses import (EllipticalShapeLoss, FeatureConsistencyLoss, TVLoss, class_weights, dice_loss, lovasz_softmax,  # noqa: F401
+                     pixel_cross_entropy)
 from .preprocess import EdgeDetector, GaussianSmoother, HistogramEqualizer, ImagePreprocessor, RandomFlipRotate, draw_flip_rotate, gaussian_kernel_q8, patch_features_u8, patch_smooth_features_u8, pil_rotation_fixed, postprocess_segmentation  # noqa: F401
 from .metrics import SegmentationEvaluator, allreduce_eval_state, evaluate_segmentation, metrics_from_confusion, segmentation_metrics  # noqa: F401
 from .objects import (ObjectShapes, ObjectTable, YieldEvaluator, clean_masks, connected_components, distance_transform,  # noqa: F401
@@ -24,7 +25,7 @@ from .region import FeatureFusion, region_edge_index, region_fuse, region_mean_p
 from .unet import ConvBlock, DecoderBlock, UNet, UNetDecoder, UNetEncoder  # noqa: F401
 from ._lib import build, lib  # noqa: F401
 
-__all__ = ["SuperpixelGraph", "connect_regions", "lab_tables", "region_adjacency", "region_features", "region_pool", "slic_labels", "superpixel_graph", "TVLoss", "dice_loss", "lovasz_softmax", "FeatureConsistencyLoss", "EllipticalShapeLoss", "ImagePreprocessor", "RandomFlipRotate", "draw_flip_rotate", "pil_rotation_fixed", "EdgeDetector", "HistogramEqualizer", "GaussianSmoother", "gaussian_kernel_q8", "patch_smooth_features_u8",
+__all__ = ["SuperpixelGraph", "connect_regions", "lab_tables", "region_adjacency", "region_features", "region_pool", "slic_labels", "superpixel_graph", "TVLoss", "dice_loss", "lovasz_softmax", "pixel_cross_entropy", "class_weights", "FeatureConsistencyLoss", "EllipticalShapeLoss", "ImagePreprocessor", "RandomFlipRotate", "draw_flip_rotate", "pil_rotation_fixed", "EdgeDetector", "HistogramEqualizer", "GaussianSmoother", "gaussian_kernel_q8", "patch_smooth_features_u8",
            "patch_features_u8", "patch_node_features", "patch_labels", "postprocess_segmentation", "DetectionHead", "FeatureFusion", "region_stage", "region_mean_pool", "region_fuse", "region_edge_index", "MinCutRefinement", "PatchSegmentPredictor", "graph_cut", "cut_capacities", "cut_energy", "GraphCut", "graph_cut_multi", "label_costs", "cut_energy_multi", "MultiCut", "UNet", "UNetEncoder", "UNetDecoder", "ConvBlock", "DecoderBlock", "GATNetwork", "MultiHeadGATLayer",
            "GraphAttentionLayer", "PatchGraphConstructor", "MinGraphUNet", "MinGraphUNetE2E", "segment_batch", "argmax_classes",
            "gat_forward_csr", "shard_batch", "segmentation_metrics", "metrics_from_confusion", "SegmentationEvaluator", "evaluate_segmentation",

@@ -11,7 +11,7 @@ import torch.nn as nn
 from . import _lib
 from ._args import check_masks, nhwc_storage
 from .gat import GATNetwork, _csr_cache, _layer_forward, _LayerCall
-from .losses import _LOVASZ_CLASSES
+from .losses import _LOVASZ_CLASSES, pixel_ce_options
 from .patch_graph import PatchGraphConstructor
 from .unet import UNet
 
@@ -225,7 +225,8 @@ class Trainer:
     own shard (DDP semantics)."""
 
     def __init__(self, model: UNet, lr=1e-3, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, process_group=None, comm="auto",
-                 loss="ce", dice_smooth=1.0, optimizer="adam", momentum=0.9, lovasz_per_image=False, lovasz_classes="present"):
+                 loss="ce", dice_smooth=1.0, optimizer="adam", momentum=0.9, lovasz_per_image=False, lovasz_classes="present",
+                 ce_weight=None, label_smoothing=0.0, focal_gamma=0.0, hard_fraction=1.0, hard_min_kept=0, hard_per_image=False):
         """comm: "auto" (default) -- with more than one rank the gradient is mean-all-reduced by torch.distributed (RCCL when the
         backend is "nccl") after backward: the path exercised with two ranks.  "rccl" -- opt in to libmgunet's own RCCL
         communicator with the bucketed exchange overlapped with backward (mgu_unet_backward_allreduce); tests/test_gpu_rccl.py
@@ -235,6 +236,10 @@ class Trainer:
         the cross-entropy gradient in the same dlogits buffer (mgu_dice_loss_backward, accumulate) before the one backward pass.
         "ce+lovasz" / "ce+dice+lovasz" -- additionally the Lovasz-Softmax loss (losses.lovasz_softmax, the IoU surrogate; options
         lovasz_per_image, lovasz_classes), added the same way after them: one mgu_lovasz_softmax_backward(accumulate) call.
+        ce_weight, label_smoothing, focal_gamma, hard_fraction, hard_min_kept, hard_per_image: the options of
+        losses.pixel_cross_entropy (weight, label_smoothing, focal_gamma, keep_fraction, min_kept, per_image; INTEGRATION.md section
+        S).  With all six at their defaults the cross-entropy term is mgu_cross_entropy, exactly as before; otherwise one
+        mgu_pixel_ce_backward call takes its place and the dice / Lovasz terms accumulate after it as they do after the plain one.
         ("rccl" also creates the communicator for a single process: the collective then degenerates to a copy.)
         optimizer: "adam" (train_segmentation.py:96, the shipped configs/training.yaml) or "sgd" -- the script's other branch,
         optim.SGD(lr, momentum=sgd_momentum, weight_decay) (:97-98; training.yaml:5-6): one fused kernel on the flat buffers either way."""
@@ -244,6 +249,7 @@ class Trainer:
             raise ValueError(f"unknown loss {loss!r}: " + ", ".join(repr(k) for k in LOSSES[:-1]) + f" or {LOSSES[-1]!r}")
         if lovasz_classes not in _LOVASZ_CLASSES:
             raise ValueError(f"unknown lovasz_classes {lovasz_classes!r}: 'present' or 'all'")
+        pixel_ce = pixel_ce_options(ce_weight, label_smoothing, focal_gamma, hard_fraction, hard_min_kept, hard_per_image, getattr(model, "num_classes", None))
         self.optimizer, self.momentum = optimizer, float(momentum)
         params = list(model.named_parameters())
         _lib.require_hip(params[0][1], "Trainer")
@@ -275,6 +281,9 @@ class Trainer:
         self.loss_kind, self.dice_smooth = loss, float(dice_smooth)
         self.lovasz_mode, self.lovasz_per_image = _LOVASZ_CLASSES[lovasz_classes], int(bool(lovasz_per_image))
         self._lovasz = torch.zeros(1, device=dev, dtype=torch.float32)
+        # the pixel cross-entropy's options, None while all of them are at their defaults (the step then calls mgu_cross_entropy)
+        self.pixel_ce = None if ce_weight is None and pixel_ce == (0.0, 0.0, 1.0, 0, 0) else pixel_ce
+        self.ce_weight = None if ce_weight is None else ce_weight.detach().to(device=dev, dtype=torch.float32).contiguous()
         self._loss = torch.zeros(1, device=dev, dtype=torch.float32)
         self._dice = torch.zeros(1, device=dev, dtype=torch.float32)
         self._rccl = False
@@ -406,7 +415,11 @@ class Trainer:
         ldd = (Cc + 3) // 4 * 4
         dlogits = torch.empty((npix, ldd), device=dev, dtype=torch.float32)
         loss = self._loss
-        _lib.call("mgu_cross_entropy", dev, nhwc, masks, npix, Cc, 1.0 / npix, dlogits, self._loss, ctx=ctx)
+        if self.pixel_ce is None:
+            _lib.call("mgu_cross_entropy", dev, nhwc, masks, npix, Cc, 1.0 / npix, dlogits, self._loss, ctx=ctx)
+        else:   # weights, smoothing, the focal term or hard-pixel mining: the same rows of dlogits, padding classes zeroed
+            _lib.call("mgu_pixel_ce_backward", dev, nhwc, masks, B, H * W, Cc, H * W * Cc, 1, Cc, self.ce_weight, *self.pixel_ce, -100,
+                      1.0, None, dlogits, H * W * ldd, 1, ldd, 0, ldd, self._loss, ctx=ctx)
         if "dice" in self.loss_kind:   # loss = loss_ce + loss_dice (:130): d(dice)/d(logits) is ADDED to the CE gradient
             _lib.call("mgu_dice_loss_backward", dev, nhwc, masks, B, H * W, Cc, H * W * Cc, 1, Cc, self.dice_smooth, 1.0, None, dlogits,
                       H * W * ldd, 1, ldd, 1, self._dice, ctx=ctx)

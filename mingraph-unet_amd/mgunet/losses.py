@@ -1,6 +1,6 @@
 """Host-side mirrors of the reference's auxiliary losses, routed through libmgunet.so: same names,
 constructor arguments, call signatures and error messages.  Each call returns a 0-dim float32 tensor on the input's device.
-TVLoss, dice_loss, lovasz_softmax and FeatureConsistencyLoss are differentiable (torch.autograd.Function nodes whose backward is a HIP kernel:
+TVLoss, dice_loss, lovasz_softmax, pixel_cross_entropy and FeatureConsistencyLoss are differentiable (torch.autograd.Function nodes whose backward is a HIP kernel:
 mgu_*_backward), so `loss.backward()` as at scripts/train_segmentation.py:133 works on them; EllipticalShapeLoss has no gradient
 w.r.t. its input (a function of arg-max pixel coordinates; the reference loop pins loss_shape to 0, train_end_to_end.py:287).
 check_labels(device) synchronises and raises where F.one_hot would have raised on an out-of-range label.
@@ -10,6 +10,7 @@ check_labels(device) synchronises and raises where F.one_hot would have raised o
     FeatureConsistencyLoss   model/unet/feature_loss.py:5-125
     EllipticalShapeLoss      model/unet/shape_loss.py:6-180
     lovasz_softmax           the build's own addition (the reference has no IoU surrogate): INTEGRATION.md section Q
+    pixel_cross_entropy      the build's own addition (class weights, label smoothing, focal term, hard-pixel mining): section S
 """
 from __future__ import annotations
 
@@ -160,6 +161,122 @@ def _lovasz_debug(pred, target, classes="present", per_image=False, ignore_index
     _lib.call("mgu_lovasz_softmax", pd.device, pd, target.contiguous(), B, H * W, C_, pd.stride(0), pd.stride(1), pd.stride(3), mode,
               per_image, ignore_index, out, errors, ranks)
     return out, errors, ranks
+
+
+def pixel_ce_options(weight, label_smoothing, focal_gamma, keep_fraction, min_kept, per_image, num_classes=None):
+    """The checked options of the pixel cross-entropy, in the order of the C-ABI after the class weights: (label_smoothing,
+    focal_gamma, keep_fraction, min_kept, per_image).  ValueError on what mgu_pixel_ce would refuse, on a weight vector of the
+    wrong length (num_classes given) and on a negative weight in a host tensor (weights already on the device are the caller's)."""
+    eps, gamma, keep, kmin = float(label_smoothing), float(focal_gamma), float(keep_fraction), int(min_kept)
+    if not 0.0 <= eps < 1.0:
+        raise ValueError(f"label_smoothing {label_smoothing!r} must lie in [0, 1)")
+    if not (gamma == 0.0 or gamma >= 1.0):
+        raise ValueError(f"focal_gamma {focal_gamma!r} must be 0 or >= 1")
+    if gamma > 0.0 and eps > 0.0:
+        raise ValueError("focal_gamma > 0 takes no label_smoothing")
+    if not 0.0 < keep <= 1.0:
+        raise ValueError(f"keep_fraction {keep_fraction!r} must lie in (0, 1]")
+    if kmin < 0:
+        raise ValueError(f"min_kept {min_kept!r} must be >= 0")
+    if weight is not None:
+        if not isinstance(weight, torch.Tensor) or weight.dim() != 1 or (num_classes is not None and weight.numel() != num_classes):
+            raise ValueError("weight must be a tensor of num_classes floats")
+        if weight.device.type == "cpu" and bool((weight.detach() < 0).any()):   # a device tensor is not read back: no host sync
+            raise ValueError("class weights must be >= 0")
+    return eps, gamma, keep, kmin, int(bool(per_image))
+
+
+class _PixelCEFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx_, pred, target, weight, opts, ignore_index):
+        pd = _pixel_strided(_f32(pred))
+        B, C_, H, W = pd.shape
+        target = target.contiguous()
+        out = torch.empty((), device=pd.device, dtype=torch.float32)
+        _lib.call("mgu_pixel_ce", pd.device, pd, target, B, H * W, C_, pd.stride(0), pd.stride(1), pd.stride(3), weight, *opts, ignore_index,
+                  out, None, None)
+        ctx_.save_for_backward(pd, target)
+        ctx_.weight, ctx_.opts, ctx_.in_dtype = weight, (opts, ignore_index), pred.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx_, g):
+        pd, target = ctx_.saved_tensors
+        B, C_, H, W = pd.shape
+        d = torch.empty_strided(pd.shape, pd.stride(), device=pd.device, dtype=torch.float32)   # NHWC storage stays NHWC
+        g = g.detach().float().contiguous()
+        opts, ignore_index = ctx_.opts
+        _lib.call("mgu_pixel_ce_backward", pd.device, pd, target, B, H * W, C_, pd.stride(0), pd.stride(1), pd.stride(3), ctx_.weight, *opts,
+                  ignore_index, 1.0, g, d, d.stride(0), d.stride(1), d.stride(3), 0, 0, None)
+        return d.to(ctx_.in_dtype), None, None, None, None
+
+
+def _pixel_ce_args(pred, target, weight, label_smoothing, focal_gamma, keep_fraction, min_kept, per_image, ignore_index):
+    _lib.require_hip(pred, "mgunet pixel_cross_entropy")
+    if pred.dim() != 4 or target.dim() != 3 or target.dtype != torch.int64:
+        raise ValueError("expected logits (B, C, H, W) and an int64 target (B, H, W)")
+    opts = pixel_ce_options(weight, label_smoothing, focal_gamma, keep_fraction, min_kept, per_image, pred.shape[1])
+    if weight is not None:
+        weight = weight.detach().to(device=pred.device, dtype=torch.float32).contiguous()
+    return weight, opts, int(ignore_index)
+
+
+def pixel_cross_entropy(pred, target, weight=None, label_smoothing=0.0, focal_gamma=0.0, keep_fraction=1.0, min_kept=0, per_image=False,
+                        ignore_index=-100):
+    """Imbalance-aware pixel-wise cross-entropy: pred (B, C, H, W) logits with C <= 8 (any strides
+    dice_loss accepts), target (B, H, W) int64.  weight (C floats >= 0) and label_smoothing are nn.CrossEntropyLoss's; focal_gamma
+    >= 1 multiplies each pixel's term by (1 - p_y)^gamma (Lin et al. 2017; takes no label_smoothing); keep_fraction < 1 keeps only
+    the hardest pixels: of the n counted pixels of the batch (per_image: of each image) the min(n, max(min_kept, ceil(keep_fraction
+    n))) with the largest loss, equal losses in pixel order, and only they carry value and gradient.  loss = sum of the kept
+    losses / sum of their class weights.  Differentiable w.r.t. pred.  A label outside [0, C) other than ignore_index makes the loss
+    NaN and is reported by check_labels(pred.device) (no host sync inside the call)."""
+    return _PixelCEFn.apply(pred, target, *_pixel_ce_args(pred, target, weight, label_smoothing, focal_gamma, keep_fraction, min_kept,
+                                                          per_image, ignore_index))
+
+
+def _pixel_ce_debug(pred, target, weight=None, label_smoothing=0.0, focal_gamma=0.0, keep_fraction=1.0, min_kept=0, per_image=False,
+                    ignore_index=-100):
+    """(loss, pixel_loss, kept) through the test hooks of mgu_pixel_ce: pixel_loss fp32 (B, H, W), the loss of every pixel (0 where
+    it is not counted), and kept int32 (B, H, W): 1 kept, 0 dropped, -1 not counted."""
+    weight, opts, ignore_index = _pixel_ce_args(pred, target, weight, label_smoothing, focal_gamma, keep_fraction, min_kept, per_image,
+                                                ignore_index)
+    pd = _pixel_strided(_f32(pred))
+    B, C_, H, W = pd.shape
+    out = torch.empty((), device=pd.device, dtype=torch.float32)
+    pixel_loss = torch.empty((B, H, W), device=pd.device, dtype=torch.float32)
+    kept = torch.empty((B, H, W), device=pd.device, dtype=torch.int32)
+    _lib.call("mgu_pixel_ce", pd.device, pd, target.contiguous(), B, H * W, C_, pd.stride(0), pd.stride(1), pd.stride(3), weight, *opts,
+              ignore_index, out, pixel_loss, kept)
+    return out, pixel_loss, kept
+
+
+CLASS_WEIGHT_SCHEMES = ("median_frequency", "inverse", "enet")
+
+
+def class_weights(counts, scheme="median_frequency"):
+    """Class weights from a (C,) vector of pixel counts (for example the row sums of SegmentationEvaluator's confusion matrix), in
+    float64 on the host; returns a float32 (C,) tensor.  With f_c = count_c / sum of the counts:
+        "median_frequency"  median of the f of the classes that occur / f_c     (Eigen & Fergus, ICCV 2015)
+        "inverse"           1 / (number of classes that occur * f_c): the weights of the classes that occur have weighted mean 1
+        "enet"              1 / ln(1.02 + f_c)                                  (Paszke et al., ENet, 2016)
+    A class with count 0 gets weight 0."""
+    if scheme not in CLASS_WEIGHT_SCHEMES:
+        raise ValueError(f"unknown scheme {scheme!r}: " + ", ".join(repr(k) for k in CLASS_WEIGHT_SCHEMES[:-1]) +
+                         f" or {CLASS_WEIGHT_SCHEMES[-1]!r}")
+    n = torch.as_tensor(counts).detach().cpu().to(torch.float64).reshape(-1)
+    if n.numel() == 0 or bool((n < 0).any()):
+        raise ValueError("counts must be a non-empty vector of non-negative numbers")
+    seen = n > 0
+    w = torch.zeros_like(n)
+    if bool(seen.any()):
+        f = n[seen] / n.sum()
+        if scheme == "median_frequency":
+            w[seen] = f.sort().values[(f.numel() - 1) // 2:f.numel() // 2 + 1].mean() / f
+        elif scheme == "inverse":
+            w[seen] = 1.0 / (f.numel() * f)
+        else:
+            w[seen] = 1.0 / torch.log(1.02 + f)
+    return w.to(torch.float32)
 
 
 class _FeatConsFn(torch.autograd.Function):
