@@ -820,6 +820,42 @@ int mgu_preprocess_image_u8_aug(mgu_ctx* ctx, const uint8_t* img_dev, int Hs, in
 /* mgu_preprocess_mask_u8 followed by the flip / rotation of the (H, W) label map; out-of-image pixels get mask_fill (not clipped). */
 int mgu_preprocess_mask_u8_aug(mgu_ctx* ctx, const uint8_t* mask_dev, int Hs, int Ws, int H, int W, int num_classes, int flip, const int32_t* fix6,
                                int64_t mask_fill, int64_t* out_dev, void* hip_stream);
+/* ---- scale, crop and colour augmentation from uint8 batches (csrc/augment_affine.hip) -----------------------------------------------
+ * The reference has no such stage.  THIS BUILD'S DEFINITION, integers only up to the last step; `>>` is the arithmetic shift (floor).
+ * img_u8 (B, Hs, Ws, 3) uint8 contiguous (bgr != 0: channel order B, G, R), mask_u8 optional (B, Hs, Ws) uint8 -> out: fp32 (B, 3, H, W),
+ * element (b, c, y, x) at out[b*s[0] + c*s[1] + y*s[2] + x*s[3]] for out_strides (HOST array of 4), and mask_out int64 (B, H, W) contiguous.
+ * params_dev: DEVICE int32 (B, 16), per image {a0..a5, A[3][3] row-major, k}.
+ * Geometry.  Output pixel (x, y) has the source coordinates, 16.16 fixed point in pixel-index units, sums in int64:
+ *     sx = a2 + y a1 + x a0          sy = a5 + y a4 + x a3
+ *   The host folds flip, rotation, zoom, aspect, crop position, the Ws/W, Hs/H stretch and both half-pixel centres into a0..a5 with
+ *   FIX(v) = floor(v 65536 + 0.5) on the float64 matrix (mgunet.preprocess.affine_fixed).
+ *   Image, bilinear with 8-bit fractions: ix = sx >> 16, fx = (sx >> 8) & 255 (iy, fy likewise); taps (ix, iy), (ix+1, iy), (ix, iy+1),
+ *   (ix+1, iy+1) with the weights (256-fx)(256-fy), fx(256-fy), (256-fx)fy, fx fy (sum 65536); a tap outside the source reads
+ *   fill_rgb[c] (HOST array of 3 bytes, R G B; no clamp to the edge); v_c = (sum w p + 32768) >> 16, exact in uint32, at most 255.
+ *   Mask, nearest: source pixel ((sx + 32768) >> 16, (sy + 32768) >> 16); outside the source mask_fill (e.g. -100, not clipped), inside
+ *   the byte, clipped to [0, num_classes - 1] when num_classes > 0.
+ * Colour, on the sampled bytes v = (v_R, v_G, v_B) (so the fill is a source colour and is jittered with the rest); A and k are Q12:
+ *     t     = (k m + 128) >> 8                                                        (int64)
+ *     out_c = clamp((A[c][0] v_R + A[c][1] v_G + A[c][2] v_B + t + 2048) >> 12, 0, 255)
+ *   m: the image's mean luma in Q8 byte units over the WHOLE SOURCE image: S = sum over pixels (77 R + 150 G + 29 B) (uint64, integer
+ *   atomics: associative, bitwise reproducible), m = (S + n/2) / n, n = Hs Ws, integer division.  |A|, |k| <= 2^15 (the host refuses
+ *   more: mgunet.preprocess.color_matrix_q12); A = 4096 I, k = 0 passes the bytes unchanged.
+ * Output: ToTensor (/255) and Normalize of out_c with mean3 / std3 (HOST arrays of 3), the float operations of mgu_preprocess_image_u8.
+ * need_mean = 0 is the caller's statement that every k is 0: no luma kernel runs and t = 0.  Launches: the luma kernel (need_mean only,
+ * after the one fill that clears its B sums in the context's scratch; 16-byte reads, one 64-bit integer atomic per workgroup and image)
+ * and one kernel for the images and masks of the whole batch; no host synchronisation.  The result is stored 16 bytes at a time when
+ * the output x-stride is 1, W % 4 == 0 and every row, channel and image of out (and mask_out) starts 16-byte aligned, else by element.
+ * MGU_ERR_INVALID, before any device work: a null pointer; B, Hs, Ws, H, W < 1; a side above 8192; mask_u8 and mask_out not both set or
+ * both null; B * tiles >= 2^31 (tiles: 32 x 32 of the result, mgu_augment_luma_tile() pixels of the source). */
+int mgu_augment_affine_color(mgu_ctx* ctx, const uint8_t* img_u8, int B, int Hs, int Ws, int bgr, const uint8_t* mask_u8, int num_classes,
+                             float* out, int H, int W, const int64_t* out_strides, const float* mean3, const float* std3,
+                             const uint8_t* fill_rgb, int64_t* mask_out, int64_t mask_fill, const int32_t* params_dev, int need_mean,
+                             void* hip_stream);
+/* source pixels per workgroup of the luma kernel (tests place image sizes on its edges) */
+int mgu_augment_luma_tile(void);
+/* The luma pass alone: sums_dev[b] = S of image b (DEVICE int64 (B), cleared by this call's fill), as mgu_augment_affine_color forms it;
+ * the mean luma of the definition is m = (S + n/2) / n. */
+int mgu_augment_luma_sums(mgu_ctx* ctx, const uint8_t* img_u8, int B, int Hs, int Ws, int bgr, int64_t* sums_dev, void* hip_stream);
 /* EdgeDetector.sobel_edges (preprocessing/graph_feature_processing/edge_detection.py:14-44), kernel size 3: RGB -> grey (15-bit fixed
  * point), Sobel x / y with reflect-101 borders, magnitude / max * 255 in double, truncated to uint8.  rgb (H,W,3) -> out (H,W). */
 int mgu_sobel_edges_u8(mgu_ctx* ctx, const uint8_t* rgb_dev, int H, int W, uint8_t* out_dev, void* hip_stream);

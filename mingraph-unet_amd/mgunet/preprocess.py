@@ -15,7 +15,8 @@ round trip).  File paths are decoded with PIL (RGB order): cv2 is not a dependen
 ImagePreprocessor(apply_augmentation=True) reproduces the reference's RandomHorizontalFlip(0.5) -> RandomRotation(15) bit for bit: the
 host makes torchvision's two draws from torch's generator (draw_flip_rotate) and the device applies PIL's fixed-point NEAREST rotation
 (pil_rotation_fixed) inside the ToTensor + Normalize pass.  preprocess_pair applies one draw to an image AND its mask (the reference
-augments only the image), and RandomFlipRotate augments a whole device batch in one launch."""
+augments only the image), and RandomFlipRotate augments a whole device batch in one launch.  RandomAffineColor is this build's
+own stage (the reference has none): scale / crop / rotation with bilinear resampling and a colour jitter, from the uint8 batch."""
 from __future__ import annotations
 
 import ctypes as C
@@ -238,6 +239,154 @@ class RandomFlipRotate:
         si, so = (C.c_int64 * 4)(*images.stride()), (C.c_int64 * 4)(*out.stride())
         fill = (C.c_float * Cc)(*self.fill)
         _lib.call("mgu_augment_flip_rotate", dev, images, out, B, Cc, H, W, si, so, fill, masks, mout, self.mask_fill, params)
+        return (out, mout) if masks is not None else out
+
+
+def _fix(v: float, bits: int) -> int:
+    return int(math.floor(v * float(1 << bits) + 0.5))
+
+
+def affine_fixed(flip, angle: float, zoom: float, aspect: float, tx: float, ty: float, src_hw, out_hw) -> tuple:
+    """The six int32 coefficients (a0..a5) of mgu_augment_affine_color for one image: output pixel (x, y) of the W x H result reads the
+    source at (sx, sy) = (a2 + y a1 + x a0, a5 + y a4 + x a3) / 65536 in pixel-index units.  The crop is the largest window of aspect
+    (Ws / Hs) * aspect inside the (Ws / zoom) x (Hs / zoom) window (zoom > 1 enlarges the fruit), centred at
+    (Ws/2 + tx (Ws/2)(1 - 1/zoom), Hs/2 + ty (Hs/2)(1 - 1/zoom)), tx, ty in [-1, 1]: for zoom >= 1 the unrotated crop stays inside the
+    source, for zoom < 1 the source stays inside the frame.  It is stretched over the result, flipped left-right when `flip`, and
+    rotated by `angle` degrees counter-clockwise about its centre (cos / sin rounded to 15 digits, as pil_rotation_fixed).  Float64
+    matrix M = R(angle) diag(+-crop_w / W, crop_h / H) on offsets from the centres, both half-pixel centres folded into a2 / a5, then
+    FIX(v) = floor(v 65536 + 0.5).  Sides above 8192 or coefficients beyond int32 raise."""
+    Hs, Ws = int(src_hw[0]), int(src_hw[1])
+    H, W = int(out_hw[0]), int(out_hw[1])
+    if not (1 <= Hs <= _MAX_SIDE and 1 <= Ws <= _MAX_SIDE and 1 <= H <= _MAX_SIDE and 1 <= W <= _MAX_SIDE):
+        raise ValueError(f"affine_fixed: {Hs} x {Ws} -> {H} x {W}: sides must be in [1, {_MAX_SIDE}]")
+    z, a = float(zoom), float(aspect)
+    if not (z > 0.0 and a > 0.0 and math.isfinite(z) and math.isfinite(a)):
+        raise ValueError("affine_fixed: zoom and aspect must be positive")
+    cw, ch = (Ws / z, Hs / (z * a)) if a >= 1.0 else (Ws * a / z, Hs / z)
+    px, py = (-cw if flip else cw) / W, ch / H
+    r = math.radians(float(angle) % 360.0)
+    co, si = round(math.cos(r), 15), round(math.sin(r), 15)
+    m00, m01, m10, m11 = co * px, -si * py, si * px, co * py
+    cx = Ws / 2.0 + float(tx) * (Ws / 2.0) * (1.0 - 1.0 / z)
+    cy = Hs / 2.0 + float(ty) * (Hs / 2.0) * (1.0 - 1.0 / z)
+    ox, oy = 0.5 - W / 2.0, 0.5 - H / 2.0
+    fix = (_fix(m00, 16), _fix(m01, 16), _fix(cx - 0.5 + m00 * ox + m01 * oy, 16),
+           _fix(m10, 16), _fix(m11, 16), _fix(cy - 0.5 + m10 * ox + m11 * oy, 16))
+    if any(abs(v) >= 2 ** 31 for v in fix):
+        raise ValueError(f"affine_fixed: coefficients {fix} do not fit int32 (zoom {z} is too small for these sizes)")
+    return fix
+
+
+_LUMA_W = (77.0 / 256.0, 150.0 / 256.0, 29.0 / 256.0)
+COLOR_Q12_LIMIT = 1 << 15
+
+
+def color_matrix_q12(brightness: float = 1.0, contrast: float = 1.0, saturation: float = 1.0, hue: float = 0.0) -> tuple:
+    """The Q12 colour parameters of mgu_augment_affine_color -> (A: 9 ints row-major, k).  A = FIX12(b c (S_s R_h)) with
+    S_s = s I + (1 - s) 1 w^T, w = (77, 150, 29) / 256, and R_h the rotation by 2 pi h about the grey axis (1, 1, 1) / sqrt 3;
+    k = FIX12(b (1 - c)): contrast pivots on the image's own mean luma.  FIX12(v) = floor(v 4096 + 0.5).  |A| or |k| above 2^15 raise."""
+    b, c, s, h = float(brightness), float(contrast), float(saturation), float(hue)
+    S = np.asarray([[s * (i == j) + (1.0 - s) * _LUMA_W[j] for j in range(3)] for i in range(3)], np.float64)
+    co, si = math.cos(2.0 * math.pi * h), math.sin(2.0 * math.pi * h)
+    K = np.asarray([[0.0, -1.0, 1.0], [1.0, 0.0, -1.0], [-1.0, 1.0, 0.0]], np.float64)
+    R = co * np.eye(3) + (1.0 - co) / 3.0 * np.ones((3, 3)) + si / math.sqrt(3.0) * K
+    M = (b * c) * (S @ R)
+    A = tuple(_fix(float(v), 12) for v in M.reshape(-1))
+    k = _fix(b * (1.0 - c), 12)
+    if max(abs(v) for v in A + (k,)) > COLOR_Q12_LIMIT:
+        raise ValueError(f"color_matrix_q12: |A| and |k| must stay within 2^15 (factors up to 8), got A = {A}, k = {k}")
+    return A, k
+
+
+def luma_sums(images_u8: torch.Tensor, bgr: bool = False) -> torch.Tensor:
+    """S[b] = sum over the pixels of image b of (77 R + 150 G + 29 B), int64 (B,) on the device: the integer sums RandomAffineColor's
+    contrast pivots on (mean luma m = (S + n/2) // n in Q8 byte units).  images_u8: (B, Hs, Ws, 3) uint8 on the device."""
+    if not isinstance(images_u8, torch.Tensor) or images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[3] != 3:
+        raise TypeError("images_u8 must be a (B, Hs, Ws, 3) uint8 tensor")
+    _lib.require_hip(images_u8, "mgunet.luma_sums")
+    images_u8 = images_u8.contiguous()
+    B, Hs, Ws, _c = images_u8.shape
+    out = torch.empty((B,), device=images_u8.device, dtype=torch.int64)
+    _lib.call("mgu_augment_luma_sums", images_u8.device, images_u8, B, Hs, Ws, int(bool(bgr)), out)
+    return out
+
+
+def _log_uniform(lo: float, hi: float, u: float) -> float:
+    return math.exp(math.log(lo) + u * (math.log(hi) - math.log(lo)))
+
+
+class RandomAffineColor:
+    """Random scale / aspect / crop / rotation / flip and colour jitter of a uint8 batch on the device, straight into the normalised
+    float32 (B, 3, H, W) batch and the int64 (B, H, W) masks Trainer.train_step takes: at most two launches and one fill, no host
+    synchronisation (include/mgunet.h, mgu_augment_affine_color: bilinear image, nearest mask, integers only, bitwise equal to
+    tests/augment_affine_oracle.py).  Draws, part of the interface: per image, in batch order, one
+    torch.rand(10, dtype=torch.float64, generator=g): [0] flip (< p_flip), [1] angle (uniform in +-degrees), [2] zoom (log-uniform in
+    scale), [3] aspect (log-uniform in ratio), [4], [5] crop position tx, ty in [-1, 1], [6..8] brightness, contrast, saturation
+    (uniform in [1 - a, 1 + a]), [9] hue (uniform in [-a, a]).  A disabled term still consumes its entry.  Source pixels outside the
+    image are `fill` (an RGB byte triple, jittered with the rest) and mask_fill (-100: ignored by every loss here)."""
+
+    def __init__(self, size, scale=(0.5, 2.0), ratio=(3 / 4, 4 / 3), degrees=15, p_flip=0.5, brightness=0.2, contrast=0.2, saturation=0.2,
+                 hue=0.02, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), fill=(0, 0, 0), mask_fill=-100, num_classes=0, bgr=False):
+        self.size = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))   # H, W
+        self.scale, self.ratio = (float(scale[0]), float(scale[1])), (float(ratio[0]), float(ratio[1]))
+        if not (0.0 < self.scale[0] <= self.scale[1] and 0.0 < self.ratio[0] <= self.ratio[1]):
+            raise ValueError("scale and ratio must be positive (lo, hi) ranges")
+        if float(degrees) < 0 or min(float(brightness), float(contrast), float(saturation), float(hue)) < 0:
+            raise ValueError("degrees and the colour ranges must be non-negative")
+        self.degrees, self.p_flip = float(degrees), float(p_flip)
+        self.brightness, self.contrast, self.saturation, self.hue = float(brightness), float(contrast), float(saturation), float(hue)
+        self.mean, self.std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
+        self.fill = tuple(int(v) for v in fill)
+        if len(self.fill) != 3 or not all(0 <= v <= 255 for v in self.fill):
+            raise ValueError("fill must be three bytes (R, G, B)")
+        self.mask_fill, self.num_classes, self.bgr = int(mask_fill), int(num_classes), bool(bgr)
+
+    def row(self, r, src_hw) -> tuple:
+        """the 16 table entries of one image from its ten draws r (floats in [0, 1))"""
+        r = [float(v) for v in r]
+        fix = affine_fixed(r[0] < self.p_flip, (2.0 * r[1] - 1.0) * self.degrees, _log_uniform(*self.scale, r[2]), _log_uniform(*self.ratio, r[3]),
+                           2.0 * r[4] - 1.0, 2.0 * r[5] - 1.0, src_hw, self.size)
+        A, k = color_matrix_q12(1.0 + (2.0 * r[6] - 1.0) * self.brightness, 1.0 + (2.0 * r[7] - 1.0) * self.contrast,
+                                1.0 + (2.0 * r[8] - 1.0) * self.saturation, (2.0 * r[9] - 1.0) * self.hue)
+        return fix + A + (k,)
+
+    def draw(self, B: int, src_hw, generator=None) -> torch.Tensor:
+        """-> (B, 16) int32 host table {a0..a5, A row-major, k}, one torch.rand(10, float64) per image in batch order."""
+        rows = [self.row(torch.rand(10, dtype=torch.float64, generator=generator).tolist(), src_hw) for _ in range(int(B))]
+        return torch.tensor(rows, dtype=torch.int32).reshape(int(B), 16)
+
+    def __call__(self, images_u8: torch.Tensor, masks: torch.Tensor = None, generator=None, out: torch.Tensor = None, params: torch.Tensor = None):
+        """images_u8: (B, Hs, Ws, 3) uint8 on the device; masks: optional (B, Hs, Ws) uint8.  -> float32 (B, 3, H, W) (a new contiguous
+        tensor, or `out` of any strides, e.g. an NHWC-strided view) and, with masks, (images, int64 (B, H, W) masks).  params: an
+        explicit (B, 16) int32 table instead of a draw (a host table lets the luma pass be skipped when every k is 0)."""
+        if not isinstance(images_u8, torch.Tensor) or images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[3] != 3:
+            raise TypeError("images_u8 must be a (B, Hs, Ws, 3) uint8 tensor")
+        _lib.require_hip(images_u8, "mgunet.RandomAffineColor")
+        dev = images_u8.device
+        images_u8 = images_u8.contiguous()
+        B, Hs, Ws, _c = images_u8.shape
+        H, W = self.size
+        if masks is not None:
+            if masks.dtype != torch.uint8 or masks.device != dev or tuple(masks.shape) != (B, Hs, Ws):
+                raise ValueError("masks must be a (B, Hs, Ws) uint8 tensor on the images' device")
+            masks = masks.contiguous()
+        if out is None:
+            out = torch.empty((B, 3, H, W), device=dev, dtype=torch.float32)
+        elif tuple(out.shape) != (B, 3, H, W) or out.dtype != torch.float32 or out.device != dev:
+            raise ValueError("`out` must be a float32 (B, 3, H, W) tensor on the images' device")
+        if params is None:
+            params = self.draw(B, (Hs, Ws), generator)
+        if tuple(params.shape) != (B, 16) or params.dtype != torch.int32:
+            raise ValueError("params must be a (B, 16) int32 table")
+        need_mean = 1 if params.is_cuda else int(bool((params[:, 15] != 0).any()))
+        if not params.is_cuda and int(params[:, 6:].abs().max()) > COLOR_Q12_LIMIT:
+            raise ValueError("params: |A| and |k| must stay within 2^15")
+        params = params.to(dev).contiguous()
+        mout = torch.empty((B, H, W), device=dev, dtype=torch.int64) if masks is not None else None
+        so = (C.c_int64 * 4)(*out.stride())
+        mean, std, fill = (C.c_float * 3)(*self.mean), (C.c_float * 3)(*self.std), (C.c_uint8 * 3)(*self.fill)
+        _lib.call("mgu_augment_affine_color", dev, images_u8, B, Hs, Ws, int(self.bgr), masks, self.num_classes, out, H, W, so, mean, std, fill,
+                  mout, self.mask_fill, params, need_mean)
         return (out, mout) if masks is not None else out
 
 
