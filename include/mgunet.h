@@ -1110,6 +1110,61 @@ int mgu_channel_sum_nhwc(mgu_ctx* ctx, const float* x_dev, int ldx, int64_t M, i
 /* out (B, C)[b] = column sums of image b of x (B, M, C) (row pitch ldx): AdaptiveAvgPool2d over a batch in one call. */
 int mgu_channel_sum_images_nhwc(mgu_ctx* ctx, const float* x_dev, int ldx, int B, int64_t M, int C, float* out_dev, void* hip_stream);
 
+/* ---- video: frame registration and object tracks (csrc/video.hip) ----------------------------------------------
+ * THIS BUILD'S DEFINITION (the reference cuts its videos into frames and has no such stage).  Integers only; every output word is a
+ * pure function of the inputs (integer atomics, ranks and scans): bitwise repeatable.  No call synchronises with the host.
+ *
+ * Registration.  frames_u8: uint8 (T, H, W, channels), channels 3 (RGB, or BGR with bgr != 0) or 1 (grey), T >= 2.
+ *   luma byte      Y = (77 R + 150 G + 29 B + 128) >> 8 (mgu_augment_affine_color's coefficients); a grey frame is its own luma
+ *   coarse plane   Hc = H / factor, Wc = W / factor (floor; trailing rows and columns are dropped), factor f in {1, 2, 4, 8};
+ *                  pixel = (sum of the f x f block of Y + f*f/2) / (f*f)
+ *   coarse search  pair (t, t+1), A / B = the coarse planes of frames t / t+1, R = radius (1..32): for every s = (sy, sx) in [-R, R]^2
+ *                  cost(s) = sum over p in [R, Hc-R) x [R, Wc-R) of |A(p) - B(p + s)| -- the same window for every s, nothing read
+ *                  outside a plane; a scene point at p in frame t lies at p + s in frame t+1.  Hc - 2R >= 8 and Wc - 2R >= 8.
+ *   choice         the smallest cost; ties: the smallest sy^2 + sx^2, then the smaller sy, then the smaller sx
+ *   fine search    (f > 1) on the full-resolution luma: shifts f*s_c + d, d in [-f, f]^2, window [M, H-M) x [M, W-M) with
+ *                  M = f*R + f for every pair, the same choice applied to d; the centre f*s_c is read from device memory
+ *   shifts_dev     int32 (T-1, 2): [dy, dx] in full-resolution pixels
+ *   cost_dev       int64 (T-1, 2): of the last level searched, [the cost at the chosen shift, the cost at that level's d = 0 (the
+ *                  zero shift when f = 1, the coarse choice f*s_c when f > 1)]
+ *   surface_dev    NULL, or int64 (T-1, 2R+1, 2R+1): the coarse cost surface, [sy + R][sx + R]
+ * A workgroup holds one 48 x 48 tile (mgu_frame_sad_tile) of the window and its search halo as bytes in LDS; a lane owns four
+ * x-shifts of one y-shift and walks the tile with v_sad_u8 on 32-bit words (an unaligned word from two neighbours: v_alignbyte_b32);
+ * tile partials are uint32, the surface is summed with 64-bit integer atomics.  No masked SAD form is used: zero bytes count.
+ * Launches whatever T and the contents: f = 1: 3 kernels (planes, SAD, pick) and 1 fill; f > 1: 6 kernels (two of each) and 2 fills.
+ * Scratch from the context: T * (Hc*Wc + H*W) bytes and the surfaces. */
+int mgu_frame_sad_tile(void);
+int mgu_frame_shifts(mgu_ctx* ctx, const uint8_t* frames_u8, int T, int H, int W, int channels, int bgr, int radius, int factor,
+                     int32_t* shifts_dev, int64_t* cost_dev, int64_t* surface_dev, void* hip_stream);
+/* One coordinate frame per pair.  labels_dev int32 (T, H, W) and offsets_dev int64 (T+1) as mgu_connected_components /
+ * mgu_split_objects write them for the T frames as one batch; shifts_dev int32 (T-1, 2) as mgu_frame_shifts writes them (read on the
+ * device; any values are safe).  For pair b = frames (b, b+1) with s = shifts[b], both int32 (T-1, H, W):
+ *   prev_aligned[b][q] = labels[b][q - s] where q - s lies inside the frame, else 0
+ *   next_cropped[b][q] = labels[b+1][q] where q - s lies inside the frame (the common rectangle of frame and frame + s), else 0
+ * vis_prev_dev / vis_next_dev: int64 (capacity), cleared by the call: at an object's batch-wide index the pixels it keeps in
+ * prev_aligned of the pair it opens (objects of frames 0..T-2) / in next_cropped of the pair it closes (frames 1..T-1); objects at
+ * an index >= capacity are not counted.  The two maps with offsets_dev (prev side) and offsets_dev + 1 (next side) are what
+ * mgu_object_overlaps and mgu_match_masks take as "gt" and "pred" of T-1 images: their indices are batch-wide, so offsets that do not
+ * start at 0 need no rebasing.  1 kernel and 2 fills.  T*H*W < 2^31. */
+int mgu_track_align(mgu_ctx* ctx, const int32_t* labels_dev, const int64_t* offsets_dev, int64_t capacity, const int32_t* shifts_dev, int T,
+                    int H, int W, int32_t* prev_aligned_dev, int32_t* next_cropped_dev, int64_t* vis_prev_dev, int64_t* vis_next_dev,
+                    void* hip_stream);
+/* Track ids.  offsets_dev int64 (T+1); link_dev int64 (capacity): the batch-wide index of an object's predecessor (an object of an
+ * earlier frame) or -1 (row 0 of mgu_match_masks' match_gt); class_dev int64 (capacity).  One workgroup walks the frames in order: an
+ * object takes its predecessor's id, an unlinked object the next fresh id in object order (*next_id_dev + its rank among the frame's
+ * unlinked objects: a scan, no atomic decides an id).  first_ids_dev: NULL (frame 0's objects are all new), or the ids of frame 0's
+ * objects from the call before, when frame 0 repeats that call's last frame: they are taken as they are and frame 0 is not counted
+ * again.  next_id_dev: int64 device scalar, read and written.
+ *   track_id_dev     int64 (capacity)
+ *   track_len_dev    int32 (track_capacity), ACCUMULATED (the caller clears it): frames in which the track has an object
+ *   track_class_dev  int64 (track_capacity): the class of the track's first object
+ *   status_dev       int32 scalar, OR-ed: 1 = an id reached track_capacity (its track is not recorded; nothing is written past the
+ *                    arrays; track_id still carries it), 2 = objects past capacity were left out
+ * 1 kernel. */
+int mgu_track_ids(mgu_ctx* ctx, const int64_t* offsets_dev, int T, int64_t capacity, const int64_t* link_dev, const int64_t* class_dev,
+                  const int64_t* first_ids_dev, int64_t* next_id_dev, int64_t* track_id_dev, int32_t* track_len_dev, int64_t* track_class_dev,
+                  int64_t track_capacity, int32_t* status_dev, void* hip_stream);
+
 /* ---- introspection for bench.py / profiles ------------------------------------------------------ */
 /* FLOPs (2*MAC, convolutions only) of one U-Net forward over B images: SURVEY 8d table. */
 double mgu_unet_flops(mgu_ctx* ctx, int B, int H, int W);
