@@ -58,9 +58,11 @@ def pick(surf: np.ndarray, variant=None):
     for sy in range(-r, r + 1):
         for sx in range(-r, r + 1):
             key = (int(surf[sy + r, sx + r]), sy * sy + sx * sx, sy, sx)
-            if best is None or key < best:
-                best = key
-    return best[2], best[3]
+            if variant == "last":          # the nearest minimum, but the last of several in raster order
+                key = key[:2] + (-sy, -sx)
+            if best is None or key < best[0]:
+                best = (key, sy, sx)
+    return best[1], best[2]
 
 
 def frame_shifts(frames, radius: int, factor: int = 1, bgr: bool = False, variant=None):
@@ -188,14 +190,33 @@ def link_objects(labels, offsets, class_id, shifts, iou=0.3, scores=None, varian
     return link
 
 
-def track_ids(offsets, link, class_id, first_ids=None, next_id=0, capacity=None):
-    """-> (track_id int64 (N), next_id, lengths {id: frames}, classes {id: class of the first object}, status)"""
+def label_batch(classmap: np.ndarray, connectivity: int = 2):
+    """label_frames' labels, offsets and class_id by the object tests' vectorised oracle (tests/objects_oracle.py), for maps too big or
+    too full for label_frames' Python flood fill, and for 4-connected objects"""
+    import objects_oracle as OO
+    labels = np.stack([OO.label(m, connectivity) for m in classmap])
+    offsets = np.concatenate([[0], np.cumsum([int(lab.max()) for lab in labels])]).astype(np.int64)
+    cls = np.concatenate([OO.stats(lab, m)[0] for lab, m in zip(labels, classmap)]).astype(np.int64)
+    return labels, offsets, cls
+
+
+def track_ids(offsets, link, class_id, first_ids=None, next_id=0, capacity=None, object_capacity=None, variant=None):
+    """-> (track_id int64 (N), next_id, lengths {id: frames}, classes {id: class of the first object}, status).  capacity: of the
+    per-track arrays (status bit 1: an id reached it; its track is not recorded, track_id still carries it).  object_capacity: of the
+    per-object arrays (status bit 2: the objects at an index past it were left out: no id, no count, no fresh id spent on them; their
+    track_id stays -1).  variant 'rank256': the rank of a fresh object restarts with every 256th object of its frame."""
     T = len(offsets) - 1
     tid = np.full(int(offsets[-1]), -1, np.int64)
     lengths, classes, status = {}, {}, 0
     for t in range(T):
-        for i in range(int(offsets[t]), int(offsets[t + 1])):
+        end = int(offsets[t + 1])
+        if object_capacity is not None and end > object_capacity:
+            end, status = max(int(object_capacity), int(offsets[t])), status | 2
+        frame_next = next_id
+        for i in range(int(offsets[t]), end):
             fresh = False
+            if variant == "rank256" and (i - int(offsets[t])) % 256 == 0:
+                next_id = frame_next                                   # the fresh ids so far are handed out again
             if t == 0 and first_ids is not None:
                 tid[i] = first_ids[i]
                 continue
