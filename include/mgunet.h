@@ -473,6 +473,23 @@ int mgu_pixel_ce_backward(mgu_ctx* ctx, const void* logits_dev, const int64_t* l
                           float focal_gamma, double keep_fraction, int64_t min_kept, int per_image, int64_t ignore_index,
                           float grad_scale, const float* grad_scale_dev, void* dlogits_dev, int64_t ds_n, int64_t ds_c, int64_t ds_p,
                           int accumulate, int zero_to, float* loss_dev, void* hip_stream);
+/* The pixel cross-entropy with a per-pixel weight map m: the arguments of mgu_pixel_ce /
+ * mgu_pixel_ce_backward plus pixel_weight_dev, fp32 (B, HW), dense, every entry >= 0 (mgu_border_weights' weight_dev is one).  The
+ * pixel's loss becomes m(p) l(p), l exactly as above; that product, clamped to >= +0.0f, is the key the hard-pixel select ranks (the
+ * tie rule is unchanged) and what pixel_loss_dev receives.
+ *   loss = sum_kept m l / sum_kept m w_y
+ * and the gradient is that of this expression with the kept set and m held fixed (m gets no gradient; a pixel with m == 0 gets a zero
+ * row).  pixel_weight_dev == NULL, or a map of ones, gives the bits of mgu_pixel_ce / mgu_pixel_ce_backward.  The same kernels and
+ * launch counts (2 / 3, with the select 8 / 9), reported in the profile as pixel_ce_map ...; the same limits and scratch. */
+int mgu_pixel_ce_map(mgu_ctx* ctx, const void* logits_dev, const int64_t* labels_dev, int B, int64_t HW, int num_classes, int64_t ls_n,
+                     int64_t ls_c, int64_t ls_p, const float* class_weight_dev, const float* pixel_weight_dev, float label_smoothing,
+                     float focal_gamma, double keep_fraction, int64_t min_kept, int per_image, int64_t ignore_index, float* loss_dev,
+                     float* pixel_loss_dev, int32_t* kept_dev, void* hip_stream);
+int mgu_pixel_ce_map_backward(mgu_ctx* ctx, const void* logits_dev, const int64_t* labels_dev, int B, int64_t HW, int num_classes,
+                              int64_t ls_n, int64_t ls_c, int64_t ls_p, const float* class_weight_dev, const float* pixel_weight_dev,
+                              float label_smoothing, float focal_gamma, double keep_fraction, int64_t min_kept, int per_image,
+                              int64_t ignore_index, float grad_scale, const float* grad_scale_dev, void* dlogits_dev, int64_t ds_n,
+                              int64_t ds_c, int64_t ds_p, int accumulate, int zero_to, float* loss_dev, void* hip_stream);
 /* Keys one workgroup counts per pass of the pixel cross-entropy's select (the tests size their groups around it). */
 int mgu_pixel_ce_tile(void);
 /* EllipticalShapeLoss.forward (model/unet/shape_loss.py:17-180).  _masks: the object_masks_list form, all masks of the batch
@@ -574,6 +591,37 @@ int mgu_distance_transform(mgu_ctx* ctx, const int32_t* labels_dev, int B, int H
 int mgu_split_objects(mgu_ctx* ctx, const int32_t* labels_dev, int B, int H, int W, int min_distance, int64_t min_radius_sq, int min_area,
                       int32_t* labels_out_dev, int64_t* counts_dev, int64_t* offsets_dev, int32_t* d2_out_dev, uint8_t* seeds_out_dev,
                       void* hip_stream);
+
+/* ---- border weight map: the per-pixel loss weight of the U-Net paper (Ronneberger et al., MICCAI 2015, eq. 2) ------------------------
+ *   w(p) = w_c(p) + w0 exp(-(d1(p) + d2(p))^2 / (2 sigma^2))
+ * d1, d2 the distances to the nearest and to the second-nearest object: the thin background gaps between two touching fruits get a
+ * large weight in training (mgu_pixel_ce_map takes the map).  Built on the device from the masks of each step, no host synchronisation.
+ * labels_dev: int32 (B,H,W), 0 = background, every other int32 value an object, compared by value (it need not be connected, ids need
+ * not be dense): what mgu_connected_components / mgu_split_objects write, or a dataset's instance map.
+ * For every pixel p (foreground or background) and every object label k present in p's image, D_k(p) = min |p - q|^2 over the pixels
+ * q of that image with label k, an exact integer; pixels outside the image take no part.  The pairs (D_k(p), k) are ordered
+ * lexicographically, k as a signed int32.  d1sq(p) = the distance of the first pair (0 on an object's own pixels), nearest(p) = its
+ * label, d2sq(p) = the distance of the second pair: the nearest object other than nearest(p).  d1sq and d2sq do not depend on the tie
+ * rule, nearest does: ties go to the smaller label.  MGU_D2_NONE where the image holds no object, for d2sq also where it holds fewer
+ * than two; nearest is 0 where there is no object.
+ * Outputs, each optional (NULL = not written): d1sq_dev, d2sq_dev, nearest_dev int32 (B,H,W); weight_dev fp32 (B,H,W),
+ *   weight = class_weight[cls(p)] + w0 * exp(-(sqrt(d1sq) + sqrt(d2sq))^2 / (2 sigma^2))
+ * evaluated in fp64 from the exact integers and rounded to fp32 once; the exponential term is exactly 0 where d2sq is MGU_D2_NONE.
+ * cls(p) = classes_dev[p], an optional int64 (B,H,W) class map; a class outside [0, num_classes) (-100) gets class term 0; without
+ * classes_dev or without class_weight_dev (fp32, num_classes entries) the class term is 1.  target_dev int64 (B,H,W): a copy of
+ * classes_dev in which an object pixel with a 4-neighbour holding a different non-zero label is set to background_class -- the
+ * one-pixel separation between touching instances the U-Net recipe assumes; it needs classes_dev.
+ * Exactly two launches, whatever B, the objects and the outputs asked for (columns: a lane per column keeps the two nearest distinct
+ * labels above and below every pixel; rows: a workgroup per row with the row's two candidates per column in LDS, every pixel walking
+ * outward until dx^2 passes its d2sq); no host synchronisation; all outputs are pure functions of the input (no float atomics,
+ * bitwise repeatable).  An image with fewer than two objects makes every pixel walk its whole row, O(W^2) per row.  Scratch: 16 bytes
+ * per pixel of the context's.  Limits: H, W <= 16384 and 16 * W bytes of LDS within what the device gives one workgroup (W <= 10240
+ * at 160 KiB), B <= 65535, B*H*W < 2^31; every real distance stays below MGU_D2_NONE.  sigma <= 0, w0 < 0, an empty shape,
+ * target_dev without classes_dev, class weights with num_classes outside 1..8 or a size past the limits return MGU_ERR_INVALID
+ * and launch nothing. */
+int mgu_border_weights(mgu_ctx* ctx, const int32_t* labels_dev, int B, int H, int W, const int64_t* classes_dev, const float* class_weight_dev,
+                       int num_classes, double w0, double sigma, int64_t background_class, int32_t* d1sq_dev, int32_t* d2sq_dev,
+                       int32_t* nearest_dev, float* weight_dev, int64_t* target_dev, void* hip_stream);
 
 /* ---- mask cleanup: close gaps, fill holes, open away spurs --------------------------------------------------------------------------
  * The stage between "argmax" and "label": a pin hole inside an object collapses its inscribed disc and mgu_split_objects then counts

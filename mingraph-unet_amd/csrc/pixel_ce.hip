@@ -9,6 +9,10 @@
 // (b, y, x) first: part of the interface.  keep_fraction == 1 keeps every counted pixel and runs no select.
 //   L = sum_kept l / sum_kept w_y     one numerator, one denominator over all groups; both sums in double in a fixed order
 // and the gradient is that of exactly this expression with the kept set held fixed: ignored and dropped pixels get exact zeros.
+//   mgu_pixel_ce_map / mgu_pixel_ce_map_backward   the same with a per-pixel weight map m >= 0 (fp32, one per pixel, e.g. border.hip's):
+// the pixel's loss is m l (clamped to >= +0.0f, the key the select ranks), L = sum_kept m l / sum_kept m w_y, m held fixed in the
+// gradient.  The same kernels, instantiated a second time with the map read in (the entries without one run the code they ran before),
+// and the same launch counts; without a map, or with m == 1 everywhere, the same bits.
 //
 // The select is a radix SELECT, not a sort: four counting passes over 8 + 8 + 8 + 7 key bits from the top.  A pass counts the keys
 // that match the prefix chosen so far into 256 bins per group (LDS counters per workgroup, then integer atomic adds of the non-empty
@@ -47,6 +51,7 @@ struct PcCall {
   const float* logits;
   const int64_t* labels;
   const float* weight;   // C class weights or nullptr
+  const float* pmap;     // the per-pixel weight map m (P floats) of the _map entries, or nullptr
   int64_t ls_n, ls_c, ls_p;
   long long ignore, min_kept;
   double keep;
@@ -80,7 +85,7 @@ __device__ __forceinline__ void pc_weights(const PcCall& k, float (&w)[NC]) {
 #pragma unroll
   for (int c = 0; c < NC; ++c) w[c] = c < k.C ? (k.weight ? k.weight[c] : 1.f) : 0.f;
 }
-template <int NC>
+template <int NC, bool MAP>
 __device__ __forceinline__ void pc_pixel(const PcCall& k, int q, int y, PcPixel<NC>& x) {
 #pragma clang fp contract(off)
   const int b = q / k.HW;
@@ -123,7 +128,15 @@ __device__ __forceinline__ void pc_pixel(const PcCall& k, int q, int y, PcPixel<
       v += (k.eps / (float)k.C) * sm;
     }
   }
+  if (MAP) v = k.pmap[q] * v;   // the _map entries rank, sum and differentiate m * l
   x.loss = v > 0.f ? v : 0.f;   // >= +0.0f (a NaN too): the key stays inside 31 bits
+}
+// the pixel's share of the denominator: w_y, times m in the _map entries (m == 1 leaves the double as it is).  MAP is a template
+// argument of every kernel that reads the map, so the entries without one run the code they ran before it existed.
+template <bool MAP>
+__device__ __forceinline__ double pc_den(const PcCall& k, int q, int y) {
+  const double wy = (double)(k.weight ? k.weight[y] : 1.f);
+  return MAP ? (double)k.pmap[q] * wy : wy;
 }
 // d loss / d logit_j of that pixel (contraction off, as above).  Both forms are A (p_j - [j == y]) plus the smoothing term, with p_y - 1 as -miss (no cancellation)
 // and sum_c w_c (p_j - [j == c]) as p_j (W - w_j) - w_j (1 - p_j).
@@ -202,7 +215,7 @@ __device__ __forceinline__ void pc_flush(int* cnt, int* row, int bins) {
 }
 
 // pass 0: the loss of every pixel into the plane (PC_IGNORED where it is not counted), the hook, and the counts of the top digit
-template <int NC>
+template <int NC, bool MAP>
 __global__ __launch_bounds__(256) void pc_loss_kernel(PcCall k, unsigned* __restrict__ plane, int* __restrict__ hist,
                                                       float* __restrict__ pixel_loss, int* __restrict__ err_word) {
   __shared__ int cnt[256];
@@ -223,7 +236,7 @@ __global__ __launch_bounds__(256) void pc_loss_kernel(PcCall k, unsigned* __rest
       if (y < 0 || y >= k.C) {
         bad = true;
       } else {
-        pc_pixel(k, q, (int)y, x);
+        pc_pixel<NC, MAP>(k, q, (int)y, x);
         key = __float_as_uint(x.loss);
         atomicAdd(&cnt[key >> 23], 1);
       }
@@ -298,7 +311,7 @@ __global__ __launch_bounds__(256) void pc_tie_scan_kernel(PcCall k, int* __restr
 // ---- sums, finish, gradient ---------------------------------------------------------------------------------------------------------
 // part[2 * (g * tiles_g + tile)] = sum of the kept losses of the tile, [+ 1] = sum of their w_y (double).  With the select the kept
 // test reads the plane and marks the dropped pixels in it; without it the losses are formed here and every counted pixel is kept.
-template <int NC, bool SELECT>
+template <int NC, bool SELECT, bool MAP>
 __global__ __launch_bounds__(256) void pc_sum_kernel(PcCall k, unsigned* __restrict__ plane, const int* __restrict__ ties,
                                                      const unsigned* __restrict__ state, double* __restrict__ part,
                                                      float* __restrict__ pixel_loss, int* __restrict__ kept, int* __restrict__ err_word) {
@@ -339,7 +352,7 @@ __global__ __launch_bounds__(256) void pc_sum_kernel(PcCall k, unsigned* __restr
       const bool keep = thr != PC_IGNORED && (key[i] > thr || (key[i] == thr && before + rank[i] < r));
       if (keep) {
         acc[0] += (double)__uint_as_float(key[i]);
-        acc[1] += (double)(k.weight ? k.weight[y] : 1.f);
+        acc[1] += pc_den<MAP>(k, q, (int)y);
       } else {
         plane[q] = key[i] | PC_DROPPED;
       }
@@ -357,10 +370,10 @@ __global__ __launch_bounds__(256) void pc_sum_kernel(PcCall k, unsigned* __restr
       const bool counted = y != k.ignore && y >= 0 && y < k.C;
       float v = 0.f;
       if (counted) {
-        pc_pixel(k, q, (int)y, x);
+        pc_pixel<NC, MAP>(k, q, (int)y, x);
         v = x.loss;
         acc[0] += (double)v;
-        acc[1] += (double)(k.weight ? k.weight[y] : 1.f);
+        acc[1] += pc_den<MAP>(k, q, (int)y);
       } else if (y != k.ignore) {
         bad = true;
         acc[0] += (double)NAN;
@@ -395,7 +408,7 @@ __global__ __launch_bounds__(256) void pc_finish_kernel(const double* __restrict
 
 // the gradient rows: kept pixels d l / d logits * grad_scale / denominator, every other pixel zeros (accumulate: left as they are);
 // classes [C, zero_to) of every pixel are written 0 when the call does not accumulate
-template <int NC, bool SELECT>
+template <int NC, bool SELECT, bool MAP>
 __global__ __launch_bounds__(256) void pc_grad_kernel(PcCall k, const unsigned* __restrict__ plane, const double* __restrict__ fin, float gs,
                                                       const float* __restrict__ gs_dev, float* __restrict__ dlogits, int64_t ds_n,
                                                       int64_t ds_c, int64_t ds_p, int accumulate, int zero_to) {
@@ -415,8 +428,13 @@ __global__ __launch_bounds__(256) void pc_grad_kernel(PcCall k, const unsigned* 
     if (SELECT) keep = keep && !(plane[q] & PC_DROPPED);
     float row[NC] = {};
     if (keep) {
-      pc_pixel(k, q, (int)y, x);
+      pc_pixel<NC, MAP>(k, q, (int)y, x);
       pc_row(k, (int)y, x, row);
+      if (MAP) {   // m is held fixed: the row of m * l
+        const float m = k.pmap[q];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) row[c] *= m;
+      }
     }
     if (!accumulate) {
 #pragma unroll
@@ -466,8 +484,12 @@ struct PcGrad {
 };
 
 int pixel_ce_run(mgu_ctx* c, const char* fn, const void* logits, const int64_t* labels, int B, int64_t HW, int C, int64_t ls_n, int64_t ls_c,
-                 int64_t ls_p, const float* weight, float eps, float gamma, double keep, int64_t min_kept, int per_image,
-                 int64_t ignore_index, float* loss, float* pixel_loss, int32_t* kept, const PcGrad* grad, hipStream_t s) {
+                 int64_t ls_p, const float* weight, const float* pmap, bool map_entry, float eps, float gamma, double keep, int64_t min_kept,
+                 int per_image, int64_t ignore_index, float* loss, float* pixel_loss, int32_t* kept, const PcGrad* grad, hipStream_t s) {
+  // the profile's kernel families: the _map entries report under names of their own
+  static const char* const NAMES[2][3] = {{"pixel_ce select", "pixel_ce sums", "pixel_ce gradient"},
+                                          {"pixel_ce_map select", "pixel_ce_map sums", "pixel_ce_map gradient"}};
+  const char* const* names = NAMES[map_entry ? 1 : 0];
   if (!logits || !labels || B < 1 || HW < 1 || C < 1 || C > 8)
     return fail(c, MGU_ERR_INVALID, "bad %s args (1 <= num_classes <= 8, a shape without pixels)", fn);
   if ((double)B * (double)HW >= (double)(1 << 30)) return fail(c, MGU_ERR_INVALID, "%s: B*HW must stay below 2^30", fn);
@@ -479,7 +501,7 @@ int pixel_ce_run(mgu_ctx* c, const char* fn, const void* logits, const int64_t* 
   HIPCHK(c, hipSetDevice(c->device));
   const bool select = keep < 1.0;
   PcCall k;
-  k.logits = (const float*)logits, k.labels = labels, k.weight = weight, k.ls_n = ls_n, k.ls_c = ls_c, k.ls_p = ls_p;
+  k.logits = (const float*)logits, k.labels = labels, k.weight = weight, k.pmap = pmap, k.ls_n = ls_n, k.ls_c = ls_c, k.ls_p = ls_p;
   k.ignore = ignore_index, k.min_kept = min_kept, k.keep = keep, k.eps = eps, k.gamma = gamma;
   k.HW = (int)HW, k.C = C, k.P = (int)(B * HW), k.G = per_image ? B : 1, k.Ng = per_image ? (int)HW : k.P;
   k.tiles_g = (k.Ng + PC_TILE - 1) / PC_TILE;
@@ -494,52 +516,74 @@ int pixel_ce_run(mgu_ctx* c, const char* fn, const void* logits, const int64_t* 
   int *hist = (int*)(ws + w.hist), *ties = (int*)(ws + w.ties);
   const int tiles = k.G * k.tiles_g;
   const dim3 grid(tiles);
+#define MGU_PC_SUM(NC, SEL, MAP) \
+  hipLaunchKernelGGL((pc_sum_kernel<NC, SEL, MAP>), grid, dim3(256), 0, s, k, plane, ties, state, part, pixel_loss, kept, err_dev)
   if (select) {
     HIPCHK(c, hipMemsetAsync(hist, 0, (size_t)PC_PASSES * k.G * 256 * 4, s));
     {
-      ProfScope ps(c, s, "pixel_ce select");
-      if (C <= 4) hipLaunchKernelGGL(pc_loss_kernel<4>, grid, dim3(256), 0, s, k, plane, hist, pixel_loss, err_dev);
-      else hipLaunchKernelGGL(pc_loss_kernel<8>, grid, dim3(256), 0, s, k, plane, hist, pixel_loss, err_dev);
+      ProfScope ps(c, s, names[0]);
+#define MGU_PC_LOSS(NC, MAP) hipLaunchKernelGGL((pc_loss_kernel<NC, MAP>), grid, dim3(256), 0, s, k, plane, hist, pixel_loss, err_dev)
+      if (pmap) {
+        if (C <= 4) MGU_PC_LOSS(4, true);
+        else MGU_PC_LOSS(8, true);
+      } else {
+        if (C <= 4) MGU_PC_LOSS(4, false);
+        else MGU_PC_LOSS(8, false);
+      }
+#undef MGU_PC_LOSS
     }
     for (int pass = 1; pass < PC_PASSES; ++pass) {
-      ProfScope ps(c, s, "pixel_ce select");
+      ProfScope ps(c, s, names[0]);
       hipLaunchKernelGGL(pc_count_kernel, grid, dim3(256), 0, s, k, plane, hist, pass);
     }
     {
-      ProfScope ps(c, s, "pixel_ce select");
+      ProfScope ps(c, s, names[0]);
       hipLaunchKernelGGL(pc_tie_count_kernel, grid, dim3(256), 0, s, k, plane, hist, ties);
     }
     {
-      ProfScope ps(c, s, "pixel_ce select");
+      ProfScope ps(c, s, names[0]);
       hipLaunchKernelGGL(pc_tie_scan_kernel, dim3(k.G), dim3(256), 0, s, k, hist, ties, state);
     }
     {
-      ProfScope ps(c, s, "pixel_ce sums");
-      hipLaunchKernelGGL((pc_sum_kernel<4, true>), grid, dim3(256), 0, s, k, plane, ties, state, part, pixel_loss, kept, err_dev);
+      ProfScope ps(c, s, names[1]);
+      if (pmap) MGU_PC_SUM(4, true, true);
+      else MGU_PC_SUM(4, true, false);
     }
   } else {
-    ProfScope ps(c, s, "pixel_ce sums");
-    if (C <= 4) hipLaunchKernelGGL((pc_sum_kernel<4, false>), grid, dim3(256), 0, s, k, plane, ties, state, part, pixel_loss, kept, err_dev);
-    else hipLaunchKernelGGL((pc_sum_kernel<8, false>), grid, dim3(256), 0, s, k, plane, ties, state, part, pixel_loss, kept, err_dev);
+    ProfScope ps(c, s, names[1]);
+    if (pmap) {
+      if (C <= 4) MGU_PC_SUM(4, false, true);
+      else MGU_PC_SUM(8, false, true);
+    } else {
+      if (C <= 4) MGU_PC_SUM(4, false, false);
+      else MGU_PC_SUM(8, false, false);
+    }
   }
   {
-    ProfScope ps(c, s, "pixel_ce sums");
+    ProfScope ps(c, s, names[1]);
     hipLaunchKernelGGL(pc_finish_kernel, dim3(1), dim3(256), 0, s, part, tiles, fin, loss);
   }
   if (grad) {
-    ProfScope ps(c, s, "pixel_ce gradient");
-#define MGU_PC_GRAD(NC, SEL)                                                                                                               \
-  hipLaunchKernelGGL((pc_grad_kernel<NC, SEL>), grid, dim3(256), 0, s, k, plane, fin, grad->scale, grad->scale_dev, grad->dlogits, grad->ds_n, \
+    ProfScope ps(c, s, names[2]);
+#define MGU_PC_GRAD(NC, SEL, MAP)                                                                                                              \
+  hipLaunchKernelGGL((pc_grad_kernel<NC, SEL, MAP>), grid, dim3(256), 0, s, k, plane, fin, grad->scale, grad->scale_dev, grad->dlogits, grad->ds_n, \
                      grad->ds_c, grad->ds_p, grad->accumulate, grad->zero_to)
+#define MGU_PC_GRAD_NC(NC, SEL)                 \
+  do {                                          \
+    if (pmap) MGU_PC_GRAD(NC, SEL, true);       \
+    else MGU_PC_GRAD(NC, SEL, false);           \
+  } while (0)
     if (select) {
-      if (C <= 4) MGU_PC_GRAD(4, true);
-      else MGU_PC_GRAD(8, true);
+      if (C <= 4) MGU_PC_GRAD_NC(4, true);
+      else MGU_PC_GRAD_NC(8, true);
     } else {
-      if (C <= 4) MGU_PC_GRAD(4, false);
-      else MGU_PC_GRAD(8, false);
+      if (C <= 4) MGU_PC_GRAD_NC(4, false);
+      else MGU_PC_GRAD_NC(8, false);
     }
+#undef MGU_PC_GRAD_NC
 #undef MGU_PC_GRAD
   }
+#undef MGU_PC_SUM
   HIPCHK(c, hipGetLastError());
   return MGU_OK;
 }
@@ -556,8 +600,8 @@ int mgu_pixel_ce(mgu_ctx* c, const void* logits_dev, const int64_t* labels_dev, 
                  void* hip_stream) {
   if (!c) return MGU_ERR_INVALID;
   if (!loss_dev) return fail(c, MGU_ERR_INVALID, "bad pixel_ce args (loss_dev is NULL)");
-  return pixel_ce_run(c, "pixel_ce", logits_dev, labels_dev, B, HW, num_classes, ls_n, ls_c, ls_p, class_weight_dev, label_smoothing,
-                      focal_gamma, keep_fraction, min_kept, per_image, ignore_index, loss_dev, pixel_loss_dev, kept_dev, nullptr,
+  return pixel_ce_run(c, "pixel_ce", logits_dev, labels_dev, B, HW, num_classes, ls_n, ls_c, ls_p, class_weight_dev, nullptr, false,
+                      label_smoothing, focal_gamma, keep_fraction, min_kept, per_image, ignore_index, loss_dev, pixel_loss_dev, kept_dev, nullptr,
                       (hipStream_t)hip_stream);
 }
 
@@ -571,9 +615,36 @@ int mgu_pixel_ce_backward(mgu_ctx* c, const void* logits_dev, const int64_t* lab
   PcGrad g;
   g.scale = grad_scale, g.scale_dev = grad_scale_dev, g.dlogits = (float*)dlogits_dev;
   g.ds_n = ds_n, g.ds_c = ds_c, g.ds_p = ds_p, g.accumulate = accumulate, g.zero_to = zero_to;
-  return pixel_ce_run(c, "pixel_ce_backward", logits_dev, labels_dev, B, HW, num_classes, ls_n, ls_c, ls_p, class_weight_dev,
-                      label_smoothing, focal_gamma, keep_fraction, min_kept, per_image, ignore_index, loss_dev, nullptr, nullptr, &g,
+  return pixel_ce_run(c, "pixel_ce_backward", logits_dev, labels_dev, B, HW, num_classes, ls_n, ls_c, ls_p, class_weight_dev, nullptr,
+                      false, label_smoothing, focal_gamma, keep_fraction, min_kept, per_image, ignore_index, loss_dev, nullptr, nullptr, &g,
                       (hipStream_t)hip_stream);
+}
+
+// the same two entries with a per-pixel weight map m (fp32 (B, HW), dense, >= 0; nullptr: the entries above, bit for bit)
+int mgu_pixel_ce_map(mgu_ctx* c, const void* logits_dev, const int64_t* labels_dev, int B, int64_t HW, int num_classes, int64_t ls_n,
+                     int64_t ls_c, int64_t ls_p, const float* class_weight_dev, const float* pixel_weight_dev, float label_smoothing,
+                     float focal_gamma, double keep_fraction, int64_t min_kept, int per_image, int64_t ignore_index, float* loss_dev,
+                     float* pixel_loss_dev, int32_t* kept_dev, void* hip_stream) {
+  if (!c) return MGU_ERR_INVALID;
+  if (!loss_dev) return fail(c, MGU_ERR_INVALID, "bad pixel_ce_map args (loss_dev is NULL)");
+  return pixel_ce_run(c, "pixel_ce_map", logits_dev, labels_dev, B, HW, num_classes, ls_n, ls_c, ls_p, class_weight_dev, pixel_weight_dev,
+                      true, label_smoothing, focal_gamma, keep_fraction, min_kept, per_image, ignore_index, loss_dev, pixel_loss_dev,
+                      kept_dev, nullptr, (hipStream_t)hip_stream);
+}
+
+int mgu_pixel_ce_map_backward(mgu_ctx* c, const void* logits_dev, const int64_t* labels_dev, int B, int64_t HW, int num_classes, int64_t ls_n,
+                              int64_t ls_c, int64_t ls_p, const float* class_weight_dev, const float* pixel_weight_dev,
+                              float label_smoothing, float focal_gamma, double keep_fraction, int64_t min_kept, int per_image,
+                              int64_t ignore_index, float grad_scale, const float* grad_scale_dev, void* dlogits_dev, int64_t ds_n,
+                              int64_t ds_c, int64_t ds_p, int accumulate, int zero_to, float* loss_dev, void* hip_stream) {
+  if (!c) return MGU_ERR_INVALID;
+  if (!dlogits_dev) return fail(c, MGU_ERR_INVALID, "bad pixel_ce_map_backward args (dlogits_dev is NULL)");
+  PcGrad g;
+  g.scale = grad_scale, g.scale_dev = grad_scale_dev, g.dlogits = (float*)dlogits_dev;
+  g.ds_n = ds_n, g.ds_c = ds_c, g.ds_p = ds_p, g.accumulate = accumulate, g.zero_to = zero_to;
+  return pixel_ce_run(c, "pixel_ce_map_backward", logits_dev, labels_dev, B, HW, num_classes, ls_n, ls_c, ls_p, class_weight_dev,
+                      pixel_weight_dev, true, label_smoothing, focal_gamma, keep_fraction, min_kept, per_image, ignore_index, loss_dev,
+                      nullptr, nullptr, &g, (hipStream_t)hip_stream);
 }
 
 }  // extern "C"

@@ -10,6 +10,7 @@ from .preprocess import EdgeDetector, GaussianSmoother, HistogramEqualizer, Imag
 from .metrics import SegmentationEvaluator, allreduce_eval_state, evaluate_segmentation, metrics_from_confusion, segmentation_metrics  # noqa: F401
 from .objects import (ObjectShapes, ObjectTable, YieldEvaluator, clean_masks, connected_components, distance_transform,  # noqa: F401
                       evaluate_yield, object_shapes, split_objects, yield_estimation_metrics)
+from .border import border_distances, border_weights  # noqa: F401
 from .tta import object_scores, predict_tta  # noqa: F401
 from .instances import (InstanceEvaluator, OverlapTable, evaluate_instances, instance_metrics, match_masks, object_detection_mAP,  # noqa: F401
                         object_overlaps, panoptic_totals)
@@ -30,4 +31,4 @@ __all__ = ["SuperpixelGraph", "connect_regions", "lab_tables", "region_adjacency
            "patch_features_u8", "patch_node_features", "patch_labels", "postprocess_segmentation", "DetectionHead", "FeatureFusion", "region_stage", "region_mean_pool", "region_fuse", "region_edge_index", "MinCutRefinement", "PatchSegmentPredictor", "graph_cut", "cut_capacities", "cut_energy", "GraphCut", "graph_cut_multi", "label_costs", "cut_energy_multi", "MultiCut", "UNet", "UNetEncoder", "UNetDecoder", "ConvBlock", "DecoderBlock", "GATNetwork", "MultiHeadGATLayer",
            "GraphAttentionLayer", "PatchGraphConstructor", "MinGraphUNet", "MinGraphUNetE2E", "segment_batch", "argmax_classes",
            "gat_forward_csr", "shard_batch", "segmentation_metrics", "metrics_from_confusion", "SegmentationEvaluator", "evaluate_segmentation",
-           "allreduce_eval_state", "clean_masks", "connected_components", "ObjectTable", "yield_estimation_metrics", "YieldEvaluator", "evaluate_yield", "object_shapes", "ObjectShapes", "object_overlaps", "OverlapTable", "match_masks", "panoptic_totals", "instance_metrics", "object_detection_mAP", "InstanceEvaluator", "evaluate_instances", "boundary_tables", "BoundaryTables", "boundary_metrics", "BoundaryEvaluator", "evaluate_boundaries", "frame_shifts", "link_objects", "track_ids", "VideoCounter", "count_video", "predict_tta", "object_scores", "predict_tiled", "tile_grid", "tile_weights", "refine_probs", "bilateral_tables", "EdgeRefiner", "Trainer", "E2ETrainer", "FlatAdam", "StepLR", "adam_state_dict", "allreduce_mean_", "load_config", "get_config_recursively", "build_from_config", "build", "lib"]
+           "allreduce_eval_state", "clean_masks", "connected_components", "border_distances", "border_weights", "ObjectTable", "yield_estimation_metrics", "YieldEvaluator", "evaluate_yield", "object_shapes", "ObjectShapes", "object_overlaps", "OverlapTable", "match_masks", "panoptic_totals", "instance_metrics", "object_detection_mAP", "InstanceEvaluator", "evaluate_instances", "boundary_tables", "BoundaryTables", "boundary_metrics", "BoundaryEvaluator", "evaluate_boundaries", "frame_shifts", "link_objects", "track_ids", "VideoCounter", "count_video", "predict_tta", "object_scores", "predict_tiled", "tile_grid", "tile_weights", "refine_probs", "bilateral_tables", "EdgeRefiner", "Trainer", "E2ETrainer", "FlatAdam", "StepLR", "adam_state_dict", "allreduce_mean_", "load_config", "get_config_recursively", "build_from_config", "build", "lib"]

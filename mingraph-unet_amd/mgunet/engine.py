@@ -10,6 +10,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._args import check_masks, nhwc_storage
+from .border import border_options
 from .gat import GATNetwork, _csr_cache, _layer_forward, _LayerCall
 from .losses import _LOVASZ_CLASSES, pixel_ce_options
 from .patch_graph import PatchGraphConstructor
@@ -226,7 +227,8 @@ class Trainer:
 
     def __init__(self, model: UNet, lr=1e-3, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, process_group=None, comm="auto",
                  loss="ce", dice_smooth=1.0, optimizer="adam", momentum=0.9, lovasz_per_image=False, lovasz_classes="present",
-                 ce_weight=None, label_smoothing=0.0, focal_gamma=0.0, hard_fraction=1.0, hard_min_kept=0, hard_per_image=False):
+                 ce_weight=None, label_smoothing=0.0, focal_gamma=0.0, hard_fraction=1.0, hard_min_kept=0, hard_per_image=False,
+                 border_w0=0.0, border_sigma=5.0, border_connectivity=2, border_separate=False):
         """comm: "auto" (default) -- with more than one rank the gradient is mean-all-reduced by torch.distributed (RCCL when the
         backend is "nccl") after backward: the path exercised with two ranks.  "rccl" -- opt in to libmgunet's own RCCL
         communicator with the bucketed exchange overlapped with backward (mgu_unet_backward_allreduce); tests/test_gpu_rccl.py
@@ -240,6 +242,13 @@ class Trainer:
         losses.pixel_cross_entropy (weight, label_smoothing, focal_gamma, keep_fraction, min_kept, per_image; INTEGRATION.md section
         S).  With all six at their defaults the cross-entropy term is mgu_cross_entropy, exactly as before; otherwise one
         mgu_pixel_ce_backward call takes its place and the dice / Lovasz terms accumulate after it as they do after the plain one.
+        border_w0, border_sigma, border_connectivity, border_separate: the U-Net paper's border weight map (mgunet.border_weights,
+        INTEGRATION.md section V).  With border_w0 > 0 every step labels its masks (the `instances` given to train_step, else
+        mgu_connected_components of the class masks with border_connectivity, foreground = not class 0), forms the map
+        ce_weight[class] + border_w0 exp(-(d1 + d2)^2 / (2 border_sigma^2)) on the device and hands it to mgu_pixel_ce_map_backward,
+        which takes the cross-entropy call's place (the class weights are then in the map, not in the loss a second time);
+        border_separate also trains on the target with touching instances set one pixel apart.  With border_w0 == 0, the default,
+        the step launches nothing new and calls exactly what it called before.
         ("rccl" also creates the communicator for a single process: the collective then degenerates to a copy.)
         optimizer: "adam" (train_segmentation.py:96, the shipped configs/training.yaml) or "sgd" -- the script's other branch,
         optim.SGD(lr, momentum=sgd_momentum, weight_decay) (:97-98; training.yaml:5-6): one fused kernel on the flat buffers either way."""
@@ -250,6 +259,11 @@ class Trainer:
         if lovasz_classes not in _LOVASZ_CLASSES:
             raise ValueError(f"unknown lovasz_classes {lovasz_classes!r}: 'present' or 'all'")
         pixel_ce = pixel_ce_options(ce_weight, label_smoothing, focal_gamma, hard_fraction, hard_min_kept, hard_per_image, getattr(model, "num_classes", None))
+        if border_connectivity not in (1, 2):
+            raise ValueError(f"border_connectivity must be 1 (4-neighbours) or 2 (8-neighbours), got {border_connectivity}")
+        w0, sigma = border_options(border_w0, border_sigma)
+        if w0 > 0.0:
+            border_options(w0, sigma, getattr(model, "num_classes", None), ce_weight)
         self.optimizer, self.momentum = optimizer, float(momentum)
         params = list(model.named_parameters())
         _lib.require_hip(params[0][1], "Trainer")
@@ -284,6 +298,8 @@ class Trainer:
         # the pixel cross-entropy's options, None while all of them are at their defaults (the step then calls mgu_cross_entropy)
         self.pixel_ce = None if ce_weight is None and pixel_ce == (0.0, 0.0, 1.0, 0, 0) else pixel_ce
         self.ce_weight = None if ce_weight is None else ce_weight.detach().to(device=dev, dtype=torch.float32).contiguous()
+        # the border weight map's options, None while border_w0 == 0 (the step then forms no map)
+        self.border = None if w0 == 0.0 else (w0, sigma, int(border_connectivity), bool(border_separate))
         self._loss = torch.zeros(1, device=dev, dtype=torch.float32)
         self._dice = torch.zeros(1, device=dev, dtype=torch.float32)
         self._rccl = False
@@ -397,10 +413,32 @@ class Trainer:
             self.load_optimizer_state_dict(ck["optimizer_state_dict"])
         return ck if isinstance(ck, dict) else {"model_state_dict": ck}
 
-    def forward_backward(self, images: torch.Tensor, masks: torch.Tensor, exchange: bool = False) -> torch.Tensor:
+    def _border_map(self, masks: torch.Tensor, instances, num_classes: int, ctx):
+        """(weight map fp32 (B, H, W), the target the cross-entropy trains on) of this step's masks: mgu_border_weights' two launches
+        on `instances`, or on the labels mgu_connected_components makes of the masks first; no host synchronisation."""
+        w0, sigma, connectivity, separate = self.border
+        B, H, W = masks.shape
+        dev = self.device
+        if instances is None:
+            lab = torch.empty((B, H, W), device=dev, dtype=torch.int32)
+            _lib.call("mgu_connected_components", dev, masks, 0, B, H, W, 0, connectivity, 0, int(num_classes), 0, lab,
+                      torch.empty(B, device=dev, dtype=torch.int64), torch.empty(B + 1, device=dev, dtype=torch.int64), ctx=ctx)
+        else:
+            if not isinstance(instances, torch.Tensor) or instances.is_floating_point() or not instances.is_cuda:
+                raise TypeError("instances must be an integer tensor on the HIP device")
+            check_masks(instances, B, H, W)
+            lab = instances.to(torch.int32).contiguous()
+        weight = torch.empty((B, H, W), device=dev, dtype=torch.float32)
+        target = torch.empty((B, H, W), device=dev, dtype=torch.int64) if separate else None
+        _lib.call("mgu_border_weights", dev, lab, B, H, W, masks, self.ce_weight, 0 if self.ce_weight is None else self.ce_weight.numel(),
+                  w0, sigma, 0, None, None, None, weight, target, ctx=ctx)
+        return weight, (target if separate else masks)
+
+    def forward_backward(self, images: torch.Tensor, masks: torch.Tensor, exchange: bool = False, instances=None) -> torch.Tensor:
         """Fills self.grad with d(mean CE)/d(params) of this rank's shard; returns the loss (device scalar).
         exchange=True (needs attach_rccl): the gradient comes back already averaged over the ranks, the all-reduce having run
-        bucket by bucket behind the layers still being differentiated."""
+        bucket by bucket behind the layers still being differentiated.  instances: with border_w0 > 0, the int (B, H, W) instance
+        map of the masks (0 = background) in the place of their connected components."""
         model, dev = self.model, self.device
         if masks.dtype != torch.int64 or not masks.is_cuda:
             raise TypeError("masks must be an int64 tensor on the HIP device")
@@ -415,7 +453,11 @@ class Trainer:
         ldd = (Cc + 3) // 4 * 4
         dlogits = torch.empty((npix, ldd), device=dev, dtype=torch.float32)
         loss = self._loss
-        if self.pixel_ce is None:
+        if self.border is not None:   # the class weights are the map's class term: the loss takes the map alone
+            pmap, target = self._border_map(masks, instances, Cc, ctx)
+            _lib.call("mgu_pixel_ce_map_backward", dev, nhwc, target, B, H * W, Cc, H * W * Cc, 1, Cc, None, pmap,
+                      *(self.pixel_ce or (0.0, 0.0, 1.0, 0, 0)), -100, 1.0, None, dlogits, H * W * ldd, 1, ldd, 0, ldd, self._loss, ctx=ctx)
+        elif self.pixel_ce is None:
             _lib.call("mgu_cross_entropy", dev, nhwc, masks, npix, Cc, 1.0 / npix, dlogits, self._loss, ctx=ctx)
         else:   # weights, smoothing, the focal term or hard-pixel mining: the same rows of dlogits, padding classes zeroed
             _lib.call("mgu_pixel_ce_backward", dev, nhwc, masks, B, H * W, Cc, H * W * Cc, 1, Cc, self.ce_weight, *self.pixel_ce, -100,
@@ -448,12 +490,12 @@ class Trainer:
                       self.betas[1], self.eps, self.wd, self.step_count, grad_scale, ctx=ctx)
         model.refresh_packed_weights(dev)   # same tensors, new contents: repack in place (no state_dict round trip per step)
 
-    def train_step(self, images: torch.Tensor, masks: torch.Tensor) -> torch.Tensor:
+    def train_step(self, images: torch.Tensor, masks: torch.Tensor, instances=None) -> torch.Tensor:
         if self._rccl:   # the only data-path collective of the build, issued from inside backward
-            loss = self.forward_backward(images, masks, exchange=True)
+            loss = self.forward_backward(images, masks, exchange=True, instances=instances)
             self.optimizer_step(1.0)
             return loss
-        loss = self.forward_backward(images, masks)
+        loss = self.forward_backward(images, masks, instances=instances)
         scale = allreduce_mean_(self.grad, self.group) if self.comm is not None else 1.0   # torch.distributed (RCCL / gloo); 1 rank: no-op
         self.optimizer_step(scale)
         return loss

@@ -10,7 +10,8 @@ check_labels(device) synchronises and raises where F.one_hot would have raised o
     FeatureConsistencyLoss   model/unet/feature_loss.py:5-125
     EllipticalShapeLoss      model/unet/shape_loss.py:6-180
     lovasz_softmax           the build's own addition (the reference has no IoU surrogate): INTEGRATION.md section Q
-    pixel_cross_entropy      the build's own addition (class weights, label smoothing, focal term, hard-pixel mining): section S
+    pixel_cross_entropy      the build's own addition (class weights, label smoothing, focal term, hard-pixel mining): section S;
+                             with pixel_weight= a per-pixel weight map such as border.border_weights': section V
 """
 from __future__ import annotations
 
@@ -186,17 +187,26 @@ def pixel_ce_options(weight, label_smoothing, focal_gamma, keep_fraction, min_ke
     return eps, gamma, keep, kmin, int(bool(per_image))
 
 
+def _pixel_ce_entry(name, pd, target, weight, pixel_weight):
+    """The entry point and the arguments up to the options: mgu_pixel_ce[_backward], or with a map mgu_pixel_ce_map[_backward], which
+    takes it after the class weights."""
+    B, C_, H, W = pd.shape
+    head = (pd.device, pd, target, B, H * W, C_, pd.stride(0), pd.stride(1), pd.stride(3), weight)
+    if pixel_weight is None:
+        return (name,) + head
+    return (name.replace("mgu_pixel_ce", "mgu_pixel_ce_map"),) + head + (pixel_weight,)
+
+
 class _PixelCEFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx_, pred, target, weight, opts, ignore_index):
+    def forward(ctx_, pred, target, weight, opts, ignore_index, pixel_weight=None):
         pd = _pixel_strided(_f32(pred))
         B, C_, H, W = pd.shape
         target = target.contiguous()
         out = torch.empty((), device=pd.device, dtype=torch.float32)
-        _lib.call("mgu_pixel_ce", pd.device, pd, target, B, H * W, C_, pd.stride(0), pd.stride(1), pd.stride(3), weight, *opts, ignore_index,
-                  out, None, None)
+        _lib.call(*_pixel_ce_entry("mgu_pixel_ce", pd, target, weight, pixel_weight), *opts, ignore_index, out, None, None)
         ctx_.save_for_backward(pd, target)
-        ctx_.weight, ctx_.opts, ctx_.in_dtype = weight, (opts, ignore_index), pred.dtype
+        ctx_.weight, ctx_.opts, ctx_.in_dtype, ctx_.pixel_weight = weight, (opts, ignore_index), pred.dtype, pixel_weight
         return out
 
     @staticmethod
@@ -206,9 +216,9 @@ class _PixelCEFn(torch.autograd.Function):
         d = torch.empty_strided(pd.shape, pd.stride(), device=pd.device, dtype=torch.float32)   # NHWC storage stays NHWC
         g = g.detach().float().contiguous()
         opts, ignore_index = ctx_.opts
-        _lib.call("mgu_pixel_ce_backward", pd.device, pd, target, B, H * W, C_, pd.stride(0), pd.stride(1), pd.stride(3), ctx_.weight, *opts,
-                  ignore_index, 1.0, g, d, d.stride(0), d.stride(1), d.stride(3), 0, 0, None)
-        return d.to(ctx_.in_dtype), None, None, None, None
+        _lib.call(*_pixel_ce_entry("mgu_pixel_ce_backward", pd, target, ctx_.weight, ctx_.pixel_weight), *opts, ignore_index, 1.0, g, d,
+                  d.stride(0), d.stride(1), d.stride(3), 0, 0, None)
+        return d.to(ctx_.in_dtype), None, None, None, None, None   # the map is held fixed: it gets no gradient
 
 
 def _pixel_ce_args(pred, target, weight, label_smoothing, focal_gamma, keep_fraction, min_kept, per_image, ignore_index):
@@ -221,21 +231,35 @@ def _pixel_ce_args(pred, target, weight, label_smoothing, focal_gamma, keep_frac
     return weight, opts, int(ignore_index)
 
 
+def pixel_weight_map(pixel_weight, pred):
+    """The per-pixel weight map of pixel_cross_entropy as the kernels read it: float32 (B, H, W), dense, on pred's device, detached
+    (None stays None).  ValueError on another shape."""
+    if pixel_weight is None:
+        return None
+    B, _, H, W = pred.shape
+    if not isinstance(pixel_weight, torch.Tensor) or tuple(pixel_weight.shape) != (B, H, W):
+        raise ValueError(f"pixel_weight must be a (B, H, W) = {(B, H, W)} tensor")
+    return pixel_weight.detach().to(device=pred.device, dtype=torch.float32).contiguous()
+
+
 def pixel_cross_entropy(pred, target, weight=None, label_smoothing=0.0, focal_gamma=0.0, keep_fraction=1.0, min_kept=0, per_image=False,
-                        ignore_index=-100):
+                        ignore_index=-100, pixel_weight=None):
     """Imbalance-aware pixel-wise cross-entropy: pred (B, C, H, W) logits with C <= 8 (any strides
     dice_loss accepts), target (B, H, W) int64.  weight (C floats >= 0) and label_smoothing are nn.CrossEntropyLoss's; focal_gamma
     >= 1 multiplies each pixel's term by (1 - p_y)^gamma (Lin et al. 2017; takes no label_smoothing); keep_fraction < 1 keeps only
     the hardest pixels: of the n counted pixels of the batch (per_image: of each image) the min(n, max(min_kept, ceil(keep_fraction
     n))) with the largest loss, equal losses in pixel order, and only they carry value and gradient.  loss = sum of the kept
     losses / sum of their class weights.  Differentiable w.r.t. pred.  A label outside [0, C) other than ignore_index makes the loss
-    NaN and is reported by check_labels(pred.device) (no host sync inside the call)."""
+    NaN and is reported by check_labels(pred.device) (no host sync inside the call).
+    pixel_weight: a per-pixel weight map m >= 0 of shape (B, H, W), for example mgunet.border_weights' (INTEGRATION.md section V):
+    every pixel's loss becomes m l, that product is what the mining ranks, loss = sum_kept m l / sum_kept m w_y, and m itself gets
+    no gradient.  A map of ones gives the bits of the call without one."""
     return _PixelCEFn.apply(pred, target, *_pixel_ce_args(pred, target, weight, label_smoothing, focal_gamma, keep_fraction, min_kept,
-                                                          per_image, ignore_index))
+                                                          per_image, ignore_index), pixel_weight_map(pixel_weight, pred))
 
 
 def _pixel_ce_debug(pred, target, weight=None, label_smoothing=0.0, focal_gamma=0.0, keep_fraction=1.0, min_kept=0, per_image=False,
-                    ignore_index=-100):
+                    ignore_index=-100, pixel_weight=None):
     """(loss, pixel_loss, kept) through the test hooks of mgu_pixel_ce: pixel_loss fp32 (B, H, W), the loss of every pixel (0 where
     it is not counted), and kept int32 (B, H, W): 1 kept, 0 dropped, -1 not counted."""
     weight, opts, ignore_index = _pixel_ce_args(pred, target, weight, label_smoothing, focal_gamma, keep_fraction, min_kept, per_image,
@@ -245,8 +269,8 @@ def _pixel_ce_debug(pred, target, weight=None, label_smoothing=0.0, focal_gamma=
     out = torch.empty((), device=pd.device, dtype=torch.float32)
     pixel_loss = torch.empty((B, H, W), device=pd.device, dtype=torch.float32)
     kept = torch.empty((B, H, W), device=pd.device, dtype=torch.int32)
-    _lib.call("mgu_pixel_ce", pd.device, pd, target.contiguous(), B, H * W, C_, pd.stride(0), pd.stride(1), pd.stride(3), weight, *opts,
-              ignore_index, out, pixel_loss, kept)
+    _lib.call(*_pixel_ce_entry("mgu_pixel_ce", pd, target.contiguous(), weight, pixel_weight_map(pixel_weight, pd)), *opts, ignore_index,
+              out, pixel_loss, kept)
     return out, pixel_loss, kept
 
 
