@@ -933,6 +933,39 @@ int mgu_gaussian_blur_u8(mgu_ctx* ctx, const uint8_t* img_dev, int B, int H, int
  * launch; patch 1..64, weights as above. */
 int mgu_patch_smooth_mean_u8(mgu_ctx* ctx, const uint8_t* rgb_dev, int B, int H, int W, int patch, const int32_t* kx_host, int kw,
                              const int32_t* ky_host, int kh, int per_channel, float* out_dev, int ld_out, int col0, void* hip_stream);
+/* Contrast-limited adaptive histogram equalisation (cv2.createCLAHE(clipLimit, tileGridSize).apply on 8-bit images), csrc/clahe.hip;
+ * INTEGRATION.md section W.  The reference has no such stage.  img (B,H,W,channels) interleaved uint8, channels 1 or 3 -> out of the same
+ * shape; grid_y x grid_x tiles, each in 1..64; clip_limit <= 0: no clipping.  channels 1: the plane v is the image; channels 3: v is Y of
+ * cv2's RGB2YUV and the output pixel is YUV2RGB(out_v, U, V) with the pixel's own U and V, as mgu_equalize_hist_rgb_u8 around its table.
+ * THIS BUILD'S DEFINITION, after OpenCV 4.x clahe.cpp for 8-bit images; cv2 is absent from this build, so equality with a cv2 build is
+ * NOT verified.  Bitwise equal to tests/clahe_oracle.py and from run to run.
+ *   geometry  H % grid_y == 0 and W % grid_x == 0: He, We = H, W.  Otherwise BOTH He = H + grid_y - H % grid_y and
+ *             We = W + grid_x - W % grid_x (OpenCV's rule: an axis that divides is still extended by a whole grid when the other does
+ *             not; 64 x 60 with 8 x 8 tiles gives 72 x 64).  th = He / grid_y, tw = We / grid_x, area = th * tw.  Extended pixel (y, x)
+ *             reads v[r(y, H)][r(x, W)], r = reflect-101 applied until the index is inside (n == 1 gives 0); no extended image is written.
+ *   table     of tile (ty, tx): h[256] over the tile's area extended pixels.  clip_limit > 0: cl = max(1, (int)(clip_limit * area / 256))
+ *             (double, on the host); clipped = sum max(h[i] - cl, 0); h[i] = min(h[i], cl) + clipped / 256; residual = clipped % 256; if
+ *             residual > 0, step = max(256 / residual, 1) and the bins k * step, k = 0 .. residual - 1, get one more each (OpenCV's loop in
+ *             closed form; the sum of h is area again; no second clipping round).  lut[i] = sat8(rint((float)S_i * lutScale)), S_i the
+ *             int32 inclusive sum converted to fp32, lutScale = 255.0f / (float)area (host), one rounded fp32 product, rint half to even.
+ *   pixel     all fp32, EVERY operation rounded on its own (no fused multiply-add), inv_tw = 1.0f / (float)tw and inv_th on the host:
+ *               txf = (float)x * inv_tw - 0.5f;  tx1 = floor(txf);  xa = txf - (float)tx1;  xa1 = 1.0f - xa
+ *               tx2 = min(tx1 + 1, grid_x - 1);  tx1 = max(tx1, 0)        (clamped after xa is formed; likewise ty1, ty2, ya, ya1)
+ *               res = (lut[ty1][tx1][v] * xa1 + lut[ty1][tx2][v] * xa) * ya1 + (lut[ty2][tx1][v] * xa1 + lut[ty2][tx2][v] * xa) * ya
+ *               out = sat8(rint(res))
+ * luts_dev: optional DEVICE (B, grid_y, grid_x, 256) uint8 that receives the tables; NULL keeps them in context scratch
+ * (B * grid_y * grid_x * 256 bytes).  out_dev == img_dev is allowed (the tables are complete before the second launch, and each pixel is
+ * read and written by one thread); any other overlap of the two, or of the tables with either, is MGU_ERR_INVALID, as are channels other
+ * than 1 or 3, a grid outside 1..64, a non-finite clip_limit, NULL pointers, H*W >= 2^31 and B > 65535.  Exactly two launches whatever B,
+ * the grid and the data are; no host synchronisation. */
+int mgu_clahe_u8(mgu_ctx* ctx, const uint8_t* img_dev, int B, int H, int W, int channels, int grid_y, int grid_x, double clip_limit,
+                 uint8_t* out_dev, uint8_t* luts_dev, void* hip_stream);
+/* The equalised column block of the node features from CLAHE: columns [col0, col0 + (per_channel ? 3 : 1)) of rows (B*nph*npw, ld_out)
+ * fp32 get, bit for bit, what mgu_patch_mean_u8 gives on mgu_clahe_u8 of image b of rgb (B,H,W,3) -- same zero padding bottom / right,
+ * row order and mean expression -- without writing an equalised image.  Other columns are not touched.  Two launches (the table launch
+ * is mgu_clahe_u8's, into context scratch); patch 1..64, the other arguments as above. */
+int mgu_patch_clahe_mean_u8(mgu_ctx* ctx, const uint8_t* rgb_dev, int B, int H, int W, int patch, int grid_y, int grid_x, double clip_limit,
+                            int per_channel, float* out_dev, int ld_out, int col0, void* hip_stream);
 /* ---- edge-aware refinement of class probabilities (csrc/refine.hip) ---------------------------------------------
  * Every class plane is filtered `iterations` times with a joint bilateral kernel guided by the photograph, then argmax: cost-volume
  * filtering (Hosni et al., PAMI 2013), the message-passing step of a dense CRF.  The reference has NO such stage: what follows is THIS

@@ -2,6 +2,7 @@
 // defined here and nowhere else under csrc/ (tests/test_csrc_helpers.py).  device.h keeps what every kernel file shares.
 //   device: wave_by_key | block_exclusive_scan | chunk_sum_scan | the pair table (PairTable, pair_add, degree / pour / place kernels;
 //           superpixels.hip shares it with instances.hip) | object_index | objects_recorded | pix_key | foreground_class
+//           (clahe.hip takes block_exclusive_scan for the cumulative histogram of a tile)
 //   host:   check_pixel_count | clear_counts | distance_transform, distance_transform_dims (declared here, defined in split.hip)
 #pragma once
 #include <climits>

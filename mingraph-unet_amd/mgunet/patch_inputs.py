@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 from ._args import nhwc_storage
-from .preprocess import _to_dev_u8, patch_smooth_features_u8
+from .preprocess import CLAHE, _to_dev_u8, patch_clahe_features_u8, patch_smooth_features_u8
 
 MAX_CLASSES = 32   # mgu_patch_labels: lane c of a wave counts class c
 
@@ -39,7 +39,7 @@ def feature_width(repeat: int = 16, unet_cols: int = 0, per_channel: bool = True
 
 
 def patch_node_features(images_u8, patch_size: int, images: torch.Tensor = None, repeat: int = 16, unet_patch_feats: torch.Tensor = None,
-                        per_channel: bool = True, pad_to: int = 4, out: torch.Tensor = None, smoother=None) -> torch.Tensor:
+                        per_channel: bool = True, pad_to: int = 4, out: torch.Tensor = None, smoother=None, equalizer=None) -> torch.Tensor:
     """images_u8: (H, W, 3) or (B, H, W, 3) RGB uint8, numpy or tensor -> (B*Np, F) float32 rows on the device, image b's patches at rows
     [b*Np, (b+1)*Np) in raster order (zero padded bottom / right, as image_to_patches).  Columns: the mean of the normalised float
     batch `images` (B, 3, H, W) -- NCHW or the U-Net's NHWC-storage view, read by strides, no copy -- over the patch and its channels,
@@ -47,7 +47,12 @@ def patch_node_features(images_u8, patch_size: int, images: torch.Tensor = None,
     wrote); the mean Sobel byte; the mean equalised bytes per channel (or over all three); zeros up to F = the used columns rounded up
     to a multiple of pad_to (the GAT wants Fin % 4 == 0).  With `smoother` (a GaussianSmoother) the "Smooth" block of
     graph_refinement.py:81 follows the equalised columns: the mean bytes of smoother.smooth(image b), per channel or over all three as
-    per_channel says -- one more launch, no smoothed image written; without it the output and the launches are unchanged."""
+    per_channel says -- one more launch, no smoothed image written; without it the output and the launches are unchanged.  With
+    `equalizer` (a CLAHE) the equalised columns hold the mean bytes of equalizer.apply(image b) instead of the globally equalised image's
+    -- two more launches after the call that fills the row, no equalised image written; the row width and every other column stay as
+    they are, and equalizer=None makes exactly the calls and the bytes it made before."""
+    if equalizer is not None and not isinstance(equalizer, CLAHE):
+        raise TypeError("equalizer must be a CLAHE instance or None")
     if images is not None:
         if not isinstance(images, torch.Tensor) or images.dtype != torch.float32:
             raise TypeError("images must be a float32 (B, 3, H, W) tensor")
@@ -85,6 +90,8 @@ def patch_node_features(images_u8, patch_size: int, images: torch.Tensor = None,
         raise ValueError(f"`out` must be a contiguous float32 ({rows}, {F}) tensor on the images' device")
     _lib.call("mgu_patch_node_features_u8", dev, u8, B, H, W, p, images, *strides, int(repeat) if images is not None else 0,
               unet_patch_feats, cu, 1 if per_channel else 0, out, F)
+    if equalizer is not None:    # over the equalised block the call above wrote
+        patch_clahe_features_u8(u8, p, equalizer, per_channel, out=out, col0=(int(repeat) if images is not None else 0) + cu + 1)
     if smoother is not None:     # after the call above, which zeroes every column past its own
         patch_smooth_features_u8(u8, p, smoother, per_channel, out=out, col0=_used_columns(repeat, cu, per_channel, images is not None))
     return out

@@ -3,6 +3,7 @@
     ImagePreprocessor        preprocessing/image_preprocessing/image_preprocess.py:6-126
     EdgeDetector             preprocessing/graph_feature_processing/edge_detection.py:4-44
     HistogramEqualizer       preprocessing/graph_feature_processing/histogram_equalization.py:4-49
+    CLAHE                    (no counterpart: cv2.createCLAHE(clipLimit, tileGridSize).apply as this build defines it)
     GaussianSmoother         preprocessing/graph_feature_processing/gaussian_smoothing.py:4-34
     patch_features_u8        scripts/graph_refinement.py:97-104   (image_to_patches(...).mean(...))
     postprocess_segmentation scripts/infer_segmentation.py:20-51
@@ -411,10 +412,108 @@ class EdgeDetector:
         return _rgb_op("mgu_sobel_edges_u8", image_array_rgb, 1)
 
 
+MAX_CLAHE_GRID = 64   # mgu_clahe_u8: tiles per axis
+
+
+class CLAHE:
+    """cv2.createCLAHE(clipLimit, tileGridSize) on uint8 as this build defines it (include/mgunet.h, mgu_clahe_u8): a clipped histogram and
+    a byte table per tile, the four nearest tables blended bilinearly in fp32, every operation rounded on its own.  It follows OpenCV
+    4.x's clahe.cpp for 8-bit images; cv2 is not a dependency, and equality with an actual cv2 build is not verified.  The defaults and
+    the (x, y) order of tile_grid_size are cv2's; clip_limit <= 0 clips nothing.  A 3-channel image is equalised on the Y plane of cv2's
+    YUV, as HistogramEqualizer.equalize_histogram_rgb."""
+
+    def __init__(self, clip_limit=40.0, tile_grid_size=(8, 8)):
+        self.clip_limit = float(clip_limit)
+        if not math.isfinite(self.clip_limit):
+            raise ValueError(f"clip_limit must be finite, got {clip_limit}")
+        try:
+            gx, gy = (int(v) for v in tile_grid_size)
+        except (TypeError, ValueError):
+            raise ValueError(f"tile_grid_size must be two integers (x, y), got {tile_grid_size!r}")
+        if (gx, gy) != tuple(tile_grid_size) or not (1 <= gx <= MAX_CLAHE_GRID and 1 <= gy <= MAX_CLAHE_GRID):
+            raise ValueError(f"tile_grid_size must be two integers in 1..{MAX_CLAHE_GRID} (x, y), got {tile_grid_size!r}")
+        self.tile_grid_size = (gx, gy)
+
+    @property
+    def grid_yx(self):
+        return self.tile_grid_size[1], self.tile_grid_size[0]
+
+    @staticmethod
+    def _batch_shape(images, channels):
+        """(B, H, W, C) of what `images` holds, checked on the metadata alone"""
+        if not isinstance(images, (np.ndarray, torch.Tensor)):
+            raise TypeError("Input must be a NumPy array or a tensor.")
+        if images.dtype != (np.uint8 if isinstance(images, np.ndarray) else torch.uint8):
+            raise TypeError(f"expected a uint8 image, got {images.dtype}")
+        s = tuple(int(v) for v in images.shape)
+        if channels not in (None, 1, 3):
+            raise ValueError(f"channels must be 1 or 3, got {channels}")
+        if len(s) == 2 and channels in (None, 1):
+            full = (1,) + s + (1,)
+        elif len(s) == 3 and channels == 1 and s[2] != 1:
+            full = s + (1,)                                  # a grey batch, only when stated
+        elif len(s) == 3 and s[2] in (1, 3) and channels in (None, s[2]):
+            full = (1,) + s
+        elif len(s) == 4 and s[3] in (1, 3) and channels in (None, s[3]):
+            full = s
+        else:
+            raise ValueError(f"expected (H, W), (H, W, 3), (B, H, W, 1 | 3) or, with channels=1, (B, H, W) uint8 images; got {s}"
+                             + (f" with channels={channels}" if channels is not None else ""))
+        if 0 in full:
+            raise ValueError(f"expected non-empty images, got {s}")
+        return full
+
+    def _run(self, images, channels, out, tables):
+        B, H, W, ch = self._batch_shape(images, channels)
+        if out is not None and (type(out) is not type(images) or tuple(out.shape) != tuple(images.shape) or out.dtype != images.dtype):
+            raise ValueError("`out` must be of the kind, shape and dtype of the images")
+        img, was_np = _to_dev_u8(images)
+        if out is None or was_np:
+            res = torch.empty_like(img)
+        else:
+            if out.device != img.device or not out.is_contiguous():
+                raise ValueError("`out` must be a contiguous tensor on the images' device")
+            res = out
+        gy, gx = self.grid_yx
+        luts = torch.empty((B, gy, gx, 256), device=img.device, dtype=torch.uint8) if tables else None
+        _lib.call("mgu_clahe_u8", img.device, img, B, H, W, ch, gy, gx, self.clip_limit, res, luts)
+        if tables:
+            return luts.cpu().numpy() if was_np else luts
+        if not was_np:
+            return res
+        host = res.cpu().numpy()
+        if out is None:
+            return host
+        out[...] = host
+        return out
+
+    def apply(self, images, out=None, channels=None):
+        """(H, W), (H, W, 3), (B, H, W, 1 | 3) or -- only with channels=1 -- a (B, H, W) grey batch, uint8 -> the same shape, two launches
+        for the batch.  numpy in -> numpy out, device tensor in -> device tensor out; out: where the result goes (the images themselves
+        are allowed: in place)."""
+        return self._run(images, channels, out, False)
+
+    def tables(self, images, channels=None):
+        """-> the uint8 (B, grid_y, grid_x, 256) tables of the tiles (B = 1 for one image)"""
+        return self._run(images, channels, None, True)
+
+
 class HistogramEqualizer:
     def equalize_histogram_rgb(self, image_array_rgb):
         """(H, W, 3) RGB uint8 -> (H, W, 3): luminance histogram equalised in YUV."""
         return _rgb_op("mgu_equalize_hist_rgb_u8", image_array_rgb, 3)
+
+    def clahe_rgb(self, image_array_rgb, clip_limit=40.0, tile_grid_size=(8, 8)):
+        """(H, W, 3) RGB uint8 -> (H, W, 3): CLAHE(clip_limit, tile_grid_size) on the luminance in YUV."""
+        if isinstance(image_array_rgb, (np.ndarray, torch.Tensor)) and (image_array_rgb.ndim != 3 or image_array_rgb.shape[2] != 3):
+            raise ValueError("Input image must be an RGB image (H, W, 3).")
+        return CLAHE(clip_limit, tile_grid_size).apply(image_array_rgb, channels=3)
+
+    def clahe_gray(self, image_array, clip_limit=40.0, tile_grid_size=(8, 8)):
+        """(H, W) uint8 -> (H, W): CLAHE(clip_limit, tile_grid_size) of a grey image."""
+        if isinstance(image_array, (np.ndarray, torch.Tensor)) and image_array.ndim != 2:
+            raise ValueError("Input image must be a grey image (H, W).")
+        return CLAHE(clip_limit, tile_grid_size).apply(image_array, channels=1)
 
 
 MAX_GAUSSIAN_KSIZE = 31   # mgu_gaussian_blur_u8: the tile and its halo live in LDS
@@ -498,11 +597,9 @@ class GaussianSmoother:
         return out.cpu().numpy() if was_np else out
 
 
-def patch_smooth_features_u8(images_u8, patch_size: int, smoother: GaussianSmoother, per_channel: bool = False, out: torch.Tensor = None,
-                             col0: int = 0) -> torch.Tensor:
-    """patch_features_u8(smoother.smooth(image b), patch_size, per_channel) for every image of an (H, W, 3) / (B, H, W, 3) RGB uint8
-    batch, bit for bit, in one launch and without the smoothed images: (B*Np, 3 | 1) float32, or columns [col0, col0 + (3 | 1)) of the
-    contiguous float32 (B*Np, F) tensor `out`, whose other columns are left alone."""
+def _patch_column_args(images_u8, patch_size, per_channel, out, col0):
+    """what the fused patch-column calls share: the (B, H, W, 3) device batch, the patch size, and the rows the columns go to (`out`
+    checked, or a new (B*Np, 3 | 1) tensor at column 0)"""
     u8, _ = _to_dev_u8(images_u8)
     if u8.dim() == 3:
         u8 = u8.unsqueeze(0)
@@ -517,7 +614,32 @@ def patch_smooth_features_u8(images_u8, patch_size: int, smoother: GaussianSmoot
         out, col0 = torch.empty((rows, n), device=u8.device, dtype=torch.float32), 0
     elif out.dim() != 2 or out.shape[0] != rows or out.dtype != torch.float32 or out.device != u8.device or not out.is_contiguous():
         raise ValueError(f"`out` must be a contiguous float32 ({rows}, F) tensor on the images' device")
-    _lib.call("mgu_patch_smooth_mean_u8", u8.device, u8, B, H, W, p, *smoother._taps(), 1 if per_channel else 0, out, out.shape[1], int(col0))
+    return u8, p, out, int(col0)
+
+
+def patch_smooth_features_u8(images_u8, patch_size: int, smoother: GaussianSmoother, per_channel: bool = False, out: torch.Tensor = None,
+                             col0: int = 0) -> torch.Tensor:
+    """patch_features_u8(smoother.smooth(image b), patch_size, per_channel) for every image of an (H, W, 3) / (B, H, W, 3) RGB uint8
+    batch, bit for bit, in one launch and without the smoothed images: (B*Np, 3 | 1) float32, or columns [col0, col0 + (3 | 1)) of the
+    contiguous float32 (B*Np, F) tensor `out`, whose other columns are left alone."""
+    u8, p, out, col0 = _patch_column_args(images_u8, patch_size, per_channel, out, col0)
+    B, H, W, _c = u8.shape
+    _lib.call("mgu_patch_smooth_mean_u8", u8.device, u8, B, H, W, p, *smoother._taps(), 1 if per_channel else 0, out, out.shape[1], col0)
+    return out
+
+
+def patch_clahe_features_u8(images_u8, patch_size: int, clahe: CLAHE, per_channel: bool = False, out: torch.Tensor = None,
+                            col0: int = 0) -> torch.Tensor:
+    """patch_features_u8(clahe.apply(image b), patch_size, per_channel) for every image of an (H, W, 3) / (B, H, W, 3) RGB uint8 batch,
+    bit for bit, in two launches and without the equalised images: (B*Np, 3 | 1) float32, or columns [col0, col0 + (3 | 1)) of the
+    contiguous float32 (B*Np, F) tensor `out`, whose other columns are left alone."""
+    if not isinstance(clahe, CLAHE):
+        raise TypeError("clahe must be a CLAHE instance")
+    u8, p, out, col0 = _patch_column_args(images_u8, patch_size, per_channel, out, col0)
+    B, H, W, _c = u8.shape
+    gy, gx = clahe.grid_yx
+    _lib.call("mgu_patch_clahe_mean_u8", u8.device, u8, B, H, W, p, gy, gx, clahe.clip_limit, 1 if per_channel else 0, out, out.shape[1],
+              col0)
     return out
 
 
