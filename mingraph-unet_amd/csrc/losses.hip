@@ -10,7 +10,7 @@
 // the masks: raw coordinate moments per object, then the Mahalanobis residuals with the 2 x 2 inverse in closed form.
 #include <algorithm>
 
-#include "ctx.h"
+#include "loss_common.h"
 
 namespace mgu {
 
@@ -64,19 +64,8 @@ __global__ __launch_bounds__(256) void dice_partial_kernel(const float* __restri
   bool bad = false;
   for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < HW; i += (int64_t)gridDim.x * 256) {
     const float* p = logits + b * ls_n + i * ls_p;
-    float l[NC], mx = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      l[c] = c < Cc ? p[c * ls_c] : -INFINITY;
-      mx = fmaxf(mx, l[c]);
-    }
-    float se = 0.f;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      l[c] = c < Cc ? expf(l[c] - mx) : 0.f;
-      se += l[c];
-    }
-    const float inv = 1.f / se;
+    float l[NC], mx;
+    const float inv = 1.f / softmax_front(p, ls_c, Cc, l, mx);
     const long long y = labels[b * HW + i];
     if (y < 0 || y >= Cc) bad = true;     // F.one_hot raises on such a label (:34)
 #pragma unroll
@@ -92,16 +81,22 @@ __global__ __launch_bounds__(256) void dice_partial_kernel(const float* __restri
   if (threadIdx.x == 0)
     for (int k = 0; k < 3 * NC; ++k) part[((size_t)b * gridDim.x + blockIdx.x) * 3 * NC + k] = v[k];
 }
+// the (I, P, T) of (b, c): the records of the image's nb workgroups, in their order
+template <int NC>
+__device__ __forceinline__ void dice_fold(const double* __restrict__ part, int b, int c, int nb, double& I, double& P, double& T) {
+  I = 0, P = 0, T = 0;
+  for (int k = 0; k < nb; ++k) {
+    const double* p = part + ((size_t)b * nb + k) * 3 * NC;
+    I += p[c], P += p[NC + c], T += p[2 * NC + c];
+  }
+}
 template <int NC>
 __global__ void dice_final_kernel(const double* __restrict__ part, int B, int nb, int Cc, double smooth, float* __restrict__ out) {
   double acc = 0;
   for (int b = 0; b < B; ++b)
     for (int c = 0; c < Cc; ++c) {
-      double I = 0, P = 0, T = 0;
-      for (int k = 0; k < nb; ++k) {
-        const double* p = part + ((size_t)b * nb + k) * 3 * NC;
-        I += p[c], P += p[NC + c], T += p[2 * NC + c];
-      }
+      double I, P, T;
+      dice_fold<NC>(part, b, c, nb, I, P, T);
       acc += (2.0 * I + smooth) / (P + T + smooth);   // :39
     }
   *out = (float)(1.0 - acc / ((double)B * Cc));       // :40
@@ -144,9 +139,7 @@ __global__ void sum_final_kernel(const double* __restrict__ part, int nb, double
 
 // ---- gradients of the differentiable losses (the reference obtains them from autograd: loss.backward() at
 // scripts/train_segmentation.py:133, scripts/train_end_to_end.py:478) ---------------------------------------------------------
-// Every backward kernel multiplies by gs = grad_scale * (*grad_scale_dev if given): the upstream gradient of the scalar loss,
-// as a host number, a device scalar (an autograd grad_output: no host synchronisation) or both.
-__device__ __forceinline__ float up_scale(float gs, const float* __restrict__ gs_dev) { return gs_dev ? gs * *gs_dev : gs; }
+// Every backward kernel multiplies by the upstream gradient of the scalar loss: up_scale (loss_common.h) of grad_scale and grad_scale_dev.
 
 // d TVLoss / dx (scripts/train_end_to_end.py:84-88): each squared difference feeds its two end points
 __global__ __launch_bounds__(256) void tv_bwd_kernel(const float* __restrict__ x, int B, int Cc, int H, int W, int64_t sn, int64_t sc,
@@ -180,11 +173,8 @@ __global__ void dice_coef_kernel(const double* __restrict__ part, int B, int nb,
   const int b = t / NC, c = t - b * NC;
   float c0 = 0.f, c1 = 0.f;
   if (c < Cc) {
-    double I = 0, P = 0, T = 0;
-    for (int k = 0; k < nb; ++k) {
-      const double* p = part + ((size_t)b * nb + k) * 3 * NC;
-      I += p[c], P += p[NC + c], T += p[2 * NC + c];
-    }
+    double I, P, T;
+    dice_fold<NC>(part, b, c, nb, I, P, T);
     const double U = P + T + smooth, inv = 1.0 / ((double)B * Cc);
     c0 = (float)(-2.0 * inv / U);
     c1 = (float)((2.0 * I + smooth) * inv / (U * U));
@@ -205,19 +195,8 @@ __global__ __launch_bounds__(256) void dice_bwd_kernel(const float* __restrict__
   for (int c = 0; c < NC; ++c) c0[c] = coef[(b * 2 + 0) * NC + c], c1[c] = coef[(b * 2 + 1) * NC + c];
   for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < HW; i += (int64_t)gridDim.x * 256) {
     const float* p = logits + b * ls_n + i * ls_p;
-    float l[NC], mx = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      l[c] = c < Cc ? p[c * ls_c] : -INFINITY;
-      mx = fmaxf(mx, l[c]);
-    }
-    float se = 0.f;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      l[c] = c < Cc ? expf(l[c] - mx) : 0.f;
-      se += l[c];
-    }
-    const float inv = 1.f / se;
+    float l[NC], mx;
+    const float inv = 1.f / softmax_front(p, ls_c, Cc, l, mx);
     const long long y = labels[b * HW + i];
     float q[NC], dot = 0.f;
 #pragma unroll
@@ -416,21 +395,14 @@ int mgu_dice_loss(mgu_ctx* c, const void* logits_dev, const int64_t* labels_dev,
   double* ws;
   int rc = loss_scratch(c, (size_t)B * nb * 24, &ws);
   if (rc) return rc;
-  if (!c->err_word) {
-    HIPCHK(c, hipHostMalloc((void**)&c->err_word, sizeof(int), hipHostMallocMapped));
-    *c->err_word = 0;
-  }
   int* err_dev = nullptr;
-  HIPCHK(c, hipHostGetDevicePointer((void**)&err_dev, c->err_word, 0));
-  if (num_classes <= 4) {
-    hipLaunchKernelGGL(dice_partial_kernel<4>, dim3(nb, B), dim3(256), 0, s, (const float*)logits_dev, labels_dev, HW, num_classes, ls_n,
+  if ((rc = err_word_dev(c, &err_dev))) return rc;
+  with_nc(num_classes, [&](auto nc) {
+    constexpr int NC = decltype(nc)::value;
+    hipLaunchKernelGGL(dice_partial_kernel<NC>, dim3(nb, B), dim3(256), 0, s, (const float*)logits_dev, labels_dev, HW, num_classes, ls_n,
                        ls_c, ls_p, ws, err_dev);
-    hipLaunchKernelGGL(dice_final_kernel<4>, dim3(1), dim3(1), 0, s, ws, B, nb, num_classes, (double)smooth, loss_dev);
-  } else {
-    hipLaunchKernelGGL(dice_partial_kernel<8>, dim3(nb, B), dim3(256), 0, s, (const float*)logits_dev, labels_dev, HW, num_classes, ls_n,
-                       ls_c, ls_p, ws, err_dev);
-    hipLaunchKernelGGL(dice_final_kernel<8>, dim3(1), dim3(1), 0, s, ws, B, nb, num_classes, (double)smooth, loss_dev);
-  }
+    hipLaunchKernelGGL(dice_final_kernel<NC>, dim3(1), dim3(1), 0, s, ws, B, nb, num_classes, (double)smooth, loss_dev);
+  });
   HIPCHK(c, hipGetLastError());
   return MGU_OK;
 }
@@ -463,25 +435,17 @@ int mgu_dice_loss_backward(mgu_ctx* c, const void* logits_dev, const int64_t* la
   int rc = loss_scratch(c, (size_t)B * nb * 24 + (size_t)B * 8, &ws);   // partial records + the coefficient table (floats)
   if (rc) return rc;
   float* coef = (float*)(ws + (size_t)B * nb * 24);
-  if (!c->err_word) {
-    HIPCHK(c, hipHostMalloc((void**)&c->err_word, sizeof(int), hipHostMallocMapped));
-    *c->err_word = 0;
-  }
   int* err_dev = nullptr;
-  HIPCHK(c, hipHostGetDevicePointer((void**)&err_dev, c->err_word, 0));
-#define MGU_DICE_BWD(NC)                                                                                                             \
-  hipLaunchKernelGGL(dice_partial_kernel<NC>, dim3(nb, B), dim3(256), 0, s, (const float*)logits_dev, labels_dev, HW, num_classes, ls_n, \
-                     ls_c, ls_p, ws, err_dev);                                                                                       \
-  if (loss_dev) hipLaunchKernelGGL(dice_final_kernel<NC>, dim3(1), dim3(1), 0, s, ws, B, nb, num_classes, (double)smooth, loss_dev);   \
-  hipLaunchKernelGGL(dice_coef_kernel<NC>, dim3((B * NC + 63) / 64), dim3(64), 0, s, ws, B, nb, num_classes, (double)smooth, coef);    \
-  hipLaunchKernelGGL(dice_bwd_kernel<NC>, dim3(nb, B), dim3(256), 0, s, (const float*)logits_dev, labels_dev, HW, num_classes, ls_n,   \
-                     ls_c, ls_p, coef, grad_scale, grad_scale_dev, (float*)dlogits_dev, ds_n, ds_c, ds_p, accumulate)
-  if (num_classes <= 4) {
-    MGU_DICE_BWD(4);
-  } else {
-    MGU_DICE_BWD(8);
-  }
-#undef MGU_DICE_BWD
+  if ((rc = err_word_dev(c, &err_dev))) return rc;
+  with_nc(num_classes, [&](auto nc) {
+    constexpr int NC = decltype(nc)::value;
+    hipLaunchKernelGGL(dice_partial_kernel<NC>, dim3(nb, B), dim3(256), 0, s, (const float*)logits_dev, labels_dev, HW, num_classes, ls_n,
+                       ls_c, ls_p, ws, err_dev);
+    if (loss_dev) hipLaunchKernelGGL(dice_final_kernel<NC>, dim3(1), dim3(1), 0, s, ws, B, nb, num_classes, (double)smooth, loss_dev);
+    hipLaunchKernelGGL(dice_coef_kernel<NC>, dim3((B * NC + 63) / 64), dim3(64), 0, s, ws, B, nb, num_classes, (double)smooth, coef);
+    hipLaunchKernelGGL(dice_bwd_kernel<NC>, dim3(nb, B), dim3(256), 0, s, (const float*)logits_dev, labels_dev, HW, num_classes, ls_n,
+                       ls_c, ls_p, coef, grad_scale, grad_scale_dev, (float*)dlogits_dev, ds_n, ds_c, ds_p, accumulate);
+  });
   HIPCHK(c, hipGetLastError());
   return MGU_OK;
 }

@@ -20,42 +20,20 @@
 // profiles/lovasz_bench.txt goes the same way, spread 0.2 %), so four it is.
 #include <algorithm>
 
+#include "loss_common.h"
 #include "objects_common.h"
 
 namespace mgu {
 
-constexpr int LV_ITEMS = 16;                 // keys per thread
-constexpr int LV_TILE = 256 * LV_ITEMS;      // keys one workgroup ranks per pass
+// A workgroup ranks the LOSS_TILE keys of one tile (loss_common.h) per pass; segment (c, g) of a LossCall is plane c, positions
+// [g * Ng, (g + 1) * Ng).
 constexpr unsigned LV_KEY_MASK = 0x3FFFFFFFu, LV_KEY_IGNORED = 0x40000000u;
 constexpr unsigned LV_PAY_FG = 0x80000000u, LV_PAY_BAD = 0x40000000u, LV_PAY_PIX = 0x3FFFFFFFu;
 
-// what every kernel knows of the call: the logits and labels, and how the P = B * HW pixels fall into G groups of Ng pixels (the
-// batch, or one image each) of tiles_g tiles; segment (c, g) is plane c, positions [g * Ng, (g + 1) * Ng)
-struct LvCall {
-  const float* logits;
-  const int64_t* labels;
-  int64_t ls_n, ls_c, ls_p;
-  long long ignore;
-  int HW, C, P, G, Ng, tiles_g;
-};
-
-struct LvTile {
-  int c, seg, tile, lo, n;   // class, segment c * G + g, tile of the segment, its first position inside the segment, its keys
-  size_t first;              // index of that position in the class plane arrays
-};
-__device__ __forceinline__ LvTile lv_tile(const LvCall& k) {
-  LvTile t;
-  const int g = blockIdx.x / k.tiles_g;
-  t.c = blockIdx.y, t.tile = blockIdx.x - g * k.tiles_g, t.seg = t.c * k.G + g;
-  t.lo = t.tile * LV_TILE, t.n = min(LV_TILE, k.Ng - t.lo);
-  t.first = (size_t)t.c * k.P + (size_t)g * k.Ng + t.lo;
-  return t;
-}
-
-// Key and payload of pixel q for class c.  The softmax is the dice kernels' (expf(l - max), one reciprocal); the error is ONE
+// Key and payload of pixel q for class c.  The softmax is the dice kernels' (softmax_front, one reciprocal); the error is ONE
 // subtraction, so a saturated softmax gives exactly 0.0f or 1.0f.  Contraction is off: the histogram and the scatter of the first
 // pass both come through here and must see the same bits.
-__device__ __forceinline__ void lv_key(const LvCall& k, int q, int c, unsigned& key, unsigned& pay, float& err, bool& bad) {
+__device__ __forceinline__ void lv_key(const LossCall& k, int q, int c, unsigned& key, unsigned& pay, float& err, bool& bad) {
 #pragma clang fp contract(off)
   const long long y = k.labels[q];
   if (y == k.ignore) {
@@ -64,19 +42,11 @@ __device__ __forceinline__ void lv_key(const LvCall& k, int q, int c, unsigned& 
   }
   const int b = q / k.HW;
   const float* p = k.logits + b * k.ls_n + (int64_t)(q - b * k.HW) * k.ls_p;
-  float l[8], mx = -INFINITY;
+  float e[8], mx, lc = 0.f;
+  const float se = softmax_front(p, k.ls_c, k.C, e, mx);
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    l[j] = j < k.C ? p[j * k.ls_c] : -INFINITY;
-    mx = fmaxf(mx, l[j]);
-  }
-  float se = 0.f, lc = 0.f;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float e = j < k.C ? expf(l[j] - mx) : 0.f;
-    se += e;
-    if (j == c) lc = e;
-  }
+  for (int j = 0; j < 8; ++j)
+    if (j == c) lc = e[j];   // a select per class: e stays in registers
   const float inv = 1.f / se, pc = lc * inv;
   const bool fg = y == c, wrong = y < 0 || y >= k.C;
   err = fminf(fmaxf(fg ? 1.f - pc : pc, 0.f), 1.f);   // the clamp moves nothing on finite logits: it keeps the key inside 30 bits
@@ -88,22 +58,22 @@ __device__ __forceinline__ void lv_key(const LvCall& k, int q, int c, unsigned& 
 // ---- one sort pass: histogram, scan, scatter ------------------------------------------------------------------------------------
 // hist[(seg * BINS + digit) * tiles_g + tile]: keys of the tile with that digit
 template <int BITS, bool FROM_LOGITS>
-__global__ __launch_bounds__(256) void lv_hist_kernel(LvCall k, const unsigned* __restrict__ keys_in, int shift, int* __restrict__ hist,
+__global__ __launch_bounds__(256) void lv_hist_kernel(LossCall k, const unsigned* __restrict__ keys_in, int shift, int* __restrict__ hist,
                                                       int* __restrict__ err_word) {
   constexpr int BINS = 1 << BITS;
   __shared__ int cnt[BINS];
   for (int d = threadIdx.x; d < BINS; d += 256) cnt[d] = 0;
   __syncthreads();
-  const LvTile t = lv_tile(k);
+  const LossTile t = loss_tile(k);
   bool bad = false;
 #pragma unroll 4
-  for (int i = 0; i < LV_ITEMS; ++i) {
+  for (int i = 0; i < LOSS_ITEMS; ++i) {
     const int j = i * 256 + threadIdx.x;
     if (j < t.n) {
       unsigned key, pay;
       float err;
-      if (FROM_LOGITS) lv_key(k, (int)(t.first - (size_t)t.c * k.P) + j, t.c, key, pay, err, bad);
-      else key = keys_in[t.first + j];
+      if (FROM_LOGITS) lv_key(k, t.first + j, t.c, key, pay, err, bad);
+      else key = keys_in[t.pfirst + j];
       atomicAdd(&cnt[(key >> shift) & (BINS - 1)], 1);
     }
   }
@@ -139,7 +109,7 @@ __global__ __launch_bounds__(256) void lv_rowscan_kernel(int* __restrict__ a, in
 // workgroup forms it again: at most 8 entries per thread) is where a digit starts in the segment.  Order of the keys of a tile: wave,
 // item, lane -- their order in the input.
 template <int BITS, bool FROM_LOGITS>
-__global__ __launch_bounds__(256) void lv_scatter_kernel(LvCall k, const unsigned* __restrict__ keys_in, const unsigned* __restrict__ pay_in,
+__global__ __launch_bounds__(256) void lv_scatter_kernel(LossCall k, const unsigned* __restrict__ keys_in, const unsigned* __restrict__ pay_in,
                                                          int shift, const int* __restrict__ offs, const int* __restrict__ dtot,
                                                          unsigned* __restrict__ keys_out, unsigned* __restrict__ pay_out,
                                                          float* __restrict__ errors) {
@@ -147,7 +117,7 @@ __global__ __launch_bounds__(256) void lv_scatter_kernel(LvCall k, const unsigne
   __shared__ int cnt[4 * BINS];
   __shared__ int dbase[BINS];
   __shared__ int shs[4];
-  const LvTile t = lv_tile(k);
+  const LossTile t = loss_tile(k);
   {
     int mine_tot[PER], sum = 0;
 #pragma unroll
@@ -157,7 +127,7 @@ __global__ __launch_bounds__(256) void lv_scatter_kernel(LvCall k, const unsigne
       sum += mine_tot[r];
     }
     int total;
-    int at = block_exclusive_scan(sum, shs, &total) + (t.seg - t.c * k.G) * k.Ng;   // the segment's first position in the class plane
+    int at = block_exclusive_scan(sum, shs, &total) + t.g * k.Ng;   // the segment's first position in the class plane
 #pragma unroll
     for (int r = 0; r < PER; ++r) {
       const int d = threadIdx.x * PER + r;
@@ -169,22 +139,22 @@ __global__ __launch_bounds__(256) void lv_scatter_kernel(LvCall k, const unsigne
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int* mine = cnt + wave * BINS;
-  unsigned key[LV_ITEMS], pay[LV_ITEMS];
-  int rank[LV_ITEMS];
+  unsigned key[LOSS_ITEMS], pay[LOSS_ITEMS];
+  int rank[LOSS_ITEMS];
   bool bad = false;
 #pragma unroll
-  for (int i = 0; i < LV_ITEMS; ++i) {
-    const int j = wave * (64 * LV_ITEMS) + i * 64 + lane;
+  for (int i = 0; i < LOSS_ITEMS; ++i) {
+    const int j = loss_item(i);
     const bool valid = j < t.n;
     key[i] = 0, pay[i] = 0;
     if (valid) {
       if (FROM_LOGITS) {
-        const int q = (int)(t.first - (size_t)t.c * k.P) + j;
+        const int q = t.first + j;
         float err;
         lv_key(k, q, t.c, key[i], pay[i], err, bad);
         if (errors) errors[(size_t)t.c * k.P + q] = err;
       } else {
-        key[i] = keys_in[t.first + j], pay[i] = pay_in[t.first + j];
+        key[i] = keys_in[t.pfirst + j], pay[i] = pay_in[t.pfirst + j];
       }
     }
     const unsigned d = (key[i] >> shift) & (BINS - 1);
@@ -219,8 +189,8 @@ __global__ __launch_bounds__(256) void lv_scatter_kernel(LvCall k, const unsigne
   }
   __syncthreads();
 #pragma unroll
-  for (int i = 0; i < LV_ITEMS; ++i) {
-    const int j = wave * (64 * LV_ITEMS) + i * 64 + lane;
+  for (int i = 0; i < LOSS_ITEMS; ++i) {
+    const int j = loss_item(i);
     if (j < t.n) {
       const int pos = mine[(key[i] >> shift) & (BINS - 1)] + rank[i];
       if ((unsigned)pos < (unsigned)k.P) {   // always, for a histogram of these very keys
@@ -233,14 +203,14 @@ __global__ __launch_bounds__(256) void lv_scatter_kernel(LvCall k, const unsigne
 
 // ---- over the sorted order ------------------------------------------------------------------------------------------------------
 // foreground pixels per tile
-__global__ __launch_bounds__(256) void lv_count_kernel(LvCall k, const unsigned* __restrict__ pay, int* __restrict__ fgc) {
+__global__ __launch_bounds__(256) void lv_count_kernel(LossCall k, const unsigned* __restrict__ pay, int* __restrict__ fgc) {
   __shared__ int sh[4];
-  const LvTile t = lv_tile(k);
+  const LossTile t = loss_tile(k);
   int s = 0;
 #pragma unroll 4
-  for (int i = 0; i < LV_ITEMS; ++i) {
+  for (int i = 0; i < LOSS_ITEMS; ++i) {
     const int j = i * 256 + threadIdx.x;
-    if (j < t.n) s += pay[t.first + j] >> 31;
+    if (j < t.n) s += pay[t.pfirst + j] >> 31;
   }
   int total;
   block_exclusive_scan(s, sh, &total);
@@ -251,20 +221,20 @@ __global__ __launch_bounds__(256) void lv_count_kernel(LvCall k, const unsigned*
 // pixels among ranks 1 .. k, U = G + k - F (the union), I = G - F (what is left of the intersection):
 //   foreground pixel 1 / U;  background pixel I / (U (U - 1));  G == 0: 1 at rank 1, else 0
 // in double, rounded once into gbuf[c][pixel]; an ignored pixel gets 0 and rank -1.  part[seg][tile] = sum e * g over the tile.
-__global__ __launch_bounds__(256) void lv_apply_kernel(LvCall k, const unsigned* __restrict__ keys, const unsigned* __restrict__ pay,
+__global__ __launch_bounds__(256) void lv_apply_kernel(LossCall k, const unsigned* __restrict__ keys, const unsigned* __restrict__ pay,
                                                        const int* __restrict__ fgoff, const int* __restrict__ seg_fg,
                                                        float* __restrict__ gbuf, int* __restrict__ ranks, double* __restrict__ part) {
   __shared__ int shs[4];
   __shared__ double shd[4];
-  const LvTile t = lv_tile(k);
-  const int j0 = threadIdx.x * LV_ITEMS;   // a thread owns consecutive ranks
-  unsigned key[LV_ITEMS], py[LV_ITEMS];
+  const LossTile t = loss_tile(k);
+  const int j0 = threadIdx.x * LOSS_ITEMS;   // a thread owns consecutive ranks
+  unsigned key[LOSS_ITEMS], py[LOSS_ITEMS];
   int s = 0;
 #pragma unroll
-  for (int i = 0; i < LV_ITEMS; ++i) {
+  for (int i = 0; i < LOSS_ITEMS; ++i) {
     const bool valid = j0 + i < t.n;
-    key[i] = valid ? keys[t.first + j0 + i] : LV_KEY_IGNORED;
-    py[i] = valid ? pay[t.first + j0 + i] : 0u;
+    key[i] = valid ? keys[t.pfirst + j0 + i] : LV_KEY_IGNORED;
+    py[i] = valid ? pay[t.pfirst + j0 + i] : 0u;
     s += py[i] >> 31;
   }
   int total;
@@ -272,7 +242,7 @@ __global__ __launch_bounds__(256) void lv_apply_kernel(LvCall k, const unsigned*
   const int G = seg_fg[t.seg];
   double acc[1] = {0.0};
 #pragma unroll
-  for (int i = 0; i < LV_ITEMS; ++i) {
+  for (int i = 0; i < LOSS_ITEMS; ++i) {
     if (j0 + i >= t.n) continue;
     const unsigned pix = py[i] & LV_PAY_PIX;
     if (pix >= (unsigned)k.P) continue;   // never: payloads are pixel indices
@@ -331,11 +301,11 @@ __global__ __launch_bounds__(64) void lv_finish_kernel(const double* __restrict_
 // image lacks, under "all"), and d_j (1 - p_j) as a difference loses ulp(1) / (1 - p_j) there -- 6e-6 of the LARGEST gradient element
 // at p_j = 0.99, which is what torch's own fp32 softmax backward loses.  C terms more per class; the pass stays bound by its loads.
 template <int NC>
-__global__ __launch_bounds__(256) void lv_bwd_kernel(LvCall k, const float* __restrict__ gbuf, const float* __restrict__ wtab, float gs,
+__global__ __launch_bounds__(256) void lv_bwd_kernel(LossCall k, const float* __restrict__ gbuf, const float* __restrict__ wtab, float gs,
                                                      const float* __restrict__ gs_dev, float* __restrict__ dlogits, int64_t ds_n,
                                                      int64_t ds_c, int64_t ds_p, int accumulate) {
   const int b = blockIdx.y, grp = k.G > 1 ? b : 0;
-  const float up = gs_dev ? gs * *gs_dev : gs;
+  const float up = up_scale(gs, gs_dev);
   float w[NC];
 #pragma unroll
   for (int c = 0; c < NC; ++c) w[c] = c < k.C ? wtab[c * k.G + grp] : 0.f;
@@ -351,19 +321,8 @@ __global__ __launch_bounds__(256) void lv_bwd_kernel(LvCall k, const float* __re
       continue;
     }
     const float* p = k.logits + b * k.ls_n + i * k.ls_p;
-    float l[NC], mx = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      l[c] = c < k.C ? p[c * k.ls_c] : -INFINITY;
-      mx = fmaxf(mx, l[c]);
-    }
-    float se = 0.f;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      l[c] = c < k.C ? expf(l[c] - mx) : 0.f;
-      se += l[c];
-    }
-    const float inv = 1.f / se;
+    float l[NC], mx;
+    const float inv = 1.f / softmax_front(p, k.ls_c, k.C, l, mx);
     float dp[NC];
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
@@ -419,49 +378,33 @@ LvScratch lv_scratch(int64_t P, int C, int G, int tiles_g, int max_bits) {
 }
 
 template <bool FROM_LOGITS>
-void lv_pass(int bits, const LvCall& k, dim3 grid, hipStream_t s, const unsigned* kin, const unsigned* pin, int shift, int* hist, int* dtot,
+void lv_pass(int bits, const LossCall& k, dim3 grid, hipStream_t s, const unsigned* kin, const unsigned* pin, int shift, int* hist, int* dtot,
              int* err_dev, unsigned* kout, unsigned* pout, float* errors) {
-#define MGU_LV_PASS(BITS)                                                                                                                  \
-  hipLaunchKernelGGL((lv_hist_kernel<BITS, FROM_LOGITS>), grid, dim3(256), 0, s, k, kin, shift, hist, err_dev);                            \
-  hipLaunchKernelGGL(lv_rowscan_kernel, dim3((k.C * k.G << BITS) / 4), dim3(256), 0, s, hist, k.C * k.G << BITS, k.tiles_g, dtot);          \
-  hipLaunchKernelGGL((lv_scatter_kernel<BITS, FROM_LOGITS>), grid, dim3(256), 0, s, k, kin, pin, shift, hist, dtot, kout, pout, errors)
-  if (bits == 7) {
-    MGU_LV_PASS(7);
-  } else if (bits == 8) {
-    MGU_LV_PASS(8);
-  } else if (bits == 10) {
-    MGU_LV_PASS(10);
-  } else {
-    MGU_LV_PASS(11);
-  }
-#undef MGU_LV_PASS
+  const auto pass = [&](auto width) {
+    constexpr int BITS = decltype(width)::value;
+    hipLaunchKernelGGL((lv_hist_kernel<BITS, FROM_LOGITS>), grid, dim3(256), 0, s, k, kin, shift, hist, err_dev);
+    hipLaunchKernelGGL(lv_rowscan_kernel, dim3((k.C * k.G << BITS) / 4), dim3(256), 0, s, hist, k.C * k.G << BITS, k.tiles_g, dtot);
+    hipLaunchKernelGGL((lv_scatter_kernel<BITS, FROM_LOGITS>), grid, dim3(256), 0, s, k, kin, pin, shift, hist, dtot, kout, pout, errors);
+  };
+  if (bits == 7) pass(int_c<7>{});
+  else if (bits == 8) pass(int_c<8>{});
+  else if (bits == 10) pass(int_c<10>{});
+  else pass(int_c<11>{});
 }
 
-struct LvGrad {
-  float scale = 1.f;
-  const float* scale_dev = nullptr;
-  float* dlogits = nullptr;
-  int64_t ds_n = 0, ds_c = 0, ds_p = 0;
-  int accumulate = 0;
-};
+const char* const LV_HINT = "1 <= num_classes <= 8, classes_mode 0 = present / 1 = all";
 
 int lovasz_run(mgu_ctx* c, const char* fn, const void* logits, const int64_t* labels, int B, int64_t HW, int C, int64_t ls_n, int64_t ls_c,
                int64_t ls_p, int classes_mode, int per_image, int64_t ignore_index, float* loss, float* errors, int32_t* ranks,
-               const LvGrad* grad, hipStream_t s) {
-  if (!logits || !labels || B < 1 || HW < 1 || C < 1 || C > 8 || classes_mode < 0 || classes_mode > 1)
-    return fail(c, MGU_ERR_INVALID, "bad %s args (1 <= num_classes <= 8, classes_mode 0 = present / 1 = all)", fn);
-  if ((double)B * (double)HW >= (double)(1 << 30)) return fail(c, MGU_ERR_INVALID, "%s: B*HW must stay below 2^30", fn);
-  HIPCHK(c, hipSetDevice(c->device));
-  LvCall k;
-  k.logits = (const float*)logits, k.labels = labels, k.ls_n = ls_n, k.ls_c = ls_c, k.ls_p = ls_p, k.ignore = ignore_index;
-  k.HW = (int)HW, k.C = C, k.P = (int)(B * HW), k.G = per_image ? B : 1, k.Ng = per_image ? (int)HW : k.P;
-  k.tiles_g = (k.Ng + LV_TILE - 1) / LV_TILE;
+               const LossGrad* grad, hipStream_t s) {
+  if (classes_mode < 0 || classes_mode > 1) return fail(c, MGU_ERR_INVALID, "bad %s args (%s)", fn, LV_HINT);
+  LossCall k;
+  int* err_dev = nullptr;
+  int rc = loss_call(c, fn, LV_HINT, logits, labels, B, HW, C, ls_n, ls_c, ls_p, per_image, ignore_index, &k, &err_dev);
+  if (rc) return rc;
   const LvSplit& split = c->tn.lovasz_passes == 3 ? LV_SPLIT3 : LV_SPLIT4;
   const LvScratch w = lv_scratch(k.P, C, k.G, k.tiles_g, *std::max_element(split.bits, split.bits + split.passes));
-  int rc = ensure(c, &c->lossws, &c->lossws_bytes, w.bytes);
-  if (rc) return rc;
-  int* err_dev = nullptr;
-  if ((rc = err_word_dev(c, &err_dev))) return rc;
+  if ((rc = ensure(c, &c->lossws, &c->lossws_bytes, w.bytes))) return rc;
   char* ws = (char*)c->lossws;
   unsigned *keys[2] = {(unsigned*)(ws + w.keys[0]), (unsigned*)(ws + w.keys[1])}, *pay[2] = {(unsigned*)(ws + w.pay[0]), (unsigned*)(ws + w.pay[1])};
   int *hist = (int*)(ws + w.hist), *dtot = (int*)(ws + w.dtot), *fgc = (int*)(ws + w.fgc), *seg_fg = (int*)(ws + w.seg_fg);
@@ -488,12 +431,10 @@ int lovasz_run(mgu_ctx* c, const char* fn, const void* logits, const int64_t* la
   if (grad) {
     ProfScope ps(c, s, "lovasz final");
     const dim3 pg(std::min(128, grid_for(HW, 1024, 1024)), B);
-    if (C <= 4)
-      hipLaunchKernelGGL(lv_bwd_kernel<4>, pg, dim3(256), 0, s, k, gbuf, wtab, grad->scale, grad->scale_dev, grad->dlogits, grad->ds_n,
-                         grad->ds_c, grad->ds_p, grad->accumulate);
-    else
-      hipLaunchKernelGGL(lv_bwd_kernel<8>, pg, dim3(256), 0, s, k, gbuf, wtab, grad->scale, grad->scale_dev, grad->dlogits, grad->ds_n,
-                         grad->ds_c, grad->ds_p, grad->accumulate);
+    with_nc(C, [&](auto nc) {
+      hipLaunchKernelGGL(lv_bwd_kernel<decltype(nc)::value>, pg, dim3(256), 0, s, k, gbuf, wtab, grad->scale, grad->scale_dev, grad->dlogits,
+                         grad->ds_n, grad->ds_c, grad->ds_p, grad->accumulate);
+    });
   }
   HIPCHK(c, hipGetLastError());
   return MGU_OK;
@@ -503,7 +444,7 @@ int lovasz_run(mgu_ctx* c, const char* fn, const void* logits, const int64_t* la
 
 extern "C" {
 
-int mgu_lovasz_tile(void) { return LV_TILE; }
+int mgu_lovasz_tile(void) { return LOSS_TILE; }
 
 int mgu_lovasz_softmax(mgu_ctx* c, const void* logits_dev, const int64_t* labels_dev, int B, int64_t HW, int num_classes, int64_t ls_n,
                        int64_t ls_c, int64_t ls_p, int classes_mode, int per_image, int64_t ignore_index, float* loss_dev,
@@ -520,9 +461,7 @@ int mgu_lovasz_softmax_backward(mgu_ctx* c, const void* logits_dev, const int64_
                                 int accumulate, float* loss_dev, void* hip_stream) {
   if (!c) return MGU_ERR_INVALID;
   if (!dlogits_dev) return fail(c, MGU_ERR_INVALID, "bad lovasz_softmax_backward args (dlogits_dev is NULL)");
-  LvGrad g;
-  g.scale = grad_scale, g.scale_dev = grad_scale_dev, g.dlogits = (float*)dlogits_dev;
-  g.ds_n = ds_n, g.ds_c = ds_c, g.ds_p = ds_p, g.accumulate = accumulate;
+  const LossGrad g{grad_scale, grad_scale_dev, (float*)dlogits_dev, ds_n, ds_c, ds_p, accumulate, 0};
   return lovasz_run(c, "lovasz_softmax_backward", logits_dev, labels_dev, B, HW, num_classes, ls_n, ls_c, ls_p, classes_mode, per_image,
                     ignore_index, loss_dev, nullptr, nullptr, &g, (hipStream_t)hip_stream);
 }

@@ -33,12 +33,12 @@
 // + 4 * T (tie counts) + 8 * G (thresholds): 8 x 512 x 512 over the batch: 8 403 456 bytes = 8.0 MiB.
 #include <algorithm>
 
+#include "loss_common.h"
 #include "objects_common.h"
 
 namespace mgu {
 
-constexpr int PC_ITEMS = 16;                 // keys per thread
-constexpr int PC_TILE = 256 * PC_ITEMS;      // keys one workgroup counts per pass
+// a workgroup counts the LOSS_TILE keys of one tile (loss_common.h) per pass
 constexpr unsigned PC_IGNORED = 0xFFFFFFFFu; // loss plane: a pixel that is not counted (ignore_index or a label outside [0, C))
 constexpr unsigned PC_DROPPED = 0x80000000u; // loss plane: set by the sums pass on a counted pixel that is not kept
 constexpr int PC_PASSES = 4;
@@ -46,38 +46,20 @@ constexpr int PC_PASSES = 4;
 __host__ __device__ constexpr int pc_shift(int pass) { return pass == 3 ? 0 : 23 - 8 * pass; }
 __host__ __device__ constexpr int pc_bins(int pass) { return pass == 3 ? 128 : 256; }
 
-// what every kernel knows of the call; the P = B * HW pixels fall into G groups of Ng consecutive pixels, each of tiles_g tiles
-struct PcCall {
-  const float* logits;
-  const int64_t* labels;
+// what every kernel knows of the call: the shared descriptor and this loss's options
+struct PcCall : LossCall {
   const float* weight;   // C class weights or nullptr
   const float* pmap;     // the per-pixel weight map m (P floats) of the _map entries, or nullptr
-  int64_t ls_n, ls_c, ls_p;
-  long long ignore, min_kept;
+  long long min_kept;
   double keep;
   float eps, gamma;
-  int HW, C, P, G, Ng, tiles_g;
 };
-
-struct PcTile {
-  int g, tile, n;   // group, tile of the group, its pixels
-  int first;        // its first pixel
-};
-__device__ __forceinline__ PcTile pc_tile(const PcCall& k) {
-  PcTile t;
-  t.g = blockIdx.x / k.tiles_g, t.tile = blockIdx.x - t.g * k.tiles_g;
-  const int lo = t.tile * PC_TILE;
-  t.n = min(PC_TILE, k.Ng - lo);
-  t.first = t.g * k.Ng + lo;
-  return t;
-}
-// position inside the tile of item i of this thread: the (wave, item, lane) order is the pixel order
-__device__ __forceinline__ int pc_item(int i) { return (threadIdx.x >> 6) * (64 * PC_ITEMS) + i * 64 + (threadIdx.x & 63); }
+static_assert(std::is_trivially_copyable<PcCall>::value, "a kernel argument by value");
 
 // One counted pixel: the softmax pieces and its loss.  Contraction is off: the select's passes and the sums must see the same bits.
 template <int NC>
 struct PcPixel {
-  float e[NC], w[NC];   // expf(l_c - max), class weights
+  float e[NC], w[NC];   // exp(l_c - max) (softmax_front), class weights
   float inv, loss, miss, py, ty;   // 1 / sum e; the loss; 1 - p_y; p_y; -lp_y
 };
 template <int NC>
@@ -90,21 +72,15 @@ __device__ __forceinline__ void pc_pixel(const PcCall& k, int q, int y, PcPixel<
 #pragma clang fp contract(off)
   const int b = q / k.HW;
   const float* p = k.logits + b * k.ls_n + (int64_t)(q - b * k.HW) * k.ls_p;
-  float l[NC], mx = -INFINITY, ly = 0.f;
+  float l[NC], mx, ly = 0.f, ey = 0.f;
+  PixelCE s;   // fed in class order as the front end forms e: s.se is its sum, the same adds in the same order (a padded class adds 0.f)
+  softmax_front(p, k.ls_c, k.C, x.e, mx, &l, [&](int c, float e) {
+    if (c < k.C) s.add(c, e);
+    if (c == y) ey = e;
+  });
 #pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    l[c] = c < k.C ? p[c * k.ls_c] : -INFINITY;
-    mx = fmaxf(mx, l[c]);
+  for (int c = 0; c < NC; ++c)
     if (c == y) ly = l[c];
-  }
-  PixelCE s;
-  float ey = 0.f;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    x.e[c] = c < k.C ? expf(l[c] - mx) : 0.f;
-    if (c < k.C) s.add(c, x.e[c]);
-    if (c == y) ey = x.e[c];
-  }
   x.inv = 1.f / s.se;
   x.ty = s.term(mx, ly);
   x.miss = s.miss(y, ey);
@@ -221,12 +197,12 @@ __global__ __launch_bounds__(256) void pc_loss_kernel(PcCall k, unsigned* __rest
   __shared__ int cnt[256];
   cnt[threadIdx.x] = 0;
   __syncthreads();
-  const PcTile t = pc_tile(k);
+  const LossTile t = loss_tile(k);
   PcPixel<NC> x;
   pc_weights(k, x.w);
   bool bad = false;
 #pragma unroll 2
-  for (int i = 0; i < PC_ITEMS; ++i) {
+  for (int i = 0; i < LOSS_ITEMS; ++i) {
     const int j = i * 256 + threadIdx.x;
     if (j >= t.n) continue;
     const int q = t.first + j;
@@ -252,7 +228,7 @@ __global__ __launch_bounds__(256) void pc_loss_kernel(PcCall k, unsigned* __rest
 __global__ __launch_bounds__(256) void pc_count_kernel(PcCall k, const unsigned* __restrict__ plane, int* __restrict__ hist, int pass) {
   __shared__ int cnt[256];
   __shared__ int shs[4], shp[2];
-  const PcTile t = pc_tile(k);
+  const LossTile t = loss_tile(k);
   int rem;
   const unsigned prefix = pc_threshold(k, hist, t.g, pass, rem, shs, shp);
   cnt[threadIdx.x] = 0;
@@ -260,7 +236,7 @@ __global__ __launch_bounds__(256) void pc_count_kernel(PcCall k, const unsigned*
   const int above = pc_shift(pass - 1), shift = pc_shift(pass), mask = pc_bins(pass) - 1;
   if (prefix != PC_IGNORED) {
 #pragma unroll 4
-    for (int i = 0; i < PC_ITEMS; ++i) {
+    for (int i = 0; i < LOSS_ITEMS; ++i) {
       const int j = i * 256 + threadIdx.x;
       if (j >= t.n) continue;
       const unsigned key = plane[t.first + j];
@@ -274,13 +250,13 @@ __global__ __launch_bounds__(256) void pc_count_kernel(PcCall k, const unsigned*
 __global__ __launch_bounds__(256) void pc_tie_count_kernel(PcCall k, const unsigned* __restrict__ plane, int* __restrict__ hist,
                                                            int* __restrict__ ties) {
   __shared__ int shs[4], shp[2];
-  const PcTile t = pc_tile(k);
+  const LossTile t = loss_tile(k);
   int rem;
   const unsigned thr = pc_threshold(k, hist, t.g, PC_PASSES, rem, shs, shp);
   int s = 0;
   if (thr != PC_IGNORED) {
 #pragma unroll 4
-    for (int i = 0; i < PC_ITEMS; ++i) {
+    for (int i = 0; i < LOSS_ITEMS; ++i) {
       const int j = i * 256 + threadIdx.x;
       if (j < t.n) s += plane[t.first + j] == thr;
     }
@@ -317,18 +293,18 @@ __global__ __launch_bounds__(256) void pc_sum_kernel(PcCall k, unsigned* __restr
                                                      float* __restrict__ pixel_loss, int* __restrict__ kept, int* __restrict__ err_word) {
   __shared__ int shw[4];
   __shared__ double shd[8];
-  const PcTile t = pc_tile(k);
+  const LossTile t = loss_tile(k);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   double acc[2] = {0.0, 0.0};
   bool bad = false;
   if (SELECT) {
     const unsigned thr = state[2 * t.g];
     const int r = (int)state[2 * t.g + 1];
-    unsigned key[PC_ITEMS];
-    int rank[PC_ITEMS], mine = 0;   // rank among the wave's pixels with key == thr; mine: how many the wave holds
+    unsigned key[LOSS_ITEMS];
+    int rank[LOSS_ITEMS], mine = 0;   // rank among the wave's pixels with key == thr; mine: how many the wave holds
 #pragma unroll
-    for (int i = 0; i < PC_ITEMS; ++i) {
-      const int j = pc_item(i);
+    for (int i = 0; i < LOSS_ITEMS; ++i) {
+      const int j = loss_item(i);
       key[i] = j < t.n ? plane[t.first + j] : PC_IGNORED;
       const unsigned long long m = __ballot(key[i] == thr && thr != PC_IGNORED);
       rank[i] = mine + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
@@ -339,8 +315,8 @@ __global__ __launch_bounds__(256) void pc_sum_kernel(PcCall k, unsigned* __restr
     int before = ties[(size_t)t.g * k.tiles_g + t.tile];
     for (int w = 0; w < wave; ++w) before += shw[w];
 #pragma unroll
-    for (int i = 0; i < PC_ITEMS; ++i) {
-      const int j = pc_item(i);
+    for (int i = 0; i < LOSS_ITEMS; ++i) {
+      const int j = loss_item(i);
       if (j >= t.n) continue;
       const int q = t.first + j;
       const long long y = k.labels[q];
@@ -362,8 +338,8 @@ __global__ __launch_bounds__(256) void pc_sum_kernel(PcCall k, unsigned* __restr
     PcPixel<NC> x;
     pc_weights(k, x.w);
 #pragma unroll 2
-    for (int i = 0; i < PC_ITEMS; ++i) {
-      const int j = pc_item(i);
+    for (int i = 0; i < LOSS_ITEMS; ++i) {
+      const int j = loss_item(i);
       if (j >= t.n) continue;
       const int q = t.first + j;
       const long long y = k.labels[q];
@@ -413,12 +389,12 @@ __global__ __launch_bounds__(256) void pc_grad_kernel(PcCall k, const unsigned* 
                                                       const float* __restrict__ gs_dev, float* __restrict__ dlogits, int64_t ds_n,
                                                       int64_t ds_c, int64_t ds_p, int accumulate, int zero_to) {
 #pragma clang fp contract(off)   // with and without the select the rows come out bit for bit the same
-  const PcTile t = pc_tile(k);
+  const LossTile t = loss_tile(k);
   const float up = (float)((double)gs * (gs_dev ? (double)*gs_dev : 1.0) / fin[1]);
   PcPixel<NC> x;
   pc_weights(k, x.w);
 #pragma unroll 2
-  for (int i = 0; i < PC_ITEMS; ++i) {
+  for (int i = 0; i < LOSS_ITEMS; ++i) {
     const int j = i * 256 + threadIdx.x;
     if (j >= t.n) continue;
     const int q = t.first + j, b = q / k.HW;
@@ -475,115 +451,83 @@ PcScratch pc_scratch(int64_t P, int G, int tiles_g, bool select) {
   return s;
 }
 
-struct PcGrad {
-  float scale = 1.f;
-  const float* scale_dev = nullptr;
-  float* dlogits = nullptr;
-  int64_t ds_n = 0, ds_c = 0, ds_p = 0;
-  int accumulate = 0, zero_to = 0;
-};
+const char* const PC_HINT = "1 <= num_classes <= 8, a shape without pixels";
 
 int pixel_ce_run(mgu_ctx* c, const char* fn, const void* logits, const int64_t* labels, int B, int64_t HW, int C, int64_t ls_n, int64_t ls_c,
                  int64_t ls_p, const float* weight, const float* pmap, bool map_entry, float eps, float gamma, double keep, int64_t min_kept,
-                 int per_image, int64_t ignore_index, float* loss, float* pixel_loss, int32_t* kept, const PcGrad* grad, hipStream_t s) {
+                 int per_image, int64_t ignore_index, float* loss, float* pixel_loss, int32_t* kept, const LossGrad* grad, hipStream_t s) {
   // the profile's kernel families: the _map entries report under names of their own
   static const char* const NAMES[2][3] = {{"pixel_ce select", "pixel_ce sums", "pixel_ce gradient"},
                                           {"pixel_ce_map select", "pixel_ce_map sums", "pixel_ce_map gradient"}};
   const char* const* names = NAMES[map_entry ? 1 : 0];
-  if (!logits || !labels || B < 1 || HW < 1 || C < 1 || C > 8)
-    return fail(c, MGU_ERR_INVALID, "bad %s args (1 <= num_classes <= 8, a shape without pixels)", fn);
-  if ((double)B * (double)HW >= (double)(1 << 30)) return fail(c, MGU_ERR_INVALID, "%s: B*HW must stay below 2^30", fn);
+  PcCall k;
+  int* err_dev = nullptr;
+  int rc = loss_call(c, fn, PC_HINT, logits, labels, B, HW, C, ls_n, ls_c, ls_p, per_image, ignore_index, &k, &err_dev);
+  if (rc) return rc;
   if (!(eps >= 0.f && eps < 1.f)) return fail(c, MGU_ERR_INVALID, "%s: label_smoothing must lie in [0, 1)", fn);
   if (!(gamma == 0.f || gamma >= 1.f)) return fail(c, MGU_ERR_INVALID, "%s: focal_gamma must be 0 or >= 1", fn);
   if (gamma > 0.f && eps > 0.f) return fail(c, MGU_ERR_INVALID, "%s: focal_gamma > 0 takes no label_smoothing", fn);
   if (!(keep > 0.0 && keep <= 1.0)) return fail(c, MGU_ERR_INVALID, "%s: keep_fraction must lie in (0, 1]", fn);
   if (min_kept < 0) return fail(c, MGU_ERR_INVALID, "%s: min_kept must be >= 0", fn);
-  HIPCHK(c, hipSetDevice(c->device));
   const bool select = keep < 1.0;
-  PcCall k;
-  k.logits = (const float*)logits, k.labels = labels, k.weight = weight, k.pmap = pmap, k.ls_n = ls_n, k.ls_c = ls_c, k.ls_p = ls_p;
-  k.ignore = ignore_index, k.min_kept = min_kept, k.keep = keep, k.eps = eps, k.gamma = gamma;
-  k.HW = (int)HW, k.C = C, k.P = (int)(B * HW), k.G = per_image ? B : 1, k.Ng = per_image ? (int)HW : k.P;
-  k.tiles_g = (k.Ng + PC_TILE - 1) / PC_TILE;
+  k.weight = weight, k.pmap = pmap, k.min_kept = min_kept, k.keep = keep, k.eps = eps, k.gamma = gamma;
   const PcScratch w = pc_scratch(k.P, k.G, k.tiles_g, select);
-  int rc = ensure(c, &c->lossws, &c->lossws_bytes, w.bytes);
-  if (rc) return rc;
-  int* err_dev = nullptr;
-  if ((rc = err_word_dev(c, &err_dev))) return rc;
+  if ((rc = ensure(c, &c->lossws, &c->lossws_bytes, w.bytes))) return rc;
   char* ws = (char*)c->lossws;
   double *part = (double*)(ws + w.part), *fin = (double*)(ws + w.fin);
   unsigned *plane = (unsigned*)(ws + w.plane), *state = (unsigned*)(ws + w.state);
   int *hist = (int*)(ws + w.hist), *ties = (int*)(ws + w.ties);
   const int tiles = k.G * k.tiles_g;
   const dim3 grid(tiles);
-#define MGU_PC_SUM(NC, SEL, MAP) \
-  hipLaunchKernelGGL((pc_sum_kernel<NC, SEL, MAP>), grid, dim3(256), 0, s, k, plane, ties, state, part, pixel_loss, kept, err_dev)
-  if (select) {
-    HIPCHK(c, hipMemsetAsync(hist, 0, (size_t)PC_PASSES * k.G * 256 * 4, s));
-    {
-      ProfScope ps(c, s, names[0]);
-#define MGU_PC_LOSS(NC, MAP) hipLaunchKernelGGL((pc_loss_kernel<NC, MAP>), grid, dim3(256), 0, s, k, plane, hist, pixel_loss, err_dev)
-      if (pmap) {
-        if (C <= 4) MGU_PC_LOSS(4, true);
-        else MGU_PC_LOSS(8, true);
-      } else {
-        if (C <= 4) MGU_PC_LOSS(4, false);
-        else MGU_PC_LOSS(8, false);
+  if (select) HIPCHK(c, hipMemsetAsync(hist, 0, (size_t)PC_PASSES * k.G * 256 * 4, s));
+  // MAP, then the padded class count and SELECT where a kernel has them, become template arguments; the selecting sums read the plane
+  // and exist for <4> only.
+  with_flag(pmap != nullptr, [&](auto map) {
+    constexpr bool MAP = decltype(map)::value;
+    if (select) {
+      {
+        ProfScope ps(c, s, names[0]);
+        with_nc(C, [&](auto nc) {
+          hipLaunchKernelGGL((pc_loss_kernel<decltype(nc)::value, MAP>), grid, dim3(256), 0, s, k, plane, hist, pixel_loss, err_dev);
+        });
       }
-#undef MGU_PC_LOSS
-    }
-    for (int pass = 1; pass < PC_PASSES; ++pass) {
-      ProfScope ps(c, s, names[0]);
-      hipLaunchKernelGGL(pc_count_kernel, grid, dim3(256), 0, s, k, plane, hist, pass);
-    }
-    {
-      ProfScope ps(c, s, names[0]);
-      hipLaunchKernelGGL(pc_tie_count_kernel, grid, dim3(256), 0, s, k, plane, hist, ties);
-    }
-    {
-      ProfScope ps(c, s, names[0]);
-      hipLaunchKernelGGL(pc_tie_scan_kernel, dim3(k.G), dim3(256), 0, s, k, hist, ties, state);
+      for (int pass = 1; pass < PC_PASSES; ++pass) {
+        ProfScope ps(c, s, names[0]);
+        hipLaunchKernelGGL(pc_count_kernel, grid, dim3(256), 0, s, k, plane, hist, pass);
+      }
+      {
+        ProfScope ps(c, s, names[0]);
+        hipLaunchKernelGGL(pc_tie_count_kernel, grid, dim3(256), 0, s, k, plane, hist, ties);
+      }
+      {
+        ProfScope ps(c, s, names[0]);
+        hipLaunchKernelGGL(pc_tie_scan_kernel, dim3(k.G), dim3(256), 0, s, k, hist, ties, state);
+      }
+      {
+        ProfScope ps(c, s, names[1]);
+        hipLaunchKernelGGL((pc_sum_kernel<4, true, MAP>), grid, dim3(256), 0, s, k, plane, ties, state, part, pixel_loss, kept, err_dev);
+      }
+    } else {
+      ProfScope ps(c, s, names[1]);
+      with_nc(C, [&](auto nc) {
+        hipLaunchKernelGGL((pc_sum_kernel<decltype(nc)::value, false, MAP>), grid, dim3(256), 0, s, k, plane, ties, state, part, pixel_loss,
+                           kept, err_dev);
+      });
     }
     {
       ProfScope ps(c, s, names[1]);
-      if (pmap) MGU_PC_SUM(4, true, true);
-      else MGU_PC_SUM(4, true, false);
+      hipLaunchKernelGGL(pc_finish_kernel, dim3(1), dim3(256), 0, s, part, tiles, fin, loss);
     }
-  } else {
-    ProfScope ps(c, s, names[1]);
-    if (pmap) {
-      if (C <= 4) MGU_PC_SUM(4, false, true);
-      else MGU_PC_SUM(8, false, true);
-    } else {
-      if (C <= 4) MGU_PC_SUM(4, false, false);
-      else MGU_PC_SUM(8, false, false);
+    if (grad) {
+      ProfScope ps(c, s, names[2]);
+      with_flag(select, [&](auto sel) {
+        with_nc(C, [&](auto nc) {
+          hipLaunchKernelGGL((pc_grad_kernel<decltype(nc)::value, decltype(sel)::value, MAP>), grid, dim3(256), 0, s, k, plane, fin,
+                             grad->scale, grad->scale_dev, grad->dlogits, grad->ds_n, grad->ds_c, grad->ds_p, grad->accumulate, grad->zero_to);
+        });
+      });
     }
-  }
-  {
-    ProfScope ps(c, s, names[1]);
-    hipLaunchKernelGGL(pc_finish_kernel, dim3(1), dim3(256), 0, s, part, tiles, fin, loss);
-  }
-  if (grad) {
-    ProfScope ps(c, s, names[2]);
-#define MGU_PC_GRAD(NC, SEL, MAP)                                                                                                              \
-  hipLaunchKernelGGL((pc_grad_kernel<NC, SEL, MAP>), grid, dim3(256), 0, s, k, plane, fin, grad->scale, grad->scale_dev, grad->dlogits, grad->ds_n, \
-                     grad->ds_c, grad->ds_p, grad->accumulate, grad->zero_to)
-#define MGU_PC_GRAD_NC(NC, SEL)                 \
-  do {                                          \
-    if (pmap) MGU_PC_GRAD(NC, SEL, true);       \
-    else MGU_PC_GRAD(NC, SEL, false);           \
-  } while (0)
-    if (select) {
-      if (C <= 4) MGU_PC_GRAD_NC(4, true);
-      else MGU_PC_GRAD_NC(8, true);
-    } else {
-      if (C <= 4) MGU_PC_GRAD_NC(4, false);
-      else MGU_PC_GRAD_NC(8, false);
-    }
-#undef MGU_PC_GRAD_NC
-#undef MGU_PC_GRAD
-  }
-#undef MGU_PC_SUM
+  });
   HIPCHK(c, hipGetLastError());
   return MGU_OK;
 }
@@ -592,7 +536,7 @@ int pixel_ce_run(mgu_ctx* c, const char* fn, const void* logits, const int64_t* 
 
 extern "C" {
 
-int mgu_pixel_ce_tile(void) { return PC_TILE; }
+int mgu_pixel_ce_tile(void) { return LOSS_TILE; }
 
 int mgu_pixel_ce(mgu_ctx* c, const void* logits_dev, const int64_t* labels_dev, int B, int64_t HW, int num_classes, int64_t ls_n, int64_t ls_c,
                  int64_t ls_p, const float* class_weight_dev, float label_smoothing, float focal_gamma, double keep_fraction,
@@ -612,9 +556,7 @@ int mgu_pixel_ce_backward(mgu_ctx* c, const void* logits_dev, const int64_t* lab
                           int zero_to, float* loss_dev, void* hip_stream) {
   if (!c) return MGU_ERR_INVALID;
   if (!dlogits_dev) return fail(c, MGU_ERR_INVALID, "bad pixel_ce_backward args (dlogits_dev is NULL)");
-  PcGrad g;
-  g.scale = grad_scale, g.scale_dev = grad_scale_dev, g.dlogits = (float*)dlogits_dev;
-  g.ds_n = ds_n, g.ds_c = ds_c, g.ds_p = ds_p, g.accumulate = accumulate, g.zero_to = zero_to;
+  const LossGrad g{grad_scale, grad_scale_dev, (float*)dlogits_dev, ds_n, ds_c, ds_p, accumulate, zero_to};
   return pixel_ce_run(c, "pixel_ce_backward", logits_dev, labels_dev, B, HW, num_classes, ls_n, ls_c, ls_p, class_weight_dev, nullptr,
                       false, label_smoothing, focal_gamma, keep_fraction, min_kept, per_image, ignore_index, loss_dev, nullptr, nullptr, &g,
                       (hipStream_t)hip_stream);
@@ -639,9 +581,7 @@ int mgu_pixel_ce_map_backward(mgu_ctx* c, const void* logits_dev, const int64_t*
                               int64_t ds_c, int64_t ds_p, int accumulate, int zero_to, float* loss_dev, void* hip_stream) {
   if (!c) return MGU_ERR_INVALID;
   if (!dlogits_dev) return fail(c, MGU_ERR_INVALID, "bad pixel_ce_map_backward args (dlogits_dev is NULL)");
-  PcGrad g;
-  g.scale = grad_scale, g.scale_dev = grad_scale_dev, g.dlogits = (float*)dlogits_dev;
-  g.ds_n = ds_n, g.ds_c = ds_c, g.ds_p = ds_p, g.accumulate = accumulate, g.zero_to = zero_to;
+  const LossGrad g{grad_scale, grad_scale_dev, (float*)dlogits_dev, ds_n, ds_c, ds_p, accumulate, zero_to};
   return pixel_ce_run(c, "pixel_ce_map_backward", logits_dev, labels_dev, B, HW, num_classes, ls_n, ls_c, ls_p, class_weight_dev,
                       pixel_weight_dev, true, label_smoothing, focal_gamma, keep_fraction, min_kept, per_image, ignore_index, loss_dev,
                       nullptr, nullptr, &g, (hipStream_t)hip_stream);

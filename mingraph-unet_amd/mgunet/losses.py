@@ -64,30 +64,46 @@ class TVLoss(nn.Module):
         return _TVFn.apply(x, self.weight)
 
 
+def _pixel_strided(pd):
+    """pd with ONE stride for the pixel index (both NCHW and NHWC storage qualify; anything else is copied)"""
+    return pd if pd.stride(2) == pd.shape[3] * pd.stride(3) else pd.contiguous()
+
+
+def _check_logits(pred, target):
+    if pred.dim() != 4 or target.dim() != 3 or target.dtype != torch.int64:
+        raise ValueError("expected logits (B, C, H, W) and an int64 target (B, H, W)")
+
+
+def _logits_head(pred, target):
+    """What every entry point of the segmentation losses starts with: (pd, target, head) with pd the float32 pixel-strided logits,
+    target contiguous and head = (device, pd, target, B, H * W, C, stride of n, of c, of the pixel index)."""
+    pd, target = _pixel_strided(_f32(pred)), target.contiguous()
+    B, C_, H, W = pd.shape
+    return pd, target, (pd.device, pd, target, B, H * W, C_, pd.stride(0), pd.stride(1), pd.stride(3))
+
+
+def _grad_args(pd, g):
+    """The gradient of the logits pd, with pd's strides (NHWC storage stays NHWC), and the tail every *_backward entry takes before its
+    own flags: (grad_scale 1.0, the upstream gradient as contiguous float32, d, d's three strides)."""
+    d = torch.empty_strided(pd.shape, pd.stride(), device=pd.device, dtype=torch.float32)
+    return d, (1.0, g.detach().float().contiguous(), d, d.stride(0), d.stride(1), d.stride(3))
+
+
 class _DiceFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx_, pred, target, smooth):
-        pd = _f32(pred)
-        B, C_, H, W = pd.shape
-        if pd.stride(2) != W * pd.stride(3):          # the pixel index must be one stride: both NCHW and NHWC storage qualify
-            pd = pd.contiguous()
-        target = target.contiguous()
+        pd, target, head = _logits_head(pred, target)
         out = torch.empty((), device=pd.device, dtype=torch.float32)
-        _lib.call("mgu_dice_loss", pd.device, pd, target, B, H * W, C_, pd.stride(0), pd.stride(1), pd.stride(3), float(smooth), out)
+        _lib.call("mgu_dice_loss", *head, float(smooth), out)
         ctx_.save_for_backward(pd, target)
         ctx_.smooth, ctx_.in_dtype = float(smooth), pred.dtype
         return out
 
     @staticmethod
     def backward(ctx_, g):
-        pd, target = ctx_.saved_tensors
-        B, C_, H, W = pd.shape
-        d = torch.empty_like(pd)                      # same strides (preserve_format): NHWC storage stays NHWC
-        if d.stride() != pd.stride():
-            d = torch.empty_strided(pd.shape, pd.stride(), device=pd.device, dtype=torch.float32)
-        g = g.detach().float().contiguous()
-        _lib.call("mgu_dice_loss_backward", pd.device, pd, target, B, H * W, C_, pd.stride(0), pd.stride(1), pd.stride(3), ctx_.smooth, 1.0,
-                  g, d, d.stride(0), d.stride(1), d.stride(3), 0, None)
+        pd, target, head = _logits_head(*ctx_.saved_tensors)
+        d, tail = _grad_args(pd, g)
+        _lib.call("mgu_dice_loss_backward", *head, ctx_.smooth, *tail, 0, None)
         return d.to(ctx_.in_dtype), None, None
 
 
@@ -95,47 +111,34 @@ def dice_loss(pred, target, smooth=1.):
     """pred (B, C, H, W) logits (any strides: NHWC storage is read in place), target (B, H, W) int64.  Differentiable w.r.t. pred.
     A label outside [0, C) -- F.one_hot raises on it -- is reported by check_labels(pred.device) (no host sync inside the call)."""
     _lib.require_hip(pred, "mgunet dice_loss")
-    if pred.dim() != 4 or target.dim() != 3 or target.dtype != torch.int64:
-        raise ValueError("expected logits (B, C, H, W) and an int64 target (B, H, W)")
+    _check_logits(pred, target)
     return _DiceFn.apply(pred, target, smooth)
 
 
 _LOVASZ_CLASSES = {"present": 0, "all": 1}
 
 
-def _pixel_strided(pd):
-    """pd with ONE stride for the pixel index (both NCHW and NHWC storage qualify; anything else is copied)"""
-    return pd if pd.stride(2) == pd.shape[3] * pd.stride(3) else pd.contiguous()
-
-
 class _LovaszFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx_, pred, target, mode, per_image, ignore_index):
-        pd = _pixel_strided(_f32(pred))
-        B, C_, H, W = pd.shape
-        target = target.contiguous()
+        pd, target, head = _logits_head(pred, target)
         out = torch.empty((), device=pd.device, dtype=torch.float32)
-        _lib.call("mgu_lovasz_softmax", pd.device, pd, target, B, H * W, C_, pd.stride(0), pd.stride(1), pd.stride(3), mode, per_image,
-                  ignore_index, out, None, None)
+        _lib.call("mgu_lovasz_softmax", *head, mode, per_image, ignore_index, out, None, None)
         ctx_.save_for_backward(pd, target)
         ctx_.opts, ctx_.in_dtype = (mode, per_image, ignore_index), pred.dtype
         return out
 
     @staticmethod
     def backward(ctx_, g):
-        pd, target = ctx_.saved_tensors
-        B, C_, H, W = pd.shape
-        d = torch.empty_strided(pd.shape, pd.stride(), device=pd.device, dtype=torch.float32)   # NHWC storage stays NHWC
-        g = g.detach().float().contiguous()
-        _lib.call("mgu_lovasz_softmax_backward", pd.device, pd, target, B, H * W, C_, pd.stride(0), pd.stride(1), pd.stride(3), *ctx_.opts,
-                  1.0, g, d, d.stride(0), d.stride(1), d.stride(3), 0, None)
+        pd, target, head = _logits_head(*ctx_.saved_tensors)
+        d, tail = _grad_args(pd, g)
+        _lib.call("mgu_lovasz_softmax_backward", *head, *ctx_.opts, *tail, 0, None)
         return d.to(ctx_.in_dtype), None, None, None, None
 
 
 def _lovasz_args(pred, target, classes, per_image, ignore_index):
     _lib.require_hip(pred, "mgunet lovasz_softmax")
-    if pred.dim() != 4 or target.dim() != 3 or target.dtype != torch.int64:
-        raise ValueError("expected logits (B, C, H, W) and an int64 target (B, H, W)")
+    _check_logits(pred, target)
     if classes not in _LOVASZ_CLASSES:
         raise ValueError(f"unknown classes {classes!r}: 'present' or 'all'")
     return _LOVASZ_CLASSES[classes], int(bool(per_image)), int(ignore_index)
@@ -154,13 +157,12 @@ def _lovasz_debug(pred, target, classes="present", per_image=False, ignore_index
     """(loss, errors, ranks) through the test hooks of mgu_lovasz_softmax: errors fp32 and ranks int32, each (C, B, H, W): the
     error of every pixel for every class and its 0-based rank inside its segment (-1: ignored pixel)."""
     mode, per_image, ignore_index = _lovasz_args(pred, target, classes, per_image, ignore_index)
-    pd = _pixel_strided(_f32(pred))
+    pd, target, head = _logits_head(pred, target)
     B, C_, H, W = pd.shape
     out = torch.empty((), device=pd.device, dtype=torch.float32)
     errors = torch.empty((C_, B, H, W), device=pd.device, dtype=torch.float32)
     ranks = torch.empty((C_, B, H, W), device=pd.device, dtype=torch.int32)
-    _lib.call("mgu_lovasz_softmax", pd.device, pd, target.contiguous(), B, H * W, C_, pd.stride(0), pd.stride(1), pd.stride(3), mode,
-              per_image, ignore_index, out, errors, ranks)
+    _lib.call("mgu_lovasz_softmax", *head, mode, per_image, ignore_index, out, errors, ranks)
     return out, errors, ranks
 
 
@@ -187,44 +189,36 @@ def pixel_ce_options(weight, label_smoothing, focal_gamma, keep_fraction, min_ke
     return eps, gamma, keep, kmin, int(bool(per_image))
 
 
-def _pixel_ce_entry(name, pd, target, weight, pixel_weight):
+def _pixel_ce_entry(name, head, weight, pixel_weight):
     """The entry point and the arguments up to the options: mgu_pixel_ce[_backward], or with a map mgu_pixel_ce_map[_backward], which
     takes it after the class weights."""
-    B, C_, H, W = pd.shape
-    head = (pd.device, pd, target, B, H * W, C_, pd.stride(0), pd.stride(1), pd.stride(3), weight)
     if pixel_weight is None:
-        return (name,) + head
-    return (name.replace("mgu_pixel_ce", "mgu_pixel_ce_map"),) + head + (pixel_weight,)
+        return (name,) + head + (weight,)
+    return (name.replace("mgu_pixel_ce", "mgu_pixel_ce_map"),) + head + (weight, pixel_weight)
 
 
 class _PixelCEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx_, pred, target, weight, opts, ignore_index, pixel_weight=None):
-        pd = _pixel_strided(_f32(pred))
-        B, C_, H, W = pd.shape
-        target = target.contiguous()
+        pd, target, head = _logits_head(pred, target)
         out = torch.empty((), device=pd.device, dtype=torch.float32)
-        _lib.call(*_pixel_ce_entry("mgu_pixel_ce", pd, target, weight, pixel_weight), *opts, ignore_index, out, None, None)
+        _lib.call(*_pixel_ce_entry("mgu_pixel_ce", head, weight, pixel_weight), *opts, ignore_index, out, None, None)
         ctx_.save_for_backward(pd, target)
         ctx_.weight, ctx_.opts, ctx_.in_dtype, ctx_.pixel_weight = weight, (opts, ignore_index), pred.dtype, pixel_weight
         return out
 
     @staticmethod
     def backward(ctx_, g):
-        pd, target = ctx_.saved_tensors
-        B, C_, H, W = pd.shape
-        d = torch.empty_strided(pd.shape, pd.stride(), device=pd.device, dtype=torch.float32)   # NHWC storage stays NHWC
-        g = g.detach().float().contiguous()
+        pd, target, head = _logits_head(*ctx_.saved_tensors)
+        d, tail = _grad_args(pd, g)
         opts, ignore_index = ctx_.opts
-        _lib.call(*_pixel_ce_entry("mgu_pixel_ce_backward", pd, target, ctx_.weight, ctx_.pixel_weight), *opts, ignore_index, 1.0, g, d,
-                  d.stride(0), d.stride(1), d.stride(3), 0, 0, None)
+        _lib.call(*_pixel_ce_entry("mgu_pixel_ce_backward", head, ctx_.weight, ctx_.pixel_weight), *opts, ignore_index, *tail, 0, 0, None)
         return d.to(ctx_.in_dtype), None, None, None, None, None   # the map is held fixed: it gets no gradient
 
 
 def _pixel_ce_args(pred, target, weight, label_smoothing, focal_gamma, keep_fraction, min_kept, per_image, ignore_index):
     _lib.require_hip(pred, "mgunet pixel_cross_entropy")
-    if pred.dim() != 4 or target.dim() != 3 or target.dtype != torch.int64:
-        raise ValueError("expected logits (B, C, H, W) and an int64 target (B, H, W)")
+    _check_logits(pred, target)
     opts = pixel_ce_options(weight, label_smoothing, focal_gamma, keep_fraction, min_kept, per_image, pred.shape[1])
     if weight is not None:
         weight = weight.detach().to(device=pred.device, dtype=torch.float32).contiguous()
@@ -264,13 +258,12 @@ def _pixel_ce_debug(pred, target, weight=None, label_smoothing=0.0, focal_gamma=
     it is not counted), and kept int32 (B, H, W): 1 kept, 0 dropped, -1 not counted."""
     weight, opts, ignore_index = _pixel_ce_args(pred, target, weight, label_smoothing, focal_gamma, keep_fraction, min_kept, per_image,
                                                 ignore_index)
-    pd = _pixel_strided(_f32(pred))
+    pd, target, head = _logits_head(pred, target)
     B, C_, H, W = pd.shape
     out = torch.empty((), device=pd.device, dtype=torch.float32)
     pixel_loss = torch.empty((B, H, W), device=pd.device, dtype=torch.float32)
     kept = torch.empty((B, H, W), device=pd.device, dtype=torch.int32)
-    _lib.call(*_pixel_ce_entry("mgu_pixel_ce", pd, target.contiguous(), weight, pixel_weight_map(pixel_weight, pd)), *opts, ignore_index,
-              out, pixel_loss, kept)
+    _lib.call(*_pixel_ce_entry("mgu_pixel_ce", head, weight, pixel_weight_map(pixel_weight, pd)), *opts, ignore_index, out, pixel_loss, kept)
     return out, pixel_loss, kept
 
 

@@ -52,6 +52,26 @@ def test_object_helpers_live_in_objects_common_h_only():
     assert [f for f in family if re.search(r"for \([^)]*\) \{\s*const unsigned long long act = __ballot|SCAN_THREADS\s*=|sh\[tid - off\]", SOURCES[f])] == []
 
 
+LOSS_FILES = ["losses.hip", "lovasz.hip", "pixel_ce.hip"]
+LOSS_HELPERS = ["softmax_front", "NoClassHook", "LossCall", "LossTile", "loss_tile", "loss_item", "up_scale", "LossGrad", "loss_call", "with_nc", "with_flag",
+                "int_c"]
+RETIRED_LOSS = ["LvCall", "LvTile", "PcTile", "LvGrad", "PcGrad", "LV_ITEMS", "PC_ITEMS", "LV_TILE", "PC_TILE", "lv_tile", "pc_tile", "pc_item"]
+
+
+def test_loss_helpers_live_in_loss_common_h_only():
+    """the softmax front end, the call descriptor, the tile arithmetic, the gradient request, the shared host checks and the
+    compile-time dispatch of the segmentation losses: one definition each, in loss_common.h, which the three kernel files include.
+    Their private copies are gone, no macro selects a kernel, no file forms an exponential or maps the error word itself."""
+    where = {n: definitions(n) for n in LOSS_HELPERS}
+    assert {n: w for n, w in where.items() if [f for f, _ in w] != ["loss_common.h"]} == {}
+    assert [f for f in LOSS_FILES if '#include "loss_common.h"' not in SOURCES[f]] == []
+    assert [(f, n) for f, t in SOURCES.items() for n in RETIRED_LOSS if re.search(r"\b" + n + r"\b", t)] == []
+    assert [f for f in LOSS_FILES if "#define MGU_" in SOURCES[f]] == []
+    assert [f for f in LOSS_FILES if re.search(r"\bexpf\s*\(", SOURCES[f])] == []
+    assert "hipHostMallocMapped" not in SOURCES["losses.hip"]
+    assert len(re.findall(r"\bsoftmax_front\s*\(", "".join(SOURCES[f] for f in LOSS_FILES))) == 5
+
+
 PACK_BODIES = ["pack_wino_w_body", "pack_first_w_body", "pack_first_mfma_body", "pack_convt_x3_body", "pack_bias_tile_body",
                "pack_dgrad_w_body", "pack_conv_w_body", "pack_convt_w_body", "pack_convt_bf16f_body", "pack_convt_dgrad_w_body"]
 
