@@ -220,6 +220,67 @@ int mgu_adam_step(mgu_ctx* ctx, void* flat_param_dev, const void* flat_grad_dev,
 int mgu_sgd_step(mgu_ctx* ctx, void* flat_param_dev, const void* flat_grad_dev, void* momentum_buf_dev, int64_t n, float lr,
                  float momentum, float weight_decay, int step, float grad_scale, void* hip_stream);
 
+/* ---- the optimizer step with its decisions on the device: AdamW, norm clipping, skip of a non-finite step, weight EMA,
+ *      gradient accumulation (csrc/optim.hip).  mgu_adam_step / mgu_sgd_step above stay what they are. ----
+ * All buffers are flat fp32 vectors of n elements on the device; a pointer needs 4-byte alignment only (16-byte accesses are used
+ * where the buffers of a call share their offset within 16 bytes, with a peeled head and tail).
+ *
+ * The control record `ctrl`: 64 bytes on the device, 8-byte aligned, owned by the caller.  A zeroed record is a fresh optimizer.
+ *   offset  0  int64   step       steps applied so far (the t of the bias corrections; a skipped step does not advance it)
+ *           8  int64   skipped    steps skipped because the gradient held an inf or a NaN
+ *          16  double  sumsq      sum of the squares of the gradient's elements (unscaled), of the last call
+ *          24  double  norm       |grad_scale| * sqrt(sumsq): the L2 norm of the scaled gradient
+ *          32  float   scale      grad_scale * coef, the factor the update kernel puts on every gradient element
+ *          36  float   bc1        1 - beta1^step
+ *          40  float   bc2_sqrt   sqrt(1 - beta2^step)
+ *          44  float   ema_d      the EMA decay of this step
+ *          48  int32   apply      1: the update kernel runs; 0: every workgroup of it returns
+ *          52  int32   nonfinite  elements of the gradient that are inf or NaN
+ *          56  8 bytes reserved (left as they are)
+ * mgu_grad_norm and mgu_optim_step write the record with plain stores from one workgroup; nothing reads it on the host. */
+#define MGU_OPTIM_CTRL_BYTES 64
+#define MGU_OPTIM_ADAM 0  /* torch.optim.Adam: L2 decay folded into the gradient */
+#define MGU_OPTIM_ADAMW 1 /* torch.optim.AdamW: decoupled decay, p *= 1 - lr * wd before the step */
+#define MGU_OPTIM_SGD 2   /* torch.optim.SGD(momentum, weight_decay), dampening 0, no Nesterov */
+typedef struct {
+  int kind;                /* MGU_OPTIM_* */
+  float lr;
+  double beta1, beta2;     /* doubles, as mgu_adam_step takes them */
+  float eps, weight_decay;
+  float momentum;          /* kind 2; the momentum buffer is exp_avg_dev (exp_avg_sq_dev may be NULL) */
+  float grad_scale;        /* factor on the gradient (1 / (world * accumulated steps)) */
+  float max_norm;          /* > 0: clip the scaled gradient to this L2 norm; 0: off */
+  int skip_nonfinite;      /* != 0: a gradient with an inf or a NaN leaves everything but ctrl->skipped as it is */
+  float ema_decay;         /* in [0, 1); 0: off, ema_dev may then be NULL */
+  int ema_warmup;          /* != 0: the decay of step t is min(ema_decay, (1 + t) / (10 + t)) */
+} mgu_optim_desc;
+/* Workgroups the partial-sums launch of mgu_grad_norm / mgu_optim_step runs for n elements, and the elements each of them owns:
+ * workgroup b sums [b * chunk, min(n, (b + 1) * chunk)).  Both depend on n alone (host routines; n < 1: 0). */
+int64_t mgu_grad_norm_chunk(int64_t n);
+int mgu_grad_norm_blocks(int64_t n);
+/* sumsq, norm and nonfinite of ctrl from the gradient; the other fields keep their contents.  Two launches: per workgroup the
+ * sum of (double)g * (double)g over its chunk -- a fixed element -> lane assignment whatever the pointer's alignment, a fixed tree
+ * over lanes, waves and the workgroup -- and the count of non-finite elements, written to context scratch; then one workgroup adds
+ * the partial sums in index order in double.  No atomics: two calls on the same bytes give the same bits. */
+int mgu_grad_norm(mgu_ctx* ctx, const void* grad_dev, int64_t n, float grad_scale, void* ctrl_dev, void* hip_stream);
+/* One optimizer step in exactly three launches whatever n and the options: the two of mgu_grad_norm, whose second also decides
+ *   coef  = max_norm > 0 ? min(1, max_norm / (norm + 1e-6)) : 1     (torch.nn.utils.clip_grad_norm_ on the scaled gradient; double)
+ *   scale = (float)(grad_scale * coef)
+ *   skip_nonfinite && nonfinite > 0:  apply = 0, skipped += 1;   else  apply = 1, step += 1
+ *   bc1 = 1 - beta1^step, bc2_sqrt = sqrt(1 - beta2^step)            (double, cast once; from the record's step)
+ *   ema_d = ema_warmup ? min(ema_decay, (1 + step) / (10 + step)) : ema_decay
+ * and the update kernel, per element with g' = scale * g:
+ *   kind 0  g' += wd * p;  m, v moments;  p -= lr / bc1 * m / (sqrt(v) / bc2_sqrt + eps)          (as mgu_adam_step)
+ *   kind 1  p *= 1 - lr * wd;  the same moments and step on g' alone                               (torch.optim.AdamW)
+ *   kind 2  g' += wd * p;  momentum != 0: buf = step == 1 ? g' : momentum * buf + g', p -= lr * buf;  else p -= lr * g'
+ *   ema_decay > 0:  ema = ema_d * ema + (1 - ema_d) * p_new
+ * With apply == 0 param, exp_avg, exp_avg_sq and ema keep their bits.  exp_avg_dev: Adam's first moment / SGD's momentum buffer
+ * (NULL allowed for kind 2 with momentum 0); exp_avg_sq_dev: NULL allowed for kind 2. */
+int mgu_optim_step(mgu_ctx* ctx, const mgu_optim_desc* desc, void* flat_param_dev, const void* flat_grad_dev, void* exp_avg_dev,
+                   void* exp_avg_sq_dev, void* ema_dev, void* ctrl_dev, int64_t n, void* hip_stream);
+/* acc = first ? grad : acc + grad (fp32, one launch). */
+int mgu_grad_accumulate(mgu_ctx* ctx, void* acc_dev, const void* grad_dev, int64_t n, int first, void* hip_stream);
+
 /* ---- gradient exchange of the data-parallel train step: RCCL over xGMI (the reference is single-process and has no
  *      collective; BASELINE configs[4] adds exactly this one, SURVEY sections 5 / 8b / 8e) -------------------------------
  * librccl is bound at run time inside libmgunet.so.  The host only moves 128 bytes: rank 0 calls mgu_comm_get_unique_id,

@@ -87,6 +87,8 @@ struct mgu_ctx {
   struct mgu_gat_weights* gat_tmp = nullptr;   // weights prepared by the one-shot mgu_gat_layer_forward
   void* lossws = nullptr;   // partial records of the auxiliary-loss reductions (losses.hip)
   size_t lossws_bytes = 0;
+  void* optws = nullptr;    // per-workgroup partial sums and non-finite counts of the gradient norm (optim.hip): one fixed size
+  size_t optws_bytes = 0;
   void* imgws = nullptr;    // resampling coefficient tables / histograms of the input pipeline (imageops.hip)
   size_t imgws_bytes = 0;
   void* ncws = nullptr;     // normalized-cut accumulators (mgu_ncut_forward)

@@ -142,6 +142,7 @@ void mgu_destroy(mgu_ctx* c) {
   if (c->labtab) (void)hipFree(c->labtab);
   if (c->lossws) (void)hipFree(c->lossws);
   if (c->imgws) (void)hipFree(c->imgws);
+  if (c->optws) (void)hipFree(c->optws);
   gat_destroy(c);
   if (c->err_word) (void)hipHostFree(c->err_word);
   for (auto e : c->ev) (void)hipEventDestroy(e);

@@ -2,7 +2,7 @@
 model/ API over libmgunet.so).  Importing works without a GPU; running anything needs one."""
 from .config import build_from_config, get_config_recursively, load_config  # noqa: F401
 from .detection import DetectionHead  # noqa: F401
-from .engine import E2ETrainer, FlatAdam, MinGraphUNet, MinGraphUNetE2E, StepLR, Trainer, adam_state_dict, allreduce_mean_, argmax_classes, gat_forward_csr, segment_batch, shard_batch  # noqa: F401
+from .engine import CosineAnnealingLR, E2ETrainer, FlatAdam, MinGraphUNet, MinGraphUNetE2E, ReduceLROnPlateau, StepLR, Trainer, scheduler_from_config, trainer_from_config, adam_state_dict, allreduce_mean_, argmax_classes, gat_forward_csr, segment_batch, shard_batch  # noqa: F401
 from .gat import GATNetwork, GraphAttentionLayer, MultiHeadGATLayer, seed_dropout  # noqa: F401
 from .losses import (EllipticalShapeLoss, FeatureConsistencyLoss, TVLoss, class_weights, dice_loss, lovasz_softmax,  # noqa: F401
                      pixel_cross_entropy)
@@ -31,4 +31,4 @@ __all__ = ["SuperpixelGraph", "connect_regions", "lab_tables", "region_adjacency
            "patch_features_u8", "patch_node_features", "patch_labels", "postprocess_segmentation", "DetectionHead", "FeatureFusion", "region_stage", "region_mean_pool", "region_fuse", "region_edge_index", "MinCutRefinement", "PatchSegmentPredictor", "graph_cut", "cut_capacities", "cut_energy", "GraphCut", "graph_cut_multi", "label_costs", "cut_energy_multi", "MultiCut", "UNet", "UNetEncoder", "UNetDecoder", "ConvBlock", "DecoderBlock", "GATNetwork", "MultiHeadGATLayer",
            "GraphAttentionLayer", "PatchGraphConstructor", "MinGraphUNet", "MinGraphUNetE2E", "segment_batch", "argmax_classes",
            "gat_forward_csr", "shard_batch", "segmentation_metrics", "metrics_from_confusion", "SegmentationEvaluator", "evaluate_segmentation",
-           "allreduce_eval_state", "clean_masks", "connected_components", "border_distances", "border_weights", "ObjectTable", "yield_estimation_metrics", "YieldEvaluator", "evaluate_yield", "object_shapes", "ObjectShapes", "object_overlaps", "OverlapTable", "match_masks", "panoptic_totals", "instance_metrics", "object_detection_mAP", "InstanceEvaluator", "evaluate_instances", "boundary_tables", "BoundaryTables", "boundary_metrics", "BoundaryEvaluator", "evaluate_boundaries", "frame_shifts", "link_objects", "track_ids", "VideoCounter", "count_video", "predict_tta", "object_scores", "predict_tiled", "tile_grid", "tile_weights", "refine_probs", "bilateral_tables", "EdgeRefiner", "Trainer", "E2ETrainer", "FlatAdam", "StepLR", "adam_state_dict", "allreduce_mean_", "load_config", "get_config_recursively", "build_from_config", "build", "lib"]
+           "allreduce_eval_state", "clean_masks", "connected_components", "border_distances", "border_weights", "ObjectTable", "yield_estimation_metrics", "YieldEvaluator", "evaluate_yield", "object_shapes", "ObjectShapes", "object_overlaps", "OverlapTable", "match_masks", "panoptic_totals", "instance_metrics", "object_detection_mAP", "InstanceEvaluator", "evaluate_instances", "boundary_tables", "BoundaryTables", "boundary_metrics", "BoundaryEvaluator", "evaluate_boundaries", "frame_shifts", "link_objects", "track_ids", "VideoCounter", "count_video", "predict_tta", "object_scores", "predict_tiled", "tile_grid", "tile_weights", "refine_probs", "bilateral_tables", "EdgeRefiner", "Trainer", "E2ETrainer", "FlatAdam", "StepLR", "CosineAnnealingLR", "ReduceLROnPlateau", "trainer_from_config", "scheduler_from_config", "adam_state_dict", "allreduce_mean_", "load_config", "get_config_recursively", "build_from_config", "build", "lib"]

@@ -29,6 +29,17 @@ class KernelStat(C.Structure):
                 ("launches", C.c_int), ("pipe", C.c_int)]
 
 
+class OptimDesc(C.Structure):
+    """mgu_optim_desc (include/mgunet.h): the options of one mgu_optim_step."""
+    _fields_ = [("kind", C.c_int), ("lr", C.c_float), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_float),
+                ("weight_decay", C.c_float), ("momentum", C.c_float), ("grad_scale", C.c_float), ("max_norm", C.c_float),
+                ("skip_nonfinite", C.c_int), ("ema_decay", C.c_float), ("ema_warmup", C.c_int)]
+
+
+OPTIM_KINDS = {"adam": 0, "adamw": 1, "sgd": 2}     # MGU_OPTIM_*
+OPTIM_CTRL_BYTES = 64                               # MGU_OPTIM_CTRL_BYTES
+
+
 def read_kernel_stats(ctx) -> list:
     """mgu_profile_read_kernels as a list of dicts (per kernel family since mgu_profile_enable(ctx, 1))."""
     arr = (KernelStat * 64)()

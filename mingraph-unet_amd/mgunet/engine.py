@@ -3,7 +3,9 @@ experiments/segmentation_performance.py:119-144 (eval) and scripts/train_end_to_
 (U-Net + patch-graph GAT forward), with the batch sharded over ranks (one process per GPU)."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import math
 
 import torch
 import torch.nn as nn
@@ -179,9 +181,10 @@ def allreduce_mean_(flat: torch.Tensor, group=None) -> float:
     return 1.0 / world
 
 
-def adam_state_dict(params, exp_avg_flat, exp_avg_sq_flat, step, lr, betas, eps, weight_decay) -> dict:
+def adam_state_dict(params, exp_avg_flat, exp_avg_sq_flat, step, lr, betas, eps, weight_decay, decoupled=False) -> dict:
     """torch.optim.Adam.state_dict() layout from flat moment buffers in named_parameters() order (pure tensor plumbing: runs on any
-    device; the CPU tier checks it against a real torch.optim.Adam)."""
+    device; the CPU tier checks it against a real torch.optim.Adam).  decoupled: torch.optim.AdamW's layout, the same with
+    decoupled_weight_decay set."""
     state, off = {}, 0
     for i, p in enumerate(params):
         k = p.numel()
@@ -190,7 +193,7 @@ def adam_state_dict(params, exp_avg_flat, exp_avg_sq_flat, step, lr, betas, eps,
                         "exp_avg_sq": exp_avg_sq_flat[off:off + k].detach().clone().view_as(p)}
         off += k
     group = {"lr": lr, "betas": tuple(betas), "eps": eps, "weight_decay": weight_decay, "amsgrad": False, "maximize": False, "foreach": None,
-             "capturable": False, "differentiable": False, "fused": None, "decoupled_weight_decay": False, "params": list(range(len(params)))}
+             "capturable": False, "differentiable": False, "fused": None, "decoupled_weight_decay": bool(decoupled), "params": list(range(len(params)))}
     return {"state": state, "param_groups": [group]}
 
 
@@ -217,7 +220,157 @@ class StepLR:
         self.trainer.set_lr(self.base_lr * self.gamma ** (self.last_epoch // self.step_size))
 
 
-class Trainer:
+class CosineAnnealingLR:
+    """optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max, eta_min) for a Trainer, stepped once per epoch: torch's own
+    recurrence on the current learning rate (not the closed form, which differs from it in the last bits), so the sequence equals
+    torch's with ==."""
+
+    def __init__(self, trainer, T_max: int, eta_min: float = 0.0):
+        self.trainer, self.T_max, self.eta_min = trainer, int(T_max), float(eta_min)
+        self.base_lr, self.last_epoch = trainer.lr, 0
+
+    def step(self) -> None:
+        m, T, lr = math, self.T_max, self.trainer.lr
+        self.last_epoch += 1
+        if (self.last_epoch - 1 - T) % (2 * T) == 0:
+            lr = lr + (self.base_lr - self.eta_min) * (1 - m.cos(m.pi / T)) / 2
+        else:
+            lr = (1 + m.cos(m.pi * self.last_epoch / T)) / (1 + m.cos(m.pi * (self.last_epoch - 1) / T)) * (lr - self.eta_min) + self.eta_min
+        self.trainer.set_lr(lr)
+
+    def get_last_lr(self):
+        return [self.trainer.lr]
+
+    def state_dict(self) -> dict:
+        return {"T_max": self.T_max, "eta_min": self.eta_min, "base_lrs": [self.base_lr], "last_epoch": self.last_epoch,
+                "_last_lr": [self.trainer.lr]}
+
+    def load_state_dict(self, sd: dict) -> None:
+        self.T_max, self.eta_min, self.base_lr, self.last_epoch = sd["T_max"], sd["eta_min"], sd["base_lrs"][0], sd["last_epoch"]
+        self.trainer.set_lr(sd["_last_lr"][0])     # the recurrence continues from the rate it had reached
+
+
+class ReduceLROnPlateau:
+    """optim.lr_scheduler.ReduceLROnPlateau for a Trainer: step(metric) once per epoch; after more than `patience` epochs without
+    an improvement (by `threshold`, relative or absolute) the rate becomes max(lr * factor, min_lr) where that lowers it by more than
+    `eps`, and `cooldown` epochs pass before bad epochs count again.  torch's own comparisons in torch's order."""
+
+    def __init__(self, trainer, mode="min", factor=0.1, patience=10, threshold=1e-4, threshold_mode="rel", cooldown=0, min_lr=0.0,
+                 eps=1e-8):
+        if factor >= 1.0:
+            raise ValueError("Factor should be < 1.0.")
+        if mode not in ("min", "max"):
+            raise ValueError(f"mode {mode} is unknown!")
+        if threshold_mode not in ("rel", "abs"):
+            raise ValueError(f"threshold mode {threshold_mode} is unknown!")
+        self.trainer, self.mode, self.factor, self.patience = trainer, mode, float(factor), int(patience)
+        self.threshold, self.threshold_mode, self.cooldown, self.min_lr, self.eps = threshold, threshold_mode, int(cooldown), float(min_lr), eps
+        self.best = float("inf") if mode == "min" else -float("inf")
+        self.cooldown_counter, self.num_bad_epochs, self.last_epoch = 0, 0, 0
+
+    def _is_better(self, a, best) -> bool:
+        if self.mode == "min" and self.threshold_mode == "rel":
+            return a < best * (1.0 - self.threshold)
+        if self.mode == "min":
+            return a < best - self.threshold
+        if self.threshold_mode == "rel":
+            return a > best * (self.threshold + 1.0)
+        return a > best + self.threshold
+
+    def step(self, metrics) -> None:
+        current = float(metrics)
+        self.last_epoch += 1
+        if self._is_better(current, self.best):
+            self.best, self.num_bad_epochs = current, 0
+        else:
+            self.num_bad_epochs += 1
+        if self.cooldown_counter > 0:
+            self.cooldown_counter -= 1
+            self.num_bad_epochs = 0
+        if self.num_bad_epochs > self.patience:
+            old = float(self.trainer.lr)
+            new = max(old * self.factor, self.min_lr)
+            if old - new > self.eps:
+                self.trainer.set_lr(new)
+            self.cooldown_counter, self.num_bad_epochs = self.cooldown, 0
+
+    def get_last_lr(self):
+        return [self.trainer.lr]
+
+    _KEYS = ("mode", "factor", "patience", "threshold", "threshold_mode", "cooldown", "min_lr", "eps", "best", "cooldown_counter",
+             "num_bad_epochs", "last_epoch")
+
+    def state_dict(self) -> dict:
+        return {**{k: getattr(self, k) for k in self._KEYS}, "_last_lr": [self.trainer.lr]}
+
+    def load_state_dict(self, sd: dict) -> None:
+        for k in self._KEYS:
+            setattr(self, k, sd[k])
+        self.trainer.set_lr(sd["_last_lr"][0])
+
+
+class _DeviceStep:
+    """What Trainer and FlatAdam share of the optimizer step whose decisions stay on the device (mgu_optim_step, INTEGRATION.md
+    section X): the options, the 64-byte control record, the EMA buffer.  The host class has flat / grad / exp_avg / exp_avg_sq,
+    lr / wd / betas / eps / momentum and device."""
+
+    def _init_device_step(self, kind, max_grad_norm, skip_nonfinite, ema_decay, ema_warmup, always=False) -> None:
+        self.optim_kind = kind
+        self.max_grad_norm, self.skip_nonfinite = float(max_grad_norm), bool(skip_nonfinite)
+        self.ema_decay, self.ema_warmup = float(ema_decay), bool(ema_warmup)
+        # with every option at its default and Adam or SGD the step stays the one mgu_adam_step / mgu_sgd_step launch
+        self.device_step = bool(always or kind == "adamw" or self.max_grad_norm > 0.0 or self.skip_nonfinite or self.ema_decay > 0.0)
+        self.ctrl = self.ema = None
+
+    @staticmethod
+    def _check_step_options(max_grad_norm, ema_decay) -> None:
+        if not (float(max_grad_norm) >= 0.0 and float(max_grad_norm) != float("inf")):
+            raise ValueError(f"max_grad_norm must be finite and >= 0 (0: no clipping), got {max_grad_norm}")
+        if not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError(f"ema_decay must lie in [0, 1) (0: no EMA), got {ema_decay}")
+
+    def _alloc_device_step(self) -> None:
+        """After the flat buffer holds the parameters: the zeroed record (a fresh optimizer) and the EMA as a copy of them."""
+        if self.device_step:
+            self.ctrl = torch.zeros(_lib.OPTIM_CTRL_BYTES // 8, device=self.device, dtype=torch.int64)
+        if self.ema_decay > 0.0:
+            self.ema = self.flat.detach().clone()
+
+    def _device_optim_step(self, grad, grad_scale, ctx=None) -> None:
+        d = _lib.OptimDesc(_lib.OPTIM_KINDS[self.optim_kind], self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
+                           getattr(self, "momentum", 0.0), grad_scale, self.max_grad_norm, int(self.skip_nonfinite), self.ema_decay,
+                           int(self.ema_warmup))
+        _lib.call("mgu_optim_step", self.device, C.byref(d), self.flat, grad, self.exp_avg,
+                  None if self.optim_kind == "sgd" else self.exp_avg_sq, self.ema, self.ctrl, self.flat.numel(), ctx=ctx)
+
+    def _need_record(self) -> None:
+        if self.ctrl is None:
+            raise RuntimeError("this optimizer steps through mgu_adam_step / mgu_sgd_step and keeps no control record: it has one with "
+                               "optimizer='adamw', max_grad_norm, skip_nonfinite or ema_decay")
+
+    @property
+    def grad_norm(self) -> torch.Tensor:
+        """L2 norm of the last step's scaled gradient (before clipping): a float64 device scalar, a view of the record -- reading it
+        here does not synchronise."""
+        self._need_record()
+        return self.ctrl.view(torch.float64)[3]
+
+    def applied_steps(self) -> int:
+        """Steps the device applied (the record's `step`).  Synchronises."""
+        self._need_record()
+        return int(self.ctrl[0])
+
+    def skipped_steps(self) -> int:
+        """Steps skipped for a non-finite gradient (the record's `skipped`).  Synchronises."""
+        self._need_record()
+        return int(self.ctrl[1])
+
+    def _set_device_steps(self, step: int) -> None:
+        if self.ctrl is not None:
+            self.ctrl[0] = int(step)
+
+
+class Trainer(_DeviceStep):
     """The train step of scripts/train_segmentation.py:117-137 on the HIP path:
     zero_grad -> logits = model(images) (train-mode BatchNorm) -> CrossEntropyLoss (mean) -> backward ->
     [mean all-reduce of the flat gradient over the data-parallel ranks] -> Adam(lr, weight_decay as L2).
@@ -228,7 +381,8 @@ class Trainer:
     def __init__(self, model: UNet, lr=1e-3, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, process_group=None, comm="auto",
                  loss="ce", dice_smooth=1.0, optimizer="adam", momentum=0.9, lovasz_per_image=False, lovasz_classes="present",
                  ce_weight=None, label_smoothing=0.0, focal_gamma=0.0, hard_fraction=1.0, hard_min_kept=0, hard_per_image=False,
-                 border_w0=0.0, border_sigma=5.0, border_connectivity=2, border_separate=False):
+                 border_w0=0.0, border_sigma=5.0, border_connectivity=2, border_separate=False, max_grad_norm=0.0,
+                 skip_nonfinite=False, ema_decay=0.0, ema_warmup=False, accumulate=1):
         """comm: "auto" (default) -- with more than one rank the gradient is mean-all-reduced by torch.distributed (RCCL when the
         backend is "nccl") after backward: the path exercised with two ranks.  "rccl" -- opt in to libmgunet's own RCCL
         communicator with the bucketed exchange overlapped with backward (mgu_unet_backward_allreduce); tests/test_gpu_rccl.py
@@ -251,9 +405,27 @@ class Trainer:
         the step launches nothing new and calls exactly what it called before.
         ("rccl" also creates the communicator for a single process: the collective then degenerates to a copy.)
         optimizer: "adam" (train_segmentation.py:96, the shipped configs/training.yaml) or "sgd" -- the script's other branch,
-        optim.SGD(lr, momentum=sgd_momentum, weight_decay) (:97-98; training.yaml:5-6): one fused kernel on the flat buffers either way."""
-        if optimizer not in ("adam", "sgd"):
-            raise ValueError(f"unknown optimizer {optimizer!r}: 'adam' or 'sgd'")
+        optim.SGD(lr, momentum=sgd_momentum, weight_decay) (:97-98; training.yaml:5-6): one fused kernel on the flat buffers either way;
+        or "adamw", torch.optim.AdamW (decoupled weight decay).
+        max_grad_norm, skip_nonfinite, ema_decay, ema_warmup, accumulate: with all five at their defaults
+        and "adam" or "sgd" the step is the one mgu_adam_step / mgu_sgd_step call it has always been.  Otherwise it is one
+        mgu_optim_step -- three launches, every decision on the device, the host never blocked: max_grad_norm > 0 clips the averaged,
+        scaled gradient to that L2 norm (torch.nn.utils.clip_grad_norm_'s arithmetic on a norm summed in double in a fixed order;
+        `grad_norm` is the device scalar); skip_nonfinite leaves parameters, moments, EMA and the step count of the bias corrections
+        untouched when the gradient holds an inf or a NaN (`skipped_steps()`); ema_decay > 0 keeps an exponential moving average of the
+        parameters, a copy of them at the start (ema_warmup: decay min(ema_decay, (1 + t) / (10 + t)) at step t; `ema_state_dict()`,
+        `with trainer.ema_weights():`).  accumulate=k: train_step runs forward and backward every call and adds the gradient into an
+        accumulator (mgu_grad_accumulate); the k-th call exchanges the accumulator (comm="auto": one all-reduce) and steps with
+        grad_scale = 1 / (k * world).  comm="rccl" with accumulate > 1 raises ValueError: that exchange runs inside backward, bucket
+        by bucket on each call's gradient, and has no accumulator to work on."""
+        if optimizer not in _lib.OPTIM_KINDS:
+            raise ValueError(f"unknown optimizer {optimizer!r}: 'adam', 'adamw' or 'sgd'")
+        self._check_step_options(max_grad_norm, ema_decay)
+        if int(accumulate) != accumulate or accumulate < 1:
+            raise ValueError(f"accumulate must be an integer >= 1, got {accumulate}")
+        if comm == "rccl" and accumulate > 1:
+            raise ValueError('comm="rccl" exchanges each backward\'s gradient inside that backward: it cannot be combined with accumulate > 1 '
+                             '(use comm="auto")')
         if loss not in LOSSES:
             raise ValueError(f"unknown loss {loss!r}: " + ", ".join(repr(k) for k in LOSSES[:-1]) + f" or {LOSSES[-1]!r}")
         if lovasz_classes not in _LOVASZ_CLASSES:
@@ -292,6 +464,10 @@ class Trainer:
         model.mark_parameters_changed()
         model._slots = None
         self.step_count = 0
+        self.accumulate, self._micro = int(accumulate), 0
+        self.acc = torch.zeros(n, device=dev, dtype=torch.float32) if self.accumulate > 1 else None
+        self._init_device_step(optimizer, max_grad_norm, skip_nonfinite, ema_decay, ema_warmup, always=self.accumulate > 1)
+        self._alloc_device_step()
         self.loss_kind, self.dice_smooth = loss, float(dice_smooth)
         self.lovasz_mode, self.lovasz_per_image = _LOVASZ_CLASSES[lovasz_classes], int(bool(lovasz_per_image))
         self._lovasz = torch.zeros(1, device=dev, dtype=torch.float32)
@@ -341,20 +517,22 @@ class Trainer:
     def optimizer_state_dict(self) -> dict:
         """What torch.optim.Adam(model.parameters(), lr, weight_decay=wd).state_dict() would hold after the same steps: per
         parameter {'step', 'exp_avg', 'exp_avg_sq'} (views of the flat moment buffers, cloned) + one param_group.  Loadable into a
-        real torch.optim.Adam, and back (load_optimizer_state_dict)."""
+        real torch.optim.Adam, and back (load_optimizer_state_dict).  optimizer="adamw": the layout of torch.optim.AdamW, loadable
+        into a real one.  With skip_nonfinite the step count is the record's (a skipped step does not count): that read synchronises."""
+        steps = self.applied_steps() if self.skip_nonfinite else self.step_count
         if self.optimizer == "sgd":   # torch.optim.SGD's layout: {'momentum_buffer'} per parameter, one param_group
             params = [p for _, p in self.model.named_parameters()]
             state, off = {}, 0
             for i, p in enumerate(params):
                 k = p.numel()
-                if self.step_count > 0 and self.momentum != 0:
+                if steps > 0 and self.momentum != 0:
                     state[i] = {"momentum_buffer": self.exp_avg[off:off + k].view_as(p).clone()}
                 off += k
             return {"state": state, "param_groups": [{"lr": self.lr, "momentum": self.momentum, "dampening": 0, "weight_decay": self.wd,
                                                       "nesterov": False, "maximize": False, "foreach": None, "differentiable": False,
                                                       "fused": None, "params": list(range(len(params)))}]}
-        return adam_state_dict([p for _, p in self.model.named_parameters()], self.exp_avg, self.exp_avg_sq, self.step_count,
-                               self.lr, self.betas, self.eps, self.wd)
+        return adam_state_dict([p for _, p in self.model.named_parameters()], self.exp_avg, self.exp_avg_sq, steps,
+                               self.lr, self.betas, self.eps, self.wd, decoupled=self.optimizer == "adamw")
 
     def load_optimizer_state_dict(self, sd: dict) -> None:
         params = [p for _, p in self.model.named_parameters()]
@@ -374,6 +552,7 @@ class Trainer:
             if have not in (0, len(params)):
                 raise ValueError("a momentum buffer for some parameters only cannot be represented by the fused flat SGD")
             self.step_count = 2 if have else 0     # SGD keeps no step count: any value past the first step continues the buffers
+            self._set_device_steps(self.step_count)
             return
         if len(sd["param_groups"]) != 1 or list(g["params"]) != list(range(len(params))):
             raise ValueError("expected the single param_group of optim.Adam(model.parameters(), ...) (train_segmentation.py:96)")
@@ -393,12 +572,60 @@ class Trainer:
         if len(steps) > 1:
             raise ValueError("parameters with different step counts cannot be represented by the fused flat Adam")
         self.step_count = steps.pop() if steps else 0
+        self._set_device_steps(self.step_count)
+
+    # ---- the averaged weights (ema_decay > 0) -------------------------------------------------------------------------------------
+    def _need_ema(self) -> None:
+        if self.ema is None:
+            raise RuntimeError("this Trainer keeps no EMA of its parameters: construct it with ema_decay > 0")
+
+    def ema_state_dict(self) -> dict:
+        """The model's state_dict with every parameter replaced by its moving average; the buffers (BatchNorm running statistics)
+        are the live model's: they are not averaged."""
+        self._need_ema()
+        sd = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
+        off = 0
+        for name, p in self.model.named_parameters():
+            k = p.numel()
+            sd[name] = self.ema[off:off + k].view_as(p).clone()
+            off += k
+        return sd
+
+    def load_ema_state_dict(self, sd: dict) -> None:
+        self._need_ema()
+        off = 0
+        for name, p in self.model.named_parameters():
+            k = p.numel()
+            self.ema[off:off + k].copy_(sd[name].reshape(-1))
+            off += k
+
+    def _swap_ema(self) -> None:
+        live = self.flat.clone()
+        self.flat.copy_(self.ema)
+        self.ema.copy_(live)
+        self.model.mark_parameters_changed()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block the model runs on the averaged parameters: the flat buffer and the EMA buffer change places on the
+        device (three copies, the parameters stay views of the flat buffer) and the model is told its parameters changed; on exit
+        they change back, bit for bit, and training continues.  Do not step inside the block."""
+        self._need_ema()
+        self._swap_ema()
+        try:
+            yield self.model
+        finally:
+            self._swap_ema()
 
     def save_checkpoint(self, path: str, epoch: int, loss: float) -> None:
         """The reference's checkpoint dict (train_segmentation.py:158-163): readable by its own loaders
-        (infer_segmentation.py:90-95, segmentation_performance.py:86-110) and by torch.optim.Adam."""
-        torch.save({"epoch": epoch, "model_state_dict": {k: v.detach().clone() for k, v in self.model.state_dict().items()},
-                    "optimizer_state_dict": self.optimizer_state_dict(), "loss": loss}, path)
+        (infer_segmentation.py:90-95, segmentation_performance.py:86-110) and by torch.optim.Adam.  With ema_decay > 0 it carries one more key, "ema_state_dict" (ema_state_dict()); those loaders
+        read the keys they know and ignore it."""
+        ck = {"epoch": epoch, "model_state_dict": {k: v.detach().clone() for k, v in self.model.state_dict().items()},
+              "optimizer_state_dict": self.optimizer_state_dict(), "loss": loss}
+        if self.ema is not None:
+            ck["ema_state_dict"] = self.ema_state_dict()
+        torch.save(ck, path)
 
     def load_checkpoint(self, path: str) -> dict:
         """Resume from either layout the reference writes: the checkpoint dict or a bare state_dict (:166-168).  Returns the dict."""
@@ -411,6 +638,11 @@ class Trainer:
         self.model.mark_parameters_changed()
         if isinstance(ck, dict) and "optimizer_state_dict" in ck:
             self.load_optimizer_state_dict(ck["optimizer_state_dict"])
+        if self.ema is not None:      # a checkpoint written without EMA restarts the average from the loaded parameters
+            if isinstance(ck, dict) and "ema_state_dict" in ck:
+                self.load_ema_state_dict(ck["ema_state_dict"])
+            else:
+                self.ema.copy_(self.flat)
         return ck if isinstance(ck, dict) else {"model_state_dict": ck}
 
     def _border_map(self, masks: torch.Tensor, instances, num_classes: int, ctx):
@@ -478,15 +710,19 @@ class Trainer:
         the ignore_index -100) -- the place torch would have raised; train_step itself never blocks the host."""
         _lib.call("mgu_sync_check", self.device, ctx=self.model._context(self.device))
 
-    def optimizer_step(self, grad_scale: float = 1.0) -> None:
+    def optimizer_step(self, grad_scale: float = 1.0, grad=None) -> None:
+        """One step on `grad` (default: self.grad, what forward_backward filled) scaled by grad_scale."""
         model, dev = self.model, self.device
         ctx = model._context(dev)
+        grad = self.grad if grad is None else grad
         self.step_count += 1
-        if self.optimizer == "sgd":   # the momentum buffer lives in exp_avg (exp_avg_sq is unused by this branch)
-            _lib.call("mgu_sgd_step", dev, self.flat, self.grad, self.exp_avg, self.flat.numel(), self.lr, self.momentum, self.wd,
+        if self.device_step:          # three launches; whether the step applied is known to the device alone
+            self._device_optim_step(grad, grad_scale, ctx=ctx)
+        elif self.optimizer == "sgd":   # the momentum buffer lives in exp_avg (exp_avg_sq is unused by this branch)
+            _lib.call("mgu_sgd_step", dev, self.flat, grad, self.exp_avg, self.flat.numel(), self.lr, self.momentum, self.wd,
                       self.step_count, grad_scale, ctx=ctx)
         else:
-            _lib.call("mgu_adam_step", dev, self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.flat.numel(), self.lr, self.betas[0],
+            _lib.call("mgu_adam_step", dev, self.flat, grad, self.exp_avg, self.exp_avg_sq, self.flat.numel(), self.lr, self.betas[0],
                       self.betas[1], self.eps, self.wd, self.step_count, grad_scale, ctx=ctx)
         model.refresh_packed_weights(dev)   # same tensors, new contents: repack in place (no state_dict round trip per step)
 
@@ -496,20 +732,75 @@ class Trainer:
             self.optimizer_step(1.0)
             return loss
         loss = self.forward_backward(images, masks, instances=instances)
-        scale = allreduce_mean_(self.grad, self.group) if self.comm is not None else 1.0   # torch.distributed (RCCL / gloo); 1 rank: no-op
-        self.optimizer_step(scale)
+        grad = self.grad
+        if self.accumulate > 1:       # every call adds its gradient; the last of each k exchanges the sum and steps
+            _lib.call("mgu_grad_accumulate", self.device, self.acc, self.grad, self.acc.numel(), int(self._micro == 0),
+                      ctx=self.model._context(self.device))
+            self._micro = (self._micro + 1) % self.accumulate
+            if self._micro:
+                return loss
+            grad = self.acc
+        scale = allreduce_mean_(grad, self.group) if self.comm is not None else 1.0   # torch.distributed (RCCL / gloo); 1 rank: no-op
+        self.optimizer_step(scale / self.accumulate, grad)
         return loss
 
 
-class FlatAdam:
+_CONFIG_OPTIMIZERS = {"adam": "adam", "adamw": "adamw", "sgd": "sgd"}
+
+
+def trainer_from_config(model: UNet, train_cfg: dict, **overrides) -> "Trainer":
+    """Trainer(model, ...) from a training config (configs/training.yaml, as load_config reads it).  The reference's keys:
+    optimizer (any letter case, as train_segmentation.py:95-98 lowers it: "Adam", "AdamW", "SGD"), learning_rate, weight_decay,
+    sgd_momentum.  Keys of this build, each optional and off when absent: grad_clip_norm (max_grad_norm), ema_decay,
+    accumulate_steps (accumulate), skip_nonfinite.  `overrides` are Trainer arguments that win over the config."""
+    name = str(train_cfg.get("optimizer", "Adam")).lower()
+    if name not in _CONFIG_OPTIMIZERS:
+        raise ValueError(f"unsupported optimizer {train_cfg.get('optimizer')!r} in the training config: 'Adam', 'AdamW' or 'SGD'")
+    kw = {"optimizer": _CONFIG_OPTIMIZERS[name]}
+    for key, arg, conv in (("learning_rate", "lr", float), ("weight_decay", "weight_decay", float), ("sgd_momentum", "momentum", float),
+                           ("grad_clip_norm", "max_grad_norm", float), ("ema_decay", "ema_decay", float),
+                           ("accumulate_steps", "accumulate", int), ("skip_nonfinite", "skip_nonfinite", bool)):
+        if train_cfg.get(key) is not None:
+            kw[arg] = conv(train_cfg[key])
+    kw.update(overrides)
+    return Trainer(model, **kw)
+
+
+def scheduler_from_config(trainer, train_cfg: dict):
+    """The scheduler a training config names under lr_scheduler: "StepLR" (lr_step_size, lr_gamma; train_segmentation.py:105),
+    "CosineAnnealingLR" (lr_t_max, default num_epochs; lr_eta_min) or "ReduceLROnPlateau" (lr_factor or lr_gamma, lr_patience);
+    None when the key is absent or empty."""
+    name = train_cfg.get("lr_scheduler")
+    if not name or str(name).lower() == "none":
+        return None
+    low = str(name).lower()
+    if low == "steplr":
+        return StepLR(trainer, int(train_cfg.get("lr_step_size", 30)), float(train_cfg.get("lr_gamma", 0.1)))
+    if low == "cosineannealinglr":
+        t_max = train_cfg.get("lr_t_max", train_cfg.get("num_epochs"))
+        if t_max is None:
+            raise ValueError("lr_scheduler CosineAnnealingLR needs lr_t_max (or num_epochs) in the training config")
+        return CosineAnnealingLR(trainer, int(t_max), float(train_cfg.get("lr_eta_min", 0.0)))
+    if low == "reducelronplateau":
+        return ReduceLROnPlateau(trainer, factor=float(train_cfg.get("lr_factor", train_cfg.get("lr_gamma", 0.1))),
+                                 patience=int(train_cfg.get("lr_patience", 10)))
+    raise ValueError(f"unsupported lr_scheduler {name!r} in the training config: 'StepLR', 'CosineAnnealingLR' or 'ReduceLROnPlateau'")
+
+
+class FlatAdam(_DeviceStep):
     """torch.optim.Adam(params, lr, betas, eps, weight_decay) (the optimizer of both reference loops, train_end_to_end.py:228) for the
     parameters of ANY modules on the HIP path: they are re-homed as views of one flat fp32 buffer, their .grad as views of a flat
     gradient buffer that autograd accumulates into, and step() is one mgu_adam_step launch.  (`Trainer` does the same for the U-Net,
     whose flat order the library fixes; this is the graph branch's half.)"""
 
-    def __init__(self, modules, lr=1e-3, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, exclude=()):
+    def __init__(self, modules, lr=1e-3, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, exclude=(), decoupled=False, max_grad_norm=0.0,
+                 skip_nonfinite=False, ema_decay=0.0, ema_warmup=False):
         """exclude: parameter-name fragments (as in named_parameters()) left out of the flat buffers -- parameters whose .grad stays
-        None in the reference loop: torch.optim.Adam skips those entirely (no step count, no weight decay)."""
+        None in the reference loop: torch.optim.Adam skips those entirely (no step count, no weight decay).
+        decoupled=True: torch.optim.AdamW.  max_grad_norm, skip_nonfinite, ema_decay, ema_warmup: as Trainer's; with all of them at
+        their defaults step() is the one mgu_adam_step launch, otherwise one mgu_optim_step (three launches).  The norm is that of
+        THIS optimizer's flat gradient: next to a Trainer (E2ETrainer) each of the two clips its own buffer."""
+        self._check_step_options(max_grad_norm, ema_decay)
         seen, params = set(), []
         for m in modules:
             for name, q in m.named_parameters():
@@ -534,14 +825,19 @@ class FlatAdam:
             q.grad = self.grad[off:off + k].view_as(q)
             off += k
         self.step_count = 0
+        self._init_device_step("adamw" if decoupled else "adam", max_grad_norm, skip_nonfinite, ema_decay, ema_warmup)
+        self._alloc_device_step()
 
     def zero_grad(self) -> None:
         self.grad.zero_()          # the .grad views stay in place (set_to_none would detach them from the flat buffer)
 
     def step(self, grad_scale: float = 1.0) -> None:
         self.step_count += 1
-        _lib.call("mgu_adam_step", self.device, self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.flat.numel(), self.lr,
-                  self.betas[0], self.betas[1], self.eps, self.wd, self.step_count, grad_scale)
+        if self.device_step:
+            self._device_optim_step(self.grad, grad_scale)
+        else:
+            _lib.call("mgu_adam_step", self.device, self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.flat.numel(), self.lr,
+                      self.betas[0], self.betas[1], self.eps, self.wd, self.step_count, grad_scale)
         for q in self.params:      # the kernel wrote the parameters behind torch's back: the packed-weight caches key on _version
             torch.autograd.graph.increment_version(q)
 
