@@ -1307,6 +1307,74 @@ int mgu_track_ids(mgu_ctx* ctx, const int64_t* offsets_dev, int T, int64_t capac
                   const int64_t* first_ids_dev, int64_t* next_id_dev, int64_t* track_id_dev, int32_t* track_len_dev, int64_t* track_class_dev,
                   int64_t track_capacity, int32_t* status_dev, void* hip_stream);
 
+/* ---- masks in and out (csrc/maskio.hip): COCO run lengths, polygon outlines, polygon fill ------------------
+ * The label map is what mgu_connected_components / mgu_split_objects write: labels_dev int32 (B, H, W), 0 = background, and
+ * offsets_dev int64 (B + 1); object k of image b is batch-wide row offsets[b] + k - 1.  A pixel whose value lies outside
+ * [1, offsets[b+1] - offsets[b]], or whose row is >= capacity (the length of the per-object arrays), belongs to no object.  All four
+ * are integer definitions of this build (the reference reads class PNGs and has no such stage).  Every output word is a pure function
+ * of the inputs: places come from scans and a stable radix sort, the only atomics are integer add and max; bitwise repeatable.  No
+ * host synchronisation, no wait between workgroups; the number of launches depends on H, W and the arguments, never on the data or
+ * on B.  Arrays are sized by the caller; status_dev is an int32 scalar, OR-ed (the caller clears it), one bit per kind of overflow,
+ * and the surplus is dropped: nothing is written past an array.  B*H*W < 2^31, B <= 65535, H, W <= 32768, capacities < 2^31.
+ * With P(n) = ceil(n / 8) sort passes and bits(v) the bits that hold v, N = capacity:
+ *
+ * mgu_mask_runs: the runs of every object in COCO's column-major order.  The position of pixel (x, y) is p = x*H + y; a run of object
+ * i is a maximal interval of consecutive positions whose pixels are i's (so a run continues from the last row of a column into the
+ * first row of the next).  CSR by object:
+ *   run_ptr_dev     int64 (capacity + 1), every entry written: the true prefix sums, also on overflow
+ *   run_start_dev   int32 (run_capacity): ascending inside a row, start[j+1] > start[j] + length[j]
+ *   run_length_dev  int32 (run_capacity)
+ *   status          1 = more runs than run_capacity (entries whose place is >= run_capacity are dropped: every row that ends at or
+ *                   before run_capacity is complete); 2 = offsets[B] > capacity (the objects past it have no row)
+ * Runs <= B*H*W, so that run_capacity never overflows.  9 + 3 P(bits(N-1)) launches and 1 fill; scratch 29 bytes per pixel + 4 per row. */
+int mgu_mask_runs(mgu_ctx* ctx, const int32_t* labels_dev, const int64_t* offsets_dev, int64_t capacity, int B, int H, int W,
+                  int64_t run_capacity, int64_t* run_ptr_dev, int32_t* run_start_dev, int32_t* run_length_dev, int32_t* status_dev,
+                  void* hip_stream);
+/* The inverse: labels_dev is filled with zeros, then every run of row i paints k = i - offsets[b] + 1 over its positions of image b
+ * (the image whose rows hold i).  Where objects overlap the largest label wins.  status: 1 = a run with start < 0, length < 1 or
+ * start + length > H*W (it paints nothing); 2 = a run of a row outside [offsets[0], offsets[B]) (nothing); 4 = run_ptr[capacity] >
+ * run_capacity (the runs past it are not there).  1 launch and 1 fill; no scratch. */
+int mgu_runs_to_labels(mgu_ctx* ctx, const int64_t* run_ptr_dev, const int32_t* run_start_dev, const int32_t* run_length_dev,
+                       int64_t run_capacity, const int64_t* offsets_dev, int64_t capacity, int B, int H, int W, int32_t* labels_dev,
+                       int32_t* status_dev, void* hip_stream);
+/* mgu_object_outlines: the closed polygons of every object on the pixel grid.  Pixel (x, y) has corners (x, y), (x+1, y), (x+1, y+1),
+ * (x, y+1); a side is an outline edge of object i when the pixel is i's and the pixel across is not -- the outside of the image
+ * counts as "not", so outlines are closed along the frame.  Sides run clockwise on the screen: top 0 (x,y)->(x+1,y), right 1
+ * (x+1,y)->(x+1,y+1), bottom 2 (x+1,y+1)->(x,y+1), left 3 (x,y+1)->(x,y); edge id = (y*W + x)*4 + side.  The successor of an edge is
+ * the edge of the same object that leaves its end point; where two leave (two pixels of i meet diagonally), connectivity 1 takes the
+ * right turn (the same pixel) and connectivity 2 the left turn (the diagonal pixel).  The cycles of that permutation are the loops.  A
+ * loop's leader is its smallest edge id; the loops of an object are listed by ascending leader; the stored vertices are the start
+ * points of the edges whose predecessor has another direction, in travel order from the first such point at or after the leader's
+ * start point.
+ *   loop_ptr_dev    int64 (capacity + 1): the loops of object i are [loop_ptr[i], loop_ptr[i+1]); true prefix sums, also on overflow
+ *   vertex_ptr_dev  int64 (loop_capacity + 1): the vertices of loop l; true prefix sums of the loops below loop_capacity
+ *   vertices_dev    int32 (vertex_capacity, 2): (x, y)
+ *   loop_area2_dev  int64 (loop_capacity): the shoelace sum of x_j y_j+1 - x_j+1 y_j: > 0 for an outer loop, < 0 for a hole; over
+ *                   the loops of an object it is twice the object's pixel count
+ *   status          1 = more loops than loop_capacity; 2 = more vertices than vertex_capacity (in both cases what lies past the
+ *                   capacity is dropped and every row that ends before it is complete); 4 = offsets[B] > capacity
+ * Loops <= B*H*W and vertices <= 4*B*H*W (every pixel its own object reaches both).  4*B*H*W < 2^31.  17 + bits(4HW-1) +
+ * 3 P(bits(N-1) + bits(4HW-1)) launches and 4 fills; scratch 165 bytes per pixel + 4 per row and per loop_ptr / vertex_ptr entry. */
+int mgu_object_outlines(mgu_ctx* ctx, const int32_t* labels_dev, const int64_t* offsets_dev, int64_t capacity, int B, int H, int W,
+                        int connectivity, int64_t loop_capacity, int64_t vertex_capacity, int64_t* loop_ptr_dev, int64_t* vertex_ptr_dev,
+                        int32_t* vertices_dev, int64_t* loop_area2_dev, int32_t* status_dev, void* hip_stream);
+/* mgu_polygons_to_labels: polygons in the layout above (loop_ptr (capacity + 1), vertex_ptr (loop_capacity + 1), vertices) into a
+ * label map.  Coordinates are fixed point with frac_bits in 0..4 fraction bits, |v| < 2^24, and may lie outside the image.  Object i
+ * covers a pixel iff an odd number of the edges of all its loops count for the pixel's centre (even-odd, not winding), exactly: in
+ * doubled units X = 2v, Cx = (2x+1) 2^frac_bits, Cy = (2y+1) 2^frac_bits, the edge (x0,y0)->(x1,y1) counts iff (y0 <= Cy) != (y1 <= Cy)
+ * and, ordered so that y0 < y1, x0 (y1-y0) + (x1-x0)(Cy-y0) < Cx (y1-y0).  Horizontal and zero-length edges never count; a centre on
+ * an edge is decided by these inequalities alone.  Every loop is closed from its last vertex to its first.  labels_dev is filled with
+ * zeros first; where objects overlap the largest label wins.  This is not COCO's rleFrPoly (which upsamples by 5 and draws lines).
+ * One crossing is kept per (edge, scanline it counts for):
+ *   status          1 = more crossings than crossing_capacity (the objects whose edges come first are complete); 2 = a loop of a row
+ *                   outside [offsets[0], offsets[B]), or loop_ptr / vertex_ptr pass loop_capacity / vertex_capacity; 4 = a coordinate
+ *                   outside (-2^24, 2^24) (the edge is left out)
+ * The outlines of a label map cross 2*B*H*W times at most.  4 + 3 P(bits(N-1) + bits(H-1) + bits(W)) launches and 1 fill; scratch
+ * 24 bytes per crossing_capacity entry + 12 per vertex. */
+int mgu_polygons_to_labels(mgu_ctx* ctx, const int64_t* loop_ptr_dev, const int64_t* vertex_ptr_dev, const int32_t* vertices_dev,
+                           int64_t loop_capacity, int64_t vertex_capacity, const int64_t* offsets_dev, int64_t capacity, int B, int H, int W,
+                           int frac_bits, int64_t crossing_capacity, int32_t* labels_dev, int32_t* status_dev, void* hip_stream);
+
 /* ---- introspection for bench.py / profiles ------------------------------------------------------ */
 /* FLOPs (2*MAC, convolutions only) of one U-Net forward over B images: SURVEY 8d table. */
 double mgu_unet_flops(mgu_ctx* ctx, int B, int H, int W);

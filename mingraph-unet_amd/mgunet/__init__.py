@@ -14,6 +14,8 @@ from .border import border_distances, border_weights  # noqa: F401
 from .tta import object_scores, predict_tta  # noqa: F401
 from .instances import (InstanceEvaluator, OverlapTable, evaluate_instances, instance_metrics, match_masks, object_detection_mAP,  # noqa: F401
                         object_overlaps, panoptic_totals)
+from .maskio import (OutlineTable, RunTable, encode_masks, labels_from_runs, object_outlines, objects_from_annotations,  # noqa: F401
+                     rasterize_polygons, rle_from_string, rle_to_string, runs_from_coco)
 from .boundary import BoundaryEvaluator, BoundaryTables, boundary_metrics, boundary_tables, evaluate_boundaries  # noqa: F401
 from .video import VideoCounter, count_video, frame_shifts, link_objects, track_ids  # noqa: F401
 from .tiled import predict_tiled, tile_grid, tile_weights  # noqa: F401
@@ -31,4 +33,4 @@ __all__ = ["SuperpixelGraph", "connect_regions", "lab_tables", "region_adjacency
            "patch_features_u8", "patch_node_features", "patch_labels", "postprocess_segmentation", "DetectionHead", "FeatureFusion", "region_stage", "region_mean_pool", "region_fuse", "region_edge_index", "MinCutRefinement", "PatchSegmentPredictor", "graph_cut", "cut_capacities", "cut_energy", "GraphCut", "graph_cut_multi", "label_costs", "cut_energy_multi", "MultiCut", "UNet", "UNetEncoder", "UNetDecoder", "ConvBlock", "DecoderBlock", "GATNetwork", "MultiHeadGATLayer",
            "GraphAttentionLayer", "PatchGraphConstructor", "MinGraphUNet", "MinGraphUNetE2E", "segment_batch", "argmax_classes",
            "gat_forward_csr", "shard_batch", "segmentation_metrics", "metrics_from_confusion", "SegmentationEvaluator", "evaluate_segmentation",
-           "allreduce_eval_state", "clean_masks", "connected_components", "border_distances", "border_weights", "ObjectTable", "yield_estimation_metrics", "YieldEvaluator", "evaluate_yield", "object_shapes", "ObjectShapes", "object_overlaps", "OverlapTable", "match_masks", "panoptic_totals", "instance_metrics", "object_detection_mAP", "InstanceEvaluator", "evaluate_instances", "boundary_tables", "BoundaryTables", "boundary_metrics", "BoundaryEvaluator", "evaluate_boundaries", "frame_shifts", "link_objects", "track_ids", "VideoCounter", "count_video", "predict_tta", "object_scores", "predict_tiled", "tile_grid", "tile_weights", "refine_probs", "bilateral_tables", "EdgeRefiner", "Trainer", "E2ETrainer", "FlatAdam", "StepLR", "CosineAnnealingLR", "ReduceLROnPlateau", "trainer_from_config", "scheduler_from_config", "adam_state_dict", "allreduce_mean_", "load_config", "get_config_recursively", "build_from_config", "build", "lib"]
+           "allreduce_eval_state", "clean_masks", "connected_components", "border_distances", "border_weights", "ObjectTable", "yield_estimation_metrics", "YieldEvaluator", "evaluate_yield", "object_shapes", "ObjectShapes", "object_overlaps", "OverlapTable", "match_masks", "panoptic_totals", "instance_metrics", "object_detection_mAP", "InstanceEvaluator", "evaluate_instances", "encode_masks", "runs_from_coco", "labels_from_runs", "rle_to_string", "rle_from_string", "RunTable", "object_outlines", "OutlineTable", "rasterize_polygons", "objects_from_annotations", "boundary_tables", "BoundaryTables", "boundary_metrics", "BoundaryEvaluator", "evaluate_boundaries", "frame_shifts", "link_objects", "track_ids", "VideoCounter", "count_video", "predict_tta", "object_scores", "predict_tiled", "tile_grid", "tile_weights", "refine_probs", "bilateral_tables", "EdgeRefiner", "Trainer", "E2ETrainer", "FlatAdam", "StepLR", "CosineAnnealingLR", "ReduceLROnPlateau", "trainer_from_config", "scheduler_from_config", "adam_state_dict", "allreduce_mean_", "load_config", "get_config_recursively", "build_from_config", "build", "lib"]

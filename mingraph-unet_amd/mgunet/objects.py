@@ -35,12 +35,15 @@ class ObjectTable:
     bbox: torch.Tensor
     sums: torch.Tensor
 
-    def to_dicts(self, scores=None, shapes=None) -> list:
+    def to_dicts(self, scores=None, shapes=None, runs=None, outlines=None) -> list:
         """The reference's per-image object lists: [[{'bbox': [xmin, ymin, xmax, ymax], 'class_id': int}, ...], ...].  With scores
         (one float per object in row order, e.g. mgunet.object_scores), every dict also carries 'confidence': float, the key
         yield_estimation_metrics sorts predictions by.  With shapes (mgunet.object_shapes of this table), every dict also carries
         'ellipse': {'center': [x, y], 'axes': [a, b], 'angle': radians, 'fill': f} and 'shape_term': float; both are None for an
-        object that was not analysed (shapes.status != 0)."""
+        object that was not analysed (shapes.status != 0).  With runs (mgunet.encode_masks of this table), every dict also carries
+        'segmentation': COCO's compressed RLE {'size': [H, W], 'counts': str}; with outlines (mgunet.object_outlines of this table),
+        'segmentation' is COCO's polygon form, a list of flat [x0, y0, x1, y1, ...] outer loops (holes are not expressible in it).  With
+        both given, runs wins."""
         off = self.offsets.cpu().tolist()
         bbox, cls = self.bbox.cpu().tolist(), self.class_id.cpu().tolist()
         rows = [{"bbox": bbox[i], "class_id": cls[i]} for i in range(len(cls))]
@@ -59,6 +62,13 @@ class ObjectTable:
                 ok = st[i] == 0
                 d["ellipse"] = {"center": cen[i], "axes": axes[i], "angle": ang[i], "fill": fill[i]} if ok else None
                 d["shape_term"] = term[i] if ok else None
+        seg = runs if runs is not None else outlines
+        if seg is not None:
+            flat = [s for per in seg.to_coco() for s in per]
+            if len(flat) != len(cls):
+                raise ValueError(f"segmentations of {len(flat)} objects for {len(cls)} objects")
+            for d, s in zip(rows, flat):
+                d["segmentation"] = s
         return [rows[off[b]:off[b + 1]] for b in range(len(off) - 1)]
 
     def masks(self) -> list:
