@@ -965,6 +965,43 @@ int mgu_augment_luma_tile(void);
 /* The luma pass alone: sums_dev[b] = S of image b (DEVICE int64 (B), cleared by this call's fill), as mgu_augment_affine_color forms it;
  * the mean luma of the definition is m = (S + n/2) / n. */
 int mgu_augment_luma_sums(mgu_ctx* ctx, const uint8_t* img_u8, int B, int Hs, int Ws, int bgr, int64_t* sums_dev, void* hip_stream);
+/* ---- elastic deformation in the scale / crop / colour pass (csrc/augment_elastic.hip) ---------------------------------------------------
+ * Random elastic deformation (Ronneberger et al., MICCAI 2015, 3.1: displacement vectors on a coarse grid, interpolated to every pixel)
+ * as one more term of the source coordinate of mgu_augment_affine_color: the image is still resampled once.  The reference has no such
+ * stage.  THIS BUILD'S DEFINITION, integers only; `>>` is the arithmetic shift (floor), `/` the integer division of non-negative values.
+ * Control grid.  Per image gh x gw nodes, 4 <= gh, gw <= 32; a node holds a displacement (cx, cy), int32 in 16.16 SOURCE-pixel units,
+ *   |c| <= 2^26 (mgunet.preprocess.elastic_control refuses more).  ctrl_dev: DEVICE int32 (B, 2, gh, gw), plane 0 x, plane 1 y, nodes
+ *   row-major.
+ * Lattice coordinate of output pixel (x, y) of the W x H result:
+ *     su = ((gw - 3) << 16) / W      u = x su + (su >> 1)  (int64)      i = u >> 16 in [0, gw - 4]      t = (u >> 8) & 255
+ *   (floored, not rounded: (W-1) su + (su >> 1) < W su <= (gw - 3) 65536, so the last pixel stays below cell gw - 3); sv, v, j, s likewise
+ *   from gh, H and y.
+ * Weights.  The uniform cubic B-spline as a Q14 table Wq[t][0..3], t = 0..255, from integers: T = 256, D = 6 T^3,
+ *     n0 = (T - t)^3     n1 = 3 t^3 - 6 T t^2 + 4 T^3     n2 = -3 t^3 + 3 T t^2 + 3 T^2 t + T^3     n3 = t^3        (sum D)
+ *     w_k = (2 * 16384 n_k + D) / (2 D)
+ *   and the larger of w1, w2 (w1 on a tie) takes the remainder, so that every row sums to 16384 exactly.  Wq[0] = (2731, 10922, 2731, 0),
+ *   Wq[128] = (341, 7851, 7851, 341).  The library forms the table itself (mgunet.preprocess.bspline_weights_q14 is the same table).
+ * Field.  Per plane  acc = sum_{b=0..3} sum_{a=0..3} Wq[s][b] Wq[t][a] c[j+b][i+a]  in int64 (|acc| < 2^54; exact, so the order of
+ *   summation is free and nothing is rounded between the two passes), D = (acc + 2^27) >> 28.  A constant control field gives D = c
+ *   exactly, zero gives zero; |D| <= 2^26.
+ * Coordinates.  sx = a2 + y a1 + x a0 + Dx     sy = a5 + y a4 + x a3 + Dy   (int64).  From here on everything is the definition of
+ *   mgu_augment_affine_color word for word: bilinear image taps with 8-bit fractions and fill_rgb, nearest mask with mask_fill and the
+ *   class clip, the Q12 colour matrix and the mean luma over the whole source image, ToTensor + Normalize, arbitrary output strides.
+ * Instance labels (optional).  labels_i32 int32 (B, Hs, Ws) -> labels_out int32 (B, H, W), both contiguous: nearest, source pixel
+ *   ((sx + 32768) >> 16, (sy + 32768) >> 16), label_fill outside the source; values are never clipped.
+ * mgu_augment_elastic_color takes the arguments of mgu_augment_affine_color, then the labels and the control grid.  ctrl_dev == NULL
+ * requires gh == gw == 0 and gives the affine result.  Launches as the affine entry: the luma fill and kernel when need_mean, then ONE
+ * kernel for the images, masks and labels of the whole batch; no host synchronisation.  The 16-byte stores need labels_out 16-byte
+ * aligned too.  MGU_ERR_INVALID, before any device work: the affine entry's conditions; gh or gw outside [4, 32] when ctrl_dev is set (not
+ * both 0 when it is not); labels_i32 and labels_out not both set or both null. */
+int mgu_augment_elastic_color(mgu_ctx* ctx, const uint8_t* img_u8, int B, int Hs, int Ws, int bgr, const uint8_t* mask_u8, int num_classes,
+                              float* out, int H, int W, const int64_t* out_strides, const float* mean3, const float* std3,
+                              const uint8_t* fill_rgb, int64_t* mask_out, int64_t mask_fill, const int32_t* params_dev, int need_mean,
+                              const int32_t* labels_i32, int32_t* labels_out, int32_t label_fill, const int32_t* ctrl_dev, int gh, int gw,
+                              void* hip_stream);
+/* The field alone: field_out DEVICE int32 (B, 2, H, W), plane 0 Dx, plane 1 Dy of every pixel of the W x H result, one launch.
+ * MGU_ERR_INVALID: a null pointer; B, H, W < 1; a side above 8192; gh or gw outside [4, 32]; B * tiles >= 2^31. */
+int mgu_elastic_field(mgu_ctx* ctx, const int32_t* ctrl_dev, int B, int gh, int gw, int H, int W, int32_t* field_out, void* hip_stream);
 /* EdgeDetector.sobel_edges (preprocessing/graph_feature_processing/edge_detection.py:14-44), kernel size 3: RGB -> grey (15-bit fixed
  * point), Sobel x / y with reflect-101 borders, magnitude / max * 255 in double, truncated to uint8.  rgb (H,W,3) -> out (H,W). */
 int mgu_sobel_edges_u8(mgu_ctx* ctx, const uint8_t* rgb_dev, int H, int W, uint8_t* out_dev, void* hip_stream);

@@ -11,21 +11,11 @@
 // byte loads per pixel), not their bytes: aff_load_run.  NOTES.md ("Affine + colour augmentation") has the timings.
 #include <algorithm>
 
-#include "ctx.h"
+#include "augment_affine.h"
 
 namespace mgu {
 
-constexpr int AFF_MAX_SIDE = 8192;
-constexpr int AFF_XV = 4;                 // consecutive output x per thread (one 16-byte store per channel on the vector path)
-constexpr int AFF_TX = 32, AFF_TY = 32;   // workgroup tile: 8 threads x 4 pixels across, 32 rows (256 threads); see augment.hip
 constexpr int AFF_LUMA_TILE = 8192;       // source pixels per workgroup of the luma kernel: 24576 bytes = 6 x 16 bytes per thread
-
-struct AffStrides {
-  int64_t b, c, h, w;
-};
-struct AffNorm {
-  float m0, m1, m2, s0, s1, s2;
-};
 
 // Bytes [3 T tile, 3 T (tile + 1)) of image b (clipped to the image): the 16-byte chunks at 16-byte aligned ADDRESSES that lie wholly
 // inside that range, several loads in flight per thread, and the fewer than 16 bytes in front of the first and behind the last of
@@ -68,39 +58,6 @@ __global__ __launch_bounds__(256) void affine_luma_kernel(const uint8_t* __restr
     __syncthreads();
     if (threadIdx.x == 0) atomicAdd(&sums[b], (unsigned long long)sh[0] + sh[1] + sh[2] + sh[3]);
     __syncthreads();
-  }
-}
-
-// m = (S + n / 2) / n for S <= 65280 n, n <= 2^26: the double quotient is within one of the integer quotient, then corrected exactly
-__device__ __forceinline__ int aff_mean_q8(unsigned long long S, int n) {
-  const long long a = (long long)S + n / 2;
-  long long q = (long long)((double)a / (double)n);
-  const long long r = a - q * n;
-  if (r < 0) --q;
-  else if (r >= n) ++q;
-  return (int)q;
-}
-
-struct AffWords {
-  unsigned a, b, c;
-};
-// The six bytes at p (taps (ix, iy) and (ix + 1, iy), three channels each; in0 / in1: the tap lies inside the image) -> r0 = bytes 0..3,
-// r1 = bytes 4, 5.  One 12-byte load at the 4-byte aligned address below p where that window lies inside the batch [lo, hi) -- bytes of
-// a tap outside the image are then whatever follows in the batch, and the caller replaces them by the fill.  Where the window leaves the
-// batch (its first and last bytes) or no tap lies inside, the load goes to `safe` (12 readable bytes: the parameter table) and the taps
-// inside are read byte by byte.  Twelve byte gathers per pixel kept the kernel at the rate of the address unit; two wide ones do not.
-__device__ __forceinline__ void aff_load_run(const uint8_t* p, const uint8_t* lo, const uint8_t* hi, const uint8_t* safe, bool in0, bool in1,
-                                             unsigned& r0, unsigned& r1) {
-  const unsigned s = (unsigned)((uintptr_t)p & 3);
-  const uint8_t* q = p - s;
-  const bool any = in0 || in1, wide = any && q >= lo && q + 12 <= hi;
-  const AffWords w = *(const AffWords*)(wide ? q : safe);
-  r0 = __builtin_amdgcn_alignbyte(w.b, w.a, s);
-  r1 = __builtin_amdgcn_alignbyte(w.c, w.b, s);
-  if (__builtin_expect(any && !wide, 0)) {
-    r0 = r1 = 0;
-    if (in0) r0 = (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16);
-    if (in1) r0 |= (unsigned)p[3] << 24, r1 = (unsigned)p[4] | ((unsigned)p[5] << 8);
   }
 }
 

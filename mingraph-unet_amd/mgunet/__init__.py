@@ -6,7 +6,7 @@ from .engine import CosineAnnealingLR, E2ETrainer, FlatAdam, MinGraphUNet, MinGr
 from .gat import GATNetwork, GraphAttentionLayer, MultiHeadGATLayer, seed_dropout  # noqa: F401
 from .losses import (EllipticalShapeLoss, FeatureConsistencyLoss, TVLoss, class_weights, dice_loss, lovasz_softmax,  # noqa: F401
                      pixel_cross_entropy)
-from .preprocess import CLAHE, EdgeDetector, GaussianSmoother, HistogramEqualizer, ImagePreprocessor, RandomAffineColor, RandomFlipRotate, affine_fixed, color_matrix_q12, draw_flip_rotate, gaussian_kernel_q8, luma_sums, patch_clahe_features_u8, patch_features_u8, patch_smooth_features_u8, pil_rotation_fixed, postprocess_segmentation  # noqa: F401
+from .preprocess import CLAHE, EdgeDetector, GaussianSmoother, HistogramEqualizer, ImagePreprocessor, RandomAffineColor, RandomElasticAffineColor, RandomFlipRotate, affine_fixed, bspline_weights_q14, color_matrix_q12, elastic_control, elastic_field, draw_flip_rotate, gaussian_kernel_q8, luma_sums, patch_clahe_features_u8, patch_features_u8, patch_smooth_features_u8, pil_rotation_fixed, postprocess_segmentation  # noqa: F401
 from .metrics import SegmentationEvaluator, allreduce_eval_state, evaluate_segmentation, metrics_from_confusion, segmentation_metrics  # noqa: F401
 from .objects import (ObjectShapes, ObjectTable, YieldEvaluator, clean_masks, connected_components, distance_transform,  # noqa: F401
                       evaluate_yield, object_shapes, split_objects, yield_estimation_metrics)
@@ -29,7 +29,7 @@ from .region import FeatureFusion, region_edge_index, region_fuse, region_mean_p
 from .unet import ConvBlock, DecoderBlock, UNet, UNetDecoder, UNetEncoder  # noqa: F401
 from ._lib import build, lib  # noqa: F401
 
-__all__ = ["SuperpixelGraph", "connect_regions", "lab_tables", "region_adjacency", "region_features", "region_pool", "slic_labels", "superpixel_graph", "TVLoss", "dice_loss", "lovasz_softmax", "pixel_cross_entropy", "class_weights", "FeatureConsistencyLoss", "EllipticalShapeLoss", "ImagePreprocessor", "RandomFlipRotate", "RandomAffineColor", "affine_fixed", "color_matrix_q12", "luma_sums", "draw_flip_rotate", "pil_rotation_fixed", "EdgeDetector", "HistogramEqualizer", "GaussianSmoother", "gaussian_kernel_q8", "patch_smooth_features_u8", "CLAHE", "patch_clahe_features_u8",
+__all__ = ["SuperpixelGraph", "connect_regions", "lab_tables", "region_adjacency", "region_features", "region_pool", "slic_labels", "superpixel_graph", "TVLoss", "dice_loss", "lovasz_softmax", "pixel_cross_entropy", "class_weights", "FeatureConsistencyLoss", "EllipticalShapeLoss", "ImagePreprocessor", "RandomFlipRotate", "RandomAffineColor", "RandomElasticAffineColor", "bspline_weights_q14", "elastic_control", "elastic_field", "affine_fixed", "color_matrix_q12", "luma_sums", "draw_flip_rotate", "pil_rotation_fixed", "EdgeDetector", "HistogramEqualizer", "GaussianSmoother", "gaussian_kernel_q8", "patch_smooth_features_u8", "CLAHE", "patch_clahe_features_u8",
            "patch_features_u8", "patch_node_features", "patch_labels", "postprocess_segmentation", "DetectionHead", "FeatureFusion", "region_stage", "region_mean_pool", "region_fuse", "region_edge_index", "MinCutRefinement", "PatchSegmentPredictor", "graph_cut", "cut_capacities", "cut_energy", "GraphCut", "graph_cut_multi", "label_costs", "cut_energy_multi", "MultiCut", "UNet", "UNetEncoder", "UNetDecoder", "ConvBlock", "DecoderBlock", "GATNetwork", "MultiHeadGATLayer",
            "GraphAttentionLayer", "PatchGraphConstructor", "MinGraphUNet", "MinGraphUNetE2E", "segment_batch", "argmax_classes",
            "gat_forward_csr", "shard_batch", "segmentation_metrics", "metrics_from_confusion", "SegmentationEvaluator", "evaluate_segmentation",

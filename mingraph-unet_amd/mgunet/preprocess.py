@@ -17,7 +17,9 @@ ImagePreprocessor(apply_augmentation=True) reproduces the reference's RandomHori
 host makes torchvision's two draws from torch's generator (draw_flip_rotate) and the device applies PIL's fixed-point NEAREST rotation
 (pil_rotation_fixed) inside the ToTensor + Normalize pass.  preprocess_pair applies one draw to an image AND its mask (the reference
 augments only the image), and RandomFlipRotate augments a whole device batch in one launch.  RandomAffineColor is this build's
-own stage (the reference has none): scale / crop / rotation with bilinear resampling and a colour jitter, from the uint8 batch."""
+own stage (the reference has none): scale / crop / rotation with bilinear resampling and a colour jitter, from the uint8 batch;
+RandomElasticAffineColor adds the U-Net paper's elastic deformation (a cubic B-spline of coarse random displacements) to the same pass
+and carries an int32 instance map along."""
 from __future__ import annotations
 
 import ctypes as C
@@ -389,6 +391,158 @@ class RandomAffineColor:
         _lib.call("mgu_augment_affine_color", dev, images_u8, B, Hs, Ws, int(self.bgr), masks, self.num_classes, out, H, W, so, mean, std, fill,
                   mout, self.mask_fill, params, need_mean)
         return (out, mout) if masks is not None else out
+
+
+ELASTIC_NODES = (4, 32)          # control nodes a side of mgu_augment_elastic_color
+ELASTIC_CTRL_LIMIT = 1 << 26     # |c|, 16.16 source pixels
+
+
+def bspline_weights_q14() -> np.ndarray:
+    """The (256, 4) int32 weight table Wq of mgu_augment_elastic_color (include/mgunet.h, "elastic deformation"): the uniform cubic
+    B-spline at t / 256 in Q14 from integers alone, every row summing to 16384 (the larger of w1, w2 takes the remainder, w1 on a tie).
+    The library forms the same table itself."""
+    T = 256
+    D = 6 * T ** 3
+    rows = []
+    for t in range(T):
+        n = ((T - t) ** 3, 3 * t ** 3 - 6 * T * t * t + 4 * T ** 3, -3 * t ** 3 + 3 * T * t * t + 3 * T * T * t + T ** 3, t ** 3)
+        w = [(2 * 16384 * v + D) // (2 * D) for v in n]
+        w[2 if w[2] > w[1] else 1] += 16384 - sum(w)
+        rows.append(w)
+    return np.asarray(rows, np.int32)
+
+
+def elastic_control(normals, sigma: float, row, nodes) -> torch.Tensor:
+    """The control nodes of one image for mgu_augment_elastic_color -> int32 (2, gh, gw) host tensor (plane 0 x, plane 1 y), 16.16
+    SOURCE-pixel units.  normals: float64 (2, gh, gw) standard normal draws, each clipped to [-3, 3]; the vector in OUTPUT pixels is
+    V = FIX16(sigma n), FIX16(v) = floor(v 65536 + 0.5).  It is carried into source units by the linear part a0, a1, a3, a4 of the image's
+    table row in Python integers (no libm): cx = (a0 VX + a1 VY + 32768) >> 16, cy = (a3 VX + a4 VY + 32768) >> 16, so the warp turns
+    and scales with the crop.  |c| > 2^26 raises."""
+    gh, gw = int(nodes[0]), int(nodes[1])
+    if not (ELASTIC_NODES[0] <= gh <= ELASTIC_NODES[1] and ELASTIC_NODES[0] <= gw <= ELASTIC_NODES[1]):
+        raise ValueError(f"elastic_control: nodes {gh} x {gw} must be in [{ELASTIC_NODES[0]}, {ELASTIC_NODES[1]}] a side")
+    n = np.asarray(normals, np.float64)
+    if n.shape != (2, gh, gw) or not np.isfinite(n).all():
+        raise ValueError(f"elastic_control: normals must be finite float64 (2, {gh}, {gw})")
+    a0, a1, _a2, a3, a4 = (int(v) for v in row[:5])
+    sg = float(sigma)
+    vx = [_fix(sg * min(max(v, -3.0), 3.0), 16) for v in n[0].reshape(-1).tolist()]
+    vy = [_fix(sg * min(max(v, -3.0), 3.0), 16) for v in n[1].reshape(-1).tolist()]
+    cx = [(a0 * x + a1 * y + 32768) >> 16 for x, y in zip(vx, vy)]
+    cy = [(a3 * x + a4 * y + 32768) >> 16 for x, y in zip(vx, vy)]
+    if max(abs(v) for v in cx + cy) > ELASTIC_CTRL_LIMIT:
+        raise ValueError(f"elastic_control: a control displacement beyond 2^26 (1024 source pixels): sigma {sg} is too large for this crop")
+    return torch.tensor([cx, cy], dtype=torch.int32).reshape(2, gh, gw)
+
+
+def elastic_field(ctrl: torch.Tensor, out_hw) -> torch.Tensor:
+    """The displacement field of mgu_augment_elastic_color alone: ctrl int32 (B, 2, gh, gw) on the device -> int32 (B, 2, H, W), plane 0
+    Dx, plane 1 Dy in 16.16 source pixels (mgu_elastic_field, one launch)."""
+    if not isinstance(ctrl, torch.Tensor) or ctrl.dtype != torch.int32 or ctrl.dim() != 4 or ctrl.shape[1] != 2:
+        raise TypeError("ctrl must be a (B, 2, gh, gw) int32 tensor")
+    _lib.require_hip(ctrl, "mgunet.elastic_field")
+    ctrl = ctrl.contiguous()
+    B, _two, gh, gw = ctrl.shape
+    H, W = int(out_hw[0]), int(out_hw[1])
+    out = torch.empty((B, 2, max(H, 0), max(W, 0)), device=ctrl.device, dtype=torch.int32)
+    _lib.call("mgu_elastic_field", ctrl.device, ctrl, B, gh, gw, H, W, out)
+    return out
+
+
+class RandomElasticAffineColor(RandomAffineColor):
+    """RandomAffineColor with a random elastic deformation folded into the same pass (Ronneberger et al. 2015, 3.1: displacement vectors on
+    a coarse grid, sigma = 10 pixels, interpolated to every pixel), and an optional int32 instance map sampled with the same
+    coordinates for Trainer.train_step(images, masks, instances=).  include/mgunet.h, mgu_augment_elastic_color: the displacement is one
+    more term of the source coordinate, so the image is still resampled once and the launches are the parent's; integers only, bitwise
+    equal to tests/augment_elastic_oracle.py.  nodes: (gh, gw) control nodes, 4..32 a side; sigma: standard deviation of a node's
+    displacement in OUTPUT pixels (normals clipped to +-3); label_fill: the instance id outside the source (0: background).
+    Draws, part of the interface: per image, in batch order, the parent's torch.rand(10, float64) and then -- sigma != 0 only --
+    torch.randn(2 gh gw, float64) reshaped (2, gh, gw)."""
+
+    def __init__(self, size, nodes=(6, 6), sigma=10.0, label_fill=0, **kw):
+        super().__init__(size, **kw)
+        self.nodes = (int(nodes[0]), int(nodes[1]))
+        if not all(ELASTIC_NODES[0] <= v <= ELASTIC_NODES[1] for v in self.nodes):
+            raise ValueError(f"nodes must be in [{ELASTIC_NODES[0]}, {ELASTIC_NODES[1]}] a side")
+        self.sigma, self.label_fill = float(sigma), int(label_fill)
+        if not (self.sigma >= 0.0 and math.isfinite(self.sigma)):
+            raise ValueError("sigma must be non-negative")
+        if not -2 ** 31 <= self.label_fill < 2 ** 31:
+            raise ValueError("label_fill must fit int32")
+
+    def draw(self, B: int, src_hw, generator=None):
+        """-> (params (B, 16) int32, ctrl (B, 2, gh, gw) int32), host tensors; sigma == 0 draws no normals and gives zero nodes."""
+        gh, gw = self.nodes
+        rows, ctrl = [], []
+        for _ in range(int(B)):
+            rows.append(self.row(torch.rand(10, dtype=torch.float64, generator=generator).tolist(), src_hw))
+            if self.sigma != 0.0:
+                n = torch.randn(2 * gh * gw, dtype=torch.float64, generator=generator).reshape(2, gh, gw)
+                ctrl.append(elastic_control(n.numpy(), self.sigma, rows[-1], self.nodes))
+            else:
+                ctrl.append(torch.zeros((2, gh, gw), dtype=torch.int32))
+        return torch.tensor(rows, dtype=torch.int32).reshape(int(B), 16), torch.stack(ctrl).reshape(int(B), 2, gh, gw)
+
+    def __call__(self, images_u8: torch.Tensor, masks: torch.Tensor = None, labels: torch.Tensor = None, generator=None,
+                 out: torch.Tensor = None, params: torch.Tensor = None, ctrl: torch.Tensor = None):
+        """images_u8, masks, out, params as RandomAffineColor; labels: optional (B, Hs, Ws) int32 instance map -> int32 (B, H, W).
+        Returns the images and, in this order, whichever of masks and labels were given.  ctrl: explicit (B, 2, gh, gw) int32 nodes
+        (any 4..32 a side).  With neither params nor ctrl both come from one draw; explicit params without ctrl are applied without a
+        displacement.  sigma == 0 without ctrl and labels is the parent's call (mgu_augment_affine_color)."""
+        if ctrl is None and labels is None and (self.sigma == 0.0 or params is not None):
+            if params is None and isinstance(images_u8, torch.Tensor) and images_u8.dim() == 4:      # the parent's draws, not this class's pair
+                params = RandomAffineColor.draw(self, images_u8.shape[0], images_u8.shape[1:3], generator)
+            return super().__call__(images_u8, masks, generator=generator, out=out, params=params)
+        if not isinstance(images_u8, torch.Tensor) or images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[3] != 3:
+            raise TypeError("images_u8 must be a (B, Hs, Ws, 3) uint8 tensor")
+        _lib.require_hip(images_u8, "mgunet.RandomElasticAffineColor")
+        dev = images_u8.device
+        images_u8 = images_u8.contiguous()
+        B, Hs, Ws, _c = images_u8.shape
+        H, W = self.size
+        if masks is not None:
+            if masks.dtype != torch.uint8 or masks.device != dev or tuple(masks.shape) != (B, Hs, Ws):
+                raise ValueError("masks must be a (B, Hs, Ws) uint8 tensor on the images' device")
+            masks = masks.contiguous()
+        if labels is not None:
+            if labels.dtype != torch.int32 or labels.device != dev or tuple(labels.shape) != (B, Hs, Ws):
+                raise ValueError("labels must be a (B, Hs, Ws) int32 tensor on the images' device")
+            labels = labels.contiguous()
+        if out is None:
+            out = torch.empty((B, 3, H, W), device=dev, dtype=torch.float32)
+        elif tuple(out.shape) != (B, 3, H, W) or out.dtype != torch.float32 or out.device != dev:
+            raise ValueError("`out` must be a float32 (B, 3, H, W) tensor on the images' device")
+        if params is None and ctrl is None:
+            if self.sigma == 0.0:
+                params = self.draw(B, (Hs, Ws), generator)[0]
+            else:
+                params, ctrl = self.draw(B, (Hs, Ws), generator)
+        elif params is None:
+            params = RandomAffineColor.draw(self, B, (Hs, Ws), generator)
+        if tuple(params.shape) != (B, 16) or params.dtype != torch.int32:
+            raise ValueError("params must be a (B, 16) int32 table")
+        gh = gw = 0
+        if ctrl is not None:
+            if ctrl.dtype != torch.int32 or ctrl.dim() != 4 or tuple(ctrl.shape[:2]) != (B, 2):
+                raise ValueError("ctrl must be a (B, 2, gh, gw) int32 tensor")
+            gh, gw = int(ctrl.shape[2]), int(ctrl.shape[3])
+            if not all(ELASTIC_NODES[0] <= v <= ELASTIC_NODES[1] for v in (gh, gw)):
+                raise ValueError(f"ctrl: {gh} x {gw} control nodes, both must be in [{ELASTIC_NODES[0]}, {ELASTIC_NODES[1]}]")
+            if not ctrl.is_cuda and ctrl.numel() and int(ctrl.abs().max()) > ELASTIC_CTRL_LIMIT:
+                raise ValueError("ctrl: |c| must stay within 2^26")
+            ctrl = ctrl.to(dev).contiguous()
+        need_mean = 1 if params.is_cuda else int(bool((params[:, 15] != 0).any()))
+        if not params.is_cuda and int(params[:, 6:].abs().max()) > COLOR_Q12_LIMIT:
+            raise ValueError("params: |A| and |k| must stay within 2^15")
+        params = params.to(dev).contiguous()
+        mout = torch.empty((B, H, W), device=dev, dtype=torch.int64) if masks is not None else None
+        lout = torch.empty((B, H, W), device=dev, dtype=torch.int32) if labels is not None else None
+        so = (C.c_int64 * 4)(*out.stride())
+        mean, std, fill = (C.c_float * 3)(*self.mean), (C.c_float * 3)(*self.std), (C.c_uint8 * 3)(*self.fill)
+        _lib.call("mgu_augment_elastic_color", dev, images_u8, B, Hs, Ws, int(self.bgr), masks, self.num_classes, out, H, W, so, mean, std, fill,
+                  mout, self.mask_fill, params, need_mean, labels, lout, self.label_fill, ctrl, gh, gw)
+        res = [out] + [t for t in (mout, lout) if t is not None]
+        return tuple(res) if len(res) > 1 else out
 
 
 def _rgb_op(fn_name, image_array_rgb, out_channels):
